@@ -18,12 +18,18 @@ ITSELF (re-executing under `python -m torch.distributed.run --nnodes=1 --nproc-p
 running inside a process group; launched by torch.distributed.run it checks that the world it finds is the `--gpus` it
 was given.  `n_gpus` is the process group's size and `rccl_ranks` the sum of an all-reduce of ones over it.
 `--mode shard` is the strong-scaling leg (ONE 16384x16384 frame per step, LF groups sharded over the ranks, one blob
-gather per frame to the assembling rank).  The frame-mode line carries the other workloads as legs: on one GPU they run
-in-process behind the timed loop; at N > 1 the legs that need every rank (shard_16k, batch_4k) are started by rank 0 as jobs of
-their own once the frame loop's process group is gone (`child_job`: `bench.py --gpus N --mode ...`, 300 s, killed as a whole on
-overrun), so that a leg that fails or hangs cannot take the headline with it.
+gather per frame to the assembling rank).
 
-Prints ONE JSON line on rank 0.  `value` is whole-job Mpixel/s over all GPUs.
+A plain frame-mode run does only what the headline needs: set up, warm up, time exactly `--steps` frames, and print the
+line.  `--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (inputs are seeded: the same arguments code
+the same pictures, so two builds can be compared output for output).  `--full` adds everything else: three longer windows and
+their spread, per-kernel and roofline figures, single-frame latency, the byte-equality checks, the drop-in API, the CPU
+baseline and the other workloads as legs: on one GPU they run in-process behind the timed loop; at N > 1 the legs that need
+every rank (shard_16k, batch_4k) are started by rank 0 as jobs of their own once the frame loop's process group is gone
+(`child_job`: `bench.py --gpus N --mode ...`, 300 s, killed as a whole on overrun), so that a leg that fails or hangs cannot
+take the headline with it.
+
+Prints ONE JSON line on rank 0.  `value` is whole-job Mpixel/s over all GPUs; `ms_per_step` the milliseconds of one timed frame.
 """
 import argparse
 import hashlib
@@ -64,7 +70,14 @@ def parse():
                     help="start the ranks exactly as a real run does, form the process group (gloo where there is no GPU), all-reduce a "
                          "one per rank, print {n_gpus, rccl_ranks} on rank 0 and stop: proves `--gpus N` reaches N ranks")
     ap.add_argument("--steps", type=int, default=120,
-                    help="frames in the timed interval (the pipeline is primed before it and kept full behind it)")
+                    help="frames in the timed interval, exactly (the pipeline is primed before it and kept full behind it)")
+    ap.add_argument("--full", action="store_true",
+                    help="frame mode: after the headline interval also run everything else the line used to carry: three longer "
+                         "windows and their spread, per-kernel and roofline figures, single-frame latency, the byte-equality checks, "
+                         "the other workloads as legs, the drop-in API and the CPU baseline (the --no-* options trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="frame mode: after the timed steps write what the last one computed (the frame's packed HF sections, "
+                         "section sizes, coded LF streams) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--size", type=int, default=8192, help="frame edge in pixels (per GPU)")
     ap.add_argument("--depth", type=int, default=16, choices=(8, 16))
@@ -107,7 +120,12 @@ def parse():
     ap.add_argument("--no-api", action="store_true")
     ap.add_argument("--no-bind", action="store_true",
                     help="leave the process where the scheduler put it instead of binding it to the CPUs of the GPU's NUMA node")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "frame":
+        ap.error("--dump-outputs: frame mode only")
+    return args
 
 
 def launch_ranks(args, argv=None):
@@ -910,6 +928,52 @@ def shard_inprocess_leg(ndev, size=16384, steps=40):
     return out
 
 
+DUMP_BUDGET = 64 << 20  # bytes of .npy files --dump-outputs may write in all
+DUMP_SEED = 20240917    # fixed: the sample positions depend on the stream's length only
+
+
+def dump_sample(data, max_elems):
+    """The bytes as float32: all of them when they fit, else one seeded position in each of `max_elems` equal bins."""
+    import numpy as np
+
+    n = len(data)
+    if n <= max_elems:
+        return data.astype(np.float32)
+    edges = np.arange(max_elems + 1, dtype=np.int64) * n // max_elems
+    rng = np.random.default_rng(DUMP_SEED)
+    pos = edges[:-1] + (rng.random(max_elems) * (edges[1:] - edges[:-1])).astype(np.int64)
+    return data[pos].astype(np.float32)
+
+
+def dump_outputs(outdir, ctx, frames, f, lfg):
+    """--dump-outputs: what a caller of the timed path receives for frame `f` of the launch group of `frames` frames that
+    `ctx` coded last: the packed HF group sections and their sizes, the coded LF streams, their sizes and code lengths.
+    Byte streams are written one float32 per byte (a seeded sample where the budget does not hold them all).  -> file names"""
+    import numpy as np
+
+    ctx.sync()
+    pay = np.frombuffer(ctx.read_payload(), np.uint8)
+    bits = np.stack([ctx.read_sections(s)[0] for s in range(frames * lfg)]).reshape(frames, lfg, -1)
+    sizes = ((bits + 7) // 8).sum(axis=(1, 2))
+    off = int(sizes[:f].sum())
+    hf = pay[off:off + int(sizes[f])]
+    lfr = ctx.read_lf_streams(lfg * frames)[f * lfg:(f + 1) * lfg]
+    lfp = ctx.read_lf_payload()
+    lf = np.concatenate([lfp[int(r["offset"]):int(r["offset"]) + (int(r["bit_count"]) + 7) // 8] for r in lfr])
+    arrays = {"hf_section_bits": bits[f].astype(np.float64),
+              "lf_stream_bits": lfr["bit_count"].astype(np.float64),
+              "lf_code_lengths": lfr["lengths"].astype(np.float32)}
+    left = DUMP_BUDGET - sum(a.nbytes for a in arrays.values()) - 4096 * 8  # (.npy headers)
+    streams = sorted((("lf_streams", lf), ("hf_sections", hf)), key=lambda s: len(s[1]))
+    for i, (name, data) in enumerate(streams):
+        arrays[name] = dump_sample(data, left // (len(streams) - i) // 4)
+        left -= arrays[name].nbytes
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return sorted(name + ".npy" for name in arrays)
+
+
 def main():
     args = parse()
     rc = launch_ranks(args)
@@ -1078,10 +1142,14 @@ def main():
     # sequence still sits between barrier + synchronize on both sides (`wall` below reports it).
     # Frames of the S streams complete in bursts, so an interval shorter than two periods of every stream
     # moves by several per cent with where it happens to start (round 2: 136-146 at --steps 20, 128-133 at 120 on the
-    # same box): at least 2 S frames are timed whatever --steps says, and the rate is reported per frame.
+    # same box).  The headline interval is exactly --steps frames all the same, the rate is reported per frame, and
+    # --full adds three longer windows (below) whose spread shows how far a short interval can be trusted.
     S = len(ctxs)
-    # at least eight periods of every stream per window (128 frames, ~65 ms), three windows: the contract line is the MEDIAN
-    # window, the spread is reported.  The event timers of hydamd_profile stay OFF in these windows (two event records per
+    N = args.steps                      # frames timed for the headline
+    NG = -(-N // FPL)                   # its launch groups; the last one codes the remaining N - (NG - 1) FPL frames
+    tail = N - (NG - 1) * FPL
+    # --full: at least eight periods of every stream per window (128 frames, ~65 ms), three windows: the MEDIAN window and
+    # the spread are reported.  The event timers of hydamd_profile stay OFF in these windows (two event records per
     # kernel lengthen every frame's stay in its stream: -4 % measured); the co-residency durations under `kernels` come from
     # a fourth, short, profiled window that is not part of the rate.
     K = max(args.steps, 8 * S * FPL)   # frames per window
@@ -1089,14 +1157,14 @@ def main():
     KG = K // FPL                       # launch groups per window
     WINDOWS = 3
 
-    def timed_run(K, step=step, windows=1, nprime=None):
+    def timed_run(K, step=step, windows=1, nprime=None, ncool=None):
         """`windows` consecutive windows of K launch groups each (FPL frames per group for the default `step`), timed by
         events, in ONE continuous run behind a priming phase.  The GPU's first ~150 ms under this all-VALU load run 10-15 %
         faster than what follows (clocks settle: the transform kernel alone, back to back on 32 streams, does 216-241
         Gpixel/s for two chunks of frames and 198-202 for the next seconds: profiles/r04_pipeline_bounds.txt), so the priming
         phase is 10 launch groups per stream (>= 0.2 s) and what is timed is the sustained rate."""
         nprime = 10 * S if nprime is None else nprime
-        ncool = S
+        ncool = S if ncool is None else ncool
 
         def mark(i):
             ev = torch.cuda.Event(enable_timing=True)
@@ -1124,10 +1192,11 @@ def main():
             dist.barrier()
         wall = time.perf_counter() - t0
         # all events on one clock: offsets from the first priming group's completion; a window boundary is the mean
-        # completion time of the S launch groups in front of it — boundaries exactly K groups apart
+        # completion time of the S launch groups in front of it — boundaries exactly K groups apart.  Every stream counts once at
+        # each boundary even when K < S (the streams complete at different phases of the cycle: fewer would bias the interval)
         base = evs[0]
         done = [base.elapsed_time(e) for e in evs]
-        w = min(S, K, nprime)
+        w = min(S, nprime)
         edge = [sum(done[nprime + j * K - w:nprime + j * K]) / w for j in range(windows + 1)]
         dts = [(edge[j + 1] - edge[j]) * 1e-3 for j in range(windows)]
         # every stream's own period inside the timed part (it completes one launch group per S group periods)
@@ -1138,32 +1207,88 @@ def main():
                 periods.append((mine[-1] - mine[0]) / (len(mine) - 1) / S / FPL)
         return dict(dt=sorted(dts)[windows // 2], dts=dts, wall=wall, frames=seq, periods=periods)
 
-    run = timed_run(KG, windows=WINDOWS)
-    if use_dist:  # every window's time is the slowest rank's
-        t = torch.tensor(run["dts"] + [run["wall"]], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        row = t.tolist()
-        run["dts"], run["wall"] = row[:-1], row[-1]
-        run["dt"] = sorted(run["dts"])[WINDOWS // 2]
-    dt, wall, total_frames = run["dt"], run["wall"], run["frames"] * FPL
-    window_rates = [round(world * W * H * K / x / 1e6, 1) for x in run["dts"]]
-    # the first 100 ms after idle, for the record: a short window right behind a short priming phase (what rounds 1-3 timed)
-    burst = timed_run(2 * S, nprime=2 * S)
-    for c in ctxs:
-        c.profile(True)
-    timed_run(2 * S, nprime=2 * S)
-    groups_profiled = FPL
+    # the headline: N frames in NG launch groups behind the priming phase.  S - 1 groups keep the pipeline full behind them,
+    # on every context but the one that took the last timed group: that context still holds the last step's results
+    nprime = 10 * S
+    last = nprime + NG - 1
 
-    # per-kernel durations from HIP events recorded on the kernels' own streams during the timed region
-    kern = {}
-    for c in ctxs:
-        for name, (ms, n) in c.profile_read().items():
-            a = kern.setdefault(name, [0.0, 0])
-            a[0] += ms
-            a[1] += n
-        c.profile(False)
-    payload_bytes = ctxs[0].payload_size() // FPL
-    symbols = sum(int(ctxs[0].read_symbol_counts(s).sum()) for s in range(lfg))
+    def step_headline(i):
+        if i == last and tail < FPL:
+            return ctxs[i % S].encode_image_tensor(pictures[i % S][0])
+        return step(i)
+
+    head = timed_run(NG, step_headline, ncool=S - 1)
+    if use_dist:  # the slowest rank's time
+        t = torch.tensor([head["dt"], head["wall"]], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        head["dt"], head["wall"] = t.tolist()
+    head_frames = head["frames"] * FPL - (FPL - tail)  # (every launch group of the run holds FPL frames but the last timed one)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, ctxs[last % S], tail, tail - 1, lfg)
+
+    config = {"workload": f"{W}x{H} RGB{args.depth} '{args.kind}' frame per GPU (BASELINE configs[2]); "
+                          "hot path device-resident RGB -> packed HF group sections "
+                          "(XYB, DCT, quantise, tokenise, ANS tables, rANS, pack)" +
+                          (f", {FPL} independent frames per launch group" if FPL > 1 else "") +
+                          (" + prefix-coded LF coefficient streams" if args.lf_coder == "on" else ""),
+              "lf_coder": "gpu, in-stream" if args.lf_coder == "on" else "off",
+              "groups": lfg * 64 if W % 2048 == 0 and H % 2048 == 0 else None, "lf_groups": lfg,
+              "streams": len(ctxs), "frames_per_launch_group": FPL, "rans_groups_per_workgroup": args.rans_waves, "parallelism": f"{world} x (one frame per GPU)" +
+                                                   (f", one RCCL gather of result blobs per {per} frames, root rotating over the ranks" if exchange else ", no collective (independent frames)")}
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "Mpixel/s encode (8K RGB, default q)",
+            "value": round(world * W * H * N / head["dt"] / 1e6, 1),
+            "unit": "Mpixel/s",
+            "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": N, "warmup": args.warmup,
+            "ms_per_step": round(head["dt"] / N * 1e3, 4),
+            "value_is": "the SUSTAINED rate: the `steps` timed frames of one continuous run behind ten launch groups per stream of priming",
+            "timing": {"method": "HIP events at the end of each frame's stream: completion of the last priming frames -> "
+                                 "completion of the last timed frames, pipeline primed before and kept full behind; "
+                                 "one continuous run: ten launch groups per stream of priming (the GPU's first 150 ms under this load run 10-15 % fast), "
+                                 "then exactly `steps` frames; no event timers inside the interval",
+                       "timed_frames": N, "timed_launch_groups": NG,
+                       "wall_ms_incl_fill_and_drain": round(head["wall"] * 1e3, 3), "frames_in_wall": head_frames,
+                       "Mpixel/s_wall": round(world * W * H * head_frames / head["wall"] / 1e6, 1)},
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "host_placement": placement or "unbound",
+            "config": config,
+            "hbm_read_roofline_Mpx_s": round(HBM_PEAK_GBS * 1e9 / (3 * args.depth // 8) / 1e6, 0),
+            "frac_of_hbm_read_roofline": round((W * H * N / head["dt"]) / (HBM_PEAK_GBS * 1e9 / (3 * args.depth // 8)), 5),
+        }
+        if dumped:
+            out["outputs"] = {"files": dumped, "of": f"the last timed step: frame {tail - 1} of the launch group context {last % S} coded last"}
+
+    if args.full:
+        run = timed_run(KG, windows=WINDOWS)
+        if use_dist:  # every window's time is the slowest rank's
+            t = torch.tensor(run["dts"] + [run["wall"]], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            row = t.tolist()
+            run["dts"], run["wall"] = row[:-1], row[-1]
+            run["dt"] = sorted(run["dts"])[WINDOWS // 2]
+        dt, wall, total_frames = run["dt"], run["wall"], run["frames"] * FPL
+        window_rates = [round(world * W * H * K / x / 1e6, 1) for x in run["dts"]]
+        # the first 100 ms after idle, for the record: a short window right behind a short priming phase (what rounds 1-3 timed)
+        burst = timed_run(2 * S, nprime=2 * S)
+        for c in ctxs:
+            c.profile(True)
+        timed_run(2 * S, nprime=2 * S)
+        groups_profiled = FPL
+
+        # per-kernel durations from HIP events recorded on the kernels' own streams during the timed region
+        kern = {}
+        for c in ctxs:
+            for name, (ms, n) in c.profile_read().items():
+                a = kern.setdefault(name, [0.0, 0])
+                a[0] += ms
+                a[1] += n
+            c.profile(False)
+        payload_bytes = ctxs[0].payload_size() // FPL
+        symbols = sum(int(ctxs[0].read_symbol_counts(s).sum()) for s in range(lfg))
 
     # What the timed contexts hold.  Every context still holds its last timed launch group — the very launch shape that was
     # timed (S in flight, FPL frames per group, lane-form entropy stage, in-stream LF coder): each frame's packed HF sections
@@ -1171,7 +1296,7 @@ def main():
     # exported and put together on the device (hydamd_assembler_*) into the FILE, whose MD5 is compared below with the
     # drop-in API's file and with the CPU reference's.
     timed_files = None
-    if rank == 0 and args.lf_coder == "on" and W * H > 65536:
+    if args.full and rank == 0 and args.lf_coder == "on" and W * H > 65536:
         def frame_digests(c, frames):
             c.sync()
             pay = c.read_payload()
@@ -1221,7 +1346,7 @@ def main():
     # un-overlapped kernel durations
     lat = None
     lat5 = None
-    if world == 1:
+    if args.full and world == 1:
         c0 = ctxs[0]
         # the throughput form's own un-overlapped durations
         c0.set_rans_waves(max(5, args.rans_waves))
@@ -1260,7 +1385,7 @@ def main():
     # reference leg: the same loop, timed the same way, with the LF-group coder switched off (SURVEY.md 8(d)(ii)'s
     # narrower definition: device-resident input -> HF group sections only)
     hf_only = None
-    if world == 1 and args.lf_coder == "on" and not args.no_legs:
+    if args.full and world == 1 and args.lf_coder == "on" and not args.no_legs:
         for c in ctxs:
             c.set_lf_coder(False)
         r2 = timed_run(4 * S)
@@ -1271,7 +1396,7 @@ def main():
 
     # the same loop with ONE frame per launch group (what rounds 1-3 timed)
     one_per_group = None
-    if world == 1 and FPL > 1 and not args.no_legs:
+    if args.full and world == 1 and FPL > 1 and not args.no_legs:
         r1 = timed_run(8 * S, lambda i: ctxs[i % S].encode_image_tensor(pictures[i % S][0]))
         one_per_group = {"Mpixel/s": round(W * H * 8 * S / r1["dt"] / 1e6, 1), "ms_per_step": round(r1["dt"] / (8 * S) * 1e3, 4), "frames": 8 * S,
                          "note": "same loop, contexts and timing, hydamd_encode_image: every frame a launch group of its own"}
@@ -1279,7 +1404,7 @@ def main():
     # and with the frame FINISHED in the loop: every step also exports the context's results and puts the codestream together
     # on the device (hydamd_assembler_*), so that a step ends with the complete .jxl file in HBM instead of its sections
     whole_file = None
-    if world == 1 and args.lf_coder == "on" and not args.no_legs and W * H > 65536:
+    if args.full and world == 1 and args.lf_coder == "on" and not args.no_legs and W * H > 65536:
         md = api.HYDImageMetadata(W, H, 0, -1, -1)
         asms = [device.Assembler(local) for _ in ctxs]
         cap = ctxs[0].blob_bound(lfg)
@@ -1305,8 +1430,7 @@ def main():
             a.close()
         del outs_w
 
-    out = None
-    if rank == 0:
+    if args.full and rank == 0:
         bytes_in = W * H * 3 * (args.depth // 8)
         kernels = {k: {"avg_ms": round(v[0] / max(v[1], 1), 4), "launches": v[1],
                        "algorithmic_GBs": round(bytes_in * groups_profiled / (v[0] / max(v[1], 1) * 1e-3) / 1e9, 1) if v[0] else None}
@@ -1353,45 +1477,25 @@ def main():
                                         "the best VALU issue rate measured on this chip; the guard-banded fast DCT that could lower it "
                                         "was measured and dropped (profiles/r03_guardband.txt)"}
         per_stream = run["periods"]
-        out = {
-            "metric": "Mpixel/s encode (8K RGB, default q)",
-            "value": round(world * W * H * K / dt / 1e6, 1),
-            "unit": "Mpixel/s",
-            "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / K * 1e3, 4),
-            "value_is": "the SUSTAINED rate: median of three consecutive windows (timing.timed_frames frames each) of one continuous run behind ten launch groups per stream of priming "
-                        "(it equals the barrier-to-barrier rate of the whole run, timing.Mpixel/s_wall, within a few per cent)",
+        out.update({
             "value_by_the_method_of_rounds_1_to_3": round(world * W * H * 2 * S * FPL / burst["dt"] / 1e6, 1),
             "value_by_the_method_of_rounds_1_to_3_is": "a short event window right behind a short priming phase, from an idle GPU (BENCH_r03: 136 941 by this "
                                                        "method); the GPU's first 150 ms under this load run 10-15 % faster than what follows (DESIGN.md 4)",
-            "timing": {"method": "HIP events at the end of each frame's stream: completion of the last priming frames -> "
-                                 "completion of the last timed frames, pipeline primed before and kept full behind; "
-                                 "one continuous run: ten launch groups per stream of priming (the GPU's first 150 ms under this load run 10-15 % fast), "
-                                 "then three consecutive windows of at least eight launch groups per stream (timed_frames frames each); the rate is "
-                                 "per frame of the median window = the SUSTAINED rate; no event timers inside the windows",
-                       "timed_frames": K, "windows": WINDOWS, "Mpixel/s_each_window": window_rates,
+            "timing": dict(out["timing"], **{
+                       "windows_method": "a second continuous run of the same loop: ten launch groups per stream of priming, then three consecutive "
+                                         "windows of at least eight launch groups per stream (window_frames frames each), timed by the same events; "
+                                         "the median window is Mpixel/s_median_window; no event timers inside the windows",
+                       "window_frames": K, "windows": WINDOWS, "Mpixel/s_each_window": window_rates,
+                       "Mpixel/s_median_window": round(world * W * H * K / dt / 1e6, 1),
                        "Mpixel/s_first_100ms_after_idle": round(world * W * H * 2 * S * FPL / burst["dt"] / 1e6, 1),
                        "first_100ms_note": "a window of two launch groups per stream right behind two of priming, from an idle GPU: the method of "
                                            "rounds 1-3 (round 3's driver line, 136.9 Gpixel/s, was measured this way); `value` is the sustained rate",
                        "spread_pct": round(100.0 * (max(window_rates) - min(window_rates)) / (sum(window_rates) / len(window_rates)), 2),
-                       "value_is": "the median window",
                        "per_stream_ms_per_step": ({"min": round(min(per_stream), 4), "mean": round(sum(per_stream) / len(per_stream), 4),
                                                    "max": round(max(per_stream), 4)} if per_stream else None),
-                       "transform_kernel_alone_ms_over_ms_per_step": round(k1_ms / (dt / K * 1e3), 3) if k1_ms else None,
-                       "wall_ms_incl_fill_and_drain": round(wall * 1e3, 3), "frames_in_wall": total_frames,
-                       "Mpixel/s_wall": round(world * W * H * total_frames / wall / 1e6, 1)},
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "host_placement": placement or "unbound",
-            "config": {"workload": f"{W}x{H} RGB{args.depth} '{args.kind}' frame per GPU (BASELINE configs[2]); "
-                                   "hot path device-resident RGB -> packed HF group sections "
-                                   "(XYB, DCT, quantise, tokenise, ANS tables, rANS, pack)" +
-                                   (f", {FPL} independent frames per launch group" if FPL > 1 else "") +
-                                   (" + prefix-coded LF coefficient streams" if args.lf_coder == "on" else ""),
-                       "lf_coder": "gpu, in-stream" if args.lf_coder == "on" else "off",
-                       "groups": lfg * 64 if W % 2048 == 0 and H % 2048 == 0 else None, "lf_groups": lfg,
-                       "streams": len(ctxs), "frames_per_launch_group": FPL, "rans_groups_per_workgroup": args.rans_waves, "parallelism": f"{world} x (one frame per GPU)" +
-                                                            (f", one RCCL gather of result blobs per {per} frames, root rotating over the ranks" if exchange else ", no collective (independent frames)")},
+                       "transform_kernel_alone_ms_over_ms_per_step": round(k1_ms / (head["dt"] / N * 1e3), 3) if k1_ms else None,
+                       "windows_wall_ms_incl_fill_and_drain": round(wall * 1e3, 3), "frames_in_windows_wall": total_frames,
+                       "Mpixel/s_windows_wall": round(world * W * H * total_frames / wall / 1e6, 1)}),
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                          "algorithmic_bytes_per_launch": bytes_in, "avg_launch_ms": round(dom_ms, 4),
@@ -1417,11 +1521,9 @@ def main():
             "finished_file_per_step": whole_file,
             "symbols_per_pixel": round(symbols / (W * H), 4),
             "section_bytes": payload_bytes,
-            "hbm_read_roofline_Mpx_s": round(HBM_PEAK_GBS * 1e9 / (3 * args.depth // 8) / 1e6, 0),
-            "frac_of_hbm_read_roofline": round((W * H * K / dt) / (HBM_PEAK_GBS * 1e9 / (3 * args.depth // 8)), 5),
-        }
+        })
     host_img = None
-    if rank == 0 and world == 1 and not (args.no_cpu_baseline and args.no_api):
+    if args.full and rank == 0 and world == 1 and not (args.no_cpu_baseline and args.no_api):
         arr = img.cpu().numpy()
         host_img = np.ascontiguousarray(arr.view(np.uint16) if args.depth == 16 else arr)
 
@@ -1445,7 +1547,7 @@ def main():
     # ---- the other two BASELINE workloads, a few hundred milliseconds each, in the same line: configs[3] (one 16K frame
     # sharded over the GPUs, assembled on the device) and configs[4] (a batch of 4K frames through the drop-in API) ----
     legs = {}
-    if not args.no_legs and world == 1:  # (N > 1: as jobs of their own once the group is gone, see child_job)
+    if args.full and not args.no_legs and world == 1:  # (N > 1: as jobs of their own once the group is gone, see child_job)
         def shard_16k():
             if not dist.is_initialized():  # a lone rank needs the process group for this leg only: it comes last
                 for k, v in (("MASTER_ADDR", "127.0.0.1"), ("MASTER_PORT", "29533"), ("RANK", "0"), ("WORLD_SIZE", "1")):
@@ -1470,7 +1572,7 @@ def main():
                 legs[name] = r
             except Exception as exc:  # a leg must not take the headline with it
                 legs[name] = {"error": f"{type(exc).__name__}: {exc}"}
-    if rank == 0:
+    if args.full and rank == 0:
         for name, r in legs.items():
             if r is None:
                 continue
@@ -1527,7 +1629,7 @@ def main():
     # gone: the other ranks are not held in a collective meanwhile (a leg that hangs on hardware it has never met would run the
     # group's watchdog out and take the headline with it), and at --gpus N their GPUs are idle when rank 0's subprocess takes them.
     if rank == 0:
-        if world > 1 and not args.no_legs:
+        if args.full and world > 1 and not args.no_legs:
             # configs[3] and configs[4] over all N GPUs, each a job of its own (in a world of one they ran in-process above)
             for name, argv in (("shard_16k", ["--mode", "shard", "--steps", "40", "--warmup", "4"]),
                                ("batch_4k", ["--mode", "batch", "--frames", str(8 * args.frames), "--threads", str(args.threads)])):
@@ -1536,7 +1638,7 @@ def main():
                 r["leg_wall_s"] = round(time.perf_counter() - t_leg, 2)
                 out[name] = {k: r[k] for k in LEG_KEYS if k in r}
                 out[name]["ran_as"] = f"a job of its own after the frame loop's process group was gone: bench.py --gpus {world} " + " ".join(argv)
-        if not args.no_legs and not args.no_api:
+        if args.full and not args.no_legs and not args.no_api:
             # the C library's own multi-device scheduler, over every GPU of the job (one GPU: an aliased list), once, on rank 0
             try:
                 out["api_multi_device"] = api_multi_device_leg(world)
@@ -1544,7 +1646,7 @@ def main():
                     out["api_multi_device"]["same_file_as_shard_16k"] = out["api_multi_device"]["md5"] == out["shard_16k"]["frame_md5"]
             except Exception as exc:
                 out["api_multi_device"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not args.no_legs:
+        if args.full and not args.no_legs:
             # the same frame as shard_16k through the C library's in-process composition (no RCCL, no host pixels)
             try:
                 out["shard_16k_inprocess"] = shard_inprocess_leg(world)

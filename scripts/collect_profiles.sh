@@ -53,13 +53,13 @@ trace() { # name, summariser args..., -- command...: rocprofv3 kernel trace of t
 }
 
 if want bench_default; then
-run bench_default json python bench.py
+run bench_default json python bench.py --full
 fi
 
 if want kernel_stats; then
 trace single -- python "$root/scripts/one_frame.py" 5 5 2
 trace single_form4 -- python "$root/scripts/one_frame.py" 5 4 2
-trace pipe -- python "$root/bench.py" --steps 256 --no-cpu-baseline --no-api --no-legs
+trace pipe -- python "$root/bench.py" --full --steps 256 --no-cpu-baseline --no-api --no-legs
 grep "^{" /tmp/kt_pipe.log | tail -1 > "$out/${tag}_bench_under_rocprof.json"; [ -s "$out/${tag}_bench_under_rocprof.json" ] || fail bench_under_rocprof /tmp/kt_pipe.log
 # the same trace per hardware queue: how long every kernel of the loop WAITS behind its predecessor on its queue, and how long it runs
 db=$(find /tmp/kt_pipe -name "*.db" 2>/dev/null | head -1)
@@ -214,7 +214,7 @@ fi
 # the noise loop by entropy-stage form (VERDICT r5 task 7: would the wave form, faster alone on long groups, serve a chain-bound loop?)
 if want noise_forms; then
 run noise_forms txt bash -c '
-  n() { python bench.py --kind noise --steps 48 --no-cpu-baseline --no-api --no-legs --no-content "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d[\"value\"]/1e3,1), \"Gpixel/s\", d[\"timing\"][\"Mpixel/s_each_window\"])"; }
+  n() { python bench.py --full --kind noise --steps 48 --no-cpu-baseline --no-api --no-legs --no-content "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d[\"timing\"][\"Mpixel/s_median_window\"]/1e3,1), \"Gpixel/s\", d[\"timing\"][\"Mpixel/s_each_window\"])"; }
   echo "# the noise loop (8192^2 RGB16 random pixels, 2.86 symbols per pixel) by entropy-stage form: 5 = one lane per group (79.5 KB of LDS per LF group), 4 = one wave per group (144 KB per workgroup of four groups); bench.py --kind noise; commit $(cat .commit 2>/dev/null)"
   for i in 1 2; do
     echo -n "lane form, 16 streams x 2: "; n --rans-waves 5
@@ -241,7 +241,7 @@ fi
 # what an RCCL process group's mere presence in the process costs the frame loop (every rank of a --gpus N job carries one)
 if want pg_presence; then
 run pg_presence txt bash -c '
-  b() { python bench.py --steps 256 --no-cpu-baseline --no-api --no-legs --no-content "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d[\"value\"]/1e3,1), \"Gpixel/s\", d[\"timing\"][\"Mpixel/s_each_window\"], \"rccl_ranks\", d.get(\"rccl_ranks\"))"; }
+  b() { python bench.py --full --steps 256 --no-cpu-baseline --no-api --no-legs --no-content "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d[\"timing\"][\"Mpixel/s_median_window\"]/1e3,1), \"Gpixel/s\", d[\"timing\"][\"Mpixel/s_each_window\"], \"rccl_ranks\", d.get(\"rccl_ranks\"))"; }
   echo "# the frame loop on one GPU without and with an RCCL process group in the process (HYDAMD_BENCH_FORCE_PG=1: what every rank of a --gpus N job carries); commit $(cat .commit 2>/dev/null)"
   for i in 1 2 3; do echo -n "no process group:   "; b; echo -n "RCCL group present: "; HYDAMD_BENCH_FORCE_PG=1 b; done
 '

@@ -90,18 +90,18 @@ def one(name, frames=6, pipe=False):
         lds, regs = ctx.transform_footprint(1)
         res["lds"], res["vgpr"] = lds, regs
     if pipe:
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "96", "--no-cpu-baseline", "--no-api", "--no-legs"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "96", "--no-cpu-baseline", "--no-api", "--no-legs"],
                            capture_output=True, text=True, env=dict(os.environ))
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])
-            res["pipe_gpx"] = round(d["value"] / 1e3, 1)
+            res["pipe_gpx"] = round(d["timing"]["Mpixel/s_median_window"] / 1e3, 1)
         except Exception as e:  # noqa: BLE001
             res["pipe_gpx"] = f"failed: {e}: {r.stderr[-300:]}"
         if os.environ.get("K1V_NOISE"):  # the chain-bound loop: 2.9 symbols per pixel
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "48", "--kind", "noise", "--no-cpu-baseline", "--no-api",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "48", "--kind", "noise", "--no-cpu-baseline", "--no-api",
                                 "--no-legs", "--no-content"], capture_output=True, text=True, env=dict(os.environ))
             try:
-                res["noise_gpx"] = round(json.loads(r.stdout.strip().splitlines()[-1])["value"] / 1e3, 1)
+                res["noise_gpx"] = round(json.loads(r.stdout.strip().splitlines()[-1])["timing"]["Mpixel/s_median_window"] / 1e3, 1)
             except Exception as e:  # noqa: BLE001
                 res["noise_gpx"] = f"failed: {e}: {r.stderr[-300:]}"
     print("RESULT " + json.dumps(res), flush=True)

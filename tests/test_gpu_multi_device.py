@@ -42,14 +42,17 @@ if a.get("order") == "reversed":
     ntx, nty = -(-w // 2048), -(-h // 2048)
     tiles = [(tx, ty) for ty in range(nty) for tx in range(ntx)][::-1]
 lib = api.Library()
+import threading
+said = threading.Lock()                 # print() writes its items one by one: lines of threads side by side would interleave
 def one(tag):
     try:
         data = api.encode_image(lib, img, order=tiles)
-        print(tag, len(data), hashlib.md5(data).hexdigest(), flush=True)
+        with said:
+            print(tag, len(data), hashlib.md5(data).hexdigest(), flush=True)
     except api.HydriumError as e:
-        print(tag, "ERR", e, flush=True)
+        with said:
+            print(tag, "ERR", e, flush=True)
 if a.get("threads"):                    # encoders side by side, one per thread (ctypes releases the GIL inside the library)
-    import threading
     ts = [threading.Thread(target=one, args=("OURS",)) for _ in range(a["threads"])]
     [t.start() for t in ts]; [t.join() for t in ts]
 else:
