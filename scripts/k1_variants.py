@@ -26,41 +26,27 @@ def lib_of(name):
 
 
 def build(specs):
+    """name=-DFLAG=1,-DOTHER=2 ... through hydrium_amd/build.py's build_variant; LF:<flag> is accepted as before (a HYDK_LF_*
+    define recompiles lf_coder.hip as well).  Linked with the HYD_TEST_HOOKS flavour's objects: the probes skip stages through
+    HYDAMD_DEBUG_SKIP.  The library is copied to scripts/probe_build/k1v_<name>.so, where the profile scripts look for it."""
+    import shutil
+
     from hydrium_amd import build as hb
 
-    hb.build()
     os.makedirs(OUT, exist_ok=True)
-    # the HYD_TEST_HOOKS flavour's objects (the probes skip stages through HYDAMD_DEBUG_SKIP), kernels.hip recompiled per variant
-    names = sorted(os.listdir(hb.OBJ_DIR))
-    base_objs = [os.path.join(hb.OBJ_DIR, f) for f in names
-                 if f != "kernels.hip.o" and (f.endswith(".test.o") or (f.endswith(".o") and f[:-2] + ".test.o" not in names))]
-    procs = []
+    want = {}
     for spec in specs:
         name, _, flags = spec.partition("=")
-        flags = [f for f in flags.split(",") if f]
-        lf_only = [f[3:] for f in flags if f.startswith("LF:")]  # LF:<flag>: for lf_coder.hip alone (and that file is recompiled)
-        flags = [f for f in flags if not f.startswith("LF:")]
-        obj = os.path.join(OUT, f"k1v_{name}.kernels.o")
-        cmd = [hb.HIPCC] + hb.HIP_FLAGS + flags + ["-c", os.path.join(hb.CSRC, "hip", "kernels.hip"), "-o", obj]
-        pr2, obj2 = None, None
-        if lf_only or any("HYDK_LF_" in f for f in flags):  # a switch lf_coder.hip reads too: that file is recompiled as well
-            obj2 = os.path.join(OUT, f"k1v_{name}.lf_coder.o")
-            pr2 = subprocess.Popen([hb.HIPCC] + hb.HIP_FLAGS + flags + lf_only + ["-c", os.path.join(hb.CSRC, "hip", "lf_coder.hip"), "-o", obj2],
-                                   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        procs.append((name, obj, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True), obj2, pr2))
-    for name, obj, pr, obj2, pr2 in procs:
-        out, _ = pr.communicate()
-        out2 = pr2.communicate()[0] if pr2 else ""
-        if pr.returncode or (pr2 and pr2.returncode):
-            print(f"{name}: COMPILE FAILED\n{out}{out2}")
-            continue
-        objs = [o for o in base_objs if not (obj2 and os.path.basename(o).startswith("lf_coder.hip"))] + [obj] + ([obj2] if obj2 else [])
-        hb._run([hb.HIPCC, f"--offload-arch={hb.ARCH}", "-shared", "-fPIC", "-Wl,-soname,libhydrium.so.0", "-o", lib_of(name)]
-                + objs + ["-lpthread"])
-        os.remove(obj)
-        if obj2:
-            os.remove(obj2)
-        print("built", lib_of(name))
+        flags = [f[3:] if f.startswith("LF:") else f for f in flags.split(",") if f]
+        want["k1v_" + name] = [f[2:] for f in flags]  # -DNAME=value -> NAME=value
+    try:
+        built = hb.build_variants(want, probe=True)
+    except RuntimeError as e:
+        print(f"COMPILE FAILED: {e}")
+        return
+    for name, path in built.items():
+        shutil.copy2(path, os.path.join(OUT, name + ".so"))
+        print("built", os.path.join(OUT, name + ".so"))
 
 
 def one(name, frames=6, pipe=False):

@@ -7,6 +7,7 @@ stay alive; oracle/ref_probe.c exposes them.
 import numpy as np
 import pytest
 
+import variant_corpus
 from hydrium_amd import api
 from oracle import binding as orc
 
@@ -19,6 +20,14 @@ CASES = [
     ("ramp", 8, 8, 8),
     ("black", 40, 24, 8),
     ("white", 33, 9, 16),
+    # edge content of tests/variant_corpus.py: the largest tokens (28), LF extremes, 16-bit extremes around the curve's branch
+    ("basis_grey", 256, 256, 16),
+    ("basis_grey", 64, 72, 8),
+    ("basis_rg", 200, 136, 16),
+    ("basis_by", 136, 200, 8),
+    ("primaries", 264, 200, 16),
+    ("primaries", 96, 40, 8),
+    ("extremes16", 300, 260, 16),
 ]
 
 
@@ -43,7 +52,7 @@ def test_luts_match_reference(ref_probe, image):
 
 @pytest.mark.parametrize("kind,w,h,depth", CASES)
 def test_stages_match_reference(ref_probe, image, kind, w, h, depth):
-    img = image(kind, w, h, depth)
+    img = variant_corpus.edge_image(kind, w, h, depth) if kind in variant_corpus.EDGE_KINDS else image(kind, w, h, depth)
     res, max_alpha = orc.encode_lf_group(img)
 
     # stage 1+2: XYB then DCT, bit-exact floats
