@@ -53,6 +53,7 @@
 #include "bitio.h"
 #include "frame.h"
 #include "prefix.h"
+#include "shards.h"
 #include "hydrium_amd.h"
 #include "libhydrium/libhydrium.h"
 
@@ -142,11 +143,12 @@ static int trace_on(void) {
     }
     return on;
 }
-#define TRACE(label, t0)                                                          \
-    do {                                                                          \
-        if (trace_on())                                                           \
-            fprintf(stderr, "[hydrium] %-28s %8.3f ms\n", (label), now_ms() - (t0)); \
+#define TRACE_MS(label, ms)                                             \
+    do {                                                                \
+        if (trace_on())                                                 \
+            fprintf(stderr, "[hydrium] %-28s %8.3f ms\n", (label), (ms)); \
     } while (0)
+#define TRACE(label, t0) TRACE_MS(label, now_ms() - (t0))
 
 /* ---------------------------------------------------------------------------------------------
  * frame assembly (shared by the product path and the CPU-only test hook)
@@ -883,66 +885,58 @@ static int host_assembly_forced(void) {
     return on;
 }
 
-/* The frame put together on the GPU (csrc/hip/assemble.hip): the context exports its results as one blob in
- * device memory, the assembler's kernels write every section into place behind the entropy stage, and the
- * finished frame comes back in ONE copy — where the host used to read back tables, section sizes and LF
- * streams slot by slot, code the LF group sections itself and splice everything together. */
-static int finish_frame_on_device(HYDEncoder *e, const HydFrameShape *shape) {
-    const size_t n = shape->lfg_count;
-    double t0 = now_ms();
-    int ret = hydamd_finish_frame(e->dev, (int)n);
-    if (ret)
-        return device_fail(e, ret);
-    HydAmdAssembler *as = hydamd_context_assembler(e->dev);
-    if (!as)
-        return device_fail(e, HYD_INTERNAL_ERROR);
+/* The frame put together on the GPU (csrc/hip/assemble.hip): the contexts export their results as blobs in device
+ * memory, the assembler's kernels write every section into place behind the entropy stage, and the finished frame comes
+ * back in ONE copy — where the host used to read back tables, section sizes and LF streams slot by slot, code the LF group
+ * sections itself and splice everything together.  The procedure is shards.c's, for one context or several; this is what
+ * hyd_send_tile makes of it: LF groups in the order they were sent, no file header in the frame, the outcome as this
+ * encoder's error and failed-device marks, the file appended to the output stream.  A peer-read mismatch is left to the
+ * caller (o->kind). */
+static int close_frame(HYDEncoder *e, const HydFrameShape *shape, HydShardFrame *f, HydShardOutcome *o, const char *hot_label, double t0) {
     uint32_t lf_ids[HYDAMD_MAX_LF_GROUPS];
-    for (size_t s = 0; s < n; s++)
+    for (size_t s = 0; s < shape->lfg_count; s++)
         lf_ids[s] = (uint32_t)shape->lfg[s].raster_id;
-    const uint32_t slots = (uint32_t)n;
-    ret = hydamd_assembler_plan(as, &e->metadata, 0, 1, 1, &slots, lf_ids, NULL, 0);
-    if (ret)
-        return FAIL(e, ret, "frame description rejected by the assembler");
-    /* the blob is a view: the output's size comes from the context's capacities plus what the assembler itself adds per
-     * LF group (head bits, TOC entries) and per frame (prefix, HFGlobal); should a frame still exceed it, the assembler
-     * says how many bytes it needs and the frame is assembled again into a buffer of that size */
-    size_t out_cap = hydamd_blob_bound(e->dev, (int)n) + 4096 * n + (256u << 10);
-    for (int attempt = 0; attempt < 4; attempt++) {
-        const void *blob = NULL;
-        size_t cap = 0, size = 0;
-        ret = hydamd_export_frame_owned(e->dev, (int)n, &blob, &cap);
-        if (!ret)
-            ret = hydamd_assembler_run(as, &blob, &cap, hydamd_get_stream(e->dev), NULL, out_cap);
-        if (ret)
-            return device_fail(e, ret);
-        ret = hydamd_sync(e->dev); /* a frame that outgrew the context's buffers is rerun in here: its blob is then stale */
-        if (ret)
-            return device_fail(e, ret);
-        TRACE("GPU hot path + assembly", t0);
-        t0 = now_ms();
-        ret = hydamd_assembler_result(as, &size);
-        if (ret) {
-            const char *m = hydamd_assembler_error(as);
-            if (m && strstr(m, "incomplete"))
-                continue; /* export the rerun frame's results and assemble again */
-            if (ret == HYD_NEED_MORE_OUTPUT && size > out_cap) {
-                out_cap = size;
-                continue;
-            }
-            if (m && strstr(m, "NaN"))
-                return FAIL(e, HYD_API_ERROR, "Invalid NaN Float");
-            mark_device_failed(e);
-            return FAIL(e, ret < HYD_ERROR_START ? ret : HYD_INTERNAL_ERROR, "GPU frame assembly failed");
-        }
-        uint8_t *dst = hb_extend(&e->stream, size);
-        if (!dst)
-            return FAIL(e, HYD_NOMEM, "out of memory");
-        ret = hydamd_assembler_read(as, dst, size);
-        TRACE("frame to the host", t0);
-        return ret ? device_fail(e, ret) : 0;
+    f->md = &e->metadata;
+    f->lf_ids = lf_ids;
+    const double lead = now_ms() - t0;
+    if (!hyd_shards_enqueue(f, o))
+        hyd_shards_wait(f, o);
+    e->dev = f->ctx[o->kind == SHARDS_DEVICE ? o->shard : f->assembling];
+    if (o->hot_ms > 0)
+        TRACE_MS(hot_label, lead + o->hot_ms);
+    switch (o->kind) {
+    case SHARDS_OK:
+        break;
+    case SHARDS_DEVICE:
+        return device_fail(e, o->code);
+    case SHARDS_PLAN:
+        return FAIL(e, o->code, "frame description rejected by the assembler");
+    case SHARDS_NAN:
+        return FAIL(e, o->code, "Invalid NaN Float");
+    case SHARDS_MISMATCH:
+        return o->code;
+    case SHARDS_ASSEMBLY:
+        mark_device_failed(e);
+        return FAIL(e, o->code, "GPU frame assembly failed");
+    default:
+        mark_device_failed(e);
+        return FAIL(e, o->code, o->msg);
     }
-    mark_device_failed(e);
-    return FAIL(e, HYD_INTERNAL_ERROR, "frame still does not fit after enlarging its buffers");
+    if (o->verify_ms > 0)
+        TRACE_MS("peer reads verified (first use of these device pairs)", o->verify_ms);
+    const double t1 = now_ms();
+    uint8_t *dst = hb_extend(&e->stream, o->size);
+    if (!dst)
+        return FAIL(e, HYD_NOMEM, "out of memory");
+    const int ret = hydamd_assembler_read(hydamd_context_assembler(e->dev), dst, o->size);
+    TRACE("frame to the host", t1);
+    return ret ? device_fail(e, ret) : 0;
+}
+
+static int finish_frame_on_device(HYDEncoder *e, const HydFrameShape *shape) {
+    HydShardFrame f = {.n = 1, .ctx = {e->dev}, .slots = {(uint32_t)shape->lfg_count}};
+    HydShardOutcome o;
+    return close_frame(e, shape, &f, &o, "GPU hot path + assembly", now_ms());
 }
 
 /* frames assembled on the host from ONE read-back (hydamd_stage_frame_blob / hydamd_read_frame_blob) instead of one small
@@ -1170,21 +1164,12 @@ static int finish_frame(HYDEncoder *e, const HydFrameShape *shape) {
  * the way the register LUT evaluation does: the FIRST sharded frame of the process over each (assembling entry, owning
  * entry) pair of the device list is verified — the floor against a host copy of the owners' maxima (hydamd_verify_floor),
  * every shard's view by a checksum on the owning and on the assembling device (hydamd_verify_enqueue) — and a pair that
- * passes is latched (cost once: ~4 ms for a 16384^2 frame).  A pair that FAILS: one line on stderr, that frame is finished
- * through host memory instead (finish_frame_through_host: same bytes, no peer read), and from then on the process keeps
- * every frame on one device.  HYDAMD_VERIFY_PEERS=1: every sharded frame is verified and a mismatch is an error that
- * names the device pair; =0: never. */
-enum { VERIFY_NEVER = 0, VERIFY_ALWAYS = 1, VERIFY_FIRST_USE = 2 };
-static int verify_peers_mode(void) {
-    static int mode = -1;
-    if (mode < 0) {
-        const char *v = getenv("HYDAMD_VERIFY_PEERS");
-        mode = !v || !*v ? VERIFY_FIRST_USE : *v == '0' ? VERIFY_NEVER : VERIFY_ALWAYS;
-    }
-    return mode;
-}
-static unsigned char g_pair_ok[HYD_MAX_DEVICES][HYD_MAX_DEVICES]; /* [assembling list entry][owning list entry], under g_ctx_lock */
-static int g_peer_reads_bad;                                       /* a first-use verification failed: no more sharded frames */
+ * passes is latched (cost once: ~4 ms for a 16384^2 frame); shards.c chooses, checks and latches.  A pair that FAILS: one
+ * line on stderr, that frame is finished through host memory instead (finish_frame_through_host: same bytes, no peer
+ * read), and from then on the process keeps every frame on one device.  HYDAMD_VERIFY_PEERS=1: every sharded frame is
+ * verified and a mismatch is an error that names the device pair; =0: never. */
+static HydPairLatch g_pair_ok = HYD_PAIR_LATCH_INIT; /* [reading list entry][owning list entry]: an aliased list's entries stay apart */
+static int g_peer_reads_bad; /* a first-use verification failed: no more sharded frames (under g_ctx_lock) */
 
 static void multi_release(HYDEncoder *e) {
     if (e->shards > 1) {
@@ -1295,202 +1280,47 @@ done:
 
 /* The closing stage of a frame whose LF groups sit on several devices' contexts (shard d: tiles first_slot[d] ... in send
  * order).  Per device what the reference does per LF group (encoder.c:928-957), with two crossings, both device-side: the
- * running alphabet maximum (hydamd_alphabet_floor_from_peers: a peer read behind the earlier shards' transform kernels)
- * and the frame itself, which the first shard's GPU — the encoder's home device — assembles from every shard's blob, read
- * in place over xGMI (hydamd_wait_for + peer access); nothing of the frame passes through host memory before the
- * finished file. */
+ * running alphabet maximum (a peer read behind the earlier shards' transform kernels) and the frame itself, which the
+ * first shard's GPU — the encoder's home device — assembles from every shard's blob, read in place over xGMI; nothing of
+ * the frame passes through host memory before the finished file.  The procedure is shards.c's (through close_frame); the
+ * policy is here: shard 0 assembles, device pairs are latched by their entries in the device list, and a peer read that
+ * fails its check is an error that names the pair (HYDAMD_VERIFY_PEERS=1) or sends this frame through host memory and
+ * every later one to a single device (first use). */
 static int finish_frame_multi(HYDEncoder *e, const HydFrameShape *shape) {
     const int N = e->shards;
-    const size_t n = shape->lfg_count;
-    HydAmdContext *ctxs[HYD_MAX_DEVICES];
-    double t0 = now_ms();
-    int ret = 0;
+    const double t0 = now_ms();
+    HydShardFrame f = {.n = N, .latch = &g_pair_ok};
+    HydShardOutcome o;
+    int ret;
     for (int d = 0; d < N; d++) {
-        ctxs[d] = e->multi[d].dev;
-        if (!ctxs[d])
+        f.ctx[d] = e->multi[d].dev;
+        f.slots[d] = (uint32_t)e->multi[d].slots;
+        f.key[d] = e->multi[d].entry;
+        if (!f.ctx[d])
             return FAIL(e, HYD_INTERNAL_ERROR, "a shard of this frame never received a tile");
     }
-    /* which of this frame's peer reads are checked: all of them (HYDAMD_VERIFY_PEERS=1), or those of a (reader, owner)
-     * pair of list entries no earlier frame of the process has verified */
-    const int mode = verify_peers_mode();
-    int check_view[HYD_MAX_DEVICES] = {0}, check_floor[HYD_MAX_DEVICES] = {0}, checking = 0;
-    if (mode != VERIFY_NEVER) {
-        pthread_mutex_lock(&g_ctx_lock);
-        for (int d = 1; d < N; d++) {
-            check_view[d] = mode == VERIFY_ALWAYS || !g_pair_ok[e->multi[0].entry][e->multi[d].entry];
-            for (int p = 0; p < d; p++) /* shard d's floor kernel reads shards 0 .. d-1 */
-                check_floor[d] |= mode == VERIFY_ALWAYS || !g_pair_ok[e->multi[d].entry][e->multi[p].entry];
-            checking |= check_view[d] | check_floor[d];
-        }
-        pthread_mutex_unlock(&g_ctx_lock);
-    }
     for (int d = 0; d < N; d++) { /* whatever of the transform stage the tiles' own calls did not enqueue */
-        e->dev = ctxs[d];
-        if ((ret = hydamd_run_transform(ctxs[d], (int)e->multi[d].slots)) != 0)
+        e->dev = f.ctx[d];
+        if ((ret = hydamd_run_transform(f.ctx[d], (int)f.slots[d])) != 0)
             return device_fail(e, ret);
     }
-    for (int d = 1; d < N; d++) { /* shard d's entropy tables start from the maximum over shards 0 .. d-1 */
-        e->dev = ctxs[d];
-        if ((ret = hydamd_alphabet_floor_from_peers(ctxs[d], d, ctxs)) != 0)
-            return device_fail(e, ret);
+    ret = close_frame(e, shape, &f, &o, "GPU hot path on every device + assembly", t0);
+    if (o.kind != SHARDS_MISMATCH)
+        return ret;
+    snprintf(e->verify_msg, sizeof(e->verify_msg), "peer read mismatch: device %d did not see what device %d wrote (shard %d, %s)",
+             hydamd_context_device(f.ctx[o.reader]), hydamd_context_device(f.ctx[o.owner < 0 ? 0 : o.owner]), o.shard,
+             o.is_floor ? "alphabet floor" : "frame view");
+    if (hyd_verify_peers_mode() == VERIFY_ALWAYS) {
+        mark_device_failed(e);
+        return FAIL(e, HYD_INTERNAL_ERROR, e->verify_msg);
     }
-    for (int d = 0; d < N; d++) {
-        e->dev = ctxs[d];
-        if ((ret = hydamd_finish_frame(ctxs[d], (int)e->multi[d].slots)) != 0)
-            return device_fail(e, ret);
-    }
-    e->dev = ctxs[0];
-    HydAmdAssembler *as = hydamd_context_assembler(ctxs[0]);
-    if (!as)
-        return device_fail(e, HYD_INTERNAL_ERROR);
-    uint32_t lf_ids[HYDAMD_MAX_LF_GROUPS], blob_slots[HYD_MAX_DEVICES];
-    for (size_t s = 0; s < n; s++)
-        lf_ids[s] = (uint32_t)shape->lfg[s].raster_id;
-    for (int d = 0; d < N; d++)
-        blob_slots[d] = (uint32_t)e->multi[d].slots;
-    ret = hydamd_assembler_plan(as, &e->metadata, 0, 1, (size_t)N, blob_slots, lf_ids, NULL, 0);
-    if (ret)
-        return FAIL(e, ret, "frame description rejected by the assembler");
-    size_t out_cap = 4096 * n + (256u << 10);
-    for (int d = 0; d < N; d++)
-        out_cap += hydamd_blob_bound(ctxs[d], (int)e->multi[d].slots);
-    unsigned reruns[HYD_MAX_DEVICES];
-    for (int d = 0; d < N; d++)
-        reruns[d] = hydamd_overflow_reruns(ctxs[d]);
-    for (int attempt = 0; attempt < 4 + 2 * N; attempt++) {
-        const void *blob[HYD_MAX_DEVICES];
-        size_t cap[HYD_MAX_DEVICES], size = 0;
-        for (int d = 0; d < N; d++) {
-            e->dev = ctxs[d];
-            if ((ret = hydamd_export_frame_owned(ctxs[d], (int)e->multi[d].slots, &blob[d], &cap[d])) != 0)
-                return device_fail(e, ret);
-        }
-        e->dev = ctxs[0];
-        for (int d = 1; d < N; d++) /* the assembling GPU's stream waits for the other shards' exports and may read their memory */
-            if ((ret = hydamd_wait_for(ctxs[0], ctxs[d])) != 0)
-                return device_fail(e, ret);
-        for (int d = 1; d < N; d++) /* a shard's view summed where it was written and where it is about to be read */
-            if (check_view[d]) {
-                e->dev = ctxs[d];
-                if ((ret = hydamd_verify_enqueue(ctxs[d], ctxs[d], (int)e->multi[d].slots, 0)) != 0)
-                    return device_fail(e, ret);
-                e->dev = ctxs[0];
-                if ((ret = hydamd_verify_enqueue(ctxs[0], ctxs[d], (int)e->multi[d].slots, d)) != 0)
-                    return device_fail(e, ret);
-            }
-        e->dev = ctxs[0];
-        ret = hydamd_assembler_run(as, blob, cap, hydamd_get_stream(ctxs[0]), NULL, out_cap);
-        if (ret)
-            return device_fail(e, ret);
-        for (int d = N - 1; d >= 0; d--) { /* a shard whose frame outgrew its buffers reruns it in here: its blob is then stale */
-            e->dev = ctxs[d];
-            if ((ret = hydamd_sync(ctxs[d])) != 0)
-                return device_fail(e, ret);
-        }
-        /* a shard that reran its frame had left INCOMPLETE alphabet maxima the first time (a group that runs out of token
-         * space stops counting): the later shards read their floor from those.  They read it again and run again. */
-        int stale_from = 0;
-        for (int d = 0; d < N; d++) {
-            const unsigned now = hydamd_overflow_reruns(ctxs[d]);
-            if (now != reruns[d] && !stale_from && d + 1 < N)
-                stale_from = d + 1;
-            reruns[d] = now;
-        }
-        if (stale_from) {
-            for (int d = stale_from; d < N; d++) {
-                e->dev = ctxs[d];
-                if ((ret = hydamd_alphabet_floor_from_peers(ctxs[d], d, ctxs)) != 0 || (ret = hydamd_replay_frame(ctxs[d])) != 0)
-                    return device_fail(e, ret);
-            }
-            continue;
-        }
-        TRACE("GPU hot path on every device + assembly", t0);
-        t0 = now_ms();
-        int asm_failed = 0;
-        ret = hydamd_assembler_result(as, &size);
-        if (ret) {
-            const char *m = hydamd_assembler_error(as);
-            if (m && strstr(m, "incomplete"))
-                continue;
-            if (ret == HYD_NEED_MORE_OUTPUT && size > out_cap) {
-                out_cap = size;
-                continue;
-            }
-            if (m && strstr(m, "NaN"))
-                return FAIL(e, HYD_API_ERROR, "Invalid NaN Float");
-            if (checking && mode == VERIFY_FIRST_USE) /* an assembler that read garbage through a bad peer mapping: let the checks decide */
-                asm_failed = 1;
-            else {
-                mark_device_failed(e);
-                return FAIL(e, ret < HYD_ERROR_START ? ret : HYD_INTERNAL_ERROR, "GPU frame assembly failed");
-            }
-        }
-        int bad_reader = -1, bad_owner = -1, bad_shard = -1;
-        const char *bad_what = "";
-        for (int d = 1; d < N && bad_shard < 0; d++) {
-            if (check_floor[d]) {
-                int ok = 0;
-                e->dev = ctxs[d];
-                if ((ret = hydamd_verify_floor(ctxs[d], d, ctxs, &ok)) != 0)
-                    return device_fail(e, ret);
-                if (!ok) {
-                    bad_reader = d, bad_owner = 0, bad_shard = d, bad_what = "alphabet floor";
-                    break;
-                }
-            }
-            if (check_view[d]) {
-                unsigned long long written = 0, seen = 0;
-                e->dev = ctxs[d];
-                if ((ret = hydamd_verify_read(ctxs[d], 0, &written)) != 0)
-                    return device_fail(e, ret);
-                e->dev = ctxs[0];
-                if ((ret = hydamd_verify_read(ctxs[0], d, &seen)) != 0)
-                    return device_fail(e, ret);
-                if (written != seen)
-                    bad_reader = 0, bad_owner = d, bad_shard = d, bad_what = "frame view";
-            }
-        }
-        e->dev = ctxs[0];
-        if (bad_shard >= 0) {
-            snprintf(e->verify_msg, sizeof(e->verify_msg), "peer read mismatch: device %d did not see what device %d wrote (shard %d, %s)",
-                     hydamd_context_device(ctxs[bad_reader]), hydamd_context_device(ctxs[bad_owner]), bad_shard, bad_what);
-            if (mode == VERIFY_ALWAYS) {
-                mark_device_failed(e);
-                return FAIL(e, HYD_INTERNAL_ERROR, e->verify_msg);
-            }
-            pthread_mutex_lock(&g_ctx_lock);
-            const int first = !g_peer_reads_bad;
-            g_peer_reads_bad = 1;
-            pthread_mutex_unlock(&g_ctx_lock);
-            if (first || trace_on())
-                fprintf(stderr, "[hydrium] %s: this frame is finished through host memory, later frames stay on one device\n", e->verify_msg);
-            return finish_frame_through_host(e, shape, ctxs);
-        }
-        if (checking) { /* every peer read of this frame was seen to return what its owner wrote: these pairs are trusted from here on */
-            pthread_mutex_lock(&g_ctx_lock);
-            for (int d = 1; d < N; d++) {
-                if (check_view[d])
-                    g_pair_ok[e->multi[0].entry][e->multi[d].entry] = 1;
-                for (int p = 0; p < d && check_floor[d]; p++)
-                    g_pair_ok[e->multi[d].entry][e->multi[p].entry] = 1;
-            }
-            pthread_mutex_unlock(&g_ctx_lock);
-            TRACE("peer reads verified (first use of these device pairs)", t0);
-            t0 = now_ms();
-        }
-        if (asm_failed) { /* the peer reads were fine: the assembly failed for a reason of its own */
-            mark_device_failed(e);
-            return FAIL(e, HYD_INTERNAL_ERROR, "GPU frame assembly failed");
-        }
-        uint8_t *dst = hb_extend(&e->stream, size);
-        if (!dst)
-            return FAIL(e, HYD_NOMEM, "out of memory");
-        ret = hydamd_assembler_read(as, dst, size);
-        TRACE("frame to the host", t0);
-        return ret ? device_fail(e, ret) : 0;
-    }
-    mark_device_failed(e);
-    return FAIL(e, HYD_INTERNAL_ERROR, "frame still does not fit after enlarging its buffers");
+    pthread_mutex_lock(&g_ctx_lock);
+    const int first = !g_peer_reads_bad;
+    g_peer_reads_bad = 1;
+    pthread_mutex_unlock(&g_ctx_lock);
+    if (first || trace_on())
+        fprintf(stderr, "[hydrium] %s: this frame is finished through host memory, later frames stay on one device\n", e->verify_msg);
+    return finish_frame_through_host(e, shape, f.ctx);
 }
 
 /* tile mode: the ring entry's frame, launched some calls ago, into the output stream */

@@ -29,6 +29,9 @@ def _lib():
         C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p),
         C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
     d.hydamd_free.argtypes = [C.c_void_p]
+    d.hydt_shard_checks.restype = C.c_int
+    d.hydt_shard_checks.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int)]
     return d
 
 
@@ -38,6 +41,20 @@ class LfStream(C.Structure):  # include/hydrium_amd.h HydAmdLfStream
 
 
 _d = None
+
+
+def shard_checks(mode, keys, assembling=0, latch=True, reset=False):
+    """One image of len(keys) shards through the shared closer's choice of peer-read checks (csrc/host/shards.c), on a
+    latch table of the hook's own -> (check_view, check_floor, ordered pairs latched so far).  mode: 0 never, 1 always,
+    2 first use; latch: the image passed its checks."""
+    global _d
+    if _d is None:
+        _d = _lib()
+    n = len(keys)
+    view, floor = (C.c_int * n)(), (C.c_int * n)()
+    pairs = _d.hydt_shard_checks(int(reset), mode, n, (C.c_int * n)(*keys), assembling, int(latch), view, floor)
+    assert pairs >= 0
+    return [bool(v) for v in view], [bool(v) for v in floor], pairs
 
 
 def frame_from_stages(md, write_header, is_last, tiles, results, max_alphabet, icc=None, coded_lf=False) -> bytes:

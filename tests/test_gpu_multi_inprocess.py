@@ -5,6 +5,10 @@ A box with one GPU runs it with the device list aliased (0,0,0,0: four contexts,
 — floor by "peer" read, views, cross-stream waits — only the xGMI hop missing); every file is compared with the
 reference's for the same pixels."""
 import hashlib
+import json
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -13,6 +17,7 @@ from conftest import has_gpu, reference_expected
 from hydrium_amd import api
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs an MI355X")]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _image(kind, w, h, depth):
@@ -121,3 +126,60 @@ def test_nan_sample_is_an_api_error_also_on_the_first_frame_whose_peer_reads_are
         with pytest.raises(device.DeviceError, match="NaN") as ei:
             m.result()
         assert ei.value.code == -14  # HYD_API_ERROR
+
+
+@pytest.mark.parametrize("depth", [8, 32], ids=["u8", "f32"])
+def test_smallest_ragged_sharded_frame_with_every_shard_assembling_in_turn(depth):
+    """4100 x 40: three LF groups, the last 4 pixels wide, one per shard.  With float samples the floor read from the
+    earlier shards decides the alphabet size."""
+    from hydrium_amd import device
+
+    t, host = _image("photo", 4100, 40, depth)
+    want = _reference(host)
+    with device.MultiFrame([0, 0, 0], 4100, 40) as m:
+        assert [m.shard_lf_groups(d) for d in range(3)] == [(0, 1), (1, 1), (2, 1)]
+        files = []
+        for asm in range(3):
+            m.encode([t, t, t], assembling_shard=asm)
+            files.append(bytes(m.read()))
+    assert all(f == want for f in files), [hashlib.md5(f).hexdigest() for f in files] + [hashlib.md5(want).hexdigest()]
+
+
+_MISMATCH = r"""
+import hashlib, json, os
+import torch
+from hydrium_amd import device, synth
+t = synth.make_image("photo", 4100, 40, 8, device="cuda")
+torch.cuda.synchronize()
+out = {}
+with device.MultiFrame([0, 0], 4100, 40) as m:
+    m.encode([t, t], assembling_shard=0)
+    try:
+        m.result()
+        out["first"] = "no error"
+    except device.DeviceError as e:
+        out["first"] = [e.code, e.message]
+    del os.environ["HYDAMD_TEST_CORRUPT_PEER_VIEW"]  # (unsetenv: the hook reads it per call)
+    m.encode([t, t], assembling_shard=0)
+    out["second_md5"] = hashlib.md5(bytes(m.read())).hexdigest()
+print("RESULT " + json.dumps(out))
+"""
+
+
+def test_a_peer_read_mismatch_fails_the_frame_with_the_pair_named_and_leaves_the_object_usable():
+    """HYD_TEST_HOOKS flavour, shard 1's view as the assembling device 'sees' it differs: result() fails with the pair in
+    the message; nothing was latched (the next frame over the same pair is checked again, and passes) and the same
+    MultiFrame codes the reference's file.  A process of its own: the latches live as long as the process."""
+    from hydrium_amd import build as hbuild
+
+    _, host = _image("photo", 4100, 40, 8)
+    want = hashlib.md5(_reference(host)).hexdigest()
+    env = dict(os.environ, PYTHONPATH=ROOT, HYDAMD_LIB=hbuild.PROBE_PATH, HYDAMD_TEST_CORRUPT_PEER_VIEW="1")
+    env.pop("HYDAMD_VERIFY_PEERS", None)
+    r = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-c", _MISMATCH], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = json.loads(next(l for l in r.stdout.splitlines() if l.startswith("RESULT "))[7:])
+    code, message = out["first"]
+    assert code == api.HYD_INTERNAL_ERROR
+    assert "peer read mismatch" in message and "shard 1" in message
+    assert out["second_md5"] == want

@@ -296,3 +296,31 @@ def test_frame_buffers_are_reused_without_changing_a_byte(ref_lib, image):
     glue._lib().hydamd_trim_cache()
     for a in (small, big):
         assert glue.encode_with_oracle_stages(a) == want[id(a)]
+
+
+def test_peer_read_checks_are_chosen_and_latched_per_ordered_pair():
+    """The shared closer's choice of peer-read checks (csrc/host/shards.c), without a GPU: five images over a four-entry
+    device list, the home entry rotating (image k: keys (k + d) % 4), shard 0 assembling, the table latched after each
+    image.  The assembling key reads every other shard's view, shard d's key reads the floors of shards 0 .. d-1."""
+    NEVER, ALWAYS, FIRST_USE = 0, 1, 2
+    images = [[(k + d) % 4 for d in range(4)] for k in range(5)]
+    checked, pairs = [], []
+    for k, keys in enumerate(images):
+        view, floor, n = glue.shard_checks(FIRST_USE, keys, reset=k == 0)
+        assert not view[0] and not floor[0]        # nobody reads the assembling shard's view or gives shard 0 a floor
+        checked.append(any(view) or any(floor))
+        pairs.append(n)
+    assert checked == [True, True, True, False, False]
+    assert pairs == [9, 11, 12, 12, 12]
+    for keys in images:                            # every frame, whatever is latched (all twelve pairs are, here)
+        view, floor, n = glue.shard_checks(ALWAYS, keys)
+        assert view == [False, True, True, True] and floor == [False, True, True, True] and n == 12
+    for k, keys in enumerate(images):              # never, whatever is not latched (nothing is, here)
+        view, floor, n = glue.shard_checks(NEVER, keys, reset=k == 0)
+        assert not any(view) and not any(floor) and n == 0
+    for _ in range(3):                             # key 16 is outside the table: its pairs are checked every time ...
+        view, floor, n = glue.shard_checks(FIRST_USE, [0, 16, 1], reset=False)
+        assert view == [False, True, _ == 0] and floor == [False, True, True]
+        assert n == 2                              # ... and never latched: (0, 1) and (1, 0) are
+    view, floor, _ = glue.shard_checks(ALWAYS, [0, 1, 2], assembling=1, latch=False, reset=True)
+    assert view == [True, False, True] and floor == [False, True, True]
