@@ -79,8 +79,10 @@ KNOBS = {
     "HYDAMD_K1_SPLIT": ["0"],
 }
 COVERED = {
-    "HYDAMD_TOKEN_CAP": "tests/test_gpu_device_parity.py::test_frame_that_outgrows_its_buffers_is_rerun_transparently",
-    "HYDAMD_PAYLOAD_CAP": "tests/test_gpu_api_parity.py::test_tile_frame_rerun_for_overflow_after_its_results_were_staged",
+    # (far from the edge as well: test_gpu_device_parity.py::test_frame_that_outgrows_its_buffers_is_rerun_transparently,
+    # test_gpu_api_parity.py::test_tile_frame_rerun_for_overflow_after_its_results_were_staged)
+    "HYDAMD_TOKEN_CAP": "tests/test_gpu_buffer_edges.py::test_exact_fit_and_one_step_short",
+    "HYDAMD_PAYLOAD_CAP": "tests/test_gpu_buffer_edges.py::test_exact_fit_and_one_step_short",
     "HYDAMD_DEVICES": "tests/test_gpu_multi_device.py::test_c_client_unchanged_runs_on_the_device_list",
     "HYDAMD_DEVICE": "tests/test_gpu_multi_device.py::test_c_client_unchanged_runs_on_the_device_list",
     "HYDAMD_SHARD_MIN_LF_GROUPS":
