@@ -24,8 +24,9 @@
  *                   and stored once — a word that two pieces share is written byte by byte, so nothing is
  *                   zeroed beforehand and nothing is ORed
  *
- * Frames of a single group are one bit-contiguous section (encoder.c:837-850,968-981 guards): they stay
- * with the host assembler (hydamd_frame_from_blobs).
+ * Frames of a single group are one bit-contiguous section (encoder.c:837-850,968-981 guards): THIS assembler leaves
+ * them to the host (hydamd_frame_from_blobs).  Tile-mode frames, single-group ones included, are built on the device by
+ * assemble_tiles.hip, many at a time.
  */
 #include <hip/hip_runtime.h>
 

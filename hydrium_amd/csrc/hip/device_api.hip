@@ -75,6 +75,7 @@ hipError_t launch_scan(const uint32_t *group_bits, int count, uint64_t *offsets,
 hipError_t launch_pack(const uint32_t *bitbuf, uint32_t bit_pitch_words, const uint32_t *group_bits, const uint64_t *offsets,
                        uint8_t *payload, int count, const uint32_t *status, hipStream_t stream);
 size_t lf_work_bytes();
+hipError_t launch_batch_extents(const void *blob, int frames, void *extents, hipStream_t stream); /* assemble_tiles.hip */
 hipError_t launch_lf_coder(const HydkLfJob *d_jobs, unsigned long long *recs, uint32_t *hist, HydkLfStream *streams,
                            uint32_t *bits, void *work, int num_slots, hipStream_t stream);
 hipError_t launch_lf_gather(HydkLfStream *streams, const uint32_t *bits, uint32_t *packed, unsigned long long *total,
@@ -245,6 +246,8 @@ struct HydAmdContext {
     size_t stage_host_cap = 0;
     int stage_slots = 0;
     HydAmdAssembler *assembler = nullptr;
+    void *batch_extents = nullptr;   /* hydamd_export_batch_owned: [slots] HydAmdBatchExtent */
+    size_t batch_extents_cap = 0;
 
     /* profiling */
     bool profiling = false;
@@ -682,6 +685,8 @@ void hydamd_destroy(HydAmdContext *ctx) {
         hydamd_assembler_destroy(ctx->assembler);
     if (ctx->own_blob)
         (void)hipFree(ctx->own_blob);
+    if (ctx->batch_extents)
+        (void)hipFree(ctx->batch_extents);
     if (ctx->stage_blob)
         (void)hipFree(ctx->stage_blob);
     if (ctx->stage_host)
@@ -1841,12 +1846,12 @@ size_t hydamd_blob_bound(HydAmdContext *ctx, int num_slots) {
     return sizeof(HydAmdBlobHeader) + (size_t)num_slots * sizeof(HydAmdBlobSlot) + lf + 16 + ctx->payload_cap + 16;
 }
 
-static int export_frame(HydAmdContext *ctx, int num_slots, void *device_dst, size_t capacity, int view) {
+static int export_frame(HydAmdContext *ctx, int num_slots, void *device_dst, size_t capacity, int view, bool batch = false) {
     if (!ctx || !device_dst)
         return ST_API_ERROR;
     if (num_slots < 1 || num_slots > ctx->coded || num_slots != ctx->slots_finished)
         return fail(ctx, ST_API_ERROR, "export needs the entropy stage of the same slots enqueued first");
-    if (ctx->slots_per_frame)
+    if (ctx->slots_per_frame && !batch)
         return fail(ctx, ST_API_ERROR, "a batch of frames is not exported as one blob: its sections and LF streams stay in the context's buffers");
     if (ctx->lf_on_device && (ctx->lf_need_gather || ctx->lf_slots != num_slots))
         return fail(ctx, ST_API_ERROR, "export needs the frame's LF streams packed (hydamd_run_entropy does it)");
@@ -1863,7 +1868,41 @@ int hydamd_export_frame(HydAmdContext *ctx, int num_slots, void *device_dst, siz
     return export_frame(ctx, num_slots, device_dst, capacity, 0);
 }
 
+static int export_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity, bool batch);
+
 int hydamd_export_frame_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity) {
+    return export_owned(ctx, num_slots, blob_dev, capacity, false);
+}
+
+/* The results of a BATCH of one-LF-group frames (hydamd_begin_batch(ctx, 1, frames)) as a view: the slot records of all
+ * its slots behind one header, the packed LF streams and HF sections left in place — and, because frame k's bytes in
+ * those two strings follow from all frames before it, a table that states them: extents[k] = {LF offset, LF bytes, HF
+ * offset, HF bytes}, written by a kernel behind the export.  hydamd_export_frame* keeps refusing batches. */
+int hydamd_export_batch_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity, const void **extents_dev) {
+    if (!ctx || !extents_dev)
+        return ST_API_ERROR;
+    if (ctx->slots_per_frame > 1)
+        return fail(ctx, ST_API_ERROR, "the batch view is for frames of one LF group");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t need = (size_t)(num_slots > 0 ? num_slots : 1) * sizeof(HydAmdBatchExtent);
+    if (need > ctx->batch_extents_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->batch_extents)
+            (void)hipFree(ctx->batch_extents);
+        ctx->batch_extents = nullptr;
+        ctx->batch_extents_cap = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->batch_extents, need));
+        ctx->batch_extents_cap = need;
+    }
+    const int st = export_owned(ctx, num_slots, blob_dev, capacity, true);
+    if (st != ST_OK)
+        return st;
+    HIP_TRY(ctx, hydk::launch_batch_extents(*blob_dev, num_slots, ctx->batch_extents, ctx->stream));
+    *extents_dev = ctx->batch_extents;
+    return ST_OK;
+}
+
+static int export_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity, bool batch) {
     if (!ctx || !blob_dev || !capacity)
         return ST_API_ERROR;
     if (num_slots < 1 || num_slots > ctx->max_slots)
@@ -1883,7 +1922,7 @@ int hydamd_export_frame_owned(HydAmdContext *ctx, int num_slots, const void **bl
         HIP_TRY(ctx, hipMalloc(&ctx->own_blob, need));
         ctx->own_blob_cap = need;
     }
-    const int st = export_frame(ctx, num_slots, ctx->own_blob, ctx->own_blob_cap, 1);
+    const int st = export_frame(ctx, num_slots, ctx->own_blob, ctx->own_blob_cap, 1, batch);
     if (st != ST_OK)
         return st;
     *blob_dev = ctx->own_blob;

@@ -1,0 +1,289 @@
+/*
+ * hydk_tiles.h — tile-mode frames assembled many at a time: the plan the host writes, the data-dependent
+ * fields of one tile frame, where its bit strings go, and the composition of an output word.  Like
+ * hydk_sections.h the same source runs on the GPU (csrc/hip/assemble_tiles.hip: one wavefront per frame,
+ * then one thread per output word) and on the host (csrc/host/tiled.c under HYD_TEST_HOOKS: the CPU tests
+ * hold it to the host assembler, frame.c, byte for byte).  Include hydrium_amd.h first (HydAmdBlobSlot).
+ *
+ * A tile is at most 2048 x 2048 pixels: ONE LF group, one preset, nine clusters, up to 64 groups.  Two layouts
+ * (reference encoder.c:380-398 and 968-1005):
+ *   one group       frame header | TOC (one entry) | LFGlobal LFGroup HFGlobal group — one bit-contiguous section,
+ *                   padded once at its end.  Four bit strings: [LFGlobal + fixed LF head + prefix codes] (HEAD),
+ *                   the LF coefficient stream, [LF tail + HFGlobal] (MID), the group's rANS bits.
+ *   several groups  frame header with the TOC permutation | TOC | LFGlobal | LFGroup | HFGlobal | groups, each padded
+ *                   to a byte.  HEAD holds the fixed LF head + prefix codes, MID holds HFGlobal.
+ * A frame is a list of HYDK_TILE_PIECES pieces, each ONE bit string at a bit position of the output; pieces of all
+ * frames of a launch group form one sorted list and every output word is composed from the pieces that touch it.
+ */
+#ifndef HYD_TILE_LAYOUT_H_
+#define HYD_TILE_LAYOUT_H_
+
+#include <stdint.h>
+
+#include "hydk_assemble.h"
+#include "hydk_sections.h"
+
+#define HYDK_TILE_MAGIC 0x4C495448u /* "HTIL" */
+#define HYDK_TILE_MAX_SHAPES 4      /* interior, right edge, bottom edge, corner */
+#define HYDK_TILE_PIECES 8
+#define HYDK_TILE_HEAD_WORDS 704    /* LFGlobal + <= 384 x 45 bits of prefix codes + fixed fields */
+#define HYDK_TILE_MID_WORDS 3072    /* LF tail + nine histograms of <= 73 words + the cluster map */
+#define HYDK_TILE_TOC_WORDS 80      /* <= 67 entries of <= 32 bits */
+#define HYDK_TILE_CLUSTERS 9
+#define HYDK_TILE_MAX_FRAMES 255    /* frames of one launch group (= LF-group slots of a context) */
+
+typedef struct HydkTileShape {
+    uint32_t ngroups;                      /* 256 x 256 groups of the tile; 1: the bit-contiguous layout */
+    uint32_t pre_off, pre_bits;            /* what opens HEAD: (LFGlobal, one group only) + the LF group's fixed fields */
+    uint32_t lfglobal_off, lfglobal_bytes; /* the byte-padded LFGlobal section (several groups) */
+    uint32_t tail_off, tail_bits;          /* geometry-only bits that close the LF group */
+    uint32_t hfpre_off, hfpre_bits;        /* HFGlobal up to and including "ANS, not prefix codes" */
+    uint32_t pad[3];
+} HydkTileShape;
+
+typedef struct HydkTileFrame { /* one tile, raster order */
+    uint32_t prefix_off, prefix_bytes; /* (file header, tile 0) + frame header with origin, size, is_last, TOC permutation */
+    uint32_t shape, pad;
+} HydkTileFrame;
+
+typedef struct HydkTilePlan { /* header of the plan buffer; offsets in bytes from its start, 16-byte aligned */
+    uint32_t magic, total_bytes, num_frames, nshapes;
+    HydkTileShape shapes[HYDK_TILE_MAX_SHAPES];
+    uint32_t frames_off, pad[3];
+} HydkTilePlan;
+
+typedef struct HydkTileSizes { /* what the preparation of one frame leaves */
+    uint32_t head_bits, mid_bits, toc_bits, err;
+    uint64_t lfsec_bytes, hfg_bytes; /* several groups: the two padded sections */
+    uint64_t hf_bytes;               /* the frame's extent in the packed HF sections */
+    uint64_t frame_bytes;
+} HydkTileSizes;
+
+typedef struct HydkTileExtent { /* a batch's results, frame by frame: where its bytes sit in the two packed strings */
+    uint64_t lf_off, lf_bytes, hf_off, hf_bytes;
+} HydkTileExtent;
+
+typedef struct HydkTilePiece {
+    uint64_t dst_bit, nbits;
+    const uint32_t *src; /* 4-byte aligned */
+    uint32_t src_bit;    /* first bit of the string inside src[0] (a byte string that starts off a word boundary) */
+    uint32_t pad;
+} HydkTilePiece;
+
+typedef struct HydkTileScratch {
+    HydkLfHeadScratch lf;
+    uint32_t hist_bits[HYDK_TILE_CLUSTERS];
+    uint32_t err;
+} HydkTileScratch;
+
+/* `nbits` bits of the zero-padded words `src` into the sink at bit `at`, dealt over the lanes */
+#define HYDK_TILE_COPY_BITS(words, cap, at, src, nbits)                                      \
+    HKS_LANES(l) {                                                                           \
+        for (uint32_t i_ = (uint32_t)l; i_ * 32u < (nbits); i_ += 64u) {                     \
+            HydkSink sk_ = {(words), (uint64_t)(at) + (uint64_t)i_ * 32u, (cap), 0, 1};      \
+            const uint32_t left_ = (nbits) - i_ * 32u;                                       \
+            hks_put(&sk_, (src)[i_], left_ < 32u ? left_ : 32u);                             \
+            if (sk_.overflow)                                                                \
+                S->err = HYDK_ASM_E_SCRATCH;                                                 \
+        }                                                                                    \
+    }
+
+/* Called by the 64 lanes of one wavefront (device) / once (host).  head, mid and toc are zeroed arrays of
+ * HYDK_TILE_*_WORDS words; `lengths` = rec->lf.lengths (on the device a copy in LDS).  Lane 0 / the caller fills *out. */
+HYDK_HD void hydk_tile_prepare(const uint8_t *planb, const HydkTileFrame *fr, const HydkTileShape *sh, const HydAmdBlobSlot *rec,
+                               const uint8_t *lengths, uint64_t lf_capacity, uint32_t *head, uint32_t *mid, uint32_t *toc,
+                               HydkTileScratch *S, HydkTileSizes *out) {
+    const int single = sh->ngroups == 1;
+    uint32_t e = 0;
+    {
+        const uint64_t lf_end = (uint64_t)rec->lf.offset + (((uint64_t)rec->lf.bit_count + 7) >> 3);
+        if (rec->preset != 0 || rec->table_error || rec->lf.error || lf_end > lf_capacity || (rec->lf.offset & 3u) || rec->lf.alphabet < 1 ||
+            rec->lf.alphabet > HYDK_LF_RUN_BASE + 128u)
+            e |= HYDK_ASM_E_SLOT;
+        for (uint32_t g = sh->ngroups; g < HYDAMD_GROUPS_PER_LFG; g++)
+            if (rec->group_bits[g])
+                e |= HYDK_ASM_E_SIZE; /* a group the tile's geometry does not have */
+    }
+    HKS_LANES(l) {
+        if (l == 0)
+            S->err = 0;
+    }
+    HKS_SYNC();
+    if (e) {
+        HKS_LANES(l) {
+            if (l == 0) {
+                HydkTileSizes z = {0, 0, 0, 0, 0, 0, 0, 0};
+                z.err = e;
+                *out = z;
+            }
+        }
+        return;
+    }
+    /* HEAD: the constant bits, then the LF stream header's data-dependent part */
+    const uint64_t head_cap = (uint64_t)HYDK_TILE_HEAD_WORDS * 32u, mid_cap = (uint64_t)HYDK_TILE_MID_WORDS * 32u;
+    HYDK_TILE_COPY_BITS(head, head_cap, 0, (const uint32_t *)(planb + sh->pre_off), sh->pre_bits)
+    HKS_SYNC();
+    uint64_t head_end = 0;
+    const int hret = hydk_lf_prefix_codes_wave(head, head_cap, sh->pre_bits, lengths, rec->lf.alphabet, rec->lf.run_pairs, &S->lf, &head_end);
+    /* MID: (the LF group's tail, one group only), HFGlobal's fixed fields, then what the tables decide (encoder.c:959-967) */
+    const uint32_t tail_here = single ? sh->tail_bits : 0u;
+    if (single)
+        HYDK_TILE_COPY_BITS(mid, mid_cap, 0, (const uint32_t *)(planb + sh->tail_off), sh->tail_bits)
+    HYDK_TILE_COPY_BITS(mid, mid_cap, tail_here, (const uint32_t *)(planb + sh->hfpre_off), sh->hfpre_bits)
+    HKS_LANES(l) {
+        if (l < HYDK_TILE_CLUSTERS) {
+            HydkSink count = {(uint32_t *)0, 0, ~(uint64_t)0, 0, 0};
+            const uint32_t a = rec->alphabet[l] > HYDAMD_ALPHABET ? HYDAMD_ALPHABET : rec->alphabet[l];
+            hydk_put_ans_distribution(&count, rec->freq[l], a);
+            S->hist_bits[l] = (uint32_t)count.pos;
+        }
+    }
+    HKS_SYNC();
+    const uint32_t max_alpha = rec->running_max_alphabet;
+    int log_alpha = max_alpha > 1 ? hks_clog2(max_alpha) : 0;
+    log_alpha = log_alpha < 5 ? 5 : log_alpha;
+    const uint32_t cfg_bits = (uint32_t)hks_clog2(1u + (uint32_t)log_alpha) + 3u + 2u; /* split 4, msb 1, lsb 0 (encoder.c:908) */
+    const uint64_t cfg_at = (uint64_t)tail_here + sh->hfpre_bits + 2u;
+    const uint64_t hist_at = cfg_at + (uint64_t)HYDK_TILE_CLUSTERS * cfg_bits;
+    uint64_t mid_end = hist_at;
+    for (int i = 0; i < HYDK_TILE_CLUSTERS; i++)
+        mid_end += S->hist_bits[i];
+    HKS_LANES(l) {
+        if (l < HYDK_TILE_CLUSTERS && log_alpha <= 8 && mid_end <= mid_cap) {
+            HydkSink sink = {mid, cfg_at - 2u, mid_cap, 0, 1};
+            if (l == 0)
+                hks_put(&sink, (uint32_t)(log_alpha - 5), 2);
+            sink.pos = cfg_at + (uint64_t)l * cfg_bits;
+            hks_put(&sink, 4, cfg_bits - 5u);
+            hks_put(&sink, 1, 3);
+            hks_put(&sink, 0, 2);
+            uint64_t at = hist_at;
+            for (int i = 0; i < l; i++)
+                at += S->hist_bits[i];
+            sink.pos = at;
+            const uint32_t a = rec->alphabet[l] > HYDAMD_ALPHABET ? HYDAMD_ALPHABET : rec->alphabet[l];
+            hydk_put_ans_distribution(&sink, rec->freq[l], a);
+        }
+    }
+    HKS_SYNC();
+    /* sizes and the TOC (encoder.c:992-1005): a handful of entries, one lane */
+    HKS_LANES(l) {
+        if (l == 0) {
+            HydkTileSizes z = {0, 0, 0, 0, 0, 0, 0, 0};
+            z.err = S->err | (hret ? HYDK_ASM_E_HEAD : 0u) | (log_alpha > 8 || mid_end > mid_cap ? HYDK_ASM_E_SCRATCH : 0u);
+            z.head_bits = (uint32_t)head_end;
+            z.mid_bits = (uint32_t)mid_end;
+            HydkSink sink = {toc, 0, (uint64_t)HYDK_TILE_TOC_WORDS * 32u, 0, 0};
+            uint64_t v = 0, body = 0;
+            uint32_t w = 1;
+            if (single) {
+                const uint64_t bits = head_end + rec->lf.bit_count + mid_end + rec->group_bits[0];
+                body = (bits + 7) >> 3;
+                z.hf_bytes = ((uint64_t)rec->group_bits[0] + 7) >> 3;
+                w = hydk_toc_entry(body, &v);
+                hks_put64(&sink, v, w);
+            } else {
+                z.lfsec_bytes = (head_end + rec->lf.bit_count + sh->tail_bits + 7) >> 3;
+                z.hfg_bytes = (mid_end + 7) >> 3;
+                for (uint32_t i = 0; i < 3 + sh->ngroups && w; i++) {
+                    const uint64_t n = i == 0 ? sh->lfglobal_bytes : i == 1 ? z.lfsec_bytes : i == 2 ? z.hfg_bytes : ((uint64_t)rec->group_bits[i - 3] + 7) >> 3;
+                    if (i >= 3)
+                        z.hf_bytes += n;
+                    body += n;
+                    w = hydk_toc_entry(n, &v);
+                    hks_put64(&sink, v, w);
+                }
+            }
+            if (!w || sink.overflow)
+                z.err |= HYDK_ASM_E_SIZE;
+            z.toc_bits = (uint32_t)sink.pos;
+            z.frame_bytes = (uint64_t)fr->prefix_bytes + ((sink.pos + 7) >> 3) + body;
+            *out = z;
+        }
+    }
+}
+
+HYDK_HD HydkTilePiece hydk_tile_piece(uint64_t dst_bit, const void *src, uint64_t nbits) {
+    HydkTilePiece p;
+    const uintptr_t a = (uintptr_t)src;
+    p.dst_bit = dst_bit;
+    p.nbits = nbits;
+    p.src = (const uint32_t *)(a & ~(uintptr_t)3);
+    p.src_bit = (uint32_t)(a & 3u) * 8u;
+    p.pad = 0;
+    return p;
+}
+
+/* the frame's pieces, in output order, for a frame that starts at byte `at` of the output */
+HYDK_HD void hydk_tile_pieces(const uint8_t *planb, const HydkTileFrame *fr, const HydkTileShape *sh, const HydkTileSizes *z,
+                              const HydAmdBlobSlot *rec, const uint32_t *head, const uint32_t *mid, const uint32_t *toc,
+                              const uint8_t *lf_src, const uint8_t *hf_src, uint64_t at, HydkTilePiece *P) {
+    uint64_t bit = at * 8u;
+    P[0] = hydk_tile_piece(bit, planb + fr->prefix_off, (uint64_t)fr->prefix_bytes * 8u);
+    bit += (uint64_t)fr->prefix_bytes * 8u;
+    P[1] = hydk_tile_piece(bit, toc, z->toc_bits);
+    bit += (((uint64_t)z->toc_bits + 7) >> 3) * 8u;
+    if (sh->ngroups == 1) {
+        P[2] = hydk_tile_piece(bit, head, z->head_bits);
+        bit += z->head_bits;
+        P[3] = hydk_tile_piece(bit, lf_src, rec->lf.bit_count);
+        bit += rec->lf.bit_count;
+        P[4] = hydk_tile_piece(bit, mid, z->mid_bits);
+        bit += z->mid_bits;
+        P[5] = hydk_tile_piece(bit, hf_src, rec->group_bits[0]);
+        bit += rec->group_bits[0];
+        P[6] = hydk_tile_piece(bit, head, 0);
+        P[7] = hydk_tile_piece(bit, head, 0);
+        return;
+    }
+    P[2] = hydk_tile_piece(bit, planb + sh->lfglobal_off, (uint64_t)sh->lfglobal_bytes * 8u);
+    bit += (uint64_t)sh->lfglobal_bytes * 8u;
+    const uint64_t lfsec = bit;
+    P[3] = hydk_tile_piece(bit, head, z->head_bits);
+    bit += z->head_bits;
+    P[4] = hydk_tile_piece(bit, lf_src, rec->lf.bit_count);
+    bit += rec->lf.bit_count;
+    P[5] = hydk_tile_piece(bit, planb + sh->tail_off, sh->tail_bits);
+    bit = lfsec + z->lfsec_bytes * 8u;
+    P[6] = hydk_tile_piece(bit, mid, z->mid_bits);
+    bit += z->hfg_bytes * 8u;
+    P[7] = hydk_tile_piece(bit, hf_src, z->hf_bytes * 8u);
+}
+
+/* bits [q, q + 32) of a piece's string as an output word sees them; zero outside the string.  Reads no word of the
+ * source that holds none of the string's bits. */
+HYDK_HD uint32_t hydk_tile_bits(const HydkTilePiece *p, int64_t q) {
+    if (!p->nbits || q <= -32 || q >= (int64_t)p->nbits)
+        return 0;
+    const uint64_t lo = q < 0 ? 0 : (uint64_t)q;
+    const uint64_t hi = (uint64_t)(q + 32) < p->nbits ? (uint64_t)(q + 32) : p->nbits;
+    const uint32_t n = (uint32_t)(hi - lo);
+    const uint64_t a = (uint64_t)p->src_bit + lo;
+    const uint64_t i = a >> 5;
+    const uint32_t sh = (uint32_t)(a & 31u);
+    uint32_t v = p->src[i] >> sh;
+    if (sh && sh + n > 32u)
+        v |= p->src[i + 1] << (32u - sh);
+    if (n < 32u)
+        v &= (1u << n) - 1u;
+    return v << (uint32_t)((int64_t)lo - q);
+}
+
+/* output word W (bits [32 W, 32 W + 32) of the output) from a sorted piece list; ends[i] = dst_bit + nbits of piece i */
+HYDK_HD uint32_t hydk_tile_word(const HydkTilePiece *P, const uint64_t *ends, uint32_t np, uint64_t W) {
+    const uint64_t b0 = W * 32u;
+    uint32_t lo = 0, hi = np; /* the first piece that ends behind b0 */
+    while (lo < hi) {
+        const uint32_t m = (lo + hi) >> 1;
+        if (ends[m] > b0)
+            hi = m;
+        else
+            lo = m + 1;
+    }
+    uint32_t v = 0;
+    for (uint32_t i = lo; i < np && P[i].dst_bit < b0 + 32u; i++)
+        v |= hydk_tile_bits(&P[i], (int64_t)b0 - (int64_t)P[i].dst_bit);
+    return v;
+}
+
+#endif /* HYD_TILE_LAYOUT_H_ */

@@ -875,7 +875,8 @@ static int device_fail(HYDEncoder *e, int code) {
 }
 
 /* HYDAMD_HOST_ASSEMBLY=1: build frames on the host from read-back results, as round 2 did (A/B measurements, and the
- * path every frame of a single group and every tile-mode frame still takes) */
+ * path hyd_send_tile's frames of a single group and its tile-mode frames still take; device-resident tile-mode images have
+ * their frames built on the GPU: tiled.c, csrc/hip/assemble_tiles.hip) */
 static int host_assembly_forced(void) {
     static int on = -1;
     if (on < 0) {

@@ -151,6 +151,24 @@ def dll(path: Optional[str] = None):
         d.hydamd_encode_image_multi.argtypes = [vp, C.POINTER(vp), C.c_ssize_t, C.c_ssize_t, i, i]
         d.hydamd_multi_result.argtypes = [vp, C.POINTER(sz)]
         d.hydamd_multi_read.argtypes = [vp, vp, sz]
+        d.hydamd_tiled_create.restype = vp
+        d.hydamd_tiled_create.argtypes = [i, C.POINTER(api.HYDImageMetadata), i, C.POINTER(i)]
+        d.hydamd_tiled_destroy.restype = None
+        d.hydamd_tiled_destroy.argtypes = [vp]
+        d.hydamd_tiled_error.restype = C.c_char_p
+        d.hydamd_tiled_error.argtypes = [vp]
+        d.hydamd_encode_image_tiled.restype = i
+        d.hydamd_encode_image_tiled.argtypes = [vp, C.POINTER(vp), C.c_ssize_t, C.c_ssize_t, i]
+        d.hydamd_tiled_result.restype = i
+        d.hydamd_tiled_result.argtypes = [vp, C.POINTER(sz)]
+        d.hydamd_tiled_read.restype = i
+        d.hydamd_tiled_read.argtypes = [vp, C.POINTER(C.c_uint8), sz]
+        d.hydamd_tiled_device.restype = C.POINTER(C.c_uint8)
+        d.hydamd_tiled_device.argtypes = [vp]
+        d.hydamd_tiled_overflow_reruns.restype = u
+        d.hydamd_tiled_overflow_reruns.argtypes = [vp]
+        d.hydamd_tiled_device_bytes.restype = sz
+        d.hydamd_tiled_device_bytes.argtypes = [vp]
         if path is not None:
             return d
         _dll = d
@@ -685,6 +703,83 @@ class MultiFrame:
 
     def context_overflow_reruns(self, shard: int) -> int:
         return int(self.d.hydamd_overflow_reruns(self.d.hydamd_multi_context(self.h, shard)))
+
+
+class TiledImage:
+    """A tile-mode image (every tile a frame of its own) from device-resident pixels, frames built on the GPU
+    (hydamd_tiled_*, csrc/host/tiled.c): tiles coded in launch groups of up to ``tiles_per_launch`` (0: the default, 32),
+    the finished file left in device memory."""
+
+    def __init__(self, width: int, height: int, shift_x: int, shift_y: int, linear_light: int = 0, device: int = 0,
+                 tiles_per_launch: int = 0):
+        self.d = dll()
+        md = api.HYDImageMetadata(width, height, int(linear_light), shift_x, shift_y)
+        st = C.c_int(0)
+        self.h = self.d.hydamd_tiled_create(device, C.byref(md), tiles_per_launch, C.byref(st))
+        if not self.h:
+            raise DeviceError(st.value, (self.d.hydamd_tiled_error(None) or b"").decode() or "tiled image could not be created")
+        self.width, self.height = width, height
+        self._keep = None
+
+    def close(self):
+        if self.h:
+            self.d.hydamd_tiled_destroy(self.h)
+            self.h = None
+        self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _ck(self, code: int):
+        if code != 0:
+            raise DeviceError(code, (self.d.hydamd_tiled_error(self.h) or b"").decode())
+
+    def encode(self, img, row_stride: Optional[int] = None, pixel_stride: Optional[int] = None, sample_fmt: Optional[int] = None):
+        """img: an interleaved (H, W, C >= 3) torch tensor on the object's device (C > 3: the first three channels,
+        pixel stride C), three (H, W) plane tensors, or three device addresses (then the strides, in samples, and the
+        sample format are the caller's).  Asynchronous: the pixels must stay alive and unchanged until result()."""
+        if hasattr(img, "data_ptr"):
+            isz = img.element_size()
+            ptrs = [img.data_ptr() + c * isz for c in range(3)]
+            row_stride, pixel_stride = img.stride(0), img.stride(1)
+            sample_fmt = {1: 0, 2: 1, 4: 2}[isz]
+        elif hasattr(img[0], "data_ptr"):
+            isz = img[0].element_size()
+            ptrs = [p.data_ptr() for p in img]
+            row_stride, pixel_stride = img[0].stride(0), img[0].stride(1)
+            sample_fmt = {1: 0, 2: 1, 4: 2}[isz]
+        else:
+            ptrs = [int(p) if p is not None else None for p in img]
+            if row_stride is None or pixel_stride is None or sample_fmt is None:
+                raise ValueError("device addresses need row_stride, pixel_stride and sample_fmt")
+        self._keep = img
+        arr = (C.c_void_p * 3)(*ptrs)
+        self._ck(self.d.hydamd_encode_image_tiled(self.h, arr, row_stride, pixel_stride, sample_fmt))
+
+    def result(self) -> int:
+        n = C.c_size_t(0)
+        self._ck(self.d.hydamd_tiled_result(self.h, C.byref(n)))
+        self._keep = None
+        return int(n.value)
+
+    def read(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        size = self.result()
+        buf = out if out is not None and out.nbytes >= size else np.empty(size, np.uint8)
+        self._ck(self.d.hydamd_tiled_read(self.h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
+        return buf[:size]
+
+    def device_ptr(self) -> int:
+        p = self.d.hydamd_tiled_device(self.h)
+        return C.cast(p, C.c_void_p).value or 0
+
+    def overflow_reruns(self) -> int:
+        return int(self.d.hydamd_tiled_overflow_reruns(self.h))
+
+    def device_bytes(self) -> int:
+        return int(self.d.hydamd_tiled_device_bytes(self.h))
 
 
 def decode_token_records(rec: np.ndarray):

@@ -383,6 +383,17 @@ HYDAMD_EXPORT int hydamd_assembler_read(HydAmdAssembler *a, uint8_t *dst, size_t
  * with these. */
 HYDAMD_EXPORT int hydamd_export_frame_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity);
 HYDAMD_EXPORT HydAmdAssembler *hydamd_context_assembler(HydAmdContext *ctx);
+/* The results of a BATCH of one-LF-group frames (hydamd_begin_batch(ctx, 1, frames): tile-mode frames) as such a view: one
+ * header, the slot records of all `num_slots` frames, the packed LF streams and HF sections left in place.  Where frame k's
+ * bytes sit in those two strings follows from every frame before it, so the view states it: *extents_dev is a device array
+ * of num_slots HydAmdBatchExtent, written by a kernel behind the export in the context's stream.  Valid until the
+ * context's next frame.  hydamd_export_frame* keeps refusing batches. */
+typedef struct HydAmdBatchExtent {
+    uint64_t lf_offset, lf_bytes; /* in the packed LF streams (= the slot record's lf.offset, and its bit count rounded up) */
+    uint64_t hf_offset, hf_bytes; /* in the packed HF sections: the frame's byte-padded group sections, raster order */
+} HydAmdBatchExtent;
+HYDAMD_EXPORT int hydamd_export_batch_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity,
+                                            const void **extents_dev);
 
 /*
  * Wrap LF-group results — from this or other GPUs — into codestream bytes (host only, no GPU).
@@ -476,6 +487,46 @@ HYDAMD_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *s
                                             int sample_fmt, int assembling_shard);
 HYDAMD_EXPORT int hydamd_multi_result(HydAmdMulti *m, size_t *size);
 HYDAMD_EXPORT int hydamd_multi_read(HydAmdMulti *m, uint8_t *dst, size_t capacity);
+
+/*
+ * A TILE-MODE image whose pixels already sit in HBM, frames built on the GPU (csrc/host/tiled.c, csrc/hip/assemble_tiles.hip).
+ * Tile mode (both tile_size_shift_x/y 0..3: tiles of 256..2048 pixels, reference libhydrium.c:147-203) codes every tile
+ * as a Frame of its own and is the only way to code an image one frame cannot hold (more than 255 LF groups, or 128).
+ * A tile is one LF group, so the tiles are coded in LAUNCH GROUPS of up to `tiles_per_launch` independent frames
+ * (hydamd_begin_batch(ctx, 1, n)); one launch sequence behind each group's entropy stage writes its frames — header, TOC,
+ * LF group, HFGlobal, HF sections; frames of a single 256x256 group as one bit-contiguous section — back to back behind
+ * the frames of the groups before it, at a running offset kept in device memory.  The host contributes the bytes that do
+ * not depend on the pixels, once per object, and waits once per launch group (never per tile).
+ *   hydamd_tiled_create        md: the image, both shifts 0..3.  tiles_per_launch: 0 = default (32), at most 255; an
+ *                              LF-group slot of the context costs 70-100 MB whatever the tile size, so the default
+ *                              object holds about 3 GB plus the output buffer.  One device per object.
+ *   hydamd_encode_image_tiled  src / strides / sample_fmt as hydamd_encode_image's (device pointers, strides in samples),
+ *                              for the image's first pixel; tiles in raster order, edge tiles clipped as hyd_send_tile
+ *                              clips them, the file header in front of tile 0, is_last on the final tile.  Enqueues the
+ *                              first launch group and returns; the pixels stay borrowed until hydamd_tiled_result.
+ *   hydamd_tiled_result        runs the remaining launch groups and waits; *size = bytes of the finished FILE, which sits
+ *                              in device memory (hydamd_tiled_device).  A launch group that outgrew the context's buffers
+ *                              is rerun inside hydamd_sync and assembled again before the next group starts, so later
+ *                              frames land where its real sizes put them; an output buffer that proves too small is grown
+ *                              and the group's assembly repeated (never HYD_NEED_MORE_OUTPUT).  A non-finite float sample:
+ *                              HYD_API_ERROR "Invalid NaN Float"; the stream is drained and the object stays usable.
+ *   hydamd_tiled_read          the file to host memory, one copy.
+ * HYD_API_ERROR: a shift of -1, a null pointer, a bad sample format, a second encode while an image is in flight,
+ * result or read without an image.  (An ICC profile belongs to one-frame mode only, as in the reference: there is no way
+ * to pass one.)  hydamd_tiled_overflow_reruns: launch groups run twice because a buffer was too small.
+ */
+typedef struct HydAmdTiled HydAmdTiled;
+HYDAMD_EXPORT HydAmdTiled *hydamd_tiled_create(int device, const HYDImageMetadata *md, int tiles_per_launch, int *status);
+HYDAMD_EXPORT void hydamd_tiled_destroy(HydAmdTiled *t);
+HYDAMD_EXPORT const char *hydamd_tiled_error(HydAmdTiled *t);
+HYDAMD_EXPORT int hydamd_encode_image_tiled(HydAmdTiled *t, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride,
+                                            int sample_fmt);
+HYDAMD_EXPORT int hydamd_tiled_result(HydAmdTiled *t, size_t *size);
+HYDAMD_EXPORT int hydamd_tiled_read(HydAmdTiled *t, uint8_t *dst, size_t capacity);
+HYDAMD_EXPORT const uint8_t *hydamd_tiled_device(HydAmdTiled *t);
+HYDAMD_EXPORT unsigned hydamd_tiled_overflow_reruns(HydAmdTiled *t);
+/* device memory the object holds right now (context arrays are estimated from its capacities; output buffer exact) */
+HYDAMD_EXPORT size_t hydamd_tiled_device_bytes(HydAmdTiled *t);
 
 #ifdef __cplusplus
 }
