@@ -19,10 +19,12 @@
  *                     bit offset a prefix sum gives it
  *       asm_layout    whichever workgroup finishes last: TOC entries (same scheme), where every section goes, the
  *                     frame's size
- *   k_asm_copy      the frame as a list of PIECES, each the concatenation of up to three bit strings at a
- *                   byte offset; every output word is composed from its piece's strings (funnel shifts)
- *                   and stored once — a word that two pieces share is written byte by byte, so nothing is
- *                   zeroed beforehand and nothing is ORed
+ *   k_pieces_copy   the frame as a sorted list of PIECES, each one bit string at a bit position (hydk_pieces.h:
+ *                   a section is one piece, an LF group three — head, coefficient stream, geometry tail — and the
+ *                   padding that ends it the gap before the next); every output word is composed from the pieces that
+ *                   touch it and stored once, the first and last word of the range byte by byte, so nothing is
+ *                   zeroed beforehand and nothing is ORed.  The tile assembler writes its launch groups with the same
+ *                   kernel (hydk::launch_pieces_copy).
  *
  * Frames of a single group are one bit-contiguous section (encoder.c:837-850,968-981 guards): THIS assembler leaves
  * them to the host (hydamd_frame_from_blobs).  Tile-mode frames, single-group ones included, are built on the device by
@@ -31,35 +33,22 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <new>
 
 #include "../../../include/hydrium_amd.h"
-#include "hydk_assemble.h"
+#include "hydk_asm_common.h"
 #include "hydk_common.h"
-#include "hydk_sections.h"
-
-#define ST_OK 0
-#define ST_NOMEM (-13)
-#define ST_API_ERROR (-14)
-#define ST_INTERNAL_ERROR (-15)
 
 namespace {
 
 constexpr int kHeadWords = 640;         /* bits in front of an LF group's symbols: <= 384 x 45 + fixed fields */
 constexpr int kHfgWords = 40 * 1024;    /* HFGlobal: <= 256 histograms of <= 73 words + the cluster map */
 constexpr int kTocWords = 18 * 1024;    /* <= 16579 entries of <= 32 bits */
-constexpr int kMaxPieces = 8 + HYDAMD_MAX_LF_GROUPS + HYDK_ASM_MAX_BLOBS;
+constexpr int kMaxPieces = 4 + 3 * HYDAMD_MAX_LF_GROUPS + HYDK_ASM_MAX_BLOBS; /* prefix, TOC, LFGlobal, HFGlobal; three per LF group; a blob's HF bytes */
 constexpr int kCopyBlocks = 1024;
-constexpr uint32_t kBlobMagic = 0x42445948u;
-
-struct Piece {
-    uint64_t dst, nbytes;
-    const uint32_t *src[3];
-    uint64_t nbits[3];
-};
+static_assert(kMaxPieces <= HYDK_COPY_MAX_PIECES, "k_pieces_copy keeps every end in LDS");
 
 struct BlobArgs {
     const uint8_t *p[HYDK_ASM_MAX_BLOBS];
@@ -73,38 +62,19 @@ struct Scratch { /* device pointers */
     uint64_t *slot_hf;    /* [slots] bytes of each LF group's HF sections */
     uint32_t *hfg;        /* [kHfgWords] */
     uint32_t *toc;        /* [kTocWords] */
-    Piece *pieces;        /* [kMaxPieces] */
+    HydkPiece *pieces;    /* [kMaxPieces] */
     uint32_t *npieces;    /* [1] */
     uint32_t *err;        /* [1] */
     uint32_t *done;       /* [1] workgroups of k_asm_prepare that have finished their part */
-    uint64_t *result;     /* [2] size, error */
+    uint64_t *result;     /* [4] error word, 0, bytes of the frame (what k_pieces_copy reads), HFGlobal's bit count */
 };
 
-/* a blob whose two byte strings stay where the context keeps them (hydamd_export_frame_owned): header.lf_coded carries
- * this mark and header.reserved[1..4] the device addresses of the packed LF streams and of the packed HF sections */
-constexpr uint32_t kLfCodedView = 0x101u;
-__device__ __forceinline__ const uint8_t *blob_lf_bytes(const uint8_t *blob) {
-    const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    if (h->lf_coded == kLfCodedView)
-        return (const uint8_t *)(((uint64_t)h->reserved[2] << 32) | h->reserved[1]);
-    return blob + sizeof(HydAmdBlobHeader) + (uint64_t)h->num_slots * sizeof(HydAmdBlobSlot);
-}
-__device__ __forceinline__ const uint8_t *blob_hf_bytes(const uint8_t *blob) {
-    const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    if (h->lf_coded == kLfCodedView)
-        return (const uint8_t *)(((uint64_t)h->reserved[4] << 32) | h->reserved[3]);
-    return blob + (h->total_bytes - h->hf_bytes);
-}
 /* header sane and consistent with the plan?  (0, or HYDK_ASM_E_* bits; nothing behind the header is touched) */
 __device__ __forceinline__ uint32_t blob_check(const uint8_t *blob, uint64_t cap, uint32_t want_slots) {
     const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    if (cap < sizeof(HydAmdBlobHeader) || h->magic != kBlobMagic || h->version != 1 || h->num_slots != want_slots)
+    if (cap < sizeof(HydAmdBlobHeader))
         return HYDK_ASM_E_BLOB;
-    uint32_t e = 0;
-    if (h->status & HYDAMD_BLOB_RETRY)
-        e |= HYDK_ASM_E_RETRY;
-    if (h->status & 1u)
-        e |= HYDK_ASM_E_NAN;
+    const uint32_t e = blob_ident(h, want_slots);
     if (e)
         return e;
     const uint64_t lf_off = sizeof(HydAmdBlobHeader) + (uint64_t)h->num_slots * sizeof(HydAmdBlobSlot);
@@ -138,12 +108,8 @@ __device__ void asm_slot(const uint8_t *__restrict__ planb, const BlobArgs &blob
     if (!e && sl.index >= h->num_slots)
         e = HYDK_ASM_E_BLOB;
     const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + sl.index;
-    if (!e) {
-        const uint64_t lf_end = (uint64_t)rec->lf.offset + (((uint64_t)rec->lf.bit_count + 7) >> 3);
-        if (rec->preset != sl.preset || rec->table_error || rec->lf.error || lf_end > h->lf_bytes || (rec->lf.offset & 3u) ||
-            rec->lf.alphabet < 1 || rec->lf.alphabet > HYDK_LF_RUN_BASE + 128u)
-            e |= HYDK_ASM_E_SLOT;
-    }
+    if (!e)
+        e = hydk_slot_check(rec, sl.preset, h->lf_bytes);
     if (e) {
         if (t == 0) {
             atomicOr(S.err, e);
@@ -212,29 +178,6 @@ __device__ void asm_slot(const uint8_t *__restrict__ planb, const BlobArgs &blob
     }
 }
 
-/* block-wide exclusive prefix sum over 256 threads; returns the thread's offset, *total the sum */
-__device__ __forceinline__ uint64_t block_scan256(uint64_t v, uint64_t *s_wave /* [4] */, uint64_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(inc, d);
-        if (lane >= d)
-            inc += t;
-    }
-    __syncthreads(); /* s_wave may still be read from an earlier call */
-    if (lane == 63)
-        s_wave[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (int w = 0; w < 4; w++) {
-        before += w < wave ? s_wave[w] : 0;
-        all += s_wave[w];
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 __device__ __forceinline__ const HydAmdBlobSlot *slot_record(const uint8_t *planb, const BlobArgs &blobs, uint32_t s) {
     const HydkAsmPlan *plan = plan_of(planb);
     const HydkAsmSlot sl = ((const HydkAsmSlot *)(planb + plan->slots_off))[s];
@@ -281,11 +224,9 @@ __device__ void asm_hfglobal(const uint8_t *__restrict__ planb, const BlobArgs &
         nb = count.pos;
     }
     uint64_t total = 0;
-    const uint64_t off = block_scan256(nb, s_wave, &total);
-    const uint32_t max_alpha = s_max;
-    int log_alpha = max_alpha > 1 ? hks_clog2(max_alpha) : 0;
-    log_alpha = log_alpha < 5 ? 5 : log_alpha;
-    const uint32_t cfg_bits = (uint32_t)hks_clog2(1u + (uint32_t)log_alpha) + 3u + 2u; /* split 4, msb 1 in clog2(5), lsb 0 in clog2(4) bits */
+    const uint64_t off = scan256(nb, s_wave, &total);
+    int log_alpha = 0;
+    const uint32_t cfg_bits = hydk_put_hf_config(nullptr, s_max, &log_alpha);
     const uint64_t base = (uint64_t)plan->hfpre_bits + 2u + (uint64_t)C * cfg_bits;
     const uint64_t bits = base + total;
     const uint64_t words = (bits + 31) >> 5;
@@ -305,14 +246,11 @@ __device__ void asm_hfglobal(const uint8_t *__restrict__ planb, const BlobArgs &
             hks_put(&sink, pre[done >> 5], plan->hfpre_bits - done < 32 ? plan->hfpre_bits - done : 32);
         hks_put(&sink, (uint32_t)(log_alpha - 5), 2);
         S.sizes[1 + plan->num_slots] = (bits + 7) >> 3;
-        S.result[1] = bits; /* scratch use: the layout kernel reads HFGlobal's bit count from here */
+        S.result[3] = bits; /* for the layout */
     }
     if ((uint32_t)t < C) {
-        /* hybrid-uint configuration (4, 1, 0) of cluster t (encoder.c:908, entropy.c:169-182) */
         sink.pos = (uint64_t)plan->hfpre_bits + 2u + (uint64_t)t * cfg_bits;
-        hks_put(&sink, 4, cfg_bits - 5u);
-        hks_put(&sink, 1, 3);
-        hks_put(&sink, 0, 2);
+        hydk_put_hf_config(&sink, s_max, &log_alpha);
         sink.pos = base + off;
         hydk_put_ans_distribution(&sink, freq, alphabet);
     }
@@ -325,17 +263,22 @@ __device__ void asm_layout(const uint8_t *__restrict__ planb, const BlobArgs &bl
     __shared__ uint64_t s_wave[4];
     const int t = threadIdx.x;
     const uint32_t n = plan->toc_n, nslots = plan->num_slots;
-    uint32_t err = *S.err;
-    if (err) {
+    /* what the copy kernel (S.result) and the host (h_result: size, error) read */
+    auto finish = [&](uint64_t size, uint32_t e) {
         if (t == 0) {
-            S.result[0] = 0;
-            S.result[1] = err;
-            h_result[0] = 0;
-            h_result[1] = err;
+            S.result[0] = e;
+            S.result[1] = 0;
+            S.result[2] = e ? 0 : size;
+            h_result[0] = size;
+            h_result[1] = e;
         }
+    };
+    const uint32_t err = *S.err;
+    if (err) {
+        finish(0, err);
         return;
     }
-    const uint64_t hfg_bits = S.result[1];
+    const uint64_t hfg_bits = S.result[3];
     if (t == 0)
         S.sizes[0] = plan->lfglobal_bytes;
     __threadfence();
@@ -352,19 +295,12 @@ __device__ void asm_layout(const uint8_t *__restrict__ planb, const BlobArgs &bl
         mine += w;
     }
     uint64_t toc_bits = 0;
-    const uint64_t start = block_scan256(mine, s_wave, &toc_bits);
+    const uint64_t start = scan256(mine, s_wave, &toc_bits);
     const uint64_t toc_words = (toc_bits + 31) >> 5;
     if (toc_words > (uint64_t)kTocWords)
         bad |= 2;
     if (__syncthreads_or((int)bad)) {
-        if (t == 0) {
-            const uint32_t e = (bad & 2) ? HYDK_ASM_E_SCRATCH : HYDK_ASM_E_SIZE;
-            atomicOr(S.err, e);
-            S.result[0] = 0;
-            S.result[1] = e;
-            h_result[0] = 0;
-            h_result[1] = e;
-        }
+        finish(0, (bad & 2) ? HYDK_ASM_E_SCRATCH : HYDK_ASM_E_SIZE);
         return;
     }
     for (uint64_t i = t; i < toc_words; i += 256)
@@ -383,7 +319,7 @@ __device__ void asm_layout(const uint8_t *__restrict__ planb, const BlobArgs &bl
     const uint64_t body = (uint64_t)plan->prefix_bytes + toc_bytes;
     /* LF group sections: thread t owns slot t */
     uint64_t lf_mine = (uint32_t)t < nslots ? S.sizes[1 + t] : 0, lf_total = 0;
-    const uint64_t lf_off = block_scan256(lf_mine, s_wave, &lf_total);
+    const uint64_t lf_off = scan256(lf_mine, s_wave, &lf_total);
     const uint64_t lf_base = body + plan->lfglobal_bytes;
     const uint64_t hfg_dst = lf_base + lf_total, hfg_bytes = (hfg_bits + 7) >> 3;
     /* HF sections: one piece per blob, in blob order; each blob's byte count must be what its slots add up to */
@@ -398,70 +334,32 @@ __device__ void asm_layout(const uint8_t *__restrict__ planb, const BlobArgs &bl
         mismatch = sum != hf_mine;
     }
     uint64_t hf_total = 0;
-    const uint64_t hf_off = block_scan256(hf_mine, s_wave, &hf_total);
+    const uint64_t hf_off = scan256(hf_mine, s_wave, &hf_total);
     const uint64_t hf_base = hfg_dst + hfg_bytes;
     const uint64_t total = hf_base + hf_total;
-    Piece *P = S.pieces;
-    const Piece none = {0, 0, {nullptr, nullptr, nullptr}, {0, 0, 0}};
+    /* the pieces, in output order: bits, where the sections are measured in bytes */
+    HydkPiece *P = S.pieces;
     if (t == 0) {
-        Piece p = none;
-        p.dst = 0;
-        p.nbytes = plan->prefix_bytes;
-        p.src[0] = (const uint32_t *)(planb + plan->prefix_off);
-        p.nbits[0] = (uint64_t)plan->prefix_bytes * 8u;
-        P[0] = p;
-        p.dst = plan->prefix_bytes;
-        p.nbytes = toc_bytes;
-        p.src[0] = S.toc;
-        p.nbits[0] = toc_bits;
-        P[1] = p;
-        p.dst = body;
-        p.nbytes = plan->lfglobal_bytes;
-        p.src[0] = (const uint32_t *)(planb + plan->lfglobal_off);
-        p.nbits[0] = (uint64_t)plan->lfglobal_bytes * 8u;
-        P[2] = p;
-        p.dst = hfg_dst;
-        p.nbytes = hfg_bytes;
-        p.src[0] = S.hfg;
-        p.nbits[0] = hfg_bits;
-        P[3 + nslots] = p;
-        *S.npieces = 4 + nslots + plan->num_blobs;
+        P[0] = hydk_piece(0, planb + plan->prefix_off, (uint64_t)plan->prefix_bytes * 8u);
+        P[1] = hydk_piece((uint64_t)plan->prefix_bytes * 8u, S.toc, toc_bits);
+        P[2] = hydk_piece(body * 8u, planb + plan->lfglobal_off, (uint64_t)plan->lfglobal_bytes * 8u);
+        P[3 + 3 * nslots] = hydk_piece(hfg_dst * 8u, S.hfg, hfg_bits);
+        *S.npieces = 4 + 3 * nslots + plan->num_blobs;
     }
     if ((uint32_t)t < nslots) {
         const HydkAsmSlot sl = ((const HydkAsmSlot *)(planb + plan->slots_off))[t];
         const uint8_t *blob = blobs.p[sl.blob];
         const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + sl.index;
-        Piece p = none;
-        p.dst = lf_base + lf_off;
-        p.nbytes = lf_mine;
-        p.src[0] = S.head + (size_t)t * kHeadWords;
-        p.nbits[0] = S.head_bits[t];
-        p.src[1] = (const uint32_t *)(blob_lf_bytes(blob) + rec->lf.offset);
-        p.nbits[1] = rec->lf.bit_count;
-        p.src[2] = (const uint32_t *)(planb + plan->tail_off[sl.tail]);
-        p.nbits[2] = plan->tail_bits[sl.tail];
-        P[3 + t] = p;
+        const uint64_t at = (lf_base + lf_off) * 8u, head_bits = S.head_bits[t];
+        P[3 + 3 * t] = hydk_piece(at, S.head + (size_t)t * kHeadWords, head_bits);
+        P[4 + 3 * t] = hydk_piece(at + head_bits, blob_lf_bytes(blob) + rec->lf.offset, rec->lf.bit_count);
+        P[5 + 3 * t] = hydk_piece(at + head_bits + rec->lf.bit_count, planb + plan->tail_off[sl.tail], plan->tail_bits[sl.tail]);
     }
-    if ((uint32_t)t < plan->num_blobs) {
-        Piece p = none;
-        p.dst = hf_base + hf_off;
-        p.nbytes = hf_mine;
-        p.src[0] = (const uint32_t *)blob_hf_bytes(blobs.p[t]);
-        p.nbits[0] = hf_mine * 8u;
-        P[4 + nslots + t] = p;
-    }
+    if ((uint32_t)t < plan->num_blobs)
+        P[4 + 3 * nslots + t] = hydk_piece((hf_base + hf_off) * 8u, blob_hf_bytes(blobs.p[t]), hf_mine * 8u);
     const int any_mismatch = __syncthreads_or((int)mismatch);
-    if (t == 0) {
-        uint32_t e = any_mismatch ? HYDK_ASM_E_SIZE : 0u;
-        if (!e && total > out_cap)
-            e = HYDK_ASM_E_SPACE;
-        if (e)
-            atomicOr(S.err, e);
-        S.result[0] = e == HYDK_ASM_E_SPACE ? total : e ? 0 : total;
-        S.result[1] = e;
-        h_result[0] = S.result[0];
-        h_result[1] = e;
-    }
+    const uint32_t e = any_mismatch ? HYDK_ASM_E_SIZE : total > out_cap ? HYDK_ASM_E_SPACE : 0u;
+    finish(e == HYDK_ASM_E_SIZE ? 0 : total, e); /* out of space: the bytes the frame needs */
 }
 
 /* ---- k_asm_prepare: grid = LF groups + 1, block = 256.  Workgroup s < LF groups: that LF group (asm_slot); the one
@@ -493,86 +391,32 @@ __global__ __launch_bounds__(256) void k_asm_prepare(const uint8_t *__restrict__
     }
 }
 
-/* ---- k_asm_copy ---- */
-__device__ __forceinline__ uint32_t word_of(const uint32_t *w, uint64_t nbits, long long i) {
-    if (i < 0 || (uint64_t)i * 32u >= nbits)
-        return 0;
-    uint32_t v = w[i];
-    const uint64_t rem = nbits - (uint64_t)i * 32u;
-    if (rem < 32)
-        v &= (1u << rem) - 1u;
-    return v;
-}
-/* bits [q, q + 32) of a bit string of nbits bits; zero outside it */
-__device__ __forceinline__ uint32_t bits_at(const uint32_t *w, uint64_t nbits, long long q) {
-    if (!nbits || q <= -32 || q >= (long long)nbits)
-        return 0;
-    const long long i = q >> 5;
-    const uint32_t sh = (uint32_t)(q & 31);
-    const uint32_t lo = word_of(w, nbits, i);
-    if (!sh)
-        return lo;
-    const uint32_t hi = word_of(w, nbits, i + 1);
-    return (lo >> sh) | (hi << (32u - sh));
-}
-/* output word W as piece p sees it (zero where p has nothing) */
-__device__ __forceinline__ uint32_t piece_word(const Piece &p, uint64_t W) {
-    long long q = (long long)(W * 32u) - (long long)(p.dst * 8u);
-    uint32_t v = bits_at(p.src[0], p.nbits[0], q);
-    if (p.nbits[1]) {
-        q -= (long long)p.nbits[0];
-        v |= bits_at(p.src[1], p.nbits[1], q);
-    } else {
-        q -= (long long)p.nbits[0];
-    }
-    if (p.nbits[2]) {
-        q -= (long long)p.nbits[1];
-        v |= bits_at(p.src[2], p.nbits[2], q);
-    }
-    return v;
-}
-
-__global__ __launch_bounds__(256) void k_asm_copy(Scratch S, uint8_t *__restrict__ out) {
-    __shared__ uint64_t s_start[kMaxPieces];
-    __shared__ uint64_t s_end[kMaxPieces];
-    const uint64_t total = S.result[0];
-    if (!total || S.result[1])
+/* ---- k_pieces_copy: any grid, block = 256.  Word W of the range belongs to thread W mod (grid x 256) ---- */
+__global__ __launch_bounds__(256) void k_pieces_copy(const HydkPiece *__restrict__ P, uint32_t np, const uint32_t *__restrict__ np_dev,
+                                                     const uint64_t *__restrict__ range, uint8_t *__restrict__ out) {
+    __shared__ uint64_t s_end[HYDK_COPY_MAX_PIECES];
+    if (range[0] || !range[2])
         return;
-    const uint32_t np = *S.npieces;
-    for (uint32_t i = threadIdx.x; i < np; i += 256) {
-        s_start[i] = S.pieces[i].dst;
-        s_end[i] = S.pieces[i].dst + S.pieces[i].nbytes;
-    }
+    const uint64_t b_lo = range[1], b_hi = b_lo + range[2]; /* bytes [b_lo, b_hi) are this launch's */
+    if (np_dev)
+        np = *np_dev;
+    np = min(np, (uint32_t)HYDK_COPY_MAX_PIECES);
+    for (uint32_t i = threadIdx.x; i < np; i += 256)
+        s_end[i] = P[i].dst_bit + P[i].nbits;
     __syncthreads();
-    auto find = [&](uint64_t byte) { /* the last piece that starts at or before `byte`: empty pieces sort in front of their successor */
-        uint32_t lo = 0, hi = np - 1;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1) >> 1;
-            if (s_start[mid] <= byte)
-                lo = mid;
-            else
-                hi = mid - 1;
-        }
-        return lo;
-    };
-    const uint64_t words = (total + 3) >> 2;
-    uint32_t *out32 = (uint32_t *)out;
-    for (uint64_t W = (uint64_t)blockIdx.x * 256u + threadIdx.x; W < words; W += (uint64_t)gridDim.x * 256u) {
-        const uint64_t b0 = W * 4u;
-        const uint32_t pi = find(b0);
-        if (b0 + 4 <= s_end[pi]) {
-            out32[W] = piece_word(S.pieces[pi], W);
-            continue;
-        }
-        /* a word that several sections share, or the frame's last: byte by byte, each from its own piece */
-        for (uint32_t j = 0; j < 4 && b0 + j < total; j++) {
-            const uint32_t pj = find(b0 + j);
-            out[b0 + j] = (uint8_t)(piece_word(S.pieces[pj], W) >> (8u * j));
-        }
-    }
+    const uint64_t w_lo = b_lo >> 2, w_hi = (b_hi + 3) >> 2;
+    for (uint64_t W = w_lo + (uint64_t)blockIdx.x * 256u + threadIdx.x; W < w_hi; W += (uint64_t)gridDim.x * 256u)
+        hydk_store_word(out, W, hydk_pieces_word(P, s_end, np, W), b_lo, b_hi);
 }
 
 } // namespace
+
+namespace hydk {
+hipError_t launch_pieces_copy(const HydkPiece *P, uint32_t np, const uint32_t *np_dev, const uint64_t *range, void *out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_pieces_copy, dim3(kCopyBlocks), dim3(256), 0, stream, P, np, np_dev, range, (uint8_t *)out);
+    return hipGetLastError();
+}
+} // namespace hydk
 
 extern "C" void hydamd_host_copy(void *dst, const void *src, size_t n); /* device_api.hip */
 
@@ -596,24 +440,6 @@ struct HydkAsm {
     uint8_t *bounce = nullptr;    /* pinned: hydk_asm_read lands frames here (DMA engines), then copies to the caller's memory */
     size_t bounce_cap = 0;
 };
-
-namespace {
-int afail(HydkAsm *a, int code, const char *what, hipError_t e = hipSuccess) {
-    if (a) {
-        if (e != hipSuccess)
-            snprintf(a->error, sizeof(a->error), "%s: %s", what, hipGetErrorString(e));
-        else
-            snprintf(a->error, sizeof(a->error), "%s", what);
-    }
-    return code;
-}
-#define ASM_TRY(a, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e__ = (call);                                                                      \
-        if (e__ != hipSuccess)                                                                        \
-            return afail(a, e__ == hipErrorOutOfMemory ? ST_NOMEM : ST_INTERNAL_ERROR, #call, e__);   \
-    } while (0)
-} // namespace
 
 extern "C" {
 
@@ -640,27 +466,27 @@ void hydk_asm_destroy(HydkAsm *a) {
 static int asm_alloc(HydkAsm *a) {
     const size_t slots = HYDAMD_MAX_LF_GROUPS;
     const size_t toc_max = 2 + slots + slots * HYDK_GROUPS_PER_LFG;
-    ASM_TRY(a, hipSetDevice(a->device));
-    ASM_TRY(a, hipMalloc(&a->S.head, slots * kHeadWords * sizeof(uint32_t)));
-    ASM_TRY(a, hipMalloc(&a->S.head_bits, slots * sizeof(uint32_t)));
-    ASM_TRY(a, hipMalloc(&a->S.sizes, toc_max * sizeof(uint64_t)));
-    ASM_TRY(a, hipMalloc(&a->S.slot_hf, slots * sizeof(uint64_t)));
-    ASM_TRY(a, hipMalloc(&a->S.hfg, (size_t)kHfgWords * sizeof(uint32_t)));
-    ASM_TRY(a, hipMalloc(&a->S.toc, (size_t)kTocWords * sizeof(uint32_t)));
-    ASM_TRY(a, hipMalloc(&a->S.pieces, (size_t)kMaxPieces * sizeof(Piece)));
-    ASM_TRY(a, hipMalloc(&a->S.npieces, sizeof(uint32_t)));
-    ASM_TRY(a, hipMalloc(&a->S.err, sizeof(uint32_t)));
-    ASM_TRY(a, hipMalloc(&a->S.done, sizeof(uint32_t)));
-    ASM_TRY(a, hipMemset(a->S.err, 0, sizeof(uint32_t)));
-    ASM_TRY(a, hipMemset(a->S.done, 0, sizeof(uint32_t)));
+    HYDK_TRY(a, hipSetDevice(a->device));
+    HYDK_TRY(a, hipMalloc(&a->S.head, slots * kHeadWords * sizeof(uint32_t)));
+    HYDK_TRY(a, hipMalloc(&a->S.head_bits, slots * sizeof(uint32_t)));
+    HYDK_TRY(a, hipMalloc(&a->S.sizes, toc_max * sizeof(uint64_t)));
+    HYDK_TRY(a, hipMalloc(&a->S.slot_hf, slots * sizeof(uint64_t)));
+    HYDK_TRY(a, hipMalloc(&a->S.hfg, (size_t)kHfgWords * sizeof(uint32_t)));
+    HYDK_TRY(a, hipMalloc(&a->S.toc, (size_t)kTocWords * sizeof(uint32_t)));
+    HYDK_TRY(a, hipMalloc(&a->S.pieces, (size_t)kMaxPieces * sizeof(HydkPiece)));
+    HYDK_TRY(a, hipMalloc(&a->S.npieces, sizeof(uint32_t)));
+    HYDK_TRY(a, hipMalloc(&a->S.err, sizeof(uint32_t)));
+    HYDK_TRY(a, hipMalloc(&a->S.done, sizeof(uint32_t)));
+    HYDK_TRY(a, hipMemset(a->S.err, 0, sizeof(uint32_t)));
+    HYDK_TRY(a, hipMemset(a->S.done, 0, sizeof(uint32_t)));
     /* hipMemset of device memory returns before it has run, in the NULL stream, which non-blocking streams do not wait
      * for: without this wait the first frame's kernels can pass the memsets (seen as a "malformed blob" once the
      * caller's stream and the null stream sat on different hardware queues) */
-    ASM_TRY(a, hipStreamSynchronize(nullptr));
-    ASM_TRY(a, hipMalloc(&a->S.result, 2 * sizeof(uint64_t)));
-    ASM_TRY(a, hipHostMalloc((void **)&a->h_result, 2 * sizeof(uint64_t), hipHostMallocDefault));
+    HYDK_TRY(a, hipStreamSynchronize(nullptr));
+    HYDK_TRY(a, hipMalloc(&a->S.result, 4 * sizeof(uint64_t)));
+    HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, 2 * sizeof(uint64_t), hipHostMallocDefault));
     a->h_result[0] = a->h_result[1] = 0;
-    ASM_TRY(a, hipEventCreateWithFlags(&a->done, hipEventDisableTiming));
+    HYDK_TRY(a, hipEventCreateWithFlags(&a->done, hipEventDisableTiming));
     return ST_OK;
 }
 
@@ -686,32 +512,32 @@ int hydk_asm_create(int device, HydkAsm **out) {
 
 int hydk_asm_set_plan(HydkAsm *a, const void *plan, size_t bytes) {
     if (!a || !plan || bytes < sizeof(HydkAsmPlan))
-        return afail(a, ST_API_ERROR, "bad plan");
+        return hydk_fail(a, ST_API_ERROR, "bad plan");
     const HydkAsmPlan *hp = (const HydkAsmPlan *)plan;
     if (hp->magic != HYDK_ASM_PLAN_MAGIC || hp->total_bytes != bytes || hp->num_slots < 1 || hp->num_slots > HYDAMD_MAX_LF_GROUPS ||
         hp->num_blobs < 1 || hp->num_blobs > HYDK_ASM_MAX_BLOBS || hp->num_presets * hp->clusters_per_preset > 256 ||
         hp->toc_n != 2 + hp->num_slots + hp->frame_groups || hp->ntails > HYDK_ASM_MAX_TAILS)
-        return afail(a, ST_API_ERROR, "inconsistent plan");
-    ASM_TRY(a, hipSetDevice(a->device));
+        return hydk_fail(a, ST_API_ERROR, "inconsistent plan");
+    HYDK_TRY(a, hipSetDevice(a->device));
     /* an earlier frame may still be reading the old plan: wait for IT only (a device-wide wait would stall every other
      * encoder thread's frames in a batch of differently shaped images) — by the assembler's own event, not by the caller's
      * stream handle, which may be gone by now; runs in different streams are chained behind each other (hydk_asm_run), so
      * the last run's event covers them all */
     if (a->unsettled) { /* kernels of a run that failed half-way may still be reading the old plan and scratch arrays */
-        ASM_TRY(a, hipDeviceSynchronize());
+        HYDK_TRY(a, hipDeviceSynchronize());
         a->unsettled = false;
     }
     if (a->ran)
-        ASM_TRY(a, hipEventSynchronize(a->done));
+        HYDK_TRY(a, hipEventSynchronize(a->done));
     if (bytes > a->plan_cap) {
         if (a->plan)
             (void)hipFree(a->plan);
         a->plan = nullptr;
         a->plan_cap = 0;
-        ASM_TRY(a, hipMalloc(&a->plan, bytes + 16)); /* + 16: the copy kernel reads whole words */
+        HYDK_TRY(a, hipMalloc(&a->plan, bytes + 16)); /* + 16: the copy kernel reads whole words */
         a->plan_cap = bytes;
     }
-    ASM_TRY(a, hipMemcpy(a->plan, plan, bytes, hipMemcpyHostToDevice));
+    HYDK_TRY(a, hipMemcpy(a->plan, plan, bytes, hipMemcpyHostToDevice));
     a->hplan = *hp;
     a->have_plan = true;
     return ST_OK;
@@ -719,8 +545,8 @@ int hydk_asm_set_plan(HydkAsm *a, const void *plan, size_t bytes) {
 
 int hydk_asm_run(HydkAsm *a, const void *const *blobs, const uint64_t *blob_caps, void *stream, void *out, uint64_t out_cap) {
     if (!a || !a->have_plan || !blobs || !blob_caps)
-        return afail(a, ST_API_ERROR, "assembler not ready");
-    ASM_TRY(a, hipSetDevice(a->device));
+        return hydk_fail(a, ST_API_ERROR, "assembler not ready");
+    HYDK_TRY(a, hipSetDevice(a->device));
     hipStream_t st = (hipStream_t)stream;
     if (!out) { /* the assembler's own device buffer: `out_cap` bytes if the caller names a size, else what the blobs could hold
                  * (no frame is larger than its self-contained blobs plus its headers; views need a size from the caller) */
@@ -731,26 +557,26 @@ int hydk_asm_run(HydkAsm *a, const void *const *blobs, const uint64_t *blob_caps
                 need += (size_t)blob_caps[b];
         }
         if (need > a->own_cap) {
-            ASM_TRY(a, hipStreamSynchronize(st));
+            HYDK_TRY(a, hipStreamSynchronize(st));
             if (a->own_out)
                 (void)hipFree(a->own_out);
             a->own_out = nullptr;
             a->own_cap = 0;
-            ASM_TRY(a, hipMalloc(&a->own_out, need));
+            HYDK_TRY(a, hipMalloc(&a->own_out, need));
             a->own_cap = need;
         }
         out = a->own_out;
         out_cap = a->own_cap;
     }
-    /* k_asm_copy moves whole 32-bit words of the output and 16-byte-aligned records of the blobs */
+    /* k_pieces_copy moves whole 32-bit words of the output and 16-byte-aligned records of the blobs */
     if ((uintptr_t)out & 3u)
-        return afail(a, ST_API_ERROR, "output buffer must be 4-byte aligned");
+        return hydk_fail(a, ST_API_ERROR, "output buffer must be 4-byte aligned");
     if (a->unsettled) { /* the last run failed half-way: nothing says when its kernels are done with the scratch arrays */
-        ASM_TRY(a, hipDeviceSynchronize());
+        HYDK_TRY(a, hipDeviceSynchronize());
         a->unsettled = false;
     }
     if (a->ran && st != a->last_stream) /* the runs share the assembler's scratch arrays: one behind the other */
-        ASM_TRY(a, hipStreamWaitEvent(st, a->done, 0));
+        HYDK_TRY(a, hipStreamWaitEvent(st, a->done, 0));
     a->last_out = (uint8_t *)out;
     a->last_cap = out_cap;
     a->last_stream = st;
@@ -759,17 +585,16 @@ int hydk_asm_run(HydkAsm *a, const void *const *blobs, const uint64_t *blob_caps
     memset(&args, 0, sizeof(args));
     for (uint32_t b = 0; b < a->hplan.num_blobs; b++) {
         if (!blobs[b])
-            return afail(a, ST_API_ERROR, "null blob");
+            return hydk_fail(a, ST_API_ERROR, "null blob");
         if ((uintptr_t)blobs[b] & 15u)
-            return afail(a, ST_API_ERROR, "blobs must be 16-byte aligned");
+            return hydk_fail(a, ST_API_ERROR, "blobs must be 16-byte aligned");
         args.p[b] = (const uint8_t *)blobs[b];
         args.cap[b] = blob_caps[b];
     }
     hipLaunchKernelGGL(k_asm_prepare, dim3(a->hplan.num_slots + 1), dim3(256), 0, st, (const uint8_t *)a->plan, args, a->S, out_cap,
                        a->h_result);
-    hipLaunchKernelGGL(k_asm_copy, dim3(kCopyBlocks), dim3(256), 0, st, a->S, (uint8_t *)out);
-    ASM_TRY(a, hipGetLastError());
-    ASM_TRY(a, hipEventRecord(a->done, st));
+    HYDK_TRY(a, hydk::launch_pieces_copy(a->S.pieces, 0, a->S.npieces, a->S.result, out, st));
+    HYDK_TRY(a, hipEventRecord(a->done, st));
     a->ran = true;
     a->unsettled = false;
     return ST_OK;
@@ -791,14 +616,14 @@ int hydk_asm_result(HydkAsm *a, uint64_t *size, uint32_t *err) {
  * of the length rounded up to 256 bytes into a pinned buffer of the assembler's (56 GB/s), then the staging threads' memcpy */
 int hydk_asm_read(HydkAsm *a, uint8_t *dst, size_t capacity) {
     if (!a || !dst || !a->last_out)
-        return afail(a, ST_API_ERROR, "nothing to read");
+        return hydk_fail(a, ST_API_ERROR, "nothing to read");
     if (a->h_result[1] || !a->h_result[0] || a->h_result[0] > capacity)
-        return afail(a, ST_API_ERROR, "no finished frame of that size");
-    ASM_TRY(a, hipSetDevice(a->device));
+        return hydk_fail(a, ST_API_ERROR, "no finished frame of that size");
+    HYDK_TRY(a, hipSetDevice(a->device));
     const size_t n = (size_t)a->h_result[0];
     const size_t padded = (n + 255) & ~(size_t)255;
     if (n < ((size_t)1 << 20) || padded > a->last_cap) { /* small, or no room to round up: the runtime's own path */
-        ASM_TRY(a, hipMemcpy(dst, a->last_out, n, hipMemcpyDeviceToHost));
+        HYDK_TRY(a, hipMemcpy(dst, a->last_out, n, hipMemcpyDeviceToHost));
         return ST_OK;
     }
     if (padded > a->bounce_cap) {
@@ -807,11 +632,11 @@ int hydk_asm_read(HydkAsm *a, uint8_t *dst, size_t capacity) {
         a->bounce = nullptr;
         a->bounce_cap = 0;
         const size_t want = padded + (padded >> 2);
-        ASM_TRY(a, hipHostMalloc((void **)&a->bounce, want, hipHostMallocDefault));
+        HYDK_TRY(a, hipHostMalloc((void **)&a->bounce, want, hipHostMallocDefault));
         a->bounce_cap = want;
     }
-    ASM_TRY(a, hipMemcpyAsync(a->bounce, a->last_out, padded, hipMemcpyDeviceToHost, a->last_stream));
-    ASM_TRY(a, hipStreamSynchronize(a->last_stream));
+    HYDK_TRY(a, hipMemcpyAsync(a->bounce, a->last_out, padded, hipMemcpyDeviceToHost, a->last_stream));
+    HYDK_TRY(a, hipStreamSynchronize(a->last_stream));
     hydamd_host_copy(dst, a->bounce, n);
     return ST_OK;
 }
@@ -820,20 +645,20 @@ int hydk_asm_debug(HydkAsm *a, uint32_t slot, uint32_t *head_bits, uint32_t *hea
                    uint32_t *hfg_words, size_t hfg_cap) {
     if (!a || slot >= HYDAMD_MAX_LF_GROUPS)
         return ST_API_ERROR;
-    ASM_TRY(a, hipSetDevice(a->device));
-    ASM_TRY(a, hipDeviceSynchronize());
+    HYDK_TRY(a, hipSetDevice(a->device));
+    HYDK_TRY(a, hipDeviceSynchronize());
     if (head_bits)
-        ASM_TRY(a, hipMemcpy(head_bits, a->S.head_bits + slot, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HYDK_TRY(a, hipMemcpy(head_bits, a->S.head_bits + slot, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (head_words)
-        ASM_TRY(a, hipMemcpy(head_words, a->S.head + (size_t)slot * kHeadWords,
+        HYDK_TRY(a, hipMemcpy(head_words, a->S.head + (size_t)slot * kHeadWords,
                              (head_cap < (size_t)kHeadWords ? head_cap : (size_t)kHeadWords) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (hfg_bits) {
         uint64_t sz = 0;
-        ASM_TRY(a, hipMemcpy(&sz, a->S.sizes + 1 + a->hplan.num_slots, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HYDK_TRY(a, hipMemcpy(&sz, a->S.sizes + 1 + a->hplan.num_slots, sizeof(uint64_t), hipMemcpyDeviceToHost));
         *hfg_bits = (uint32_t)(sz * 8u);
     }
     if (hfg_words)
-        ASM_TRY(a, hipMemcpy(hfg_words, a->S.hfg, (hfg_cap < (size_t)kHfgWords ? hfg_cap : (size_t)kHfgWords) * sizeof(uint32_t),
+        HYDK_TRY(a, hipMemcpy(hfg_words, a->S.hfg, (hfg_cap < (size_t)kHfgWords ? hfg_cap : (size_t)kHfgWords) * sizeof(uint32_t),
                              hipMemcpyDeviceToHost));
     return ST_OK;
 }

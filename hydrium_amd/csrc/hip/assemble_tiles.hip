@@ -13,9 +13,10 @@
  *   k_tiles_layout   one workgroup: prefix sums over the frames' sizes and over their extents in the packed strings;
  *                    the group starts at the running offset kept in device memory, which it advances — only when the
  *                    group is complete (no buffer of the context outgrown, no NaN) and fits the output
- *   k_tiles_copy     every output word composed from the pieces that touch it and stored once; the words the group
- *                    shares with its neighbours (first and last) are written byte by byte.  Nothing is zeroed
- *                    beforehand, nothing is ORed into memory.
+ *   k_pieces_copy    (assemble.hip, shared with the frame assembler) every output word composed from the pieces
+ *                    that touch it (hydk_pieces.h) and stored once; the words the group shares with its neighbours
+ *                    (first and last) are written byte by byte.  Nothing is zeroed beforehand, nothing is ORed into
+ *                    memory.
  *
  * Frames of one group take the same path as all others: their single section is four bit strings at bit positions
  * that depend on the pixels (hydk_tiles.h).  The host contributes the plan (csrc/host/tiled.c), once per image shape.
@@ -23,7 +24,6 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <new>
@@ -31,70 +31,26 @@
 #include "../../../include/hydrium_amd.h"
 #include "hydk_tiles.h"
 
-#define ST_OK 0
-#define ST_NOMEM (-13)
-#define ST_API_ERROR (-14)
-#define ST_INTERNAL_ERROR (-15)
-
 namespace {
 
-constexpr uint32_t kBlobMagic = 0x42445948u;
-constexpr uint32_t kLfCodedView = 0x101u;
-constexpr int kCopyBlocks = 1024;
-constexpr int kMaxPieces = HYDK_TILE_MAX_FRAMES * HYDK_TILE_PIECES;
+static_assert(HYDK_TILE_MAX_FRAMES * HYDK_TILE_PIECES <= HYDK_COPY_MAX_PIECES, "k_pieces_copy keeps every end in LDS");
 
 struct TileScratch { /* device pointers */
     uint32_t *head;         /* [frames][HYDK_TILE_HEAD_WORDS] */
     uint32_t *mid;          /* [frames][HYDK_TILE_MID_WORDS] */
     uint32_t *toc;          /* [frames][HYDK_TILE_TOC_WORDS] */
     HydkTileSizes *sizes;   /* [frames] */
-    HydkTilePiece *pieces;  /* [frames][HYDK_TILE_PIECES] */
+    HydkPiece *pieces;  /* [frames][HYDK_TILE_PIECES] */
     uint64_t *cursor;       /* [1] bytes of the file written by the launch groups so far */
-    uint64_t *result;       /* [4] error word, first byte of this group, bytes behind it, bytes the output must hold */
+    uint64_t *result;       /* [4] error word, first byte of this group, bytes behind it (what k_pieces_copy reads), bytes the output must hold */
 };
 
+/* the tile assembler follows views only (hydamd_export_batch_owned) */
 __device__ __forceinline__ uint32_t view_check(const uint8_t *blob, uint32_t frames) {
     const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    if (h->magic != kBlobMagic || h->version != 1 || h->num_slots != frames || h->lf_coded != kLfCodedView ||
-        !(h->reserved[1] | h->reserved[2]) || !(h->reserved[3] | h->reserved[4]) || (h->reserved[1] & 3u))
+    if (h->lf_coded != kLfCodedView || !(h->reserved[1] | h->reserved[2]) || !(h->reserved[3] | h->reserved[4]) || (h->reserved[1] & 3u))
         return HYDK_ASM_E_BLOB;
-    uint32_t e = 0;
-    if (h->status & HYDAMD_BLOB_RETRY)
-        e |= HYDK_ASM_E_RETRY;
-    if (h->status & 1u)
-        e |= HYDK_ASM_E_NAN;
-    return e;
-}
-__device__ __forceinline__ const uint8_t *view_lf(const uint8_t *blob) {
-    const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    return (const uint8_t *)(((uint64_t)h->reserved[2] << 32) | h->reserved[1]);
-}
-__device__ __forceinline__ const uint8_t *view_hf(const uint8_t *blob) {
-    const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    return (const uint8_t *)(((uint64_t)h->reserved[4] << 32) | h->reserved[3]);
-}
-
-/* block-wide exclusive prefix sum over 256 threads; returns the thread's offset, *total the sum */
-__device__ __forceinline__ uint64_t scan256(uint64_t v, uint64_t *s_wave /* [4] */, uint64_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(inc, d);
-        if (lane >= d)
-            inc += t;
-    }
-    __syncthreads();
-    if (lane == 63)
-        s_wave[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (int w = 0; w < 4; w++) {
-        before += w < wave ? s_wave[w] : 0;
-        all += s_wave[w];
-    }
-    *total = all;
-    return before + inc - v;
+    return blob_ident(h, frames);
 }
 
 /* ---- a batch's results, frame by frame: grid 1, block 256 ---- */
@@ -198,8 +154,8 @@ __global__ __launch_bounds__(256) void k_tiles_layout(const uint8_t *__restrict_
         const HydkTileFrame fr = ((const HydkTileFrame *)(planb + plan->frames_off))[first_frame + t];
         const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + t;
         hydk_tile_pieces(planb, &fr, &plan->shapes[fr.shape], &z, rec, S.head + (size_t)t * HYDK_TILE_HEAD_WORDS,
-                         S.mid + (size_t)t * HYDK_TILE_MID_WORDS, S.toc + (size_t)t * HYDK_TILE_TOC_WORDS, view_lf(blob) + ext[t].lf_off,
-                         view_hf(blob) + ext[t].hf_off, start + at, S.pieces + (size_t)t * HYDK_TILE_PIECES);
+                         S.mid + (size_t)t * HYDK_TILE_MID_WORDS, S.toc + (size_t)t * HYDK_TILE_TOC_WORDS, blob_lf_bytes(blob) + ext[t].lf_off,
+                         blob_hf_bytes(blob) + ext[t].hf_off, start + at, S.pieces + (size_t)t * HYDK_TILE_PIECES);
     }
     if (t == 0) {
         S.result[0] = fin;
@@ -210,31 +166,6 @@ __global__ __launch_bounds__(256) void k_tiles_layout(const uint8_t *__restrict_
             *S.cursor = start + total;
         for (int i = 0; i < 4; i++)
             h_result[i] = S.result[i];
-    }
-}
-
-/* ---- k_tiles_copy ---- */
-__global__ __launch_bounds__(256) void k_tiles_copy(TileScratch S, uint32_t frames, uint8_t *__restrict__ out) {
-    __shared__ uint64_t s_end[kMaxPieces];
-    if (S.result[0] || !S.result[2])
-        return;
-    const uint64_t b_lo = S.result[1], b_hi = b_lo + S.result[2]; /* bytes [b_lo, b_hi) are this group's */
-    const uint32_t np = frames * HYDK_TILE_PIECES;
-    for (uint32_t i = threadIdx.x; i < np; i += 256)
-        s_end[i] = S.pieces[i].dst_bit + S.pieces[i].nbits;
-    __syncthreads();
-    uint32_t *out32 = (uint32_t *)out;
-    const uint64_t w_lo = b_lo >> 2, w_hi = (b_hi + 3) >> 2;
-    for (uint64_t W = w_lo + (uint64_t)blockIdx.x * 256u + threadIdx.x; W < w_hi; W += (uint64_t)gridDim.x * 256u) {
-        const uint32_t v = hydk_tile_word(S.pieces, s_end, np, W);
-        const uint64_t b0 = W * 4u;
-        if (b0 >= b_lo && b0 + 4 <= b_hi) {
-            out32[W] = v;
-            continue;
-        }
-        for (uint32_t j = 0; j < 4; j++) /* a word shared with the launch group in front, or the file's last */
-            if (b0 + j >= b_lo && b0 + j < b_hi)
-                out[b0 + j] = (uint8_t)(v >> (8u * j));
     }
 }
 
@@ -257,24 +188,6 @@ struct HydkTileAsm {
     uint8_t *out = nullptr;       /* the file: owned, grown on demand (hydk_tiles_reserve) */
     uint64_t out_cap = 0;
 };
-
-namespace {
-int tfail(HydkTileAsm *a, int code, const char *what, hipError_t e = hipSuccess) {
-    if (a) {
-        if (e != hipSuccess)
-            snprintf(a->error, sizeof(a->error), "%s: %s", what, hipGetErrorString(e));
-        else
-            snprintf(a->error, sizeof(a->error), "%s", what);
-    }
-    return code;
-}
-#define TILE_TRY(a, call)                                                                             \
-    do {                                                                                              \
-        hipError_t e__ = (call);                                                                      \
-        if (e__ != hipSuccess)                                                                        \
-            return tfail(a, e__ == hipErrorOutOfMemory ? ST_NOMEM : ST_INTERNAL_ERROR, #call, e__);   \
-    } while (0)
-} // namespace
 
 extern "C" {
 
@@ -309,19 +222,19 @@ int hydk_tiles_create(int device, int max_frames, const void *plan, size_t plan_
     a->plan_frames = hp->num_frames;
     const size_t n = (size_t)max_frames;
     auto alloc = [&]() -> int {
-        TILE_TRY(a, hipSetDevice(device));
-        TILE_TRY(a, hipMalloc(&a->plan, plan_bytes + 16)); /* + 16: the copy kernel reads whole words */
-        TILE_TRY(a, hipMemcpy(a->plan, plan, plan_bytes, hipMemcpyHostToDevice));
-        TILE_TRY(a, hipMalloc(&a->S.head, n * HYDK_TILE_HEAD_WORDS * sizeof(uint32_t)));
-        TILE_TRY(a, hipMalloc(&a->S.mid, n * HYDK_TILE_MID_WORDS * sizeof(uint32_t)));
-        TILE_TRY(a, hipMalloc(&a->S.toc, n * HYDK_TILE_TOC_WORDS * sizeof(uint32_t)));
-        TILE_TRY(a, hipMalloc(&a->S.sizes, n * sizeof(HydkTileSizes)));
-        TILE_TRY(a, hipMalloc(&a->S.pieces, n * HYDK_TILE_PIECES * sizeof(HydkTilePiece)));
-        TILE_TRY(a, hipMalloc(&a->S.cursor, sizeof(uint64_t)));
-        TILE_TRY(a, hipMalloc(&a->S.result, 4 * sizeof(uint64_t)));
-        TILE_TRY(a, hipMemset(a->S.cursor, 0, sizeof(uint64_t)));
-        TILE_TRY(a, hipStreamSynchronize(nullptr)); /* the memset runs in the NULL stream, which the context's stream does not wait for */
-        TILE_TRY(a, hipHostMalloc((void **)&a->h_result, 4 * sizeof(uint64_t), hipHostMallocDefault));
+        HYDK_TRY(a, hipSetDevice(device));
+        HYDK_TRY(a, hipMalloc(&a->plan, plan_bytes + 16)); /* + 16: the copy kernel reads whole words */
+        HYDK_TRY(a, hipMemcpy(a->plan, plan, plan_bytes, hipMemcpyHostToDevice));
+        HYDK_TRY(a, hipMalloc(&a->S.head, n * HYDK_TILE_HEAD_WORDS * sizeof(uint32_t)));
+        HYDK_TRY(a, hipMalloc(&a->S.mid, n * HYDK_TILE_MID_WORDS * sizeof(uint32_t)));
+        HYDK_TRY(a, hipMalloc(&a->S.toc, n * HYDK_TILE_TOC_WORDS * sizeof(uint32_t)));
+        HYDK_TRY(a, hipMalloc(&a->S.sizes, n * sizeof(HydkTileSizes)));
+        HYDK_TRY(a, hipMalloc(&a->S.pieces, n * HYDK_TILE_PIECES * sizeof(HydkPiece)));
+        HYDK_TRY(a, hipMalloc(&a->S.cursor, sizeof(uint64_t)));
+        HYDK_TRY(a, hipMalloc(&a->S.result, 4 * sizeof(uint64_t)));
+        HYDK_TRY(a, hipMemset(a->S.cursor, 0, sizeof(uint64_t)));
+        HYDK_TRY(a, hipStreamSynchronize(nullptr)); /* the memset runs in the NULL stream, which the context's stream does not wait for */
+        HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, 4 * sizeof(uint64_t), hipHostMallocDefault));
         memset(a->h_result, 0, 4 * sizeof(uint64_t));
         return ST_OK;
     };
@@ -340,16 +253,15 @@ int hydk_tiles_run(HydkTileAsm *a, uint32_t first_frame, uint32_t frames, const 
     void *out = a ? a->out : nullptr;
     const uint64_t out_cap = a ? a->out_cap : 0;
     if (!a || !blob || !extents || !out || frames < 1 || frames > HYDK_TILE_MAX_FRAMES || (uint64_t)first_frame + frames > a->plan_frames)
-        return tfail(a, ST_API_ERROR, "bad launch group");
+        return hydk_fail(a, ST_API_ERROR, "bad launch group");
     if (((uintptr_t)out & 3u) || ((uintptr_t)blob & 15u))
-        return tfail(a, ST_API_ERROR, "output buffer must be 4-byte aligned, the view 16-byte aligned");
-    TILE_TRY(a, hipSetDevice(a->device));
+        return hydk_fail(a, ST_API_ERROR, "output buffer must be 4-byte aligned, the view 16-byte aligned");
+    HYDK_TRY(a, hipSetDevice(a->device));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_tiles_prepare, dim3(frames), dim3(64), 0, st, (const uint8_t *)a->plan, first_frame, (const uint8_t *)blob, frames, a->S);
     hipLaunchKernelGGL(k_tiles_layout, dim3(1), dim3(256), 0, st, (const uint8_t *)a->plan, first_frame, (const uint8_t *)blob, frames,
                        (const HydkTileExtent *)extents, a->S, first_group, out_cap, a->h_result);
-    hipLaunchKernelGGL(k_tiles_copy, dim3(kCopyBlocks), dim3(256), 0, st, a->S, frames, (uint8_t *)out);
-    TILE_TRY(a, hipGetLastError());
+    HYDK_TRY(a, hydk::launch_pieces_copy(a->S.pieces, frames * HYDK_TILE_PIECES, nullptr, a->S.result, out, st));
     return ST_OK;
 }
 
@@ -359,15 +271,15 @@ int hydk_tiles_reserve(HydkTileAsm *a, uint64_t bytes, uint64_t keep, void *stre
         return ST_API_ERROR;
     if (bytes <= a->out_cap)
         return ST_OK;
-    TILE_TRY(a, hipSetDevice(a->device));
-    TILE_TRY(a, hipStreamSynchronize((hipStream_t)stream));
+    HYDK_TRY(a, hipSetDevice(a->device));
+    HYDK_TRY(a, hipStreamSynchronize((hipStream_t)stream));
     uint8_t *bigger = nullptr;
-    TILE_TRY(a, hipMalloc(&bigger, bytes + 16));
+    HYDK_TRY(a, hipMalloc(&bigger, bytes + 16));
     if (a->out && keep) {
         const hipError_t e = hipMemcpy(bigger, a->out, keep < a->out_cap ? keep : a->out_cap, hipMemcpyDeviceToDevice);
         if (e != hipSuccess) {
             (void)hipFree(bigger);
-            return tfail(a, ST_INTERNAL_ERROR, "moving the output buffer", e);
+            return hydk_fail(a, ST_INTERNAL_ERROR, "moving the output buffer", e);
         }
     }
     if (a->out)
@@ -383,16 +295,16 @@ uint64_t hydk_tiles_out_capacity(HydkTileAsm *a) { return a ? a->out_cap : 0; }
 int hydk_tiles_wait(HydkTileAsm *a, void *stream) {
     if (!a)
         return ST_API_ERROR;
-    TILE_TRY(a, hipSetDevice(a->device));
-    TILE_TRY(a, hipStreamSynchronize((hipStream_t)stream));
+    HYDK_TRY(a, hipSetDevice(a->device));
+    HYDK_TRY(a, hipStreamSynchronize((hipStream_t)stream));
     return ST_OK;
 }
 
 int hydk_tiles_read(HydkTileAsm *a, uint8_t *dst, size_t n) {
     if (!a || !dst || !a->out || n > a->out_cap)
-        return tfail(a, ST_API_ERROR, "nothing to read");
-    TILE_TRY(a, hipSetDevice(a->device));
-    TILE_TRY(a, hipMemcpy(dst, a->out, n, hipMemcpyDeviceToHost));
+        return hydk_fail(a, ST_API_ERROR, "nothing to read");
+    HYDK_TRY(a, hipSetDevice(a->device));
+    HYDK_TRY(a, hipMemcpy(dst, a->out, n, hipMemcpyDeviceToHost));
     return ST_OK;
 }
 

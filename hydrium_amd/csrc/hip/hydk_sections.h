@@ -158,6 +158,21 @@ HYDK_HD void hydk_put_ans_distribution(HydkSink *s, const uint32_t *freq, uint32
     }
 }
 
+/* HFGlobal's hybrid-uint configuration of one cluster (encoder.c:908, entropy.c:169-182): split 4, msb 1 and lsb 0, in
+ * widths the frame's largest alphabet decides (*log_alpha: 5 or more; above 8 the frame cannot be written).  Returns
+ * the bits one configuration takes; s == NULL: only that. */
+HYDK_HD uint32_t hydk_put_hf_config(HydkSink *s, uint32_t max_alphabet, int *log_alpha) {
+    const int la = max_alphabet > 32 ? hks_clog2(max_alphabet) : 5;
+    const uint32_t split_bits = (uint32_t)hks_clog2(1u + (uint32_t)la);
+    *log_alpha = la;
+    if (s) {
+        hks_put(s, 4, split_bits);
+        hks_put(s, 1, 3); /* in clog2(5) bits */
+        hks_put(s, 0, 2); /* in clog2(4) bits */
+    }
+    return split_bits + 3u + 2u;
+}
+
 /* ---------------------------------------------------------------------------------------------
  * depth-limited code lengths for a small alphabet (entropy.c:577-662): the reference's selection
  * loop as it stands — round k settles slots 2k and 2k+1 as the children of node n + k; candidates are

@@ -1,6 +1,6 @@
 /*
  * hydk_tiles.h — tile-mode frames assembled many at a time: the plan the host writes, the data-dependent
- * fields of one tile frame, where its bit strings go, and the composition of an output word.  Like
+ * fields of one tile frame and where its bit strings go.  Like
  * hydk_sections.h the same source runs on the GPU (csrc/hip/assemble_tiles.hip: one wavefront per frame,
  * then one thread per output word) and on the host (csrc/host/tiled.c under HYD_TEST_HOOKS: the CPU tests
  * hold it to the host assembler, frame.c, byte for byte).  Include hydrium_amd.h first (HydAmdBlobSlot).
@@ -12,16 +12,15 @@
  *                   the LF coefficient stream, [LF tail + HFGlobal] (MID), the group's rANS bits.
  *   several groups  frame header with the TOC permutation | TOC | LFGlobal | LFGroup | HFGlobal | groups, each padded
  *                   to a byte.  HEAD holds the fixed LF head + prefix codes, MID holds HFGlobal.
- * A frame is a list of HYDK_TILE_PIECES pieces, each ONE bit string at a bit position of the output; pieces of all
- * frames of a launch group form one sorted list and every output word is composed from the pieces that touch it.
+ * A frame is a list of HYDK_TILE_PIECES pieces (hydk_pieces.h); the pieces of all frames of a launch group form one
+ * sorted list, from which every output word is composed.
  */
 #ifndef HYD_TILE_LAYOUT_H_
 #define HYD_TILE_LAYOUT_H_
 
 #include <stdint.h>
 
-#include "hydk_assemble.h"
-#include "hydk_sections.h"
+#include "hydk_asm_common.h"
 
 #define HYDK_TILE_MAGIC 0x4C495448u /* "HTIL" */
 #define HYDK_TILE_MAX_SHAPES 4      /* interior, right edge, bottom edge, corner */
@@ -63,13 +62,6 @@ typedef struct HydkTileExtent { /* a batch's results, frame by frame: where its 
     uint64_t lf_off, lf_bytes, hf_off, hf_bytes;
 } HydkTileExtent;
 
-typedef struct HydkTilePiece {
-    uint64_t dst_bit, nbits;
-    const uint32_t *src; /* 4-byte aligned */
-    uint32_t src_bit;    /* first bit of the string inside src[0] (a byte string that starts off a word boundary) */
-    uint32_t pad;
-} HydkTilePiece;
-
 typedef struct HydkTileScratch {
     HydkLfHeadScratch lf;
     uint32_t hist_bits[HYDK_TILE_CLUSTERS];
@@ -94,16 +86,10 @@ HYDK_HD void hydk_tile_prepare(const uint8_t *planb, const HydkTileFrame *fr, co
                                const uint8_t *lengths, uint64_t lf_capacity, uint32_t *head, uint32_t *mid, uint32_t *toc,
                                HydkTileScratch *S, HydkTileSizes *out) {
     const int single = sh->ngroups == 1;
-    uint32_t e = 0;
-    {
-        const uint64_t lf_end = (uint64_t)rec->lf.offset + (((uint64_t)rec->lf.bit_count + 7) >> 3);
-        if (rec->preset != 0 || rec->table_error || rec->lf.error || lf_end > lf_capacity || (rec->lf.offset & 3u) || rec->lf.alphabet < 1 ||
-            rec->lf.alphabet > HYDK_LF_RUN_BASE + 128u)
-            e |= HYDK_ASM_E_SLOT;
-        for (uint32_t g = sh->ngroups; g < HYDAMD_GROUPS_PER_LFG; g++)
-            if (rec->group_bits[g])
-                e |= HYDK_ASM_E_SIZE; /* a group the tile's geometry does not have */
-    }
+    uint32_t e = hydk_slot_check(rec, 0, lf_capacity);
+    for (uint32_t g = sh->ngroups; g < HYDAMD_GROUPS_PER_LFG; g++)
+        if (rec->group_bits[g])
+            e |= HYDK_ASM_E_SIZE; /* a group the tile's geometry does not have */
     HKS_LANES(l) {
         if (l == 0)
             S->err = 0;
@@ -139,10 +125,8 @@ HYDK_HD void hydk_tile_prepare(const uint8_t *planb, const HydkTileFrame *fr, co
         }
     }
     HKS_SYNC();
-    const uint32_t max_alpha = rec->running_max_alphabet;
-    int log_alpha = max_alpha > 1 ? hks_clog2(max_alpha) : 0;
-    log_alpha = log_alpha < 5 ? 5 : log_alpha;
-    const uint32_t cfg_bits = (uint32_t)hks_clog2(1u + (uint32_t)log_alpha) + 3u + 2u; /* split 4, msb 1, lsb 0 (encoder.c:908) */
+    int log_alpha = 0;
+    const uint32_t cfg_bits = hydk_put_hf_config((HydkSink *)0, rec->running_max_alphabet, &log_alpha);
     const uint64_t cfg_at = (uint64_t)tail_here + sh->hfpre_bits + 2u;
     const uint64_t hist_at = cfg_at + (uint64_t)HYDK_TILE_CLUSTERS * cfg_bits;
     uint64_t mid_end = hist_at;
@@ -154,9 +138,7 @@ HYDK_HD void hydk_tile_prepare(const uint8_t *planb, const HydkTileFrame *fr, co
             if (l == 0)
                 hks_put(&sink, (uint32_t)(log_alpha - 5), 2);
             sink.pos = cfg_at + (uint64_t)l * cfg_bits;
-            hks_put(&sink, 4, cfg_bits - 5u);
-            hks_put(&sink, 1, 3);
-            hks_put(&sink, 0, 2);
+            hydk_put_hf_config(&sink, rec->running_max_alphabet, &log_alpha);
             uint64_t at = hist_at;
             for (int i = 0; i < l; i++)
                 at += S->hist_bits[i];
@@ -203,87 +185,40 @@ HYDK_HD void hydk_tile_prepare(const uint8_t *planb, const HydkTileFrame *fr, co
     }
 }
 
-HYDK_HD HydkTilePiece hydk_tile_piece(uint64_t dst_bit, const void *src, uint64_t nbits) {
-    HydkTilePiece p;
-    const uintptr_t a = (uintptr_t)src;
-    p.dst_bit = dst_bit;
-    p.nbits = nbits;
-    p.src = (const uint32_t *)(a & ~(uintptr_t)3);
-    p.src_bit = (uint32_t)(a & 3u) * 8u;
-    p.pad = 0;
-    return p;
-}
-
 /* the frame's pieces, in output order, for a frame that starts at byte `at` of the output */
 HYDK_HD void hydk_tile_pieces(const uint8_t *planb, const HydkTileFrame *fr, const HydkTileShape *sh, const HydkTileSizes *z,
                               const HydAmdBlobSlot *rec, const uint32_t *head, const uint32_t *mid, const uint32_t *toc,
-                              const uint8_t *lf_src, const uint8_t *hf_src, uint64_t at, HydkTilePiece *P) {
+                              const uint8_t *lf_src, const uint8_t *hf_src, uint64_t at, HydkPiece *P) {
     uint64_t bit = at * 8u;
-    P[0] = hydk_tile_piece(bit, planb + fr->prefix_off, (uint64_t)fr->prefix_bytes * 8u);
+    P[0] = hydk_piece(bit, planb + fr->prefix_off, (uint64_t)fr->prefix_bytes * 8u);
     bit += (uint64_t)fr->prefix_bytes * 8u;
-    P[1] = hydk_tile_piece(bit, toc, z->toc_bits);
+    P[1] = hydk_piece(bit, toc, z->toc_bits);
     bit += (((uint64_t)z->toc_bits + 7) >> 3) * 8u;
     if (sh->ngroups == 1) {
-        P[2] = hydk_tile_piece(bit, head, z->head_bits);
+        P[2] = hydk_piece(bit, head, z->head_bits);
         bit += z->head_bits;
-        P[3] = hydk_tile_piece(bit, lf_src, rec->lf.bit_count);
+        P[3] = hydk_piece(bit, lf_src, rec->lf.bit_count);
         bit += rec->lf.bit_count;
-        P[4] = hydk_tile_piece(bit, mid, z->mid_bits);
+        P[4] = hydk_piece(bit, mid, z->mid_bits);
         bit += z->mid_bits;
-        P[5] = hydk_tile_piece(bit, hf_src, rec->group_bits[0]);
+        P[5] = hydk_piece(bit, hf_src, rec->group_bits[0]);
         bit += rec->group_bits[0];
-        P[6] = hydk_tile_piece(bit, head, 0);
-        P[7] = hydk_tile_piece(bit, head, 0);
+        P[6] = hydk_piece(bit, head, 0);
+        P[7] = hydk_piece(bit, head, 0);
         return;
     }
-    P[2] = hydk_tile_piece(bit, planb + sh->lfglobal_off, (uint64_t)sh->lfglobal_bytes * 8u);
+    P[2] = hydk_piece(bit, planb + sh->lfglobal_off, (uint64_t)sh->lfglobal_bytes * 8u);
     bit += (uint64_t)sh->lfglobal_bytes * 8u;
     const uint64_t lfsec = bit;
-    P[3] = hydk_tile_piece(bit, head, z->head_bits);
+    P[3] = hydk_piece(bit, head, z->head_bits);
     bit += z->head_bits;
-    P[4] = hydk_tile_piece(bit, lf_src, rec->lf.bit_count);
+    P[4] = hydk_piece(bit, lf_src, rec->lf.bit_count);
     bit += rec->lf.bit_count;
-    P[5] = hydk_tile_piece(bit, planb + sh->tail_off, sh->tail_bits);
+    P[5] = hydk_piece(bit, planb + sh->tail_off, sh->tail_bits);
     bit = lfsec + z->lfsec_bytes * 8u;
-    P[6] = hydk_tile_piece(bit, mid, z->mid_bits);
+    P[6] = hydk_piece(bit, mid, z->mid_bits);
     bit += z->hfg_bytes * 8u;
-    P[7] = hydk_tile_piece(bit, hf_src, z->hf_bytes * 8u);
-}
-
-/* bits [q, q + 32) of a piece's string as an output word sees them; zero outside the string.  Reads no word of the
- * source that holds none of the string's bits. */
-HYDK_HD uint32_t hydk_tile_bits(const HydkTilePiece *p, int64_t q) {
-    if (!p->nbits || q <= -32 || q >= (int64_t)p->nbits)
-        return 0;
-    const uint64_t lo = q < 0 ? 0 : (uint64_t)q;
-    const uint64_t hi = (uint64_t)(q + 32) < p->nbits ? (uint64_t)(q + 32) : p->nbits;
-    const uint32_t n = (uint32_t)(hi - lo);
-    const uint64_t a = (uint64_t)p->src_bit + lo;
-    const uint64_t i = a >> 5;
-    const uint32_t sh = (uint32_t)(a & 31u);
-    uint32_t v = p->src[i] >> sh;
-    if (sh && sh + n > 32u)
-        v |= p->src[i + 1] << (32u - sh);
-    if (n < 32u)
-        v &= (1u << n) - 1u;
-    return v << (uint32_t)((int64_t)lo - q);
-}
-
-/* output word W (bits [32 W, 32 W + 32) of the output) from a sorted piece list; ends[i] = dst_bit + nbits of piece i */
-HYDK_HD uint32_t hydk_tile_word(const HydkTilePiece *P, const uint64_t *ends, uint32_t np, uint64_t W) {
-    const uint64_t b0 = W * 32u;
-    uint32_t lo = 0, hi = np; /* the first piece that ends behind b0 */
-    while (lo < hi) {
-        const uint32_t m = (lo + hi) >> 1;
-        if (ends[m] > b0)
-            hi = m;
-        else
-            lo = m + 1;
-    }
-    uint32_t v = 0;
-    for (uint32_t i = lo; i < np && P[i].dst_bit < b0 + 32u; i++)
-        v |= hydk_tile_bits(&P[i], (int64_t)b0 - (int64_t)P[i].dst_bit);
-    return v;
+    P[7] = hydk_piece(bit, hf_src, z->hf_bytes * 8u);
 }
 
 #endif /* HYD_TILE_LAYOUT_H_ */

@@ -18,9 +18,7 @@
 #include "frame.h"
 #include "hydrium_amd.h"
 #include "libhydrium/libhydrium.h"
-
-int hyd_internal_file_header(const HYDImageMetadata *md, const uint8_t *icc, size_t icc_size, HydBits *out, const char **err);
-const HydBits *hyd_internal_lf_tail(size_t vbw, size_t vbh);
+#include "planbuf.h"
 
 struct HydAmdAssembler {
     HydkAsm *dev;
@@ -29,50 +27,6 @@ struct HydAmdAssembler {
     uint8_t *key;
     size_t key_len;
 };
-
-typedef struct Buf {
-    uint8_t *p;
-    size_t len, cap;
-    int failed;
-} Buf;
-
-static size_t buf_reserve(Buf *b, size_t n) { /* returns the 16-byte aligned offset of n fresh zero bytes */
-    const size_t at = (b->len + 15) & ~(size_t)15;
-    const size_t need = at + ((n + 15) & ~(size_t)15) + 16;
-    if (need > b->cap) {
-        size_t ncap = b->cap ? b->cap : 4096;
-        while (ncap < need)
-            ncap *= 2;
-        uint8_t *np = realloc(b->p, ncap);
-        if (!np) {
-            b->failed = 1;
-            return 0;
-        }
-        memset(np + b->cap, 0, ncap - b->cap);
-        b->p = np;
-        b->cap = ncap;
-    }
-    b->len = at + n;
-    return at;
-}
-
-/* a bit string (whole bytes + pending bits of a HydBits) as zero-padded words; returns its offset, *bits its length */
-static size_t buf_add_bits(Buf *b, const HydBits *src, uint32_t *bits) {
-    const size_t nbytes = src->len + (size_t)((src->nacc + 7) >> 3);
-    const size_t at = buf_reserve(b, nbytes ? nbytes : 1);
-    if (b->failed)
-        return 0;
-    memset(b->p + at, 0, (nbytes + 15) & ~(size_t)15);
-    if (src->len)
-        memcpy(b->p + at, src->data, src->len);
-    uint64_t acc = src->acc;
-    if (src->nacc < 64)
-        acc &= (UINT64_C(1) << src->nacc) - 1;
-    for (int i = 0; i * 8 < src->nacc; i++)
-        b->p[at + src->len + (size_t)i] = (uint8_t)(acc >> (8 * i));
-    *bits = (uint32_t)(src->len * 8 + (size_t)src->nacc);
-    return at;
-}
 
 #define AFAIL(a, code, msg) ((a)->error = (msg), (code))
 

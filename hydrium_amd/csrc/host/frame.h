@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "bitio.h"
+#include "libhydrium/libhydrium.h"
 
 #define HYD_FRAME_MAX_CLUSTERS 9
 #define HYD_FRAME_ALPHABET 128
@@ -79,5 +80,11 @@ int hyd_hf_cluster_map(uint8_t *map, unsigned num_presets);
 int hyd_write_hf_global(HydBits *out, unsigned num_presets, size_t num_frame_groups,
                         const uint32_t (*freq)[HYD_FRAME_MAX_CLUSTERS][HYD_FRAME_ALPHABET],
                         const uint32_t (*alphabet)[HYD_FRAME_MAX_CLUSTERS], unsigned max_alphabet, const char **err);
+
+/* for the planners of the device-side assemblers (assembler.c, tiled.c), from encoder.c: the file header hyd_send_tile
+ * writes in front of this image's first frame, and the cached geometry-only bits that close an LF group section
+ * (NULL: the cache is full, code them with hyd_write_lf_group_tail) */
+int hyd_internal_file_header(const HYDImageMetadata *md, const uint8_t *icc, size_t icc_size, HydBits *out, const char **err);
+const HydBits *hyd_internal_lf_tail(size_t vbw, size_t vbh);
 
 #endif /* HYD_FRAME_H_ */

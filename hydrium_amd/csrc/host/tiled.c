@@ -22,6 +22,7 @@
 #include "frame.h"
 #include "hydrium_amd.h"
 #include "libhydrium/libhydrium.h"
+#include "planbuf.h"
 
 #include "../hip/hydk_tiles.h"
 
@@ -30,9 +31,6 @@
 #endif
 
 #define TILED_DEFAULT_LAUNCH 32
-
-int hyd_internal_file_header(const HYDImageMetadata *md, const uint8_t *icc, size_t icc_size, HydBits *out, const char **err);
-const HydBits *hyd_internal_lf_tail(size_t vbw, size_t vbh);
 
 typedef struct HydkTileAsm HydkTileAsm; /* assemble_tiles.hip */
 int hydk_tiles_create(int device, int max_frames, const void *plan, size_t plan_bytes, HydkTileAsm **out);
@@ -50,49 +48,6 @@ uint64_t hydk_tiles_device_free(int device);
 /* ---------------------------------------------------------------------------------------------
  * the plan
  * ------------------------------------------------------------------------------------------- */
-typedef struct Buf {
-    uint8_t *p;
-    size_t len, cap;
-    int failed;
-} Buf;
-
-static size_t buf_reserve(Buf *b, size_t n) { /* returns the 16-byte aligned offset of n fresh zero bytes */
-    const size_t at = (b->len + 15) & ~(size_t)15;
-    const size_t need = at + ((n + 15) & ~(size_t)15) + 16;
-    if (need > b->cap) {
-        size_t ncap = b->cap ? b->cap : 4096;
-        while (ncap < need)
-            ncap *= 2;
-        uint8_t *np = realloc(b->p, ncap);
-        if (!np) {
-            b->failed = 1;
-            return 0;
-        }
-        memset(np + b->cap, 0, ncap - b->cap);
-        b->p = np;
-        b->cap = ncap;
-    }
-    b->len = at + n;
-    return at;
-}
-
-/* a bit string (whole bytes + pending bits of a HydBits) as zero-padded words; returns its offset, *bits its length */
-static size_t buf_add_bits(Buf *b, const HydBits *src, uint32_t *bits) {
-    const size_t nbytes = src->len + (size_t)((src->nacc + 7) >> 3);
-    const size_t at = buf_reserve(b, nbytes ? nbytes : 1);
-    if (b->failed)
-        return 0;
-    if (src->len)
-        memcpy(b->p + at, src->data, src->len);
-    uint64_t acc = src->acc;
-    if (src->nacc < 64)
-        acc &= (UINT64_C(1) << src->nacc) - 1;
-    for (int i = 0; i * 8 < src->nacc; i++)
-        b->p[at + src->len + (size_t)i] = (uint8_t)(acc >> (8 * i));
-    *bits = (uint32_t)(src->len * 8 + (size_t)src->nacc);
-    return at;
-}
-
 typedef struct TileGeometry {
     size_t W, H, tw, th, ntx, nty, ntiles;
 } TileGeometry;
@@ -525,7 +480,7 @@ HYDT_EXPORT int hydt_tiles_from_streams(const HYDImageMetadata *md, size_t nfram
     uint32_t *head = calloc(nframes * HYDK_TILE_HEAD_WORDS, 4), *mid = calloc(nframes * HYDK_TILE_MID_WORDS, 4),
              *toc = calloc(nframes * HYDK_TILE_TOC_WORDS, 4);
     HydkTileSizes *sizes = calloc(nframes, sizeof(*sizes));
-    HydkTilePiece *pieces = calloc(nframes * HYDK_TILE_PIECES, sizeof(*pieces));
+    HydkPiece *pieces = calloc(nframes * HYDK_TILE_PIECES, sizeof(*pieces));
     uint64_t *ends = calloc(nframes * HYDK_TILE_PIECES, sizeof(*ends));
     HydkTileScratch *scratch = calloc(1, sizeof(*scratch));
     size_t lf_len = 0;
@@ -582,11 +537,8 @@ HYDT_EXPORT int hydt_tiles_from_streams(const HYDImageMetadata *md, size_t nfram
             if (!file) {
                 ret = HYD_NOMEM;
             } else {
-                for (uint64_t W = 0; W * 4 < at; W++) {
-                    const uint32_t v = hydk_tile_word(pieces, ends, np, W);
-                    for (int j = 0; j < 4; j++)
-                        file[W * 4 + (uint64_t)j] = (uint8_t)(v >> (8 * j));
-                }
+                for (uint64_t W = 0; W * 4 < at; W++)
+                    hydk_store_word(file, W, hydk_pieces_word(pieces, ends, np, W), 0, at);
                 *out = file;
                 *out_len = (size_t)at;
             }
@@ -603,6 +555,26 @@ HYDT_EXPORT int hydt_tiles_from_streams(const HYDImageMetadata *md, size_t nfram
     free(lf_packed);
     free(hf);
     free(plan);
+    return ret;
+}
+
+/* the shared composer (hydk_pieces.h) on a crafted list: piece i is nbits[i] bits from byte src_off[i] of `src`, at bit
+ * dst_bit[i]; bytes [lo, lo + bytes) of `out` (4-byte aligned, whole words) are written the way k_pieces_copy writes them */
+HYDT_EXPORT int hydt_compose_pieces(const uint64_t *dst_bit, const uint64_t *nbits, const uint64_t *src_off, uint32_t np, const uint8_t *src,
+                                    uint64_t lo, uint64_t bytes, uint8_t *out) {
+    HydkPiece *P = calloc(np ? np : 1, sizeof(*P));
+    uint64_t *ends = calloc(np ? np : 1, sizeof(*ends));
+    if (P && ends) {
+        for (uint32_t i = 0; i < np; i++) {
+            P[i] = hydk_piece(dst_bit[i], src + src_off[i], nbits[i]);
+            ends[i] = dst_bit[i] + nbits[i];
+        }
+        for (uint64_t W = lo >> 2; W * 4 < lo + bytes; W++)
+            hydk_store_word(out, W, hydk_pieces_word(P, ends, np, W), lo, lo + bytes);
+    }
+    const int ret = P && ends ? HYD_OK : HYD_NOMEM;
+    free(P);
+    free(ends);
     return ret;
 }
 #endif /* HYD_TEST_HOOKS */
