@@ -41,17 +41,15 @@
  *     prediction, as a decoder must (it learns byte 41 only there); the reference indexes
  *     "I "[i - 42] with i = 41 (libhydrium.c:219-224), 4 GB past the literal, and crashes.
  */
-#define _POSIX_C_SOURCE 200809L /* clock_gettime under -std=c99 */
 #include <malloc.h>
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
-#include <unistd.h>
 
 #include "bitio.h"
 #include "frame.h"
+#include "hostframe.h"
 #include "prefix.h"
 #include "shards.h"
 #include "hydrium_amd.h"
@@ -59,16 +57,6 @@
 
 #define TILE_PIPE_MAX 8
 #define HYD_MAX_DEVICES HYDAMD_MAX_PEERS /* devices one encoder can deal a frame to */
-
-typedef struct LfgResult {
-    int32_t *dc; /* [3][vbh][vbw]; NULL when the LF coefficients were coded on the device */
-    uint8_t *lf_bits;                    /* device-coded LF-coefficient symbols (borrowed) or NULL */
-    uint8_t lf_lengths[HYD_LF_CODES];
-    uint32_t lf_alphabet, lf_run_pairs, lf_bit_count;
-    uint32_t freq[HYD_FRAME_MAX_CLUSTERS][HYD_FRAME_ALPHABET];
-    uint32_t alphabet[HYD_FRAME_MAX_CLUSTERS];
-    uint32_t bits[HYDAMD_GROUPS_PER_LFG];
-} LfgResult;
 
 struct HYDEncoder {
     HYDImageMetadata metadata;
@@ -129,317 +117,9 @@ struct HYDEncoder {
 
 #define FAIL(enc, code, msg) ((enc)->error = (msg), (code))
 
-/* HYDAMD_TRACE=1 prints where the host-pointer API path spends its wall time (stderr) */
-static double now_ms(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
-static int trace_on(void) {
-    static int on = -1;
-    if (on < 0) {
-        const char *e = getenv("HYDAMD_TRACE");
-        on = e && *e && *e != '0';
-    }
-    return on;
-}
-#define TRACE_MS(label, ms)                                             \
-    do {                                                                \
-        if (trace_on())                                                 \
-            fprintf(stderr, "[hydrium] %-28s %8.3f ms\n", (label), (ms)); \
-    } while (0)
-#define TRACE(label, t0) TRACE_MS(label, now_ms() - (t0))
-
-/* ---------------------------------------------------------------------------------------------
- * frame assembly (shared by the product path and the CPU-only test hook)
- * ------------------------------------------------------------------------------------------- */
-
-/* The LF groups of a frame are independent prefix-coded sections; in a frame with more than one
- * group each starts on a byte boundary, so they are coded by a few host threads into private
- * buffers and appended in send order. */
-typedef struct LfWork {
-    const HydFrameShape *shape;
-    const LfgResult *res;
-    HydBits *out;       /* [lfg_count] */
-    int *status;        /* [lfg_count] */
-    const char **err;   /* [lfg_count] */
-    size_t first, stride;
-} LfWork;
-
-/* The HF-metadata sub-streams of an LF group depend on its geometry only (frame.c:
- * hyd_write_lf_group_tail), cost ~200k symbol sends for a full LF group and compress to a few
- * hundred bytes: keep them per (vbw, vbh) for the life of the process.  Entries are immutable once
- * published, so readers only need the lock to find them. */
-typedef struct TailEntry {
-    size_t vbw, vbh;
-    HydBits bits;
-} TailEntry;
-static pthread_mutex_t g_tail_lock = PTHREAD_MUTEX_INITIALIZER;
-static TailEntry g_tails[32];
-static int g_ntails;
-
-static const HydBits *find_tail_locked(size_t vbw, size_t vbh) {
-    for (int i = 0; i < g_ntails; i++)
-        if (g_tails[i].vbw == vbw && g_tails[i].vbh == vbh)
-            return &g_tails[i].bits;
-    return NULL;
-}
-
-static const HydBits *lf_tail(size_t vbw, size_t vbh) {
-    pthread_mutex_lock(&g_tail_lock);
-    const HydBits *hit = find_tail_locked(vbw, vbh);
-    pthread_mutex_unlock(&g_tail_lock);
-    if (hit)
-        return hit;
-    HydBits fresh;
-    const char *err = NULL;
-    hb_init(&fresh);
-    if (hyd_write_lf_group_tail(&fresh, vbw, vbh, &err) || fresh.failed) {
-        hb_free(&fresh);
-        return NULL; /* the caller codes it inline and reports the error there */
-    }
-    pthread_mutex_lock(&g_tail_lock);
-    hit = find_tail_locked(vbw, vbh);
-    if (!hit && g_ntails < (int)(sizeof(g_tails) / sizeof(g_tails[0]))) {
-        g_tails[g_ntails].vbw = vbw;
-        g_tails[g_ntails].vbh = vbh;
-        g_tails[g_ntails].bits = fresh;
-        hit = &g_tails[g_ntails++].bits;
-        fresh.data = NULL;
-    }
-    pthread_mutex_unlock(&g_tail_lock);
-    if (fresh.data)
-        hb_free(&fresh);
-    return hit;
-}
-
-static int write_one_lf_group(HydBits *out, const LfgResult *r, size_t vbw, size_t vbh, const char **err) {
-    if (r->lf_bits) {
-        const HydLfCoded lf = {r->lf_lengths, r->lf_alphabet, r->lf_run_pairs, r->lf_bits, r->lf_bit_count};
-        return hyd_write_lf_group_coded(out, vbw, vbh, &lf, lf_tail(vbw, vbh), err);
-    }
-    return hyd_write_lf_group(out, r->dc, vbw, vbh, err);
-}
-
-static void *lf_worker(void *arg) {
-    const LfWork *w = arg;
-    for (size_t s = w->first; s < w->shape->lfg_count; s += w->stride) {
-        const size_t vbw = (w->shape->lfg[s].width + 7) >> 3, vbh = (w->shape->lfg[s].height + 7) >> 3;
-        hb_init(&w->out[s]);
-        w->err[s] = NULL;
-        w->status[s] = write_one_lf_group(&w->out[s], &w->res[s], vbw, vbh, &w->err[s]);
-        hb_align(&w->out[s]);
-    }
-    return NULL;
-}
-
-static int code_lf_groups_parallel(HYDEncoder *e, const HydFrameShape *shape, const LfgResult *res, HydBits *out) {
-    const size_t n = shape->lfg_count;
-    int *status = calloc(n, sizeof(int));
-    const char **err = calloc(n, sizeof(char *));
-    if (!status || !err) {
-        free(status);
-        free(err);
-        return FAIL(e, HYD_NOMEM, "out of memory");
-    }
-    long cores = sysconf(_SC_NPROCESSORS_ONLN);
-    size_t threads = cores > 1 ? (size_t)cores : 1;
-    if (threads > n)
-        threads = n;
-    if (threads > 16)
-        threads = 16;
-    LfWork work[16];
-    pthread_t tid[16];
-    size_t started = 0;
-    for (size_t i = 0; i < threads; i++) {
-        work[i] = (LfWork){shape, res, out, status, err, i, threads};
-        if (i + 1 < threads && pthread_create(&tid[started], NULL, lf_worker, &work[i]) == 0)
-            started++;
-        else
-            lf_worker(&work[i]); /* the calling thread takes the last share (and any that could not be spawned) */
-    }
-    for (size_t i = 0; i < started; i++)
-        pthread_join(tid[i], NULL);
-    int ret = 0;
-    for (size_t s = 0; s < n && !ret; s++) {
-        if (status[s] || out[s].failed) {
-            e->error = err[s] ? err[s] : "LF group coding failed";
-            ret = status[s] ? status[s] : HYD_NOMEM;
-        }
-    }
-    free(status);
-    free(err);
-    return ret;
-}
-
-static int device_fail(HYDEncoder *e, int code);
+static void take_spare_buffer_for(HydBits *b, size_t want); /* below, with the other spare-buffer functions */
 static void pipe_release(HYDEncoder *e);
 static void multi_release(HYDEncoder *e);
-
-/* payload == NULL: the packed HF sections are still on the device (e->dev) and are copied straight
- * into the output stream */
-typedef struct PayloadSegments { /* the packed HF sections in pieces (one per shard blob) instead of one string */
-    size_t count;
-    const uint8_t *const *ptr;
-    const size_t *len;
-} PayloadSegments;
-
-static int assemble_frame(HYDEncoder *e, const HydFrameShape *shape, const LfgResult *res, unsigned max_alphabet,
-                          const uint8_t *payload, size_t payload_len, HydBits *lf_prebuilt, const PayloadSegments *segs) {
-    uint8_t *fetched = NULL;
-    const size_t fg = ((shape->frame_width + 255) >> 8) * ((shape->frame_height + 255) >> 8);
-    const int multi = fg > 1;
-    const size_t toc_n = hyd_toc_entries(shape);
-    const unsigned num_presets = (unsigned)shape->lfg_count;
-    int ret = 0;
-    HydBits body;
-    hb_init(&body);
-    size_t *sizes = calloc(toc_n, sizeof(size_t));
-    uint32_t(*freq)[HYD_FRAME_MAX_CLUSTERS][HYD_FRAME_ALPHABET] = calloc(num_presets, sizeof(*freq));
-    uint32_t(*alpha)[HYD_FRAME_MAX_CLUSTERS] = calloc(num_presets, sizeof(*alpha));
-    if (!sizes || !freq || !alpha) {
-        ret = FAIL(e, HYD_NOMEM, "out of memory");
-        goto done;
-    }
-    size_t k = 0, mark = 0;
-    int overflow = 0; /* more sections than the frame geometry has TOC entries: inconsistent LF-group list */
-#define PUSH_SIZE(v)                       \
-    do {                                   \
-        if (k < toc_n)                     \
-            sizes[k++] = (v);              \
-        else                               \
-            overflow = 1;                  \
-    } while (0)
-#define CLOSE_SECTION()                    \
-    do {                                   \
-        if (multi) {                       \
-            hb_align(&body);               \
-            PUSH_SIZE(body.len - mark);    \
-            mark = body.len;               \
-        }                                  \
-    } while (0)
-
-    double t0 = now_ms();
-    hyd_write_lf_global(&body);
-    CLOSE_SECTION();
-    if (multi && lf_prebuilt) { /* coded while the GPU was still busy with the entropy stage (finish_frame) */
-        for (size_t s = 0; s < shape->lfg_count; s++) {
-            hb_append_bytes(&body, lf_prebuilt[s].data, lf_prebuilt[s].len);
-            CLOSE_SECTION();
-        }
-    } else if (multi && shape->lfg_count > 1) {
-        HydBits *lf = calloc(shape->lfg_count, sizeof(HydBits));
-        if (!lf) {
-            ret = FAIL(e, HYD_NOMEM, "out of memory");
-            goto done;
-        }
-        ret = code_lf_groups_parallel(e, shape, res, lf);
-        for (size_t s = 0; s < shape->lfg_count; s++) {
-            if (!ret) {
-                hb_append_bytes(&body, lf[s].data, lf[s].len);
-                CLOSE_SECTION();
-            }
-            hb_free(&lf[s]);
-        }
-        free(lf);
-        if (ret)
-            goto done;
-    } else {
-        for (size_t s = 0; s < shape->lfg_count; s++) {
-            const size_t vbw = (shape->lfg[s].width + 7) >> 3, vbh = (shape->lfg[s].height + 7) >> 3;
-            ret = write_one_lf_group(&body, &res[s], vbw, vbh, &e->error);
-            if (ret)
-                goto done;
-            CLOSE_SECTION();
-        }
-    }
-    TRACE("  LF group sections", t0);
-    t0 = now_ms();
-    /* tables are signalled per preset = raster LF-group id, whatever the send order was */
-    for (size_t s = 0; s < shape->lfg_count; s++) {
-        const size_t p = shape->lfg[s].raster_id;
-        memcpy(freq[p], res[s].freq, sizeof(res[s].freq));
-        memcpy(alpha[p], res[s].alphabet, sizeof(res[s].alphabet));
-    }
-    ret = hyd_write_hf_global(&body, num_presets, fg, (const uint32_t(*)[HYD_FRAME_MAX_CLUSTERS][HYD_FRAME_ALPHABET])freq,
-                              (const uint32_t(*)[HYD_FRAME_MAX_CLUSTERS])alpha, max_alphabet, &e->error);
-    if (ret)
-        goto done;
-    CLOSE_SECTION();
-    TRACE("  HFGlobal", t0);
-    t0 = now_ms();
-    if (multi) {
-        /* the device payload already is: byte-padded sections, send order, raster inside an LF group;
-         * it follows the body, so only its sizes are needed here */
-        for (size_t s = 0; s < shape->lfg_count; s++) {
-            const size_t ng = ((shape->lfg[s].width + 255) >> 8) * ((shape->lfg[s].height + 255) >> 8);
-            for (size_t g = 0; g < ng && g < HYDAMD_GROUPS_PER_LFG; g++)
-                PUSH_SIZE((res[s].bits[g] + 7u) >> 3);
-        }
-    } else {
-        /* a single-group frame is one bit-contiguous section (encoder.c:837-850,968-981 guards) */
-        if (!payload && payload_len) {
-            fetched = malloc(payload_len);
-            if (!fetched) {
-                ret = FAIL(e, HYD_NOMEM, "out of memory");
-                goto done;
-            }
-            ret = hydamd_read_payload(e->dev, fetched, payload_len);
-            if (ret) {
-                ret = device_fail(e, ret);
-                goto done;
-            }
-            payload = fetched;
-        }
-        hb_append_bits(&body, payload, res[0].bits[0]);
-    }
-    hb_align(&body);
-    if (!multi)
-        PUSH_SIZE(body.len);
-    if (overflow || k != toc_n || body.failed) {
-        ret = FAIL(e, body.failed ? HYD_NOMEM : HYD_INTERNAL_ERROR, "frame assembly inconsistency");
-        goto done;
-    }
-    ret = hyd_write_frame_header(&e->stream, shape, &e->error);
-    if (!ret)
-        ret = hyd_write_toc_sizes(&e->stream, sizes, toc_n);
-    if (ret) {
-        if (!e->error)
-            e->error = "frame header could not be written";
-        goto done;
-    }
-    hb_append_bytes(&e->stream, body.data, body.len);
-    if (multi && payload_len) {
-        if (segs) { /* straight from the shards' blobs into the output: the only copy the sections see here */
-            uint8_t *dst = hb_extend(&e->stream, payload_len);
-            for (size_t i = 0; dst && i < segs->count; i++) {
-                memcpy(dst, segs->ptr[i], segs->len[i]);
-                dst += segs->len[i];
-            }
-        } else if (payload) {
-            hb_append_bytes(&e->stream, payload, payload_len);
-        } else {
-            uint8_t *dst = hb_extend(&e->stream, payload_len);
-            if (dst && (ret = hydamd_read_payload(e->dev, dst, payload_len)) != 0)
-                ret = device_fail(e, ret);
-        }
-    }
-    if (!ret && e->stream.failed)
-        ret = FAIL(e, HYD_NOMEM, "out of memory");
-    TRACE("  frame header, TOC, body + HF sections", t0);
-done:
-    free(fetched);
-#undef CLOSE_SECTION
-#undef PUSH_SIZE
-    free(sizes);
-    free(freq);
-    free(alpha);
-    hb_free(&body);
-    return ret;
-}
-
-static void take_spare_buffer(HydBits *b); /* below, with the other spare-buffer functions */
-static void take_spare_buffer_for(HydBits *b, size_t want);
 
 static int emit_file_header(HYDEncoder *e) {
     if (e->wrote_header)
@@ -721,7 +401,6 @@ static void take_spare_buffer_for(HydBits *b, size_t want) {
     }
     pthread_mutex_unlock(&g_buf_lock);
 }
-static void take_spare_buffer(HydBits *b) { take_spare_buffer_for(b, 0); }
 
 /* keeps p (returns 1) in a free slot or in place of a smaller spare, which is freed */
 static int offer_spare_buffer(void *p, size_t cap) {
@@ -756,7 +435,7 @@ HYDRIUM_EXPORT HYDStatusCode hyd_encoder_destroy(HYDEncoder *e) {
     multi_release(e);
     pipe_release(e);
     if (e->dev) {
-        const double t0 = now_ms();
+        const double t0 = hyd_now_ms();
         ctx_release(e->dev, e->dev_slots, e->dev_linear, !e->dev_failed);
         TRACE("release device context", t0);
     }
@@ -836,13 +515,18 @@ HYDRIUM_EXPORT HYDStatusCode hyd_release_output_buffer(HYDEncoder *e, size_t *wr
     return HYD_OK;
 }
 
-HYDRIUM_EXPORT HYDStatusCode hyd_flush(HYDEncoder *e) {
-    if (e->one_frame && !e->last_tile)
-        return HYD_OK; /* libhydrium.c:148-149 */
+/* what is pending into the buffer on loan; HYD_NEED_MORE_OUTPUT while some of it is left */
+static HYDStatusCode hand_over(HYDEncoder *e) {
     if (!e->out)
         return FAIL(e, HYD_API_ERROR, "buffer was never provided");
     drain(e);
     return e->stream_pos < e->stream.len ? HYD_NEED_MORE_OUTPUT : HYD_OK;
+}
+
+HYDRIUM_EXPORT HYDStatusCode hyd_flush(HYDEncoder *e) {
+    if (e->one_frame && !e->last_tile)
+        return HYD_OK; /* libhydrium.c:148-149 */
+    return hand_over(e);
 }
 
 /* the context e->dev is not to be parked for reuse; in tile mode that is recorded in the ring entry that owns it,
@@ -861,7 +545,7 @@ static int device_fail(HYDEncoder *e, int code) {
     /* hydamd status codes are HYDStatusCode values; keep a static string for the message */
     static const char *const generic = "GPU encode failed (see hydamd_error)";
     const char *m = hydamd_error(e->dev);
-    if (m && getenv("HYDAMD_TRACE"))
+    if (m && hyd_trace_on())
         fprintf(stderr, "[hydrium] device error %d: %s\n", code, m);
     if (m && strstr(m, "NaN"))
         e->error = "Invalid NaN Float";
@@ -872,6 +556,15 @@ static int device_fail(HYDEncoder *e, int code) {
     else
         e->error = generic;
     return code;
+}
+
+/* the host's frame writer (hostframe.c) into this encoder's stream; a payload it has to fetch comes from e->dev */
+static int assemble_frame(HYDEncoder *e, const HydFrameShape *shape, const HydLfgResult *res, unsigned max_alphabet,
+                          const uint8_t *payload, size_t payload_len, HydBits *lf_prebuilt, const HydPayloadSegments *segs) {
+    int device = 0;
+    const int ret = hyd_assemble_frame(&e->stream, &e->error, e->dev, &device, shape, res, max_alphabet, payload, payload_len,
+                                       lf_prebuilt, segs);
+    return device ? device_fail(e, ret) : ret;
 }
 
 /* HYDAMD_HOST_ASSEMBLY=1: build frames on the host from read-back results, as round 2 did (A/B measurements, and the
@@ -899,7 +592,7 @@ static int close_frame(HYDEncoder *e, const HydFrameShape *shape, HydShardFrame 
         lf_ids[s] = (uint32_t)shape->lfg[s].raster_id;
     f->md = &e->metadata;
     f->lf_ids = lf_ids;
-    const double lead = now_ms() - t0;
+    const double lead = hyd_now_ms() - t0;
     if (!hyd_shards_enqueue(f, o))
         hyd_shards_wait(f, o);
     e->dev = f->ctx[o->kind == SHARDS_DEVICE ? o->shard : f->assembling];
@@ -925,7 +618,7 @@ static int close_frame(HYDEncoder *e, const HydFrameShape *shape, HydShardFrame 
     }
     if (o->verify_ms > 0)
         TRACE_MS("peer reads verified (first use of these device pairs)", o->verify_ms);
-    const double t1 = now_ms();
+    const double t1 = hyd_now_ms();
     uint8_t *dst = hb_extend(&e->stream, o->size);
     if (!dst)
         return FAIL(e, HYD_NOMEM, "out of memory");
@@ -937,7 +630,7 @@ static int close_frame(HYDEncoder *e, const HydFrameShape *shape, HydShardFrame 
 static int finish_frame_on_device(HYDEncoder *e, const HydFrameShape *shape) {
     HydShardFrame f = {.n = 1, .ctx = {e->dev}, .slots = {(uint32_t)shape->lfg_count}};
     HydShardOutcome o;
-    return close_frame(e, shape, &f, &o, "GPU hot path + assembly", now_ms());
+    return close_frame(e, shape, &f, &o, "GPU hot path + assembly", hyd_now_ms());
 }
 
 /* frames assembled on the host from ONE read-back (hydamd_stage_frame_blob / hydamd_read_frame_blob) instead of one small
@@ -955,11 +648,10 @@ static int staged_readback(const HYDEncoder *e, size_t n) {
 /* The host-assembly path in two halves, both on e->dev: every kernel of the frame is enqueued (nothing waits) ... */
 static int finish_frame_launch(HYDEncoder *e, const HydFrameShape *shape) {
     const size_t n = shape->lfg_count;
-    const size_t fg = ((shape->frame_width + 255) >> 8) * ((shape->frame_height + 255) >> 8);
     /* With more than one group the LF groups are byte-aligned sections of their own: the LF coder is
      * then put in front of the entropy stage, so that its streams can be read back and wrapped
      * into sections on the host while the (2 ms, latency-bound) entropy stage is still running. */
-    const int early_lf = hydamd_lf_coder(e->dev) && fg > 1;
+    const int early_lf = hydamd_lf_coder(e->dev) && hyd_frame_groups(shape) > 1;
     int ret = 0;
     if (early_lf)
         ret = hydamd_run_lf_coder(e->dev, (int)n, 1);
@@ -973,20 +665,16 @@ static int finish_frame_launch(HYDEncoder *e, const HydFrameShape *shape) {
 /* ... and everything the frame assembler needs is read back and the frame written */
 static int finish_frame_collect(HYDEncoder *e, const HydFrameShape *shape) {
     const size_t n = shape->lfg_count;
-    const size_t fg = ((shape->frame_width + 255) >> 8) * ((shape->frame_height + 255) >> 8);
     const int lf_on_gpu = hydamd_lf_coder(e->dev);
-    const int early_lf = lf_on_gpu && fg > 1;
+    const int early_lf = lf_on_gpu && hyd_frame_groups(shape) > 1;
     int staged = staged_readback(e, n); /* finish_frame_launch staged the frame's blob: one copy brings everything */
-    const uint8_t *payload = NULL;      /* staged: the HF sections inside the blob's host copy */
-    double t0 = now_ms();
-    int ret = 0;
-    LfgResult *res = calloc(n, sizeof(LfgResult));
+    HydBlobView view = {0};             /* staged: the HF sections inside the blob's host copy */
+    double t0 = hyd_now_ms();
+    int ret = 0, device = 0;
+    HydLfgResult *res = calloc(n, sizeof(HydLfgResult));
     HydBits *lf_sections = NULL;
-    HydAmdLfInfo *lf_info = NULL;
     uint8_t *lf_blob = NULL;
-    size_t lf_len = 0;
     unsigned max_alphabet = 0;
-    size_t payload_len = 0;
     if (!res)
         return FAIL(e, HYD_NOMEM, "out of memory");
     if (early_lf) {
@@ -1000,31 +688,11 @@ static int finish_frame_collect(HYDEncoder *e, const HydFrameShape *shape) {
         ret = device_fail(e, ret);
         goto done;
     }
-    t0 = now_ms();
+    t0 = hyd_now_ms();
     if (lf_on_gpu && (early_lf || !staged)) { /* two copies bring every LF group's coded coefficient stream */
-        lf_len = hydamd_lf_payload_size(e->dev);
-        lf_info = malloc(n * sizeof(HydAmdLfInfo));
-        lf_blob = malloc(lf_len ? lf_len : 1);
-        if (!lf_info || !lf_blob) {
-            ret = FAIL(e, HYD_NOMEM, "out of memory");
-            goto done;
-        }
-        ret = hydamd_read_lf_streams(e->dev, 0, (int)n, lf_info);
-        if (!ret)
-            ret = hydamd_read_lf_payload(e->dev, lf_blob, lf_len);
-        for (size_t s = 0; s < n && !ret; s++) {
-            if ((size_t)lf_info[s].offset + (((size_t)lf_info[s].bit_count + 7) >> 3) > lf_len) {
-                ret = HYD_INTERNAL_ERROR;
-                break;
-            }
-            memcpy(res[s].lf_lengths, lf_info[s].lengths, HYD_LF_CODES);
-            res[s].lf_alphabet = lf_info[s].alphabet;
-            res[s].lf_run_pairs = lf_info[s].run_pairs;
-            res[s].lf_bit_count = lf_info[s].bit_count;
-            res[s].lf_bits = lf_blob + lf_info[s].offset; /* borrowed from lf_blob */
-        }
+        ret = hyd_read_lf_results(e->dev, n, res, &lf_blob, &device, &e->error);
         if (ret) {
-            ret = device_fail(e, ret);
+            ret = device ? device_fail(e, ret) : ret;
             goto done;
         }
     }
@@ -1034,107 +702,46 @@ static int finish_frame_collect(HYDEncoder *e, const HydFrameShape *shape) {
             ret = FAIL(e, HYD_NOMEM, "out of memory");
             goto done;
         }
-        ret = code_lf_groups_parallel(e, shape, res, lf_sections);
+        ret = hyd_code_lf_groups_parallel(shape, res, lf_sections, &e->error);
         TRACE("LF group sections (beside the entropy stage)", t0);
         if (ret)
             goto done;
-        t0 = now_ms();
+        t0 = hyd_now_ms();
         ret = hydamd_sync(e->dev);
         TRACE("entropy stage done", t0);
         if (ret) {
             ret = device_fail(e, ret);
             goto done;
         }
-        t0 = now_ms();
+        t0 = hyd_now_ms();
     }
-    payload_len = hydamd_payload_size(e->dev);
+    size_t payload_len = hydamd_payload_size(e->dev);
     if (staged) {
         const void *blob = NULL;
         size_t bsize = 0;
         ret = hydamd_read_frame_blob(e->dev, (int)n, &blob, &bsize);
-        const HydAmdBlobHeader *h = blob;
-        if (!ret && (bsize < sizeof(*h) || h->magic != 0x42445948u || h->version != 1 || h->num_slots != n || h->lf_coded != 1 ||
-                     h->total_bytes > bsize || (h->status & HYDAMD_BLOB_RETRY)))
+        const int cls = ret ? HYD_BLOB_USABLE : hyd_read_blob(blob, bsize, n, &view, res, &max_alphabet);
+        if (cls == HYD_BLOB_NOT_USABLE)
             staged = 0; /* e.g. the frame outgrew a buffer and was rerun inside hydamd_sync: the staged blob is the first run's */
-        if (!ret && staged) {
-            const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(h + 1);
-            const uint64_t lf_off = sizeof(*h) + (uint64_t)n * sizeof(HydAmdBlobSlot);
-            const int sane = lf_off <= h->total_bytes && h->lf_bytes <= h->total_bytes - lf_off && h->hf_bytes <= h->total_bytes &&
-                             ((lf_off + h->lf_bytes + 15u) & ~(uint64_t)15u) + h->hf_bytes == h->total_bytes;
-            if (!sane)
-                ret = HYD_INTERNAL_ERROR;
-            const uint8_t *lf_bytes = (const uint8_t *)blob + lf_off;
-            for (size_t s = 0; s < n && !ret; s++) {
-                if (rec[s].table_error || rec[s].lf.error ||
-                    (uint64_t)rec[s].lf.offset + (((uint64_t)rec[s].lf.bit_count + 7) >> 3) > h->lf_bytes) {
-                    ret = HYD_INTERNAL_ERROR;
-                    break;
-                }
-                memcpy(res[s].freq, rec[s].freq, sizeof(res[s].freq));
-                memcpy(res[s].alphabet, rec[s].alphabet, sizeof(res[s].alphabet));
-                memcpy(res[s].bits, rec[s].group_bits, sizeof(res[s].bits));
-                if (rec[s].running_max_alphabet > max_alphabet)
-                    max_alphabet = rec[s].running_max_alphabet;
-                if (!early_lf) {
-                    memcpy(res[s].lf_lengths, rec[s].lf.lengths, HYD_LF_CODES);
-                    res[s].lf_alphabet = rec[s].lf.alphabet;
-                    res[s].lf_run_pairs = rec[s].lf.run_pairs;
-                    res[s].lf_bit_count = rec[s].lf.bit_count;
-                    res[s].lf_bits = (uint8_t *)(uintptr_t)(lf_bytes + rec[s].lf.offset); /* borrowed from the context's pinned copy */
-                }
-            }
-            payload = (const uint8_t *)blob + h->total_bytes - h->hf_bytes;
-            payload_len = (size_t)h->hf_bytes;
-        }
+        else if (cls != HYD_BLOB_USABLE)
+            ret = HYD_INTERNAL_ERROR;
+        else
+            payload_len = view.hf_len;
     }
-    if (!ret && !staged && lf_on_gpu && !early_lf && !lf_info) { /* (the staged blob was stale: the LF streams the old way) */
-        lf_len = hydamd_lf_payload_size(e->dev);
-        lf_info = malloc(n * sizeof(HydAmdLfInfo));
-        lf_blob = malloc(lf_len ? lf_len : 1);
-        if (!lf_info || !lf_blob) {
-            ret = FAIL(e, HYD_NOMEM, "out of memory");
+    if (!ret && !staged && lf_on_gpu && !lf_blob) { /* (the staged blob was stale: the LF streams the old way) */
+        ret = hyd_read_lf_results(e->dev, n, res, &lf_blob, &device, &e->error);
+        if (ret && !device)
             goto done;
-        }
-        ret = hydamd_read_lf_streams(e->dev, 0, (int)n, lf_info);
-        if (!ret)
-            ret = hydamd_read_lf_payload(e->dev, lf_blob, lf_len);
-        for (size_t s = 0; s < n && !ret; s++) {
-            if ((size_t)lf_info[s].offset + (((size_t)lf_info[s].bit_count + 7) >> 3) > lf_len) {
-                ret = HYD_INTERNAL_ERROR;
-                break;
-            }
-            memcpy(res[s].lf_lengths, lf_info[s].lengths, HYD_LF_CODES);
-            res[s].lf_alphabet = lf_info[s].alphabet;
-            res[s].lf_run_pairs = lf_info[s].run_pairs;
-            res[s].lf_bit_count = lf_info[s].bit_count;
-            res[s].lf_bits = lf_blob + lf_info[s].offset;
-        }
     }
-    for (size_t s = 0; s < n && !ret && !staged; s++) {
-        const size_t vbw = (shape->lfg[s].width + 7) >> 3, vbh = (shape->lfg[s].height + 7) >> 3;
-        uint32_t log_alpha = 0, running = 0;
-        if (!lf_on_gpu) {
-            res[s].dc = malloc(3 * vbw * vbh * sizeof(int32_t));
-            if (!res[s].dc) {
-                ret = HYD_NOMEM;
-                break;
-            }
-            ret = hydamd_read_dc(e->dev, (int)s, res[s].dc, vbw, vbh);
-        }
-        if (!ret)
-            ret = hydamd_read_tables(e->dev, (int)s, res[s].freq, res[s].alphabet, &log_alpha, &running);
-        if (!ret)
-            ret = hydamd_read_sections(e->dev, (int)s, res[s].bits, NULL);
-        if (running > max_alphabet)
-            max_alphabet = running;
-    }
+    if (!ret && !staged)
+        ret = hyd_read_table_results(e->dev, shape->lfg, n, res, &max_alphabet);
     if (ret) {
         ret = device_fail(e, ret);
         goto done;
     }
     TRACE("read back results", t0);
-    t0 = now_ms();
-    ret = assemble_frame(e, shape, res, max_alphabet, staged ? payload : NULL, payload_len, lf_sections, NULL);
+    t0 = hyd_now_ms();
+    ret = assemble_frame(e, shape, res, max_alphabet, view.hf, payload_len, lf_sections, NULL);
     TRACE("assemble frame (host)", t0);
 done:
     for (size_t s = 0; s < n; s++) {
@@ -1144,14 +751,12 @@ done:
     }
     free(lf_sections);
     free(res);
-    free(lf_info);
     free(lf_blob);
     return ret;
 }
 
 static int finish_frame(HYDEncoder *e, const HydFrameShape *shape) {
-    const size_t fg = ((shape->frame_width + 255) >> 8) * ((shape->frame_height + 255) >> 8);
-    if (shape->one_frame && fg > 1 && hydamd_lf_coder(e->dev) && !host_assembly_forced())
+    if (shape->one_frame && hyd_frame_groups(shape) > 1 && hydamd_lf_coder(e->dev) && !host_assembly_forced())
         return finish_frame_on_device(e, shape);
     const int ret = finish_frame_launch(e, shape);
     return ret ? ret : finish_frame_collect(e, shape);
@@ -1192,23 +797,19 @@ static void multi_release(HYDEncoder *e) {
  * (assemble_frame), the sections in one piece per shard.  One GPU's rate at best; the reference's bytes. */
 static int finish_frame_through_host(HYDEncoder *e, const HydFrameShape *shape, HydAmdContext *const *ctxs) {
     const int N = e->shards;
-    const size_t n = shape->lfg_count;
-    int ret = 0;
+    int ret = 0, device = 0;
     unsigned max_alphabet = 0;
     uint32_t floor_so_far = 0;
-    LfgResult *res = calloc(n, sizeof(LfgResult));
-    HydAmdLfInfo *lf_info = malloc(n * sizeof(HydAmdLfInfo));
+    HydLfgResult *res = calloc(shape->lfg_count, sizeof(HydLfgResult));
     uint8_t *lf_blob[HYD_MAX_DEVICES] = {0}, *hf[HYD_MAX_DEVICES] = {0};
     size_t hf_len[HYD_MAX_DEVICES] = {0};
     const uint8_t *seg_ptr[HYD_MAX_DEVICES];
-    double t0 = now_ms();
-    if (!res || !lf_info) {
-        ret = FAIL(e, HYD_NOMEM, "out of memory");
-        goto done;
-    }
+    double t0 = hyd_now_ms();
+    if (!res)
+        return FAIL(e, HYD_NOMEM, "out of memory");
     for (int d = 0; d < N && !ret; d++) {
         HydAmdContext *c = ctxs[d];
-        const int slots = (int)e->multi[d].slots;
+        const size_t first = e->multi[d].first_slot, slots = e->multi[d].slots;
         e->dev = c;
         if (d > 0) { /* the running maximum of entropy.c:459-460 over everything sent before this shard, as a host value */
             if ((ret = hydamd_set_alphabet_floor_device(c, NULL)) != 0 || (ret = hydamd_set_alphabet_floor(c, floor_so_far)) != 0 ||
@@ -1217,52 +818,32 @@ static int finish_frame_through_host(HYDEncoder *e, const HydFrameShape *shape, 
         }
         if ((ret = hydamd_sync(c)) != 0)
             break;
-        for (int i = 0; i < slots && !ret; i++) {
+        for (size_t i = 0; i < slots && !ret; i++) {
             uint32_t m = 0;
-            ret = hydamd_read_alphabet_max(c, i, &m);
+            ret = hydamd_read_alphabet_max(c, (int)i, &m);
             floor_so_far = m > floor_so_far ? m : floor_so_far;
         }
         if (ret)
             break;
-        LfgResult *r = res + e->multi[d].first_slot;
-        HydAmdLfInfo *li = lf_info + e->multi[d].first_slot;
-        const size_t lf_len = hydamd_lf_payload_size(c);
-        lf_blob[d] = malloc(lf_len ? lf_len : 1);
         hf_len[d] = hydamd_payload_size(c);
-        hf[d] = malloc(hf_len[d] ? hf_len[d] : 1);
-        if (!lf_blob[d] || !hf[d]) {
+        seg_ptr[d] = hf[d] = malloc(hf_len[d] ? hf_len[d] : 1);
+        if (!hf[d]) {
             ret = FAIL(e, HYD_NOMEM, "out of memory");
             goto done;
         }
-        if ((ret = hydamd_read_lf_streams(c, 0, slots, li)) != 0 || (ret = hydamd_read_lf_payload(c, lf_blob[d], lf_len)) != 0 ||
-            (ret = hydamd_read_payload(c, hf[d], hf_len[d])) != 0)
-            break;
-        for (int i = 0; i < slots && !ret; i++) {
-            uint32_t log_alpha = 0, running = 0;
-            if ((size_t)li[i].offset + (((size_t)li[i].bit_count + 7) >> 3) > lf_len) {
-                ret = HYD_INTERNAL_ERROR;
-                break;
-            }
-            memcpy(r[i].lf_lengths, li[i].lengths, HYD_LF_CODES);
-            r[i].lf_alphabet = li[i].alphabet;
-            r[i].lf_run_pairs = li[i].run_pairs;
-            r[i].lf_bit_count = li[i].bit_count;
-            r[i].lf_bits = lf_blob[d] + li[i].offset; /* borrowed from lf_blob[d] */
-            if ((ret = hydamd_read_tables(c, i, r[i].freq, r[i].alphabet, &log_alpha, &running)) == 0)
-                ret = hydamd_read_sections(c, i, r[i].bits, NULL);
-            if (running > max_alphabet)
-                max_alphabet = running;
-        }
-        seg_ptr[d] = hf[d];
+        if ((ret = hyd_read_lf_results(c, slots, res + first, &lf_blob[d], &device, &e->error)) != 0 && !device)
+            goto done;
+        if (!ret && (ret = hydamd_read_payload(c, hf[d], hf_len[d])) == 0)
+            ret = hyd_read_table_results(c, shape->lfg + first, slots, res + first, &max_alphabet);
     }
     if (ret) {
         ret = ret == HYD_NOMEM ? ret : device_fail(e, ret);
         goto done;
     }
     TRACE("every shard again, floors and results through the host", t0);
-    t0 = now_ms();
+    t0 = hyd_now_ms();
     {
-        const PayloadSegments segs = {(size_t)N, seg_ptr, hf_len};
+        const HydPayloadSegments segs = {(size_t)N, seg_ptr, hf_len};
         size_t hf_total = 0;
         for (int d = 0; d < N; d++)
             hf_total += hf_len[d];
@@ -1274,7 +855,6 @@ done:
         free(lf_blob[d]);
         free(hf[d]);
     }
-    free(lf_info);
     free(res);
     return ret;
 }
@@ -1289,7 +869,7 @@ done:
  * every later one to a single device (first use). */
 static int finish_frame_multi(HYDEncoder *e, const HydFrameShape *shape) {
     const int N = e->shards;
-    const double t0 = now_ms();
+    const double t0 = hyd_now_ms();
     HydShardFrame f = {.n = N, .latch = &g_pair_ok};
     HydShardOutcome o;
     int ret;
@@ -1319,7 +899,7 @@ static int finish_frame_multi(HYDEncoder *e, const HydFrameShape *shape) {
     const int first = !g_peer_reads_bad;
     g_peer_reads_bad = 1;
     pthread_mutex_unlock(&g_ctx_lock);
-    if (first || trace_on())
+    if (first || hyd_trace_on())
         fprintf(stderr, "[hydrium] %s: this frame is finished through host memory, later frames stay on one device\n", e->verify_msg);
     return finish_frame_through_host(e, shape, f.ctx);
 }
@@ -1389,6 +969,95 @@ HYDRIUM_EXPORT int hydamd_set_tile_pipeline(HYDEncoder *e, int depth) {
 
 HYDRIUM_EXPORT int hydamd_get_tile_pipeline(const HYDEncoder *e) { return e ? tile_pipeline_depth(e) : 0; }
 
+/* a context of `slots` LF-group slots on `device`, parked or new; hyd_send_tile's words for what can keep it from one */
+static int acquire_context(HYDEncoder *e, int device, size_t slots, const char *label, HydAmdContext **ctx) {
+    int st = 0;
+    const double tc = hyd_now_ms();
+    *ctx = ctx_acquire(device, slots, e->dev_linear, &st);
+    TRACE(label, tc);
+    if (*ctx)
+        return 0;
+    const char *m = hydamd_error(NULL);
+    if (st == HYD_NOMEM)
+        return FAIL(e, HYD_NOMEM, "out of device memory");
+    return FAIL(e, HYD_INTERNAL_ERROR, m && strstr(m, "no usable HIP device") ? "no usable HIP device (this build has no CPU fallback)"
+                                                                                : "GPU initialisation failed");
+}
+
+/* the tile (tx, ty), inside the image, as the LF group in place `slot` of the frame's send order */
+static const HydFrameLfg *record_tile(HYDEncoder *e, size_t slot, size_t tx, size_t ty) {
+    const size_t W = e->metadata.width, H = e->metadata.height;
+    HydFrameLfg *l = &e->sent[slot];
+    l->raster_id = e->one_frame ? ty * e->lfg_count_x + tx : 0;
+    l->x = tx;
+    l->y = ty;
+    l->width = (tx + 1) * e->tile_w > W ? W - tx * e->tile_w : e->tile_w;
+    l->height = (ty + 1) * e->tile_h > H ? H - ty * e->tile_h : e->tile_h;
+    return l;
+}
+
+/* the caller's samples of LF group *l into slot `local` of e->dev */
+static int upload_tile(HYDEncoder *e, int local, const void *const buffer[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride,
+                       HYDSampleFormat sample_fmt, const HydFrameLfg *l) {
+    const double tu = hyd_now_ms();
+    int ret = hydamd_encode_lf_group_host(e->dev, local, buffer, row_stride, pixel_stride, (int)sample_fmt, l->width, l->height,
+                                          (unsigned)l->raster_id);
+    if (!ret && eager_on()) { /* work on this LF group while the caller prepares / we stage the next tile */
+        ret = hydamd_submit_lf_group(e->dev, local);
+        /* and every fourth tile the LF coder for the four just transformed: a launch of it takes
+         * 0.25 ms whether it codes one LF group or sixteen, four tiles take 2 ms to stage.  Not behind the frame's final
+         * tile: there nothing is left to hide it, and the closing stage runs it on a side stream beside the
+         * (2 ms, latency-bound) entropy stage instead of in front of it */
+        if (!ret && e->one_frame && (local & 3) == 3 && !e->last_tile && hydamd_lf_coder(e->dev))
+            ret = hydamd_run_lf_coder(e->dev, local + 1, 0);
+    }
+    if (ret)
+        return device_fail(e, ret);
+    TRACE(e->shards > 1 ? "stage + upload tile (shard)" : "stage + upload tile", tu);
+    return 0;
+}
+
+/* the frame the LF groups in e->sent make up: the image (one-frame mode) or the tile e->sent[0] */
+static HydFrameShape frame_shape(const HYDEncoder *e, int is_last) {
+    HydFrameShape shape;
+    memset(&shape, 0, sizeof(shape));
+    shape.one_frame = e->one_frame;
+    shape.image_width = e->metadata.width;
+    shape.image_height = e->metadata.height;
+    shape.frame_width = e->one_frame ? e->metadata.width : e->sent[0].width;
+    shape.frame_height = e->one_frame ? e->metadata.height : e->sent[0].height;
+    shape.tile_count_x = e->tile_w >> 8;
+    shape.tile_count_y = e->tile_h >> 8;
+    shape.lfg_count = e->lfg_per_frame;
+    shape.lfg = e->sent;
+    shape.is_last = is_last;
+    return shape;
+}
+
+/* tile mode: this call's frame into its ring entry and on its way; the image's final tile collects every frame in flight,
+ * oldest first */
+static int pipe_launch(HYDEncoder *e, struct PendingTile *pend, const HydFrameShape *shape) {
+    pend->dev = e->dev;
+    pend->failed = e->dev_failed;
+    pend->lfg = e->sent[0];
+    pend->shape = *shape;
+    pend->shape.lfg = &pend->lfg;
+    e->tile_seq++;
+    const double tl = hyd_now_ms();
+    int ret = finish_frame_launch(e, &pend->shape);
+    TRACE("launch tile frame", tl);
+    pend->failed |= e->dev_failed;
+    if (ret)
+        return ret;
+    pend->active = 1;
+    for (int i = 0; e->last_tile && i < e->pipe_depth; i++) {
+        struct PendingTile *q = &e->pipe[(e->tile_seq + (size_t)i) % (size_t)e->pipe_depth];
+        if (q->active && (ret = pipe_collect(e, q)) != 0)
+            return ret;
+    }
+    return 0;
+}
+
 HYDRIUM_EXPORT HYDStatusCode hyd_send_tile(HYDEncoder *e, const void *const buffer[3], uint32_t tile_x, uint32_t tile_y,
                                            ptrdiff_t row_stride, ptrdiff_t pixel_stride, int is_last,
                                            HYDSampleFormat sample_fmt) {
@@ -1405,8 +1074,6 @@ HYDRIUM_EXPORT HYDStatusCode hyd_send_tile(HYDEncoder *e, const void *const buff
         return FAIL(e, HYD_API_ERROR, "the final tile of this image was already sent");
     if (e->one_frame && e->sent_mask[(size_t)tile_y * e->lfg_count_x + tile_x])
         return FAIL(e, HYD_API_ERROR, "this tile was already sent");
-    const size_t tw = ((size_t)tile_x + 1) * e->tile_w > W ? W - tile_x * e->tile_w : e->tile_w;
-    const size_t th = ((size_t)tile_y + 1) * e->tile_h > H ? H - tile_y * e->tile_h : e->tile_h;
     e->last_tile = is_last < 0 ? ((size_t)tile_x + 1) * e->tile_w >= W && ((size_t)tile_y + 1) * e->tile_h >= H : !!is_last;
 
     ret = emit_file_header(e);
@@ -1439,7 +1106,7 @@ HYDRIUM_EXPORT HYDStatusCode hyd_send_tile(HYDEncoder *e, const void *const buff
              * not when the last one arrives.  Without peer access between all of the devices the frame stays on this
              * encoder's home device (same bytes, one GPU's rate) */
             static int said;
-            if (!said++ || trace_on())
+            if (!said++ || hyd_trace_on())
                 fprintf(stderr, "[hydrium] no peer access between the %d devices of this frame: coded on device %d alone\n",
                         e->shards, e->home_device);
             e->shards = 1;
@@ -1450,143 +1117,62 @@ HYDRIUM_EXPORT HYDStatusCode hyd_send_tile(HYDEncoder *e, const void *const buff
             e->multi[d].slots = (size_t)(d + 1) * n / (size_t)e->shards - e->multi[d].first_slot;
             e->multi[d].entry = (e->home_index + d) % g_device_count;
         }
-        if (e->shards > 1 && trace_on())
+        if (e->shards > 1 && hyd_trace_on())
             fprintf(stderr, "[hydrium] frame dealt to %d shards, list entries %d.. (mod %d), assembled on entry %d = device %d\n",
                     e->shards, e->home_index, g_device_count, e->home_index, e->home_device);
     }
-    if (e->shards > 1) { /* one frame dealt to several devices: this tile goes to the shard that owns its place in send order */
-        const size_t slot = e->tiles_sent;
+    /* place the tile: the shard that owns its place in send order (one frame dealt to several devices), its ring entry
+     * (pipelined tile mode), or the encoder's own context; e->dev is that context from here on */
+    const size_t slot = e->one_frame ? e->tiles_sent : 0;
+    int local = (int)slot;
+    struct PendingTile *pend = NULL;
+    e->cur_pend = NULL;
+    if (e->shards > 1) {
         int d = e->shards - 1;
         while (d > 0 && slot < e->multi[d].first_slot)
             d--;
         struct Shard *sh = &e->multi[d];
-        e->cur_pend = NULL;
         e->dev_linear = e->metadata.linear_light != 0;
         if (!sh->dev) {
-            int st = 0;
-            const double tc = now_ms();
-            sh->dev = ctx_acquire(g_devices[sh->entry], sh->slots, e->dev_linear, &st);
-            TRACE("acquire device context (shard)", tc);
-            if (!sh->dev) {
-                const char *m = hydamd_error(NULL);
-                if (st == HYD_NOMEM)
-                    return FAIL(e, HYD_NOMEM, "out of device memory");
-                return FAIL(e, HYD_INTERNAL_ERROR, m && strstr(m, "no usable HIP device")
-                                                       ? "no usable HIP device (this build has no CPU fallback)"
-                                                       : "GPU initialisation failed");
-            }
+            if ((ret = acquire_context(e, g_devices[sh->entry], sh->slots, "acquire device context (shard)", &sh->dev)) != 0)
+                return ret;
             e->dev = sh->dev;
             if ((ret = hydamd_begin_frame(sh->dev, (unsigned)e->lfg_per_frame)) != 0)
                 return device_fail(e, ret);
         }
         e->dev = sh->dev;
-        const int local = (int)(slot - sh->first_slot);
-        HydFrameLfg *l = &e->sent[slot];
-        l->raster_id = (size_t)tile_y * e->lfg_count_x + tile_x;
-        l->x = tile_x;
-        l->y = tile_y;
-        l->width = tw;
-        l->height = th;
-        const double tu = now_ms();
-        ret = hydamd_encode_lf_group_host(sh->dev, local, buffer, row_stride, pixel_stride, (int)sample_fmt, tw, th, (unsigned)l->raster_id);
-        if (!ret && eager_on()) {
-            ret = hydamd_submit_lf_group(sh->dev, local);
-            if (!ret && (local & 3) == 3 && !e->last_tile && hydamd_lf_coder(sh->dev))
-                ret = hydamd_run_lf_coder(sh->dev, local + 1, 0);
+        local = (int)(slot - sh->first_slot);
+    } else {
+        if (!e->one_frame && tile_pipeline_depth(e) > 1) {
+            /* this tile's ring entry: the frame it still holds is the oldest in flight */
+            e->pipe_depth = tile_pipeline_depth(e);
+            pend = &e->pipe[e->tile_seq % (size_t)e->pipe_depth];
+            if (pend->active && (ret = pipe_collect(e, pend)) != 0)
+                return ret;
+            e->dev = pend->dev;
+            e->dev_failed = pend->failed;
+            e->cur_pend = pend;
         }
-        if (ret)
-            return device_fail(e, ret);
-        TRACE("stage + upload tile (shard)", tu);
-        e->sent_mask[l->raster_id] = 1;
-        e->tiles_sent++;
-        if (!e->last_tile) {
-            drain(e);
-            return HYD_OK;
-        }
-        if (e->tiles_sent != e->lfg_per_frame)
-            return FAIL(e, HYD_API_ERROR, "one-frame mode needs every tile before the final one");
-        HydFrameShape shape;
-        memset(&shape, 0, sizeof(shape));
-        shape.one_frame = 1;
-        shape.image_width = shape.frame_width = W;
-        shape.image_height = shape.frame_height = H;
-        shape.tile_count_x = e->tile_w >> 8;
-        shape.tile_count_y = e->tile_h >> 8;
-        shape.lfg_count = e->lfg_per_frame;
-        shape.lfg = e->sent;
-        shape.is_last = e->last_tile;
-        if ((ret = finish_frame_multi(e, &shape)) != 0)
-            return ret;
-        e->frame_done = 1;
-        if (!e->out)
-            return FAIL(e, HYD_API_ERROR, "buffer was never provided");
-        drain(e);
-        return e->stream_pos < e->stream.len ? HYD_NEED_MORE_OUTPUT : HYD_OK;
-    }
-
-    struct PendingTile *pend = NULL;
-    e->cur_pend = NULL;
-    if (!e->one_frame && tile_pipeline_depth(e) > 1) {
-        /* this tile's ring entry: the frame it still holds is the oldest in flight */
-        e->pipe_depth = tile_pipeline_depth(e);
-        pend = &e->pipe[e->tile_seq % (size_t)e->pipe_depth];
-        if (pend->active) {
-            ret = pipe_collect(e, pend);
-            if (ret)
+        if (!e->dev) {
+            e->dev_slots = e->lfg_per_frame;
+            e->dev_linear = e->metadata.linear_light != 0;
+            e->dev_failed = 0;
+            if ((ret = acquire_context(e, e->home_device, e->dev_slots, "acquire device context", &e->dev)) != 0)
                 return ret;
         }
-        e->dev = pend->dev;
-        e->dev_failed = pend->failed;
-        e->cur_pend = pend;
-    }
-    if (!e->dev) {
-        int st = 0;
-        const double tc = now_ms();
-        e->dev_slots = e->lfg_per_frame;
-        e->dev_linear = e->metadata.linear_light != 0;
-        e->dev_failed = 0;
-        e->dev = ctx_acquire(e->home_device, e->dev_slots, e->dev_linear, &st);
-        TRACE("acquire device context", tc);
-        if (!e->dev) {
-            const char *m = hydamd_error(NULL);
-            if (st == HYD_NOMEM)
-                return FAIL(e, HYD_NOMEM, "out of device memory");
-            return FAIL(e, HYD_INTERNAL_ERROR, m && strstr(m, "no usable HIP device")
-                                                   ? "no usable HIP device (this build has no CPU fallback)"
-                                                   : "GPU initialisation failed");
+        if (pend)
+            pend->dev = e->dev; /* the ring owns it from here on, whatever happens to this tile */
+        if (slot == 0) {
+            const double tb = hyd_now_ms();
+            ret = hydamd_begin_frame(e->dev, (unsigned)e->lfg_per_frame);
+            if (ret)
+                return device_fail(e, ret);
+            TRACE("begin frame", tb);
         }
     }
-    if (pend)
-        pend->dev = e->dev; /* the ring owns it from here on, whatever happens to this tile */
-    const size_t slot = e->one_frame ? e->tiles_sent : 0;
-    if (slot == 0) {
-        const double tb = now_ms();
-        ret = hydamd_begin_frame(e->dev, (unsigned)e->lfg_per_frame);
-        if (ret)
-            return device_fail(e, ret);
-        TRACE("begin frame", tb);
-    }
-    HydFrameLfg *l = &e->sent[slot];
-    l->raster_id = e->one_frame ? (size_t)tile_y * e->lfg_count_x + tile_x : 0;
-    l->x = tile_x;
-    l->y = tile_y;
-    l->width = tw;
-    l->height = th;
-    const double tu = now_ms();
-    ret = hydamd_encode_lf_group_host(e->dev, (int)slot, buffer, row_stride, pixel_stride, (int)sample_fmt, tw, th,
-                                      (unsigned)l->raster_id);
-    if (!ret && eager_on()) { /* work on this LF group while the caller prepares / we stage the next tile */
-        ret = hydamd_submit_lf_group(e->dev, (int)slot);
-        /* and every fourth tile the LF coder for the four just transformed: a launch of it takes
-         * 0.25 ms whether it codes one LF group or sixteen, four tiles take 2 ms to stage.  Not behind the frame's final
-         * tile: there nothing is left to hide it, and the closing stage runs it on a side stream beside the
-         * (2 ms, latency-bound) entropy stage instead of in front of it */
-        if (!ret && e->one_frame && (slot & 3) == 3 && !e->last_tile && hydamd_lf_coder(e->dev))
-            ret = hydamd_run_lf_coder(e->dev, (int)slot + 1, 0);
-    }
-    if (ret)
-        return device_fail(e, ret);
-    TRACE("stage + upload tile", tu);
+    const HydFrameLfg *l = record_tile(e, slot, tile_x, tile_y);
+    if ((ret = upload_tile(e, local, buffer, row_stride, pixel_stride, sample_fmt, l)) != 0)
+        return ret;
 
     if (e->one_frame) {
         e->sent_mask[l->raster_id] = 1;
@@ -1599,52 +1185,15 @@ HYDRIUM_EXPORT HYDStatusCode hyd_send_tile(HYDEncoder *e, const void *const buff
             return FAIL(e, HYD_API_ERROR, "one-frame mode needs every tile before the final one");
     }
 
-    HydFrameShape shape;
-    memset(&shape, 0, sizeof(shape));
-    shape.one_frame = e->one_frame;
-    shape.image_width = W;
-    shape.image_height = H;
-    shape.frame_width = e->one_frame ? W : tw;
-    shape.frame_height = e->one_frame ? H : th;
-    shape.tile_count_x = e->tile_w >> 8;
-    shape.tile_count_y = e->tile_h >> 8;
-    shape.lfg_count = e->lfg_per_frame;
-    shape.lfg = e->sent;
-    shape.is_last = e->last_tile;
-    if (pend) {
-        pend->dev = e->dev;
-        pend->failed = e->dev_failed;
-        pend->lfg = e->sent[0];
-        pend->shape = shape;
-        pend->shape.lfg = &pend->lfg;
-        e->tile_seq++;
-        const double tl = now_ms();
-        ret = finish_frame_launch(e, &pend->shape);
-        TRACE("launch tile frame", tl);
-        pend->failed |= e->dev_failed;
-        if (ret)
-            return ret;
-        pend->active = 1;
-        if (e->last_tile) { /* the image ends here: every frame in flight, oldest first */
-            for (int i = 0; i < e->pipe_depth; i++) {
-                struct PendingTile *q = &e->pipe[(e->tile_seq + (size_t)i) % (size_t)e->pipe_depth];
-                if (q->active && (ret = pipe_collect(e, q)) != 0)
-                    return ret;
-            }
-        }
-    } else {
-        ret = finish_frame(e, &shape);
-        if (ret)
-            return ret;
-    }
+    const HydFrameShape shape = frame_shape(e, e->last_tile);
+    ret = e->shards > 1 ? finish_frame_multi(e, &shape) : pend ? pipe_launch(e, pend, &shape) : finish_frame(e, &shape);
+    if (ret)
+        return ret;
     if (e->one_frame)
         e->frame_done = 1;
     /* the reference ends the tile with hyd_flush (encoder.c:1008): its error when no buffer is on loan
      * reaches the caller (libhydrium.c:193-195); HYD_NEED_MORE_OUTPUT is what the header documents */
-    if (!e->out)
-        return FAIL(e, HYD_API_ERROR, "buffer was never provided");
-    drain(e);
-    return e->stream_pos < e->stream.len ? HYD_NEED_MORE_OUTPUT : HYD_OK;
+    return hand_over(e);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -1737,8 +1286,8 @@ HYDRIUM_EXPORT HYDStatusCode hyd_set_suggested_icc_profile(HYDEncoder *e, const 
  * ------------------------------------------------------------------------------------------- */
 static int frame_from_parts(const HYDImageMetadata *md, int write_header, int is_last, size_t lfg_count,
                             const uint32_t *tile_xy, const int32_t *const *dc, const HydAmdLfStream *lf, const uint32_t *freq,
-                            const uint32_t *alphabet, const uint32_t *group_bits, unsigned max_alphabet,
-                            const uint8_t *payload, size_t payload_len, const PayloadSegments *segs, const uint8_t *icc,
+                            const uint32_t *alphabet, const uint32_t *group_bits, HydLfgResult *filled, unsigned max_alphabet,
+                            const uint8_t *payload, size_t payload_len, const HydPayloadSegments *segs, const uint8_t *icc,
                             size_t icc_size, uint8_t **out, size_t *out_len, const char **err) {
     HYDEncoder *e = hyd_encoder_new();
     if (!e)
@@ -1748,7 +1297,8 @@ static int frame_from_parts(const HYDImageMetadata *md, int write_header, int is
         ret = hyd_set_suggested_icc_profile(e, icc, icc_size);
     if (!ret && lfg_count != e->lfg_per_frame)
         ret = FAIL(e, HYD_API_ERROR, "a frame needs every one of its LF groups");
-    LfgResult *res = calloc(lfg_count ? lfg_count : 1, sizeof(LfgResult));
+    /* `filled`: the caller read the results from blobs already; else they arrive in the flat arrays */
+    HydLfgResult *res = filled ? filled : calloc(lfg_count ? lfg_count : 1, sizeof(HydLfgResult));
     if (!ret && !res)
         ret = HYD_NOMEM;
     if (!ret)
@@ -1763,16 +1313,14 @@ static int frame_from_parts(const HYDImageMetadata *md, int write_header, int is
                 ret = FAIL(e, HYD_API_ERROR, "tile out of bounds");
                 break;
             }
-            e->sent[s].raster_id = e->one_frame ? ty * e->lfg_count_x + tx : 0;
-            if (e->sent_mask[e->sent[s].raster_id]) {
+            const size_t id = record_tile(e, s, tx, ty)->raster_id;
+            if (e->sent_mask[id]) {
                 ret = FAIL(e, HYD_API_ERROR, "an LF group appears twice in the frame description");
                 break;
             }
-            e->sent_mask[e->sent[s].raster_id] = 1;
-            e->sent[s].x = tx;
-            e->sent[s].y = ty;
-            e->sent[s].width = (tx + 1) * e->tile_w > W ? W - tx * e->tile_w : e->tile_w;
-            e->sent[s].height = (ty + 1) * e->tile_h > H ? H - ty * e->tile_h : e->tile_h;
+            e->sent_mask[id] = 1;
+            if (filled)
+                continue;
             if (lf) { /* LF coefficients already coded (on a GPU): borrowed, like dc */
                 if (!lf[s].lengths || (!lf[s].bits && lf[s].bit_count) || lf[s].bit_count > UINT32_MAX) {
                     ret = FAIL(e, HYD_API_ERROR, "incomplete LF stream");
@@ -1792,18 +1340,7 @@ static int frame_from_parts(const HYDImageMetadata *md, int write_header, int is
         }
     }
     if (!ret) {
-        HydFrameShape shape;
-        memset(&shape, 0, sizeof(shape));
-        shape.one_frame = e->one_frame;
-        shape.image_width = md->width;
-        shape.image_height = md->height;
-        shape.frame_width = e->one_frame ? md->width : e->sent[0].width;
-        shape.frame_height = e->one_frame ? md->height : e->sent[0].height;
-        shape.tile_count_x = e->tile_w >> 8;
-        shape.tile_count_y = e->tile_h >> 8;
-        shape.lfg_count = lfg_count;
-        shape.lfg = e->sent;
-        shape.is_last = is_last;
+        const HydFrameShape shape = frame_shape(e, is_last);
         ret = assemble_frame(e, &shape, res, max_alphabet, payload, payload_len, NULL, segs);
     }
     if (!ret) {
@@ -1819,7 +1356,8 @@ static int frame_from_parts(const HYDImageMetadata *md, int write_header, int is
     }
     if (err)
         *err = e->error;
-    free(res);
+    if (!filled)
+        free(res);
     hyd_encoder_destroy(e);
     return ret;
 }
@@ -1831,7 +1369,7 @@ HYDRIUM_EXPORT int hydamd_frame_from_results(const HYDImageMetadata *md, int wri
                                              size_t icc_size, uint8_t **out, size_t *out_len, const char **err) {
     if (!dc)
         return HYD_API_ERROR;
-    return frame_from_parts(md, write_header, is_last, lfg_count, tile_xy, dc, NULL, freq, alphabet, group_bits, max_alphabet,
+    return frame_from_parts(md, write_header, is_last, lfg_count, tile_xy, dc, NULL, freq, alphabet, group_bits, NULL, max_alphabet,
                             payload, payload_len, NULL, icc, icc_size, out, out_len, err);
 }
 
@@ -1842,7 +1380,7 @@ HYDRIUM_EXPORT int hydamd_frame_from_streams(const HYDImageMetadata *md, int wri
                                              size_t icc_size, uint8_t **out, size_t *out_len, const char **err) {
     if (!lf)
         return HYD_API_ERROR;
-    return frame_from_parts(md, write_header, is_last, lfg_count, tile_xy, NULL, lf, freq, alphabet, group_bits, max_alphabet,
+    return frame_from_parts(md, write_header, is_last, lfg_count, tile_xy, NULL, lf, freq, alphabet, group_bits, NULL, max_alphabet,
                             payload, payload_len, NULL, icc, icc_size, out, out_len, err);
 }
 
@@ -1863,40 +1401,23 @@ HYDRIUM_EXPORT int hydamd_frame_from_blobs(const HYDImageMetadata *md, int write
         return HYD_API_ERROR;
     }
     size_t slots = 0, hf_total = 0;
-    for (size_t b = 0; b < nblobs; b++) {
-        const HydAmdBlobHeader *h = blobs[b];
-        if (!h || blob_sizes[b] < sizeof(*h) || h->magic != 0x42445948u || h->version != 1 || h->total_bytes > blob_sizes[b] ||
-            (h->status & HYDAMD_BLOB_RETRY) || h->lf_coded != 1) { /* 0: LF ints not coded; 0x101: a view, for device assemblers only */
+    HydBlobView view;
+    unsigned max_alphabet = 0;
+    for (size_t b = 0; b < nblobs; b++) { /* the headers: how many LF groups, how many bytes of HF sections */
+        const int cls = hyd_read_blob(blobs[b], blob_sizes[b], 0, &view, NULL, &max_alphabet);
+        if (cls != HYD_BLOB_USABLE || (view.header->status & 1u)) {
             if (err)
-                *err = h && blob_sizes[b] >= sizeof(*h) && (h->status & HYDAMD_BLOB_RETRY)
+                *err = cls == HYD_BLOB_NOT_USABLE && view.header && (view.header->status & HYDAMD_BLOB_RETRY)
                            ? "a blob is incomplete (its frame outgrew a buffer): rerun that shard"
-                           : bad;
+                           : cls != HYD_BLOB_USABLE ? bad : "Invalid NaN Float";
             return HYD_API_ERROR;
         }
-        const uint64_t lf_off = sizeof(*h) + (uint64_t)h->num_slots * sizeof(HydAmdBlobSlot);
-        /* every size is checked against the blob's own length before it enters a sum: a damaged lf_bytes near
-         * 2^64 must not wrap hf_off back into range */
-        const int sane = lf_off <= h->total_bytes && h->lf_bytes <= h->total_bytes - lf_off && h->hf_bytes <= h->total_bytes;
-        const uint64_t hf_off = sane ? (lf_off + h->lf_bytes + 15u) & ~(uint64_t)15u : 0;
-        if (!sane || hf_off > h->total_bytes || hf_off + h->hf_bytes != h->total_bytes) {
-            if (err)
-                *err = bad;
-            return HYD_API_ERROR;
-        }
-        if (h->status & 1u) {
-            if (err)
-                *err = "Invalid NaN Float";
-            return HYD_API_ERROR;
-        }
-        slots += h->num_slots;
-        hf_total += (size_t)h->hf_bytes;
+        slots += view.header->num_slots;
+        hf_total += view.hf_len;
     }
     const size_t lfg_x = (md->width + 2047) >> 11;
     uint32_t *tile_xy = malloc((slots ? slots : 1) * 2 * sizeof(uint32_t));
-    HydAmdLfStream *lf = calloc(slots ? slots : 1, sizeof(HydAmdLfStream));
-    uint32_t *freq = malloc((slots ? slots : 1) * sizeof(((HydAmdBlobSlot *)0)->freq));
-    uint32_t *alpha = malloc((slots ? slots : 1) * sizeof(((HydAmdBlobSlot *)0)->alphabet));
-    uint32_t *bits = malloc((slots ? slots : 1) * sizeof(((HydAmdBlobSlot *)0)->group_bits));
+    HydLfgResult *res = calloc(slots ? slots : 1, sizeof(HydLfgResult));
     /* a frame of one group splices its only section bit by bit and wants it in one piece; any other
      * frame takes the sections piece by piece, straight from the blobs */
     const int one_group = ((md->width + 255) >> 8) * ((md->height + 255) >> 8) == 1;
@@ -1904,58 +1425,40 @@ HYDRIUM_EXPORT int hydamd_frame_from_blobs(const HYDImageMetadata *md, int write
     const uint8_t **seg_ptr = malloc(nblobs * sizeof(*seg_ptr));
     size_t *seg_len = malloc(nblobs * sizeof(*seg_len));
     int ret = HYD_OK;
-    unsigned max_alphabet = 0;
-    if (!tile_xy || !lf || !freq || !alpha || !bits || (one_group && !payload) || !seg_ptr || !seg_len) {
+    if (!tile_xy || !res || (one_group && !payload) || !seg_ptr || !seg_len) {
         ret = HYD_NOMEM;
         if (err)
             *err = "out of memory";
     }
     size_t s = 0, hf_pos = 0;
     for (size_t b = 0; b < nblobs && !ret; b++) {
-        const HydAmdBlobHeader *h = blobs[b];
-        const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(h + 1);
-        const uint8_t *lf_bytes = (const uint8_t *)blobs[b] + sizeof(*h) + (size_t)h->num_slots * sizeof(HydAmdBlobSlot);
-        const uint8_t *hf_bytes = (const uint8_t *)blobs[b] + h->total_bytes - h->hf_bytes;
-        for (uint32_t i = 0; i < h->num_slots && !ret; i++, s++) {
-            if (rec[i].table_error || rec[i].lf.error ||
-                (uint64_t)rec[i].lf.offset + (((uint64_t)rec[i].lf.bit_count + 7) >> 3) > h->lf_bytes) {
-                ret = HYD_INTERNAL_ERROR;
-                if (err)
-                    *err = rec[i].table_error ? "ANS table construction failed on the device"
-                                              : rec[i].lf.error ? "LF code construction failed on the device" : bad;
-                break;
-            }
-            tile_xy[2 * s] = (uint32_t)(rec[i].preset % lfg_x);
-            tile_xy[2 * s + 1] = (uint32_t)(rec[i].preset / lfg_x);
-            lf[s].lengths = rec[i].lf.lengths;
-            lf[s].alphabet = rec[i].lf.alphabet;
-            lf[s].run_pairs = rec[i].lf.run_pairs;
-            lf[s].bits = lf_bytes + rec[i].lf.offset;
-            lf[s].bit_count = rec[i].lf.bit_count;
-            memcpy(freq + s * HYD_FRAME_MAX_CLUSTERS * HYD_FRAME_ALPHABET, rec[i].freq, sizeof(rec[i].freq));
-            memcpy(alpha + s * HYD_FRAME_MAX_CLUSTERS, rec[i].alphabet, sizeof(rec[i].alphabet));
-            memcpy(bits + s * HYDAMD_GROUPS_PER_LFG, rec[i].group_bits, sizeof(rec[i].group_bits));
-            if (rec[i].running_max_alphabet > max_alphabet)
-                max_alphabet = rec[i].running_max_alphabet;
+        const int cls = hyd_read_blob(blobs[b], blob_sizes[b], 0, &view, res + s, &max_alphabet);
+        if (cls != HYD_BLOB_USABLE) {
+            ret = HYD_INTERNAL_ERROR;
+            if (err)
+                *err = cls == HYD_BLOB_TABLE_ERROR ? "ANS table construction failed on the device"
+                                                   : cls == HYD_BLOB_LF_ERROR ? "LF code construction failed on the device" : bad;
+            break;
+        }
+        for (uint32_t i = 0; i < view.header->num_slots; i++, s++) {
+            tile_xy[2 * s] = (uint32_t)(view.slot[i].preset % lfg_x);
+            tile_xy[2 * s + 1] = (uint32_t)(view.slot[i].preset / lfg_x);
         }
         if (payload)
-            memcpy(payload + hf_pos, hf_bytes, (size_t)h->hf_bytes);
-        seg_ptr[b] = hf_bytes;
-        seg_len[b] = (size_t)h->hf_bytes;
-        hf_pos += (size_t)h->hf_bytes;
+            memcpy(payload + hf_pos, view.hf, view.hf_len);
+        seg_ptr[b] = view.hf;
+        seg_len[b] = view.hf_len;
+        hf_pos += view.hf_len;
     }
     if (!ret) {
-        const PayloadSegments segs = {nblobs, seg_ptr, seg_len};
-        ret = frame_from_parts(md, write_header, is_last, slots, tile_xy, NULL, lf, freq, alpha, bits, max_alphabet, payload,
+        const HydPayloadSegments segs = {nblobs, seg_ptr, seg_len};
+        ret = frame_from_parts(md, write_header, is_last, slots, tile_xy, NULL, NULL, NULL, NULL, NULL, res, max_alphabet, payload,
                                hf_total, one_group ? NULL : &segs, icc, icc_size, out, out_len, err);
     }
     free((void *)seg_ptr);
     free(seg_len);
     free(tile_xy);
-    free(lf);
-    free(freq);
-    free(alpha);
-    free(bits);
+    free(res);
     free(payload);
     return ret;
 }
@@ -1977,9 +1480,6 @@ int hyd_internal_file_header(const HYDImageMetadata *md, const uint8_t *icc, siz
     hyd_encoder_destroy(e);
     return ret;
 }
-
-/* the geometry-only bits that close an LF group section (cached per shape for the life of the process) */
-const HydBits *hyd_internal_lf_tail(size_t vbw, size_t vbh) { return lf_tail(vbw, vbh); }
 
 HYDRIUM_EXPORT void hydamd_free(void *p) {
     if (!p)
@@ -2015,7 +1515,7 @@ HYDRIUM_EXPORT void hydamd_trim_cache(void) {
         free(spares[i]);
 }
 
-/* the CPU-only tests drive the same function through libhydrium_hosttest.so */
+/* the CPU-only tests drive the same function through libhydrium_probe.so */
 #ifdef HYD_TEST_HOOKS
 #define HYDT_EXPORT __attribute__((visibility("default")))
 HYDT_EXPORT int hydt_frame_from_stages(const HYDImageMetadata *md, int write_header, int is_last, size_t lfg_count,
@@ -2085,6 +1585,6 @@ HYDT_EXPORT int hydt_lf_group_coded(size_t vbw, size_t vbh, const uint8_t *lengt
     const char *err = NULL;
     const HydLfCoded lf = {lengths, alphabet, run_pairs, bits, bit_count};
     hb_init(&b);
-    return hydt_take(&b, hyd_write_lf_group_coded(&b, vbw, vbh, &lf, lf_tail(vbw, vbh), &err), out, out_len);
+    return hydt_take(&b, hyd_write_lf_group_coded(&b, vbw, vbh, &lf, hyd_internal_lf_tail(vbw, vbh), &err), out, out_len);
 }
 #endif /* HYD_TEST_HOOKS */

@@ -81,9 +81,9 @@ int hyd_write_hf_global(HydBits *out, unsigned num_presets, size_t num_frame_gro
                         const uint32_t (*freq)[HYD_FRAME_MAX_CLUSTERS][HYD_FRAME_ALPHABET],
                         const uint32_t (*alphabet)[HYD_FRAME_MAX_CLUSTERS], unsigned max_alphabet, const char **err);
 
-/* for the planners of the device-side assemblers (assembler.c, tiled.c), from encoder.c: the file header hyd_send_tile
- * writes in front of this image's first frame, and the cached geometry-only bits that close an LF group section
- * (NULL: the cache is full, code them with hyd_write_lf_group_tail) */
+/* for the planners of the device-side assemblers (assembler.c, tiled.c): from encoder.c the file header hyd_send_tile
+ * writes in front of this image's first frame, from hostframe.c the cached geometry-only bits that close an LF group
+ * section (NULL: the cache is full, code them with hyd_write_lf_group_tail) */
 int hyd_internal_file_header(const HYDImageMetadata *md, const uint8_t *icc, size_t icc_size, HydBits *out, const char **err);
 const HydBits *hyd_internal_lf_tail(size_t vbw, size_t vbh);
 

@@ -282,6 +282,52 @@ def test_frame_from_blobs_single_process_and_malformed_input(ref_lib, image):
     fails([blobs[0], bytes(huge)])
 
 
+def test_blob_reader_classes_for_the_staged_read_back(image):
+    """The staged read-back of hyd_send_tile goes through the reader hydamd_frame_from_blobs uses (csrc/host/hostframe.c,
+    hyd_read_blob) and needs more of it: a blob of a frame that was rerun, of another slot count or cut short is "not
+    usable" (the frame is then read the separate way), damaged sizes are "malformed" and a slot's error word is kept apart
+    (both HYD_INTERNAL_ERROR there).  A one-slot blob from oracle results; every blob is handed over as a bytes object of
+    exactly the size the reader is told, so a read past it leaves the object."""
+    import ctypes as C
+
+    import torch
+
+    import oracle_engine
+    from hydrium_amd import device
+
+    USABLE, NOT_USABLE, MALFORMED, TABLE_ERROR = 0, 1, 2, 3
+    e = oracle_engine.OracleShardEngine(image("photo", 200, 120, 8), [0])
+    e.enqueue_transform()
+    e.enqueue_entropy(torch.tensor([0], dtype=torch.int32))
+    out = torch.zeros(e.blob_bound(), dtype=torch.uint8)
+    e.export_blob(out)
+    n = int(device.blob_header(out[:64].numpy().tobytes())["total_bytes"])
+    good = out[:n].numpy().tobytes()
+    if glue._d is None:
+        glue._d = glue._lib()
+    d = glue._d
+    d.hydt_blob_class.restype = C.c_int
+    d.hydt_blob_class.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t]
+
+    def cls(blob, expected=1, **header):
+        b = np.frombuffer(blob, np.uint8).copy()
+        for k, v in header.items():
+            b[:64].view(device.BLOB_HEADER_DTYPE)[k] = v
+        return d.hydt_blob_class(b.tobytes(), b.size, expected)
+
+    assert cls(good) == USABLE and cls(good, expected=0) == USABLE
+    assert cls(good, status=2) == NOT_USABLE                  # HYDAMD_BLOB_RETRY: the frame was rerun after it was staged
+    assert cls(good, expected=2) == NOT_USABLE
+    assert cls(good[:n - 1]) == NOT_USABLE                    # one byte short of total_bytes
+    assert cls(b"") == NOT_USABLE and cls(good[:63]) == NOT_USABLE
+    lf_off = 64 + device.BLOB_SLOT_DTYPE.itemsize
+    for lf_bytes, hf_bytes in ((2 ** 64 - lf_off - 16, 64), (2 ** 64 - 1, 0), (32, 2 ** 63), (n, 0)):
+        assert cls(good, lf_bytes=lf_bytes, hf_bytes=hf_bytes) == MALFORMED, (lf_bytes, hf_bytes)
+    bad = bytearray(good)
+    bad[64 + 12] = 1                                          # slot 0: table_error
+    assert cls(bytes(bad)) == TABLE_ERROR
+
+
 def test_frame_buffers_are_reused_without_changing_a_byte(ref_lib, image):
     """Frames above 1 MB leave through a buffer the library may keep when it comes back (hydamd_free) and hand to the
     next frame: a larger frame, a smaller one and the first again give the reference's bytes each time, before and
