@@ -1,0 +1,404 @@
+/*
+ * assemble_batch.hip — the frames of a BATCH of independent one-frame images, assembled side by side on the GPU into
+ * finished files.
+ *
+ * hydamd_encode_image_batch codes F pictures of one shape (n LF groups each) as one launch group and leaves their
+ * sections and coded LF streams in the context's buffers.  Here one launch sequence in the context's stream takes
+ * those results as a view (hydamd_export_batch_owned: one header, the F x n slot records, frame k's at k n .. k n + n - 1,
+ * the packed LF streams and HF sections in place, per-slot extents) and writes F complete files — file header, frame
+ * header with is_last, TOC, LFGlobal, LF groups, HFGlobal, HF sections: what the reference writes for each picture
+ * alone — back to back at byte granularity into one buffer, with the table of their offsets beside it:
+ *
+ *   k_batch_prepare      grid F x (n + 1), block 256: workgroup (f, s) is part s of frame f of hydk_asm_writers.h's
+ *                        asm_frame — the same writers as k_asm_prepare's, on frame f's slot records and frame f's
+ *                        scratch; the frame's last finisher lays it out, its pieces counted from the frame's first byte
+ *   k_batch_prepare_one  (shapes of ONE LF group, a single bit-contiguous section included) grid F, block 64: the
+ *                        tile assembler's per-frame preparation and pieces (hydk_tiles.h) with a plan whose one frame
+ *                        carries the file header and is_last
+ *   k_batch_place        one workgroup: the union of the frames' error words, a prefix sum over their sizes = the
+ *                        offsets table, every piece moved to its frame's start, the range k_pieces_copy reads
+ *   k_pieces_copy        (assemble.hip) every output word composed from the pieces that touch it and stored once; the
+ *                        padding that ends a section, and a file, is the gap no piece covers
+ *
+ * Every frame of a batch has the same pixel-independent bytes: ONE plan (csrc/host/batch.c builds it with the frame
+ * planner, or the tile planner for n = 1) serves all of them.  No host synchronisation between the entropy stage and
+ * the finished files.
+ */
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+
+#include <new>
+
+#include "../../../include/hydrium_amd.h"
+#include "hydk_tiles.h"
+#include "hydk_common.h"
+#include "hydk_asm_writers.h"
+
+namespace {
+
+constexpr int kMaxSlots = HYDAMD_MAX_LF_GROUPS; /* F x n: the slots of one context */
+/* pieces of a batch: F x (3 n + 5) with F n <= 255 is at most 3 x 255 + 5 F <= 765 + 5 x 255 = 2040; frames of one
+ * LF group take HYDK_TILE_PIECES = 8 = 3 + 5 each, the same bound */
+static_assert(3 * kMaxSlots + 5 * kMaxSlots <= HYDK_COPY_MAX_PIECES && HYDK_TILE_PIECES * kMaxSlots <= HYDK_COPY_MAX_PIECES,
+              "k_pieces_copy keeps every end in LDS");
+
+struct BatchScratch { /* device pointers; frame f's part of each array is what asm_frame / hydk_tile_prepare gets */
+    uint32_t *head;       /* [slots][kHeadWords]            | n = 1: [frames][HYDK_TILE_HEAD_WORDS] */
+    uint32_t *head_bits;  /* [slots]                        | n = 1: null, like sizes, slot_hf, npieces, err, done */
+    uint64_t *sizes;      /* [frames][toc_n] */
+    uint64_t *slot_hf;    /* [slots] */
+    uint32_t *hfg;        /* [frames][hfg_words]            | n = 1: [frames][HYDK_TILE_MID_WORDS] */
+    uint32_t *toc;        /* [frames][toc_words]            | n = 1: [frames][HYDK_TILE_TOC_WORDS] */
+    HydkPiece *pieces;    /* [frames][pieces_per_frame] */
+    uint32_t *npieces;    /* [frames] */
+    uint32_t *err;        /* [frames] */
+    uint32_t *done;       /* [frames] */
+    uint64_t *result;     /* [frames][4] error word, 0, bytes of the frame, HFGlobal's bit count */
+    uint64_t *offsets;    /* [frames + 1] the table the caller gets */
+    uint64_t *range;      /* [4] error word, 0, bytes of all files (what k_pieces_copy reads), bytes the output must hold */
+    uint32_t n, toc_n, hfg_words, toc_words, pieces_per_frame;
+};
+
+__device__ __forceinline__ Scratch frame_scratch(const BatchScratch &B, uint32_t f) {
+    Scratch S;
+    S.head = B.head + (size_t)f * B.n * kHeadWords;
+    S.head_bits = B.head_bits + (size_t)f * B.n;
+    S.sizes = B.sizes + (size_t)f * B.toc_n;
+    S.slot_hf = B.slot_hf + (size_t)f * B.n;
+    S.hfg = B.hfg + (size_t)f * B.hfg_words;
+    S.toc = B.toc + (size_t)f * B.toc_words;
+    S.pieces = B.pieces + (size_t)f * B.pieces_per_frame;
+    S.npieces = B.npieces + f;
+    S.err = B.err + f;
+    S.done = B.done + f;
+    S.result = B.result + (size_t)f * 4;
+    S.hfg_words = B.hfg_words;
+    S.toc_words = B.toc_words;
+    return S;
+}
+
+/* ---- k_batch_prepare: grid = frames x (n + 1), block = 256 ---- */
+__global__ __launch_bounds__(256) void k_batch_prepare(const uint8_t *__restrict__ planb, const uint8_t *__restrict__ blob, uint64_t blob_cap,
+                                                       const HydkTileExtent *__restrict__ ext, uint32_t frames, BatchScratch B) {
+    __builtin_amdgcn_s_setprio(3); /* late work of a batch whose stream holds nothing else */
+    const uint32_t n = B.n, f = blockIdx.x / (n + 1), part = blockIdx.x % (n + 1);
+    BlobArgs blobs;
+    blobs.p[0] = blob;
+    blobs.cap[0] = blob_cap;
+    /* the frame's HF sections: its slots' extents, one behind the other in the packed string (k_batch_extents; the
+     * layout holds their sum against the section sizes the slot records give, k_batch_place the grand total against the
+     * header; until the header has been checked — asm_slot, asm_hfglobal — nothing is read through these) */
+    const HydkTileExtent first = ext[(size_t)f * n], last = ext[(size_t)f * n + n - 1];
+    AsmFrame F;
+    F.slot_base = f * n;
+    F.view_slots = frames * n;
+    F.hf = blob_hf_bytes(blob) + first.hf_off;
+    F.hf_bytes = last.hf_off + last.hf_bytes - first.hf_off;
+    asm_frame(planb, blobs, frame_scratch(B, f), F, part, n + 1, ~0ull, nullptr);
+}
+
+/* ---- k_batch_prepare_one: grid = frames, block = 64 (one wavefront); every frame is frame 0 of the tile plan ---- */
+__global__ __launch_bounds__(64) void k_batch_prepare_one(const uint8_t *__restrict__ planb, const uint8_t *__restrict__ blob,
+                                                          const HydkTileExtent *__restrict__ ext, uint32_t frames, BatchScratch B) {
+    const uint32_t f = blockIdx.x;
+    uint64_t *result = B.result + (size_t)f * 4;
+    const uint32_t bad = blob_view_check(blob, frames);
+    if (bad) {
+        if (threadIdx.x == 0) {
+            result[0] = bad;
+            result[1] = result[2] = result[3] = 0;
+        }
+        return;
+    }
+    const HydkTilePlan *plan = (const HydkTilePlan *)planb;
+    const HydkTileFrame fr = ((const HydkTileFrame *)(planb + plan->frames_off))[0];
+    const HydkTileShape *sh = &plan->shapes[fr.shape];
+    const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
+    const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + f;
+    uint32_t *head = B.head + (size_t)f * HYDK_TILE_HEAD_WORDS, *mid = B.hfg + (size_t)f * HYDK_TILE_MID_WORDS,
+             *toc = B.toc + (size_t)f * HYDK_TILE_TOC_WORDS;
+    const HydkTileSizes z = hydk_tile_prepare_wave(planb, &fr, sh, rec, h->lf_bytes, head, mid, toc);
+    if (threadIdx.x == 0) {
+        const HydkTileExtent x = ext[f];
+        uint32_t e = z.err;
+        if (!e && (x.hf_bytes != z.hf_bytes || x.hf_off + z.hf_bytes > h->hf_bytes))
+            e = HYDK_ASM_E_SIZE;
+        if (!e)
+            hydk_tile_pieces(planb, &fr, sh, &z, rec, head, mid, toc, blob_lf_bytes(blob) + x.lf_off, blob_hf_bytes(blob) + x.hf_off, 0,
+                             B.pieces + (size_t)f * HYDK_TILE_PIECES);
+        result[0] = e;
+        result[1] = 0;
+        result[2] = e ? 0 : z.frame_bytes;
+        result[3] = 0;
+    }
+}
+
+/* ---- k_batch_place: grid 1, block 256 ---- */
+__global__ __launch_bounds__(256) void k_batch_place(const uint8_t *__restrict__ blob, const HydkTileExtent *__restrict__ ext, uint32_t frames,
+                                                     BatchScratch B, uint64_t out_cap, uint64_t *h_result /* pinned [4 + frames + 1] */) {
+    __shared__ uint64_t s_wave[4];
+    __shared__ uint64_t s_at[256];
+    __shared__ uint32_t s_err;
+    const uint32_t t = threadIdx.x;
+    const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
+    const uint32_t slots = frames * B.n;
+    uint32_t e = 0;
+    uint64_t size = 0;
+    if (t < frames) {
+        e = (uint32_t)B.result[(size_t)t * 4];
+        size = B.result[(size_t)t * 4 + 2];
+    }
+    if (t == 0) {
+        s_err = 0;
+        /* the frames' HF extents together are the packed string, no more and no less */
+        uint32_t he = blob_ident(h, slots);
+        if (!he && ext[slots - 1].hf_off + ext[slots - 1].hf_bytes != h->hf_bytes)
+            he = HYDK_ASM_E_SIZE;
+        e |= he;
+    }
+    __syncthreads();
+    if (e)
+        atomicOr(&s_err, e);
+    __syncthreads();
+    const uint32_t err = s_err;
+    uint64_t total = 0;
+    const uint64_t at = scan256(err ? 0 : size, s_wave, &total);
+    s_at[t] = at;
+    const uint32_t fin = err ? err : total > out_cap ? HYDK_ASM_E_SPACE : 0u;
+    if (t < frames) {
+        B.offsets[t] = at;
+        h_result[4 + t] = at;
+    }
+    __syncthreads();
+    if (!fin) {
+        const uint32_t np = frames * B.pieces_per_frame;
+        for (uint32_t i = t; i < np; i += 256)
+            B.pieces[i].dst_bit += s_at[i / B.pieces_per_frame] * 8u;
+    }
+    if (t == 0) {
+        B.offsets[frames] = total;
+        h_result[4 + frames] = total;
+        B.range[0] = fin;
+        B.range[1] = 0;
+        B.range[2] = fin ? 0 : total;
+        B.range[3] = total;
+        for (int i = 0; i < 4; i++)
+            h_result[i] = B.range[i];
+    }
+}
+
+} // namespace
+
+struct HydkBatchAsm {
+    int device = 0;
+    char error[256] = "";
+    uint8_t *arena = nullptr;     /* the plan, then every array of B: one allocation */
+    uint8_t *plan = nullptr;
+    int max_frames = 0;
+    bool one = false;             /* frames of one LF group: the plan is a tile plan (hydk_tiles.h) */
+    BatchScratch B = {};
+    uint64_t fixed = 0;           /* bytes of a frame beyond its packed LF streams and HF sections, at most */
+    uint64_t *h_result = nullptr; /* pinned [4 + max_frames + 1]: the range quadruple, then the offsets table */
+    uint8_t *out = nullptr;       /* the files: owned, grown on demand (hydk_batch_reserve) */
+    uint64_t out_cap = 0;
+};
+
+extern "C" {
+
+const char *hydk_batch_error(HydkBatchAsm *a) { return a ? a->error : "null batch assembler"; }
+
+void hydk_batch_destroy(HydkBatchAsm *a) {
+    if (!a)
+        return;
+    (void)hipSetDevice(a->device);
+    if (a->out)
+        (void)hipFree(a->out);
+    if (a->arena)
+        (void)hipFree(a->arena);
+    if (a->h_result)
+        (void)hipHostFree(a->h_result);
+    delete a;
+}
+
+/* scratch for batches of up to `max_frames` frames of the plan's shape; the plan — a HydkAsmPlan of one blob, or a
+ * HydkTilePlan of one frame for shapes of one LF group — is copied to the device */
+int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_bytes, HydkBatchAsm **out) {
+    if (!out)
+        return ST_API_ERROR;
+    *out = nullptr;
+    if (max_frames < 1 || !plan || plan_bytes < 8)
+        return ST_API_ERROR;
+    const uint32_t magic = *(const uint32_t *)plan;
+    const HydkAsmPlan *ap = (const HydkAsmPlan *)plan;
+    const HydkTilePlan *tp = (const HydkTilePlan *)plan;
+    HydkBatchAsm *a = new (std::nothrow) HydkBatchAsm();
+    if (!a)
+        return ST_NOMEM;
+    a->device = device;
+    a->max_frames = max_frames;
+    BatchScratch &B = a->B;
+    size_t head_words = 0;
+    if (magic == HYDK_TILE_MAGIC && plan_bytes >= sizeof(HydkTilePlan) && tp->total_bytes == plan_bytes && tp->num_frames == 1 &&
+        max_frames <= HYDK_TILE_MAX_FRAMES) {
+        a->one = true;
+        B.n = 1;
+        B.pieces_per_frame = HYDK_TILE_PIECES;
+        B.hfg_words = HYDK_TILE_MID_WORDS;
+        B.toc_words = HYDK_TILE_TOC_WORDS;
+        B.toc_n = 1;
+        head_words = HYDK_TILE_HEAD_WORDS;
+        const HydkTileFrame *fr = (const HydkTileFrame *)((const uint8_t *)plan + tp->frames_off);
+        a->fixed = (uint64_t)fr->prefix_bytes + tp->shapes[fr->shape].lfglobal_bytes +
+                   4u * (HYDK_TILE_HEAD_WORDS + HYDK_TILE_MID_WORDS + HYDK_TILE_TOC_WORDS) + (tp->shapes[fr->shape].tail_bits >> 3) + 16u;
+    } else if (magic == HYDK_ASM_PLAN_MAGIC && plan_bytes >= sizeof(HydkAsmPlan) && ap->total_bytes == plan_bytes && ap->num_blobs == 1 &&
+               ap->num_slots >= 1 && (uint64_t)ap->num_slots * (uint64_t)max_frames <= (uint64_t)kMaxSlots &&
+               ap->num_presets * ap->clusters_per_preset <= 256 && ap->toc_n == 2 + ap->num_slots + ap->frame_groups &&
+               ap->ntails <= HYDK_ASM_MAX_TAILS) {
+        const uint32_t C = ap->num_presets * ap->clusters_per_preset;
+        B.n = ap->num_slots;
+        B.pieces_per_frame = 3 * ap->num_slots + 5;
+        /* HFGlobal: the fixed fields, two bits, a configuration of <= 9 bits and a histogram of <= 73 words per cluster */
+        B.hfg_words = (ap->hfpre_bits + 2u + C * 9u + 31u) / 32u + C * 73u + 2u;
+        B.toc_words = ap->toc_n + 2u; /* entries of <= 32 bits */
+        B.toc_n = ap->toc_n;
+        head_words = (size_t)B.n * kHeadWords;
+        uint32_t tail = 0;
+        for (uint32_t i = 0; i < ap->ntails; i++)
+            tail = ap->tail_bits[i] > tail ? ap->tail_bits[i] : tail;
+        a->fixed = (uint64_t)ap->prefix_bytes + ap->lfglobal_bytes + 4ull * (B.hfg_words + B.toc_words) +
+                   (uint64_t)B.n * (4u * kHeadWords + (tail >> 3) + 2u) + 16u;
+    } else {
+        delete a;
+        return ST_API_ERROR;
+    }
+    const size_t F = (size_t)max_frames;
+    /* one arena: the plan (+ 16: the copy kernel reads whole words), then the arrays, each 16-byte aligned.  The
+     * one-LF-group path keeps its sizes in registers and needs no counters: those arrays stay null */
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t off = at;
+        at += (bytes + 15) & ~(size_t)15;
+        return off;
+    };
+    const size_t o_plan = take(plan_bytes + 16), o_head = take(F * head_words * 4), o_hfg = take(F * B.hfg_words * 4),
+                 o_toc = take(F * B.toc_words * 4), o_pieces = take(F * B.pieces_per_frame * sizeof(HydkPiece)),
+                 o_result = take(F * 4 * 8), o_offsets = take((F + 1) * 8), o_range = take(4 * 8);
+    const bool one = a->one;
+    const size_t o_head_bits = one ? 0 : take(F * B.n * 4), o_sizes = one ? 0 : take(F * B.toc_n * 8), o_slot_hf = one ? 0 : take(F * B.n * 8),
+                 o_npieces = one ? 0 : take(F * 4), o_counters = one ? 0 : take(2 * F * 4);
+    auto alloc = [&]() -> int {
+        HYDK_TRY(a, hipSetDevice(device));
+        HYDK_TRY(a, hipMalloc(&a->arena, at));
+        uint8_t *m = a->arena;
+        a->plan = m + o_plan;
+        B.head = (uint32_t *)(m + o_head);
+        B.hfg = (uint32_t *)(m + o_hfg);
+        B.toc = (uint32_t *)(m + o_toc);
+        B.pieces = (HydkPiece *)(m + o_pieces);
+        B.result = (uint64_t *)(m + o_result);
+        B.offsets = (uint64_t *)(m + o_offsets);
+        B.range = (uint64_t *)(m + o_range);
+        if (!one) {
+            B.head_bits = (uint32_t *)(m + o_head_bits);
+            B.sizes = (uint64_t *)(m + o_sizes);
+            B.slot_hf = (uint64_t *)(m + o_slot_hf);
+            B.npieces = (uint32_t *)(m + o_npieces);
+            B.err = (uint32_t *)(m + o_counters); /* err and done: zero between batches */
+            B.done = B.err + F;
+            HYDK_TRY(a, hipMemset(B.err, 0, 2 * F * sizeof(uint32_t)));
+        }
+        HYDK_TRY(a, hipMemcpy(a->plan, plan, plan_bytes, hipMemcpyHostToDevice));
+        HYDK_TRY(a, hipStreamSynchronize(nullptr)); /* the memset runs in the NULL stream, which the context's stream does not wait for */
+        HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, (4 + F + 1) * sizeof(uint64_t), hipHostMallocDefault));
+        memset(a->h_result, 0, (4 + F + 1) * sizeof(uint64_t));
+        return ST_OK;
+    };
+    const int st = alloc();
+    if (st != ST_OK) {
+        hydk_batch_destroy(a);
+        return st;
+    }
+    *out = a;
+    return ST_OK;
+}
+
+/* bytes a frame can add to its packed LF streams and HF sections: what the plan fixes and the scratch can hold */
+uint64_t hydk_batch_fixed_bytes(HydkBatchAsm *a) { return a ? a->fixed : 0; }
+
+/* enqueue the assembly of `frames` frames on `stream`, behind whatever fills the view `blob` (`blob_cap` readable bytes)
+ * and its extents (hydamd_export_batch_owned over frames x n slots): three launches */
+int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t blob_cap, const void *extents, void *stream) {
+    if (!a || !blob || !extents || !a->out || frames < 1 || frames > (uint32_t)a->max_frames)
+        return hydk_fail(a, ST_API_ERROR, "bad batch");
+    if (((uintptr_t)a->out & 3u) || ((uintptr_t)blob & 15u))
+        return hydk_fail(a, ST_API_ERROR, "output buffer must be 4-byte aligned, the view 16-byte aligned");
+    HYDK_TRY(a, hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    const HydkTileExtent *ext = (const HydkTileExtent *)extents;
+    if (a->one)
+        hipLaunchKernelGGL(k_batch_prepare_one, dim3(frames), dim3(64), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob, ext, frames, a->B);
+    else
+        hipLaunchKernelGGL(k_batch_prepare, dim3(frames * (a->B.n + 1)), dim3(256), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob,
+                           blob_cap, ext, frames, a->B);
+    HYDK_TRY(a, hipGetLastError());
+    hipLaunchKernelGGL(k_batch_place, dim3(1), dim3(256), 0, st, (const uint8_t *)blob, ext, frames, a->B, a->out_cap, a->h_result);
+    HYDK_TRY(a, hipGetLastError());
+    HYDK_TRY(a, hydk::launch_pieces_copy(a->B.pieces, frames * a->B.pieces_per_frame, nullptr, a->B.range, a->out, st));
+    return ST_OK;
+}
+
+/* the output buffer holds at least `bytes`.  Waits for `stream` when it has to be replaced. */
+int hydk_batch_reserve(HydkBatchAsm *a, uint64_t bytes, void *stream) {
+    if (!a)
+        return ST_API_ERROR;
+    if (bytes <= a->out_cap)
+        return ST_OK;
+    HYDK_TRY(a, hipSetDevice(a->device));
+    HYDK_TRY(a, hipStreamSynchronize((hipStream_t)stream));
+    if (a->out)
+        (void)hipFree(a->out);
+    a->out = nullptr;
+    a->out_cap = 0;
+    HYDK_TRY(a, hipMalloc(&a->out, bytes + 16));
+    a->out_cap = bytes;
+    return ST_OK;
+}
+
+const uint8_t *hydk_batch_out(HydkBatchAsm *a) { return a ? a->out : nullptr; }
+const uint64_t *hydk_batch_offsets_dev(HydkBatchAsm *a) { return a ? a->B.offsets : nullptr; }
+
+int hydk_batch_wait(HydkBatchAsm *a, void *stream) {
+    if (!a)
+        return ST_API_ERROR;
+    HYDK_TRY(a, hipSetDevice(a->device));
+    HYDK_TRY(a, hipStreamSynchronize((hipStream_t)stream));
+    return ST_OK;
+}
+
+/* after the stream has been synchronised: the device's error word (HYDK_ASM_E_*), the bytes of all files, and the
+ * host copy of the offsets table ([frames + 1], valid until the next run) */
+int hydk_batch_result(HydkBatchAsm *a, uint32_t *err, uint64_t *total, const uint64_t **offsets) {
+    if (!a)
+        return ST_API_ERROR;
+    if (err)
+        *err = (uint32_t)a->h_result[0];
+    if (total)
+        *total = a->h_result[3];
+    if (offsets)
+        *offsets = a->h_result + 4;
+    return ST_OK;
+}
+
+int hydk_batch_read(HydkBatchAsm *a, uint64_t from, uint8_t *dst, size_t n) {
+    if (!a || !dst || !a->out || from + n > a->out_cap)
+        return hydk_fail(a, ST_API_ERROR, "nothing to read");
+    if (!n)
+        return ST_OK;
+    HYDK_TRY(a, hipSetDevice(a->device));
+    HYDK_TRY(a, hipMemcpy(dst, a->out + from, n, hipMemcpyDeviceToHost));
+    return ST_OK;
+}
+
+} /* extern "C" */

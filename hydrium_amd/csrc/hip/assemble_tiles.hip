@@ -45,15 +45,7 @@ struct TileScratch { /* device pointers */
     uint64_t *result;       /* [4] error word, first byte of this group, bytes behind it (what k_pieces_copy reads), bytes the output must hold */
 };
 
-/* the tile assembler follows views only (hydamd_export_batch_owned) */
-__device__ __forceinline__ uint32_t view_check(const uint8_t *blob, uint32_t frames) {
-    const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    if (h->lf_coded != kLfCodedView || !(h->reserved[1] | h->reserved[2]) || !(h->reserved[3] | h->reserved[4]) || (h->reserved[1] & 3u))
-        return HYDK_ASM_E_BLOB;
-    return blob_ident(h, frames);
-}
-
-/* ---- a batch's results, frame by frame: grid 1, block 256 ---- */
+/* ---- a batch's results, slot by slot (a tile frame is one slot; `frames` = slots of the view): grid 1, block 256 ---- */
 __global__ __launch_bounds__(256) void k_batch_extents(const uint8_t *__restrict__ blob, uint32_t frames, HydkTileExtent *__restrict__ ext) {
     __shared__ uint64_t s_wave[4];
     const uint32_t t = threadIdx.x;
@@ -76,16 +68,9 @@ __global__ __launch_bounds__(256) void k_batch_extents(const uint8_t *__restrict
 /* ---- k_tiles_prepare: grid = frames, block = 64 (one wavefront) ---- */
 __global__ __launch_bounds__(64) void k_tiles_prepare(const uint8_t *__restrict__ planb, uint32_t first_frame, const uint8_t *__restrict__ blob,
                                                       uint32_t frames, TileScratch S) {
-    __shared__ uint32_t s_head[HYDK_TILE_HEAD_WORDS];
-    __shared__ uint32_t s_mid[HYDK_TILE_MID_WORDS];
-    __shared__ uint32_t s_toc[HYDK_TILE_TOC_WORDS];
-    __shared__ uint8_t s_len[HYDK_LF_CODES];
-    __shared__ HydkTileScratch s_scratch;
-    __shared__ HydkTileSizes s_sizes;
-    const int t = threadIdx.x;
     const uint32_t f = blockIdx.x;
-    if (view_check(blob, frames)) { /* the layout kernel reports it */
-        if (t == 0) {
+    if (blob_view_check(blob, frames)) { /* the layout kernel reports it */
+        if (threadIdx.x == 0) {
             HydkTileSizes z = {};
             S.sizes[f] = z;
         }
@@ -93,29 +78,11 @@ __global__ __launch_bounds__(64) void k_tiles_prepare(const uint8_t *__restrict_
     }
     const HydkTilePlan *plan = (const HydkTilePlan *)planb;
     const HydkTileFrame fr = ((const HydkTileFrame *)(planb + plan->frames_off))[first_frame + f];
-    const HydkTileShape *sh = &plan->shapes[fr.shape];
     const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + f;
-    for (int i = t; i < HYDK_TILE_HEAD_WORDS; i += 64)
-        s_head[i] = 0;
-    for (int i = t; i < HYDK_TILE_MID_WORDS; i += 64)
-        s_mid[i] = 0;
-    for (int i = t; i < HYDK_TILE_TOC_WORDS; i += 64)
-        s_toc[i] = 0;
-    for (int i = t; i < HYDK_LF_CODES; i += 64)
-        s_len[i] = rec->lf.lengths[i];
-    __syncthreads();
-    hydk_tile_prepare(planb, &fr, sh, rec, s_len, ((const HydAmdBlobHeader *)blob)->lf_bytes, s_head, s_mid, s_toc, &s_scratch, &s_sizes);
-    __syncthreads();
-    const HydkTileSizes z = s_sizes;
-    uint32_t *head = S.head + (size_t)f * HYDK_TILE_HEAD_WORDS, *mid = S.mid + (size_t)f * HYDK_TILE_MID_WORDS,
-             *toc = S.toc + (size_t)f * HYDK_TILE_TOC_WORDS;
-    for (uint32_t i = t; i < (z.head_bits + 31u) >> 5; i += 64)
-        head[i] = s_head[i];
-    for (uint32_t i = t; i < (z.mid_bits + 31u) >> 5; i += 64)
-        mid[i] = s_mid[i];
-    for (uint32_t i = t; i < (z.toc_bits + 31u) >> 5; i += 64)
-        toc[i] = s_toc[i];
-    if (t == 0)
+    const HydkTileSizes z = hydk_tile_prepare_wave(planb, &fr, &plan->shapes[fr.shape], rec, ((const HydAmdBlobHeader *)blob)->lf_bytes,
+                                                   S.head + (size_t)f * HYDK_TILE_HEAD_WORDS, S.mid + (size_t)f * HYDK_TILE_MID_WORDS,
+                                                   S.toc + (size_t)f * HYDK_TILE_TOC_WORDS);
+    if (threadIdx.x == 0)
         S.sizes[f] = z;
 }
 
@@ -126,7 +93,7 @@ __global__ __launch_bounds__(256) void k_tiles_layout(const uint8_t *__restrict_
     __shared__ uint64_t s_wave[4];
     const uint32_t t = threadIdx.x;
     const uint64_t start = first_group ? 0 : *S.cursor;
-    uint32_t e = view_check(blob, frames);
+    uint32_t e = blob_view_check(blob, frames);
     const HydkTilePlan *plan = (const HydkTilePlan *)planb;
     const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
     HydkTileSizes z = {};
@@ -259,8 +226,10 @@ int hydk_tiles_run(HydkTileAsm *a, uint32_t first_frame, uint32_t frames, const 
     HYDK_TRY(a, hipSetDevice(a->device));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_tiles_prepare, dim3(frames), dim3(64), 0, st, (const uint8_t *)a->plan, first_frame, (const uint8_t *)blob, frames, a->S);
+    HYDK_TRY(a, hipGetLastError());
     hipLaunchKernelGGL(k_tiles_layout, dim3(1), dim3(256), 0, st, (const uint8_t *)a->plan, first_frame, (const uint8_t *)blob, frames,
                        (const HydkTileExtent *)extents, a->S, first_group, out_cap, a->h_result);
+    HYDK_TRY(a, hipGetLastError());
     HYDK_TRY(a, hydk::launch_pieces_copy(a->S.pieces, frames * HYDK_TILE_PIECES, nullptr, a->S.result, out, st));
     return ST_OK;
 }

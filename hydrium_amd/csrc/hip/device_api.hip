@@ -1874,15 +1874,14 @@ int hydamd_export_frame_owned(HydAmdContext *ctx, int num_slots, const void **bl
     return export_owned(ctx, num_slots, blob_dev, capacity, false);
 }
 
-/* The results of a BATCH of one-LF-group frames (hydamd_begin_batch(ctx, 1, frames)) as a view: the slot records of all
- * its slots behind one header, the packed LF streams and HF sections left in place — and, because frame k's bytes in
- * those two strings follow from all frames before it, a table that states them: extents[k] = {LF offset, LF bytes, HF
- * offset, HF bytes}, written by a kernel behind the export.  hydamd_export_frame* keeps refusing batches. */
+/* The results of a BATCH of frames (hydamd_begin_batch(ctx, n, frames)) as a view: the slot records of all its slots
+ * behind one header, frame k's at k n .. k n + n - 1, the packed LF streams and HF sections left in place — and, because
+ * a slot's bytes in those two strings follow from all slots before it, a table that states them: extents[s] = {LF offset,
+ * LF bytes, HF offset, HF bytes} of slot s, written by a kernel behind the export (a frame's HF sections: from its first
+ * slot's offset to its last slot's end).  hydamd_export_frame* keeps refusing batches. */
 int hydamd_export_batch_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity, const void **extents_dev) {
     if (!ctx || !extents_dev)
         return ST_API_ERROR;
-    if (ctx->slots_per_frame > 1)
-        return fail(ctx, ST_API_ERROR, "the batch view is for frames of one LF group");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t need = (size_t)(num_slots > 0 ? num_slots : 1) * sizeof(HydAmdBatchExtent);
     if (need > ctx->batch_extents_cap) {

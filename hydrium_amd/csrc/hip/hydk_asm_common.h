@@ -60,6 +60,14 @@ static __device__ __forceinline__ uint32_t blob_ident(const HydAmdBlobHeader *h,
     return ((h->status & HYDAMD_BLOB_RETRY) ? HYDK_ASM_E_RETRY : 0u) | ((h->status & 1u) ? HYDK_ASM_E_NAN : 0u);
 }
 
+/* a batch view of `slots` slot records (hydamd_export_batch_owned), for the assemblers that follow views only */
+static __device__ __forceinline__ uint32_t blob_view_check(const uint8_t *blob, uint32_t slots) {
+    const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
+    if (h->lf_coded != kLfCodedView || !(h->reserved[1] | h->reserved[2]) || !(h->reserved[3] | h->reserved[4]) || (h->reserved[1] & 3u))
+        return HYDK_ASM_E_BLOB;
+    return blob_ident(h, slots);
+}
+
 /* block-wide exclusive prefix sum over 256 threads; returns the thread's offset, *total the sum */
 static __device__ __forceinline__ uint64_t scan256(uint64_t v, uint64_t *s_wave /* [4] */, uint64_t *total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

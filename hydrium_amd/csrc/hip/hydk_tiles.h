@@ -221,4 +221,40 @@ HYDK_HD void hydk_tile_pieces(const uint8_t *planb, const HydkTileFrame *fr, con
     P[7] = hydk_piece(bit, hf_src, z->hf_bytes * 8u);
 }
 
+#if defined(__HIPCC__)
+/* One workgroup of 64 threads (one wavefront): hydk_tile_prepare for the frame `fr` of the plan from slot record `rec`,
+ * through LDS, the strings copied out to head / mid / toc (device arrays of HYDK_TILE_*_WORDS words).  Every lane
+ * gets the frame's sizes.  What k_tiles_prepare (assemble_tiles.hip) and k_batch_prepare_one (assemble_batch.hip) run. */
+static __device__ __forceinline__ HydkTileSizes hydk_tile_prepare_wave(const uint8_t *planb, const HydkTileFrame *fr, const HydkTileShape *sh,
+                                                                       const HydAmdBlobSlot *rec, uint64_t lf_capacity, uint32_t *head,
+                                                                       uint32_t *mid, uint32_t *toc) {
+    __shared__ uint32_t s_head[HYDK_TILE_HEAD_WORDS];
+    __shared__ uint32_t s_mid[HYDK_TILE_MID_WORDS];
+    __shared__ uint32_t s_toc[HYDK_TILE_TOC_WORDS];
+    __shared__ uint8_t s_len[HYDK_LF_CODES];
+    __shared__ HydkTileScratch s_scratch;
+    __shared__ HydkTileSizes s_sizes;
+    const int t = threadIdx.x;
+    for (int i = t; i < HYDK_TILE_HEAD_WORDS; i += 64)
+        s_head[i] = 0;
+    for (int i = t; i < HYDK_TILE_MID_WORDS; i += 64)
+        s_mid[i] = 0;
+    for (int i = t; i < HYDK_TILE_TOC_WORDS; i += 64)
+        s_toc[i] = 0;
+    for (int i = t; i < HYDK_LF_CODES; i += 64)
+        s_len[i] = rec->lf.lengths[i];
+    __syncthreads();
+    hydk_tile_prepare(planb, fr, sh, rec, s_len, lf_capacity, s_head, s_mid, s_toc, &s_scratch, &s_sizes);
+    __syncthreads();
+    const HydkTileSizes z = s_sizes;
+    for (uint32_t i = t; i < (z.head_bits + 31u) >> 5; i += 64)
+        head[i] = s_head[i];
+    for (uint32_t i = t; i < (z.mid_bits + 31u) >> 5; i += 64)
+        mid[i] = s_mid[i];
+    for (uint32_t i = t; i < (z.toc_bits + 31u) >> 5; i += 64)
+        toc[i] = s_toc[i];
+    return z;
+}
+#endif
+
 #endif /* HYD_TILE_LAYOUT_H_ */

@@ -1,0 +1,403 @@
+/*
+ * batch.c — a BATCH of one-frame images whose pixels already sit in HBM, every one a finished file, from C
+ * (include/hydrium_amd.h, hydamd_batch_*).
+ *
+ * hydamd_encode_image_batch codes F independent pictures of one shape as one launch group — the fastest regime the
+ * library has — and stops at sections and coded LF streams in the context's buffers.  Here one launch sequence behind
+ * the batch's entropy stage (csrc/hip/assemble_batch.hip) turns them into F complete files, each what the reference
+ * writes for that picture alone (libhydrium.c:172-203, encoder.c:968-1005), back to back in one device buffer with a
+ * table of their offsets.
+ *
+ * Policy HERE, as in tiled.c wherever the two coincide: the PLAN — every byte that does not depend on the pixels, the
+ * same for every frame of a batch — built once per object with the planners the other device-side assemblers use
+ * (assembler.c's for shapes of several LF groups, tiled.c's shape planner for shapes of one); ONE context of
+ * max_frames x n slots and one stream; the host waits once per batch (hydamd_sync, which is also where a batch that
+ * outgrew the context's buffers is rerun), checks what the assembly left and repeats it if the batch was rerun; after a
+ * failure the stream is drained before the call returns.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "bitio.h"
+#include "frame.h"
+#include "hydrium_amd.h"
+#include "libhydrium/libhydrium.h"
+#include "planbuf.h"
+
+#include "../hip/hydk_tiles.h"
+
+#ifndef HYDRIUM_EXPORT
+#define HYDRIUM_EXPORT __attribute__((visibility("default")))
+#endif
+
+typedef struct HydkBatchAsm HydkBatchAsm; /* assemble_batch.hip */
+int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_bytes, HydkBatchAsm **out);
+void hydk_batch_destroy(HydkBatchAsm *a);
+const char *hydk_batch_error(HydkBatchAsm *a);
+uint64_t hydk_batch_fixed_bytes(HydkBatchAsm *a);
+int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t blob_cap, const void *extents, void *stream);
+int hydk_batch_reserve(HydkBatchAsm *a, uint64_t bytes, void *stream);
+const uint8_t *hydk_batch_out(HydkBatchAsm *a);
+const uint64_t *hydk_batch_offsets_dev(HydkBatchAsm *a);
+int hydk_batch_wait(HydkBatchAsm *a, void *stream);
+int hydk_batch_result(HydkBatchAsm *a, uint32_t *err, uint64_t *total, const uint64_t **offsets);
+int hydk_batch_read(HydkBatchAsm *a, uint64_t from, uint8_t *dst, size_t n);
+
+/* k_pieces_copy takes at most 2040 pieces (HYDK_COPY_MAX_PIECES): a batch has F (3 n + 5) of them, and with F n <= 255
+ * that is at most 3 x 255 + 5 x 255 = 2040 (frames of one LF group: 8 F) */
+#define BATCH_MAX_SLOTS HYDAMD_MAX_LF_GROUPS
+
+/* ---------------------------------------------------------------------------------------------
+ * the plan
+ * ------------------------------------------------------------------------------------------- */
+/* shapes of one LF group: a tile plan (hydk_tiles.h) whose one frame is the whole image — file header, the one-frame
+ * frame header, is_last */
+static int plan_one_lf_group(const HYDImageMetadata *md, const uint8_t *icc, size_t icc_size, uint8_t **plan_out, size_t *plan_len,
+                             const char **err) {
+    int ret = HYD_OK;
+    Buf buf = {0};
+    HydBits bits, part;
+    hb_init(&bits);
+    hb_init(&part);
+    HydkTilePlan plan;
+    memset(&plan, 0, sizeof(plan));
+    plan.magic = HYDK_TILE_MAGIC;
+    plan.num_frames = 1;
+    plan.nshapes = 1;
+    buf_reserve(&buf, sizeof(plan));
+    ret = hydk_tile_plan_shape(&buf, &bits, &part, md->width, md->height, &plan.shapes[0], err);
+    const size_t frames_off = ret ? 0 : buf_reserve(&buf, sizeof(HydkTileFrame));
+    plan.frames_off = (uint32_t)frames_off;
+    if (!ret && !buf.failed) {
+        HydFrameLfg l;
+        memset(&l, 0, sizeof(l));
+        l.width = md->width;
+        l.height = md->height;
+        HydFrameShape shape;
+        memset(&shape, 0, sizeof(shape));
+        shape.one_frame = 1;
+        shape.image_width = shape.frame_width = md->width;
+        shape.image_height = shape.frame_height = md->height;
+        shape.tile_count_x = shape.tile_count_y = 8;
+        shape.lfg_count = 1;
+        shape.lfg = &l;
+        shape.is_last = 1;
+        hb_reset(&bits);
+        ret = hyd_internal_file_header(md, icc, icc_size, &bits, err);
+        if (!ret)
+            ret = hyd_write_frame_header(&bits, &shape, err);
+        if (ret && !*err)
+            *err = "frame header could not be written";
+        if (!ret) {
+            hb_align(&bits);
+            HydkTileFrame fr;
+            uint32_t nbits = 0;
+            memset(&fr, 0, sizeof(fr));
+            fr.prefix_off = (uint32_t)buf_add_bits(&buf, &bits, &nbits);
+            fr.prefix_bytes = nbits >> 3;
+            if (!buf.failed)
+                memcpy(buf.p + frames_off, &fr, sizeof(fr));
+        }
+    }
+    if (!ret && (buf.failed || bits.failed || part.failed)) {
+        *err = "out of memory";
+        ret = HYD_NOMEM;
+    }
+    if (!ret) {
+        buf.len = (buf.len + 15) & ~(size_t)15;
+        plan.total_bytes = (uint32_t)buf.len;
+        memcpy(buf.p, &plan, sizeof(plan));
+        *plan_out = buf.p;
+        *plan_len = buf.len;
+        buf.p = NULL;
+    }
+    free(buf.p);
+    hb_free(&bits);
+    hb_free(&part);
+    return ret;
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * the object
+ * ------------------------------------------------------------------------------------------- */
+struct HydAmdBatch {
+    int device, max_frames;
+    size_t W, H, n; /* n: LF groups of a frame */
+    HydAmdContext *ctx;
+    HydkBatchAsm *as;
+    int frames;     /* of the batch in flight / finished */
+    int in_flight, have_result;
+    size_t total;
+    uint64_t offsets[BATCH_MAX_SLOTS + 1];
+    unsigned reruns;
+    char err[256];
+};
+
+static char g_create_error[256];
+
+static int fail(HydAmdBatch *b, int code, const char *what, const char *detail) {
+    snprintf(b->err, sizeof(b->err), "%s%s%s", what, detail && *detail ? ": " : "", detail && *detail ? detail : "");
+    return code;
+}
+
+HYDRIUM_EXPORT const char *hydamd_batch_error(HydAmdBatch *b) { return b ? b->err : g_create_error; }
+
+HYDRIUM_EXPORT void hydamd_batch_destroy(HydAmdBatch *b) {
+    if (!b)
+        return;
+    if (b->ctx) {
+        (void)hydamd_sync(b->ctx);
+        hydk_batch_destroy(b->as);
+        hydamd_destroy(b->ctx);
+    }
+    free(b);
+}
+
+HYDRIUM_EXPORT HydAmdBatch *hydamd_batch_create(int device, const HYDImageMetadata *md, int max_frames, const uint8_t *icc, size_t icc_size,
+                                                int *status) {
+    int st = HYD_API_ERROR;
+    HydAmdBatch *b = NULL;
+    uint8_t *plan = NULL;
+    uint32_t *ids = NULL;
+    size_t plan_len = 0, n = 0;
+    const char *err = NULL;
+    g_create_error[0] = 0;
+    if (!md) {
+        err = "null metadata";
+        goto out;
+    }
+    if (md->tile_size_shift_x >= 0 || md->tile_size_shift_y >= 0) {
+        err = "a batch holds one-frame images: both tile_size_shift_x and tile_size_shift_y must be -1";
+        goto out;
+    }
+    if (!md->width || !md->height || md->width > (1u << 30) || md->height > (1u << 30)) {
+        err = "width or height out of bounds";
+        goto out;
+    }
+    n = (((size_t)md->width + 2047) >> 11) * (((size_t)md->height + 2047) >> 11);
+    if (n > HYDAMD_MAX_LF_GROUPS || n == 128) {
+        err = "unsupported number of LF groups per frame (1..255 except 128)";
+        goto out;
+    }
+    if (max_frames < 1) {
+        err = "max_frames must be at least 1";
+        goto out;
+    }
+    if ((size_t)max_frames * n > BATCH_MAX_SLOTS) {
+        err = "max_frames times the LF groups of a frame must not exceed 255 (the slots of one context)";
+        goto out;
+    }
+    if (hydamd_device_count() < 1 || device < 0 || device >= hydamd_device_count()) {
+        st = HYD_INTERNAL_ERROR;
+        err = "no usable HIP device";
+        goto out;
+    }
+    {
+        /* the bytes the plan is made of are written by an encoder object, which also checks the image's bounds */
+        HYDEncoder *e = hyd_encoder_new();
+        st = e ? hyd_set_metadata(e, md) : HYD_NOMEM;
+        if (st && e)
+            snprintf(g_create_error, sizeof(g_create_error), "%s", hyd_error_message_get(e));
+        hyd_encoder_destroy(e);
+        if (st)
+            goto out;
+    }
+    if (n == 1) {
+        st = plan_one_lf_group(md, icc, icc_size, &plan, &plan_len, &err);
+    } else { /* one blob (the batch view), its LF groups in raster order */
+        const uint32_t slots = (uint32_t)n;
+        ids = malloc(n * sizeof(*ids));
+        for (size_t i = 0; ids && i < n; i++)
+            ids[i] = (uint32_t)i;
+        st = ids ? hydk_plan_frame(md, 1, 1, 1, &slots, ids, icc, icc_size, &plan, &plan_len, &err) : HYD_NOMEM;
+    }
+    if (st)
+        goto out;
+    b = calloc(1, sizeof(*b));
+    if (!b) {
+        st = HYD_NOMEM;
+        goto out;
+    }
+    b->device = device;
+    b->max_frames = max_frames;
+    b->W = md->width;
+    b->H = md->height;
+    b->n = n;
+    b->ctx = hydamd_create(device, (int)((size_t)max_frames * n), md->linear_light != 0, 0, &st);
+    if (!b->ctx) {
+        snprintf(g_create_error, sizeof(g_create_error), "%s", hydamd_error(NULL));
+        free(b);
+        b = NULL;
+        goto out;
+    }
+    if ((st = hydamd_set_lf_coder(b->ctx, 2)) != 0 || (st = hydamd_set_rans_waves(b->ctx, 5)) != 0) {
+        snprintf(g_create_error, sizeof(g_create_error), "%s", hydamd_error(b->ctx));
+    } else if ((st = hydk_batch_create(device, max_frames, plan, plan_len, &b->as)) != 0) {
+        snprintf(g_create_error, sizeof(g_create_error), "the batch assembler could not be created (status %d)", st);
+    }
+    if (st) {
+        hydamd_destroy(b->ctx);
+        free(b);
+        b = NULL;
+        goto out;
+    }
+    st = HYD_OK;
+out:
+    if (err && !g_create_error[0])
+        snprintf(g_create_error, sizeof(g_create_error), "%s", err);
+    free(plan);
+    free(ids);
+    if (status)
+        *status = st;
+    return b;
+}
+
+/* after a failure once work was enqueued: nothing of this object is left running when the call returns */
+static void drain(HydAmdBatch *b) {
+    (void)hydamd_sync(b->ctx);
+    (void)hydk_batch_wait(b->as, hydamd_get_stream(b->ctx));
+    b->in_flight = 0;
+}
+
+/* The output holds whatever the context's buffers can: their bound for ALL the object's slots plus what the plan and
+ * the assembler's scratch add per frame.  Replacing the buffer waits for the stream, so it is sized for max_frames and
+ * reserved BEFORE a batch is enqueued (an object's first batch allocates, later ones find it there); it is looked at
+ * again before every assembly, where only a context that has enlarged its buffers since (a rerun) makes it grow. */
+static int reserve_output(HydAmdBatch *b) {
+    const uint64_t want = (uint64_t)hydamd_blob_bound(b->ctx, (int)((size_t)b->max_frames * b->n)) +
+                          (uint64_t)b->max_frames * hydk_batch_fixed_bytes(b->as);
+    const int st = hydk_batch_reserve(b->as, want, hydamd_get_stream(b->ctx));
+    return st ? fail(b, st, "output buffer", hydk_batch_error(b->as)) : HYD_OK;
+}
+
+/* the batch's results as a view, and its assembly behind them */
+static int assemble(HydAmdBatch *b) {
+    const void *blob = NULL, *ext = NULL;
+    size_t cap = 0;
+    const int slots = (int)((size_t)b->frames * b->n);
+    void *stream = hydamd_get_stream(b->ctx);
+    int st = reserve_output(b);
+    if (st)
+        return st;
+    st = hydamd_export_batch_owned(b->ctx, slots, &blob, &cap, &ext);
+    if (st)
+        return fail(b, st, "batch view", hydamd_error(b->ctx));
+    st = hydk_batch_run(b->as, (uint32_t)b->frames, blob, cap, ext, stream);
+    return st ? fail(b, st, "batch assembly", hydk_batch_error(b->as)) : HYD_OK;
+}
+
+HYDRIUM_EXPORT int hydamd_encode_batch(HydAmdBatch *b, int frames, const void *const *src, ptrdiff_t row_stride, ptrdiff_t pixel_stride,
+                                       int sample_fmt) {
+    if (!b)
+        return HYD_API_ERROR;
+    if (frames < 1 || frames > b->max_frames)
+        return fail(b, HYD_API_ERROR, "frames must be between 1 and max_frames", NULL);
+    if (!src)
+        return fail(b, HYD_API_ERROR, "null pixel pointer", NULL);
+    for (int i = 0; i < 3 * frames; i++)
+        if (!src[i])
+            return fail(b, HYD_API_ERROR, "null pixel pointer", NULL);
+    if (sample_fmt != HYD_UINT8 && sample_fmt != HYD_UINT16 && sample_fmt != HYD_FLOAT32)
+        return fail(b, HYD_API_ERROR, "Invalid Sample Format", NULL);
+    if (b->in_flight)
+        return fail(b, HYD_API_ERROR, "a batch is in flight: hydamd_batch_result first", NULL);
+    b->err[0] = 0;
+    b->have_result = 0;
+    b->frames = frames;
+    int st = reserve_output(b); /* nothing of this batch is in the stream yet */
+    if (st)
+        return st;
+    b->in_flight = 1;
+    st = hydamd_encode_image_batch(b->ctx, frames, src, row_stride, pixel_stride, sample_fmt, b->W, b->H);
+    if (st)
+        st = fail(b, st, "batch", hydamd_error(b->ctx));
+    else
+        st = assemble(b);
+    if (st)
+        drain(b);
+    return st;
+}
+
+/* the batch in flight: wait, let hydamd_sync rerun it if it outgrew a buffer, and see its frames into their files */
+static int settle(HydAmdBatch *b) {
+    const unsigned before = hydamd_overflow_reruns(b->ctx);
+    int st = hydamd_sync(b->ctx);
+    if (st)
+        return fail(b, st, "batch", hydamd_error(b->ctx));
+    b->reruns += hydamd_overflow_reruns(b->ctx) - before;
+    for (int attempt = 0; attempt < 4; attempt++) {
+        uint32_t err = 0;
+        uint64_t total = 0;
+        const uint64_t *offsets = NULL;
+        hydk_batch_result(b->as, &err, &total, &offsets);
+        if (!err) {
+            b->total = (size_t)total;
+            memcpy(b->offsets, offsets, ((size_t)b->frames + 1) * sizeof(uint64_t));
+            return HYD_OK;
+        }
+        if (err & HYDK_ASM_E_NAN)
+            return fail(b, HYD_API_ERROR, "Invalid NaN Float", NULL);
+        if (err & HYDK_ASM_E_SPACE) /* the output was sized from the context's capacities */
+            return fail(b, HYD_INTERNAL_ERROR, "the batch's files are larger than the bound of their output buffer", NULL);
+        if (err & (HYDK_ASM_E_BLOB | HYDK_ASM_E_SLOT | HYDK_ASM_E_HEAD | HYDK_ASM_E_SIZE | HYDK_ASM_E_SCRATCH))
+            return fail(b, HYD_INTERNAL_ERROR, "batch assembly failed on the device", NULL);
+        /* RETRY: the assembly saw the first run's incomplete results (hydamd_sync has rerun the batch since): the view
+         * and the same launches again, into an output sized for the enlarged context */
+        if ((st = assemble(b)) != 0)
+            return st;
+        if ((st = hydk_batch_wait(b->as, hydamd_get_stream(b->ctx))) != 0)
+            return fail(b, st, "batch assembly", hydk_batch_error(b->as));
+    }
+    return fail(b, HYD_INTERNAL_ERROR, "a batch is still incomplete after its rerun", NULL);
+}
+
+HYDRIUM_EXPORT int hydamd_batch_result(HydAmdBatch *b, size_t *total_bytes) {
+    if (!b)
+        return HYD_API_ERROR;
+    if (!b->have_result) {
+        if (!b->in_flight)
+            return fail(b, HYD_API_ERROR, "no batch in flight", NULL);
+        const int st = settle(b);
+        if (st) {
+            drain(b);
+            return st;
+        }
+        b->in_flight = 0;
+        b->have_result = 1;
+    }
+    if (total_bytes)
+        *total_bytes = b->total;
+    return HYD_OK;
+}
+
+HYDRIUM_EXPORT int hydamd_batch_offsets(HydAmdBatch *b, uint64_t *offsets) {
+    if (!b || !b->have_result)
+        return b ? fail(b, HYD_API_ERROR, "no finished batch: hydamd_batch_result first", NULL) : HYD_API_ERROR;
+    if (!offsets)
+        return fail(b, HYD_API_ERROR, "null output pointer", NULL);
+    memcpy(offsets, b->offsets, ((size_t)b->frames + 1) * sizeof(uint64_t));
+    return HYD_OK;
+}
+
+HYDRIUM_EXPORT int hydamd_batch_read(HydAmdBatch *b, int frame, uint8_t *dst, size_t capacity) {
+    if (!b || !b->have_result)
+        return b ? fail(b, HYD_API_ERROR, "no finished batch: hydamd_batch_result first", NULL) : HYD_API_ERROR;
+    if (!dst)
+        return fail(b, HYD_API_ERROR, "null output pointer", NULL);
+    if (frame < -1 || frame >= b->frames)
+        return fail(b, HYD_API_ERROR, "no such frame in the batch", NULL);
+    const uint64_t from = frame < 0 ? 0 : b->offsets[frame], to = frame < 0 ? b->total : b->offsets[frame + 1];
+    if (capacity < to - from)
+        return fail(b, HYD_API_ERROR, "output buffer too small", NULL);
+    const int st = hydk_batch_read(b->as, from, dst, (size_t)(to - from));
+    return st ? fail(b, st, "read-back", hydk_batch_error(b->as)) : HYD_OK;
+}
+
+HYDRIUM_EXPORT const uint8_t *hydamd_batch_device(HydAmdBatch *b) { return b && b->have_result ? hydk_batch_out(b->as) : NULL; }
+
+HYDRIUM_EXPORT const uint64_t *hydamd_batch_offsets_device(HydAmdBatch *b) {
+    return b && b->have_result ? hydk_batch_offsets_dev(b->as) : NULL;
+}
+
+HYDRIUM_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b) { return b ? b->reruns : 0; }

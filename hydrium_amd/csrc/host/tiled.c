@@ -78,6 +78,46 @@ static int tile_geometry(const HYDImageMetadata *md, TileGeometry *g, const char
 /* the four tile shapes an image can have: (interior | right edge) x (interior | bottom edge) */
 static uint32_t shape_of(const TileGeometry *g, size_t tx, size_t ty) { return (tx == g->ntx - 1 ? 1u : 0u) | (ty == g->nty - 1 ? 2u : 0u); }
 
+/* the constant sub-streams of one frame shape of w x h pixels (one LF group), appended to the plan buffer; `bits` and
+ * `part` are the caller's to reuse.  Also what the batch object plans its one-LF-group frames with (batch.c). */
+int hydk_tile_plan_shape(Buf *buf, HydBits *bits, HydBits *part, size_t w, size_t h, HydkTileShape *sh, const char **err) {
+    const size_t vbw = (w + 7) >> 3, vbh = (h + 7) >> 3;
+    sh->ngroups = (uint32_t)(((w + 255) >> 8) * ((h + 255) >> 8));
+    /* LFGlobal (encoder.c:510-537): a section of its own, or the opening bits of the only one */
+    hb_reset(bits);
+    hyd_write_lf_global(bits);
+    if (sh->ngroups > 1) {
+        uint32_t nbits = 0;
+        hb_align(bits);
+        sh->lfglobal_off = (uint32_t)buf_add_bits(buf, bits, &nbits);
+        sh->lfglobal_bytes = nbits >> 3;
+        hb_reset(bits);
+    }
+    int ret = hyd_write_lf_group_fixed_head(bits, err);
+    if (ret)
+        return ret;
+    sh->pre_off = (uint32_t)buf_add_bits(buf, bits, &sh->pre_bits);
+    const HydBits *tail = hyd_internal_lf_tail(vbw, vbh);
+    if (!tail) { /* the process-wide cache of tails is full: code this one here */
+        hb_reset(part);
+        ret = hyd_write_lf_group_tail(part, vbw, vbh, err);
+        if (ret)
+            return ret;
+        tail = part;
+    }
+    sh->tail_off = (uint32_t)buf_add_bits(buf, tail, &sh->tail_bits);
+    hb_reset(bits);
+    ret = hyd_write_hf_global_fixed(bits, 1, sh->ngroups, NULL, err);
+    if (ret)
+        return ret;
+    sh->hfpre_off = (uint32_t)buf_add_bits(buf, bits, &sh->hfpre_bits);
+    if ((uint64_t)sh->tail_bits + sh->hfpre_bits + 2u + 9u * 8u + 9u * 73u * 32u > (uint64_t)HYDK_TILE_MID_WORDS * 32u) {
+        *err = "a tile's constant sub-streams do not fit the assembler's scratch";
+        return HYD_INTERNAL_ERROR;
+    }
+    return HYD_OK;
+}
+
 static int build_plan(const HYDImageMetadata *md, const TileGeometry *g, uint8_t **plan_out, size_t *plan_len, const char **err) {
     int ret = HYD_OK;
     Buf buf = {0};
@@ -91,43 +131,9 @@ static int build_plan(const HYDImageMetadata *md, const TileGeometry *g, uint8_t
     plan.nshapes = HYDK_TILE_MAX_SHAPES;
     buf_reserve(&buf, sizeof(plan));
     for (uint32_t s = 0; s < HYDK_TILE_MAX_SHAPES && !ret; s++) {
-        HydkTileShape *sh = &plan.shapes[s];
         const size_t w = (s & 1u) ? g->W - (g->ntx - 1) * g->tw : g->tw < g->W ? g->tw : g->W;
         const size_t h = (s & 2u) ? g->H - (g->nty - 1) * g->th : g->th < g->H ? g->th : g->H;
-        const size_t vbw = (w + 7) >> 3, vbh = (h + 7) >> 3;
-        sh->ngroups = (uint32_t)(((w + 255) >> 8) * ((h + 255) >> 8));
-        /* LFGlobal (encoder.c:510-537): a section of its own, or the opening bits of the only one */
-        hb_reset(&bits);
-        hyd_write_lf_global(&bits);
-        if (sh->ngroups > 1) {
-            uint32_t nbits = 0;
-            hb_align(&bits);
-            sh->lfglobal_off = (uint32_t)buf_add_bits(&buf, &bits, &nbits);
-            sh->lfglobal_bytes = nbits >> 3;
-            hb_reset(&bits);
-        }
-        ret = hyd_write_lf_group_fixed_head(&bits, err);
-        if (ret)
-            break;
-        sh->pre_off = (uint32_t)buf_add_bits(&buf, &bits, &sh->pre_bits);
-        const HydBits *tail = hyd_internal_lf_tail(vbw, vbh);
-        if (!tail) { /* the process-wide cache of tails is full: code this one here */
-            hb_reset(&part);
-            ret = hyd_write_lf_group_tail(&part, vbw, vbh, err);
-            if (ret)
-                break;
-            tail = &part;
-        }
-        sh->tail_off = (uint32_t)buf_add_bits(&buf, tail, &sh->tail_bits);
-        hb_reset(&bits);
-        ret = hyd_write_hf_global_fixed(&bits, 1, sh->ngroups, NULL, err);
-        if (ret)
-            break;
-        sh->hfpre_off = (uint32_t)buf_add_bits(&buf, &bits, &sh->hfpre_bits);
-        if ((uint64_t)sh->tail_bits + sh->hfpre_bits + 2u + 9u * 8u + 9u * 73u * 32u > (uint64_t)HYDK_TILE_MID_WORDS * 32u) {
-            *err = "a tile's constant sub-streams do not fit the assembler's scratch";
-            ret = HYD_INTERNAL_ERROR;
-        }
+        ret = hydk_tile_plan_shape(&buf, &bits, &part, w, h, &plan.shapes[s], err);
     }
     /* one frame header per tile: origin, size and is_last differ, and with them the header's length */
     const size_t frames_off = ret ? 0 : buf_reserve(&buf, g->ntiles * sizeof(HydkTileFrame));

@@ -169,6 +169,29 @@ def dll(path: Optional[str] = None):
         d.hydamd_tiled_overflow_reruns.argtypes = [vp]
         d.hydamd_tiled_device_bytes.restype = sz
         d.hydamd_tiled_device_bytes.argtypes = [vp]
+        d.hydamd_context_assembler.restype = vp
+        d.hydamd_context_assembler.argtypes = [vp]
+        d.hydamd_export_batch_owned.argtypes = [vp, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
+        d.hydamd_batch_create.restype = vp
+        d.hydamd_batch_create.argtypes = [i, C.POINTER(api.HYDImageMetadata), i, C.c_char_p, sz, C.POINTER(i)]
+        d.hydamd_batch_destroy.restype = None
+        d.hydamd_batch_destroy.argtypes = [vp]
+        d.hydamd_batch_error.restype = C.c_char_p
+        d.hydamd_batch_error.argtypes = [vp]
+        d.hydamd_encode_batch.restype = i
+        d.hydamd_encode_batch.argtypes = [vp, i, C.POINTER(vp), C.c_ssize_t, C.c_ssize_t, i]
+        d.hydamd_batch_result.restype = i
+        d.hydamd_batch_result.argtypes = [vp, C.POINTER(sz)]
+        d.hydamd_batch_offsets.restype = i
+        d.hydamd_batch_offsets.argtypes = [vp, C.POINTER(C.c_uint64)]
+        d.hydamd_batch_device.restype = C.POINTER(C.c_uint8)
+        d.hydamd_batch_device.argtypes = [vp]
+        d.hydamd_batch_offsets_device.restype = C.POINTER(C.c_uint64)
+        d.hydamd_batch_offsets_device.argtypes = [vp]
+        d.hydamd_batch_read.restype = i
+        d.hydamd_batch_read.argtypes = [vp, i, C.POINTER(C.c_uint8), sz]
+        d.hydamd_batch_overflow_reruns.restype = u
+        d.hydamd_batch_overflow_reruns.argtypes = [vp]
         if path is not None:
             return d
         _dll = d
@@ -780,6 +803,107 @@ class TiledImage:
 
     def device_bytes(self) -> int:
         return int(self.d.hydamd_tiled_device_bytes(self.h))
+
+
+class FrameBatch:
+    """Batches of up to ``max_frames`` one-frame images of one shape from device-resident pixels, every one a finished
+    file built on the GPU (hydamd_batch_*, csrc/host/batch.c): the files back to back in one device buffer, the table of
+    their offsets beside it."""
+
+    def __init__(self, width: int, height: int, max_frames: int, linear_light: int = 0, device: int = 0,
+                 icc: Optional[bytes] = None):
+        self.d = dll()
+        md = api.HYDImageMetadata(width, height, int(linear_light), -1, -1)
+        st = C.c_int(0)
+        self.h = self.d.hydamd_batch_create(device, C.byref(md), max_frames, icc, len(icc) if icc else 0, C.byref(st))
+        if not self.h:
+            raise DeviceError(st.value, (self.d.hydamd_batch_error(None) or b"").decode() or "frame batch could not be created")
+        self.width, self.height, self.max_frames = width, height, max_frames
+        self.frames = 0
+        self._keep = None
+
+    def close(self):
+        if self.h:
+            self.d.hydamd_batch_destroy(self.h)
+            self.h = None
+        self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _ck(self, code: int):
+        if code != 0:
+            raise DeviceError(code, (self.d.hydamd_batch_error(self.h) or b"").decode())
+
+    def encode(self, imgs, row_stride: Optional[int] = None, pixel_stride: Optional[int] = None, sample_fmt: Optional[int] = None):
+        """imgs: one entry per frame, all of one layout — interleaved (H, W, C >= 3) torch tensors on the object's device
+        (C > 3: the first three channels, pixel stride C), triples of (H, W) plane tensors, or triples of device addresses
+        (then the strides, in samples, and the sample format are the caller's).  Asynchronous: the pixels must stay alive
+        and unchanged until result()."""
+        ptrs = []
+        for img in imgs:
+            if hasattr(img, "data_ptr"):
+                isz = img.element_size()
+                ptrs += [img.data_ptr() + c * isz for c in range(3)]
+                layout = (img.stride(0), img.stride(1), {1: 0, 2: 1, 4: 2}[isz])
+            elif hasattr(img[0], "data_ptr"):
+                ptrs += [p.data_ptr() for p in img]
+                layout = (img[0].stride(0), img[0].stride(1), {1: 0, 2: 1, 4: 2}[img[0].element_size()])
+            else:
+                if row_stride is None or pixel_stride is None or sample_fmt is None:
+                    raise ValueError("device addresses need row_stride, pixel_stride and sample_fmt")
+                ptrs += [int(p) if p is not None else None for p in img]
+                layout = (row_stride, pixel_stride, sample_fmt)
+            if (row_stride, pixel_stride, sample_fmt) == (None, None, None):
+                row_stride, pixel_stride, sample_fmt = layout
+            elif layout != (row_stride, pixel_stride, sample_fmt):
+                raise ValueError("the frames of a batch share one layout and sample format")
+        self._keep = imgs
+        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        self._ck(self.d.hydamd_encode_batch(self.h, len(imgs), arr, row_stride or 0, pixel_stride or 0,
+                                            sample_fmt if sample_fmt is not None else -1))
+        self.frames = len(imgs)
+
+    def result(self) -> int:
+        """Waits for the batch; bytes of all its files."""
+        n = C.c_size_t(0)
+        try:
+            self._ck(self.d.hydamd_batch_result(self.h, C.byref(n)))
+        finally:
+            self._keep = None
+        return int(n.value)
+
+    def offsets(self) -> np.ndarray:
+        """uint64[frames + 1]: file k is bytes offsets[k] .. offsets[k + 1] of the device buffer."""
+        self.result()
+        out = np.zeros(self.frames + 1, np.uint64)
+        self._ck(self.d.hydamd_batch_offsets(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def read(self, k: Optional[int] = None):
+        """File k as a uint8 array; None: the list of all files (one copy from the device)."""
+        off = self.offsets()
+        if k is None:
+            buf = np.empty(max(int(off[-1]), 1), np.uint8)
+            self._ck(self.d.hydamd_batch_read(self.h, -1, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
+            return [buf[int(off[i]):int(off[i + 1])] for i in range(self.frames)]
+        if not 0 <= k < self.frames:
+            raise IndexError("no such frame in the batch")
+        buf = np.empty(max(int(off[k + 1] - off[k]), 1), np.uint8)
+        self._ck(self.d.hydamd_batch_read(self.h, k, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
+        return buf[: int(off[k + 1] - off[k])]
+
+    def device_ptr(self) -> int:
+        return C.cast(self.d.hydamd_batch_device(self.h), C.c_void_p).value or 0
+
+    def offsets_device_ptr(self) -> int:
+        return C.cast(self.d.hydamd_batch_offsets_device(self.h), C.c_void_p).value or 0
+
+    def overflow_reruns(self) -> int:
+        return int(self.d.hydamd_batch_overflow_reruns(self.h))
 
 
 def decode_token_records(rec: np.ndarray):

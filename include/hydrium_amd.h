@@ -137,7 +137,8 @@ HYDAMD_EXPORT int hydamd_encode_image(HydAmdContext *ctx, const void *const src[
  * (k + 1) * num_presets - 1, presets 0 .. num_presets - 1 in each; hydamd_encode_image_batch = hydamd_encode_image for
  * src[3 k .. 3 k + 2] of every frame, then hydamd_finish_frame over all slots.  Results per slot as usual
  * (hydamd_read_sections, hydamd_read_tables, hydamd_read_lf_streams); frame k's sections follow frame k - 1's in the
- * payload.  A batch is not exported as a blob (hydamd_export_frame*: HYD_API_ERROR): code one frame per context for that. */
+ * payload.  A batch is not exported as a blob (hydamd_export_frame*: HYD_API_ERROR): hydamd_export_batch_owned gives its
+ * results as a view, and hydamd_batch_* (below) turns a batch into finished files on the device. */
 HYDAMD_EXPORT int hydamd_begin_batch(HydAmdContext *ctx, unsigned num_presets, int frames);
 HYDAMD_EXPORT int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const *src, ptrdiff_t row_stride,
                                             ptrdiff_t pixel_stride, int sample_fmt, size_t width, size_t height);
@@ -383,14 +384,16 @@ HYDAMD_EXPORT int hydamd_assembler_read(HydAmdAssembler *a, uint8_t *dst, size_t
  * with these. */
 HYDAMD_EXPORT int hydamd_export_frame_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity);
 HYDAMD_EXPORT HydAmdAssembler *hydamd_context_assembler(HydAmdContext *ctx);
-/* The results of a BATCH of one-LF-group frames (hydamd_begin_batch(ctx, 1, frames): tile-mode frames) as such a view: one
- * header, the slot records of all `num_slots` frames, the packed LF streams and HF sections left in place.  Where frame k's
- * bytes sit in those two strings follows from every frame before it, so the view states it: *extents_dev is a device array
- * of num_slots HydAmdBatchExtent, written by a kernel behind the export in the context's stream.  Valid until the
- * context's next frame.  hydamd_export_frame* keeps refusing batches. */
+/* The results of a BATCH of frames (hydamd_begin_batch(ctx, n, frames): n = 1 for tile-mode frames, the LF groups of the
+ * shape for hydamd_encode_image_batch) as such a view: one header, the slot records of all `num_slots` = frames x n slots —
+ * frame k's at k n .. k n + n - 1 —, the packed LF streams and HF sections left in place.  Where slot s's bytes sit in those
+ * two strings follows from every slot before it, so the view states it: *extents_dev is a device array of num_slots
+ * HydAmdBatchExtent, written by a kernel behind the export in the context's stream; a frame's HF sections reach from its
+ * first slot's hf_offset to its last slot's hf_offset + hf_bytes.  Valid until the context's next frame.
+ * hydamd_export_frame* keeps refusing batches. */
 typedef struct HydAmdBatchExtent {
     uint64_t lf_offset, lf_bytes; /* in the packed LF streams (= the slot record's lf.offset, and its bit count rounded up) */
-    uint64_t hf_offset, hf_bytes; /* in the packed HF sections: the frame's byte-padded group sections, raster order */
+    uint64_t hf_offset, hf_bytes; /* in the packed HF sections: the slot's byte-padded group sections, raster order */
 } HydAmdBatchExtent;
 HYDAMD_EXPORT int hydamd_export_batch_owned(HydAmdContext *ctx, int num_slots, const void **blob_dev, size_t *capacity,
                                             const void **extents_dev);
@@ -527,6 +530,53 @@ HYDAMD_EXPORT const uint8_t *hydamd_tiled_device(HydAmdTiled *t);
 HYDAMD_EXPORT unsigned hydamd_tiled_overflow_reruns(HydAmdTiled *t);
 /* device memory the object holds right now (context arrays are estimated from its capacities; output buffer exact) */
 HYDAMD_EXPORT size_t hydamd_tiled_device_bytes(HydAmdTiled *t);
+
+/*
+ * A BATCH of one-frame images whose pixels already sit in HBM, every one a finished FILE, built on the GPU
+ * (csrc/host/batch.c, csrc/hip/assemble_batch.hip) — for a queue of 4K/8K frames in device memory of which each must
+ * become a .jxl (a video pipeline).  hydamd_encode_image_batch codes `frames` independent pictures of one shape as one
+ * launch group, their serial rANS chains side by side; one launch sequence behind its entropy stage then writes every
+ * frame — file header, frame header with is_last, TOC, LFGlobal, LF groups, HFGlobal, HF sections; frames of a single
+ * 256x256 group as one bit-contiguous section — exactly as the reference writes that picture alone, the files back to
+ * back at byte granularity in ONE device buffer the object owns, with the table of their offsets beside it.  The host
+ * contributes the bytes that do not depend on the pixels, once per object, and waits once per batch.
+ *   hydamd_batch_create          md: a one-frame image (both tile_size_shift -1) of n = LF groups; max_frames: frames a batch
+ *                                may hold, max_frames x n <= 255 (the slots of the object's one context; n = 128 and
+ *                                n > 255 cannot be one frame).  icc: optional profile, written into every file as
+ *                                hydamd_assembler_plan writes it.  One device and one stream per object.
+ *   hydamd_encode_batch          `frames` <= max_frames pictures of the object's shape: src[3 k .. 3 k + 2] are frame k's
+ *                                channel pointers (device memory), strides in samples and sample_fmt as
+ *                                hydamd_encode_image_batch's.  Enqueues the batch and its assembly and returns; the
+ *                                pixels stay borrowed until hydamd_batch_result.  (An object's first batch allocates
+ *                                the output buffer, for max_frames, before it enqueues anything.)
+ *   hydamd_batch_result          waits; *total_bytes = bytes of all files.  A batch that outgrew the context's buffers is
+ *                                rerun inside hydamd_sync and exported and assembled again first; the output buffer is
+ *                                sized from the context's capacities (never HYD_NEED_MORE_OUTPUT).  A non-finite float
+ *                                sample ANYWHERE fails the WHOLE batch — HYD_API_ERROR "Invalid NaN Float"; the context's
+ *                                status word belongs to the launch group, so the frame cannot be named.  After a failure
+ *                                the stream is drained and the object stays usable.
+ *   hydamd_batch_offsets         offsets[k] .. offsets[k + 1] bound file k; offsets[0] = 0, offsets[frames] = total.
+ *   hydamd_batch_device,         the files and the same table (frames + 1 entries) in device memory, for a consumer
+ *   hydamd_batch_offsets_device  that never leaves the GPU.  Everything is valid until the object's next hydamd_encode_batch.
+ *   hydamd_batch_read            file `frame` (or, with -1, all of them back to back) to host memory, one copy.
+ * HYD_API_ERROR: a shift other than -1, max_frames out of range, a null pointer, a bad sample format, `frames` out of
+ * range, a second encode while a batch is in flight, result / offsets / read without a batch, a destination that is too
+ * small.  hydamd_batch_overflow_reruns: batches run twice because a buffer was too small.  Keep several objects for a
+ * deeper queue (scripts/batch_files_probe.py keeps four).
+ */
+typedef struct HydAmdBatch HydAmdBatch;
+HYDAMD_EXPORT HydAmdBatch *hydamd_batch_create(int device, const HYDImageMetadata *md, int max_frames, const uint8_t *icc, size_t icc_size,
+                                               int *status);
+HYDAMD_EXPORT void hydamd_batch_destroy(HydAmdBatch *b);
+HYDAMD_EXPORT const char *hydamd_batch_error(HydAmdBatch *b);
+HYDAMD_EXPORT int hydamd_encode_batch(HydAmdBatch *b, int frames, const void *const *src, ptrdiff_t row_stride, ptrdiff_t pixel_stride,
+                                      int sample_fmt);
+HYDAMD_EXPORT int hydamd_batch_result(HydAmdBatch *b, size_t *total_bytes);
+HYDAMD_EXPORT int hydamd_batch_offsets(HydAmdBatch *b, uint64_t *offsets);
+HYDAMD_EXPORT const uint8_t *hydamd_batch_device(HydAmdBatch *b);
+HYDAMD_EXPORT const uint64_t *hydamd_batch_offsets_device(HydAmdBatch *b);
+HYDAMD_EXPORT int hydamd_batch_read(HydAmdBatch *b, int frame, uint8_t *dst, size_t capacity);
+HYDAMD_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b);
 
 #ifdef __cplusplus
 }
