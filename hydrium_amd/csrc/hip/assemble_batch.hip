@@ -15,13 +15,17 @@
  *   k_batch_prepare_one  (shapes of ONE LF group, a single bit-contiguous section included) grid F, block 64: the
  *                        tile assembler's per-frame preparation and pieces (hydk_tiles.h) with a plan whose one frame
  *                        carries the file header and is_last
+ *   k_batch_prepare_mixed  (one-LF-group frames EACH OF ITS OWN SIZE, csrc/host/mixed.c) the same wavefront body with
+ *                        frame f's own record of a mixed plan — its own file header and frame header — and the shape
+ *                        that record names, after checking on the device that the plan covers the batch
  *   k_batch_place        one workgroup: the union of the frames' error words, a prefix sum over their sizes = the
  *                        offsets table, every piece moved to its frame's start, the range k_pieces_copy reads
  *   k_pieces_copy        (assemble.hip) every output word composed from the pieces that touch it and stored once; the
  *                        padding that ends a section, and a file, is the gap no piece covers
  *
  * Every frame of a batch has the same pixel-independent bytes: ONE plan (csrc/host/batch.c builds it with the frame
- * planner, or the tile planner for n = 1) serves all of them.  No host synchronisation between the entropy stage and
+ * planner, or the tile planner for n = 1) serves all of them; a mixed batch brings a plan of its own, one record per
+ * frame and one per distinct shape, uploaded in the stream ahead of the assembly.  No host synchronisation between the entropy stage and
  * the finished files.
  */
 #include <hip/hip_runtime.h>
@@ -99,22 +103,12 @@ __global__ __launch_bounds__(256) void k_batch_prepare(const uint8_t *__restrict
     asm_frame(planb, blobs, frame_scratch(B, f), F, part, n + 1, ~0ull, nullptr);
 }
 
-/* ---- k_batch_prepare_one: grid = frames, block = 64 (one wavefront); every frame is frame 0 of the tile plan ---- */
-__global__ __launch_bounds__(64) void k_batch_prepare_one(const uint8_t *__restrict__ planb, const uint8_t *__restrict__ blob,
-                                                          const HydkTileExtent *__restrict__ ext, uint32_t frames, BatchScratch B) {
-    const uint32_t f = blockIdx.x;
+/* one wavefront, frame f of a view of one-LF-group frames: the tile assembler's preparation and pieces with the frame
+ * record `fr` and the shape `sh` of the plan `planb` (the view has been checked) */
+static __device__ __forceinline__ void prepare_one(const uint8_t *__restrict__ planb, const HydkTileFrame &fr, const HydkTileShape *sh,
+                                                   const uint8_t *__restrict__ blob, const HydkTileExtent *__restrict__ ext, uint32_t f,
+                                                   const BatchScratch &B) {
     uint64_t *result = B.result + (size_t)f * 4;
-    const uint32_t bad = blob_view_check(blob, frames);
-    if (bad) {
-        if (threadIdx.x == 0) {
-            result[0] = bad;
-            result[1] = result[2] = result[3] = 0;
-        }
-        return;
-    }
-    const HydkTilePlan *plan = (const HydkTilePlan *)planb;
-    const HydkTileFrame fr = ((const HydkTileFrame *)(planb + plan->frames_off))[0];
-    const HydkTileShape *sh = &plan->shapes[fr.shape];
     const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
     const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + f;
     uint32_t *head = B.head + (size_t)f * HYDK_TILE_HEAD_WORDS, *mid = B.hfg + (size_t)f * HYDK_TILE_MID_WORDS,
@@ -133,6 +127,45 @@ __global__ __launch_bounds__(64) void k_batch_prepare_one(const uint8_t *__restr
         result[2] = e ? 0 : z.frame_bytes;
         result[3] = 0;
     }
+}
+
+static __device__ __forceinline__ void prepare_failed(const BatchScratch &B, uint32_t f, uint32_t bad) {
+    if (threadIdx.x == 0) {
+        uint64_t *result = B.result + (size_t)f * 4;
+        result[0] = bad;
+        result[1] = result[2] = result[3] = 0;
+    }
+}
+
+/* ---- k_batch_prepare_one: grid = frames, block = 64 (one wavefront); every frame is frame 0 of the tile plan ---- */
+__global__ __launch_bounds__(64) void k_batch_prepare_one(const uint8_t *__restrict__ planb, const uint8_t *__restrict__ blob,
+                                                          const HydkTileExtent *__restrict__ ext, uint32_t frames, BatchScratch B) {
+    const uint32_t f = blockIdx.x;
+    const uint32_t bad = blob_view_check(blob, frames);
+    if (bad)
+        return prepare_failed(B, f, bad);
+    const HydkTilePlan *plan = (const HydkTilePlan *)planb;
+    const HydkTileFrame fr = ((const HydkTileFrame *)(planb + plan->frames_off))[0];
+    prepare_one(planb, fr, &plan->shapes[fr.shape], blob, ext, f, B);
+}
+
+/* ---- k_batch_prepare_mixed: grid = frames, block = 64; frame f is frame f of a MIXED plan (hydk_tiles.h), with its own
+ * prefix and the shape it names.  The plan arrives per batch, so what the indices below rest on is checked here: a plan
+ * of another kind or of fewer frames than the batch is a malformed input (BLOB), a shape the plan does not hold an
+ * inconsistent record (SLOT); nothing behind the plan's header is read before the first, nothing of a shape before the second ---- */
+__global__ __launch_bounds__(64) void k_batch_prepare_mixed(const uint8_t *__restrict__ planb, const uint8_t *__restrict__ blob,
+                                                            const HydkTileExtent *__restrict__ ext, uint32_t frames, BatchScratch B) {
+    const uint32_t f = blockIdx.x;
+    const HydkMixedPlan *plan = (const HydkMixedPlan *)planb;
+    uint32_t bad = blob_view_check(blob, frames);
+    if (!bad && (plan->magic != HYDK_MIXED_MAGIC || plan->num_frames < frames))
+        bad = HYDK_ASM_E_BLOB;
+    if (bad)
+        return prepare_failed(B, f, bad);
+    const HydkTileFrame fr = ((const HydkTileFrame *)(planb + plan->frames_off))[f];
+    if (fr.shape >= plan->nshapes)
+        return prepare_failed(B, f, HYDK_ASM_E_SLOT);
+    prepare_one(planb, fr, (const HydkTileShape *)(planb + plan->shapes_off) + fr.shape, blob, ext, f, B);
 }
 
 /* ---- k_batch_place: grid 1, block 256 ---- */
@@ -198,8 +231,13 @@ struct HydkBatchAsm {
     uint8_t *plan = nullptr;
     int max_frames = 0;
     bool one = false;             /* frames of one LF group: the plan is a tile plan (hydk_tiles.h) */
+    bool mixed = false;           /* ... each of its own size: a mixed plan per batch (hydk_batch_set_plan), in a region of its own */
+    size_t plan_cap = 0;          /* mixed: bytes of that region and of the pinned buffer the plan travels through */
+    uint8_t *h_plan = nullptr;
+    uint32_t plan_frames = 0;     /* mixed: frames of the plan on the device */
     BatchScratch B = {};
-    uint64_t fixed = 0;           /* bytes of a frame beyond its packed LF streams and HF sections, at most */
+    uint64_t fixed = 0;           /* bytes of a frame beyond its packed LF streams and HF sections, at most; stays 0 for a
+                                   * mixed assembler, whose frames differ: mixed.c sums the same terms per batch, from its plan */
     uint64_t *h_result = nullptr; /* pinned [4 + max_frames + 1]: the range quadruple, then the offsets table */
     uint8_t *out = nullptr;       /* the files: owned, grown on demand (hydk_batch_reserve) */
     uint64_t out_cap = 0;
@@ -215,6 +253,10 @@ void hydk_batch_destroy(HydkBatchAsm *a) {
     (void)hipSetDevice(a->device);
     if (a->out)
         (void)hipFree(a->out);
+    if (a->mixed && a->plan)
+        (void)hipFree(a->plan);
+    if (a->h_plan)
+        (void)hipHostFree(a->h_plan);
     if (a->arena)
         (void)hipFree(a->arena);
     if (a->h_result)
@@ -223,14 +265,15 @@ void hydk_batch_destroy(HydkBatchAsm *a) {
 }
 
 /* scratch for batches of up to `max_frames` frames of the plan's shape; the plan — a HydkAsmPlan of one blob, or a
- * HydkTilePlan of one frame for shapes of one LF group — is copied to the device */
+ * HydkTilePlan of one frame for shapes of one LF group — is copied to the device.  No plan: frames of one LF group, each
+ * of its own size, whose (mixed) plan comes with every batch (hydk_batch_set_plan) */
 int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_bytes, HydkBatchAsm **out) {
     if (!out)
         return ST_API_ERROR;
     *out = nullptr;
-    if (max_frames < 1 || !plan || plan_bytes < 8)
+    if (max_frames < 1 || (plan && plan_bytes < 8))
         return ST_API_ERROR;
-    const uint32_t magic = *(const uint32_t *)plan;
+    const uint32_t magic = plan ? *(const uint32_t *)plan : 0u;
     const HydkAsmPlan *ap = (const HydkAsmPlan *)plan;
     const HydkTilePlan *tp = (const HydkTilePlan *)plan;
     HydkBatchAsm *a = new (std::nothrow) HydkBatchAsm();
@@ -240,15 +283,12 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
     a->max_frames = max_frames;
     BatchScratch &B = a->B;
     size_t head_words = 0;
-    if (magic == HYDK_TILE_MAGIC && plan_bytes >= sizeof(HydkTilePlan) && tp->total_bytes == plan_bytes && tp->num_frames == 1 &&
+    if (!plan && max_frames <= HYDK_TILE_MAX_FRAMES) {
+        a->one = a->mixed = true;
+        plan_bytes = 0;
+    } else if (magic == HYDK_TILE_MAGIC && plan_bytes >= sizeof(HydkTilePlan) && tp->total_bytes == plan_bytes && tp->num_frames == 1 &&
         max_frames <= HYDK_TILE_MAX_FRAMES) {
         a->one = true;
-        B.n = 1;
-        B.pieces_per_frame = HYDK_TILE_PIECES;
-        B.hfg_words = HYDK_TILE_MID_WORDS;
-        B.toc_words = HYDK_TILE_TOC_WORDS;
-        B.toc_n = 1;
-        head_words = HYDK_TILE_HEAD_WORDS;
         const HydkTileFrame *fr = (const HydkTileFrame *)((const uint8_t *)plan + tp->frames_off);
         a->fixed = (uint64_t)fr->prefix_bytes + tp->shapes[fr->shape].lfglobal_bytes +
                    4u * (HYDK_TILE_HEAD_WORDS + HYDK_TILE_MID_WORDS + HYDK_TILE_TOC_WORDS) + (tp->shapes[fr->shape].tail_bits >> 3) + 16u;
@@ -273,6 +313,14 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
         delete a;
         return ST_API_ERROR;
     }
+    if (a->one) {
+        B.n = 1;
+        B.pieces_per_frame = HYDK_TILE_PIECES;
+        B.hfg_words = HYDK_TILE_MID_WORDS;
+        B.toc_words = HYDK_TILE_TOC_WORDS;
+        B.toc_n = 1;
+        head_words = HYDK_TILE_HEAD_WORDS;
+    }
     const size_t F = (size_t)max_frames;
     /* one arena: the plan (+ 16: the copy kernel reads whole words), then the arrays, each 16-byte aligned.  The
      * one-LF-group path keeps its sizes in registers and needs no counters: those arrays stay null */
@@ -282,7 +330,7 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
         at += (bytes + 15) & ~(size_t)15;
         return off;
     };
-    const size_t o_plan = take(plan_bytes + 16), o_head = take(F * head_words * 4), o_hfg = take(F * B.hfg_words * 4),
+    const size_t o_plan = take(plan ? plan_bytes + 16 : 0), o_head = take(F * head_words * 4), o_hfg = take(F * B.hfg_words * 4),
                  o_toc = take(F * B.toc_words * 4), o_pieces = take(F * B.pieces_per_frame * sizeof(HydkPiece)),
                  o_result = take(F * 4 * 8), o_offsets = take((F + 1) * 8), o_range = take(4 * 8);
     const bool one = a->one;
@@ -292,7 +340,7 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
         HYDK_TRY(a, hipSetDevice(device));
         HYDK_TRY(a, hipMalloc(&a->arena, at));
         uint8_t *m = a->arena;
-        a->plan = m + o_plan;
+        a->plan = plan ? m + o_plan : nullptr;
         B.head = (uint32_t *)(m + o_head);
         B.hfg = (uint32_t *)(m + o_hfg);
         B.toc = (uint32_t *)(m + o_toc);
@@ -309,7 +357,8 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
             B.done = B.err + F;
             HYDK_TRY(a, hipMemset(B.err, 0, 2 * F * sizeof(uint32_t)));
         }
-        HYDK_TRY(a, hipMemcpy(a->plan, plan, plan_bytes, hipMemcpyHostToDevice));
+        if (plan)
+            HYDK_TRY(a, hipMemcpy(a->plan, plan, plan_bytes, hipMemcpyHostToDevice));
         HYDK_TRY(a, hipStreamSynchronize(nullptr)); /* the memset runs in the NULL stream, which the context's stream does not wait for */
         HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, (4 + F + 1) * sizeof(uint64_t), hipHostMallocDefault));
         memset(a->h_result, 0, (4 + F + 1) * sizeof(uint64_t));
@@ -327,6 +376,38 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
 /* bytes a frame can add to its packed LF streams and HF sections: what the plan fixes and the scratch can hold */
 uint64_t hydk_batch_fixed_bytes(HydkBatchAsm *a) { return a ? a->fixed : 0; }
 
+/* a mixed assembler's plan for the batches that follow: `bytes` of a HydkMixedPlan, through the pinned buffer and one
+ * asynchronous copy on `stream`, ahead of the assembly that reads it.  The caller has waited for the previous batch
+ * (one batch in flight per object), so neither buffer is being read; both grow on demand, and wait for `stream` when they do */
+int hydk_batch_set_plan(HydkBatchAsm *a, const void *plan, size_t bytes, void *stream) {
+    const HydkMixedPlan *mp = (const HydkMixedPlan *)plan;
+    if (!a || !a->mixed || !plan || bytes < sizeof(HydkMixedPlan) || mp->magic != HYDK_MIXED_MAGIC || mp->total_bytes != bytes ||
+        mp->num_frames < 1 || mp->num_frames > (uint32_t)a->max_frames || mp->nshapes < 1 || mp->nshapes > mp->num_frames ||
+        (uint64_t)mp->shapes_off + (uint64_t)mp->nshapes * sizeof(HydkTileShape) > bytes ||
+        (uint64_t)mp->frames_off + (uint64_t)mp->num_frames * sizeof(HydkTileFrame) > bytes)
+        return hydk_fail(a, ST_API_ERROR, "bad mixed plan");
+    HYDK_TRY(a, hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    a->plan_frames = 0;
+    if (bytes > a->plan_cap) {
+        HYDK_TRY(a, hipStreamSynchronize(st));
+        if (a->plan)
+            (void)hipFree(a->plan);
+        if (a->h_plan)
+            (void)hipHostFree(a->h_plan);
+        a->plan = a->h_plan = nullptr;
+        a->plan_cap = 0;
+        const size_t cap = bytes + (bytes >> 1) + 4096; /* room for the next, larger list of sizes */
+        HYDK_TRY(a, hipMalloc(&a->plan, cap + 16));     /* + 16: the copy kernel reads whole words */
+        HYDK_TRY(a, hipHostMalloc((void **)&a->h_plan, cap, hipHostMallocDefault));
+        a->plan_cap = cap;
+    }
+    memcpy(a->h_plan, plan, bytes);
+    HYDK_TRY(a, hipMemcpyAsync(a->plan, a->h_plan, bytes, hipMemcpyHostToDevice, st));
+    a->plan_frames = mp->num_frames;
+    return ST_OK;
+}
+
 /* enqueue the assembly of `frames` frames on `stream`, behind whatever fills the view `blob` (`blob_cap` readable bytes)
  * and its extents (hydamd_export_batch_owned over frames x n slots): three launches */
 int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t blob_cap, const void *extents, void *stream) {
@@ -337,7 +418,11 @@ int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t 
     HYDK_TRY(a, hipSetDevice(a->device));
     hipStream_t st = (hipStream_t)stream;
     const HydkTileExtent *ext = (const HydkTileExtent *)extents;
-    if (a->one)
+    if (a->mixed && frames > a->plan_frames)
+        return hydk_fail(a, ST_API_ERROR, "the batch has more frames than its plan");
+    if (a->mixed)
+        hipLaunchKernelGGL(k_batch_prepare_mixed, dim3(frames), dim3(64), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob, ext, frames, a->B);
+    else if (a->one)
         hipLaunchKernelGGL(k_batch_prepare_one, dim3(frames), dim3(64), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob, ext, frames, a->B);
     else
         hipLaunchKernelGGL(k_batch_prepare, dim3(frames * (a->B.n + 1)), dim3(256), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob,

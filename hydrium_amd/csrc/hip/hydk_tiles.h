@@ -51,6 +51,15 @@ typedef struct HydkTilePlan { /* header of the plan buffer; offsets in bytes fro
     uint32_t frames_off, pad[3];
 } HydkTilePlan;
 
+/* A MIXED plan (csrc/host/mixed.c): one-frame images of different sizes side by side, every frame with a prefix of its own
+ * (its file header, its frame header) and any number of shapes — the shape records live in the buffer, `nshapes` of them
+ * at `shapes_off`, a frame's `shape` indexing them.  Offsets inside the records count from the start of the plan, as above. */
+#define HYDK_MIXED_MAGIC 0x58494D48u /* "HMIX" */
+typedef struct HydkMixedPlan {
+    uint32_t magic, total_bytes, num_frames, nshapes;
+    uint32_t shapes_off, frames_off, pad[2];
+} HydkMixedPlan;
+
 typedef struct HydkTileSizes { /* what the preparation of one frame leaves */
     uint32_t head_bits, mid_bits, toc_bits, err;
     uint64_t lfsec_bytes, hfg_bytes; /* several groups: the two padded sections */

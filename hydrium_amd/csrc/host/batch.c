@@ -51,6 +51,39 @@ int hydk_batch_read(HydkBatchAsm *a, uint64_t from, uint8_t *dst, size_t n);
 /* ---------------------------------------------------------------------------------------------
  * the plan
  * ------------------------------------------------------------------------------------------- */
+/* the prefix of a one-frame image of ONE LF group: its file header and the one-frame frame header with is_last, byte
+ * aligned, appended to the plan buffer as frame record `fr` names it.  `bits` is the caller's to reuse.  Also what the
+ * mixed-size batch object plans every one of its frames with (mixed.c). */
+int hydk_plan_one_frame_prefix(Buf *buf, HydBits *bits, const HYDImageMetadata *md, const uint8_t *icc, size_t icc_size, HydkTileFrame *fr,
+                               const char **err) {
+    HydFrameLfg l;
+    memset(&l, 0, sizeof(l));
+    l.width = md->width;
+    l.height = md->height;
+    HydFrameShape shape;
+    memset(&shape, 0, sizeof(shape));
+    shape.one_frame = 1;
+    shape.image_width = shape.frame_width = md->width;
+    shape.image_height = shape.frame_height = md->height;
+    shape.tile_count_x = shape.tile_count_y = 8;
+    shape.lfg_count = 1;
+    shape.lfg = &l;
+    shape.is_last = 1;
+    hb_reset(bits);
+    int ret = hyd_internal_file_header(md, icc, icc_size, bits, err);
+    if (!ret)
+        ret = hyd_write_frame_header(bits, &shape, err);
+    if (ret && !*err)
+        *err = "frame header could not be written";
+    if (ret)
+        return ret;
+    hb_align(bits);
+    uint32_t nbits = 0;
+    fr->prefix_off = (uint32_t)buf_add_bits(buf, bits, &nbits);
+    fr->prefix_bytes = nbits >> 3;
+    return HYD_OK;
+}
+
 /* shapes of one LF group: a tile plan (hydk_tiles.h) whose one frame is the whole image — file header, the one-frame
  * frame header, is_last */
 static int plan_one_lf_group(const HYDImageMetadata *md, const uint8_t *icc, size_t icc_size, uint8_t **plan_out, size_t *plan_len,
@@ -70,35 +103,11 @@ static int plan_one_lf_group(const HYDImageMetadata *md, const uint8_t *icc, siz
     const size_t frames_off = ret ? 0 : buf_reserve(&buf, sizeof(HydkTileFrame));
     plan.frames_off = (uint32_t)frames_off;
     if (!ret && !buf.failed) {
-        HydFrameLfg l;
-        memset(&l, 0, sizeof(l));
-        l.width = md->width;
-        l.height = md->height;
-        HydFrameShape shape;
-        memset(&shape, 0, sizeof(shape));
-        shape.one_frame = 1;
-        shape.image_width = shape.frame_width = md->width;
-        shape.image_height = shape.frame_height = md->height;
-        shape.tile_count_x = shape.tile_count_y = 8;
-        shape.lfg_count = 1;
-        shape.lfg = &l;
-        shape.is_last = 1;
-        hb_reset(&bits);
-        ret = hyd_internal_file_header(md, icc, icc_size, &bits, err);
-        if (!ret)
-            ret = hyd_write_frame_header(&bits, &shape, err);
-        if (ret && !*err)
-            *err = "frame header could not be written";
-        if (!ret) {
-            hb_align(&bits);
-            HydkTileFrame fr;
-            uint32_t nbits = 0;
-            memset(&fr, 0, sizeof(fr));
-            fr.prefix_off = (uint32_t)buf_add_bits(&buf, &bits, &nbits);
-            fr.prefix_bytes = nbits >> 3;
-            if (!buf.failed)
-                memcpy(buf.p + frames_off, &fr, sizeof(fr));
-        }
+        HydkTileFrame fr;
+        memset(&fr, 0, sizeof(fr));
+        ret = hydk_plan_one_frame_prefix(&buf, &bits, md, icc, icc_size, &fr, err);
+        if (!ret && !buf.failed)
+            memcpy(buf.p + frames_off, &fr, sizeof(fr));
     }
     if (!ret && (buf.failed || bits.failed || part.failed)) {
         *err = "out of memory";

@@ -461,27 +461,13 @@ HYDRIUM_EXPORT size_t hydamd_tiled_device_bytes(HydAmdTiled *t) { return t ? (si
  * ------------------------------------------------------------------------------------------- */
 #ifdef HYD_TEST_HOOKS
 #define HYDT_EXPORT __attribute__((visibility("default")))
-HYDT_EXPORT int hydt_tiles_from_streams(const HYDImageMetadata *md, size_t nframes, const HydAmdLfStream *lf, const uint32_t *freq,
-                                        const uint32_t *alphabet, const uint32_t *group_bits, const uint32_t *max_alphabet,
-                                        const uint8_t *payload, size_t payload_len, uint64_t *frame_offsets /* [nframes + 1] or NULL */,
-                                        uint8_t **out, size_t *out_len, const char **err) {
-    static const char *none = NULL;
-    const char **e = err ? err : &none;
-    TileGeometry g;
-    uint8_t *plan = NULL;
-    size_t plan_len = 0;
-    *e = NULL;
-    int ret = tile_geometry(md, &g, e);
-    if (!ret && nframes != g.ntiles) {
-        *e = "one frame per tile of the image";
-        ret = HYD_API_ERROR;
-    }
-    if (!ret)
-        ret = build_plan(md, &g, &plan, &plan_len, e);
-    if (ret)
-        return ret;
-    const HydkTilePlan *hp = (const HydkTilePlan *)plan;
-    const HydkTileFrame *frames = (const HydkTileFrame *)(plan + hp->frames_off);
+/* frame f of `plan` laid out by frames[f] and shapes[frames[f].shape]: hydk_tile_prepare, hydk_tile_pieces and the shared
+ * composer, frame by frame (planbuf.h; also what mixed.c's hook runs on its own plan) */
+int hydt_layout_from_streams(const uint8_t *plan, const HydkTileFrame *frames, const HydkTileShape *shapes, size_t nframes,
+                             const HydAmdLfStream *lf, const uint32_t *freq, const uint32_t *alphabet, const uint32_t *group_bits,
+                             const uint32_t *max_alphabet, const uint8_t *payload, size_t payload_len, uint64_t *frame_offsets,
+                             uint8_t **out, size_t *out_len, const char **e) {
+    int ret = HYD_OK;
     HydAmdBlobSlot *rec = calloc(nframes, sizeof(*rec));
     uint32_t *head = calloc(nframes * HYDK_TILE_HEAD_WORDS, 4), *mid = calloc(nframes * HYDK_TILE_MID_WORDS, 4),
              *toc = calloc(nframes * HYDK_TILE_TOC_WORDS, 4);
@@ -517,7 +503,7 @@ HYDT_EXPORT int hydt_tiles_from_streams(const HYDImageMetadata *md, size_t nfram
             const size_t nb = ((size_t)lf[f].bit_count + 7) >> 3;
             if (nb)
                 memcpy(lf_packed + lf_at, lf[f].bits, nb);
-            const HydkTileShape *sh = &hp->shapes[frames[f].shape];
+            const HydkTileShape *sh = &shapes[frames[f].shape];
             hydk_tile_prepare(plan, &frames[f], sh, r, r->lf.lengths, lf_len, head + f * HYDK_TILE_HEAD_WORDS, mid + f * HYDK_TILE_MID_WORDS,
                               toc + f * HYDK_TILE_TOC_WORDS, scratch, &sizes[f]);
             if (sizes[f].err || hf_at + sizes[f].hf_bytes > payload_len) {
@@ -560,6 +546,31 @@ HYDT_EXPORT int hydt_tiles_from_streams(const HYDImageMetadata *md, size_t nfram
     free(scratch);
     free(lf_packed);
     free(hf);
+    return ret;
+}
+
+HYDT_EXPORT int hydt_tiles_from_streams(const HYDImageMetadata *md, size_t nframes, const HydAmdLfStream *lf, const uint32_t *freq,
+                                        const uint32_t *alphabet, const uint32_t *group_bits, const uint32_t *max_alphabet,
+                                        const uint8_t *payload, size_t payload_len, uint64_t *frame_offsets /* [nframes + 1] or NULL */,
+                                        uint8_t **out, size_t *out_len, const char **err) {
+    static const char *none = NULL;
+    const char **e = err ? err : &none;
+    TileGeometry g;
+    uint8_t *plan = NULL;
+    size_t plan_len = 0;
+    *e = NULL;
+    int ret = tile_geometry(md, &g, e);
+    if (!ret && nframes != g.ntiles) {
+        *e = "one frame per tile of the image";
+        ret = HYD_API_ERROR;
+    }
+    if (!ret)
+        ret = build_plan(md, &g, &plan, &plan_len, e);
+    if (ret)
+        return ret;
+    const HydkTilePlan *hp = (const HydkTilePlan *)plan;
+    ret = hydt_layout_from_streams(plan, (const HydkTileFrame *)(plan + hp->frames_off), hp->shapes, nframes, lf, freq, alphabet, group_bits,
+                                   max_alphabet, payload, payload_len, frame_offsets, out, out_len, e);
     free(plan);
     return ret;
 }

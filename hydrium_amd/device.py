@@ -33,6 +33,11 @@ class DeviceError(RuntimeError):
         self.message = msg
 
 
+class HydAmdImageDesc(C.Structure):  # include/hydrium_amd.h
+    _fields_ = [("src", C.c_void_p * 3), ("row_stride", C.c_ssize_t), ("pixel_stride", C.c_ssize_t), ("width", C.c_size_t),
+                ("height", C.c_size_t)]
+
+
 _dll = None
 
 
@@ -192,6 +197,26 @@ def dll(path: Optional[str] = None):
         d.hydamd_batch_read.argtypes = [vp, i, C.POINTER(C.c_uint8), sz]
         d.hydamd_batch_overflow_reruns.restype = u
         d.hydamd_batch_overflow_reruns.argtypes = [vp]
+        d.hydamd_mixed_create.restype = vp
+        d.hydamd_mixed_create.argtypes = [i, i, i, C.POINTER(i)]
+        d.hydamd_mixed_destroy.restype = None
+        d.hydamd_mixed_destroy.argtypes = [vp]
+        d.hydamd_mixed_error.restype = C.c_char_p
+        d.hydamd_mixed_error.argtypes = [vp]
+        d.hydamd_encode_mixed.restype = i
+        d.hydamd_encode_mixed.argtypes = [vp, i, C.POINTER(HydAmdImageDesc), i]
+        d.hydamd_mixed_result.restype = i
+        d.hydamd_mixed_result.argtypes = [vp, C.POINTER(sz)]
+        d.hydamd_mixed_offsets.restype = i
+        d.hydamd_mixed_offsets.argtypes = [vp, C.POINTER(C.c_uint64)]
+        d.hydamd_mixed_device.restype = C.POINTER(C.c_uint8)
+        d.hydamd_mixed_device.argtypes = [vp]
+        d.hydamd_mixed_offsets_device.restype = C.POINTER(C.c_uint64)
+        d.hydamd_mixed_offsets_device.argtypes = [vp]
+        d.hydamd_mixed_read.restype = i
+        d.hydamd_mixed_read.argtypes = [vp, i, C.POINTER(C.c_uint8), sz]
+        d.hydamd_mixed_overflow_reruns.restype = u
+        d.hydamd_mixed_overflow_reruns.argtypes = [vp]
         if path is not None:
             return d
         _dll = d
@@ -904,6 +929,110 @@ class FrameBatch:
 
     def overflow_reruns(self) -> int:
         return int(self.d.hydamd_batch_overflow_reruns(self.h))
+
+
+class MixedBatch:
+    """Batches of up to ``max_frames`` (0: the default, 32) one-frame images, EACH OF ITS OWN SIZE up to 2048 x 2048, from
+    device-resident pixels, every one a finished file built on the GPU (hydamd_mixed_*, csrc/host/mixed.c): the files back
+    to back in one device buffer, the table of their offsets beside it.  Conventions as FrameBatch's."""
+
+    def __init__(self, max_frames: int = 0, linear_light: int = 0, device: int = 0):
+        self.d = dll()
+        st = C.c_int(0)
+        self.h = self.d.hydamd_mixed_create(device, max_frames, int(linear_light), C.byref(st))
+        if not self.h:
+            raise DeviceError(st.value, (self.d.hydamd_mixed_error(None) or b"").decode() or "mixed batch could not be created")
+        self.max_frames = max_frames or 32
+        self.frames = 0
+        self._keep = None
+
+    def close(self):
+        if self.h:
+            self.d.hydamd_mixed_destroy(self.h)
+            self.h = None
+        self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _ck(self, code: int):
+        if code != 0:
+            raise DeviceError(code, (self.d.hydamd_mixed_error(self.h) or b"").decode())
+
+    def encode(self, imgs, sample_fmt: Optional[int] = None):
+        """imgs: one entry per image, each of its own size and layout — an interleaved (H, W, C >= 3) torch tensor on the
+        object's device (any row pitch; C > 3: the first three channels, pixel stride C), a triple of (H, W) plane
+        tensors, or (ptrs, row_stride, pixel_stride, width, height) with three device addresses and strides in samples
+        (then sample_fmt is the caller's).  One sample format per call.  Asynchronous: the pixels must stay alive and
+        unchanged until result()."""
+        descs = (HydAmdImageDesc * max(len(imgs), 1))()
+        for k, img in enumerate(imgs):
+            if hasattr(img, "data_ptr"):
+                isz = img.element_size()
+                ptrs = [img.data_ptr() + c * isz for c in range(3)]
+                rs, ps, (h, w) = img.stride(0), img.stride(1), img.shape[:2]
+                fmt = {1: 0, 2: 1, 4: 2}[isz]
+            elif hasattr(img[0], "data_ptr"):  # planes keep their shape: the size is theirs, never a bare pointer's
+                ptrs = [p.data_ptr() for p in img]
+                rs, ps, (h, w) = img[0].stride(0), img[0].stride(1), img[0].shape[:2]
+                if any(tuple(p.shape[:2]) != (h, w) or (p.stride(0), p.stride(1)) != (rs, ps) for p in img):
+                    raise ValueError("the three planes of an image share one shape and one layout")
+                fmt = {1: 0, 2: 1, 4: 2}[img[0].element_size()]
+            else:
+                ptrs, rs, ps, w, h = img
+                ptrs = [int(p) if p is not None else None for p in ptrs]
+                if sample_fmt is None:
+                    raise ValueError("device addresses need sample_fmt")
+                fmt = sample_fmt
+            if sample_fmt is None:
+                sample_fmt = fmt
+            elif fmt != sample_fmt:
+                raise ValueError("the images of a batch share one sample format")
+            descs[k] = HydAmdImageDesc((C.c_void_p * 3)(*ptrs), int(rs), int(ps), int(w), int(h))
+        self._keep = imgs
+        self._ck(self.d.hydamd_encode_mixed(self.h, len(imgs), descs, sample_fmt if sample_fmt is not None else -1))
+        self.frames = len(imgs)
+
+    def result(self) -> int:
+        """Waits for the batch; bytes of all its files."""
+        n = C.c_size_t(0)
+        try:
+            self._ck(self.d.hydamd_mixed_result(self.h, C.byref(n)))
+        finally:
+            self._keep = None
+        return int(n.value)
+
+    def offsets(self) -> np.ndarray:
+        """uint64[frames + 1]: file k is bytes offsets[k] .. offsets[k + 1] of the device buffer."""
+        self.result()
+        out = np.zeros(self.frames + 1, np.uint64)
+        self._ck(self.d.hydamd_mixed_offsets(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def read(self, k: Optional[int] = None):
+        """File k as a uint8 array; None: the list of all files (one copy from the device)."""
+        off = self.offsets()
+        if k is None:
+            buf = np.empty(max(int(off[-1]), 1), np.uint8)
+            self._ck(self.d.hydamd_mixed_read(self.h, -1, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
+            return [buf[int(off[i]):int(off[i + 1])] for i in range(self.frames)]
+        if not 0 <= k < self.frames:
+            raise IndexError("no such frame in the batch")
+        buf = np.empty(max(int(off[k + 1] - off[k]), 1), np.uint8)
+        self._ck(self.d.hydamd_mixed_read(self.h, k, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
+        return buf[: int(off[k + 1] - off[k])]
+
+    def device_ptr(self) -> int:
+        return C.cast(self.d.hydamd_mixed_device(self.h), C.c_void_p).value or 0
+
+    def offsets_device_ptr(self) -> int:
+        return C.cast(self.d.hydamd_mixed_offsets_device(self.h), C.c_void_p).value or 0
+
+    def overflow_reruns(self) -> int:
+        return int(self.d.hydamd_mixed_overflow_reruns(self.h))
 
 
 def decode_token_records(rec: np.ndarray):

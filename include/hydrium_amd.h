@@ -578,6 +578,65 @@ HYDAMD_EXPORT const uint64_t *hydamd_batch_offsets_device(HydAmdBatch *b);
 HYDAMD_EXPORT int hydamd_batch_read(HydAmdBatch *b, int frame, uint8_t *dst, size_t capacity);
 HYDAMD_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b);
 
+/*
+ * A batch of one-frame images EACH OF ITS OWN SIZE whose pixels already sit in HBM, every one a finished FILE, built on
+ * the GPU (csrc/host/mixed.c, csrc/hip/assemble_batch.hip) — for a queue of pictures of many sizes in device memory
+ * (thumbnails, product shots, crops, the output of a GPU decoder), which hydamd_batch_* would need one object per shape
+ * for.  Every image is at most 2048 x 2048 pixels, ONE LF group; the images of a batch are coded as one launch group
+ * (hydamd_begin_batch(ctx, 1, frames), each LF group of its own size, as a tile-mode image's ragged tiles are), and the
+ * launch sequence behind hydamd_batch_*'s entropy stage writes every frame — file header, frame header with is_last, TOC,
+ * LFGlobal, LF group, HFGlobal, HF sections; images of a single 256x256 group as one bit-contiguous section — exactly as
+ * the reference writes that picture alone with tile_size_shift_x = tile_size_shift_y = -1, the files back to back at byte
+ * granularity in ONE device buffer the object owns, with the table of their offsets beside it.  The host contributes
+ * the bytes that do not depend on the pixels — a plan per batch, a record per distinct size and one per image, uploaded
+ * in the stream; a batch whose list of sizes equals the previous batch's reuses the plan on the device — and waits once
+ * per batch.  The protocol is hydamd_batch_*'s, call for call.
+ *   hydamd_mixed_create          max_frames: images a batch may hold, 1..255 (the slots of the object's one context),
+ *                                0 = default (32); an LF-group slot of the context costs 70-100 MB of device memory
+ *                                whatever the image sizes, so the default object holds about 3 GB plus the output
+ *                                buffer, one of 255 about 22 GB.  linear_light: as HYDImageMetadata's, for every image.
+ *                                One device and one stream per object.
+ *   hydamd_encode_mixed          `frames` <= max_frames images: images[k].src are image k's channel pointers (device
+ *                                memory, its first pixel), row_stride / pixel_stride in samples as hyd_send_tile's,
+ *                                width and height 1..2048; one sample_fmt for the whole call.  Enqueues the batch and
+ *                                its assembly and returns; the pixels stay borrowed until hydamd_mixed_result, the
+ *                                descriptors only for the call.  The output buffer is sized before anything is
+ *                                enqueued, from the batch's plan and the context's capacities.
+ *   hydamd_mixed_result          waits; *total_bytes = bytes of all files.  A batch that outgrew the context's buffers is
+ *                                rerun inside hydamd_sync and exported and assembled again first (never
+ *                                HYD_NEED_MORE_OUTPUT).  A non-finite float sample ANYWHERE fails the WHOLE batch —
+ *                                HYD_API_ERROR "Invalid NaN Float"; the image cannot be named.  After a failure the
+ *                                stream is drained and the object stays usable.
+ *   hydamd_mixed_offsets         offsets[k] .. offsets[k + 1] bound file k; offsets[0] = 0, offsets[frames] = total.
+ *   hydamd_mixed_device,         the files and the same table (frames + 1 entries) in device memory.  Everything is
+ *   hydamd_mixed_offsets_device  valid until the object's next hydamd_encode_mixed.
+ *   hydamd_mixed_read            file `frame` (or, with -1, all of them back to back) to host memory, one copy.
+ * HYD_API_ERROR: max_frames out of range, a null descriptor array or channel pointer, a width or height of 0 or above
+ * 2048, `frames` outside 1..max_frames, a bad sample format, a second encode while a batch is in flight, result / offsets
+ * / read without a batch, a destination that is too small.  No usable device at creation: HYD_INTERNAL_ERROR.
+ * hydamd_mixed_overflow_reruns: batches run twice because a buffer was too small.  Keep several objects for a deeper
+ * queue (scripts/mixed_batch_probe.py keeps four).
+ * OUT OF SCOPE: images of more than one LF group (a context's slots per frame, cluster scheme and preset bits are
+ * uniform per launch group: such images go through one hydamd_batch_* object per shape); an ICC profile (it would sit in
+ * every frame's prefix); sample formats mixed within one call; naming the image that held a NaN; several devices per object.
+ */
+typedef struct HydAmdImageDesc {
+    const void *src[3];                 /* device pointers: R, G, B of the image's first pixel */
+    ptrdiff_t row_stride, pixel_stride; /* in samples, as hyd_send_tile's */
+    size_t width, height;               /* 1..2048 each */
+} HydAmdImageDesc;
+typedef struct HydAmdMixed HydAmdMixed;
+HYDAMD_EXPORT HydAmdMixed *hydamd_mixed_create(int device, int max_frames, int linear_light, int *status);
+HYDAMD_EXPORT void hydamd_mixed_destroy(HydAmdMixed *m);
+HYDAMD_EXPORT const char *hydamd_mixed_error(HydAmdMixed *m);
+HYDAMD_EXPORT int hydamd_encode_mixed(HydAmdMixed *m, int frames, const HydAmdImageDesc *images, int sample_fmt);
+HYDAMD_EXPORT int hydamd_mixed_result(HydAmdMixed *m, size_t *total_bytes);
+HYDAMD_EXPORT int hydamd_mixed_offsets(HydAmdMixed *m, uint64_t *offsets);
+HYDAMD_EXPORT const uint8_t *hydamd_mixed_device(HydAmdMixed *m);
+HYDAMD_EXPORT const uint64_t *hydamd_mixed_offsets_device(HydAmdMixed *m);
+HYDAMD_EXPORT int hydamd_mixed_read(HydAmdMixed *m, int frame, uint8_t *dst, size_t capacity);
+HYDAMD_EXPORT unsigned hydamd_mixed_overflow_reruns(HydAmdMixed *m);
+
 #ifdef __cplusplus
 }
 #endif
