@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libhydrium.so.0")
 PROBE_PATH = os.path.join(LIB_DIR, "libhydrium_probe.so")
 HOSTTEST_PATH = PROBE_PATH
 # HIP sources that read HYD_TEST_HOOKS (the others are compiled once and shared by both flavours)
-HOOKED_HIP = ("device_api.hip",)
+HOOKED_HIP = ("device_api.hip", "assemble.hip")
 
 ARCH = os.environ.get("HYDAMD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -333,4 +333,58 @@ int hydk_asm_debug(HydkAsm *a, uint32_t slot, uint32_t *head_bits, uint32_t *hea
     return ST_OK;
 }
 
+#ifdef HYD_TEST_HOOKS
+/* k_pieces_copy itself on a crafted list (tests/test_gpu_builder_content.py; the probe flavour only): the arguments of
+ * tiled.c's hydt_compose_pieces, which runs the same composer on the host, plus what a kernel launch has to be told —
+ * how long `src` and `out` are, and the error word of the range.  Piece i is nbits[i] bits from byte src_off[i] of `src`,
+ * at bit dst_bit[i]; the range is bytes [lo, lo + bytes) of `out`.  `src` is uploaded into one allocation with 16 bytes
+ * of slack on either side, `out` (filled by the caller) as it is; one launch through hydk::launch_pieces_copy, and the
+ * WHOLE buffer comes back: a store outside the range shows.  Lists that would read or write outside the two buffers
+ * are refused here, before anything is launched. */
+__attribute__((visibility("default"))) int hydt_pieces_copy_device(const uint64_t *dst_bit, const uint64_t *nbits, const uint64_t *src_off,
+                                                                   uint32_t np, const uint8_t *src, uint64_t src_bytes, uint64_t lo,
+                                                                   uint64_t bytes, uint32_t err_word, uint8_t *out, uint64_t out_bytes) {
+    constexpr size_t kSlack = 16;
+    if (!src || !out || (np && (!dst_bit || !nbits || !src_off)) || np > HYDK_COPY_MAX_PIECES || (out_bytes & 3u) ||
+        lo > out_bytes || bytes > out_bytes - lo || ((lo + bytes + 3) & ~(uint64_t)3) > out_bytes)
+        return ST_API_ERROR;
+    for (uint32_t i = 0; i < np; i++)
+        if (src_off[i] > src_bytes || ((nbits[i] + 7) >> 3) > src_bytes - src_off[i])
+            return ST_API_ERROR;
+    uint8_t *d_src = nullptr, *d_out = nullptr;
+    HydkPiece *d_P = nullptr;
+    uint64_t *d_range = nullptr;
+    HydkPiece *P = new (std::nothrow) HydkPiece[np ? np : 1];
+    if (!P)
+        return ST_NOMEM;
+    auto run = [&]() -> int {
+        HYDK_TRY((HydkAsm *)nullptr, hipMalloc(&d_src, (size_t)src_bytes + 2 * kSlack));
+        HYDK_TRY((HydkAsm *)nullptr, hipMalloc(&d_out, (size_t)out_bytes + 4));
+        HYDK_TRY((HydkAsm *)nullptr, hipMalloc(&d_P, (np ? np : 1) * sizeof(HydkPiece)));
+        HYDK_TRY((HydkAsm *)nullptr, hipMalloc(&d_range, 4 * sizeof(uint64_t)));
+        for (uint32_t i = 0; i < np; i++)
+            P[i] = hydk_piece(dst_bit[i], d_src + kSlack + src_off[i], nbits[i]);
+        const uint64_t range[4] = {err_word, lo, bytes, 0};
+        HYDK_TRY((HydkAsm *)nullptr, hipMemset(d_src, 0x3C, (size_t)src_bytes + 2 * kSlack));
+        HYDK_TRY((HydkAsm *)nullptr, hipMemcpy(d_src + kSlack, src, (size_t)src_bytes, hipMemcpyHostToDevice));
+        HYDK_TRY((HydkAsm *)nullptr, hipMemcpy(d_out, out, (size_t)out_bytes, hipMemcpyHostToDevice));
+        if (np)
+            HYDK_TRY((HydkAsm *)nullptr, hipMemcpy(d_P, P, np * sizeof(HydkPiece), hipMemcpyHostToDevice));
+        HYDK_TRY((HydkAsm *)nullptr, hipMemcpy(d_range, range, sizeof(range), hipMemcpyHostToDevice));
+        HYDK_TRY((HydkAsm *)nullptr, hipDeviceSynchronize()); /* the memset ran in the NULL stream */
+        HYDK_TRY((HydkAsm *)nullptr, hydk::launch_pieces_copy(d_P, np, nullptr, d_range, d_out, nullptr));
+        HYDK_TRY((HydkAsm *)nullptr, hipDeviceSynchronize());
+        HYDK_TRY((HydkAsm *)nullptr, hipMemcpy(out, d_out, (size_t)out_bytes, hipMemcpyDeviceToHost));
+        return ST_OK;
+    };
+    const int st = run();
+    void *dev[] = {d_src, d_out, d_P, d_range};
+    for (void *p : dev)
+        if (p)
+            (void)hipFree(p);
+    delete[] P;
+    return st;
+}
+#endif /* HYD_TEST_HOOKS */
+
 } /* extern "C" */

@@ -588,6 +588,18 @@ __device__ __forceinline__ void store_record(void *tok, uint32_t at, uint32_t to
     }
 }
 
+/* float -> int as the reference's quantisation converts (encoder.c:582,808: a C cast, on the reference's platform one
+ * cvttss2si): what does not fit — 2^31 and above, NaN — gives INT_MIN, where v_cvt_i32_f32 saturates to INT_MAX and turns
+ * NaN into 0.  Only float input reaches such values (samples outside [0, 1] whose weighted sum is negative: the cube
+ * root's approximation of a negative number is some 1e12); integer input keeps the bare conversion. */
+template <int FMT>
+__device__ __forceinline__ int trunc_as_reference(float x) {
+    const int q = (int)x;
+    if (FMT != HYDK_FMT_F32)
+        return q;
+    return x < 2147483648.0f ? q : (int)0x80000000u;
+}
+
 #define HYDK_K1_OCCUPANCY __launch_bounds__(kThreads, HYDK_K1_WAVES)
 template <int FMT, int XMODE>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
@@ -950,9 +962,11 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                 for (int kv = 0; kv < 8; kv++) {
                     /* encoder.c:808-811: trunc((coef * weight) * 5); +-1 is the dead zone */
                     const float scaled = v[kv] * wq[kv] * 5.0f;
-                    int qq = (int)scaled;
-                    /* |trunc(x)| >= 2 exactly when |x| >= 2 (NaN: neither, and converts to 0) */
-                    const bool nz = __builtin_fabsf(scaled) >= 2.0f && !(kv == 0 && kh == 0); /* the DC slot is coded by the LF path */
+                    int qq = trunc_as_reference<FMT>(scaled);
+                    /* |trunc(x)| >= 2 exactly when |x| >= 2 (NaN: neither, and converts to 0; float input: NaN converts
+                     * to INT_MIN as the reference's does, and is kept) */
+                    const bool nz = (FMT == HYDK_FMT_F32 ? !(__builtin_fabsf(scaled) < 2.0f) : __builtin_fabsf(scaled) >= 2.0f) &&
+                                    !(kv == 0 && kh == 0); /* the DC slot is coded by the LF path */
                     qq = nz ? qq : 0;
                     q[kv] = qq;
                     if (kv < 4)
@@ -989,7 +1003,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                 /* the loaded masks are first used after the loop: the next channel's transform runs while they travel */
                 if (!(HYDK_K1_SKIP & 4))
                 msk[c] = *(const unsigned long long *)(nib + (nib_row | nlo)) | *(const unsigned long long *)(nib + (nib_row | 128u | nhi));
-                lf_int[c] = (int32_t)(v[0] * kLfShift[c]); /* LF int: trunc(dc * shift[c]) (encoder.c:573,582) */
+                lf_int[c] = trunc_as_reference<FMT>(v[0] * kLfShift[c]); /* LF int: trunc(dc * shift[c]) (encoder.c:573,582) */
         };
 #if HYDK_K1_CHANSEQ
         {

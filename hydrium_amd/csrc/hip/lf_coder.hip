@@ -296,25 +296,34 @@ __device__ __forceinline__ uint32_t lf_tokens_window(const HydkLfJob &job, const
     const int last_q = sh.n - 1 - tb; /* window-relative index of the stream's last value */
     uint32_t lit[4], r[4];
     bool need[4], any_need = false;
-    int s4v[4];
+    int s4v[4], hq[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int q = q0 + j;
         const bool valid = q < kEmitSpan && q <= last_q;
-        const int c = (tb + q - rs[j]) & 127;
+        /* The symbol 0xFFFFFFFF (the residual of an LF int of INT_MIN, which only float input reaches) is the one the
+         * reference's run detector cannot tell from "no symbol yet": it keeps last_symbol = symbol + 1, 0 for none
+         * (entropy.c:508,520).  So up to 3 repeats behind such a literal are not written at all (entropy.c:489 sends them
+         * only if last_symbol is set), and a stream that STARTS with it takes its first values for repeats of a value
+         * in front of the stream: the run's chunks count from position -1, whose literal nobody sends and whose run
+         * pair — when more than 3 values follow it — position 0 sends. */
+        const bool wraps = v[j] == 0xFFFFFFFFu;
+        const bool phantom = wraps && tb + q == 0;
+        const int c = (tb + q - rs[j] + (wraps && rs[j] == 0 ? 1 : 0)) & 127;
         const int s4 = q - c + 4;
         const bool same4 = c <= 3 && s4 <= last_q && s_rs[s4 < kScanSpan ? s4 : kScanSpan - 1] == rs[j];
-        lit[j] = valid && (c == 0 || (c <= 3 && !same4));
-        need[j] = valid && c == 0 && same4;
+        lit[j] = valid && (c == 0 || (c <= 3 && !same4 && !wraps));
+        need[j] = valid && (c == 0 || phantom) && same4;
         r[j] = 0;
         s4v[j] = s4;
+        hq[j] = q - c; /* the chunk's head: q itself, or -1 in front of the stream */
         any_need |= need[j];
     }
     if (__any(any_need)) { /* some chunk head has a run behind it: how long, up to 127 (7 halvings) */
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int q = q0 + j;
-            int lo = need[j] ? s4v[j] : 0, hi = q + 127 < last_q ? q + 127 : last_q;
+            int lo = need[j] ? s4v[j] : 0, hi = hq[j] + 127 < last_q ? hq[j] + 127 : last_q;
             hi = need[j] ? hi : 0;
 #pragma unroll
             for (int it = 0; it < 7; it++) {
@@ -323,7 +332,7 @@ __device__ __forceinline__ uint32_t lf_tokens_window(const HydkLfJob &job, const
                 lo = in_run ? mid : lo;
                 hi = in_run ? hi : mid - 1;
             }
-            r[j] = need[j] ? (uint32_t)(lo - q) : 0u;
+            r[j] = need[j] ? (uint32_t)(lo - hq[j]) : 0u;
         }
     }
     uint32_t residue_bits = 0;

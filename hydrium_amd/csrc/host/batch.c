@@ -410,3 +410,44 @@ HYDRIUM_EXPORT const uint64_t *hydamd_batch_offsets_device(HydAmdBatch *b) {
 }
 
 HYDRIUM_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b) { return b ? b->reruns : 0; }
+
+/* ---------------------------------------------------------------------------------------------
+ * CPU-only test hook: the plan of a batch of one-LF-group frames (plan_one_lf_group above, the product's own) and the
+ * batched layout (hydk_tiles.h compiled for the host, tiled.c's hydt_layout_from_streams) on results handed in as
+ * hydt_tiles_from_streams takes them, one frame per picture, every one laid out by the plan's ONE frame record — what
+ * k_batch_prepare_one, k_batch_place and k_pieces_copy do, held to frame.c by tests/test_batch_layout.py.  (Shapes of
+ * several LF groups go through hydk_asm_writers.h, which has no host build: those are held on the GPU only.)
+ * ------------------------------------------------------------------------------------------- */
+#ifdef HYD_TEST_HOOKS
+__attribute__((visibility("default"))) int hydt_batch_from_streams(const HYDImageMetadata *md, size_t nframes, const HydAmdLfStream *lf,
+                                                                   const uint32_t *freq, const uint32_t *alphabet, const uint32_t *group_bits,
+                                                                   const uint32_t *max_alphabet, const uint8_t *payload, size_t payload_len,
+                                                                   uint64_t *frame_offsets /* [nframes + 1] or NULL */, uint8_t **out,
+                                                                   size_t *out_len, const char **err) {
+    static const char *none = NULL;
+    const char **e = err ? err : &none;
+    uint8_t *plan = NULL;
+    size_t plan_len = 0;
+    *e = NULL;
+    if (!md || nframes < 1 || nframes > HYDK_TILE_MAX_FRAMES || md->width > 2048 || md->height > 2048) {
+        *e = "between 1 and 255 frames of one LF group";
+        return HYD_API_ERROR;
+    }
+    int ret = plan_one_lf_group(md, NULL, 0, &plan, &plan_len, e);
+    if (ret)
+        return ret;
+    const HydkTilePlan *hp = (const HydkTilePlan *)plan;
+    HydkTileFrame *frames = malloc(nframes * sizeof(*frames));
+    if (!frames) {
+        free(plan);
+        return HYD_NOMEM;
+    }
+    for (size_t f = 0; f < nframes; f++) /* k_batch_prepare_one: every frame is frame 0 of the tile plan */
+        frames[f] = ((const HydkTileFrame *)(plan + hp->frames_off))[0];
+    ret = hydt_layout_from_streams(plan, frames, hp->shapes, nframes, lf, freq, alphabet, group_bits, max_alphabet, payload, payload_len,
+                                   frame_offsets, out, out_len, e);
+    free(frames);
+    free(plan);
+    return ret;
+}
+#endif /* HYD_TEST_HOOKS */

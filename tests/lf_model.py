@@ -153,7 +153,13 @@ def hybrid(v: np.ndarray):
 
 
 def emissions(v: np.ndarray):
-    """Per position: literal flag and run length r (0 = no run pair), entropy.c:473-524."""
+    """Per position: literal flag and run length r (0 = no run pair), entropy.c:473-524.
+
+    The symbol 0xFFFFFFFF (the residual of an LF int of INT_MIN) is the one the reference cannot tell from "no symbol
+    yet": it keeps last_symbol = symbol + 1, 0 for none (entropy.c:508,520).  Up to 3 repeats behind such a literal are
+    dropped (entropy.c:489 sends them only if last_symbol is set), and a stream that starts with it takes its first
+    values for repeats of a value in front of the stream: the run's chunks count from position -1, whose literal nobody
+    sends and whose run pair, when more than 3 values follow, is sent at position 0."""
     n = len(v)
     head = np.ones(n, bool)
     head[1:] = v[1:] != v[:-1]
@@ -161,12 +167,14 @@ def emissions(v: np.ndarray):
     start = np.maximum.accumulate(np.where(head, idx, 0))
     nxt = np.where(head, idx, n)
     end = np.minimum.accumulate(np.append(nxt[1:], n)[::-1])[::-1]  # first head after i
-    off = idx - start
+    wraps = v == np.uint64(0xFFFFFFFF)
+    off = idx - start + (wraps & (start == 0))
     c = off & 127
     chunk_start = idx - c
     r_chunk = np.minimum(127, end - chunk_start - 1)
-    lit = (c == 0) | ((c <= 3) & (r_chunk <= 3))
-    r = np.where((c == 0) & (r_chunk > 3), r_chunk, 0)
+    lit = (c == 0) | ((c <= 3) & (r_chunk <= 3) & ~wraps)
+    sends_pair = (c == 0) | (wraps & (idx == 0))
+    r = np.where(sends_pair & (r_chunk > 3), r_chunk, 0)
     return lit, r
 
 

@@ -134,6 +134,40 @@ def test_float_input_large_residuals():
     assert lf_model.coded_lf_group(65, 33, lengths, alphabet, pairs, bits, nbits) == lf_model.host_lf_group(dc)
 
 
+def _starts_with_wrapping_symbols(first, w=136, h=24):
+    """float picture whose first `first` LF residuals are 0xFFFFFFFF: blocks of -0.4 (the reference's cube root of a
+    negative sum is some 1e12, its LF int INT_MIN) alternate with black ones (LF int 0) along the top row; grey behind
+    them, and noise in [-0.5, 1.5) everywhere else"""
+    img = (synth.make_image_f32("noise", w, h, seed=9) * 2.0 - 0.5).astype(np.float32)
+    for k in range(first):
+        img[:8, 8 * k:8 * k + 8] = -0.4 if k % 2 == 0 else 0.0
+    img[:8, 8 * first:8 * first + 8] = 0.5
+    return np.ascontiguousarray(img)
+
+
+@pytest.mark.parametrize("first", [0, 1, 3, 4, 6])
+def test_lf_ints_of_int_min_at_the_start_of_the_stream_and_inside_it(first):
+    """the residual symbol 0xFFFFFFFF, which the reference's run detector takes for "no symbol yet" (tests/lf_model.py's
+    emissions, tests/test_lf_model.py): the device's stream spliced by the host equals the host coder's section, and is
+    the model's"""
+    import torch
+
+    img = _starts_with_wrapping_symbols(first)
+    t = torch.from_numpy(img).cuda()
+    with dev.DeviceContext(0, 1) as c:
+        c.encode_image_tensor(t)
+        c.sync()
+        dc = c.read_dc(0, 17, 3)
+        lengths, alphabet, pairs, nbits = c.read_lf_stream(0)
+        bits = c.read_lf_bits(0, nbits)
+    v = lf_model.residuals(dc)
+    assert (v[:first] == 0xFFFFFFFF).all() and v[first] != 0xFFFFFFFF and (v[first + 1:] == 0xFFFFFFFF).any()
+    assert lf_model.coded_lf_group(17, 3, lengths, alphabet, pairs, bits, nbits) == lf_model.host_lf_group(dc)
+    _, m_lengths, m_alphabet, m_pairs, m_bits, m_nbits = lf_model.model(dc)
+    assert (alphabet, pairs, nbits) == (m_alphabet, m_pairs, m_nbits)
+    assert np.array_equal(lengths, m_lengths) and np.array_equal(bits[:nbits // 8], m_bits[:nbits // 8])  # (whole bytes)
+
+
 def test_api_bytes_identical_with_host_lf_coder(monkeypatch):
     from hydrium_amd import api
 

@@ -55,3 +55,46 @@ def test_model_run_rules():
     assert lit[s] and r[s] == 127 and lit[s + 128] and r[s + 128] == 0  # 8 x129: chunk + lone literal
     s = 137 + 129
     assert r[s] == 127 and lit[s + 128] and r[s + 128] == 4       # 9 x133: chunk + literal + run of 4
+
+
+INT_MIN = -(1 << 31)
+
+
+@pytest.mark.parametrize("first", range(0, 9))
+@pytest.mark.parametrize("seed", range(3))
+def test_lf_ints_of_int_min(first, seed):
+    """An LF int of INT_MIN next to other values leaves the residual symbol 0xFFFFFFFF, which the reference's run
+    detector takes for "no symbol yet" (entropy.c:508,520; the host coder does the same): runs of it of every length
+    around the minimum run length and the chunk size, at the start of the stream (`first` values of it in front: the
+    reference takes them for repeats of nothing) and inside it, against the host coder."""
+    rng = np.random.default_rng(100 + seed)
+    vbw, vbh = 70, 23
+    a = rng.integers(-900, 900, 3 * vbh * vbw).astype(np.int64)
+    # rows of INT_MIN give residuals of zero behind one 0xFFFFFFFF; isolated ones give it two or three times in a row
+    a[rng.random(a.size) < (0.02, 0.3, 0.9)[seed]] = INT_MIN
+    dc = a.reshape(3, vbh, vbw).astype(np.int32)
+    # residual k of the stream is Y's k-th: the first `first` alternate INT_MIN / 0 so that each residual is 0xFFFFFFFF
+    dc[1, 0, :first] = [INT_MIN if k % 2 == 0 else 0 for k in range(first)]
+    if first < vbw:
+        dc[1, 0, first] = 5 if first % 2 == 0 else INT_MIN + 7
+    v = lf_model.residuals(dc)
+    assert (v[:first] == 0xFFFFFFFF).all() and (first >= vbw or v[first] != 0xFFFFFFFF)
+    want = lf_model.host_lf_group(dc)
+    _, lengths, alphabet, pairs, bits, nbits = lf_model.model(dc)
+    assert lf_model.coded_lf_group(vbw, vbh, lengths, alphabet, pairs, bits, nbits) == want
+
+
+def test_model_run_rules_of_the_symbol_that_wraps():
+    S = 0xFFFFFFFF
+    v = np.array([S] * 3 + [1] + [S] * 3 + [2] + [S] * 6 + [3], np.uint64)
+    lit, r = lf_model.emissions(v)
+    assert not lit[:3].any() and not r[:3].any()                  # in front of the stream, 3 or fewer: never written
+    assert lit[4] and not lit[5:7].any() and not r[4:7].any()     # literal, its 2 repeats dropped
+    assert lit[8] and r[8] == 5 and not lit[9:14].any()           # literal + run of 5
+    v = np.array([S] * 130 + [4], np.uint64)
+    lit, r = lf_model.emissions(v)
+    assert not lit[0] and r[0] == 127 and not lit[1:127].any()    # 127 repeats of nothing as one pair
+    assert lit[127] and r[127] == 0 and not lit[128:130].any()    # then a literal whose 2 repeats are dropped
+    v = np.array([S] * 5 + [4], np.uint64)
+    lit, r = lf_model.emissions(v)
+    assert not lit[:5].any() and r[0] == 5 and lit[5]

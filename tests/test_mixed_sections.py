@@ -11,6 +11,7 @@ import pytest
 from hydrium_amd import api, build as hbuild
 from oracle import binding as orc
 
+import content_corpus as cc
 import glue
 import lf_model
 
@@ -135,6 +136,28 @@ def test_one_image_and_the_largest_side(lib, image):
     """a batch of one; and 2048 x 16, the widest one LF group gets (eight groups in a row)"""
     for sizes in ([(232, 188)], [(2048, 16), (16, 300)]):
         _hold(lib, sizes, [_picture(image, 40 + k, w, h) for k, (w, h) in enumerate(sizes)])
+
+
+@pytest.mark.parametrize("depth", sorted(cc.MIXED))
+def test_the_content_corpus_forward_and_reversed(lib, depth):
+    """one batch per sample format of the pictures that move the layout's own fields furthest (tests/content_corpus.py):
+    files of 102 bytes beside files of 250 KB in one offsets table, HF sections of 4 bytes beside ones above 100 KB, TOCs
+    of 10-bit entries only and of 10- and 22-bit ones, an empty LF stream, token 28, log_alphabet_size 7 beside 5 — each
+    file what frame.c writes for that picture alone"""
+    pictures = cc.MIXED[depth]
+    sizes = [(w, h) for _, w, h, _, _ in pictures]
+    stages = [(r, mx, want) for r, mx, _, want in (cc.stage(*p) for p in pictures)]
+    assert len({want for _, _, want in stages}) == len(stages)
+    fwd, foffs = _hold(lib, sizes, stages)
+    rev, roffs = _hold(lib, sizes[::-1], stages[::-1])
+    n = len(stages)
+    assert [rev[roffs[k]:roffs[k + 1]] for k in range(n)] == [fwd[foffs[k]:foffs[k + 1]] for k in range(n)][::-1]
+    lens = [len(want) for _, _, want in stages]
+    print(f"{depth}-bit corpus batch: files of", lens, "bytes")
+    if depth == 8:
+        assert min(lens) < 128 and max(lens) > 200 * 1024  # the extremes of one offsets table
+    if depth == 32:
+        assert [r.log_alphabet_size for r, _, _ in stages] == [7, 5, 5, 7]
 
 
 def test_what_the_hook_refuses(lib):

@@ -21,10 +21,15 @@ SRC = np.random.default_rng(7).integers(0, 256, 4096, dtype=np.uint8)
 SRC_BITS = np.unpackbits(SRC, bitorder="little")
 
 
+def _out_size(lo, nbytes):
+    """bytes of the buffer a range is composed into: whole words, and two more behind them that must stay as they were"""
+    return (lo + nbytes + 3) // 4 * 4 + 8
+
+
 def _model(pieces, lo, nbytes, fill):
     """pieces: (dst_bit, nbits, source byte offset).  The whole buffer: `fill` outside [lo, lo + nbytes), inside it the
     pieces' bits, LSB first, and zero where no piece lies."""
-    size = (lo + nbytes + 3) // 4 * 4 + 8
+    size = _out_size(lo, nbytes)
     bits = np.zeros(max([size * 8] + [d + n for d, n, _ in pieces]) + 7 & ~7, np.uint8)
     for dst, n, off in pieces:
         bits[dst:dst + n] = SRC_BITS[off * 8:off * 8 + n]
@@ -36,7 +41,7 @@ def _model(pieces, lo, nbytes, fill):
 def _compose(lib, pieces, lo, nbytes, fill):
     a = np.array(pieces, np.uint64).reshape(-1, 3)
     dst, n, off = (np.ascontiguousarray(a[:, i]) for i in range(3))
-    out = np.full((lo + nbytes + 3) // 4 * 4 + 8, fill, np.uint8)
+    out = np.full(_out_size(lo, nbytes), fill, np.uint8)
     assert out.ctypes.data % 4 == 0
     assert lib.hydt_compose_pieces(dst.ctypes.data, n.ctypes.data, off.ctypes.data, len(a), SRC.ctypes.data, lo, nbytes, out.ctypes.data) == 0
     return out

@@ -9,6 +9,7 @@ import pytest
 from hydrium_amd import api, build as hbuild
 from oracle import binding as orc
 
+import content_corpus as cc
 import glue
 import lf_model
 
@@ -122,3 +123,21 @@ def test_single_group_frames_in_sequence_off_word_boundaries(lib, image):
     got, offs = _batched(lib, md, st)
     assert offs[-1] == sum(map(len, want))
     assert got == b"".join(want)
+
+
+@pytest.mark.parametrize("picture,sx,sy", cc.TILED, ids=[f"{p[0]}-{p[1]}x{p[2]}-{p[3]}b-shift{sx}{sy}" for p, sx, sy in cc.TILED])
+def test_the_content_corpus_in_tile_mode(lib, picture, sx, sy):
+    """tests/content_corpus.py: neighbouring tiles that are entirely different frames (black, noise, primaries, photo:
+    frames of 4 and of 115974 HF bytes side by side), frames of nothing but 4-byte sections at 16 bit, and the empty LF
+    stream of a black 8 x 8 tile — every frame what frame.c writes for that tile"""
+    img = cc.picture(*picture)
+    h, w, _ = img.shape
+    md = api.HYDImageMetadata(w, h, 0, sx, sy)
+    st = _stages(img, sx, sy)
+    want = _host_frames(md, st)
+    got, offs = _batched(lib, md, st)
+    assert offs == [sum(map(len, want[:k])) for k in range(len(want) + 1)]
+    for k, frame in enumerate(want):
+        assert got[offs[k]:offs[k + 1]] == frame, (k, st[k][0])
+    assert got == b"".join(want)
+    print(picture, (sx, sy), "frames of", [len(f) for f in want], "bytes")
