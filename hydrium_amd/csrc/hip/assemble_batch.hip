@@ -18,6 +18,11 @@
  *   k_batch_prepare_mixed  (one-LF-group frames EACH OF ITS OWN SIZE, csrc/host/mixed.c) the same wavefront body with
  *                        frame f's own record of a mixed plan — its own file header and frame header — and the shape
  *                        that record names, after checking on the device that the plan covers the batch
+ *   k_batch_prepare_frames  (frames of DIFFERENT LF-group counts side by side, a frames plan of mixed.c) grid = sum of
+ *                        (n_k + 1) over the frames of several LF groups, block 256: a workgroup looks its (frame, part) up in
+ *                        the plan's table and runs asm_frame with THAT frame's plan, slots and share of the scratch; the
+ *                        batch's frames of one LF group take the wavefront path beside it (k_batch_prepare_frames_one,
+ *                        grid F), on their first slot and their share
  *   k_batch_place        one workgroup: the union of the frames' error words, a prefix sum over their sizes = the
  *                        offsets table, every piece moved to its frame's start, the range k_pieces_copy reads
  *   k_pieces_copy        (assemble.hip) every output word composed from the pieces that touch it and stored once; the
@@ -25,7 +30,8 @@
  *
  * Every frame of a batch has the same pixel-independent bytes: ONE plan (csrc/host/batch.c builds it with the frame
  * planner, or the tile planner for n = 1) serves all of them; a mixed batch brings a plan of its own, one record per
- * frame and one per distinct shape, uploaded in the stream ahead of the assembly.  No host synchronisation between the entropy stage and
+ * frame and one per distinct shape (and, where frames hold several LF groups, a frame plan per distinct size of those),
+ * uploaded in the stream ahead of the assembly.  No host synchronisation between the entropy stage and
  * the finished files.
  */
 #include <hip/hip_runtime.h>
@@ -63,6 +69,9 @@ struct BatchScratch { /* device pointers; frame f's part of each array is what a
     uint64_t *offsets;    /* [frames + 1] the table the caller gets */
     uint64_t *range;      /* [4] error word, 0, bytes of all files (what k_pieces_copy reads), bytes the output must hold */
     uint32_t n, toc_n, hfg_words, toc_words, pieces_per_frame;
+    /* a frames plan (hydk_tiles.h, HydkFramesPlan): the five above are zero — every frame's record names its slots and its
+     * offsets into hfg, toc, sizes and pieces; head is [slots][HYDK_FRAMES_HEAD_STRIDE] — and these are what the arrays hold */
+    uint32_t hfg_cap, toc_cap, sizes_cap, pieces_cap;
 };
 
 __device__ __forceinline__ Scratch frame_scratch(const BatchScratch &B, uint32_t f) {
@@ -103,25 +112,37 @@ __global__ __launch_bounds__(256) void k_batch_prepare(const uint8_t *__restrict
     asm_frame(planb, blobs, frame_scratch(B, f), F, part, n + 1, ~0ull, nullptr);
 }
 
-/* one wavefront, frame f of a view of one-LF-group frames: the tile assembler's preparation and pieces with the frame
+/* where a frame of one LF group sits: its slot of the view and its share of the scratch arrays */
+struct OneFrame {
+    uint32_t slot;
+    uint32_t *head, *mid, *toc; /* HYDK_TILE_HEAD_WORDS, HYDK_TILE_MID_WORDS, HYDK_TILE_TOC_WORDS words */
+    HydkPiece *pieces;          /* HYDK_TILE_PIECES */
+};
+
+/* in a view whose every frame holds one LF group, frame f has slot f and the f-th part of every array */
+static __device__ __forceinline__ OneFrame one_frame_uniform(const BatchScratch &B, uint32_t f) {
+    return {f, B.head + (size_t)f * HYDK_TILE_HEAD_WORDS, B.hfg + (size_t)f * HYDK_TILE_MID_WORDS, B.toc + (size_t)f * HYDK_TILE_TOC_WORDS,
+            B.pieces + (size_t)f * HYDK_TILE_PIECES};
+}
+
+/* one wavefront, frame f of a view, a frame of ONE LF group: the tile assembler's preparation and pieces with the frame
  * record `fr` and the shape `sh` of the plan `planb` (the view has been checked) */
 static __device__ __forceinline__ void prepare_one(const uint8_t *__restrict__ planb, const HydkTileFrame &fr, const HydkTileShape *sh,
                                                    const uint8_t *__restrict__ blob, const HydkTileExtent *__restrict__ ext, uint32_t f,
-                                                   const BatchScratch &B) {
+                                                   const OneFrame &at, const BatchScratch &B) {
     uint64_t *result = B.result + (size_t)f * 4;
     const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + f;
-    uint32_t *head = B.head + (size_t)f * HYDK_TILE_HEAD_WORDS, *mid = B.hfg + (size_t)f * HYDK_TILE_MID_WORDS,
-             *toc = B.toc + (size_t)f * HYDK_TILE_TOC_WORDS;
+    const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + at.slot;
+    uint32_t *head = at.head, *mid = at.mid, *toc = at.toc;
     const HydkTileSizes z = hydk_tile_prepare_wave(planb, &fr, sh, rec, h->lf_bytes, head, mid, toc);
     if (threadIdx.x == 0) {
-        const HydkTileExtent x = ext[f];
+        const HydkTileExtent x = ext[at.slot];
         uint32_t e = z.err;
         if (!e && (x.hf_bytes != z.hf_bytes || x.hf_off + z.hf_bytes > h->hf_bytes))
             e = HYDK_ASM_E_SIZE;
         if (!e)
             hydk_tile_pieces(planb, &fr, sh, &z, rec, head, mid, toc, blob_lf_bytes(blob) + x.lf_off, blob_hf_bytes(blob) + x.hf_off, 0,
-                             B.pieces + (size_t)f * HYDK_TILE_PIECES);
+                             at.pieces);
         result[0] = e;
         result[1] = 0;
         result[2] = e ? 0 : z.frame_bytes;
@@ -146,7 +167,7 @@ __global__ __launch_bounds__(64) void k_batch_prepare_one(const uint8_t *__restr
         return prepare_failed(B, f, bad);
     const HydkTilePlan *plan = (const HydkTilePlan *)planb;
     const HydkTileFrame fr = ((const HydkTileFrame *)(planb + plan->frames_off))[0];
-    prepare_one(planb, fr, &plan->shapes[fr.shape], blob, ext, f, B);
+    prepare_one(planb, fr, &plan->shapes[fr.shape], blob, ext, f, one_frame_uniform(B, f), B);
 }
 
 /* ---- k_batch_prepare_mixed: grid = frames, block = 64; frame f is frame f of a MIXED plan (hydk_tiles.h), with its own
@@ -165,18 +186,138 @@ __global__ __launch_bounds__(64) void k_batch_prepare_mixed(const uint8_t *__res
     const HydkTileFrame fr = ((const HydkTileFrame *)(planb + plan->frames_off))[f];
     if (fr.shape >= plan->nshapes)
         return prepare_failed(B, f, HYDK_ASM_E_SLOT);
-    prepare_one(planb, fr, (const HydkTileShape *)(planb + plan->shapes_off) + fr.shape, blob, ext, f, B);
+    prepare_one(planb, fr, (const HydkTileShape *)(planb + plan->shapes_off) + fr.shape, blob, ext, f, one_frame_uniform(B, f), B);
+}
+
+/* ---- frames of different LF-group counts side by side (a FRAMES plan, hydk_tiles.h).  The plan arrives per batch, so both
+ * kernels check on the device what their indices rest on, before they follow any of them: the view, and that the plan is
+ * of this kind and covers the batch — its frames, its slots, its tables inside its bytes (BLOB; nothing behind the plan's
+ * header is read before); then the frame's record — its slots inside the view, its own plan inside the plan's bytes, of one
+ * blob and as many LF groups (SLOT), its share of the scratch inside the arrays (SCRATCH) ---- */
+static __device__ __forceinline__ uint32_t frames_plan_check(const uint8_t *__restrict__ planb, const uint8_t *__restrict__ blob, uint32_t frames,
+                                                             uint32_t slots) {
+    const HydkFramesPlan *plan = (const HydkFramesPlan *)planb;
+    const uint32_t bad = blob_view_check(blob, slots);
+    if (bad)
+        return bad;
+    if (plan->magic != HYDK_FRAMES_MAGIC || plan->num_frames != frames || plan->num_slots != slots ||
+        (uint64_t)plan->frames_off + (uint64_t)frames * sizeof(HydkBatchFrame) > plan->total_bytes ||
+        (uint64_t)plan->shapes_off + (uint64_t)plan->nshapes * sizeof(HydkTileShape) > plan->total_bytes ||
+        (uint64_t)plan->parts_off + (uint64_t)plan->nparts * sizeof(uint32_t) > plan->total_bytes)
+        return HYDK_ASM_E_BLOB;
+    return 0;
+}
+
+static __device__ __forceinline__ uint32_t frames_record_check(const uint8_t *__restrict__ planb, const HydkBatchFrame &fr, const BatchScratch &B) {
+    const HydkFramesPlan *plan = (const HydkFramesPlan *)planb;
+    const uint64_t n = fr.lf_groups;
+    if (n < 1 || (uint64_t)fr.first_slot + n > plan->num_slots)
+        return HYDK_ASM_E_SLOT;
+    uint64_t sizes = 0;
+    if (fr.plan_off) {
+        if ((fr.plan_off & 15u) || (uint64_t)fr.plan_off + sizeof(HydkAsmPlan) > plan->total_bytes)
+            return HYDK_ASM_E_SLOT;
+        const HydkAsmPlan *ap = (const HydkAsmPlan *)(planb + fr.plan_off);
+        if (ap->magic != HYDK_ASM_PLAN_MAGIC || (uint64_t)fr.plan_off + ap->total_bytes > plan->total_bytes || ap->num_blobs != 1 ||
+            ap->num_slots != n || ap->blob_slots[0] != n || ap->num_presets * ap->clusters_per_preset > 256 || ap->ntails > HYDK_ASM_MAX_TAILS)
+            return HYDK_ASM_E_SLOT;
+        sizes = ap->toc_n;
+    } else if (n != 1 || fr.one.shape >= plan->nshapes || fr.hfg_words < HYDK_TILE_MID_WORDS || fr.toc_words < HYDK_TILE_TOC_WORDS) {
+        return HYDK_ASM_E_SLOT;
+    }
+    if ((uint64_t)fr.hfg_off + fr.hfg_words > B.hfg_cap || (uint64_t)fr.toc_off + fr.toc_words > B.toc_cap ||
+        (uint64_t)fr.sizes_off + sizes > B.sizes_cap || (uint64_t)fr.piece_base + 3u * n + 5u > B.pieces_cap)
+        return HYDK_ASM_E_SCRATCH;
+    return 0;
+}
+
+/* ---- k_batch_prepare_frames: grid = the plan's parts (n_k + 1 per frame of several LF groups), block = 256 ---- */
+__global__ __launch_bounds__(256) void k_batch_prepare_frames(const uint8_t *__restrict__ planb, const uint8_t *__restrict__ blob, uint64_t blob_cap,
+                                                              const HydkTileExtent *__restrict__ ext, uint32_t frames, uint32_t slots,
+                                                              BatchScratch B) {
+    __builtin_amdgcn_s_setprio(3);
+    const HydkFramesPlan *plan = (const HydkFramesPlan *)planb;
+    const uint32_t bad = frames_plan_check(planb, blob, frames, slots);
+    if (bad) { /* no table to look a frame up in: the word goes to every frame (the other launch may have none) */
+        if (blockIdx.x == 0)
+            for (uint32_t f = threadIdx.x; f < frames; f += 256) {
+                uint64_t *result = B.result + (size_t)f * 4;
+                result[0] = bad;
+                result[1] = result[2] = result[3] = 0;
+            }
+        return;
+    }
+    if (blockIdx.x >= plan->nparts)
+        return;
+    const uint32_t fp = ((const uint32_t *)(planb + plan->parts_off))[blockIdx.x], f = fp >> 8, part = fp & 255u;
+    if (f >= frames)
+        return;
+    const HydkBatchFrame fr = ((const HydkBatchFrame *)(planb + plan->frames_off))[f];
+    const uint32_t e = fr.plan_off ? frames_record_check(planb, fr, B) : HYDK_ASM_E_SLOT;
+    if (e) { /* every part of the frame sees the same record: none of them counts itself done */
+        if (part == 0)
+            prepare_failed(B, f, e);
+        return;
+    }
+    if (part > fr.lf_groups)
+        return;
+    BlobArgs blobs;
+    blobs.p[0] = blob;
+    blobs.cap[0] = blob_cap;
+    Scratch S;
+    S.head = B.head + (size_t)fr.first_slot * HYDK_FRAMES_HEAD_STRIDE; /* the frame's slots follow at kHeadWords inside it */
+    S.head_bits = B.head_bits + fr.first_slot;
+    S.sizes = B.sizes + fr.sizes_off;
+    S.slot_hf = B.slot_hf + fr.first_slot;
+    S.hfg = B.hfg + fr.hfg_off;
+    S.toc = B.toc + fr.toc_off;
+    S.pieces = B.pieces + fr.piece_base;
+    S.npieces = B.npieces + f;
+    S.err = B.err + f;
+    S.done = B.done + f;
+    S.result = B.result + (size_t)f * 4;
+    S.hfg_words = fr.hfg_words;
+    S.toc_words = fr.toc_words;
+    /* the frame's HF sections: its slots' extents, as k_batch_prepare's */
+    const HydkTileExtent first = ext[fr.first_slot], last = ext[fr.first_slot + fr.lf_groups - 1];
+    AsmFrame F;
+    F.slot_base = fr.first_slot;
+    F.view_slots = slots;
+    F.hf = blob_hf_bytes(blob) + first.hf_off;
+    F.hf_bytes = last.hf_off + last.hf_bytes - first.hf_off;
+    asm_frame(planb + fr.plan_off, blobs, S, F, part, fr.lf_groups + 1, ~0ull, nullptr);
+}
+
+/* ---- k_batch_prepare_frames_one: grid = frames, block = 64; the frames of ONE LF group of the same plan (the others':
+ * nothing to do here), as k_batch_prepare_mixed's but for the frame's slot and its share of the arrays ---- */
+__global__ __launch_bounds__(64) void k_batch_prepare_frames_one(const uint8_t *__restrict__ planb, const uint8_t *__restrict__ blob,
+                                                                 const HydkTileExtent *__restrict__ ext, uint32_t frames, uint32_t slots,
+                                                                 BatchScratch B) {
+    const uint32_t f = blockIdx.x;
+    const HydkFramesPlan *plan = (const HydkFramesPlan *)planb;
+    const uint32_t bad = frames_plan_check(planb, blob, frames, slots);
+    if (bad)
+        return prepare_failed(B, f, bad);
+    const HydkBatchFrame fr = ((const HydkBatchFrame *)(planb + plan->frames_off))[f];
+    if (fr.plan_off)
+        return;
+    const uint32_t e = frames_record_check(planb, fr, B);
+    if (e)
+        return prepare_failed(B, f, e);
+    const OneFrame at = {fr.first_slot, B.head + (size_t)fr.first_slot * HYDK_FRAMES_HEAD_STRIDE, B.hfg + fr.hfg_off, B.toc + fr.toc_off,
+                         B.pieces + fr.piece_base};
+    prepare_one(planb, fr.one, (const HydkTileShape *)(planb + plan->shapes_off) + fr.one.shape, blob, ext, f, at, B);
 }
 
 /* ---- k_batch_place: grid 1, block 256 ---- */
 __global__ __launch_bounds__(256) void k_batch_place(const uint8_t *__restrict__ blob, const HydkTileExtent *__restrict__ ext, uint32_t frames,
+                                                     uint32_t slots /* of the view */, const uint8_t *__restrict__ frames_plan /* or null */,
                                                      BatchScratch B, uint64_t out_cap, uint64_t *h_result /* pinned [4 + frames + 1] */) {
     __shared__ uint64_t s_wave[4];
     __shared__ uint64_t s_at[256];
     __shared__ uint32_t s_err;
     const uint32_t t = threadIdx.x;
     const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    const uint32_t slots = frames * B.n;
     uint32_t e = 0;
     uint64_t size = 0;
     if (t < frames) {
@@ -205,7 +346,16 @@ __global__ __launch_bounds__(256) void k_batch_place(const uint8_t *__restrict__
         h_result[4 + t] = at;
     }
     __syncthreads();
-    if (!fin) {
+    if (!fin && frames_plan) {
+        /* frames of different LF-group counts: frame f's 3 n + 5 pieces start where its record says — the sum over the
+         * frames before it, so that the list stays contiguous and in output order (no error: the plan has been checked) */
+        if (t < frames) {
+            const HydkFramesPlan *plan = (const HydkFramesPlan *)frames_plan;
+            const HydkBatchFrame fr = ((const HydkBatchFrame *)(frames_plan + plan->frames_off))[t];
+            for (uint32_t i = 0; i < 3u * fr.lf_groups + 5u; i++)
+                B.pieces[fr.piece_base + i].dst_bit += at * 8u;
+        }
+    } else if (!fin) {
         const uint32_t np = frames * B.pieces_per_frame;
         for (uint32_t i = t; i < np; i += 256)
             B.pieces[i].dst_bit += s_at[i / B.pieces_per_frame] * 8u;
@@ -235,6 +385,9 @@ struct HydkBatchAsm {
     size_t plan_cap = 0;          /* mixed: bytes of that region and of the pinned buffer the plan travels through */
     uint8_t *h_plan = nullptr;
     uint32_t plan_frames = 0;     /* mixed: frames of the plan on the device */
+    bool several = false;         /* mixed, frames of 1..28 LF groups: the plan is a frames plan, and these are its: */
+    int max_slots = 0;
+    uint32_t plan_slots = 0, plan_parts = 0, plan_pieces = 0;
     BatchScratch B = {};
     uint64_t fixed = 0;           /* bytes of a frame beyond its packed LF streams and HF sections, at most; stays 0 for a
                                    * mixed assembler, whose frames differ: mixed.c sums the same terms per batch, from its plan */
@@ -373,14 +526,124 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
     return ST_OK;
 }
 
+/* scratch for batches of up to `max_frames` images of 1..28 LF groups each, `max_slots` LF groups in all, each image of
+ * its own size: the arrays hold what hydk_tiles.h's HYDK_FRAMES_*_CAP say, whatever the sizes; the (frames) plan comes
+ * with every batch (hydk_batch_set_plan) */
+int hydk_batch_create_frames(int device, int max_frames, int max_slots, HydkBatchAsm **out) {
+    if (!out)
+        return ST_API_ERROR;
+    *out = nullptr;
+    if (max_frames < 1 || max_frames > HYDK_TILE_MAX_FRAMES || max_slots < max_frames || max_slots > kMaxSlots)
+        return ST_API_ERROR;
+    HydkBatchAsm *a = new (std::nothrow) HydkBatchAsm();
+    if (!a)
+        return ST_NOMEM;
+    a->device = device;
+    a->max_frames = max_frames;
+    a->max_slots = max_slots;
+    a->mixed = a->several = true;
+    BatchScratch &B = a->B;
+    const size_t F = (size_t)max_frames, N = (size_t)max_slots;
+    B.hfg_cap = (uint32_t)HYDK_FRAMES_HFG_CAP(F, N);
+    B.toc_cap = (uint32_t)HYDK_FRAMES_TOC_CAP(F, N);
+    B.sizes_cap = (uint32_t)HYDK_FRAMES_SIZES_CAP(F, N);
+    B.pieces_cap = (uint32_t)HYDK_FRAMES_PIECES_CAP(F, N);
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t off = at;
+        at += (bytes + 15) & ~(size_t)15;
+        return off;
+    };
+    const size_t o_head = take(N * HYDK_FRAMES_HEAD_STRIDE * 4), o_hfg = take((size_t)B.hfg_cap * 4), o_toc = take((size_t)B.toc_cap * 4),
+                 o_pieces = take((size_t)B.pieces_cap * sizeof(HydkPiece)), o_result = take(F * 4 * 8), o_offsets = take((F + 1) * 8),
+                 o_range = take(4 * 8), o_head_bits = take(N * 4), o_sizes = take((size_t)B.sizes_cap * 8), o_slot_hf = take(N * 8),
+                 o_npieces = take(F * 4), o_counters = take(2 * F * 4);
+    auto alloc = [&]() -> int {
+        HYDK_TRY(a, hipSetDevice(device));
+        HYDK_TRY(a, hipMalloc(&a->arena, at));
+        uint8_t *m = a->arena;
+        B.head = (uint32_t *)(m + o_head);
+        B.hfg = (uint32_t *)(m + o_hfg);
+        B.toc = (uint32_t *)(m + o_toc);
+        B.pieces = (HydkPiece *)(m + o_pieces);
+        B.result = (uint64_t *)(m + o_result);
+        B.offsets = (uint64_t *)(m + o_offsets);
+        B.range = (uint64_t *)(m + o_range);
+        B.head_bits = (uint32_t *)(m + o_head_bits);
+        B.sizes = (uint64_t *)(m + o_sizes);
+        B.slot_hf = (uint64_t *)(m + o_slot_hf);
+        B.npieces = (uint32_t *)(m + o_npieces);
+        B.err = (uint32_t *)(m + o_counters); /* err and done: zero between batches */
+        B.done = B.err + F;
+        HYDK_TRY(a, hipMemset(B.err, 0, 2 * F * sizeof(uint32_t)));
+        HYDK_TRY(a, hipStreamSynchronize(nullptr));
+        HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, (4 + F + 1) * sizeof(uint64_t), hipHostMallocDefault));
+        memset(a->h_result, 0, (4 + F + 1) * sizeof(uint64_t));
+        return ST_OK;
+    };
+    const int st = alloc();
+    if (st != ST_OK) {
+        hydk_batch_destroy(a);
+        return st;
+    }
+    *out = a;
+    return ST_OK;
+}
+
 /* bytes a frame can add to its packed LF streams and HF sections: what the plan fixes and the scratch can hold */
 uint64_t hydk_batch_fixed_bytes(HydkBatchAsm *a) { return a ? a->fixed : 0; }
 
 /* a mixed assembler's plan for the batches that follow: `bytes` of a HydkMixedPlan, through the pinned buffer and one
  * asynchronous copy on `stream`, ahead of the assembly that reads it.  The caller has waited for the previous batch
  * (one batch in flight per object), so neither buffer is being read; both grow on demand, and wait for `stream` when they do */
+/* a frames plan as the kernels will follow it: every table inside its bytes, every frame's slots, share of the scratch
+ * and plan where the object can hold them, the workgroup table the frames of several LF groups part by part, in order */
+static bool frames_plan_ok(const HydkBatchAsm *a, const uint8_t *plan, size_t bytes) {
+    const HydkFramesPlan *fp = (const HydkFramesPlan *)plan;
+    if (bytes < sizeof(HydkFramesPlan) || fp->magic != HYDK_FRAMES_MAGIC || fp->total_bytes != bytes || fp->num_frames < 1 ||
+        fp->num_frames > (uint32_t)a->max_frames || fp->num_slots > (uint32_t)a->max_slots || fp->nshapes > fp->num_frames ||
+        ((fp->shapes_off | fp->frames_off | fp->parts_off) & 3u) ||
+        (uint64_t)fp->shapes_off + (uint64_t)fp->nshapes * sizeof(HydkTileShape) > bytes ||
+        (uint64_t)fp->frames_off + (uint64_t)fp->num_frames * sizeof(HydkBatchFrame) > bytes ||
+        (uint64_t)fp->parts_off + (uint64_t)fp->nparts * sizeof(uint32_t) > bytes)
+        return false;
+    const HydkBatchFrame *fr = (const HydkBatchFrame *)(plan + fp->frames_off);
+    const uint32_t *parts = (const uint32_t *)(plan + fp->parts_off);
+    const BatchScratch &B = a->B;
+    uint32_t slot = 0, piece = 0, part = 0;
+    for (uint32_t f = 0; f < fp->num_frames; f++) {
+        const uint32_t n = fr[f].lf_groups;
+        uint64_t sizes = 0;
+        if (n < 1 || n > HYDK_FRAMES_MAX_LF_GROUPS || fr[f].first_slot != slot || fr[f].piece_base != piece)
+            return false;
+        if (fr[f].plan_off) {
+            const HydkAsmPlan *ap = (const HydkAsmPlan *)(plan + fr[f].plan_off);
+            if ((fr[f].plan_off & 15u) || (uint64_t)fr[f].plan_off + sizeof(HydkAsmPlan) > bytes || ap->magic != HYDK_ASM_PLAN_MAGIC ||
+                (uint64_t)fr[f].plan_off + ap->total_bytes > bytes || ap->num_blobs != 1 || ap->num_slots != n || ap->blob_slots[0] != n ||
+                ap->toc_n != 2 + n + ap->frame_groups || ap->ntails > HYDK_ASM_MAX_TAILS)
+                return false;
+            sizes = ap->toc_n;
+            for (uint32_t i = 0; i <= n; i++, part++)
+                if (part >= fp->nparts || parts[part] != (f << 8 | i))
+                    return false;
+        } else if (n != 1 || fr[f].one.shape >= fp->nshapes || fr[f].hfg_words < HYDK_TILE_MID_WORDS || fr[f].toc_words < HYDK_TILE_TOC_WORDS) {
+            return false;
+        }
+        if ((uint64_t)fr[f].hfg_off + fr[f].hfg_words > B.hfg_cap || (uint64_t)fr[f].toc_off + fr[f].toc_words > B.toc_cap ||
+            (uint64_t)fr[f].sizes_off + sizes > B.sizes_cap)
+            return false;
+        slot += n;
+        piece += 3 * n + 5;
+    }
+    return slot == fp->num_slots && piece == fp->npieces && part == fp->nparts && piece <= B.pieces_cap && piece <= HYDK_COPY_MAX_PIECES;
+}
+
 int hydk_batch_set_plan(HydkBatchAsm *a, const void *plan, size_t bytes, void *stream) {
     const HydkMixedPlan *mp = (const HydkMixedPlan *)plan;
+    if (a && a->several) {
+        if (!plan || !frames_plan_ok(a, (const uint8_t *)plan, bytes))
+            return hydk_fail(a, ST_API_ERROR, "bad frames plan");
+    } else
     if (!a || !a->mixed || !plan || bytes < sizeof(HydkMixedPlan) || mp->magic != HYDK_MIXED_MAGIC || mp->total_bytes != bytes ||
         mp->num_frames < 1 || mp->num_frames > (uint32_t)a->max_frames || mp->nshapes < 1 || mp->nshapes > mp->num_frames ||
         (uint64_t)mp->shapes_off + (uint64_t)mp->nshapes * sizeof(HydkTileShape) > bytes ||
@@ -404,7 +667,13 @@ int hydk_batch_set_plan(HydkBatchAsm *a, const void *plan, size_t bytes, void *s
     }
     memcpy(a->h_plan, plan, bytes);
     HYDK_TRY(a, hipMemcpyAsync(a->plan, a->h_plan, bytes, hipMemcpyHostToDevice, st));
-    a->plan_frames = mp->num_frames;
+    a->plan_frames = mp->num_frames; /* (both plan headers begin alike) */
+    if (a->several) {
+        const HydkFramesPlan *fp = (const HydkFramesPlan *)plan;
+        a->plan_slots = fp->num_slots;
+        a->plan_parts = fp->nparts;
+        a->plan_pieces = fp->npieces;
+    }
     return ST_OK;
 }
 
@@ -420,7 +689,20 @@ int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t 
     const HydkTileExtent *ext = (const HydkTileExtent *)extents;
     if (a->mixed && frames > a->plan_frames)
         return hydk_fail(a, ST_API_ERROR, "the batch has more frames than its plan");
-    if (a->mixed)
+    uint32_t slots = frames * a->B.n, npieces = frames * a->B.pieces_per_frame;
+    if (a->several) {
+        if (frames != a->plan_frames)
+            return hydk_fail(a, ST_API_ERROR, "the batch is not its plan's");
+        slots = a->plan_slots;
+        npieces = a->plan_pieces;
+        if (a->plan_parts)
+            hipLaunchKernelGGL(k_batch_prepare_frames, dim3(a->plan_parts), dim3(256), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob,
+                               blob_cap, ext, frames, slots, a->B);
+        HYDK_TRY(a, hipGetLastError());
+        if (a->plan_parts < slots + frames) /* (the parts are n + 1 per frame of several LF groups: some frame has one) */
+            hipLaunchKernelGGL(k_batch_prepare_frames_one, dim3(frames), dim3(64), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob, ext,
+                               frames, slots, a->B);
+    } else if (a->mixed)
         hipLaunchKernelGGL(k_batch_prepare_mixed, dim3(frames), dim3(64), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob, ext, frames, a->B);
     else if (a->one)
         hipLaunchKernelGGL(k_batch_prepare_one, dim3(frames), dim3(64), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob, ext, frames, a->B);
@@ -428,9 +710,10 @@ int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t 
         hipLaunchKernelGGL(k_batch_prepare, dim3(frames * (a->B.n + 1)), dim3(256), 0, st, (const uint8_t *)a->plan, (const uint8_t *)blob,
                            blob_cap, ext, frames, a->B);
     HYDK_TRY(a, hipGetLastError());
-    hipLaunchKernelGGL(k_batch_place, dim3(1), dim3(256), 0, st, (const uint8_t *)blob, ext, frames, a->B, a->out_cap, a->h_result);
+    hipLaunchKernelGGL(k_batch_place, dim3(1), dim3(256), 0, st, (const uint8_t *)blob, ext, frames, slots,
+                       a->several ? (const uint8_t *)a->plan : (const uint8_t *)nullptr, a->B, a->out_cap, a->h_result);
     HYDK_TRY(a, hipGetLastError());
-    HYDK_TRY(a, hydk::launch_pieces_copy(a->B.pieces, frames * a->B.pieces_per_frame, nullptr, a->B.range, a->out, st));
+    HYDK_TRY(a, hydk::launch_pieces_copy(a->B.pieces, npieces, nullptr, a->B.range, a->out, st));
     return ST_OK;
 }
 

@@ -43,19 +43,19 @@ hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt
                             uint2 *part_info, int plog, hipStream_t stream);
 hipError_t launch_tables(const uint32_t *hist, HydkTables *tabs, const uint32_t *alpha_max, int nclusters, int first_slot,
                          int num_slots, uint32_t alpha_floor, const uint32_t *alpha_floor_dev, const uint32_t *lf_hist,
-                         HydkLfStream *lf_streams, void *lf_work, int slots_per_frame, hipStream_t stream);
+                         HydkLfStream *lf_streams, void *lf_work, const HydkLfJob *jobs_all, hipStream_t stream);
 hipError_t launch_export(const HydkLfJob *d_jobs, const HydkTables *tabs, const uint32_t *group_bits, const HydkLfStream *lf_streams,
                          const uint8_t *payload, const uint64_t *hf_total, const uint8_t *lf_packed,
                          const unsigned long long *lf_total, const uint32_t *status, int num_slots, int lf_coded, uint8_t *dst,
                          uint64_t capacity, int view, hipStream_t stream);
 hipError_t launch_rans(const HydkLfJob *d_jobs, const uint32_t *sym_count, const HydkTables *tabs, uint32_t *bitbuf,
-                       uint32_t bit_pitch_words, uint32_t *group_bits, int preset_bits, int num_slots, const uint32_t *status,
+                       uint32_t bit_pitch_words, uint32_t *group_bits, int num_slots, const uint32_t *status,
                        hipStream_t stream);
 hipError_t launch_rans_deferred(const HydkLfJob *d_jobs, const uint32_t *sym_count, const HydkTables *tabs, uint16_t *aux,
                                 uint16_t *flags, uint32_t aux_pitch, uint32_t *final_state, uint32_t *group_bits,
-                                int preset_bits, int num_slots, const uint32_t *status, hipStream_t stream);
+                                int num_slots, const uint32_t *status, hipStream_t stream);
 hipError_t launch_rans_lanes(const HydkLfJob *d_jobs, const uint32_t *sym_count, const HydkTables *tabs, uint16_t *aux,
-                             uint16_t *flags, uint32_t aux_pitch, uint32_t *final_state, uint32_t *group_bits, int preset_bits,
+                             uint16_t *flags, uint32_t aux_pitch, uint32_t *final_state, uint32_t *group_bits,
                              int nclusters, int num_slots, const uint32_t *status, const uint32_t *lf_hist,
                              HydkLfStream *lf_streams, void *lf_work, hipStream_t stream);
 hipError_t launch_lf_front(const HydkLfJob *d_jobs, unsigned long long *recs, uint32_t *hist, void *work, int num_slots,
@@ -64,7 +64,7 @@ hipError_t launch_lf_back(const HydkLfJob *d_jobs, const unsigned long long *rec
                           void *work, int num_slots, hipStream_t stream);
 hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, const uint16_t *aux, const uint16_t *flags,
                             uint32_t aux_pitch, const uint32_t *final_state, const uint32_t *group_bits, const uint64_t *offsets,
-                            uint8_t *payload, int preset_bits, int num_slots, const uint32_t *status, hipStream_t stream);
+                            uint8_t *payload, int num_slots, const uint32_t *status, hipStream_t stream);
 hipError_t launch_frame_begin(const HydkLfJob *host_jobs, HydkLfJob *d_jobs, int count, uint32_t *accum, size_t accum_words,
                               hipStream_t stream);
 hipError_t launch_publish(const uint64_t *total, uint64_t *h_total, const unsigned long long *lf_total,
@@ -148,7 +148,6 @@ struct HydAmdContext {
     unsigned num_presets = 1;
     int scheme = 0;
     int nclusters = 9;
-    int preset_bits = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     char error[256] = "";
@@ -222,7 +221,10 @@ struct HydAmdContext {
     uint64_t h_total = 0;
     uint32_t h_status = 0;
     int slots_finished = 0;
-    int slots_per_frame = 0; /* > 0: the slots hold a batch of independent frames of this many LF groups each (hydamd_begin_batch) */
+    int slots_per_frame = 0; /* > 0: the slots hold a batch of independent frames of this many LF groups each (hydamd_begin_batch);
+                              * < 0: of frames of different LF-group counts (hydamd_begin_batch_frames), slot by slot: */
+    uint8_t slot_frame_first[HYDAMD_MAX_LF_GROUPS] = {};  /* the first slot of the slot's frame */
+    uint8_t slot_frame_groups[HYDAMD_MAX_LF_GROUPS] = {}; /* the LF groups of the slot's frame (0: the slot belongs to none) */
     bool results_valid = false;
     uint32_t *accum = nullptr;       /* [hist | alpha_max | status | lf_hist]: cleared once per frame by k_frame_begin */
     size_t accum_words = 0;
@@ -375,7 +377,15 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
         return fail(ctx, ST_API_ERROR, "LF group must be between 1 and 2048 pixels in each direction");
     if (fmt != HYDK_FMT_U8 && fmt != HYDK_FMT_U16 && fmt != HYDK_FMT_F32)
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
-    if (preset >= ctx->num_presets)
+    /* the slot's frame: the whole launch group, or one frame of a batch — presets and the alphabet maximum restart with it */
+    unsigned frame_first = 0, frame_groups = ctx->num_presets;
+    if (ctx->slots_per_frame > 0) {
+        frame_first = (unsigned)slot - (unsigned)slot % (unsigned)ctx->slots_per_frame;
+    } else if (ctx->slots_per_frame < 0) {
+        frame_first = ctx->slot_frame_first[slot];
+        frame_groups = ctx->slot_frame_groups[slot];
+    }
+    if (preset >= frame_groups)
         return fail(ctx, ST_API_ERROR, "preset out of range for this frame");
     if (fmt == HYDK_FMT_F32 && ctx->rec_bytes != 8) { /* float tokens need the 8-byte record: once per context */
         const int st = widen_token_records(ctx);
@@ -398,6 +408,9 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.scheme = ctx->scheme;
     job.use_luts = fmt == HYDK_FMT_F32 ? 0 : ctx->use_luts;
     job.preset = preset;
+    while ((1u << job.preset_bits) < frame_groups) /* hyd_cllog2, encoder.c:940 */
+        job.preset_bits++;
+    job.frame_first = (unsigned short)frame_first;
     job.in_lut8 = ctx->in_lut8;
     job.in_lut16 = ctx->in_lut16;
     job.bias_lut = ctx->bias_lut;
@@ -1140,10 +1153,6 @@ int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets) {
         ctx->scheme = 3;
         ctx->nclusters = 1;
     }
-    int bits = 0;
-    while ((1u << bits) < num_presets)
-        bits++;
-    ctx->preset_bits = bits; /* hyd_cllog2(num_presets), encoder.c:940 */
     {
         /* Another context of this process met content that outgrew the default arrays (noise: 2.9 symbols and 1.8 section
          * bytes per pixel) and had to run its frame twice.  A queue of frames is of one kind as a rule: a context whose
@@ -1286,6 +1295,37 @@ int hydamd_begin_batch(HydAmdContext *ctx, unsigned num_presets, int frames) {
     if (st == ST_OK && frames > 1)
         ctx->slots_per_frame = (int)num_presets;
     return st;
+}
+
+/* A batch of independent frames of DIFFERENT LF-group counts as one launch group: frame k occupies lf_groups[k] slots behind
+ * frame k - 1's.  Every frame of at most 28 LF groups clusters nine ways (hydamd_begin_frame), so the scheme, the table
+ * kernel's cluster count and the chain kernel's instantiation stay launch-wide; what differs per frame — the width of the
+ * preset field and where the running alphabet maximum starts afresh — travels in each slot's job descriptor. */
+int hydamd_begin_batch_frames(HydAmdContext *ctx, int frames, const unsigned *lf_groups) {
+    if (!ctx)
+        return ST_API_ERROR;
+    if (frames < 1 || !lf_groups)
+        return fail(ctx, ST_API_ERROR, "a batch needs at least one frame and their LF-group counts");
+    size_t total = 0;
+    for (int k = 0; k < frames; k++) {
+        if (lf_groups[k] < 1 || lf_groups[k] > HYDAMD_BATCH_FRAME_LF_GROUPS)
+            return fail(ctx, ST_API_ERROR, "a frame of such a batch holds between 1 and 28 LF groups (the nine-cluster scheme)");
+        total += lf_groups[k];
+        if (total > (size_t)ctx->max_slots)
+            return fail(ctx, ST_API_ERROR, "the context has too few LF-group slots for this batch");
+    }
+    const int st = hydamd_begin_frame(ctx, 1); /* the nine-cluster scheme */
+    if (st != ST_OK)
+        return st;
+    memset(ctx->slot_frame_groups, 0, sizeof(ctx->slot_frame_groups));
+    unsigned first = 0;
+    for (int k = 0; k < frames; first += lf_groups[k++])
+        for (unsigned i = 0; i < lf_groups[k]; i++) {
+            ctx->slot_frame_first[first + i] = (uint8_t)first;
+            ctx->slot_frame_groups[first + i] = (uint8_t)lf_groups[k];
+        }
+    ctx->slots_per_frame = -1;
+    return ST_OK;
 }
 
 int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const *src /* [frames][3] */, ptrdiff_t row_stride,
@@ -2206,7 +2246,7 @@ static int entropy_range(HydAmdContext *ctx, int first, int count, bool with_lf_
         HIP_TRY(ctx, hydk::launch_tables(ctx->hist, ctx->tables, ctx->alpha_max, ctx->nclusters, first, count,
                                          ctx->alpha_floor, ctx->alpha_floor_dev,
                                          here ? ctx->lf_hist + (size_t)first * HYDK_LF_CODES : nullptr, ctx->lf_streams + first,
-                                         ctx->lf_work + (size_t)first * hydk::lf_work_bytes(), ctx->slots_per_frame, ctx->stream));
+                                         ctx->lf_work + (size_t)first * hydk::lf_work_bytes(), ctx->d_jobs, ctx->stream));
         if (here)
             with_lf_codes = false;
         }
@@ -2228,7 +2268,7 @@ static int entropy_range(HydAmdContext *ctx, int first, int count, bool with_lf_
         } else if (lanes) {
             HIP_TRY(ctx, hydk::launch_rans_lanes(jobs, ctx->sym_count + g0, ctx->tables + first,
                                                  ctx->rans_aux + g0 * ctx->tok_cap, ctx->rans_flags + g0 * (ctx->tok_cap / 16),
-                                                 ctx->tok_cap, ctx->rans_final + g0, ctx->group_bits + g0, ctx->preset_bits,
+                                                 ctx->tok_cap, ctx->rans_final + g0, ctx->group_bits + g0,
                                                  ctx->nclusters, count, ctx->status,
                                                  with_lf_codes ? ctx->lf_hist + (size_t)first * HYDK_LF_CODES : nullptr,
                                                  ctx->lf_streams + first, ctx->lf_work + (size_t)first * hydk::lf_work_bytes(),
@@ -2238,7 +2278,7 @@ static int entropy_range(HydAmdContext *ctx, int first, int count, bool with_lf_
              * every 64 symbols to scan, pack and store their bits itself) */
             HIP_TRY(ctx, hydk::launch_rans_deferred(jobs, ctx->sym_count + g0, ctx->tables + first, ctx->rans_aux + g0 * ctx->tok_cap,
                                                     ctx->rans_flags + g0 * (ctx->tok_cap / 16), ctx->tok_cap, ctx->rans_final + g0,
-                                                    ctx->group_bits + g0, ctx->preset_bits, count, ctx->status, ctx->stream));
+                                                    ctx->group_bits + g0, count, ctx->status, ctx->stream));
             emits = true;
         } else {
             const int st = ensure_bitbuf(ctx);
@@ -2246,7 +2286,7 @@ static int entropy_range(HydAmdContext *ctx, int first, int count, bool with_lf_
                 return st;
             HIP_TRY(ctx, hydk::launch_rans(jobs, ctx->sym_count + g0, ctx->tables + first,
                                            ctx->bitbuf + g0 * ctx->bit_pitch_words, ctx->bit_pitch_words,
-                                           ctx->group_bits + g0, ctx->preset_bits, count, ctx->status, ctx->stream));
+                                           ctx->group_bits + g0, count, ctx->status, ctx->stream));
         }
         for (int i = first; i < first + count; i++)
             ctx->slot_lanes[i] = emits;
@@ -2306,7 +2346,7 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
                 HIP_TRY(ctx, hydk::launch_rans_emit(ctx->d_jobs + first, ctx->sym_count + g0, ctx->rans_aux + g0 * ctx->tok_cap,
                                                     ctx->rans_flags + g0 * (ctx->tok_cap / 16), ctx->tok_cap,
                                                     ctx->rans_final + g0, ctx->group_bits + g0, ctx->offsets + g0, ctx->payload,
-                                                    ctx->preset_bits, n, ctx->status, ctx->stream));
+                                                    n, ctx->status, ctx->stream));
             else
                 HIP_TRY(ctx, hydk::launch_pack(ctx->bitbuf + g0 * ctx->bit_pitch_words, ctx->bit_pitch_words,
                                                ctx->group_bits + g0, ctx->offsets + g0, ctx->payload,

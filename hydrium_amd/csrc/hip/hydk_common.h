@@ -85,7 +85,8 @@ typedef struct HydkLfJob {
     int scheme;              /* HF clustering scheme 0..3 = 9 / 3 / 2 / 1 clusters per preset */
     int use_luts;            /* 1: gather from the uploaded LUTs instead of evaluating them in registers */
     unsigned preset;         /* HF preset id of this LF group (written in front of each group section) */
-    int pad0;
+    unsigned short preset_bits; /* hyd_cllog2(LF groups of this LF group's frame): the width of that field (encoder.c:940) */
+    unsigned short frame_first; /* the first slot of this LF group's frame: where the running alphabet maximum starts afresh */
     const uint16_t *in_lut8;   /* 256 entries   */
     const uint16_t *in_lut16;  /* 65536 entries */
     const float *bias_lut;     /* 65536 entries */

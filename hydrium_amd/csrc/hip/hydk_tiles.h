@@ -60,6 +60,42 @@ typedef struct HydkMixedPlan {
     uint32_t shapes_off, frames_off, pad[2];
 } HydkMixedPlan;
 
+/* A FRAMES plan (csrc/host/mixed.c, hydamd_mixed_create_slots): one-frame images of different sizes AND different LF-group
+ * counts side by side.  A frame record says which kind its frame is: one LF group — `one`, the mixed plan's record, and the
+ * shape it names — or several — `plan_off`, where in this buffer a complete HydkAsmPlan of that image lies (hydk_assemble.h:
+ * one blob, the LF groups in raster order, file header, is_last; images of one size share one).  Either way the record
+ * names the frame's slots in the batch view and its part of each of the assembler's scratch arrays, prefix sums the host
+ * computes: heads, head bits and HF byte counts are indexed by slot, HFGlobal, TOC, section sizes and pieces per frame.
+ * `parts` maps a workgroup of k_batch_prepare_frames to (frame << 8 | part) over the frames of several LF groups. */
+#define HYDK_FRAMES_MAGIC 0x46584D48u /* "HMXF" */
+#define HYDK_FRAMES_MAX_LF_GROUPS 28  /* of one image: up to here a frame clusters nine ways (HYDAMD_BATCH_FRAME_LF_GROUPS) */
+typedef struct HydkBatchFrame {
+    HydkTileFrame one;             /* one LF group: the frame's prefix and shape */
+    uint32_t plan_off;             /* several: the frame's HydkAsmPlan; 0: one LF group */
+    uint32_t first_slot, lf_groups;
+    uint32_t piece_base;           /* sum of 3 n + 5 over the frames before it */
+    uint32_t hfg_off, hfg_words;   /* in words */
+    uint32_t toc_off, toc_words;
+    uint32_t sizes_off, pad[3];    /* in entries of 8 bytes; a frame of several LF groups has toc_n of them */
+} HydkBatchFrame;
+
+typedef struct HydkFramesPlan {
+    uint32_t magic, total_bytes, num_frames, nshapes;
+    uint32_t shapes_off, frames_off, parts_off, nparts; /* HydkTileShape[], HydkBatchFrame[], uint32_t[] */
+    uint32_t num_slots, npieces, nplans, pad;           /* LF groups and pieces of the batch; distinct HydkAsmPlans */
+} HydkFramesPlan;
+
+/* what the assembler's scratch arrays hold for batches of up to F frames and N LF groups in all, whatever the sizes: a
+ * slot's head is the larger of the two layouts'; a frame of n LF groups has 3 n + 5 pieces, a TOC of 2 + n + (<= 64 n)
+ * entries and an HFGlobal of (hfpre_bits + 2 + 9 C) / 32 + 73 C + 2 words with C = 9 n, where hfpre holds the cluster map
+ * of 1485 n contexts at no more than 16 bits each; a frame of one LF group the tile layout's fixed arrays.  The planner
+ * holds every batch against these (mixed.c), the device each frame against its own share (HYDK_ASM_E_SCRATCH). */
+#define HYDK_FRAMES_HEAD_STRIDE HYDK_TILE_HEAD_WORDS
+#define HYDK_FRAMES_HFG_CAP(F, N) ((size_t)(F) * HYDK_TILE_MID_WORDS + (size_t)(N) * (743u + 660u))
+#define HYDK_FRAMES_TOC_CAP(F, N) ((size_t)(F) * HYDK_TILE_TOC_WORDS + (size_t)(N) * 65u)
+#define HYDK_FRAMES_SIZES_CAP(F, N) ((size_t)(F) * 2u + (size_t)(N) * 65u)
+#define HYDK_FRAMES_PIECES_CAP(F, N) ((size_t)(F) * 5u + (size_t)(N) * 3u)
+
 typedef struct HydkTileSizes { /* what the preparation of one frame leaves */
     uint32_t head_bits, mid_bits, toc_bits, err;
     uint64_t lfsec_bytes, hfg_bytes; /* several groups: the two padded sections */

@@ -1323,7 +1323,7 @@ __global__ __launch_bounds__(kThreads) void k_build_tables(const uint32_t *hist_
                                                            const uint32_t *alpha_max_all, int nclusters,
                                                            uint32_t alpha_floor, const uint32_t *alpha_floor_dev,
                                                            int first_slot, int num_slots, const uint32_t *lf_hist,
-                                                           HydkLfStream *lf_streams, void *lf_work, int slots_per_frame) {
+                                                           HydkLfStream *lf_streams, void *lf_work, const HydkLfJob *__restrict__ jobs_all) {
     HYDK_URGENT();
     if ((int)blockIdx.x >= num_slots) {
         __shared__ LfHuffScratch s_huff;
@@ -1372,9 +1372,10 @@ __global__ __launch_bounds__(kThreads) void k_build_tables(const uint32_t *hist_
         uint32_t mx = alpha_floor; /* maximum over the LF groups other GPUs coded before ours */
         if (alpha_floor_dev)       /* ... when it was exchanged on the device (no host round trip) */
             mx = max(mx, *alpha_floor_dev);
-        /* a context that codes a BATCH of independent frames in one launch group (hydamd_begin_batch) holds frame k in slots
-         * k * slots_per_frame ...: the maximum starts afresh with every frame */
-        const unsigned frame_first = slots_per_frame > 0 ? slot - slot % (unsigned)slots_per_frame : 0u;
+        /* a context that codes a BATCH of independent frames in one launch group (hydamd_begin_batch, hydamd_begin_batch_frames)
+         * holds every frame in slots of its own: the maximum starts afresh at the frame's first slot, which the slot's job
+         * descriptor names (jobs_all, like every array here, is indexed by the context's slot) */
+        const unsigned frame_first = min((unsigned)jobs_all[slot].frame_first, slot);
         for (unsigned sl = frame_first; sl <= slot; sl++)
             mx = max(mx, alpha_max_all[sl]);
         uint32_t lg = mx > 1 ? 32 - __clz((int)(mx - 1)) : 0; /* ceil(log2(mx)) */
@@ -1614,7 +1615,7 @@ template <int WAVES, bool DEFER> /* groups (= waves) per workgroup; DEFER: the b
 __global__ __launch_bounds__(64 * WAVES) void k_rans_encode(const HydkLfJob *__restrict__ jobs, const uint32_t *sym_count_all,
                                                             const HydkTables *tabs, uint32_t *bitbuf_all,
                                                             uint32_t bit_pitch_words, uint32_t *group_bits_all,
-                                                            int preset_bits, const uint32_t *status, uint16_t *aux_all,
+                                                            const uint32_t *status, uint16_t *aux_all,
                                                             uint16_t *flags_all, uint32_t aux_pitch, uint32_t *final_state_all) {
     constexpr int kThreads = 64 * WAVES;                             /* shadows the file-level constant */
     constexpr int kBlocksPerLfg = HYDK_GROUPS_PER_LFG / WAVES;
@@ -1831,7 +1832,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_rans_encode(const HydkLfJob *__r
         if (lane == 0) {
             final_state_all[G] = state;
             /* [preset id][final state][per symbol: refill word, residue bits] (encoder.c:945, entropy.c:1127-1147) */
-            group_bits_all[G] = (uint32_t)preset_bits + (n > 0 ? 32u : 0u) + 16u * refills + HYDK_GLOBAL(const uint32_t, jobs[slot].rbits_total)[g];
+            group_bits_all[G] = (uint32_t)jobs[slot].preset_bits + (n > 0 ? 32u : 0u) + 16u * refills + HYDK_GLOBAL(const uint32_t, jobs[slot].rbits_total)[g];
         }
         return;
     }
@@ -1844,7 +1845,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_rans_encode(const HydkLfJob *__r
             nb = 32;
         } else if (lane == 1) {
             val = jobs[slot].preset;
-            nb = (uint32_t)preset_bits;
+            nb = (uint32_t)jobs[slot].preset_bits;
         }
         emit(val, nb);
     }
@@ -1969,7 +1970,7 @@ __global__ __launch_bounds__(64) void k_rans_lanes(const HydkLfJob *__restrict__
                                                    const HydkTables *tabs, uint16_t *aux_all, uint16_t *flags_all,
                                                    uint32_t aux_pitch /* symbols per group in aux / flags */,
                                                    uint32_t *final_state_all, uint32_t *group_bits_all,
-                                                   int preset_bits, const uint32_t *status, int num_slots,
+                                                   const uint32_t *status, int num_slots,
                                                    const uint32_t *lf_hist, HydkLfStream *lf_streams, void *lf_work) {
     /* The workgroup HOLDS its LDS for the whole walk, and in the pipelined loop that (times the walk's duration, which
      * more than doubles beside other frames' transform workgroups) is what the chains cost the kernels around them
@@ -2446,7 +2447,7 @@ __global__ __launch_bounds__(64) void k_rans_lanes(const HydkLfJob *__restrict__
     if (lane < ngroups) {
         final_state_all[G] = state;
         /* [preset id][final state][per symbol: refill word, residue bits] (encoder.c:945, entropy.c:1127-1147) */
-        group_bits_all[G] = (uint32_t)preset_bits + (n > 0 ? 32u : 0u) + 16u * refills + HYDK_GLOBAL(const uint32_t, jobs[slot].rbits_total)[lane];
+        group_bits_all[G] = (uint32_t)jobs[slot].preset_bits + (n > 0 ? 32u : 0u) + 16u * refills + HYDK_GLOBAL(const uint32_t, jobs[slot].rbits_total)[lane];
     } else {
         group_bits_all[G] = 0;
     }
@@ -2478,7 +2479,7 @@ constexpr int kEmitWin = kEmitBatch + 4;     /* 512 symbols x at most 32 bits = 
 __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restrict__ jobs, const uint32_t *sym_count_all,
                                                         const uint16_t *aux_all, const uint16_t *flags_all, uint32_t aux_pitch,
                                                         const uint32_t *final_state_all, const uint32_t *group_bits_all,
-                                                        const uint64_t *offsets_all, uint8_t *payload, int preset_bits,
+                                                        const uint64_t *offsets_all, uint8_t *payload,
                                                         const uint32_t *status, int vblocks) {
     __shared__ uint32_t s_win[4][kEmitWin];
     HYDK_URGENT();
@@ -2634,7 +2635,7 @@ __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restr
         uint32_t val[kEmitPer] = {0, 0, 0, 0, 0, 0, 0, 0}, nb[kEmitPer] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (lane == 0) {
             val[0] = jobs[slot].preset;
-            nb[0] = (uint32_t)preset_bits;
+            nb[0] = (uint32_t)jobs[slot].preset_bits;
             if (n > 0) {
                 val[1] = final_state_all[G];
                 nb[1] = 32;
@@ -2936,17 +2937,17 @@ hipError_t transform_footprint(int fmt, int xmode, int *lds_bytes, int *register
  * lf_hist / lf_streams / lf_work already point at the first of them */
 hipError_t launch_tables(const uint32_t *hist, HydkTables *tabs, const uint32_t *alpha_max, int nclusters, int first_slot,
                          int num_slots, uint32_t alpha_floor, const uint32_t *alpha_floor_dev, const uint32_t *lf_hist,
-                         HydkLfStream *lf_streams, void *lf_work, int slots_per_frame, hipStream_t stream) {
+                         HydkLfStream *lf_streams, void *lf_work, const HydkLfJob *jobs_all, hipStream_t stream) {
     hipLaunchKernelGGL(k_build_tables, dim3(lf_hist ? 2 * num_slots : num_slots), dim3(kThreads), 0, stream, hist, tabs, alpha_max,
-                       nclusters, alpha_floor, alpha_floor_dev, first_slot, num_slots, lf_hist, lf_streams, lf_work, slots_per_frame);
+                       nclusters, alpha_floor, alpha_floor_dev, first_slot, num_slots, lf_hist, lf_streams, lf_work, jobs_all);
     return hipGetLastError();
 }
 
 hipError_t launch_rans(const HydkLfJob *d_jobs, const uint32_t *sym_count, const HydkTables *tabs, uint32_t *bitbuf,
-                       uint32_t bit_pitch_words, uint32_t *group_bits, int preset_bits, int num_slots, const uint32_t *status,
+                       uint32_t bit_pitch_words, uint32_t *group_bits, int num_slots, const uint32_t *status,
                        hipStream_t stream) {
     hipLaunchKernelGGL((k_rans_encode<4, false>), dim3(num_slots * 16), dim3(256), 0, stream, d_jobs, sym_count, tabs, bitbuf,
-                       bit_pitch_words, group_bits, preset_bits, status, (uint16_t *)nullptr, (uint16_t *)nullptr, 0u,
+                       bit_pitch_words, group_bits, status, (uint16_t *)nullptr, (uint16_t *)nullptr, 0u,
                        (uint32_t *)nullptr);
     return hipGetLastError();
 }
@@ -2954,15 +2955,15 @@ hipError_t launch_rans(const HydkLfJob *d_jobs, const uint32_t *sym_count, const
 /* the same walk leaving refill words and flags for k_rans_emit instead of writing bits itself (4-byte records only) */
 hipError_t launch_rans_deferred(const HydkLfJob *d_jobs, const uint32_t *sym_count, const HydkTables *tabs, uint16_t *aux,
                                 uint16_t *flags, uint32_t aux_pitch, uint32_t *final_state, uint32_t *group_bits,
-                                int preset_bits, int num_slots, const uint32_t *status, hipStream_t stream) {
+                                int num_slots, const uint32_t *status, hipStream_t stream) {
     hipLaunchKernelGGL((k_rans_encode<4, true>), dim3(num_slots * 16), dim3(256), 0, stream, d_jobs, sym_count, tabs,
-                       (uint32_t *)nullptr, 0u, group_bits, preset_bits, status, aux, flags, aux_pitch, final_state);
+                       (uint32_t *)nullptr, 0u, group_bits, status, aux, flags, aux_pitch, final_state);
     return hipGetLastError();
 }
 
 /* lf_hist != NULL: the launch also builds the LF coder's prefix codes of the same LF groups (num_slots more workgroups) */
 hipError_t launch_rans_lanes(const HydkLfJob *d_jobs, const uint32_t *sym_count, const HydkTables *tabs, uint16_t *aux,
-                             uint16_t *flags, uint32_t aux_pitch, uint32_t *final_state, uint32_t *group_bits, int preset_bits,
+                             uint16_t *flags, uint32_t aux_pitch, uint32_t *final_state, uint32_t *group_bits,
                              int nclusters, int num_slots, const uint32_t *status, const uint32_t *lf_hist,
                              HydkLfStream *lf_streams, void *lf_work, hipStream_t stream) {
     const dim3 grid(lf_hist ? 2 * num_slots : num_slots);
@@ -2979,12 +2980,12 @@ hipError_t launch_rans_lanes(const HydkLfJob *d_jobs, const uint32_t *sym_count,
             opted.fetch_or(1u << (dev & 31));                                                                                  \
         }                                                                                                                      \
         hipLaunchKernelGGL(k_rans_lanes<NC>, grid, dim3(64), (size_t)lanes_lds_bytes(NC), stream, d_jobs, sym_count, tabs, aux, flags, aux_pitch, \
-                           final_state, group_bits, preset_bits, status, num_slots, lf_hist, lf_streams, lf_work);             \
+                           final_state, group_bits, status, num_slots, lf_hist, lf_streams, lf_work);                          \
     } while (0)
 #else
 #define HYDK_LAUNCH_LANES(NC)                                                                                                  \
     hipLaunchKernelGGL(k_rans_lanes<NC>, grid, dim3(64), 0, stream, d_jobs, sym_count, tabs, aux, flags, aux_pitch, final_state, \
-                       group_bits, preset_bits, status, num_slots, lf_hist, lf_streams, lf_work)
+                       group_bits, status, num_slots, lf_hist, lf_streams, lf_work)
 #endif
     /* the tables in LDS are sized by the clustering scheme (encoder.c:862-901: 9 / 3 / 2 / 1 clusters per preset) */
     if (nclusters == 9)
@@ -3003,7 +3004,7 @@ hipError_t launch_rans_lanes(const HydkLfJob *d_jobs, const uint32_t *sym_count,
 
 hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, const uint16_t *aux, const uint16_t *flags,
                             uint32_t aux_pitch, const uint32_t *final_state, const uint32_t *group_bits, const uint64_t *offsets,
-                            uint8_t *payload, int preset_bits, int num_slots, const uint32_t *status, hipStream_t stream) {
+                            uint8_t *payload, int num_slots, const uint32_t *status, hipStream_t stream) {
     /* virtual blocks per workgroup: HYDAMD_EMIT_SHARE (A/B; 1 = one workgroup per four groups, as until round 5) */
     static const int share = [] {
         const char *v = getenv("HYDAMD_EMIT_SHARE");
@@ -3012,7 +3013,7 @@ hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, 
     }();
     const int vblocks = num_slots * 16;
     hipLaunchKernelGGL(k_rans_emit, dim3((vblocks + share - 1) / share), dim3(kThreads), 0, stream, d_jobs, sym_count, aux, flags,
-                       aux_pitch, final_state, group_bits, offsets, payload, preset_bits, status, vblocks);
+                       aux_pitch, final_state, group_bits, offsets, payload, status, vblocks);
     return hipGetLastError();
 }
 

@@ -75,6 +75,10 @@ def dll(path: Optional[str] = None):
         d.hydamd_debug_shader_clock_mhz.argtypes = [vp, C.POINTER(C.c_double)]
         d.hydamd_encode_image_batch.argtypes = [vp, i, C.POINTER(vp), C.c_ssize_t, C.c_ssize_t, i, sz, sz]
         d.hydamd_begin_batch.argtypes = [vp, u, i]
+        d.hydamd_begin_batch_frames.restype = i
+        d.hydamd_begin_batch_frames.argtypes = [vp, i, C.POINTER(u)]
+        d.hydamd_replay_frame.restype = i
+        d.hydamd_replay_frame.argtypes = [vp]
         d.hydamd_finish_frame.argtypes = [vp, i]
         d.hydamd_run_transform.argtypes = [vp, i]
         d.hydamd_run_entropy.argtypes = [vp, i]
@@ -199,6 +203,8 @@ def dll(path: Optional[str] = None):
         d.hydamd_batch_overflow_reruns.argtypes = [vp]
         d.hydamd_mixed_create.restype = vp
         d.hydamd_mixed_create.argtypes = [i, i, i, C.POINTER(i)]
+        d.hydamd_mixed_create_slots.restype = vp
+        d.hydamd_mixed_create_slots.argtypes = [i, i, i, i, C.POINTER(i)]
         d.hydamd_mixed_destroy.restype = None
         d.hydamd_mixed_destroy.argtypes = [vp]
         d.hydamd_mixed_error.restype = C.c_char_p
@@ -278,6 +284,12 @@ class DeviceContext:
 
     def begin_frame(self, num_presets: int):
         self._ck(self.d.hydamd_begin_frame(self.h, num_presets))
+
+    def begin_batch_frames(self, lf_groups: Sequence[int]):
+        """One launch group of len(lf_groups) independent images, image k of lf_groups[k] LF groups (1..28) in the slots
+        behind image k - 1's; then encode_lf_group per slot (preset: the raster index inside the image) and finish_frame."""
+        counts = (C.c_uint * max(len(lf_groups), 1))(*[int(n) for n in lf_groups])
+        self._ck(self.d.hydamd_begin_batch_frames(self.h, len(lf_groups), counts))
 
     def encode_lf_group(self, slot: int, ptrs: Sequence[int], row_stride: int, pixel_stride: int, fmt: int,
                         width: int, height: int, preset: int, host: bool = False):
@@ -934,15 +946,23 @@ class FrameBatch:
 class MixedBatch:
     """Batches of up to ``max_frames`` (0: the default, 32) one-frame images, EACH OF ITS OWN SIZE up to 2048 x 2048, from
     device-resident pixels, every one a finished file built on the GPU (hydamd_mixed_*, csrc/host/mixed.c): the files back
-    to back in one device buffer, the table of their offsets beside it.  Conventions as FrameBatch's."""
+    to back in one device buffer, the table of their offsets beside it.  Conventions as FrameBatch's.
 
-    def __init__(self, max_frames: int = 0, linear_light: int = 0, device: int = 0):
+    ``max_lf_groups`` (max_frames..255; None: as above, a slot per image): the LF-group slots of the object's context — an
+    image may then hold up to 28 LF groups of 2048 x 2048 pixels, a batch up to max_lf_groups of them in all
+    (hydamd_mixed_create_slots)."""
+
+    def __init__(self, max_frames: int = 0, linear_light: int = 0, device: int = 0, max_lf_groups: Optional[int] = None):
         self.d = dll()
         st = C.c_int(0)
-        self.h = self.d.hydamd_mixed_create(device, max_frames, int(linear_light), C.byref(st))
+        if max_lf_groups is None:
+            self.h = self.d.hydamd_mixed_create(device, max_frames, int(linear_light), C.byref(st))
+        else:
+            self.h = self.d.hydamd_mixed_create_slots(device, max_frames, int(max_lf_groups), int(linear_light), C.byref(st))
         if not self.h:
             raise DeviceError(st.value, (self.d.hydamd_mixed_error(None) or b"").decode() or "mixed batch could not be created")
         self.max_frames = max_frames or 32
+        self.max_lf_groups = max_lf_groups
         self.frames = 0
         self._keep = None
 

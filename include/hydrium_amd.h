@@ -140,6 +140,14 @@ HYDAMD_EXPORT int hydamd_encode_image(HydAmdContext *ctx, const void *const src[
  * payload.  A batch is not exported as a blob (hydamd_export_frame*: HYD_API_ERROR): hydamd_export_batch_owned gives its
  * results as a view, and hydamd_batch_* (below) turns a batch into finished files on the device. */
 HYDAMD_EXPORT int hydamd_begin_batch(HydAmdContext *ctx, unsigned num_presets, int frames);
+/* `frames` independent images of DIFFERENT shapes as one launch group: image k of lf_groups[k] LF groups (1..28 each: the
+ * nine-cluster scheme, which keeps the cluster count launch-wide), in slots first_k .. first_k + lf_groups[k] - 1 with
+ * first_k = sum of lf_groups[0 .. k - 1]; presets and the running alphabet maximum restart with every image.  Then
+ * hydamd_encode_lf_group per slot (preset: the LF group's raster index inside its image), hydamd_finish_frame and
+ * hydamd_export_batch_owned over all slots, as for hydamd_begin_batch.  HYD_API_ERROR: frames < 1, a null pointer, a count
+ * of 0 or above 28, more LF groups in all than the context has slots. */
+#define HYDAMD_BATCH_FRAME_LF_GROUPS 28
+HYDAMD_EXPORT int hydamd_begin_batch_frames(HydAmdContext *ctx, int frames, const unsigned *lf_groups);
 HYDAMD_EXPORT int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const *src, ptrdiff_t row_stride,
                                             ptrdiff_t pixel_stride, int sample_fmt, size_t width, size_t height);
 
@@ -582,8 +590,10 @@ HYDAMD_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b);
  * A batch of one-frame images EACH OF ITS OWN SIZE whose pixels already sit in HBM, every one a finished FILE, built on
  * the GPU (csrc/host/mixed.c, csrc/hip/assemble_batch.hip) — for a queue of pictures of many sizes in device memory
  * (thumbnails, product shots, crops, the output of a GPU decoder), which hydamd_batch_* would need one object per shape
- * for.  Every image is at most 2048 x 2048 pixels, ONE LF group; the images of a batch are coded as one launch group
- * (hydamd_begin_batch(ctx, 1, frames), each LF group of its own size, as a tile-mode image's ragged tiles are), and the
+ * for.  Every image is at most 2048 x 2048 pixels, ONE LF group (hydamd_mixed_create), or up to 28 LF groups — 117
+ * Mpixel, e.g. 14336 x 8192 — (hydamd_mixed_create_slots); the images of a batch are coded as one launch group
+ * (hydamd_begin_batch(ctx, 1, frames), each LF group of its own size, as a tile-mode image's ragged tiles are;
+ * hydamd_begin_batch_frames where images may hold several LF groups), and the
  * launch sequence behind hydamd_batch_*'s entropy stage writes every frame — file header, frame header with is_last, TOC,
  * LFGlobal, LF group, HFGlobal, HF sections; images of a single 256x256 group as one bit-contiguous section — exactly as
  * the reference writes that picture alone with tile_size_shift_x = tile_size_shift_y = -1, the files back to back at byte
@@ -596,9 +606,16 @@ HYDAMD_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b);
  *                                whatever the image sizes, so the default object holds about 3 GB plus the output
  *                                buffer, one of 255 about 22 GB.  linear_light: as HYDImageMetadata's, for every image.
  *                                One device and one stream per object.
+ *   hydamd_mixed_create_slots    as hydamd_mixed_create, with max_lf_groups (max_frames..255) slots in the object's context:
+ *                                an image may then hold up to 28 LF groups, a batch up to max_frames images and
+ *                                max_lf_groups LF groups in all.  28: up to there a frame clusters nine ways whatever its
+ *                                LF-group count, so one chain launch serves frames of 1, 4 and 9 LF groups side by side;
+ *                                what differs per frame (the width of the preset field, where the alphabet maximum
+ *                                restarts, the frame's plan) travels per slot and per frame.
  *   hydamd_encode_mixed          `frames` <= max_frames images: images[k].src are image k's channel pointers (device
  *                                memory, its first pixel), row_stride / pixel_stride in samples as hyd_send_tile's,
- *                                width and height 1..2048; one sample_fmt for the whole call.  Enqueues the batch and
+ *                                width and height 1..2048 (hydamd_mixed_create_slots: at least 1, at most 28 LF groups of
+ *                                2048 x 2048, the batch's LF groups at most max_lf_groups); one sample_fmt for the whole call.  Enqueues the batch and
  *                                its assembly and returns; the pixels stay borrowed until hydamd_mixed_result, the
  *                                descriptors only for the call.  The output buffer is sized before anything is
  *                                enqueued, from the batch's plan and the context's capacities.
@@ -611,22 +628,25 @@ HYDAMD_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b);
  *   hydamd_mixed_device,         the files and the same table (frames + 1 entries) in device memory.  Everything is
  *   hydamd_mixed_offsets_device  valid until the object's next hydamd_encode_mixed.
  *   hydamd_mixed_read            file `frame` (or, with -1, all of them back to back) to host memory, one copy.
- * HYD_API_ERROR: max_frames out of range, a null descriptor array or channel pointer, a width or height of 0 or above
- * 2048, `frames` outside 1..max_frames, a bad sample format, a second encode while a batch is in flight, result / offsets
+ * HYD_API_ERROR: max_frames or max_lf_groups out of range, a null descriptor array or channel pointer, a width or height of
+ * 0 or above 2048 (hydamd_mixed_create_slots: an image of more than 28 LF groups, a batch of more LF groups than
+ * max_lf_groups), `frames` outside 1..max_frames, a bad sample format, a second encode while a batch is in flight, result / offsets
  * / read without a batch, a destination that is too small.  No usable device at creation: HYD_INTERNAL_ERROR.
  * hydamd_mixed_overflow_reruns: batches run twice because a buffer was too small.  Keep several objects for a deeper
  * queue (scripts/mixed_batch_probe.py keeps four).
- * OUT OF SCOPE: images of more than one LF group (a context's slots per frame, cluster scheme and preset bits are
- * uniform per launch group: such images go through one hydamd_batch_* object per shape); an ICC profile (it would sit in
- * every frame's prefix); sample formats mixed within one call; naming the image that held a NaN; several devices per object.
+ * OUT OF SCOPE: images of more than 28 LF groups (other cluster schemes would need chain launches per cluster count: such
+ * images go through one hydamd_batch_* object per shape, or hydamd_encode_image); an ICC profile (it would sit in
+ * every frame's prefix); sample formats mixed within one call; naming the image that held a NaN; several devices per object;
+ * closing the throughput gap to the padded-classes upper reference that profiles/mixed_batch.txt records.
  */
 typedef struct HydAmdImageDesc {
     const void *src[3];                 /* device pointers: R, G, B of the image's first pixel */
     ptrdiff_t row_stride, pixel_stride; /* in samples, as hyd_send_tile's */
-    size_t width, height;               /* 1..2048 each */
+    size_t width, height;               /* 1..2048 each; hydamd_mixed_create_slots: >= 1, at most 28 LF groups of 2048 x 2048 */
 } HydAmdImageDesc;
 typedef struct HydAmdMixed HydAmdMixed;
 HYDAMD_EXPORT HydAmdMixed *hydamd_mixed_create(int device, int max_frames, int linear_light, int *status);
+HYDAMD_EXPORT HydAmdMixed *hydamd_mixed_create_slots(int device, int max_frames, int max_lf_groups, int linear_light, int *status);
 HYDAMD_EXPORT void hydamd_mixed_destroy(HydAmdMixed *m);
 HYDAMD_EXPORT const char *hydamd_mixed_error(HydAmdMixed *m);
 HYDAMD_EXPORT int hydamd_encode_mixed(HydAmdMixed *m, int frames, const HydAmdImageDesc *images, int sample_fmt);
