@@ -24,7 +24,10 @@
  *                        batch's frames of one LF group take the wavefront path beside it (k_batch_prepare_frames_one,
  *                        grid F), on their first slot and their share
  *   k_batch_place        one workgroup: the union of the frames' error words, a prefix sum over their sizes = the
- *                        offsets table, every piece moved to its frame's start, the range k_pieces_copy reads
+ *                        offsets table, every piece moved to its frame's start, the range k_pieces_copy reads; with
+ *                        per-image outcomes (hydk_batch_set_image_errors) a frame ANY of whose slots carries the bad-sample
+ *                        flag (HydAmdBlobSlot.reserved[0]) — whichever of the five kernels above prepared it — counts 0
+ *                        bytes, has its pieces emptied in place and its status word set, and fails nothing
  *   k_pieces_copy        (assemble.hip) every output word composed from the pieces that touch it and stored once; the
  *                        padding that ends a section, and a file, is the gap no piece covers
  *
@@ -67,6 +70,7 @@ struct BatchScratch { /* device pointers; frame f's part of each array is what a
     uint32_t *done;       /* [frames] */
     uint64_t *result;     /* [frames][4] error word, 0, bytes of the frame, HFGlobal's bit count */
     uint64_t *offsets;    /* [frames + 1] the table the caller gets */
+    uint32_t *status;     /* [frames] beside it: 0 a file, HYDAMD_IMAGE_BAD_SAMPLE no bytes (per-image outcomes only) */
     uint64_t *range;      /* [4] error word, 0, bytes of all files (what k_pieces_copy reads), bytes the output must hold */
     uint32_t n, toc_n, hfg_words, toc_words, pieces_per_frame;
     /* a frames plan (hydk_tiles.h, HydkFramesPlan): the five above are zero — every frame's record names its slots and its
@@ -312,22 +316,43 @@ __global__ __launch_bounds__(64) void k_batch_prepare_frames_one(const uint8_t *
 /* ---- k_batch_place: grid 1, block 256 ---- */
 __global__ __launch_bounds__(256) void k_batch_place(const uint8_t *__restrict__ blob, const HydkTileExtent *__restrict__ ext, uint32_t frames,
                                                      uint32_t slots /* of the view */, const uint8_t *__restrict__ frames_plan /* or null */,
-                                                     BatchScratch B, uint64_t out_cap, uint64_t *h_result /* pinned [4 + frames + 1] */) {
+                                                     BatchScratch B, uint64_t out_cap, uint32_t per_image,
+                                                     uint64_t *h_result /* pinned [4 + frames + 1] */, uint64_t *h_status /* pinned [frames] */) {
     __shared__ uint64_t s_wave[4];
     __shared__ uint64_t s_at[256];
+    __shared__ uint8_t s_skip[256];
     __shared__ uint32_t s_err;
     const uint32_t t = threadIdx.x;
     const HydAmdBlobHeader *h = (const HydAmdBlobHeader *)blob;
-    uint32_t e = 0;
+    uint32_t e = 0, skip = 0;
     uint64_t size = 0;
     if (t < frames) {
         e = (uint32_t)B.result[(size_t)t * 4];
         size = B.result[(size_t)t * 4 + 2];
+        /* per-image outcomes: the frame's slots are looked at only where its preparation found nothing wrong — the view is
+         * this batch's and, with a frames plan, the frame's record names slots inside it (frames_record_check) */
+        if (per_image && !e) {
+            uint32_t first = t * B.n, n = B.n;
+            if (frames_plan) {
+                const HydkFramesPlan *plan = (const HydkFramesPlan *)frames_plan;
+                const HydkBatchFrame fr = ((const HydkBatchFrame *)(frames_plan + plan->frames_off))[t];
+                first = fr.first_slot;
+                n = fr.lf_groups;
+            }
+            const HydAmdBlobSlot *rec = (const HydAmdBlobSlot *)(blob + sizeof(HydAmdBlobHeader)) + first;
+            if ((uint64_t)first + n <= slots)
+                skip = hydk_frame_flagged(rec, n);
+            if (skip)
+                size = 0; /* no bytes: offsets[t + 1] == offsets[t] */
+        }
     }
+    s_skip[t] = (uint8_t)skip;
     if (t == 0) {
         s_err = 0;
         /* the frames' HF extents together are the packed string, no more and no less */
         uint32_t he = blob_ident(h, slots);
+        if (per_image)
+            he &= ~(uint32_t)HYDK_ASM_E_NAN; /* (a context in per-slot mode never sets the bit: the outcome is the frame's) */
         if (!he && ext[slots - 1].hf_off + ext[slots - 1].hf_bytes != h->hf_bytes)
             he = HYDK_ASM_E_SIZE;
         e |= he;
@@ -344,8 +369,14 @@ __global__ __launch_bounds__(256) void k_batch_place(const uint8_t *__restrict__
     if (t < frames) {
         B.offsets[t] = at;
         h_result[4 + t] = at;
+        B.status[t] = skip ? HYDAMD_IMAGE_BAD_SAMPLE : 0u;
+        h_status[t] = skip ? HYDAMD_IMAGE_BAD_SAMPLE : 0u;
     }
     __syncthreads();
+    /* A skipped frame keeps its places in the piece list — the list k_pieces_copy searches stays as long, contiguous and in
+     * output order — but every one of them becomes an EMPTY piece at the frame's offset, which is also the next frame's
+     * (hydk_place_piece): ends stay monotone, no bit of the output is covered, and the files on both sides meet inside one
+     * output word. */
     if (!fin && frames_plan) {
         /* frames of different LF-group counts: frame f's 3 n + 5 pieces start where its record says — the sum over the
          * frames before it, so that the list stays contiguous and in output order (no error: the plan has been checked) */
@@ -353,12 +384,14 @@ __global__ __launch_bounds__(256) void k_batch_place(const uint8_t *__restrict__
             const HydkFramesPlan *plan = (const HydkFramesPlan *)frames_plan;
             const HydkBatchFrame fr = ((const HydkBatchFrame *)(frames_plan + plan->frames_off))[t];
             for (uint32_t i = 0; i < 3u * fr.lf_groups + 5u; i++)
-                B.pieces[fr.piece_base + i].dst_bit += at * 8u;
+                hydk_place_piece(&B.pieces[fr.piece_base + i], at, skip);
         }
     } else if (!fin) {
         const uint32_t np = frames * B.pieces_per_frame;
-        for (uint32_t i = t; i < np; i += 256)
-            B.pieces[i].dst_bit += s_at[i / B.pieces_per_frame] * 8u;
+        for (uint32_t i = t; i < np; i += 256) {
+            const uint32_t f = i / B.pieces_per_frame;
+            hydk_place_piece(&B.pieces[i], s_at[f], s_skip[f]);
+        }
     }
     if (t == 0) {
         B.offsets[frames] = total;
@@ -391,7 +424,9 @@ struct HydkBatchAsm {
     BatchScratch B = {};
     uint64_t fixed = 0;           /* bytes of a frame beyond its packed LF streams and HF sections, at most; stays 0 for a
                                    * mixed assembler, whose frames differ: mixed.c sums the same terms per batch, from its plan */
-    uint64_t *h_result = nullptr; /* pinned [4 + max_frames + 1]: the range quadruple, then the offsets table */
+    uint64_t *h_result = nullptr; /* pinned [4 + max_frames + 1 + max_frames]: the range quadruple, the offsets table ([frames + 1]
+                                   * of the batch), and from 4 + max_frames + 1 on the frames' status words */
+    bool per_image = false;       /* hydk_batch_set_image_errors */
     uint8_t *out = nullptr;       /* the files: owned, grown on demand (hydk_batch_reserve) */
     uint64_t out_cap = 0;
 };
@@ -485,7 +520,7 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
     };
     const size_t o_plan = take(plan ? plan_bytes + 16 : 0), o_head = take(F * head_words * 4), o_hfg = take(F * B.hfg_words * 4),
                  o_toc = take(F * B.toc_words * 4), o_pieces = take(F * B.pieces_per_frame * sizeof(HydkPiece)),
-                 o_result = take(F * 4 * 8), o_offsets = take((F + 1) * 8), o_range = take(4 * 8);
+                 o_result = take(F * 4 * 8), o_offsets = take((F + 1) * 8), o_range = take(4 * 8), o_status = take(F * 4);
     const bool one = a->one;
     const size_t o_head_bits = one ? 0 : take(F * B.n * 4), o_sizes = one ? 0 : take(F * B.toc_n * 8), o_slot_hf = one ? 0 : take(F * B.n * 8),
                  o_npieces = one ? 0 : take(F * 4), o_counters = one ? 0 : take(2 * F * 4);
@@ -501,6 +536,7 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
         B.result = (uint64_t *)(m + o_result);
         B.offsets = (uint64_t *)(m + o_offsets);
         B.range = (uint64_t *)(m + o_range);
+        B.status = (uint32_t *)(m + o_status);
         if (!one) {
             B.head_bits = (uint32_t *)(m + o_head_bits);
             B.sizes = (uint64_t *)(m + o_sizes);
@@ -513,8 +549,8 @@ int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_
         if (plan)
             HYDK_TRY(a, hipMemcpy(a->plan, plan, plan_bytes, hipMemcpyHostToDevice));
         HYDK_TRY(a, hipStreamSynchronize(nullptr)); /* the memset runs in the NULL stream, which the context's stream does not wait for */
-        HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, (4 + F + 1) * sizeof(uint64_t), hipHostMallocDefault));
-        memset(a->h_result, 0, (4 + F + 1) * sizeof(uint64_t));
+        HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, (4 + F + 1 + F) * sizeof(uint64_t), hipHostMallocDefault));
+        memset(a->h_result, 0, (4 + F + 1 + F) * sizeof(uint64_t));
         return ST_OK;
     };
     const int st = alloc();
@@ -556,7 +592,7 @@ int hydk_batch_create_frames(int device, int max_frames, int max_slots, HydkBatc
     };
     const size_t o_head = take(N * HYDK_FRAMES_HEAD_STRIDE * 4), o_hfg = take((size_t)B.hfg_cap * 4), o_toc = take((size_t)B.toc_cap * 4),
                  o_pieces = take((size_t)B.pieces_cap * sizeof(HydkPiece)), o_result = take(F * 4 * 8), o_offsets = take((F + 1) * 8),
-                 o_range = take(4 * 8), o_head_bits = take(N * 4), o_sizes = take((size_t)B.sizes_cap * 8), o_slot_hf = take(N * 8),
+                 o_range = take(4 * 8), o_status = take(F * 4), o_head_bits = take(N * 4), o_sizes = take((size_t)B.sizes_cap * 8), o_slot_hf = take(N * 8),
                  o_npieces = take(F * 4), o_counters = take(2 * F * 4);
     auto alloc = [&]() -> int {
         HYDK_TRY(a, hipSetDevice(device));
@@ -569,6 +605,7 @@ int hydk_batch_create_frames(int device, int max_frames, int max_slots, HydkBatc
         B.result = (uint64_t *)(m + o_result);
         B.offsets = (uint64_t *)(m + o_offsets);
         B.range = (uint64_t *)(m + o_range);
+        B.status = (uint32_t *)(m + o_status);
         B.head_bits = (uint32_t *)(m + o_head_bits);
         B.sizes = (uint64_t *)(m + o_sizes);
         B.slot_hf = (uint64_t *)(m + o_slot_hf);
@@ -577,8 +614,8 @@ int hydk_batch_create_frames(int device, int max_frames, int max_slots, HydkBatc
         B.done = B.err + F;
         HYDK_TRY(a, hipMemset(B.err, 0, 2 * F * sizeof(uint32_t)));
         HYDK_TRY(a, hipStreamSynchronize(nullptr));
-        HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, (4 + F + 1) * sizeof(uint64_t), hipHostMallocDefault));
-        memset(a->h_result, 0, (4 + F + 1) * sizeof(uint64_t));
+        HYDK_TRY(a, hipHostMalloc((void **)&a->h_result, (4 + F + 1 + F) * sizeof(uint64_t), hipHostMallocDefault));
+        memset(a->h_result, 0, (4 + F + 1 + F) * sizeof(uint64_t));
         return ST_OK;
     };
     const int st = alloc();
@@ -711,7 +748,8 @@ int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t 
                            blob_cap, ext, frames, a->B);
     HYDK_TRY(a, hipGetLastError());
     hipLaunchKernelGGL(k_batch_place, dim3(1), dim3(256), 0, st, (const uint8_t *)blob, ext, frames, slots,
-                       a->several ? (const uint8_t *)a->plan : (const uint8_t *)nullptr, a->B, a->out_cap, a->h_result);
+                       a->several ? (const uint8_t *)a->plan : (const uint8_t *)nullptr, a->B, a->out_cap, a->per_image ? 1u : 0u,
+                       a->h_result, a->h_result + 4 + a->max_frames + 1);
     HYDK_TRY(a, hipGetLastError());
     HYDK_TRY(a, hydk::launch_pieces_copy(a->B.pieces, npieces, nullptr, a->B.range, a->out, st));
     return ST_OK;
@@ -733,6 +771,18 @@ int hydk_batch_reserve(HydkBatchAsm *a, uint64_t bytes, void *stream) {
     a->out_cap = bytes;
     return ST_OK;
 }
+
+/* per-image outcomes for the runs that follow: a frame with a flagged slot (the view's context in per-slot mode,
+ * hydamd_set_bad_sample_per_slot) yields no bytes and a status word instead of failing the batch */
+void hydk_batch_set_image_errors(HydkBatchAsm *a, int per_image) {
+    if (a)
+        a->per_image = per_image != 0;
+}
+
+/* the frames' status words: after the stream has been synchronised the host copy ([frames] of 64 bits, valid until the
+ * next run), and the device copy ([frames] of 32 bits) */
+const uint64_t *hydk_batch_status(HydkBatchAsm *a) { return a ? a->h_result + 4 + a->max_frames + 1 : nullptr; }
+const uint32_t *hydk_batch_status_dev(HydkBatchAsm *a) { return a ? a->B.status : nullptr; }
 
 const uint8_t *hydk_batch_out(HydkBatchAsm *a) { return a ? a->out : nullptr; }
 const uint64_t *hydk_batch_offsets_dev(HydkBatchAsm *a) { return a ? a->B.offsets : nullptr; }

@@ -169,6 +169,8 @@ struct HydAmdContext {
     uint64_t *total = nullptr;      /* [1] */
     uint32_t *status = nullptr;     /* [1] bit 0: non-finite float sample */
     uint32_t *alpha_max = nullptr;  /* [slots] largest token + 1 per LF group */
+    uint32_t *bad_slots = nullptr;  /* [slots] non-zero: the slot held a non-finite float sample (written only with bad_per_slot) */
+    bool bad_per_slot = false;      /* hydamd_set_bad_sample_per_slot: the flag per slot instead of bit 0 of the status word */
     HydkLfJob *d_jobs = nullptr;    /* [slots] */
     HydkLfJob *h_jobs = nullptr;    /* [slots] pinned mirror of the frame being submitted (one of the ring below) */
     HydkLfJob *h_jobs_ring[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -226,7 +228,7 @@ struct HydAmdContext {
     uint8_t slot_frame_first[HYDAMD_MAX_LF_GROUPS] = {};  /* the first slot of the slot's frame */
     uint8_t slot_frame_groups[HYDAMD_MAX_LF_GROUPS] = {}; /* the LF groups of the slot's frame (0: the slot belongs to none) */
     bool results_valid = false;
-    uint32_t *accum = nullptr;       /* [hist | alpha_max | status | lf_hist]: cleared once per frame by k_frame_begin */
+    uint32_t *accum = nullptr;       /* [hist | alpha_max | status | lf_hist | bad_slots]: cleared once per frame by k_frame_begin */
     size_t accum_words = 0;
     bool accum_stale = true;
     bool lf_total_unpublished = false;
@@ -419,6 +421,7 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.rbits_total = ctx->rbits_total + (size_t)slot * HYDK_GROUPS_PER_LFG;
     job.hist = ctx->hist + (size_t)slot * HYDK_MAX_CLUSTERS * HYDK_ALPHABET;
     job.alpha_max = ctx->alpha_max + slot;
+    job.bad_slot = ctx->bad_per_slot ? ctx->bad_slots + slot : nullptr;
     job.dc = ctx->dc + (size_t)slot * 3 * HYDK_DC_PITCH * HYDK_DC_PITCH;
     if (slot == 0) { /* the dump planes hold one LF group */
         job.dbg_xyb = ctx->dbg_xyb;
@@ -924,13 +927,15 @@ static int create_impl(HydAmdContext *ctx, int debug_planes) {
          * first job descriptors: one launch where four memsets and a copy used to sit in the stream */
         const size_t hist_words = slots * HYDK_MAX_CLUSTERS * HYDK_ALPHABET, lf_words = (slots + 1) * HYDK_LF_CODES; /* +1: the unit-test entry's scratch */
         const size_t head_words = (slots + 1 + 3) & ~(size_t)3; /* alpha_max[slots], status, padding to 16 bytes */
-        ctx->accum_words = hist_words + head_words + ((lf_words + 3) & ~(size_t)3);
+        const size_t lf_padded = (lf_words + 3) & ~(size_t)3, bad_words = (slots + 3) & ~(size_t)3;
+        ctx->accum_words = hist_words + head_words + lf_padded + bad_words;
         HIP_TRY(ctx, hipMalloc(&ctx->accum, ctx->accum_words * sizeof(uint32_t)));
         HIP_TRY(ctx, hipMemset(ctx->accum, 0, ctx->accum_words * sizeof(uint32_t)));
         ctx->hist = ctx->accum;
         ctx->alpha_max = ctx->accum + hist_words;
         ctx->status = ctx->alpha_max + slots;
         ctx->lf_hist = ctx->accum + hist_words + head_words;
+        ctx->bad_slots = ctx->lf_hist + lf_padded;
     }
     HIP_TRY(ctx, hipMalloc(&ctx->sym_count, slots * G * sizeof(uint32_t)));
     HIP_TRY(ctx, hipMalloc(&ctx->part_info, (size_t)(split_slots() > kSplitSlots ? split_slots() : kSplitSlots) * G * 4 * sizeof(uint2)));
@@ -1607,6 +1612,34 @@ int hydamd_read_alphabet_max(HydAmdContext *ctx, int slot, uint32_t *max_token_p
     if (st != ST_OK)
         return st;
     HIP_TRY(ctx, hipMemcpy(max_token_plus_one, ctx->alpha_max + slot, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return ST_OK;
+}
+
+/* Where a non-finite float sample is recorded.  Off (default): bit 0 of the launch-wide status word — hydamd_sync fails with
+ * "Invalid NaN Float", a view's header carries the bit.  On: one word per SLOT, cleared with the frame's other accumulators
+ * (so an overflow rerun and hydamd_replay_frame start from zero again and the transform kernels set it afresh); the sample is
+ * coded as 0.0, the status word and the header stay clean, hydamd_sync succeeds, and the flag travels in the slot's record of
+ * a view (HydAmdBlobSlot.reserved[0]).  The flag's address rides in each slot's job descriptor, so the switch holds for the LF
+ * groups recorded after the call: set it between frames. */
+int hydamd_set_bad_sample_per_slot(HydAmdContext *ctx, int on) {
+    if (!ctx)
+        return ST_API_ERROR;
+    ctx->bad_per_slot = on != 0;
+    return ST_OK;
+}
+
+/* flags[i] != 0: slot first_slot + i of the current frame held a non-finite float sample.  Waits for the frame (a frame that
+ * outgrew its buffers is rerun first); all zeros while the per-slot mode is off. */
+int hydamd_read_bad_slots(HydAmdContext *ctx, int first_slot, int count, uint32_t *flags) {
+    if (!ctx)
+        return ST_API_ERROR;
+    if (!flags || first_slot < 0 || count < 1 || first_slot + count > ctx->max_slots)
+        return fail(ctx, ST_API_ERROR, "slot range out of bounds");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int st = wait_for_frame(ctx);
+    if (st != ST_OK)
+        return st;
+    HIP_TRY(ctx, hipMemcpy(flags, ctx->bad_slots + first_slot, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return ST_OK;
 }
 

@@ -101,6 +101,8 @@ typedef struct HydkLfJob {
     float *dbg_xyb;          /* optional [3][2048][2048] dumps for parity tests, else NULL */
     float *dbg_dct;
     int32_t *dbg_quant;
+    uint32_t *bad_slot;      /* per-slot outcomes (hydamd_set_bad_sample_per_slot): this slot's flag word, cleared with the frame's
+                              * accumulators — a non-finite float sample sets it and is coded as 0.0; NULL: the launch-wide status bit */
 } HydkLfJob;
 
 /* ---- LF-group coder (the modular sub-stream of the LF coefficients, encoder.c:560-596) ----

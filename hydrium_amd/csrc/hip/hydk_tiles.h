@@ -96,6 +96,25 @@ typedef struct HydkFramesPlan {
 #define HYDK_FRAMES_SIZES_CAP(F, N) ((size_t)(F) * 2u + (size_t)(N) * 65u)
 #define HYDK_FRAMES_PIECES_CAP(F, N) ((size_t)(F) * 5u + (size_t)(N) * 3u)
 
+/* ---- an outcome per image (hydamd_*_set_image_errors): what k_batch_place (assemble_batch.hip) does with a frame whose
+ * context flagged one of its slots, in the words the host build (tiled.c, HYD_TEST_HOOKS) runs too ---- */
+/* is any of the frame's n slot records flagged?  (HydAmdBlobSlot.reserved[0]: hydamd_set_bad_sample_per_slot) */
+HYDK_HD uint32_t hydk_frame_flagged(const HydAmdBlobSlot *rec, uint32_t n) {
+    uint32_t any = 0;
+    for (uint32_t i = 0; i < n; i++)
+        any |= rec[i].reserved[0] != 0;
+    return any;
+}
+/* one piece of a frame that starts at byte `at` of the output, as its preparation left it (counted from the frame's first
+ * byte): moved there — or, the frame skipped, made an EMPTY piece at `at`, which is also where the next frame starts.  The
+ * list keeps its length and its order, its ends stay monotone (what hydk_pieces_word's search needs), no bit is covered. */
+HYDK_HD void hydk_place_piece(HydkPiece *p, uint64_t at, uint32_t skip) {
+    if (skip)
+        *p = hydk_piece(at * 8u, (const void *)0, 0);
+    else
+        p->dst_bit += at * 8u;
+}
+
 typedef struct HydkTileSizes { /* what the preparation of one frame leaves */
     uint32_t head_bits, mid_bits, toc_bits, err;
     uint64_t lfsec_bytes, hfg_bytes; /* several groups: the two padded sections */

@@ -878,7 +878,20 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                         const sample_t sg = ((const sample_t *)job.src[1])[off];
                         const sample_t sb = ((const sample_t *)job.src[2])[off];
                         if (FMT == HYDK_FMT_F32) {
-                            if (!lms_mix_f32((float)sr, (float)sg, (float)sb, job.linear_light, xv[i], yv[i], bv[i]))
+                            float fr = (float)sr, fg = (float)sg, fb = (float)sb;
+                            if (job.bad_slot) {
+                                /* per-slot outcomes: the slot is flagged and the sample coded as 0.0, so that what follows
+                                 * — bias curve, DCT, conversion, tokens — sees an ordinary picture and the slot's frame can
+                                 * neither fail nor rerun the launch group; a finite sample passes through bit for bit */
+                                const bool ir = (__float_as_uint(fr) & 0x7f800000u) == 0x7f800000u;
+                                const bool ig = (__float_as_uint(fg) & 0x7f800000u) == 0x7f800000u;
+                                const bool ib = (__float_as_uint(fb) & 0x7f800000u) == 0x7f800000u;
+                                bad_sample = bad_sample || ir || ig || ib;
+                                fr = ir ? 0.0f : fr;
+                                fg = ig ? 0.0f : fg;
+                                fb = ib ? 0.0f : fb;
+                            }
+                            if (!lms_mix_f32(fr, fg, fb, job.linear_light, xv[i], yv[i], bv[i]))
                                 bad_sample = true;
                         } else {
                             uint32_t rgb[3] = {(uint32_t)sr, (uint32_t)sg, (uint32_t)sb};
@@ -1244,8 +1257,12 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
         if (overflowed)
             atomicOr(status, HYDK_STATUS_TOKENS);
     }
-    if (FMT == HYDK_FMT_F32 && bad_sample)
-        atomicOr(status, HYDK_STATUS_BAD_SAMPLE);
+    if (FMT == HYDK_FMT_F32 && bad_sample) {
+        if (job.bad_slot)
+            atomicOr(job.bad_slot, 1u); /* the slot's own word: the launch-wide status stays clean */
+        else
+            atomicOr(status, HYDK_STATUS_BAD_SAMPLE);
+    }
 }
 
 #include "lf_huffman.h" /* the LF coder's code construction rides in the table kernel's (or the chain kernel's) launch, see below */
@@ -2794,8 +2811,8 @@ __global__ __launch_bounds__(kThreads) void k_export_frame(const HydkLfJob *__re
         }
         if (t < HYDK_MAX_CLUSTERS)
             rec[4 + t] = tab->alphabet[t];
-        if (t < 3)
-            rec[13 + t] = 0;
+        if (t < 3) /* reserved[0]: the slot's bad-sample flag (per-slot outcomes; 0 otherwise) */
+            rec[13 + t] = t == 0 && jobs[b].bad_slot ? *jobs[b].bad_slot : 0u;
         if (t < HYDK_GROUPS_PER_LFG)
             rec[16 + t] = group_bits[(size_t)b * HYDK_GROUPS_PER_LFG + t];
         for (int i = t; i < HYDK_MAX_CLUSTERS * HYDK_ALPHABET; i += kThreads)

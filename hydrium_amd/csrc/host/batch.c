@@ -43,6 +43,9 @@ const uint64_t *hydk_batch_offsets_dev(HydkBatchAsm *a);
 int hydk_batch_wait(HydkBatchAsm *a, void *stream);
 int hydk_batch_result(HydkBatchAsm *a, uint32_t *err, uint64_t *total, const uint64_t **offsets);
 int hydk_batch_read(HydkBatchAsm *a, uint64_t from, uint8_t *dst, size_t n);
+void hydk_batch_set_image_errors(HydkBatchAsm *a, int per_image);
+const uint64_t *hydk_batch_status(HydkBatchAsm *a);
+const uint32_t *hydk_batch_status_dev(HydkBatchAsm *a);
 
 /* k_pieces_copy takes at most 2040 pieces (HYDK_COPY_MAX_PIECES): a batch has F (3 n + 5) of them, and with F n <= 255
  * that is at most 3 x 255 + 5 x 255 = 2040 (frames of one LF group: 8 F) */
@@ -139,6 +142,7 @@ struct HydAmdBatch {
     int in_flight, have_result;
     size_t total;
     uint64_t offsets[BATCH_MAX_SLOTS + 1];
+    uint32_t status[BATCH_MAX_SLOTS]; /* of the finished batch's frames */
     unsigned reruns;
     char err[256];
 };
@@ -343,6 +347,8 @@ static int settle(HydAmdBatch *b) {
         if (!err) {
             b->total = (size_t)total;
             memcpy(b->offsets, offsets, ((size_t)b->frames + 1) * sizeof(uint64_t));
+            for (int f = 0; f < b->frames; f++)
+                b->status[f] = (uint32_t)hydk_batch_status(b->as)[f];
             return HYD_OK;
         }
         if (err & HYDK_ASM_E_NAN)
@@ -407,6 +413,32 @@ HYDRIUM_EXPORT const uint8_t *hydamd_batch_device(HydAmdBatch *b) { return b && 
 
 HYDRIUM_EXPORT const uint64_t *hydamd_batch_offsets_device(HydAmdBatch *b) {
     return b && b->have_result ? hydk_batch_offsets_dev(b->as) : NULL;
+}
+
+/* per-image outcomes, as hydamd_mixed_set_image_errors (mixed.c) */
+HYDRIUM_EXPORT int hydamd_batch_set_image_errors(HydAmdBatch *b, int per_image) {
+    if (!b)
+        return HYD_API_ERROR;
+    if (b->in_flight)
+        return fail(b, HYD_API_ERROR, "a batch is in flight: hydamd_batch_result first", NULL);
+    const int st = hydamd_set_bad_sample_per_slot(b->ctx, per_image != 0);
+    if (st)
+        return fail(b, st, "image errors", hydamd_error(b->ctx));
+    hydk_batch_set_image_errors(b->as, per_image != 0);
+    return HYD_OK;
+}
+
+HYDRIUM_EXPORT int hydamd_batch_image_status(HydAmdBatch *b, uint32_t *status) {
+    if (!b || !b->have_result)
+        return b ? fail(b, HYD_API_ERROR, "no finished batch: hydamd_batch_result first", NULL) : HYD_API_ERROR;
+    if (!status)
+        return fail(b, HYD_API_ERROR, "null output pointer", NULL);
+    memcpy(status, b->status, (size_t)b->frames * sizeof(uint32_t));
+    return HYD_OK;
+}
+
+HYDRIUM_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b) {
+    return b && b->have_result ? hydk_batch_status_dev(b->as) : NULL;
 }
 
 HYDRIUM_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b) { return b ? b->reruns : 0; }

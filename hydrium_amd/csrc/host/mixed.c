@@ -54,6 +54,9 @@ const uint64_t *hydk_batch_offsets_dev(HydkBatchAsm *a);
 int hydk_batch_wait(HydkBatchAsm *a, void *stream);
 int hydk_batch_result(HydkBatchAsm *a, uint32_t *err, uint64_t *total, const uint64_t **offsets);
 int hydk_batch_read(HydkBatchAsm *a, uint64_t from, uint8_t *dst, size_t n);
+void hydk_batch_set_image_errors(HydkBatchAsm *a, int per_image);
+const uint64_t *hydk_batch_status(HydkBatchAsm *a);
+const uint32_t *hydk_batch_status_dev(HydkBatchAsm *a);
 
 /* ---------------------------------------------------------------------------------------------
  * the plan
@@ -315,6 +318,7 @@ struct HydAmdMixed {
     uint64_t fixed;                          /* that plan's share of the output reservation */
     size_t total;
     uint64_t offsets[HYDK_TILE_MAX_FRAMES + 1];
+    uint32_t status[HYDK_TILE_MAX_FRAMES];   /* of the finished batch's images */
     unsigned reruns;
     char err[256];
 };
@@ -469,17 +473,18 @@ static int assemble(HydAmdMixed *m) {
 
 /* the launch group of images of 1..28 LF groups: image after image, an image's LF groups in raster order, each with its
  * own pointers — computed from the image's strides as hydamd_encode_image does — and clipped to the image */
-static int enqueue_several(HydAmdMixed *m, const HydAmdImageDesc *images, int sample_fmt) {
+static int enqueue_several(HydAmdMixed *m, const HydAmdImageDesc *images, const int *sample_fmts) {
     unsigned counts[HYDK_TILE_MAX_FRAMES];
     for (int f = 0; f < m->frames; f++)
         counts[f] = lf_groups_of(images[f].width, images[f].height);
     int st = hydamd_begin_batch_frames(m->ctx, m->frames, counts);
     if (st)
         return fail(m, st, "begin launch group", hydamd_error(m->ctx));
-    const ptrdiff_t ss = sample_fmt == HYD_UINT8 ? 1 : sample_fmt == HYD_UINT16 ? 2 : 4;
     int slot = 0;
     for (int f = 0; f < m->frames; f++) {
         const HydAmdImageDesc *d = &images[f];
+        const int sample_fmt = sample_fmts[f];
+        const ptrdiff_t ss = sample_fmt == HYD_UINT8 ? 1 : sample_fmt == HYD_UINT16 ? 2 : 4;
         const size_t lfx = (d->width + 2047) >> 11, lfy = (d->height + 2047) >> 11;
         for (size_t ty = 0; ty < lfy; ty++)
             for (size_t tx = 0; tx < lfx; tx++, slot++) {
@@ -497,15 +502,15 @@ static int enqueue_several(HydAmdMixed *m, const HydAmdImageDesc *images, int sa
 }
 
 /* the launch group: tiled.c's, every image an LF group of its own size in a slot of its own */
-static int enqueue(HydAmdMixed *m, const HydAmdImageDesc *images, int sample_fmt) {
+static int enqueue(HydAmdMixed *m, const HydAmdImageDesc *images, const int *sample_fmts) {
     if (m->several)
-        return enqueue_several(m, images, sample_fmt);
+        return enqueue_several(m, images, sample_fmts);
     int st = hydamd_begin_batch(m->ctx, 1, m->frames);
     if (st)
         return fail(m, st, "begin launch group", hydamd_error(m->ctx));
     for (int f = 0; f < m->frames; f++) {
         const HydAmdImageDesc *d = &images[f];
-        if ((st = hydamd_encode_lf_group(m->ctx, f, d->src, d->row_stride, d->pixel_stride, sample_fmt, d->width, d->height, 0)) != 0)
+        if ((st = hydamd_encode_lf_group(m->ctx, f, d->src, d->row_stride, d->pixel_stride, sample_fmts[f], d->width, d->height, 0)) != 0)
             return fail(m, st, "image", hydamd_error(m->ctx));
     }
     if ((st = hydamd_finish_frame(m->ctx, m->frames)) != 0)
@@ -513,7 +518,10 @@ static int enqueue(HydAmdMixed *m, const HydAmdImageDesc *images, int sample_fmt
     return assemble(m);
 }
 
-HYDRIUM_EXPORT int hydamd_encode_mixed(HydAmdMixed *m, int frames, const HydAmdImageDesc *images, int sample_fmt) {
+/* every image in its own sample format: the layer underneath takes a format per LF group (the transform launch builds a
+ * format mask, the entropy stage picks its chain form from whether any slot is float), and neither the plan nor its reuse
+ * depends on formats */
+HYDRIUM_EXPORT int hydamd_encode_mixed_formats(HydAmdMixed *m, int frames, const HydAmdImageDesc *images, const int *sample_fmts) {
     if (!m)
         return HYD_API_ERROR;
     if (frames < 1 || frames > m->max_frames)
@@ -539,8 +547,11 @@ HYDRIUM_EXPORT int hydamd_encode_mixed(HydAmdMixed *m, int frames, const HydAmdI
     }
     if (slots > m->max_slots)
         return fail(m, HYD_API_ERROR, "the batch holds more LF groups than the object has slots", NULL);
-    if (sample_fmt != HYD_UINT8 && sample_fmt != HYD_UINT16 && sample_fmt != HYD_FLOAT32)
-        return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
+    if (!sample_fmts)
+        return fail(m, HYD_API_ERROR, "null sample formats", NULL);
+    for (int f = 0; f < frames; f++)
+        if (sample_fmts[f] != HYD_UINT8 && sample_fmts[f] != HYD_UINT16 && sample_fmts[f] != HYD_FLOAT32)
+            return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
     if (m->in_flight)
         return fail(m, HYD_API_ERROR, "a batch is in flight: hydamd_mixed_result first", NULL);
     m->err[0] = 0;
@@ -553,10 +564,31 @@ HYDRIUM_EXPORT int hydamd_encode_mixed(HydAmdMixed *m, int frames, const HydAmdI
     if (st)
         return st;
     m->in_flight = 1;
-    st = enqueue(m, images, sample_fmt);
+    st = enqueue(m, images, sample_fmts);
     if (st)
         drain(m);
     return st;
+}
+
+HYDRIUM_EXPORT int hydamd_encode_mixed(HydAmdMixed *m, int frames, const HydAmdImageDesc *images, int sample_fmt) {
+    int fmts[HYDK_TILE_MAX_FRAMES]; /* one format, repeated (a `frames` out of range is refused before any is read) */
+    for (int f = 0; f < HYDK_TILE_MAX_FRAMES; f++)
+        fmts[f] = sample_fmt;
+    return hydamd_encode_mixed_formats(m, frames, images, fmts);
+}
+
+/* per-image outcomes: the context flags non-finite float samples per slot and codes them as 0.0, the assembly gives a
+ * flagged image no bytes and a status word; off, a NaN fails the batch as hydamd_sync and the view's header report it */
+HYDRIUM_EXPORT int hydamd_mixed_set_image_errors(HydAmdMixed *m, int per_image) {
+    if (!m)
+        return HYD_API_ERROR;
+    if (m->in_flight)
+        return fail(m, HYD_API_ERROR, "a batch is in flight: hydamd_mixed_result first", NULL);
+    const int st = hydamd_set_bad_sample_per_slot(m->ctx, per_image != 0);
+    if (st)
+        return fail(m, st, "image errors", hydamd_error(m->ctx));
+    hydk_batch_set_image_errors(m->as, per_image != 0);
+    return HYD_OK;
 }
 
 /* the batch in flight: wait, let hydamd_sync rerun it if it outgrew a buffer, and see its frames into their files */
@@ -574,6 +606,8 @@ static int settle(HydAmdMixed *m) {
         if (!err) {
             m->total = (size_t)total;
             memcpy(m->offsets, offsets, ((size_t)m->frames + 1) * sizeof(uint64_t));
+            for (int f = 0; f < m->frames; f++)
+                m->status[f] = (uint32_t)hydk_batch_status(m->as)[f];
             return HYD_OK;
         }
         if (err & HYDK_ASM_E_NAN)
@@ -640,6 +674,19 @@ HYDRIUM_EXPORT const uint64_t *hydamd_mixed_offsets_device(HydAmdMixed *m) {
     return m && m->have_result ? hydk_batch_offsets_dev(m->as) : NULL;
 }
 
+HYDRIUM_EXPORT int hydamd_mixed_image_status(HydAmdMixed *m, uint32_t *status) {
+    if (!m || !m->have_result)
+        return m ? fail(m, HYD_API_ERROR, "no finished batch: hydamd_mixed_result first", NULL) : HYD_API_ERROR;
+    if (!status)
+        return fail(m, HYD_API_ERROR, "null output pointer", NULL);
+    memcpy(status, m->status, (size_t)m->frames * sizeof(uint32_t));
+    return HYD_OK;
+}
+
+HYDRIUM_EXPORT const uint32_t *hydamd_mixed_image_status_device(HydAmdMixed *m) {
+    return m && m->have_result ? hydk_batch_status_dev(m->as) : NULL;
+}
+
 HYDRIUM_EXPORT unsigned hydamd_mixed_overflow_reruns(HydAmdMixed *m) { return m ? m->reruns : 0; }
 
 /* ---------------------------------------------------------------------------------------------
@@ -682,6 +729,43 @@ HYDT_EXPORT int hydt_mixed_from_streams(size_t n, const uint32_t *widths, const 
      * planner never writes a plan that trips them, and no test does) */
     ret = hydt_layout_from_streams(plan, frames, (const HydkTileShape *)(plan + hp->shapes_off), n, lf, freq, alphabet, group_bits,
                                        max_alphabet, payload, payload_len, frame_offsets, out, out_len, e);
+    free(plan);
+    return ret;
+}
+
+/* the same batch with an outcome per image: flags[f] != 0 stands for what the context leaves in image f's slot record when
+ * the picture held a non-finite sample; status [n], piece_bits [n x HYDK_TILE_PIECES][2] (dst_bit, nbits) as placed */
+HYDT_EXPORT int hydt_mixed_from_streams_skip(size_t n, const uint32_t *widths, const uint32_t *heights, const HydAmdLfStream *lf,
+                                             const uint32_t *freq, const uint32_t *alphabet, const uint32_t *group_bits,
+                                             const uint32_t *max_alphabet, const uint8_t *payload, size_t payload_len,
+                                             const uint32_t *flags, uint64_t *frame_offsets, uint32_t *status, uint64_t *piece_bits,
+                                             uint8_t **out, size_t *out_len, const char **err) {
+    static const char *none = NULL;
+    const char **e = err ? err : &none;
+    MixedSize sz[HYDK_TILE_MAX_FRAMES];
+    uint8_t *plan = NULL;
+    size_t plan_len = 0;
+    uint64_t fixed = 0;
+    *e = NULL;
+    if (n < 1 || n > HYDK_TILE_MAX_FRAMES) {
+        *e = "between 1 and 255 images";
+        return HYD_API_ERROR;
+    }
+    for (size_t f = 0; f < n; f++) {
+        if (!widths[f] || !heights[f] || widths[f] > MIXED_MAX_SIDE || heights[f] > MIXED_MAX_SIDE) {
+            *e = "every image of a mixed batch must be between 1 and 2048 pixels in each direction";
+            return HYD_API_ERROR;
+        }
+        sz[f].w = widths[f];
+        sz[f].h = heights[f];
+    }
+    int ret = build_plan((int)n, sz, 0, &plan, &plan_len, &fixed, e);
+    if (ret)
+        return ret;
+    const HydkMixedPlan *hp = (const HydkMixedPlan *)plan;
+    ret = hydt_layout_from_streams_skip(plan, (const HydkTileFrame *)(plan + hp->frames_off), (const HydkTileShape *)(plan + hp->shapes_off),
+                                        n, lf, freq, alphabet, group_bits, max_alphabet, payload, payload_len, flags, frame_offsets, status,
+                                        piece_bits, out, out_len, e);
     free(plan);
     return ret;
 }

@@ -43,6 +43,12 @@ int hydt_layout_from_streams(const uint8_t *plan, const struct HydkTileFrame *fr
                              const struct HydAmdLfStream *lf, const uint32_t *freq, const uint32_t *alphabet, const uint32_t *group_bits,
                              const uint32_t *max_alphabet, const uint8_t *payload, size_t payload_len, uint64_t *frame_offsets,
                              uint8_t **out, size_t *out_len, const char **err);
+/* the same with an outcome per image: flags[f] as the slot record would carry it; a flagged frame yields no bytes */
+int hydt_layout_from_streams_skip(const uint8_t *plan, const struct HydkTileFrame *frames, const struct HydkTileShape *shapes, size_t nframes,
+                                  const struct HydAmdLfStream *lf, const uint32_t *freq, const uint32_t *alphabet, const uint32_t *group_bits,
+                                  const uint32_t *max_alphabet, const uint8_t *payload, size_t payload_len, const uint32_t *flags,
+                                  uint64_t *frame_offsets, uint32_t *status, uint64_t *piece_bits, uint8_t **out, size_t *out_len,
+                                  const char **err);
 #endif
 
 #endif /* HYD_PLANBUF_H_ */

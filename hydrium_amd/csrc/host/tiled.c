@@ -463,10 +463,15 @@ HYDRIUM_EXPORT size_t hydamd_tiled_device_bytes(HydAmdTiled *t) { return t ? (si
 #define HYDT_EXPORT __attribute__((visibility("default")))
 /* frame f of `plan` laid out by frames[f] and shapes[frames[f].shape]: hydk_tile_prepare, hydk_tile_pieces and the shared
  * composer, frame by frame (planbuf.h; also what mixed.c's hook runs on its own plan) */
-int hydt_layout_from_streams(const uint8_t *plan, const HydkTileFrame *frames, const HydkTileShape *shapes, size_t nframes,
-                             const HydAmdLfStream *lf, const uint32_t *freq, const uint32_t *alphabet, const uint32_t *group_bits,
-                             const uint32_t *max_alphabet, const uint8_t *payload, size_t payload_len, uint64_t *frame_offsets,
-                             uint8_t **out, size_t *out_len, const char **e) {
+/* ... with an outcome per image, as k_batch_place arrives at it (assemble_batch.hip): flags[f] is what the context's export
+ * would leave in frame f's slot record (HydAmdBlobSlot.reserved[0]); every frame is prepared and its pieces counted from
+ * its own first byte, then a flagged frame counts 0 bytes and each piece is placed by hydk_place_piece.  status[f] (optional):
+ * HYDAMD_IMAGE_BAD_SAMPLE or 0; piece_bits (optional): [nframes x HYDK_TILE_PIECES][2] dst_bit and nbits of the placed list. */
+int hydt_layout_from_streams_skip(const uint8_t *plan, const HydkTileFrame *frames, const HydkTileShape *shapes, size_t nframes,
+                                  const HydAmdLfStream *lf, const uint32_t *freq, const uint32_t *alphabet, const uint32_t *group_bits,
+                                  const uint32_t *max_alphabet, const uint8_t *payload, size_t payload_len, const uint32_t *flags,
+                                  uint64_t *frame_offsets, uint32_t *status, uint64_t *piece_bits, uint8_t **out, size_t *out_len,
+                                  const char **e) {
     int ret = HYD_OK;
     HydAmdBlobSlot *rec = calloc(nframes, sizeof(*rec));
     uint32_t *head = calloc(nframes * HYDK_TILE_HEAD_WORDS, 4), *mid = calloc(nframes * HYDK_TILE_MID_WORDS, 4),
@@ -500,6 +505,7 @@ int hydt_layout_from_streams(const uint8_t *plan, const HydkTileFrame *frames, c
             r->lf.run_pairs = lf[f].run_pairs;
             r->lf.bit_count = (uint32_t)lf[f].bit_count;
             r->lf.offset = (uint32_t)lf_at;
+            r->reserved[0] = flags ? flags[f] : 0u;
             const size_t nb = ((size_t)lf[f].bit_count + 7) >> 3;
             if (nb)
                 memcpy(lf_packed + lf_at, lf[f].bits, nb);
@@ -512,10 +518,15 @@ int hydt_layout_from_streams(const uint8_t *plan, const HydkTileFrame *frames, c
                 break;
             }
             hydk_tile_pieces(plan, &frames[f], sh, &sizes[f], r, head + f * HYDK_TILE_HEAD_WORDS, mid + f * HYDK_TILE_MID_WORDS,
-                             toc + f * HYDK_TILE_TOC_WORDS, lf_packed + lf_at, hf + hf_at, at, pieces + f * HYDK_TILE_PIECES);
+                             toc + f * HYDK_TILE_TOC_WORDS, lf_packed + lf_at, hf + hf_at, 0, pieces + f * HYDK_TILE_PIECES);
+            const uint32_t skip = hydk_frame_flagged(r, 1);
+            for (uint32_t i = 0; i < HYDK_TILE_PIECES; i++)
+                hydk_place_piece(&pieces[f * HYDK_TILE_PIECES + i], at, skip);
             if (frame_offsets)
                 frame_offsets[f] = at;
-            at += sizes[f].frame_bytes;
+            if (status)
+                status[f] = skip ? HYDAMD_IMAGE_BAD_SAMPLE : 0u;
+            at += skip ? 0 : sizes[f].frame_bytes;
             lf_at += (nb + 3) & ~(size_t)3;
             hf_at += sizes[f].hf_bytes;
         }
@@ -523,8 +534,13 @@ int hydt_layout_from_streams(const uint8_t *plan, const HydkTileFrame *frames, c
             if (frame_offsets)
                 frame_offsets[nframes] = at;
             const uint32_t np = (uint32_t)(nframes * HYDK_TILE_PIECES);
-            for (uint32_t i = 0; i < np; i++)
+            for (uint32_t i = 0; i < np; i++) {
                 ends[i] = pieces[i].dst_bit + pieces[i].nbits;
+                if (piece_bits) {
+                    piece_bits[2 * i] = pieces[i].dst_bit;
+                    piece_bits[2 * i + 1] = pieces[i].nbits;
+                }
+            }
             file = malloc((size_t)at + 4);
             if (!file) {
                 ret = HYD_NOMEM;
@@ -547,6 +563,14 @@ int hydt_layout_from_streams(const uint8_t *plan, const HydkTileFrame *frames, c
     free(lf_packed);
     free(hf);
     return ret;
+}
+
+int hydt_layout_from_streams(const uint8_t *plan, const HydkTileFrame *frames, const HydkTileShape *shapes, size_t nframes,
+                             const HydAmdLfStream *lf, const uint32_t *freq, const uint32_t *alphabet, const uint32_t *group_bits,
+                             const uint32_t *max_alphabet, const uint8_t *payload, size_t payload_len, uint64_t *frame_offsets,
+                             uint8_t **out, size_t *out_len, const char **e) {
+    return hydt_layout_from_streams_skip(plan, frames, shapes, nframes, lf, freq, alphabet, group_bits, max_alphabet, payload, payload_len,
+                                         NULL, frame_offsets, NULL, NULL, out, out_len, e);
 }
 
 HYDT_EXPORT int hydt_tiles_from_streams(const HYDImageMetadata *md, size_t nframes, const HydAmdLfStream *lf, const uint32_t *freq,

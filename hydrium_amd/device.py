@@ -83,6 +83,10 @@ def dll(path: Optional[str] = None):
         d.hydamd_run_transform.argtypes = [vp, i]
         d.hydamd_run_entropy.argtypes = [vp, i]
         d.hydamd_read_alphabet_max.argtypes = [vp, i, C.POINTER(C.c_uint32)]
+        d.hydamd_set_bad_sample_per_slot.restype = i
+        d.hydamd_set_bad_sample_per_slot.argtypes = [vp, i]
+        d.hydamd_read_bad_slots.restype = i
+        d.hydamd_read_bad_slots.argtypes = [vp, i, i, C.POINTER(C.c_uint32)]
         d.hydamd_set_alphabet_floor.argtypes = [vp, C.c_uint32]
         d.hydamd_alphabet_max_device.restype = vp
         d.hydamd_alphabet_max_device.argtypes = [vp]
@@ -201,6 +205,15 @@ def dll(path: Optional[str] = None):
         d.hydamd_batch_read.argtypes = [vp, i, C.POINTER(C.c_uint8), sz]
         d.hydamd_batch_overflow_reruns.restype = u
         d.hydamd_batch_overflow_reruns.argtypes = [vp]
+        for obj in ("batch", "mixed"):
+            f = getattr(d, f"hydamd_{obj}_set_image_errors")
+            f.restype, f.argtypes = i, [vp, i]
+            f = getattr(d, f"hydamd_{obj}_image_status")
+            f.restype, f.argtypes = i, [vp, C.POINTER(C.c_uint32)]
+            f = getattr(d, f"hydamd_{obj}_image_status_device")
+            f.restype, f.argtypes = C.POINTER(C.c_uint32), [vp]
+        d.hydamd_encode_mixed_formats.restype = i
+        d.hydamd_encode_mixed_formats.argtypes = [vp, i, C.POINTER(HydAmdImageDesc), C.POINTER(i)]
         d.hydamd_mixed_create.restype = vp
         d.hydamd_mixed_create.argtypes = [i, i, i, C.POINTER(i)]
         d.hydamd_mixed_create_slots.restype = vp
@@ -285,6 +298,11 @@ class DeviceContext:
     def begin_frame(self, num_presets: int):
         self._ck(self.d.hydamd_begin_frame(self.h, num_presets))
 
+    def begin_batch(self, num_presets: int, frames: int):
+        """One launch group of `frames` independent images of `num_presets` LF groups each, image k in slots
+        k * num_presets ...; then encode_lf_group per slot and finish_frame."""
+        self._ck(self.d.hydamd_begin_batch(self.h, num_presets, frames))
+
     def begin_batch_frames(self, lf_groups: Sequence[int]):
         """One launch group of len(lf_groups) independent images, image k of lf_groups[k] LF groups (1..28) in the slots
         behind image k - 1's; then encode_lf_group per slot (preset: the raster index inside the image) and finish_frame."""
@@ -310,6 +328,17 @@ class DeviceContext:
         v = C.c_uint32(0)
         self._ck(self.d.hydamd_read_alphabet_max(self.h, slot, C.byref(v)))
         return v.value
+
+    def set_bad_sample_per_slot(self, on: bool):
+        """A non-finite float sample flags its SLOT (read_bad_slots, the slot's record of a view) and is coded as 0.0,
+        instead of failing the launch group through the status word.  For LF groups recorded after the call."""
+        self._ck(self.d.hydamd_set_bad_sample_per_slot(self.h, int(bool(on))))
+
+    def read_bad_slots(self, count: int, first: int = 0) -> np.ndarray:
+        """uint32[count], non-zero where the slot held a non-finite float sample; waits for the frame."""
+        out = np.zeros(count, np.uint32)
+        self._ck(self.d.hydamd_read_bad_slots(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
     def set_alphabet_floor(self, floor: int):
         self._ck(self.d.hydamd_set_alphabet_floor(self.h, floor))
@@ -848,7 +877,7 @@ class FrameBatch:
     their offsets beside it."""
 
     def __init__(self, width: int, height: int, max_frames: int, linear_light: int = 0, device: int = 0,
-                 icc: Optional[bytes] = None):
+                 icc: Optional[bytes] = None, image_errors: bool = False):
         self.d = dll()
         md = api.HYDImageMetadata(width, height, int(linear_light), -1, -1)
         st = C.c_int(0)
@@ -858,6 +887,8 @@ class FrameBatch:
         self.width, self.height, self.max_frames = width, height, max_frames
         self.frames = 0
         self._keep = None
+        if image_errors:
+            self.set_image_errors(True)
 
     def close(self):
         if self.h:
@@ -939,8 +970,74 @@ class FrameBatch:
     def offsets_device_ptr(self) -> int:
         return C.cast(self.d.hydamd_batch_offsets_device(self.h), C.c_void_p).value or 0
 
+    def set_image_errors(self, on: bool):
+        """An outcome per image (status()): an image with a non-finite float sample yields no bytes, the others their
+        files; off, such a sample fails the whole batch.  Not while a batch is in flight."""
+        self._ck(self.d.hydamd_batch_set_image_errors(self.h, int(bool(on))))
+
+    def status(self) -> np.ndarray:
+        """uint32[frames]: 0 a file, IMAGE_BAD_SAMPLE a non-finite sample and no bytes."""
+        self.result()
+        out = np.zeros(max(self.frames, 1), np.uint32)
+        self._ck(self.d.hydamd_batch_image_status(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[: self.frames]
+
+    def status_device_ptr(self) -> int:
+        return C.cast(self.d.hydamd_batch_image_status_device(self.h), C.c_void_p).value or 0
+
     def overflow_reruns(self) -> int:
         return int(self.d.hydamd_batch_overflow_reruns(self.h))
+
+
+IMAGE_BAD_SAMPLE = 1  # include/hydrium_amd.h, HYDAMD_IMAGE_BAD_SAMPLE
+
+
+def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
+    """MixedBatch.encode's reading of its arguments, without a device: (HydAmdImageDesc array, [format of image k]).
+
+    sample_fmts None: one format for all — sample_fmt, else the tensors' common dtype (ValueError when they differ, or
+    when address tuples come without sample_fmt).  "each": every tensor's own dtype (address tuples: sample_fmt).  A
+    sequence: image k's format, which a tensor's dtype must agree with (a value that is no format goes through to the
+    library, which refuses the batch)."""
+    if sample_fmts is not None and not isinstance(sample_fmts, str):
+        sample_fmts = [int(f) for f in sample_fmts]
+        if len(sample_fmts) != len(imgs):
+            raise ValueError("sample_fmts names one format per image")
+    elif sample_fmts is not None and sample_fmts != "each":
+        raise ValueError('sample_fmts is None, "each" or one format per image')
+    descs = (HydAmdImageDesc * max(len(imgs), 1))()
+    fmts = []
+    for k, img in enumerate(imgs):
+        given = sample_fmts[k] if isinstance(sample_fmts, list) else sample_fmt
+        if hasattr(img, "data_ptr"):
+            isz = img.element_size()
+            ptrs = [img.data_ptr() + c * isz for c in range(3)]
+            rs, ps, (h, w) = img.stride(0), img.stride(1), img.shape[:2]
+            fmt = {1: 0, 2: 1, 4: 2}[isz]
+        elif hasattr(img[0], "data_ptr"):  # planes keep their shape: the size is theirs, never a bare pointer's
+            ptrs = [p.data_ptr() for p in img]
+            rs, ps, (h, w) = img[0].stride(0), img[0].stride(1), img[0].shape[:2]
+            if any(tuple(p.shape[:2]) != (h, w) or (p.stride(0), p.stride(1)) != (rs, ps) for p in img):
+                raise ValueError("the three planes of an image share one shape and one layout")
+            fmt = {1: 0, 2: 1, 4: 2}[img[0].element_size()]
+        else:
+            ptrs, rs, ps, w, h = img
+            ptrs = [int(p) if p is not None else None for p in ptrs]
+            if given is None:
+                raise ValueError("device addresses need sample_fmt")
+            fmt = given
+        if sample_fmts is None:
+            if sample_fmt is None:
+                sample_fmt = fmt
+            elif fmt != sample_fmt:
+                raise ValueError("the images of a batch share one sample format")
+        elif isinstance(sample_fmts, list) and fmt != given:
+            if given in (0, 1, 2):
+                raise ValueError("sample_fmts disagrees with a tensor's dtype")
+            fmt = given  # not a format at all: the library refuses it (HYD_API_ERROR), nothing is enqueued
+        fmts.append(fmt)
+        descs[k] = HydAmdImageDesc((C.c_void_p * 3)(*ptrs), int(rs), int(ps), int(w), int(h))
+    return descs, fmts
 
 
 class MixedBatch:
@@ -952,7 +1049,8 @@ class MixedBatch:
     image may then hold up to 28 LF groups of 2048 x 2048 pixels, a batch up to max_lf_groups of them in all
     (hydamd_mixed_create_slots)."""
 
-    def __init__(self, max_frames: int = 0, linear_light: int = 0, device: int = 0, max_lf_groups: Optional[int] = None):
+    def __init__(self, max_frames: int = 0, linear_light: int = 0, device: int = 0, max_lf_groups: Optional[int] = None,
+                 image_errors: bool = False):
         self.d = dll()
         st = C.c_int(0)
         if max_lf_groups is None:
@@ -965,6 +1063,8 @@ class MixedBatch:
         self.max_lf_groups = max_lf_groups
         self.frames = 0
         self._keep = None
+        if image_errors:
+            self.set_image_errors(True)
 
     def close(self):
         if self.h:
@@ -982,38 +1082,19 @@ class MixedBatch:
         if code != 0:
             raise DeviceError(code, (self.d.hydamd_mixed_error(self.h) or b"").decode())
 
-    def encode(self, imgs, sample_fmt: Optional[int] = None):
+    def encode(self, imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
         """imgs: one entry per image, each of its own size and layout — an interleaved (H, W, C >= 3) torch tensor on the
         object's device (any row pitch; C > 3: the first three channels, pixel stride C), a triple of (H, W) plane
         tensors, or (ptrs, row_stride, pixel_stride, width, height) with three device addresses and strides in samples
-        (then sample_fmt is the caller's).  One sample format per call.  Asynchronous: the pixels must stay alive and
-        unchanged until result()."""
-        descs = (HydAmdImageDesc * max(len(imgs), 1))()
-        for k, img in enumerate(imgs):
-            if hasattr(img, "data_ptr"):
-                isz = img.element_size()
-                ptrs = [img.data_ptr() + c * isz for c in range(3)]
-                rs, ps, (h, w) = img.stride(0), img.stride(1), img.shape[:2]
-                fmt = {1: 0, 2: 1, 4: 2}[isz]
-            elif hasattr(img[0], "data_ptr"):  # planes keep their shape: the size is theirs, never a bare pointer's
-                ptrs = [p.data_ptr() for p in img]
-                rs, ps, (h, w) = img[0].stride(0), img[0].stride(1), img[0].shape[:2]
-                if any(tuple(p.shape[:2]) != (h, w) or (p.stride(0), p.stride(1)) != (rs, ps) for p in img):
-                    raise ValueError("the three planes of an image share one shape and one layout")
-                fmt = {1: 0, 2: 1, 4: 2}[img[0].element_size()]
-            else:
-                ptrs, rs, ps, w, h = img
-                ptrs = [int(p) if p is not None else None for p in ptrs]
-                if sample_fmt is None:
-                    raise ValueError("device addresses need sample_fmt")
-                fmt = sample_fmt
-            if sample_fmt is None:
-                sample_fmt = fmt
-            elif fmt != sample_fmt:
-                raise ValueError("the images of a batch share one sample format")
-            descs[k] = HydAmdImageDesc((C.c_void_p * 3)(*ptrs), int(rs), int(ps), int(w), int(h))
+        (then sample_fmt is the caller's).  One sample format per call, unless sample_fmts says otherwise: "each" takes
+        every tensor's own dtype, a list names image k's format (0 / 1 / 2: 8-bit, 16-bit, float; what address tuples
+        need).  Asynchronous: the pixels must stay alive and unchanged until result()."""
+        descs, fmts = mixed_descriptors(imgs, sample_fmt, sample_fmts)
         self._keep = imgs
-        self._ck(self.d.hydamd_encode_mixed(self.h, len(imgs), descs, sample_fmt if sample_fmt is not None else -1))
+        if sample_fmts is None:
+            self._ck(self.d.hydamd_encode_mixed(self.h, len(imgs), descs, fmts[0] if fmts else -1))
+        else:
+            self._ck(self.d.hydamd_encode_mixed_formats(self.h, len(imgs), descs, (C.c_int * max(len(fmts), 1))(*fmts)))
         self.frames = len(imgs)
 
     def result(self) -> int:
@@ -1050,6 +1131,21 @@ class MixedBatch:
 
     def offsets_device_ptr(self) -> int:
         return C.cast(self.d.hydamd_mixed_offsets_device(self.h), C.c_void_p).value or 0
+
+    def set_image_errors(self, on: bool):
+        """An outcome per image (status()): an image with a non-finite float sample yields no bytes, the others their
+        files; off, such a sample fails the whole batch.  Not while a batch is in flight."""
+        self._ck(self.d.hydamd_mixed_set_image_errors(self.h, int(bool(on))))
+
+    def status(self) -> np.ndarray:
+        """uint32[frames]: 0 a file, IMAGE_BAD_SAMPLE a non-finite sample and no bytes."""
+        self.result()
+        out = np.zeros(max(self.frames, 1), np.uint32)
+        self._ck(self.d.hydamd_mixed_image_status(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[: self.frames]
+
+    def status_device_ptr(self) -> int:
+        return C.cast(self.d.hydamd_mixed_image_status_device(self.h), C.c_void_p).value or 0
 
     def overflow_reruns(self) -> int:
         return int(self.d.hydamd_mixed_overflow_reruns(self.h))

@@ -180,6 +180,16 @@ HYDAMD_EXPORT int hydamd_finish_frame(HydAmdContext *ctx, int num_slots);
  * sample -> HYD_API_ERROR, table construction failure -> HYD_INTERNAL_ERROR). */
 HYDAMD_EXPORT int hydamd_sync(HydAmdContext *ctx);
 
+/* Where a non-finite float sample is recorded.  Off (default): bit 0 of the launch-wide status word — hydamd_sync fails with
+ * "Invalid NaN Float" and a view's header carries the bit: the LF group cannot be named.  On: one flag per SLOT, cleared and
+ * rerun with the frame's other accumulators; the sample is coded as 0.0 (the slot's results are those of an ordinary picture
+ * and can neither fail nor rerun its launch group), the status word and the view's header stay clean and hydamd_sync returns
+ * HYD_OK.  The switch holds for LF groups recorded after the call: set it between frames.
+ * hydamd_read_bad_slots waits for the frame and copies `count` flags from slot `first_slot` on (non-zero: flagged; all zero
+ * while the switch is off); in a view the flag travels in each slot's record (HydAmdBlobSlot.reserved[0]). */
+HYDAMD_EXPORT int hydamd_set_bad_sample_per_slot(HydAmdContext *ctx, int on);
+HYDAMD_EXPORT int hydamd_read_bad_slots(HydAmdContext *ctx, int first_slot, int count, uint32_t *flags);
+
 /* ---- results; valid after hydamd_sync() ---- */
 HYDAMD_EXPORT size_t hydamd_payload_size(HydAmdContext *ctx);
 /* The device pointer may change when a frame outgrows its buffers (see below): fetch it after hydamd_sync(). */
@@ -326,7 +336,7 @@ typedef struct HydAmdBlobSlot {
     uint32_t preset;                /* = raster id of the LF group in its frame */
     uint32_t running_max_alphabet, log_alphabet_size, table_error;
     uint32_t alphabet[HYDAMD_MAX_CLUSTERS];
-    uint32_t reserved[3];
+    uint32_t reserved[3];           /* [0]: non-zero when the slot held a non-finite float sample (hydamd_set_bad_sample_per_slot on; else 0) */
     uint32_t group_bits[HYDAMD_GROUPS_PER_LFG];
     uint32_t freq[HYDAMD_MAX_CLUSTERS][HYDAMD_ALPHABET];
     HydAmdLfInfo lf;                /* lf.offset is relative to the blob's LF byte string */
@@ -559,10 +569,20 @@ HYDAMD_EXPORT size_t hydamd_tiled_device_bytes(HydAmdTiled *t);
  *                                the output buffer, for max_frames, before it enqueues anything.)
  *   hydamd_batch_result          waits; *total_bytes = bytes of all files.  A batch that outgrew the context's buffers is
  *                                rerun inside hydamd_sync and exported and assembled again first; the output buffer is
- *                                sized from the context's capacities (never HYD_NEED_MORE_OUTPUT).  A non-finite float
- *                                sample ANYWHERE fails the WHOLE batch — HYD_API_ERROR "Invalid NaN Float"; the context's
- *                                status word belongs to the launch group, so the frame cannot be named.  After a failure
- *                                the stream is drained and the object stays usable.
+ *                                sized from the context's capacities (never HYD_NEED_MORE_OUTPUT).  By default a non-finite
+ *                                float sample ANYWHERE fails the WHOLE batch — HYD_API_ERROR "Invalid NaN Float" (see
+ *                                hydamd_batch_set_image_errors).  After a failure the stream is drained and the object
+ *                                stays usable.
+ *   hydamd_batch_set_image_errors  per_image != 0: an outcome per image instead.  The context records non-finite samples
+ *                                per slot (hydamd_set_bad_sample_per_slot) and the assembly gives an image ANY of whose LF
+ *                                groups is flagged no bytes: hydamd_batch_result returns HYD_OK, *total_bytes counts the
+ *                                delivered files only (0 when every image is flagged), offsets[k + 1] == offsets[k] and
+ *                                hydamd_batch_read copies 0 bytes for such an image, and the files on both sides of it
+ *                                still meet at byte granularity.  Every other error fails the batch as before.  0
+ *                                (default): as above.  HYD_API_ERROR while a batch is in flight.
+ *   hydamd_batch_image_status    after hydamd_batch_result: status[k] for the batch's `frames` images, 0 = a file,
+ *                                HYDAMD_IMAGE_BAD_SAMPLE = a non-finite sample, no bytes.  All zeros with the switch off.
+ *   hydamd_batch_image_status_device  the same words (uint32, `frames` of them) in device memory, beside the offsets table.
  *   hydamd_batch_offsets         offsets[k] .. offsets[k + 1] bound file k; offsets[0] = 0, offsets[frames] = total.
  *   hydamd_batch_device,         the files and the same table (frames + 1 entries) in device memory, for a consumer
  *   hydamd_batch_offsets_device  that never leaves the GPU.  Everything is valid until the object's next hydamd_encode_batch.
@@ -585,6 +605,10 @@ HYDAMD_EXPORT const uint8_t *hydamd_batch_device(HydAmdBatch *b);
 HYDAMD_EXPORT const uint64_t *hydamd_batch_offsets_device(HydAmdBatch *b);
 HYDAMD_EXPORT int hydamd_batch_read(HydAmdBatch *b, int frame, uint8_t *dst, size_t capacity);
 HYDAMD_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b);
+#define HYDAMD_IMAGE_BAD_SAMPLE 1u
+HYDAMD_EXPORT int hydamd_batch_set_image_errors(HydAmdBatch *b, int per_image);
+HYDAMD_EXPORT int hydamd_batch_image_status(HydAmdBatch *b, uint32_t *status);
+HYDAMD_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b);
 
 /*
  * A batch of one-frame images EACH OF ITS OWN SIZE whose pixels already sit in HBM, every one a finished FILE, built on
@@ -615,15 +639,25 @@ HYDAMD_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b);
  *   hydamd_encode_mixed          `frames` <= max_frames images: images[k].src are image k's channel pointers (device
  *                                memory, its first pixel), row_stride / pixel_stride in samples as hyd_send_tile's,
  *                                width and height 1..2048 (hydamd_mixed_create_slots: at least 1, at most 28 LF groups of
- *                                2048 x 2048, the batch's LF groups at most max_lf_groups); one sample_fmt for the whole call.  Enqueues the batch and
+ *                                2048 x 2048, the batch's LF groups at most max_lf_groups); one sample_fmt for the whole call
+ *                                (hydamd_encode_mixed_formats: one per image).  Enqueues the batch and
  *                                its assembly and returns; the pixels stay borrowed until hydamd_mixed_result, the
  *                                descriptors only for the call.  The output buffer is sized before anything is
  *                                enqueued, from the batch's plan and the context's capacities.
+ *   hydamd_encode_mixed_formats  the same with image k's samples in sample_fmts[k] (HYD_UINT8 / HYD_UINT16 / HYD_FLOAT32):
+ *                                8-bit, 16-bit and float pictures side by side in one launch group, every file what the
+ *                                reference writes for that picture in its format.  A bad entry is HYD_API_ERROR "Invalid
+ *                                Sample Format" with nothing enqueued.  The plan and its reuse depend on sizes only.
  *   hydamd_mixed_result          waits; *total_bytes = bytes of all files.  A batch that outgrew the context's buffers is
  *                                rerun inside hydamd_sync and exported and assembled again first (never
- *                                HYD_NEED_MORE_OUTPUT).  A non-finite float sample ANYWHERE fails the WHOLE batch —
- *                                HYD_API_ERROR "Invalid NaN Float"; the image cannot be named.  After a failure the
- *                                stream is drained and the object stays usable.
+ *                                HYD_NEED_MORE_OUTPUT).  By default a non-finite float sample ANYWHERE fails the WHOLE
+ *                                batch — HYD_API_ERROR "Invalid NaN Float".  After a failure the stream is drained and
+ *                                the object stays usable.
+ *   hydamd_mixed_set_image_errors, hydamd_mixed_image_status, hydamd_mixed_image_status_device
+ *                                an outcome per image, exactly as hydamd_batch_set_image_errors and its companions: an
+ *                                image with a non-finite sample in ANY of its LF groups yields no bytes and status
+ *                                HYDAMD_IMAGE_BAD_SAMPLE, the others their files; the rerun of a batch that outgrew its
+ *                                buffers arrives at the same outcomes.
  *   hydamd_mixed_offsets         offsets[k] .. offsets[k + 1] bound file k; offsets[0] = 0, offsets[frames] = total.
  *   hydamd_mixed_device,         the files and the same table (frames + 1 entries) in device memory.  Everything is
  *   hydamd_mixed_offsets_device  valid until the object's next hydamd_encode_mixed.
@@ -636,7 +670,8 @@ HYDAMD_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b);
  * queue (scripts/mixed_batch_probe.py keeps four).
  * OUT OF SCOPE: images of more than 28 LF groups (other cluster schemes would need chain launches per cluster count: such
  * images go through one hydamd_batch_* object per shape, or hydamd_encode_image); an ICC profile (it would sit in
- * every frame's prefix); sample formats mixed within one call; naming the image that held a NaN; several devices per object;
+ * every frame's prefix); several devices per object; outcomes per image for hydamd_tiled_* and hydamd_multi_* (one image, one
+ * outcome);
  * closing the throughput gap to the padded-classes upper reference that profiles/mixed_batch.txt records.
  */
 typedef struct HydAmdImageDesc {
@@ -650,12 +685,16 @@ HYDAMD_EXPORT HydAmdMixed *hydamd_mixed_create_slots(int device, int max_frames,
 HYDAMD_EXPORT void hydamd_mixed_destroy(HydAmdMixed *m);
 HYDAMD_EXPORT const char *hydamd_mixed_error(HydAmdMixed *m);
 HYDAMD_EXPORT int hydamd_encode_mixed(HydAmdMixed *m, int frames, const HydAmdImageDesc *images, int sample_fmt);
+HYDAMD_EXPORT int hydamd_encode_mixed_formats(HydAmdMixed *m, int frames, const HydAmdImageDesc *images, const int *sample_fmts);
 HYDAMD_EXPORT int hydamd_mixed_result(HydAmdMixed *m, size_t *total_bytes);
 HYDAMD_EXPORT int hydamd_mixed_offsets(HydAmdMixed *m, uint64_t *offsets);
 HYDAMD_EXPORT const uint8_t *hydamd_mixed_device(HydAmdMixed *m);
 HYDAMD_EXPORT const uint64_t *hydamd_mixed_offsets_device(HydAmdMixed *m);
 HYDAMD_EXPORT int hydamd_mixed_read(HydAmdMixed *m, int frame, uint8_t *dst, size_t capacity);
 HYDAMD_EXPORT unsigned hydamd_mixed_overflow_reruns(HydAmdMixed *m);
+HYDAMD_EXPORT int hydamd_mixed_set_image_errors(HydAmdMixed *m, int per_image);
+HYDAMD_EXPORT int hydamd_mixed_image_status(HydAmdMixed *m, uint32_t *status);
+HYDAMD_EXPORT const uint32_t *hydamd_mixed_image_status_device(HydAmdMixed *m);
 
 #ifdef __cplusplus
 }
