@@ -2600,6 +2600,32 @@ int hydamd_read_dc(HydAmdContext *ctx, int slot, int32_t *dst, size_t vbw, size_
     return ST_OK;
 }
 
+#ifdef HYD_TEST_HOOKS
+/* Test hook, the mirror of hydamd_read_dc (probe flavour only, not declared in include/): LF ints of the caller's choice
+ * into a slot whose transform kernel is enqueued, planes X, Y, B of vbh x vbw each — how crafted residual streams reach
+ * the LF coder's kernels (tests/test_gpu_lf_streams.py).  Waits for the context's streams first: the transform kernel
+ * that writes the planes has finished and nothing reads them. */
+__attribute__((visibility("default"))) int hydt_write_lf_ints(HydAmdContext *ctx, int slot, const int32_t *src, size_t vbw, size_t vbh) {
+    int st = check_slot(ctx, slot);
+    if (st != ST_OK)
+        return st;
+    if (!src)
+        return fail(ctx, ST_API_ERROR, "no LF ints to write");
+    if (vbw > HYDK_DC_PITCH || vbh > HYDK_DC_PITCH)
+        return fail(ctx, ST_API_ERROR, "DC plane larger than an LF group");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->lf_stream)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->lf_stream));
+    int32_t *dst = ctx->dc + (size_t)slot * 3 * HYDK_DC_PITCH * HYDK_DC_PITCH;
+    for (int c = 0; c < 3; c++)
+        HIP_TRY(ctx, hipMemcpy2D(dst + (size_t)c * HYDK_DC_PITCH * HYDK_DC_PITCH, HYDK_DC_PITCH * sizeof(int32_t),
+                                 src + (size_t)c * vbw * vbh, vbw * sizeof(int32_t), vbw * sizeof(int32_t), vbh,
+                                 hipMemcpyHostToDevice));
+    return ST_OK;
+}
+#endif
+
 int hydamd_set_lf_coder(HydAmdContext *ctx, int on_device) {
     if (!ctx)
         return ST_API_ERROR;

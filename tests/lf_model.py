@@ -5,7 +5,9 @@ TEST INFRASTRUCTURE ONLY.  It restates the reference's LF-coefficient stream
 and entropy.c:664-707,1003-1021 for codes and write-out) as whole-array operations, taking the
 code lengths from the product's host prefix coder (already pinned against the reference by
 test_host_glue.py).  CPU tests check that the host splice around such a stream reproduces the
-host-coded section; GPU tests check that the device produces exactly this model's output.
+host-coded section; GPU tests check that the device produces exactly this model's output.  The
+crafted-stream tests (tests/lf_streams.py, test_lf_streams.py, test_gpu_lf_streams.py) hold the device
+to the serial host coder as well: the model restates the kernels' chunk rule, the host coder does not.
 """
 from __future__ import annotations
 
@@ -178,9 +180,10 @@ def emissions(v: np.ndarray):
     return lit, r
 
 
-def model(dc: np.ndarray):
-    """(hist384, lengths384, alphabet, run_pairs, packed bits as uint8 array, bit_count)."""
-    v = residuals(dc)
+def strings(v: np.ndarray):
+    """Per position of the residual stream v: what it sends under the stream's own code.
+
+    -> (hist384, lengths384, alphabet, lit, r, val, ln): literal flag, run length, bit string (LSB first) and its length."""
     lit, r = emissions(v)
     tok, nb, res = hybrid(v)
     hist = np.zeros(LF_CODES, np.uint32)
@@ -189,13 +192,18 @@ def model(dc: np.ndarray):
     lengths = lengths_for_hist(hist)
     codes = canonical_codes(lengths)
     _, alphabet = compact_to_tokens(hist)
-    # per-position bit strings
     e_lit = codes[np.where(lit, tok, 0)].astype(np.uint64)
     val = np.where(lit, (e_lit & np.uint64(0xFFFF)) | (res << (e_lit >> np.uint64(16))), np.uint64(0))
     ln = np.where(lit, (e_lit >> np.uint64(16)).astype(np.int64) + nb, 0)
     e_run = codes[np.where(r > 0, 256 + r - 3, 0)].astype(np.uint64)
     val = np.where(r > 0, val | ((e_run & np.uint64(0xFFFF)) << ln.astype(np.uint64)), val)
     ln = np.where(r > 0, ln + (e_run >> np.uint64(16)).astype(np.int64), ln)
+    return hist, lengths, alphabet, lit, r, val, ln
+
+
+def model_of_stream(v: np.ndarray):
+    """(hist384, lengths384, alphabet, run_pairs, packed bits as uint8 array, bit_count) of a residual stream."""
+    hist, lengths, alphabet, lit, r, val, ln = strings(v)
     total = int(ln.sum())
     # expand to bits (LSB first); fine for test sizes
     keep = ln > 0
@@ -208,3 +216,8 @@ def model(dc: np.ndarray):
         bitarr[offs[m] + b] = ((val[m] >> np.uint64(b)) & np.uint64(1)).astype(np.uint8)
     packed = np.packbits(bitarr[: (total + 7) // 8 * 8], bitorder="little")
     return hist, lengths, alphabet, int((r > 0).sum()), packed, total
+
+
+def model(dc: np.ndarray):
+    """(hist384, lengths384, alphabet, run_pairs, packed bits as uint8 array, bit_count)."""
+    return model_of_stream(residuals(dc))
