@@ -35,6 +35,7 @@
 
 #include "../../../include/hydrium_amd.h"
 #include "hydk_common.h"
+#include "../hyd_sample_fmt.h"
 
 #pragma clang fp contract(off)
 
@@ -69,7 +70,7 @@ hipError_t launch_frame_begin(const HydkLfJob *host_jobs, HydkLfJob *d_jobs, int
                               hipStream_t stream);
 hipError_t launch_publish(const uint64_t *total, uint64_t *h_total, const unsigned long long *lf_total,
                           unsigned long long *h_lf_total, const uint32_t *status, uint32_t *h_status, hipStream_t stream);
-hipError_t transform_footprint(int fmt, int xmode, int *lds_bytes, int *registers);
+hipError_t transform_footprint(int fmt, int storage, int xmode, int *lds_bytes, int *registers);
 hipError_t launch_scan(const uint32_t *group_bits, int count, uint64_t *offsets, uint64_t *total, uint8_t *payload,
                        uint64_t payload_cap, int clear_shared_words, uint32_t *status, hipStream_t stream);
 hipError_t launch_pack(const uint32_t *bitbuf, uint32_t bit_pitch_words, const uint32_t *group_bits, const uint64_t *offsets,
@@ -308,7 +309,19 @@ void host_input_lut(uint16_t *lut, size_t size, int linear_light) {
     }
 }
 
-size_t sample_size(int fmt) { return fmt == HYDK_FMT_U8 ? 1 : fmt == HYDK_FMT_U16 ? 2 : 4; }
+static_assert(HYD_FMT_UINT8 == HYDK_FMT_U8 && HYD_FMT_UINT16 == HYDK_FMT_U16 && HYD_FMT_FLOAT32 == HYDK_FMT_F32 &&
+                  HYD_FMT_FLOAT16 == HYDAMD_FLOAT16 && HYD_FMT_BFLOAT16 == HYDAMD_BFLOAT16,
+              "the public formats' integer classes are the kernels' classes");
+
+/* a public sample format's class (what job.fmt holds) and, for the float class, its storage form */
+int fmt_class(int sample_fmt) { return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : sample_fmt; }
+uint32_t fmt_storage(int sample_fmt) {
+    return sample_fmt == HYD_FMT_FLOAT16 ? HYDK_STORE_F16 : sample_fmt == HYD_FMT_BFLOAT16 ? HYDK_STORE_BF16 : HYDK_STORE_F32;
+}
+/* the public format a recorded job reads */
+int job_sample_fmt(const HydkLfJob &job) {
+    return job.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : job.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : job.fmt;
+}
 
 /* forms 1-3 (several chains per wavefront, by rows) were replaced by form 5: select it, and say so once */
 int retired_rans_form(int waves) {
@@ -374,11 +387,14 @@ int widen_token_records(HydAmdContext *ctx);
 
 /* Record one LF group's job; the kernels run batched over all recorded slots in hydamd_finish_frame. */
 int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride,
-                    int fmt, size_t width, size_t height, unsigned preset) {
+                    int sample_fmt, size_t width, size_t height, unsigned preset) {
     if (width == 0 || height == 0 || width > 2048 || height > 2048)
         return fail(ctx, ST_API_ERROR, "LF group must be between 1 and 2048 pixels in each direction");
-    if (fmt != HYDK_FMT_U8 && fmt != HYDK_FMT_U16 && fmt != HYDK_FMT_F32)
+    if (!hyd_fmt_is_device(sample_fmt))
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
+    /* half precision is a storage form of the float class: the job is a float job, and every `fmt == HYDK_FMT_F32` below
+     * and in the kernels keeps meaning "float class" */
+    const int fmt = fmt_class(sample_fmt);
     /* the slot's frame: the whole launch group, or one frame of a batch — presets and the alphabet maximum restart with it */
     unsigned frame_first = 0, frame_groups = ctx->num_presets;
     if (ctx->slots_per_frame > 0) {
@@ -402,6 +418,13 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.row_stride = row_stride;
     job.pixel_stride = pixel_stride;
     job.fmt = fmt;
+    job.storage = fmt_storage(sample_fmt);
+#ifdef HYD_TEST_HOOKS
+    /* HYDAMD_DEBUG_HALF_PER_SAMPLE (bit 0 interleaved, bit 1 planar): half-precision rows that qualify for the dword runs
+     * read sample by sample instead — same bytes; what the runs are worth (scripts/half_formats_probe.py) */
+    static const int half_per_sample = getenv("HYDAMD_DEBUG_HALF_PER_SAMPLE") ? atoi(getenv("HYDAMD_DEBUG_HALF_PER_SAMPLE")) : 0;
+    job.per_sample = (uint32_t)half_per_sample & 3u;
+#endif
     job.linear_light = ctx->linear_light;
     job.width = (int)width;
     job.height = (int)height;
@@ -493,7 +516,7 @@ int ensure_staging(HydAmdContext *ctx, size_t tile_bytes) {
             const char *old_base = ctx->d_arena + (size_t)i * ctx->arena_tile;
             if (!job.width || (const char *)job.src[0] != old_base)
                 continue; /* not a host-staged slot */
-            const size_t ss = sample_size(job.fmt);
+            const size_t ss = hyd_fmt_bytes(job_sample_fmt(job));
             char *base = fresh + (size_t)i * tile_bytes;
             HIP_TRY(ctx, hipMemcpy(base, old_base, (size_t)job.width * job.height * 3 * ss, hipMemcpyDeviceToDevice));
             job.src[0] = base;
@@ -1220,10 +1243,10 @@ int hydamd_encode_lf_group_host(HydAmdContext *ctx, int slot, const void *const 
         return fail(ctx, ST_API_ERROR, "null pixel pointer");
     if (width == 0 || height == 0 || width > 2048 || height > 2048)
         return fail(ctx, ST_API_ERROR, "LF group must be between 1 and 2048 pixels in each direction");
-    if (sample_fmt != HYDK_FMT_U8 && sample_fmt != HYDK_FMT_U16 && sample_fmt != HYDK_FMT_F32)
+    if (!hyd_fmt_is_host(sample_fmt)) /* host pixels come in the reference's three formats */
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t ss = sample_size(sample_fmt);
+    const size_t ss = hyd_fmt_bytes(sample_fmt);
     const size_t bytes = width * height * 3 * ss;
     /* size for full 2048x2048 tiles of this sample type so that later tiles never reallocate */
     st = ensure_staging(ctx, (size_t)2048 * 2048 * 3 * ss);
@@ -1268,10 +1291,10 @@ int hydamd_encode_image(HydAmdContext *ctx, const void *const src[3], ptrdiff_t 
     const size_t lfx = (width + 2047) >> 11, lfy = (height + 2047) >> 11;
     if (lfx * lfy > (size_t)ctx->max_slots)
         return fail(ctx, ST_API_ERROR, "context has too few LF-group slots for this image");
-    if (sample_fmt != HYDK_FMT_U8 && sample_fmt != HYDK_FMT_U16 && sample_fmt != HYDK_FMT_F32)
+    if (!hyd_fmt_is_device(sample_fmt))
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     int st = hydamd_begin_frame(ctx, (unsigned)(lfx * lfy));
-    const ptrdiff_t ss = (ptrdiff_t)sample_size(sample_fmt);
+    const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(sample_fmt);
     for (size_t ty = 0; ty < lfy && st == ST_OK; ty++)
         for (size_t tx = 0; tx < lfx && st == ST_OK; tx++) {
             const ptrdiff_t off = ((ptrdiff_t)(ty * 2048) * row_stride + (ptrdiff_t)(tx * 2048) * pixel_stride) * ss;
@@ -1341,11 +1364,11 @@ int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const 
         return fail(ctx, ST_API_ERROR, "null pixel pointer");
     if (width == 0 || height == 0)
         return fail(ctx, ST_API_ERROR, "empty image");
-    if (sample_fmt != HYDK_FMT_U8 && sample_fmt != HYDK_FMT_U16 && sample_fmt != HYDK_FMT_F32)
+    if (!hyd_fmt_is_device(sample_fmt))
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     const size_t lfx = (width + 2047) >> 11, lfy = (height + 2047) >> 11, n = lfx * lfy;
     int st = hydamd_begin_batch(ctx, (unsigned)n, frames);
-    const ptrdiff_t ss = (ptrdiff_t)sample_size(sample_fmt);
+    const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(sample_fmt);
     for (int f = 0; f < frames && st == ST_OK; f++) {
         const void *const *s3 = src + 3 * (size_t)f;
         if (!s3[0] || !s3[1] || !s3[2])
@@ -1371,7 +1394,8 @@ static int transform_range(HydAmdContext *ctx, int first, int count) {
     for (int i = first; i < first + count; i++) {
         if (ctx->h_jobs[i].width == 0)
             return fail(ctx, ST_API_ERROR, "an LF-group slot of this frame was never submitted");
-        mask |= 1u << ctx->h_jobs[i].fmt;
+        /* bits 0, 1: the integer classes; bits 2 + HYDK_STORE_*: the float class by storage form (launch_transform) */
+        mask |= 1u << (ctx->h_jobs[i].fmt + (ctx->h_jobs[i].fmt == HYDK_FMT_F32 ? (int)ctx->h_jobs[i].storage : 0));
     }
     ctx->status_published = false;
     /* the descriptors travel by a kernel that reads the pinned ring; the frame's first such launch also
@@ -2624,6 +2648,47 @@ __attribute__((visibility("default"))) int hydt_write_lf_ints(HydAmdContext *ctx
                                  hipMemcpyHostToDevice));
     return ST_OK;
 }
+
+/* Test hooks (probe flavour only, not declared in include/): the widening of half-precision samples (hydk_half.h) as the
+ * host compiler built it and as the device runs it.  storage: HYDK_STORE_F16 (1) or HYDK_STORE_BF16 (2); out[i] holds the
+ * float32 bits of in[i]. */
+__attribute__((visibility("default"))) int hydt_widen_half_host(int storage, const uint16_t *in, uint32_t *out, size_t n) {
+    if ((storage != HYDK_STORE_F16 && storage != HYDK_STORE_BF16) || !in || !out)
+        return ST_API_ERROR;
+    for (size_t i = 0; i < n; i++)
+        out[i] = hydk_widen_half(storage, in[i]);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_widen_half_probe(int storage, const uint16_t *in, uint32_t *out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x; /* grid = 256 workgroups: one thread per 16-bit pattern */
+    out[i] = hydk_widen_half(storage, in[i]);
+}
+} /* namespace */
+
+/* one launch over 65 536 inputs (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_widen_half_device(int device, int storage, const uint16_t *in, uint32_t *out) {
+    if ((storage != HYDK_STORE_F16 && storage != HYDK_STORE_BF16) || !in || !out || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    constexpr size_t kN = 65536;
+    uint16_t *d_in = nullptr;
+    uint32_t *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_in, kN * sizeof(uint16_t));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&d_out, kN * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(d_in, in, kN * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_widen_half_probe, dim3(kN / 256), dim3(256), 0, nullptr, storage, d_in, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpy(out, d_out, kN * sizeof(uint32_t), hipMemcpyDeviceToHost); /* (waits for the kernel) */
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+}
 #endif
 
 int hydamd_set_lf_coder(HydAmdContext *ctx, int on_device) {
@@ -2699,10 +2764,10 @@ int hydamd_read_lf_streams(HydAmdContext *ctx, int first_slot, int count, HydAmd
 }
 
 int hydamd_debug_transform_footprint(HydAmdContext *ctx, int sample_fmt, int *lds_bytes, int *registers) {
-    if (!ctx || !lds_bytes || !registers || sample_fmt < 0 || sample_fmt > 2)
+    if (!ctx || !lds_bytes || !registers || !hyd_fmt_is_device(sample_fmt))
         return ST_API_ERROR;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hydk::transform_footprint(sample_fmt, ctx->use_luts, lds_bytes, registers));
+    HIP_TRY(ctx, hydk::transform_footprint(fmt_class(sample_fmt), (int)fmt_storage(sample_fmt), ctx->use_luts, lds_bytes, registers));
     return ST_OK;
 }
 

@@ -10,6 +10,10 @@
 
 #include <stdint.h>
 
+#include "hydk_half.h" /* HYDK_STORE_*: how a float-class LF group's samples are stored */
+
+/* sample CLASSES: what a job's fmt and the transform kernel's FMT name.  Half-precision pixels (hyd_sample_fmt.h: 3, 4) are
+ * float-class jobs — fmt == HYDK_FMT_F32 means "float class" everywhere — whose storage field says how to load a sample */
 #define HYDK_FMT_U8 0
 #define HYDK_FMT_U16 1
 #define HYDK_FMT_F32 2
@@ -103,6 +107,9 @@ typedef struct HydkLfJob {
     int32_t *dbg_quant;
     uint32_t *bad_slot;      /* per-slot outcomes (hydamd_set_bad_sample_per_slot): this slot's flag word, cleared with the frame's
                               * accumulators — a non-finite float sample sets it and is coded as 0.0; NULL: the launch-wide status bit */
+    uint32_t storage;        /* float class only: HYDK_STORE_F32 (0, what a zeroed job says), _F16 or _BF16 — 2-byte samples, widened on load */
+    uint32_t per_sample;     /* probe flavour only (HYDAMD_DEBUG_HALF_PER_SAMPLE, for A/B): bit 0 interleaved, bit 1 planar half rows
+                              * go through the per-sample loader although they qualify for the dword runs; the product leaves 0 */
 } HydkLfJob;
 
 /* ---- LF-group coder (the modular sub-stream of the LF coefficients, encoder.c:560-596) ----

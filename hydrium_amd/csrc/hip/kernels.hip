@@ -601,10 +601,14 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
 }
 
 #define HYDK_K1_OCCUPANCY __launch_bounds__(kThreads, HYDK_K1_WAVES)
-template <int FMT, int XMODE>
+/* STORE: how a float-class instance's samples are stored (HYDK_STORE_*); a half-precision sample is widened exactly on load
+ * (hydk_half.h) and is a float32 sample from there on.  The integer instances know one storage form each. */
+template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
-    typedef typename SampleOf<FMT>::type sample_t;
+    static_assert(STORE == HYDK_STORE_F32 || FMT == HYDK_FMT_F32, "only the float class has storage forms");
+    constexpr bool HALF = STORE != HYDK_STORE_F32;
+    typedef typename std::conditional<HALF, uint16_t, typename SampleOf<FMT>::type>::type sample_t;
     constexpr bool LUTS = XMODE == kXybGather;
     constexpr int kWords = FMT == HYDK_FMT_U8 ? 6 : 12; /* dwords holding 8 packed RGB pixels */
 #if HYDK_K1_PRIO
@@ -615,7 +619,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
      * its symbols in its own share of the group's token array and k_join_parts closes the gaps (round 5) */
     const unsigned bid = blockIdx.x >> plog, part = blockIdx.x & ((1u << plog) - 1u);
     const HydkLfJob job = jobs[bid >> 6];
-    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE)))
+    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE)) || (FMT == HYDK_FMT_F32 && job.storage != (uint32_t)STORE))
         return; /* another template instance of this launch round owns this LF group */
     if ((int)(bid & 63) >= job.gcols * job.grows)
         return;
@@ -707,12 +711,48 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
 #else
     const int ar = t >> 5, ab = t & 31;
 #endif
+    /* half-precision storage: a block row's 24 samples are 12 dwords too — 8 interleaved pixels in one run (hrun 1), or 4
+     * dwords from each of three planes (hrun 2: what an NCHW network output is) — when every row starts on a dword: the base
+     * addresses and the row stride in BYTES (an odd number of samples misaligns every other row).  Anything else — RGBA,
+     * odd bases, odd strides — reads sample by sample below, as float32 storage always does (job.per_sample: the probe
+     * flavour's A/B switch, profiles/half_formats.txt). */
+    int hrun = 0;
+    if (HALF) {
+        const bool rows4 = ((job.row_stride * 2) & 3) == 0;
+        if (!(job.per_sample & 1u) && job.pixel_stride == 3 && rows4 && ((uintptr_t)job.src[0] & 3) == 0 &&
+            (const char *)job.src[1] == (const char *)job.src[0] + 2 && (const char *)job.src[2] == (const char *)job.src[0] + 4)
+            hrun = 1;
+        else if (!(job.per_sample & 2u) && job.pixel_stride == 1 && rows4 &&
+                 (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)job.src[2]) & 3) == 0)
+            hrun = 2;
+    }
+    const bool hfast = HALF && hrun != 0 && ab < gbw && ab * 8 + 8 <= gw;
     const bool fast = packed && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
     uint32_t nxt[kWords];
 #pragma unroll
     for (int k = 0; k < kWords; k++)
         nxt[k] = 0;
     auto prefetch = [&](int s) {
+        if (HALF) {
+            if (hfast && s * 8 + ar < gh) {
+                const long long row = (long long)(py0 + s * 8 + ar) * job.row_stride;
+                if (hrun == 1) {
+                    const char *p = (const char *)job.src[0] + (row + (long long)(px0 + ab * 8) * 3) * 2;
+#pragma unroll
+                    for (int k = 0; k < 12; k++)
+                        nxt[k] = HYDK_GLOBAL(const uint32_t, p)[k];
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) {
+                        const char *p = (const char *)job.src[c] + (row + (long long)(px0 + ab * 8)) * 2;
+#pragma unroll
+                        for (int k = 0; k < 4; k++)
+                            nxt[4 * c + k] = HYDK_GLOBAL(const uint32_t, p)[k];
+                    }
+                }
+            }
+            return;
+        }
         if (fast && s * 8 + ar < gh) {
             const uint32_t *p = (const uint32_t *)((const char *)job.src[0] +
                                                    ((long long)(py0 + s * 8 + ar) * job.row_stride +
@@ -744,7 +784,42 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
             const int y = py0 + s * 8 + ar; /* row inside the LF group */
             const int x0 = px0 + ab * 8;
             const bool row_ok = s * 8 + ar < gh;
-            if (fast) {
+            /* one float-class pixel, whatever its storage was: the non-finite check, then XYB */
+            auto float_pixel = [&](float fr, float fg, float fb, float &X, float &Y, float &B) {
+                if (job.bad_slot) {
+                    /* per-slot outcomes: the slot is flagged and the sample coded as 0.0, so that what follows
+                     * — bias curve, DCT, conversion, tokens — sees an ordinary picture and the slot's frame can
+                     * neither fail nor rerun the launch group; a finite sample passes through bit for bit */
+                    const bool ir = (__float_as_uint(fr) & 0x7f800000u) == 0x7f800000u;
+                    const bool ig = (__float_as_uint(fg) & 0x7f800000u) == 0x7f800000u;
+                    const bool ib = (__float_as_uint(fb) & 0x7f800000u) == 0x7f800000u;
+                    bad_sample = bad_sample || ir || ig || ib;
+                    fr = ir ? 0.0f : fr;
+                    fg = ig ? 0.0f : fg;
+                    fb = ib ? 0.0f : fb;
+                }
+                if (!lms_mix_f32(fr, fg, fb, job.linear_light, X, Y, B))
+                    bad_sample = true;
+            };
+            if (HALF && hfast) {
+                /* this strip's samples, fetched a strip ago: sample k of the row's 24 is half k & 1 of dword k >> 1 —
+                 * k = 3 * pixel + channel in an interleaved run, 8 * channel + pixel in three planes' */
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    xv[i] = yv[i] = bv[i] = 0.0f;
+                    if (row_ok) {
+                        float f[3];
+#pragma unroll
+                        for (int ch = 0; ch < 3; ch++) {
+                            const int ki = i * 3 + ch, kp = ch * 8 + i;
+                            const uint32_t wi = nxt[ki >> 1] >> (16 * (ki & 1)), wp = nxt[kp >> 1] >> (16 * (kp & 1));
+                            f[ch] = __uint_as_float(hydk_widen_half(STORE, (hrun == 1 ? wi : wp) & 0xFFFFu));
+                        }
+                        float_pixel(f[0], f[1], f[2], xv[i], yv[i], bv[i]);
+                    }
+                }
+                prefetch(s + 1);
+            } else if (fast) {
                 uint32_t(&w)[kWords] = nxt; /* this strip's pixels, fetched a strip ago */
                 /* which form of the transfer curve this wavefront's 16-bit samples need (wave-uniform) */
                 int curve = kCurveBoth;
@@ -878,21 +953,15 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                         const sample_t sg = ((const sample_t *)job.src[1])[off];
                         const sample_t sb = ((const sample_t *)job.src[2])[off];
                         if (FMT == HYDK_FMT_F32) {
-                            float fr = (float)sr, fg = (float)sg, fb = (float)sb;
-                            if (job.bad_slot) {
-                                /* per-slot outcomes: the slot is flagged and the sample coded as 0.0, so that what follows
-                                 * — bias curve, DCT, conversion, tokens — sees an ordinary picture and the slot's frame can
-                                 * neither fail nor rerun the launch group; a finite sample passes through bit for bit */
-                                const bool ir = (__float_as_uint(fr) & 0x7f800000u) == 0x7f800000u;
-                                const bool ig = (__float_as_uint(fg) & 0x7f800000u) == 0x7f800000u;
-                                const bool ib = (__float_as_uint(fb) & 0x7f800000u) == 0x7f800000u;
-                                bad_sample = bad_sample || ir || ig || ib;
-                                fr = ir ? 0.0f : fr;
-                                fg = ig ? 0.0f : fg;
-                                fb = ib ? 0.0f : fb;
+                            float fr, fg, fb;
+                            if (HALF) {
+                                fr = __uint_as_float(hydk_widen_half(STORE, (uint32_t)sr));
+                                fg = __uint_as_float(hydk_widen_half(STORE, (uint32_t)sg));
+                                fb = __uint_as_float(hydk_widen_half(STORE, (uint32_t)sb));
+                            } else {
+                                fr = (float)sr, fg = (float)sg, fb = (float)sb;
                             }
-                            if (!lms_mix_f32(fr, fg, fb, job.linear_light, xv[i], yv[i], bv[i]))
-                                bad_sample = true;
+                            float_pixel(fr, fg, fb, xv[i], yv[i], bv[i]);
                         } else {
                             uint32_t rgb[3] = {(uint32_t)sr, (uint32_t)sg, (uint32_t)sb};
 #pragma unroll
@@ -2889,7 +2958,8 @@ __global__ void k_lut_selftest(const uint16_t *in_lut16, const float *bias_lut, 
 namespace hydk {
 
 /* One launch per template instance that owns at least one LF group of this round; an instance
- * returns at once for the LF groups of another sample format. */
+ * returns at once for the LF groups of another sample format.  fmt_mask: bits 0, 1 the integer classes, bits 2 + HYDK_STORE_*
+ * the float class's storage forms. */
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream) {
     const dim3 grid((num_slots * HYDK_GROUPS_PER_LFG) << plog), block(kThreads);
@@ -2911,8 +2981,14 @@ hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt
         HYDK_LAUNCH_K1_MODES(HYDK_FMT_U8);
     if (fmt_mask & (1u << HYDK_FMT_U16))
         HYDK_LAUNCH_K1_MODES(HYDK_FMT_U16);
-    if (fmt_mask & (1u << HYDK_FMT_F32))
-        HYDK_LAUNCH_K1(HYDK_FMT_F32, kXybIeeeDiv);
+    /* the float class: one instance per storage form (bit HYDK_FMT_F32 + HYDK_STORE_* of the mask) */
+#define HYDK_LAUNCH_K1_FLOAT(STORE)                       \
+    if (fmt_mask & (1u << (HYDK_FMT_F32 + (STORE))))      \
+    hipLaunchKernelGGL((k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog)
+    HYDK_LAUNCH_K1_FLOAT(HYDK_STORE_F32);
+    HYDK_LAUNCH_K1_FLOAT(HYDK_STORE_F16);
+    HYDK_LAUNCH_K1_FLOAT(HYDK_STORE_BF16);
+#undef HYDK_LAUNCH_K1_FLOAT
 #undef HYDK_LAUNCH_K1_MODES
 #undef HYDK_LAUNCH_K1
     if (plog)
@@ -2920,10 +2996,14 @@ hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt
     return hipGetLastError();
 }
 
-hipError_t transform_footprint(int fmt, int xmode, int *lds_bytes, int *registers) {
+hipError_t transform_footprint(int fmt, int storage, int xmode, int *lds_bytes, int *registers) {
     const void *fn = nullptr;
 #define HYDK_K1_PTR(FMT, XM) fn = (const void *)k_transform_tokenize<FMT, XM>
-    if (fmt == HYDK_FMT_F32)
+    if (fmt == HYDK_FMT_F32 && storage == HYDK_STORE_F16)
+        fn = (const void *)k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, HYDK_STORE_F16>;
+    else if (fmt == HYDK_FMT_F32 && storage == HYDK_STORE_BF16)
+        fn = (const void *)k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, HYDK_STORE_BF16>;
+    else if (fmt == HYDK_FMT_F32)
         HYDK_K1_PTR(HYDK_FMT_F32, kXybIeeeDiv);
     else if (fmt == HYDK_FMT_U8) {
         if (xmode == kXybFastRcp)

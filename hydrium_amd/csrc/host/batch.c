@@ -24,6 +24,7 @@
 #include "hydrium_amd.h"
 #include "libhydrium/libhydrium.h"
 #include "planbuf.h"
+#include "../hyd_sample_fmt.h"
 
 #include "../hip/hydk_tiles.h"
 
@@ -311,7 +312,7 @@ HYDRIUM_EXPORT int hydamd_encode_batch(HydAmdBatch *b, int frames, const void *c
     for (int i = 0; i < 3 * frames; i++)
         if (!src[i])
             return fail(b, HYD_API_ERROR, "null pixel pointer", NULL);
-    if (sample_fmt != HYD_UINT8 && sample_fmt != HYD_UINT16 && sample_fmt != HYD_FLOAT32)
+    if (!hyd_fmt_is_device(sample_fmt))
         return fail(b, HYD_API_ERROR, "Invalid Sample Format", NULL);
     if (b->in_flight)
         return fail(b, HYD_API_ERROR, "a batch is in flight: hydamd_batch_result first", NULL);

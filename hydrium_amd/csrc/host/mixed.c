@@ -31,6 +31,7 @@
 #include "hydrium_amd.h"
 #include "libhydrium/libhydrium.h"
 #include "planbuf.h"
+#include "../hyd_sample_fmt.h"
 
 #include "../hip/hydk_tiles.h"
 
@@ -484,7 +485,7 @@ static int enqueue_several(HydAmdMixed *m, const HydAmdImageDesc *images, const 
     for (int f = 0; f < m->frames; f++) {
         const HydAmdImageDesc *d = &images[f];
         const int sample_fmt = sample_fmts[f];
-        const ptrdiff_t ss = sample_fmt == HYD_UINT8 ? 1 : sample_fmt == HYD_UINT16 ? 2 : 4;
+        const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(sample_fmt);
         const size_t lfx = (d->width + 2047) >> 11, lfy = (d->height + 2047) >> 11;
         for (size_t ty = 0; ty < lfy; ty++)
             for (size_t tx = 0; tx < lfx; tx++, slot++) {
@@ -550,7 +551,7 @@ HYDRIUM_EXPORT int hydamd_encode_mixed_formats(HydAmdMixed *m, int frames, const
     if (!sample_fmts)
         return fail(m, HYD_API_ERROR, "null sample formats", NULL);
     for (int f = 0; f < frames; f++)
-        if (sample_fmts[f] != HYD_UINT8 && sample_fmts[f] != HYD_UINT16 && sample_fmts[f] != HYD_FLOAT32)
+        if (!hyd_fmt_is_device(sample_fmts[f]))
             return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
     if (m->in_flight)
         return fail(m, HYD_API_ERROR, "a batch is in flight: hydamd_mixed_result first", NULL);

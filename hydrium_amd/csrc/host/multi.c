@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include "shards.h"
+#include "../hyd_sample_fmt.h"
 
 #ifndef HYDRIUM_EXPORT
 #define HYDRIUM_EXPORT __attribute__((visibility("default")))
@@ -152,11 +153,11 @@ HYDRIUM_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *
     HydShardFrame *f = &m->f;
     if (!src || assembling_shard < 0 || assembling_shard >= f->n)
         return fail(m, HYD_API_ERROR, "bad arguments", NULL);
-    if (sample_fmt != HYD_UINT8 && sample_fmt != HYD_UINT16 && sample_fmt != HYD_FLOAT32)
+    if (!hyd_fmt_is_device(sample_fmt))
         return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
     if (m->in_flight)
         return fail(m, HYD_API_ERROR, "a frame is in flight: hydamd_multi_result first", NULL);
-    const ptrdiff_t ss = sample_fmt == HYD_UINT8 ? 1 : sample_fmt == HYD_UINT16 ? 2 : 4;
+    const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(sample_fmt);
     const size_t W = m->md.width, H = m->md.height;
     int st;
     f->assembling = assembling_shard;

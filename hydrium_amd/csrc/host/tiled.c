@@ -23,6 +23,7 @@
 #include "hydrium_amd.h"
 #include "libhydrium/libhydrium.h"
 #include "planbuf.h"
+#include "../hyd_sample_fmt.h"
 
 #include "../hip/hydk_tiles.h"
 
@@ -325,7 +326,7 @@ static int assemble_group(HydAmdTiled *t) {
 static int enqueue_group(HydAmdTiled *t) {
     const TileGeometry *g = &t->g;
     const size_t left = g->ntiles - t->next, n = left < (size_t)t->launch ? left : (size_t)t->launch;
-    const ptrdiff_t ss = t->fmt == HYD_UINT8 ? 1 : t->fmt == HYD_UINT16 ? 2 : 4;
+    const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(t->fmt);
     int st = hydamd_begin_batch(t->ctx, 1, (int)n);
     if (st)
         return fail(t, st, "begin launch group", hydamd_error(t->ctx));
@@ -349,7 +350,7 @@ HYDRIUM_EXPORT int hydamd_encode_image_tiled(HydAmdTiled *t, const void *const s
         return HYD_API_ERROR;
     if (!src || !src[0] || !src[1] || !src[2])
         return fail(t, HYD_API_ERROR, "null pixel pointer", NULL);
-    if (sample_fmt != HYD_UINT8 && sample_fmt != HYD_UINT16 && sample_fmt != HYD_FLOAT32)
+    if (!hyd_fmt_is_device(sample_fmt))
         return fail(t, HYD_API_ERROR, "Invalid Sample Format", NULL);
     if (t->in_flight)
         return fail(t, HYD_API_ERROR, "an image is in flight: hydamd_tiled_result first", NULL);

@@ -24,6 +24,25 @@ LF_BITWORDS = 3 * 256 * 256 * 2 + 2                     # HYDK_LF_BITWORDS
 LF_CODES = 384  # compact token space of the LF-coefficient stream (include/hydrium_amd.h HYDAMD_LF_CODES)
 
 FMT_OF_DTYPE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2}
+# device pixels only (include/hydrium_amd.h, HYDAMD_FLOAT16 / HYDAMD_BFLOAT16): half-precision samples, widened exactly on load
+FLOAT16 = 3
+BFLOAT16 = 4
+
+
+def sample_fmt_of(t) -> int:
+    """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
+    float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0."""
+    name = str(t.dtype).rpartition(".")[2]
+    if name == "float16":
+        return FLOAT16
+    if name == "bfloat16":
+        return BFLOAT16
+    if name == "float32":
+        return 2
+    isz = t.element_size()
+    if isz in (1, 2) and not name.startswith(("float", "bfloat", "complex")):
+        return isz - 1
+    raise ValueError(f"no sample format for pixels of type {t.dtype}")
 
 
 class DeviceError(RuntimeError):
@@ -379,7 +398,7 @@ class DeviceContext:
         unmodified) until ``sync()``."""
         h, w, _ = img.shape
         isz = img.element_size()
-        fmt = {1: 0, 2: 1, 4: 2}[isz]
+        fmt = sample_fmt_of(img)
         lfx, lfy = -(-w // 2048), -(-h // 2048)
         n = lfx * lfy
         if num_slots_check and n > self.max_lf_groups:
@@ -406,13 +425,13 @@ class DeviceContext:
         (hydamd_encode_image_batch): frame k in slots k * n ... (k + 1) * n - 1."""
         h, w, _ = imgs[0].shape
         isz = imgs[0].element_size()
-        fmt = {1: 0, 2: 1, 4: 2}[isz]
+        fmt = sample_fmt_of(imgs[0])
         n = (-(-w // 2048)) * (-(-h // 2048))
         if n * len(imgs) > self.max_lf_groups:
             raise ValueError("context has too few LF-group slots for this batch")
         ptrs = []
         for t in imgs:
-            assert t.shape == imgs[0].shape and t.element_size() == isz
+            assert t.shape == imgs[0].shape and t.dtype == imgs[0].dtype
             b = t.data_ptr()
             ptrs += [b, b + isz, b + 2 * isz]
         arr = (C.c_void_p * len(ptrs))(*ptrs)
@@ -580,7 +599,7 @@ class DeviceContext:
         return v.value
 
     def transform_footprint(self, sample_fmt: int):
-        """(static LDS bytes, registers per thread) of the transform kernel instance serving `sample_fmt` (0 u8, 1 u16, 2 f32)."""
+        """(static LDS bytes, registers per thread) of the transform kernel instance serving `sample_fmt` (0 u8, 1 u16, 2 f32, 3 f16, 4 bf16)."""
         lds, regs = C.c_int(0), C.c_int(0)
         self._ck(self.d.hydamd_debug_transform_footprint(self.h, int(sample_fmt), C.byref(lds), C.byref(regs)))
         return lds.value, regs.value
@@ -764,20 +783,22 @@ class MultiFrame:
         """origins[d]: an interleaved (H, W, 3) torch tensor on shard d's device holding (at least) that shard's LF
         groups at their place in the image — or an int: the device address pixel (0, 0) would have.  Asynchronous; the
         tensors must stay alive until result()."""
-        ptrs, isz = [], None
+        ptrs, isz, fmt = [], None, None
         for o in origins:
             if hasattr(o, "data_ptr"):
-                isz = o.element_size()
+                isz, fmt = o.element_size(), sample_fmt_of(o)
                 b = o.data_ptr()
             else:
                 b = int(o)
             ptrs.append(b)
         isz = isz or getattr(self, "sample_bytes", 1)
+        if fmt is None:
+            fmt = {1: 0, 2: 1, 4: 2}[isz]  # bare addresses: sample_bytes names an integer format or float32
         flat = []
         for b in ptrs:
             flat += [b, b + isz, b + 2 * isz]
         arr = (C.c_void_p * len(flat))(*flat)
-        self._ck(self.d.hydamd_encode_image_multi(self.h, arr, 3 * self.width, 3, {1: 0, 2: 1, 4: 2}[isz], assembling_shard))
+        self._ck(self.d.hydamd_encode_image_multi(self.h, arr, 3 * self.width, 3, fmt, assembling_shard))
 
     def result(self) -> int:
         n = C.c_size_t(0)
@@ -834,12 +855,11 @@ class TiledImage:
             isz = img.element_size()
             ptrs = [img.data_ptr() + c * isz for c in range(3)]
             row_stride, pixel_stride = img.stride(0), img.stride(1)
-            sample_fmt = {1: 0, 2: 1, 4: 2}[isz]
+            sample_fmt = sample_fmt_of(img)
         elif hasattr(img[0], "data_ptr"):
-            isz = img[0].element_size()
             ptrs = [p.data_ptr() for p in img]
             row_stride, pixel_stride = img[0].stride(0), img[0].stride(1)
-            sample_fmt = {1: 0, 2: 1, 4: 2}[isz]
+            sample_fmt = sample_fmt_of(img[0])
         else:
             ptrs = [int(p) if p is not None else None for p in img]
             if row_stride is None or pixel_stride is None or sample_fmt is None:
@@ -916,10 +936,10 @@ class FrameBatch:
             if hasattr(img, "data_ptr"):
                 isz = img.element_size()
                 ptrs += [img.data_ptr() + c * isz for c in range(3)]
-                layout = (img.stride(0), img.stride(1), {1: 0, 2: 1, 4: 2}[isz])
+                layout = (img.stride(0), img.stride(1), sample_fmt_of(img))
             elif hasattr(img[0], "data_ptr"):
                 ptrs += [p.data_ptr() for p in img]
-                layout = (img[0].stride(0), img[0].stride(1), {1: 0, 2: 1, 4: 2}[img[0].element_size()])
+                layout = (img[0].stride(0), img[0].stride(1), sample_fmt_of(img[0]))
             else:
                 if row_stride is None or pixel_stride is None or sample_fmt is None:
                     raise ValueError("device addresses need row_stride, pixel_stride and sample_fmt")
@@ -1013,13 +1033,13 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
             isz = img.element_size()
             ptrs = [img.data_ptr() + c * isz for c in range(3)]
             rs, ps, (h, w) = img.stride(0), img.stride(1), img.shape[:2]
-            fmt = {1: 0, 2: 1, 4: 2}[isz]
+            fmt = sample_fmt_of(img)
         elif hasattr(img[0], "data_ptr"):  # planes keep their shape: the size is theirs, never a bare pointer's
             ptrs = [p.data_ptr() for p in img]
             rs, ps, (h, w) = img[0].stride(0), img[0].stride(1), img[0].shape[:2]
             if any(tuple(p.shape[:2]) != (h, w) or (p.stride(0), p.stride(1)) != (rs, ps) for p in img):
                 raise ValueError("the three planes of an image share one shape and one layout")
-            fmt = {1: 0, 2: 1, 4: 2}[img[0].element_size()]
+            fmt = sample_fmt_of(img[0])
         else:
             ptrs, rs, ps, w, h = img
             ptrs = [int(p) if p is not None else None for p in ptrs]
@@ -1032,7 +1052,7 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
             elif fmt != sample_fmt:
                 raise ValueError("the images of a batch share one sample format")
         elif isinstance(sample_fmts, list) and fmt != given:
-            if given in (0, 1, 2):
+            if given in (0, 1, 2, FLOAT16, BFLOAT16):
                 raise ValueError("sample_fmts disagrees with a tensor's dtype")
             fmt = given  # not a format at all: the library refuses it (HYD_API_ERROR), nothing is enqueued
         fmts.append(fmt)

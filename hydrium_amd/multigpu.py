@@ -45,7 +45,7 @@ class Shard:
         if not self.lf_ids:
             return
         isz = tensor.element_size()
-        fmt = {1: 0, 2: 1, 4: 2}[isz]
+        fmt = device.sample_fmt_of(tensor)
         pitch = tensor.shape[1]
         self.ctx.begin_frame(self.lfx * self.lfy)
         for slot, lf in enumerate(self.lf_ids):

@@ -116,10 +116,30 @@ HYDAMD_EXPORT int hydamd_set_rans_waves(HydAmdContext *ctx, int waves);
 HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
 
 /*
+ * Half-precision DEVICE pixels: two sample formats beside the drop-in API's HYD_UINT8 (0), HYD_UINT16 (1) and
+ * HYD_FLOAT32 (2), which include/libhydrium/libhydrium.h keeps as the reference has them.  What a network or a GPU image
+ * pipeline leaves in device memory goes in as it is, without a float32 copy.
+ *   HYDAMD_FLOAT16   IEEE binary16 (torch.float16)
+ *   HYDAMD_BFLOAT16  bfloat16: the upper half of a float32 (torch.bfloat16)
+ * A sample is 2 bytes and strides stay in samples.  The file is byte for byte what the reference writes for the same
+ * picture given as HYD_FLOAT32 with every sample widened exactly (both widenings are lossless).  A non-finite sample
+ * (binary16 exponent 31, bfloat16 exponent 255) is what a non-finite float32 sample is: "Invalid NaN Float" for the frame
+ * or batch, or that image's HYDAMD_IMAGE_BAD_SAMPLE under hydamd_*_set_image_errors.
+ * Accepted wherever a sample_fmt names device pixels: hydamd_encode_lf_group, hydamd_encode_image,
+ * hydamd_encode_image_batch, hydamd_encode_batch, hydamd_encode_mixed, hydamd_encode_mixed_formats,
+ * hydamd_encode_image_tiled, hydamd_encode_image_multi and hydamd_debug_transform_footprint.  Entry points that read HOST
+ * pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse both with "Invalid Sample Format", as they and every
+ * other entry point refuse anything outside 0..4.
+ */
+#define HYDAMD_FLOAT16 3
+#define HYDAMD_BFLOAT16 4
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
- * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers.
+ * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
+ * HYDAMD_FLOAT16 or HYDAMD_BFLOAT16.
  */
 HYDAMD_EXPORT int hydamd_encode_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
                                          ptrdiff_t pixel_stride, int sample_fmt, size_t width, size_t height,
@@ -152,7 +172,8 @@ HYDAMD_EXPORT int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, cons
                                             ptrdiff_t pixel_stride, int sample_fmt, size_t width, size_t height);
 
 /* Same, from HOST pointers: the samples are gathered into pinned staging (the caller's buffers may
- * be reused as soon as this returns, as after hyd_send_tile) and copied to the GPU on the stream. */
+ * be reused as soon as this returns, as after hyd_send_tile) and copied to the GPU on the stream.  sample_fmt is one of
+ * HYD_UINT8, HYD_UINT16, HYD_FLOAT32: the half-precision formats name device pixels only. */
 HYDAMD_EXPORT int hydamd_encode_lf_group_host(HydAmdContext *ctx, int slot, const void *const src[3],
                                               ptrdiff_t row_stride, ptrdiff_t pixel_stride, int sample_fmt,
                                               size_t width, size_t height, unsigned preset);
@@ -644,7 +665,7 @@ HYDAMD_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b);
  *                                its assembly and returns; the pixels stay borrowed until hydamd_mixed_result, the
  *                                descriptors only for the call.  The output buffer is sized before anything is
  *                                enqueued, from the batch's plan and the context's capacities.
- *   hydamd_encode_mixed_formats  the same with image k's samples in sample_fmts[k] (HYD_UINT8 / HYD_UINT16 / HYD_FLOAT32):
+ *   hydamd_encode_mixed_formats  the same with image k's samples in sample_fmts[k] (HYD_UINT8 / HYD_UINT16 / HYD_FLOAT32 / HYDAMD_FLOAT16 / HYDAMD_BFLOAT16):
  *                                8-bit, 16-bit and float pictures side by side in one launch group, every file what the
  *                                reference writes for that picture in its format.  A bad entry is HYD_API_ERROR "Invalid
  *                                Sample Format" with nothing enqueued.  The plan and its reuse depend on sizes only.
