@@ -312,15 +312,27 @@ void host_input_lut(uint16_t *lut, size_t size, int linear_light) {
 static_assert(HYD_FMT_UINT8 == HYDK_FMT_U8 && HYD_FMT_UINT16 == HYDK_FMT_U16 && HYD_FMT_FLOAT32 == HYDK_FMT_F32 &&
                   HYD_FMT_FLOAT16 == HYDAMD_FLOAT16 && HYD_FMT_BFLOAT16 == HYDAMD_BFLOAT16,
               "the public formats' integer classes are the kernels' classes");
+static_assert(HYD_FMT_NV12_BT709 == HYDAMD_NV12_BT709 && HYD_FMT_NV12_BT709_FULL == HYDAMD_NV12_BT709_FULL &&
+                  HYD_FMT_NV12_BT601 == HYDAMD_NV12_BT601 && HYD_FMT_NV12_BT601_FULL == HYDAMD_NV12_BT601_FULL &&
+                  HYDAMD_NV12_BT709 + HYDK_YUV_BT709_FULL == HYDAMD_NV12_BT709_FULL &&
+                  HYDAMD_NV12_BT709 + HYDK_YUV_BT601 == HYDAMD_NV12_BT601 &&
+                  HYDAMD_NV12_BT709 + HYDK_YUV_BT601_FULL == HYDAMD_NV12_BT601_FULL,
+              "the NV12 formats are 16 + the kernels' matrix index");
 
-/* a public sample format's class (what job.fmt holds) and, for the float class, its storage form */
-int fmt_class(int sample_fmt) { return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : sample_fmt; }
+/* a public sample format's class (what job.fmt holds) and its storage form: the float class's three, NV12 of the 8-bit class */
+int fmt_class(int sample_fmt) { return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : hyd_fmt_is_nv12(sample_fmt) ? HYDK_FMT_U8 : sample_fmt; }
 uint32_t fmt_storage(int sample_fmt) {
-    return sample_fmt == HYD_FMT_FLOAT16 ? HYDK_STORE_F16 : sample_fmt == HYD_FMT_BFLOAT16 ? HYDK_STORE_BF16 : HYDK_STORE_F32;
+    return sample_fmt == HYD_FMT_FLOAT16    ? HYDK_STORE_F16
+           : sample_fmt == HYD_FMT_BFLOAT16 ? HYDK_STORE_BF16
+           : hyd_fmt_is_nv12(sample_fmt)    ? HYDK_STORE_NV12
+                                            : HYDK_STORE_F32;
 }
 /* the public format a recorded job reads */
 int job_sample_fmt(const HydkLfJob &job) {
-    return job.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : job.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : job.fmt;
+    return job.storage == HYDK_STORE_F16    ? HYD_FMT_FLOAT16
+           : job.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16
+           : job.storage == HYDK_STORE_NV12 ? HYD_FMT_NV12_BT709 + (int)job.matrix
+                                            : job.fmt;
 }
 
 /* forms 1-3 (several chains per wavefront, by rows) were replaced by form 5: select it, and say so once */
@@ -392,8 +404,11 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
         return fail(ctx, ST_API_ERROR, "LF group must be between 1 and 2048 pixels in each direction");
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
+    if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
+        return fail(ctx, ST_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG);
     /* half precision is a storage form of the float class: the job is a float job, and every `fmt == HYDK_FMT_F32` below
-     * and in the kernels keeps meaning "float class" */
+     * and in the kernels keeps meaning "float class".  NV12 is a storage form of the 8-bit class: 4-byte token records, the
+     * 8-bit transfer table, and whatever form of the entropy stage is selected */
     const int fmt = fmt_class(sample_fmt);
     /* the slot's frame: the whole launch group, or one frame of a batch — presets and the alphabet maximum restart with it */
     unsigned frame_first = 0, frame_groups = ctx->num_presets;
@@ -419,6 +434,7 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.pixel_stride = pixel_stride;
     job.fmt = fmt;
     job.storage = fmt_storage(sample_fmt);
+    job.matrix = hyd_fmt_is_nv12(sample_fmt) ? (uint32_t)hyd_fmt_nv12_matrix(sample_fmt) : 0u;
 #ifdef HYD_TEST_HOOKS
     /* HYDAMD_DEBUG_HALF_PER_SAMPLE (bit 0 interleaved, bit 1 planar): half-precision rows that qualify for the dword runs
      * read sample by sample instead — same bytes; what the runs are worth (scripts/half_formats_probe.py) */
@@ -431,7 +447,7 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.gcols = (int)((width + 255) >> 8);
     job.grows = (int)((height + 255) >> 8);
     job.scheme = ctx->scheme;
-    job.use_luts = fmt == HYDK_FMT_F32 ? 0 : ctx->use_luts;
+    job.use_luts = fmt == HYDK_FMT_F32 ? 0 : ctx->use_luts + (job.storage == HYDK_STORE_NV12 ? HYDK_VARIANT_NV12 : 0);
     job.preset = preset;
     while ((1u << job.preset_bits) < frame_groups) /* hyd_cllog2, encoder.c:940 */
         job.preset_bits++;
@@ -1293,12 +1309,13 @@ int hydamd_encode_image(HydAmdContext *ctx, const void *const src[3], ptrdiff_t 
         return fail(ctx, ST_API_ERROR, "context has too few LF-group slots for this image");
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
+    if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
+        return fail(ctx, ST_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG);
     int st = hydamd_begin_frame(ctx, (unsigned)(lfx * lfy));
-    const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(sample_fmt);
     for (size_t ty = 0; ty < lfy && st == ST_OK; ty++)
         for (size_t tx = 0; tx < lfx && st == ST_OK; tx++) {
-            const ptrdiff_t off = ((ptrdiff_t)(ty * 2048) * row_stride + (ptrdiff_t)(tx * 2048) * pixel_stride) * ss;
-            const void *p[3] = {(const char *)src[0] + off, (const char *)src[1] + off, (const char *)src[2] + off};
+            const void *p[3];
+            hyd_fmt_origin(sample_fmt, src, row_stride, pixel_stride, tx * 2048, ty * 2048, p);
             const size_t w = width - tx * 2048 < 2048 ? width - tx * 2048 : 2048;
             const size_t h = height - ty * 2048 < 2048 ? height - ty * 2048 : 2048;
             st = hydamd_encode_lf_group(ctx, (int)(ty * lfx + tx), p, row_stride, pixel_stride, sample_fmt, w, h,
@@ -1366,17 +1383,19 @@ int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const 
         return fail(ctx, ST_API_ERROR, "empty image");
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
+    for (int f = 0; f < frames; f++)
+        if (src[3 * (size_t)f + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * (size_t)f, pixel_stride))
+            return fail(ctx, ST_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG);
     const size_t lfx = (width + 2047) >> 11, lfy = (height + 2047) >> 11, n = lfx * lfy;
     int st = hydamd_begin_batch(ctx, (unsigned)n, frames);
-    const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(sample_fmt);
     for (int f = 0; f < frames && st == ST_OK; f++) {
         const void *const *s3 = src + 3 * (size_t)f;
         if (!s3[0] || !s3[1] || !s3[2])
             return fail(ctx, ST_API_ERROR, "null pixel pointer");
         for (size_t ty = 0; ty < lfy && st == ST_OK; ty++)
             for (size_t tx = 0; tx < lfx && st == ST_OK; tx++) {
-                const ptrdiff_t off = ((ptrdiff_t)(ty * 2048) * row_stride + (ptrdiff_t)(tx * 2048) * pixel_stride) * ss;
-                const void *p[3] = {(const char *)s3[0] + off, (const char *)s3[1] + off, (const char *)s3[2] + off};
+                const void *p[3];
+                hyd_fmt_origin(sample_fmt, s3, row_stride, pixel_stride, tx * 2048, ty * 2048, p);
                 const size_t w = width - tx * 2048 < 2048 ? width - tx * 2048 : 2048;
                 const size_t h = height - ty * 2048 < 2048 ? height - ty * 2048 : 2048;
                 st = hydamd_encode_lf_group(ctx, (int)((size_t)f * n + ty * lfx + tx), p, row_stride, pixel_stride, sample_fmt, w, h,
@@ -1394,8 +1413,8 @@ static int transform_range(HydAmdContext *ctx, int first, int count) {
     for (int i = first; i < first + count; i++) {
         if (ctx->h_jobs[i].width == 0)
             return fail(ctx, ST_API_ERROR, "an LF-group slot of this frame was never submitted");
-        /* bits 0, 1: the integer classes; bits 2 + HYDK_STORE_*: the float class by storage form (launch_transform) */
-        mask |= 1u << (ctx->h_jobs[i].fmt + (ctx->h_jobs[i].fmt == HYDK_FMT_F32 ? (int)ctx->h_jobs[i].storage : 0));
+        /* bits 0, 1: the integer classes' own samples; bits 2 + HYDK_STORE_*: the storage forms (launch_transform) */
+        mask |= 1u << (ctx->h_jobs[i].storage ? HYDK_FMT_F32 + (int)ctx->h_jobs[i].storage : ctx->h_jobs[i].fmt);
     }
     ctx->status_published = false;
     /* the descriptors travel by a kernel that reads the pinned ring; the frame's first such launch also
@@ -2685,6 +2704,55 @@ __attribute__((visibility("default"))) int hydt_widen_half_device(int device, in
     }
     if (e == hipSuccess)
         e = hipMemcpy(out, d_out, kN * sizeof(uint32_t), hipMemcpyDeviceToHost); /* (waits for the kernel) */
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the YCbCr conversion (hydk_yuv.h) as the host compiler built it
+ * and as the device runs it.  matrix: HYDK_YUV_* (0 ... 3); yuv holds n (Y, U, V) byte triples, rgb receives n (R, G, B). */
+__attribute__((visibility("default"))) int hydt_yuv_to_rgb_host(int matrix, const uint8_t *yuv, uint8_t *rgb, size_t n) {
+    if (matrix < 0 || matrix >= HYDK_YUV_MATRICES || !yuv || !rgb)
+        return ST_API_ERROR;
+    const HydkYuvMatrix m = hydk_yuv_matrix(matrix);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t out[3];
+        hydk_yuv_to_rgb(m, yuv[3 * i], yuv[3 * i + 1], yuv[3 * i + 2], out);
+        for (int c = 0; c < 3; c++)
+            rgb[3 * i + c] = (uint8_t)out[c];
+    }
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_yuv_to_rgb_probe(int matrix, const uint8_t *yuv, uint8_t *rgb, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per triple */
+    if (i >= n)
+        return;
+    uint32_t out[3];
+    hydk_yuv_to_rgb(hydk_yuv_matrix(matrix), yuv[3 * i], yuv[3 * i + 1], yuv[3 * i + 2], out);
+    for (int c = 0; c < 3; c++)
+        rgb[3 * i + c] = (uint8_t)out[c];
+}
+} /* namespace */
+
+/* one launch over n triples (host arrays, n < 2^31) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_yuv_to_rgb_device(int device, int matrix, const uint8_t *yuv, uint8_t *rgb, size_t n) {
+    if (matrix < 0 || matrix >= HYDK_YUV_MATRICES || !yuv || !rgb || n == 0 || n >= ((size_t)1 << 31) ||
+        hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_in, 3 * n);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&d_out, 3 * n);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_in, yuv, 3 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_yuv_to_rgb_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, matrix, d_in, d_out, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpy(rgb, d_out, 3 * n, hipMemcpyDeviceToHost); /* (waits for the kernel) */
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return e == hipSuccess ? ST_OK : ST_API_ERROR;

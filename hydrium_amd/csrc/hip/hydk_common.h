@@ -11,9 +11,12 @@
 #include <stdint.h>
 
 #include "hydk_half.h" /* HYDK_STORE_*: how a float-class LF group's samples are stored */
+#include "hydk_yuv.h"  /* HYDK_STORE_NV12: an 8-bit-class LF group whose pixels are an NV12 picture */
 
 /* sample CLASSES: what a job's fmt and the transform kernel's FMT name.  Half-precision pixels (hyd_sample_fmt.h: 3, 4) are
- * float-class jobs — fmt == HYDK_FMT_F32 means "float class" everywhere — whose storage field says how to load a sample */
+ * float-class jobs — fmt == HYDK_FMT_F32 means "float class" everywhere — whose storage field says how to load a sample;
+ * NV12 pictures (16 ... 19) are 8-bit-class jobs of storage HYDK_STORE_NV12: 8-bit RGB from the load on (hydk_yuv.h) */
+#define HYDK_VARIANT_NV12 8 /* HydkLfJob.use_luts of an NV12 job: XYB mode + 8 */
 #define HYDK_FMT_U8 0
 #define HYDK_FMT_U16 1
 #define HYDK_FMT_F32 2
@@ -87,7 +90,8 @@ typedef struct HydkLfJob {
     int width, height;       /* LF group size in pixels */
     int gcols, grows;        /* groups across / down */
     int scheme;              /* HF clustering scheme 0..3 = 9 / 3 / 2 / 1 clusters per preset */
-    int use_luts;            /* 1: gather from the uploaded LUTs instead of evaluating them in registers */
+    int use_luts;            /* which transform kernel variant owns the job: the XYB mode it was recorded under (0, 1: curves in
+                              * registers, 2: gathers from the uploaded LUTs), + HYDK_VARIANT_NV12 for storage HYDK_STORE_NV12 */
     unsigned preset;         /* HF preset id of this LF group (written in front of each group section) */
     unsigned short preset_bits; /* hyd_cllog2(LF groups of this LF group's frame): the width of that field (encoder.c:940) */
     unsigned short frame_first; /* the first slot of this LF group's frame: where the running alphabet maximum starts afresh */
@@ -107,9 +111,12 @@ typedef struct HydkLfJob {
     int32_t *dbg_quant;
     uint32_t *bad_slot;      /* per-slot outcomes (hydamd_set_bad_sample_per_slot): this slot's flag word, cleared with the frame's
                               * accumulators — a non-finite float sample sets it and is coded as 0.0; NULL: the launch-wide status bit */
-    uint32_t storage;        /* float class only: HYDK_STORE_F32 (0, what a zeroed job says), _F16 or _BF16 — 2-byte samples, widened on load */
+    uint32_t storage;        /* float class: HYDK_STORE_F32 (0, what a zeroed job says), _F16 or _BF16 — 2-byte samples, widened on load;
+                              * 8-bit class: 0 (RGB samples) or HYDK_STORE_NV12 — src[0] the Y plane, src[1], src[2] the U and V bytes of the
+                              * chroma plane, row_stride the pitch of both */
     uint32_t per_sample;     /* probe flavour only (HYDAMD_DEBUG_HALF_PER_SAMPLE, for A/B): bit 0 interleaved, bit 1 planar half rows
                               * go through the per-sample loader although they qualify for the dword runs; the product leaves 0 */
+    uint32_t matrix;         /* HYDK_STORE_NV12 only: HYDK_YUV_* (0 ... 3), the YCbCr matrix and range */
 } HydkLfJob;
 
 /* ---- LF-group coder (the modular sub-stream of the LF coefficients, encoder.c:560-596) ----

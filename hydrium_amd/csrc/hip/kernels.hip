@@ -602,12 +602,16 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
 
 #define HYDK_K1_OCCUPANCY __launch_bounds__(kThreads, HYDK_K1_WAVES)
 /* STORE: how a float-class instance's samples are stored (HYDK_STORE_*); a half-precision sample is widened exactly on load
- * (hydk_half.h) and is a float32 sample from there on.  The integer instances know one storage form each. */
+ * (hydk_half.h) and is a float32 sample from there on.  The 8-bit class has one storage form beside its RGB samples:
+ * HYDK_STORE_NV12, a Y plane and a half-resolution plane of U, V pairs — a pixel is converted right after the load
+ * (hydk_yuv.h) and is an 8-bit RGB pixel from the transfer-curve lookup on.  The 16-bit class knows one form. */
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
-    static_assert(STORE == HYDK_STORE_F32 || FMT == HYDK_FMT_F32, "only the float class has storage forms");
-    constexpr bool HALF = STORE != HYDK_STORE_F32;
+    static_assert(STORE == HYDK_STORE_F32 || (STORE == HYDK_STORE_NV12 ? FMT == HYDK_FMT_U8 : FMT == HYDK_FMT_F32),
+                  "the float class has the half-precision storage forms, the 8-bit class NV12");
+    constexpr bool NV12 = STORE == HYDK_STORE_NV12;
+    constexpr bool HALF = STORE != HYDK_STORE_F32 && !NV12;
     typedef typename std::conditional<HALF, uint16_t, typename SampleOf<FMT>::type>::type sample_t;
     constexpr bool LUTS = XMODE == kXybGather;
     constexpr int kWords = FMT == HYDK_FMT_U8 ? 6 : 12; /* dwords holding 8 packed RGB pixels */
@@ -619,7 +623,9 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
      * its symbols in its own share of the group's token array and k_join_parts closes the gaps (round 5) */
     const unsigned bid = blockIdx.x >> plog, part = blockIdx.x & ((1u << plog) - 1u);
     const HydkLfJob job = jobs[bid >> 6];
-    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE)) || (FMT == HYDK_FMT_F32 && job.storage != (uint32_t)STORE))
+    /* (an NV12 job names its variant as mode + HYDK_VARIANT_NV12: the 8-bit instances' own test turns it away as it stands) */
+    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE) + (NV12 ? HYDK_VARIANT_NV12 : 0)) ||
+        (FMT == HYDK_FMT_F32 && job.storage != (uint32_t)STORE))
         return; /* another template instance of this launch round owns this LF group */
     if ((int)(bid & 63) >= job.gcols * job.grows)
         return;
@@ -697,7 +703,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     /* first cluster holding coefficient contexts, by scheme (encoder.c:862-901) */
     const int coef_cl_lo = job.scheme == 0 ? 3 : job.scheme == 3 ? 0 : 1;
 
-    const bool packed = job.pixel_stride == 3 &&
+    const bool packed = !NV12 && job.pixel_stride == 3 &&
                         (const char *)job.src[1] == (const char *)job.src[0] + sizeof(sample_t) &&
                         (const char *)job.src[2] == (const char *)job.src[0] + 2 * sizeof(sample_t) &&
                         (((uintptr_t)job.src[0] | (uintptr_t)(job.row_stride * (long long)sizeof(sample_t))) & 3) == 0 &&
@@ -727,7 +733,11 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
             hrun = 2;
     }
     const bool hfast = HALF && hrun != 0 && ab < gbw && ab * 8 + 8 <= gw;
-    const bool fast = packed && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
+    /* NV12: a block row is two dwords of Y and, from chroma row y >> 1, two dwords of U, V pairs (a pair serves two pixels, and
+     * the block's first column is even) when both planes and the pitch are dword multiples; anything else reads byte by byte */
+    const bool nvrun = NV12 && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)job.row_stride) & 3) == 0;
+    const HydkYuvMatrix yuv = hydk_yuv_matrix(NV12 ? (int)job.matrix : 0);
+    const bool fast = (NV12 ? nvrun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
     uint32_t nxt[kWords];
 #pragma unroll
     for (int k = 0; k < kWords; k++)
@@ -749,6 +759,19 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                         for (int k = 0; k < 4; k++)
                             nxt[4 * c + k] = HYDK_GLOBAL(const uint32_t, p)[k];
                     }
+                }
+            }
+            return;
+        }
+        if (NV12) {
+            if (fast && s * 8 + ar < gh) {
+                const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
+                const char *py = (const char *)job.src[0] + y * job.row_stride + x;
+                const char *pc = (const char *)job.src[1] + (y >> 1) * job.row_stride + x;
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    nxt[k] = HYDK_GLOBAL(const uint32_t, py)[k];
+                    nxt[2 + k] = HYDK_GLOBAL(const uint32_t, pc)[k];
                 }
             }
             return;
@@ -820,7 +843,25 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                 }
                 prefetch(s + 1);
             } else if (fast) {
-                uint32_t(&w)[kWords] = nxt; /* this strip's pixels, fetched a strip ago */
+                /* NV12: the eight pixels of the four fetched dwords, converted and packed as an interleaved RGB row has them */
+                uint32_t cvt[kWords];
+                if (NV12) {
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        cvt[k] = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        uint32_t rgb[3];
+                        hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, (nxt[2 + (i >> 2)] >> (8 * (i & 2))) & 0xFF,
+                                        (nxt[2 + (i >> 2)] >> (8 * (i & 2) + 8)) & 0xFF, rgb);
+#pragma unroll
+                        for (int ch = 0; ch < 3; ch++) {
+                            const int si = i * 3 + ch;
+                            cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
+                        }
+                    }
+                }
+                uint32_t(&w)[kWords] = NV12 ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
                 /* which form of the transfer curve this wavefront's 16-bit samples need (wave-uniform) */
                 int curve = kCurveBoth;
                 if (FMT == HYDK_FMT_U16 && !LUTS) {
@@ -949,9 +990,11 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                     xv[i] = yv[i] = bv[i] = 0.0f; /* edge padding is XYB = 0 (format.c:182-191) */
                     if (i < nvalid) {
                         const long long off = (long long)y * job.row_stride + (long long)(x0 + i) * job.pixel_stride;
+                        /* (NV12: the pixel's Y; its U and V sit in chroma row y >> 1 at the even byte x & ~1 and behind it) */
+                        const long long offc = NV12 ? (long long)(y >> 1) * job.row_stride + (long long)((x0 + i) & ~1) : off;
                         const sample_t sr = ((const sample_t *)job.src[0])[off];
-                        const sample_t sg = ((const sample_t *)job.src[1])[off];
-                        const sample_t sb = ((const sample_t *)job.src[2])[off];
+                        const sample_t sg = ((const sample_t *)job.src[1])[offc];
+                        const sample_t sb = ((const sample_t *)job.src[2])[offc];
                         if (FMT == HYDK_FMT_F32) {
                             float fr, fg, fb;
                             if (HALF) {
@@ -964,6 +1007,8 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                             float_pixel(fr, fg, fb, xv[i], yv[i], bv[i]);
                         } else {
                             uint32_t rgb[3] = {(uint32_t)sr, (uint32_t)sg, (uint32_t)sb};
+                            if (NV12)
+                                hydk_yuv_to_rgb(yuv, (uint32_t)sr, (uint32_t)sg, (uint32_t)sb, rgb);
 #pragma unroll
                             for (int ch = 0; ch < 3; ch++) {
                                 if (FMT == HYDK_FMT_U8)
@@ -2958,8 +3003,8 @@ __global__ void k_lut_selftest(const uint16_t *in_lut16, const float *bias_lut, 
 namespace hydk {
 
 /* One launch per template instance that owns at least one LF group of this round; an instance
- * returns at once for the LF groups of another sample format.  fmt_mask: bits 0, 1 the integer classes, bits 2 + HYDK_STORE_*
- * the float class's storage forms. */
+ * returns at once for the LF groups of another sample format.  fmt_mask: bits 0, 1 the integer classes' own samples, bits
+ * 2 + HYDK_STORE_* the storage forms: the float class's three, and NV12 of the 8-bit class. */
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream) {
     const dim3 grid((num_slots * HYDK_GROUPS_PER_LFG) << plog), block(kThreads);
@@ -2989,6 +3034,19 @@ hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt
     HYDK_LAUNCH_K1_FLOAT(HYDK_STORE_F16);
     HYDK_LAUNCH_K1_FLOAT(HYDK_STORE_BF16);
 #undef HYDK_LAUNCH_K1_FLOAT
+    /* NV12: the 8-bit class's three XYB modes; the all-register variants (3, 4: dense content) differ from 0 and 1 in where a
+     * curve value comes from, never in its bits, and NV12 keeps to the three */
+    if (fmt_mask & (1u << (HYDK_FMT_F32 + HYDK_STORE_NV12))) {
+#define HYDK_LAUNCH_K1_NV12(XM) \
+    hipLaunchKernelGGL((k_transform_tokenize<HYDK_FMT_U8, XM, HYDK_STORE_NV12>), grid, block, 0, stream, d_jobs, status, part_info, plog)
+        if (xyb_arith(xmode) == kXybFastRcp)
+            HYDK_LAUNCH_K1_NV12(kXybFastRcp);
+        else if (xyb_arith(xmode) == kXybIeeeDiv)
+            HYDK_LAUNCH_K1_NV12(kXybIeeeDiv);
+        else
+            HYDK_LAUNCH_K1_NV12(kXybGather);
+#undef HYDK_LAUNCH_K1_NV12
+    }
 #undef HYDK_LAUNCH_K1_MODES
 #undef HYDK_LAUNCH_K1
     if (plog)
@@ -3005,7 +3063,14 @@ hipError_t transform_footprint(int fmt, int storage, int xmode, int *lds_bytes, 
         fn = (const void *)k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, HYDK_STORE_BF16>;
     else if (fmt == HYDK_FMT_F32)
         HYDK_K1_PTR(HYDK_FMT_F32, kXybIeeeDiv);
-    else if (fmt == HYDK_FMT_U8) {
+    else if (fmt == HYDK_FMT_U8 && storage == HYDK_STORE_NV12) {
+        if (xmode == kXybFastRcp)
+            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybFastRcp, HYDK_STORE_NV12>;
+        else if (xmode == kXybIeeeDiv)
+            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybIeeeDiv, HYDK_STORE_NV12>;
+        else
+            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybGather, HYDK_STORE_NV12>;
+    } else if (fmt == HYDK_FMT_U8) {
         if (xmode == kXybFastRcp)
             HYDK_K1_PTR(HYDK_FMT_U8, kXybFastRcp);
         else if (xmode == kXybIeeeDiv)

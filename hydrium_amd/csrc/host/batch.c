@@ -314,6 +314,9 @@ HYDRIUM_EXPORT int hydamd_encode_batch(HydAmdBatch *b, int frames, const void *c
             return fail(b, HYD_API_ERROR, "null pixel pointer", NULL);
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(b, HYD_API_ERROR, "Invalid Sample Format", NULL);
+    for (int f = 0; f < frames; f++)
+        if (!hyd_fmt_layout_ok(sample_fmt, src + 3 * f, pixel_stride))
+            return fail(b, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
     if (b->in_flight)
         return fail(b, HYD_API_ERROR, "a batch is in flight: hydamd_batch_result first", NULL);
     b->err[0] = 0;

@@ -485,12 +485,11 @@ static int enqueue_several(HydAmdMixed *m, const HydAmdImageDesc *images, const 
     for (int f = 0; f < m->frames; f++) {
         const HydAmdImageDesc *d = &images[f];
         const int sample_fmt = sample_fmts[f];
-        const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(sample_fmt);
         const size_t lfx = (d->width + 2047) >> 11, lfy = (d->height + 2047) >> 11;
         for (size_t ty = 0; ty < lfy; ty++)
             for (size_t tx = 0; tx < lfx; tx++, slot++) {
-                const ptrdiff_t off = ((ptrdiff_t)(ty * 2048) * d->row_stride + (ptrdiff_t)(tx * 2048) * d->pixel_stride) * ss;
-                const void *p[3] = {(const char *)d->src[0] + off, (const char *)d->src[1] + off, (const char *)d->src[2] + off};
+                const void *p[3];
+                hyd_fmt_origin(sample_fmt, d->src, d->row_stride, d->pixel_stride, tx * 2048, ty * 2048, p);
                 const size_t w = d->width - tx * 2048 < 2048 ? d->width - tx * 2048 : 2048;
                 const size_t h = d->height - ty * 2048 < 2048 ? d->height - ty * 2048 : 2048;
                 if ((st = hydamd_encode_lf_group(m->ctx, slot, p, d->row_stride, d->pixel_stride, sample_fmt, w, h, (unsigned)(ty * lfx + tx))) != 0)
@@ -553,6 +552,9 @@ HYDRIUM_EXPORT int hydamd_encode_mixed_formats(HydAmdMixed *m, int frames, const
     for (int f = 0; f < frames; f++)
         if (!hyd_fmt_is_device(sample_fmts[f]))
             return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
+    for (int f = 0; f < frames; f++)
+        if (!hyd_fmt_layout_ok(sample_fmts[f], images[f].src, images[f].pixel_stride))
+            return fail(m, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
     if (m->in_flight)
         return fail(m, HYD_API_ERROR, "a batch is in flight: hydamd_mixed_result first", NULL);
     m->err[0] = 0;

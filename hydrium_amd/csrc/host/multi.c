@@ -155,9 +155,11 @@ HYDRIUM_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *
         return fail(m, HYD_API_ERROR, "bad arguments", NULL);
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
+    for (int d = 0; d < f->n; d++)
+        if (src[3 * d + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * d, pixel_stride))
+            return fail(m, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
     if (m->in_flight)
         return fail(m, HYD_API_ERROR, "a frame is in flight: hydamd_multi_result first", NULL);
-    const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(sample_fmt);
     const size_t W = m->md.width, H = m->md.height;
     int st;
     f->assembling = assembling_shard;
@@ -171,8 +173,8 @@ HYDRIUM_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *
             return fail(m, st, "begin frame", c);
         for (size_t i = 0; i < f->slots[d]; i++) {
             const size_t g = m->first[d] + i, tx = g % m->lfx, ty = g / m->lfx;
-            const ptrdiff_t off = ((ptrdiff_t)(ty * 2048) * row_stride + (ptrdiff_t)(tx * 2048) * pixel_stride) * ss;
-            const void *p[3] = {(const char *)src[3 * d] + off, (const char *)src[3 * d + 1] + off, (const char *)src[3 * d + 2] + off};
+            const void *p[3];
+            hyd_fmt_origin(sample_fmt, src + 3 * d, row_stride, pixel_stride, tx * 2048, ty * 2048, p);
             const size_t w = W - tx * 2048 < 2048 ? W - tx * 2048 : 2048, h = H - ty * 2048 < 2048 ? H - ty * 2048 : 2048;
             if ((st = hydamd_encode_lf_group(c, (int)i, p, row_stride, pixel_stride, sample_fmt, w, h, (unsigned)g)) != 0)
                 return fail(m, st, "LF group", c);

@@ -326,14 +326,13 @@ static int assemble_group(HydAmdTiled *t) {
 static int enqueue_group(HydAmdTiled *t) {
     const TileGeometry *g = &t->g;
     const size_t left = g->ntiles - t->next, n = left < (size_t)t->launch ? left : (size_t)t->launch;
-    const ptrdiff_t ss = (ptrdiff_t)hyd_fmt_bytes(t->fmt);
     int st = hydamd_begin_batch(t->ctx, 1, (int)n);
     if (st)
         return fail(t, st, "begin launch group", hydamd_error(t->ctx));
     for (size_t i = 0; i < n; i++) {
         const size_t k = t->next + i, tx = k % g->ntx, ty = k / g->ntx;
-        const ptrdiff_t off = ((ptrdiff_t)(ty * g->th) * t->row_stride + (ptrdiff_t)(tx * g->tw) * t->pixel_stride) * ss;
-        const void *p[3] = {(const char *)t->src[0] + off, (const char *)t->src[1] + off, (const char *)t->src[2] + off};
+        const void *p[3];
+        hyd_fmt_origin(t->fmt, t->src, t->row_stride, t->pixel_stride, tx * g->tw, ty * g->th, p);
         const size_t w = (tx + 1) * g->tw > g->W ? g->W - tx * g->tw : g->tw, h = (ty + 1) * g->th > g->H ? g->H - ty * g->th : g->th;
         if ((st = hydamd_encode_lf_group(t->ctx, (int)i, p, t->row_stride, t->pixel_stride, t->fmt, w, h, 0)) != 0)
             return fail(t, st, "tile", hydamd_error(t->ctx));
@@ -352,6 +351,8 @@ HYDRIUM_EXPORT int hydamd_encode_image_tiled(HydAmdTiled *t, const void *const s
         return fail(t, HYD_API_ERROR, "null pixel pointer", NULL);
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(t, HYD_API_ERROR, "Invalid Sample Format", NULL);
+    if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
+        return fail(t, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
     if (t->in_flight)
         return fail(t, HYD_API_ERROR, "an image is in flight: hydamd_tiled_result first", NULL);
     t->err[0] = 0;

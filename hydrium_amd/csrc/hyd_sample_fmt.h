@@ -4,6 +4,11 @@
  * 0, 1, 2 are the drop-in API's HYDSampleFormat (include/libhydrium/libhydrium.h); 3 and 4 (include/hydrium_amd.h) name
  * pixels that already sit in device memory as IEEE binary16 or bfloat16.  Half precision is a STORAGE FORM of the float
  * class: a sample is widened exactly on load and from there on is a float32 sample (hip/hydk_half.h).
+ *
+ * 16 ... 19 (include/hydrium_amd.h) name NV12 pictures in device memory: an 8-bit Y plane and a half-resolution plane of
+ * interleaved U, V pairs, under one of four matrices.  NV12 is a storage form of the 8-BIT class: a pixel becomes an
+ * ordinary 8-bit RGB pixel right after the load (hip/hydk_yuv.h).  src[0] is the first Y sample, src[1] the first U sample,
+ * src[2] == src[1] + 1, the pixel stride is 1 and the row stride is the pitch of both planes in bytes.
  */
 #ifndef HYD_SAMPLE_FMT_H_
 #define HYD_SAMPLE_FMT_H_
@@ -15,9 +20,17 @@
 #define HYD_FMT_FLOAT32 2
 #define HYD_FMT_FLOAT16 3
 #define HYD_FMT_BFLOAT16 4
+#define HYD_FMT_NV12_BT709 16
+#define HYD_FMT_NV12_BT709_FULL 17
+#define HYD_FMT_NV12_BT601 18
+#define HYD_FMT_NV12_BT601_FULL 19
+
+/* YCbCr 4:2:0 in two planes, and which of the four matrices of hip/hydk_yuv.h (0 ... 3) */
+static inline int hyd_fmt_is_nv12(int fmt) { return fmt >= HYD_FMT_NV12_BT709 && fmt <= HYD_FMT_NV12_BT601_FULL; }
+static inline int hyd_fmt_nv12_matrix(int fmt) { return fmt - HYD_FMT_NV12_BT709; }
 
 /* what an entry point that reads DEVICE pixels takes */
-static inline int hyd_fmt_is_device(int fmt) { return fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_BFLOAT16; }
+static inline int hyd_fmt_is_device(int fmt) { return (fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_BFLOAT16) || hyd_fmt_is_nv12(fmt); }
 /* what an entry point that reads HOST pixels takes: the reference's three */
 static inline int hyd_fmt_is_host(int fmt) { return fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_FLOAT32; }
 /* float class: 8-byte token records, 72 histogram bins, the non-finite check */
@@ -26,6 +39,10 @@ static inline int hyd_fmt_is_float(int fmt) { return fmt >= HYD_FMT_FLOAT32 && f
 static inline size_t hyd_fmt_bytes(int fmt) {
     switch (fmt) {
     case HYD_FMT_UINT8:
+    case HYD_FMT_NV12_BT709:
+    case HYD_FMT_NV12_BT709_FULL:
+    case HYD_FMT_NV12_BT601:
+    case HYD_FMT_NV12_BT601_FULL:
         return 1;
     case HYD_FMT_UINT16:
     case HYD_FMT_FLOAT16:
@@ -36,6 +53,31 @@ static inline size_t hyd_fmt_bytes(int fmt) {
     default:
         return 0;
     }
+}
+
+/* NV12's layout: unit pixel stride and V one byte behind U; every other format takes any layout.  An entry point that
+ * finds 0 here fails with HYD_FMT_NV12_LAYOUT_MSG before it enqueues anything. */
+#define HYD_FMT_NV12_LAYOUT_MSG "NV12 wants pixel_stride 1 and V one byte behind U"
+static inline int hyd_fmt_layout_ok(int fmt, const void *const src[3], ptrdiff_t pixel_stride) {
+    return !hyd_fmt_is_nv12(fmt) || (pixel_stride == 1 && (const char *)src[2] == (const char *)src[1] + 1);
+}
+
+/* The three origin pointers of the sub-rectangle at pixel (x0, y0) of a picture of a device format — an LF group, a tile, a
+ * shard's first row.  Strides are in samples.  NV12: the chroma plane has a row for every two picture rows and two bytes for
+ * every two columns, so its origin is row y0 / 2, byte x0; x0 and y0 must be even (every origin the library computes is a
+ * multiple of 256). */
+static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride, size_t x0,
+                                  size_t y0, const void *origin[3]) {
+    if (hyd_fmt_is_nv12(fmt)) {
+        const ptrdiff_t chroma = (ptrdiff_t)(y0 / 2) * row_stride + (ptrdiff_t)x0;
+        origin[0] = (const char *)src[0] + (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;
+        origin[1] = (const char *)src[1] + chroma;
+        origin[2] = (const char *)src[2] + chroma;
+        return;
+    }
+    const ptrdiff_t off = ((ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0 * pixel_stride) * (ptrdiff_t)hyd_fmt_bytes(fmt);
+    for (int c = 0; c < 3; c++)
+        origin[c] = (const char *)src[c] + off;
 }
 
 #endif /* HYD_SAMPLE_FMT_H_ */

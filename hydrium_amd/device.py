@@ -27,11 +27,63 @@ FMT_OF_DTYPE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float
 # device pixels only (include/hydrium_amd.h, HYDAMD_FLOAT16 / HYDAMD_BFLOAT16): half-precision samples, widened exactly on load
 FLOAT16 = 3
 BFLOAT16 = 4
+# device pixels only (HYDAMD_NV12_*): a decoder's NV12 surface — an 8-bit Y plane and a half-resolution plane of U, V pairs —
+# under one of four matrices; converted in fixed point right after the load (csrc/hip/hydk_yuv.h)
+NV12_BT709 = 16       # BT.709, limited range: HD video
+NV12_BT709_FULL = 17  # BT.709, full range
+NV12_BT601 = 18       # BT.601, limited range: SD video
+NV12_BT601_FULL = 19  # BT.601, full range: what a JPEG decoder leaves (JFIF)
+NV12_FORMATS = (NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL)
+
+
+class Nv12:
+    """An NV12 picture in device memory, accepted wherever an image tensor is (DeviceContext.encode_image_tensor and
+    encode_image_batch, FrameBatch, MixedBatch, TiledImage, MultiFrame).
+
+    ``y``: uint8 tensor (H, W) with unit column stride.  ``uv``: uint8 tensor (ceil(H / 2), ceil(W / 2), 2) with strides
+    (pitch, 2, 1), U first; its pitch is the Y plane's (NV12 has one pitch).  ``matrix``: one of NV12_FORMATS.  A crop of a
+    larger surface must start on even coordinates (y[y0:, x0:] with uv[y0 // 2:, x0 // 2:])."""
+
+    def __init__(self, y, uv, matrix: int = NV12_BT709):
+        if int(matrix) not in NV12_FORMATS:
+            raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL")
+        if y.element_size() != 1 or uv.element_size() != 1 or y.dim() != 2 or uv.dim() != 3:
+            raise ValueError("NV12 planes are 8-bit: y (H, W), uv (ceil(H / 2), ceil(W / 2), 2)")
+        h, w = y.shape
+        if h < 1 or w < 1 or tuple(uv.shape) != (-(-h // 2), -(-w // 2), 2):
+            raise ValueError("the chroma plane of an (H, W) picture is (ceil(H / 2), ceil(W / 2), 2)")
+        if y.stride(1) != 1 or (uv.stride(1), uv.stride(2)) != (2, 1):
+            raise ValueError("NV12 planes have unit column stride: y (pitch, 1), uv (pitch, 2, 1)")
+        if uv.shape[0] > 1 and h > 1 and uv.stride(0) != y.stride(0):
+            raise ValueError("the two planes of an NV12 picture share one pitch")
+        self.y, self.uv, self.sample_fmt = y, uv, int(matrix)
+        self.height, self.width = int(h), int(w)
+        self.pitch = int(y.stride(0) if h > 1 else uv.stride(0) if uv.shape[0] > 1 else max(y.stride(0), uv.stride(0)))
+
+    @classmethod
+    def from_surface(cls, buf, width: int, height: int, pitch: int, chroma_offset: int, matrix: int = NV12_BT709):
+        """A decoder's single allocation: ``buf`` a 1-D uint8 tensor, Y rows at 0, pitch, 2 * pitch ..., chroma rows at
+        chroma_offset, chroma_offset + pitch ... (bytes)."""
+        y = buf.as_strided((height, width), (pitch, 1), 0)
+        uv = buf.as_strided((-(-height // 2), -(-width // 2), 2), (pitch, 2, 1), chroma_offset)
+        return cls(y, uv, matrix)
+
+    @property
+    def shape(self):
+        return (self.height, self.width, 3)
+
+    def pointers(self):
+        """src[0 ... 2] of the C API: Y, U, V = U + 1."""
+        u = self.uv.data_ptr()
+        return [self.y.data_ptr(), u, u + 1]
 
 
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
-    float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0."""
+    float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
+    An Nv12 object: its own format."""
+    if isinstance(t, Nv12):
+        return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]
     if name == "float16":
         return FLOAT16
@@ -395,14 +447,17 @@ class DeviceContext:
         """Enqueue the hot path for every LF group of an interleaved (H, W, 3) torch CUDA tensor.
 
         The kernels read the tensor's memory asynchronously: the caller must keep it alive (and
-        unmodified) until ``sync()``."""
+        unmodified) until ``sync()``.  An Nv12 object goes the same way."""
         h, w, _ = img.shape
-        isz = img.element_size()
         fmt = sample_fmt_of(img)
         lfx, lfy = -(-w // 2048), -(-h // 2048)
         n = lfx * lfy
         if num_slots_check and n > self.max_lf_groups:
             raise ValueError("context has too few LF-group slots for this image")
+        if isinstance(img, Nv12):
+            self._ck(self.d.hydamd_encode_image(self.h, (C.c_void_p * 3)(*img.pointers()), img.pitch, 1, fmt, w, h))
+            return n
+        isz = img.element_size()
         if not getattr(self, "per_lf_group_calls", False):
             # one C call per frame (hydamd_encode_image): eighteen ctypes calls cost the host as much as the GPU needs
             base = img.data_ptr()
@@ -422,14 +477,22 @@ class DeviceContext:
 
     def encode_image_batch(self, imgs):
         """Enqueue a batch of interleaved (H, W, 3) torch CUDA tensors of one shape as one launch group
-        (hydamd_encode_image_batch): frame k in slots k * n ... (k + 1) * n - 1."""
+        (hydamd_encode_image_batch): frame k in slots k * n ... (k + 1) * n - 1.  Or of Nv12 objects of one shape, pitch
+        and matrix."""
         h, w, _ = imgs[0].shape
-        isz = imgs[0].element_size()
         fmt = sample_fmt_of(imgs[0])
         n = (-(-w // 2048)) * (-(-h // 2048))
         if n * len(imgs) > self.max_lf_groups:
             raise ValueError("context has too few LF-group slots for this batch")
         ptrs = []
+        if isinstance(imgs[0], Nv12):
+            for t in imgs:
+                assert isinstance(t, Nv12) and (t.shape, t.pitch, t.sample_fmt) == (imgs[0].shape, imgs[0].pitch, fmt)
+                ptrs += t.pointers()
+            arr = (C.c_void_p * len(ptrs))(*ptrs)
+            self._ck(self.d.hydamd_encode_image_batch(self.h, len(imgs), arr, imgs[0].pitch, 1, fmt, w, h))
+            return n * len(imgs)
+        isz = imgs[0].element_size()
         for t in imgs:
             assert t.shape == imgs[0].shape and t.dtype == imgs[0].dtype
             b = t.data_ptr()
@@ -599,7 +662,8 @@ class DeviceContext:
         return v.value
 
     def transform_footprint(self, sample_fmt: int):
-        """(static LDS bytes, registers per thread) of the transform kernel instance serving `sample_fmt` (0 u8, 1 u16, 2 f32, 3 f16, 4 bf16)."""
+        """(static LDS bytes, registers per thread) of the transform kernel instance serving `sample_fmt` (0 u8, 1 u16, 2 f32, 3 f16, 4 bf16,
+        16 ... 19 NV12)."""
         lds, regs = C.c_int(0), C.c_int(0)
         self._ck(self.d.hydamd_debug_transform_footprint(self.h, int(sample_fmt), C.byref(lds), C.byref(regs)))
         return lds.value, regs.value
@@ -782,7 +846,16 @@ class MultiFrame:
     def encode(self, origins, assembling_shard: int = 0):
         """origins[d]: an interleaved (H, W, 3) torch tensor on shard d's device holding (at least) that shard's LF
         groups at their place in the image — or an int: the device address pixel (0, 0) would have.  Asynchronous; the
-        tensors must stay alive until result()."""
+        tensors must stay alive until result().  Or Nv12 objects of the image's size, one pitch and one matrix."""
+        if origins and isinstance(origins[0], Nv12):
+            flat, o0 = [], origins[0]
+            for o in origins:
+                if not isinstance(o, Nv12) or (o.pitch, o.sample_fmt) != (o0.pitch, o0.sample_fmt):
+                    raise ValueError("the shards of a frame share one layout and sample format")
+                flat += o.pointers()
+            arr = (C.c_void_p * len(flat))(*flat)
+            self._ck(self.d.hydamd_encode_image_multi(self.h, arr, o0.pitch, 1, o0.sample_fmt, assembling_shard))
+            return
         ptrs, isz, fmt = [], None, None
         for o in origins:
             if hasattr(o, "data_ptr"):
@@ -850,8 +923,11 @@ class TiledImage:
     def encode(self, img, row_stride: Optional[int] = None, pixel_stride: Optional[int] = None, sample_fmt: Optional[int] = None):
         """img: an interleaved (H, W, C >= 3) torch tensor on the object's device (C > 3: the first three channels,
         pixel stride C), three (H, W) plane tensors, or three device addresses (then the strides, in samples, and the
-        sample format are the caller's).  Asynchronous: the pixels must stay alive and unchanged until result()."""
-        if hasattr(img, "data_ptr"):
+        sample format are the caller's), or an Nv12 object.  Asynchronous: the pixels must stay alive and unchanged until
+        result()."""
+        if isinstance(img, Nv12):
+            ptrs, row_stride, pixel_stride, sample_fmt = img.pointers(), img.pitch, 1, img.sample_fmt
+        elif hasattr(img, "data_ptr"):
             isz = img.element_size()
             ptrs = [img.data_ptr() + c * isz for c in range(3)]
             row_stride, pixel_stride = img.stride(0), img.stride(1)
@@ -933,7 +1009,10 @@ class FrameBatch:
         and unchanged until result()."""
         ptrs = []
         for img in imgs:
-            if hasattr(img, "data_ptr"):
+            if isinstance(img, Nv12):  # (one pitch and one matrix for all)
+                ptrs += img.pointers()
+                layout = (img.pitch, 1, img.sample_fmt)
+            elif hasattr(img, "data_ptr"):
                 isz = img.element_size()
                 ptrs += [img.data_ptr() + c * isz for c in range(3)]
                 layout = (img.stride(0), img.stride(1), sample_fmt_of(img))
@@ -1029,7 +1108,9 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
     fmts = []
     for k, img in enumerate(imgs):
         given = sample_fmts[k] if isinstance(sample_fmts, list) else sample_fmt
-        if hasattr(img, "data_ptr"):
+        if isinstance(img, Nv12):  # V one byte behind U, pixel stride 1, the pitch of both planes
+            ptrs, rs, ps, h, w, fmt = img.pointers(), img.pitch, 1, img.height, img.width, img.sample_fmt
+        elif hasattr(img, "data_ptr"):
             isz = img.element_size()
             ptrs = [img.data_ptr() + c * isz for c in range(3)]
             rs, ps, (h, w) = img.stride(0), img.stride(1), img.shape[:2]
@@ -1052,7 +1133,7 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
             elif fmt != sample_fmt:
                 raise ValueError("the images of a batch share one sample format")
         elif isinstance(sample_fmts, list) and fmt != given:
-            if given in (0, 1, 2, FLOAT16, BFLOAT16):
+            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FORMATS:
                 raise ValueError("sample_fmts disagrees with a tensor's dtype")
             fmt = given  # not a format at all: the library refuses it (HYD_API_ERROR), nothing is enqueued
         fmts.append(fmt)
@@ -1105,8 +1186,8 @@ class MixedBatch:
     def encode(self, imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
         """imgs: one entry per image, each of its own size and layout — an interleaved (H, W, C >= 3) torch tensor on the
         object's device (any row pitch; C > 3: the first three channels, pixel stride C), a triple of (H, W) plane
-        tensors, or (ptrs, row_stride, pixel_stride, width, height) with three device addresses and strides in samples
-        (then sample_fmt is the caller's).  One sample format per call, unless sample_fmts says otherwise: "each" takes
+        tensors, an Nv12 object, or (ptrs, row_stride, pixel_stride, width, height) with three device addresses and strides
+        in samples (then sample_fmt is the caller's).  One sample format per call, unless sample_fmts says otherwise: "each" takes
         every tensor's own dtype, a list names image k's format (0 / 1 / 2: 8-bit, 16-bit, float; what address tuples
         need).  Asynchronous: the pixels must stay alive and unchanged until result()."""
         descs, fmts = mixed_descriptors(imgs, sample_fmt, sample_fmts)

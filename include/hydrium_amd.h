@@ -129,17 +129,62 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * hydamd_encode_image_batch, hydamd_encode_batch, hydamd_encode_mixed, hydamd_encode_mixed_formats,
  * hydamd_encode_image_tiled, hydamd_encode_image_multi and hydamd_debug_transform_footprint.  Entry points that read HOST
  * pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse both with "Invalid Sample Format", as they and every
- * other entry point refuse anything outside 0..4.
+ * other entry point refuse anything that is neither 0..4 nor an NV12 format (16..19, below).
  */
 #define HYDAMD_FLOAT16 3
 #define HYDAMD_BFLOAT16 4
+
+/*
+ * NV12 DEVICE pixels: what a hardware video or JPEG decoder leaves in device memory — a full-resolution 8-bit Y plane and a
+ * half-resolution plane of interleaved U, V pairs (YCbCr 4:2:0) — read by the transform kernel as it is, without an RGB
+ * copy.  Four formats, by matrix and range:
+ *   HYDAMD_NV12_BT709       BT.709 matrix, limited range (Y 16..235, U and V 16..240): HD video
+ *   HYDAMD_NV12_BT709_FULL  BT.709 matrix, full range
+ *   HYDAMD_NV12_BT601       BT.601 matrix, limited range: SD video
+ *   HYDAMD_NV12_BT601_FULL  BT.601 matrix, full range: what a JPEG decoder leaves (JFIF)
+ * (the numbers start at 16: 5..15 and everything from 20 up stay "Invalid Sample Format").
+ *
+ * The file is byte for byte what the reference writes for the HYD_UINT8 picture this conversion produces.  For pixel (x, y):
+ * Y = luma[y][x]; U, V = the chroma pair at (x >> 1, y >> 1) (nearest neighbour: every 2 x 2 block shares one pair);
+ * c = Y - yo, d = U - 128, e = V - 128 in 32-bit integers, >> an arithmetic shift:
+ *   R = clamp((cy*c         + crv*e + 8192) >> 14, 0, 255)
+ *   G = clamp((cy*c - cgu*d - cgv*e + 8192) >> 14, 0, 255)
+ *   B = clamp((cy*c + cbu*d         + 8192) >> 14, 0, 255)
+ *                 yo     cy    crv    cgu    cgv    cbu
+ *   BT709         16  19077  29372   3494   8731  34610
+ *   BT709_FULL     0  16384  25802   3069   7670  30402
+ *   BT601         16  19077  26149   6419  13320  33050
+ *   BT601_FULL     0  16384  22970   5638  11700  29032
+ * — round(v * 2^14) of the real coefficients; within 0.51 of the clamped real-valued conversion for every (Y, U, V).
+ *
+ * How an NV12 picture is named, wherever a sample_fmt names device pixels (the list above) and in sample_fmts[k] of
+ * hydamd_encode_mixed_formats:
+ *   src[0]        the first Y sample of the picture or LF group
+ *   src[1]        the first U sample of its chroma row 0;  src[2] must equal src[1] + 1
+ *   pixel_stride  must be 1
+ *   row_stride    the pitch in bytes of BOTH planes, as NV12 defines it; may be negative.  Width and height may be odd: the
+ *                 chroma plane then holds ceil(w / 2) x ceil(h / 2) pairs, a chroma row 2 * ceil(w / 2) bytes.
+ * A bad src[2] or pixel_stride is HYD_API_ERROR "NV12 wants pixel_stride 1 and V one byte behind U", nothing enqueued.
+ * The library finds an LF group, tile or shard at pixel (x0, y0) at src[0] + y0 * row_stride + x0 and
+ * src[1] + (y0 / 2) * row_stride + x0; its own origins are multiples of 256.  A caller's own crop (a HydAmdImageDesc, or an
+ * LF group given to hydamd_encode_lf_group) must start on EVEN coordinates x0, y0 of the surface, or its pixels meet
+ * their neighbours' chroma: this cannot be checked.
+ * Entry points that read HOST pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse all four with "Invalid
+ * Sample Format".
+ * Out of scope: NV21, planar I420, 4:2:2 and 4:4:4; 10- and 16-bit P010 / P016 (they need a fixed-point derivation of their
+ * own); bilinear or siting-aware chroma upsampling; host-pointer NV12; any colour description other than the four above.
+ */
+#define HYDAMD_NV12_BT709 16
+#define HYDAMD_NV12_BT709_FULL 17
+#define HYDAMD_NV12_BT601 18
+#define HYDAMD_NV12_BT601_FULL 19
 
 /*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16 or HYDAMD_BFLOAT16.
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_* formats (whose src and strides are described above).
  */
 HYDAMD_EXPORT int hydamd_encode_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
                                          ptrdiff_t pixel_stride, int sample_fmt, size_t width, size_t height,
@@ -173,7 +218,7 @@ HYDAMD_EXPORT int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, cons
 
 /* Same, from HOST pointers: the samples are gathered into pinned staging (the caller's buffers may
  * be reused as soon as this returns, as after hyd_send_tile) and copied to the GPU on the stream.  sample_fmt is one of
- * HYD_UINT8, HYD_UINT16, HYD_FLOAT32: the half-precision formats name device pixels only. */
+ * HYD_UINT8, HYD_UINT16, HYD_FLOAT32: the half-precision and NV12 formats name device pixels only. */
 HYDAMD_EXPORT int hydamd_encode_lf_group_host(HydAmdContext *ctx, int slot, const void *const src[3],
                                               ptrdiff_t row_stride, ptrdiff_t pixel_stride, int sample_fmt,
                                               size_t width, size_t height, unsigned preset);
@@ -665,7 +710,7 @@ HYDAMD_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b);
  *                                its assembly and returns; the pixels stay borrowed until hydamd_mixed_result, the
  *                                descriptors only for the call.  The output buffer is sized before anything is
  *                                enqueued, from the batch's plan and the context's capacities.
- *   hydamd_encode_mixed_formats  the same with image k's samples in sample_fmts[k] (HYD_UINT8 / HYD_UINT16 / HYD_FLOAT32 / HYDAMD_FLOAT16 / HYDAMD_BFLOAT16):
+ *   hydamd_encode_mixed_formats  the same with image k's samples in sample_fmts[k] (HYD_UINT8 / HYD_UINT16 / HYD_FLOAT32 / HYDAMD_FLOAT16 / HYDAMD_BFLOAT16 / HYDAMD_NV12_*):
  *                                8-bit, 16-bit and float pictures side by side in one launch group, every file what the
  *                                reference writes for that picture in its format.  A bad entry is HYD_API_ERROR "Invalid
  *                                Sample Format" with nothing enqueued.  The plan and its reuse depend on sizes only.
@@ -696,7 +741,7 @@ HYDAMD_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b);
  * closing the throughput gap to the padded-classes upper reference that profiles/mixed_batch.txt records.
  */
 typedef struct HydAmdImageDesc {
-    const void *src[3];                 /* device pointers: R, G, B of the image's first pixel */
+    const void *src[3];                 /* device pointers: R, G, B of the image's first pixel (HYDAMD_NV12_*: Y, U, U + 1) */
     ptrdiff_t row_stride, pixel_stride; /* in samples, as hyd_send_tile's */
     size_t width, height;               /* 1..2048 each; hydamd_mixed_create_slots: >= 1, at most 28 LF groups of 2048 x 2048 */
 } HydAmdImageDesc;
