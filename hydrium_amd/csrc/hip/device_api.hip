@@ -64,8 +64,9 @@ hipError_t launch_lf_front(const HydkLfJob *d_jobs, unsigned long long *recs, ui
 hipError_t launch_lf_back(const HydkLfJob *d_jobs, const unsigned long long *recs, HydkLfStream *streams, uint32_t *bits,
                           void *work, int num_slots, hipStream_t stream);
 hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, const uint16_t *aux, const uint16_t *flags,
-                            uint32_t aux_pitch, const uint32_t *final_state, const uint32_t *group_bits, const uint64_t *offsets,
-                            uint8_t *payload, int num_slots, const uint32_t *status, hipStream_t stream);
+                            uint32_t aux_pitch, const uint32_t *final_state, const uint32_t *group_bits, uint64_t *offsets,
+                            uint8_t *payload, int num_slots, uint32_t *status, uint64_t *total, uint64_t payload_cap,
+                            hipStream_t stream);
 hipError_t launch_frame_begin(const HydkLfJob *host_jobs, HydkLfJob *d_jobs, int count, uint32_t *accum, size_t accum_words,
                               hipStream_t stream);
 hipError_t launch_publish(const uint64_t *total, uint64_t *h_total, const unsigned long long *lf_total,
@@ -143,6 +144,7 @@ struct HydAmdContext {
     uint32_t bit_pitch_words = 0;   /* words per group in bitbuf (0: not allocated yet) */
     int want_transform = 0, want_entropy = 0; /* what the caller asked for this frame: replayed if a buffer was too small */
     bool slot_lanes[HYDAMD_MAX_LF_GROUPS] = {}; /* which entropy form coded each slot of the current frame */
+    bool slot_lane_chain[HYDAMD_MAX_LF_GROUPS] = {}; /* ... and whether that was the lane-form chain: implies slot_lanes; the two differ only for a wave form that defers its bits to k_rans_emit (HYDAMD_WAVE_FORM_EMITS), which keeps the scan kernel */
     unsigned overflow_reruns = 0;   /* frames run twice because a buffer was too small (hydamd_overflow_reruns) */
     uint32_t alpha_floor = 0;       /* running maximum alphabet of the LF groups coded before this context's */
     const uint32_t *alpha_floor_dev = nullptr; /* the same, left in device memory by the caller's exchange (or NULL) */
@@ -1456,7 +1458,7 @@ static int transform_range(HydAmdContext *ctx, int first, int count) {
  * are already enqueued.  It needs only the LF ints they write: forked onto its own stream so that it
  * overlaps the HF entropy stage; join_lf brings the streams back together. */
 #ifdef HYD_TEST_HOOKS
-/* HYDAMD_DEBUG_LF_DROP (timing only, wrong LF streams): 1 the token kernel, 2 the code passengers, 4 offsets + pack, 8 the gather */
+/* HYDAMD_DEBUG_LF_DROP (timing only, wrong LF streams): 1 the token kernel, 2 the code passengers (with them the windows' offsets), 4 the pack kernel, 8 the gather */
 static int lf_drop() {
     static const int v = getenv("HYDAMD_DEBUG_LF_DROP") ? atoi(getenv("HYDAMD_DEBUG_LF_DROP")) : 0;
     return v;
@@ -2364,8 +2366,10 @@ static int entropy_range(HydAmdContext *ctx, int first, int count, bool with_lf_
                                            ctx->bitbuf + g0 * ctx->bit_pitch_words, ctx->bit_pitch_words,
                                            ctx->group_bits + g0, count, ctx->status, ctx->stream));
         }
-        for (int i = first; i < first + count; i++)
+        for (int i = first; i < first + count; i++) {
             ctx->slot_lanes[i] = emits;
+            ctx->slot_lane_chain[i] = lanes;
+        }
     }
     return ST_OK;
 }
@@ -2383,7 +2387,7 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
     ctx->want_entropy = num_slots;
     /* In-stream LF coder + lane-form entropy stage: the LF coder's 200 us of serial code construction per LF
      * group rides in the chain kernel's launch instead of sitting in the stream on its own — tokens before
-     * the entropy stage, offsets + pack behind it. */
+     * the entropy stage, pack behind it (the windows' offsets come from the code builder). */
     int lf_first = -1, lf_count = 0;
     if (num_slots > ctx->coded && ctx->lf_on_device == 2 && ctx->rans_lanes && ctx->lf_coded == ctx->coded && !ctx->lf_pending &&
         !(debug_skip() & 8)) {
@@ -2408,11 +2412,20 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
     }
     if (!(debug_skip() & 4)) {
         /* section sizes -> byte offsets, then the sections themselves: lane-form slots write their bits
-         * straight into place, wave-form slots copy theirs out of the reversed bit buffers */
+         * straight into place, wave-form slots copy theirs out of the reversed bit buffers.  A frame whose slots are all
+         * lane-form needs no scan kernel: the one emit launch finds the offsets and the total itself */
         ScopedTimer timer(ctx, HYDAMD_K_PACK);
-        HIP_TRY(ctx, hydk::launch_scan(ctx->group_bits, count, ctx->offsets, ctx->total, ctx->payload, ctx->payload_cap, 1,
-                                       ctx->status, ctx->stream));
-        for (int first = 0; first < num_slots;) {
+        bool all_emit = true;
+        for (int i = 0; i < num_slots; i++)
+            all_emit = all_emit && ctx->slot_lane_chain[i];
+        if (all_emit)
+            HIP_TRY(ctx, hydk::launch_rans_emit(ctx->d_jobs, ctx->sym_count, ctx->rans_aux, ctx->rans_flags, ctx->tok_cap,
+                                                ctx->rans_final, ctx->group_bits, ctx->offsets, ctx->payload, num_slots,
+                                                ctx->status, ctx->total, ctx->payload_cap, ctx->stream));
+        else
+            HIP_TRY(ctx, hydk::launch_scan(ctx->group_bits, count, ctx->offsets, ctx->total, ctx->payload, ctx->payload_cap, 1,
+                                           ctx->status, ctx->stream));
+        for (int first = all_emit ? num_slots : 0; first < num_slots;) {
             int last = first;
             while (last + 1 < num_slots && ctx->slot_lanes[last + 1] == ctx->slot_lanes[first])
                 last++;
@@ -2422,7 +2435,7 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
                 HIP_TRY(ctx, hydk::launch_rans_emit(ctx->d_jobs + first, ctx->sym_count + g0, ctx->rans_aux + g0 * ctx->tok_cap,
                                                     ctx->rans_flags + g0 * (ctx->tok_cap / 16), ctx->tok_cap,
                                                     ctx->rans_final + g0, ctx->group_bits + g0, ctx->offsets + g0, ctx->payload,
-                                                    n, ctx->status, ctx->stream));
+                                                    n, ctx->status, nullptr, 0, ctx->stream));
             else
                 HIP_TRY(ctx, hydk::launch_pack(ctx->bitbuf + g0 * ctx->bit_pitch_words, ctx->bit_pitch_words,
                                                ctx->group_bits + g0, ctx->offsets + g0, ctx->payload,
@@ -2797,8 +2810,15 @@ int hydamd_read_lf_bits(HydAmdContext *ctx, int slot, uint8_t *dst, size_t capac
         return fail(ctx, ST_API_ERROR, "no device-coded LF stream: the LF coder is off or the frame was not synchronised");
     if (capacity > (size_t)HYDK_LF_BITWORDS * sizeof(uint32_t))
         return fail(ctx, ST_API_ERROR, "LF bit request too large");
-    if (capacity)
-        HIP_TRY(ctx, hipMemcpy(dst, ctx->lf_bits + (size_t)slot * HYDK_LF_BITWORDS, capacity, hipMemcpyDeviceToHost));
+    if (!capacity)
+        return ST_OK;
+    /* the slot's words behind its stream hold whatever an earlier frame left: the caller gets zero there */
+    HydkLfStream h;
+    HIP_TRY(ctx, hipMemcpy(&h, ctx->lf_streams + slot, sizeof(h), hipMemcpyDeviceToHost));
+    const size_t have = ((size_t)h.bit_count + 7u) / 8u, n = capacity < have ? capacity : have;
+    if (n)
+        HIP_TRY(ctx, hipMemcpy(dst, ctx->lf_bits + (size_t)slot * HYDK_LF_BITWORDS, n, hipMemcpyDeviceToHost));
+    memset(dst + n, 0, capacity - n);
     return ST_OK;
 }
 

@@ -14,8 +14,10 @@
  *   k_rans_lanes / k_rans_emit   the same chain with one LANE per group — a wavefront walks the 64
  *                         chains of an LF group and records each step's refill word — and a
  *                         wave-parallel kernel that writes the bits straight into the frame's
- *                         payload (highest frame rate: 0.3 instructions per symbol).
- *   k_scan_sections / k_pack_sections   byte sizes and offsets of the HF sections; packing of the wave form's.
+ *                         payload (highest frame rate: 0.3 instructions per symbol); in a frame whose
+ *                         slots are all lane-form it also finds the sections' offsets and the total.
+ *   k_scan_sections / k_pack_sections   frames with a wave-form range: byte sizes and offsets of the HF
+ *                         sections; packing of the wave form's.
  *
  * Arithmetic contract: IEEE binary32, source operation order, NO fused multiply-add — the
  * reference's canonical bytes are the non-contracted ones.  This file is
@@ -26,6 +28,7 @@
 #include <stdint.h>
 
 #include "hydk_common.h"
+#include "hydk_edges.h" /* a section's first and last word as byte stores (k_rans_emit's self-placing mode) */
 #include <atomic>
 #include <type_traits>
 
@@ -1460,7 +1463,8 @@ __global__ __launch_bounds__(kThreads) void k_build_tables(const uint32_t *hist_
         __shared__ LfHuffScratch s_huff;
         const int s = (int)blockIdx.x - num_slots;
         if (threadIdx.x < 64)
-            lf_huffman_wave(lf_hist + (size_t)s * HYDK_LF_CODES, ((LfWork *)lf_work)[s].codes, lf_streams + s, s_huff, (int)threadIdx.x);
+            lf_code_and_offsets_wave(lf_hist + (size_t)s * HYDK_LF_CODES, ((LfWork *)lf_work)[s], lf_streams + s,
+                                     jobs_all[first_slot + s], s_huff, (int)threadIdx.x);
         return;
     }
     const unsigned slot = (unsigned)first_slot + blockIdx.x; /* all arrays are indexed by the frame's slot */
@@ -2142,7 +2146,8 @@ __global__ __launch_bounds__(64) void k_rans_lanes(const HydkLfJob *__restrict__
         /* passengers: workgroup num_slots + s builds the prefix code of LF group s's coefficient stream
          * (lf_coder.hip; 200 us of serial work on one wavefront, like the chains and independent of them) */
         const int s = (int)blockIdx.x - num_slots;
-        lf_huffman_wave(lf_hist + (size_t)s * HYDK_LF_CODES, ((LfWork *)lf_work)[s].codes, lf_streams + s, *(LfHuffScratch *)s_mem, lane);
+        lf_code_and_offsets_wave(lf_hist + (size_t)s * HYDK_LF_CODES, ((LfWork *)lf_work)[s], lf_streams + s, jobs[s],
+                                 *(LfHuffScratch *)s_mem, lane);
         return;
     }
     const int slot = blockIdx.x;
@@ -2594,8 +2599,17 @@ __global__ __launch_bounds__(64) void k_rans_lanes(const HydkLfJob *__restrict__
 }
 
 /* one wave per group: records + the chain's refill words -> bits, written straight to the section's
- * place in the frame's payload (k_scan_sections has turned the chain's bit counts into byte offsets
- * and cleared the two words a section may share with its neighbours).  The section is filled from
+ * place in the frame's payload.  Where that place is:
+ *   SELF   (every slot of the frame is lane-form, one launch for all `count` groups) the wavefront sums the byte
+ *          sizes (group_bits[i] + 7) >> 3 of the groups before its own — at most 255 x 64 words, resident in L2, strided by the
+ *          lanes and reduced with the wave scan — and writes offsets[G] itself, for EVERY group of the frame, the empty ones
+ *          (g >= ngroups) included: export, read-back and the assemblers keep reading offsets[].  The wavefront of group 0
+ *          also writes the frame's total and raises HYDK_STATUS_PAYLOAD (all > payload_cap, what the scan kernel tests).
+ *          Nothing clears words beforehand: a first or last word that the section shares with its neighbours is written
+ *          as byte stores of exactly the section's own bytes (hydk_edges.h), interior words as whole words.
+ *   !SELF  (frames with a wave-form range) k_scan_sections has turned the bit counts into byte offsets and cleared the two
+ *          words a section may share with its neighbours, which are ORed into.
+ * The section is filled from
  * its END in batches of 512 symbols aligned to the start of the token array (eight consecutive symbols
  * per lane: two aligned 16-byte record loads, one 16-byte load of refill words); inside a batch the
  * stream order [refill_p][residue_p][refill_p+1].. is plain ascending (lane, symbol) order.
@@ -2607,11 +2621,12 @@ constexpr int kEmitPer = 8;                  /* symbols per lane and batch */
 constexpr int kEmitBatch = 64 * kEmitPer;    /* 512 */
 constexpr int kEmitWin = kEmitBatch + 4;     /* 512 symbols x at most 32 bits = 512 words + alignment slack */
 
+template <bool SELF>
 __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restrict__ jobs, const uint32_t *sym_count_all,
                                                         const uint16_t *aux_all, const uint16_t *flags_all, uint32_t aux_pitch,
                                                         const uint32_t *final_state_all, const uint32_t *group_bits_all,
-                                                        const uint64_t *offsets_all, uint8_t *payload,
-                                                        const uint32_t *status, int vblocks) {
+                                                        uint64_t *offsets_all, uint8_t *payload, uint32_t *status, int vblocks,
+                                                        uint64_t *total, uint64_t payload_cap) {
     __shared__ uint32_t s_win[4][kEmitWin];
     HYDK_URGENT();
     /* a workgroup takes the virtual blocks blockIdx.x, blockIdx.x + gridDim.x, ... (four groups each, one per wavefront):
@@ -2619,12 +2634,51 @@ __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restr
      * whatever a compute unit frees, and this kernel's queue gets its turn among theirs — far longer than it runs, so
      * fewer workgroups with more to do each finish sooner (launch_rans_emit, HYDAMD_EMIT_SHARE) */
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    /* 64-bit byte counts summed over the wave: per lane below 255 x 2^29, in two pieces of 24 and 14 bits that the 32-bit wave
+     * scan cannot overflow */
+    auto wave_sum = [](uint64_t v) {
+        const uint32_t lo = __builtin_amdgcn_readlane(scan64_inclusive((uint32_t)v & 0xFFFFFFu), 63);
+        const uint32_t hi = __builtin_amdgcn_readlane(scan64_inclusive((uint32_t)(v >> 24)), 63);
+        return ((uint64_t)hi << 24) + lo;
+    };
+    /* SELF: the frame's section bytes and whether they fit, once per wavefront whatever number of virtual blocks it takes */
+    uint64_t all = 0;
+    bool fits = true;
+    if (SELF) {
+        uint64_t mine_all = 0;
+        for (int i = lane; i < vblocks * 4; i += 64)
+            mine_all += (group_bits_all[i] + 7u) >> 3;
+        all = wave_sum(mine_all);
+        fits = all <= payload_cap && !(*status & HYDK_STATUS_OVERFLOW);
+    }
     auto one_block = [&](const int vb) {
     const int slot = vb >> 4;
     const int g = ((vb & 15) << 2) + wave;
     const int ngroups = jobs[slot].gcols * jobs[slot].grows;
     const size_t G = (size_t)slot * HYDK_GROUPS_PER_LFG + g;
-    if (g >= ngroups || (*status & HYDK_STATUS_OVERFLOW))
+    uint64_t sec_lo = 0; /* SELF: the section's byte offset */
+    if (SELF) {
+        /* byte sizes of the groups before this one: only the G words in front of it are read */
+        uint64_t mine_before = 0;
+        for (size_t i = lane; i < G; i += 64)
+            mine_before += (group_bits_all[i] + 7u) >> 3;
+        sec_lo = wave_sum(mine_before);
+        if (lane == 0) {
+            offsets_all[G] = sec_lo;
+            if (G == 0) {
+                *total = fits ? all : 0;
+                if (all > payload_cap)
+                    atomicOr(status, HYDK_STATUS_PAYLOAD); /* the host enlarges the payload and reruns the frame */
+                /* the bytes between the frame's end and the next word boundary belong to no section: zero, as they were when
+                 * the scan kernel cleared the last section's last word (the payload is allocated 16 bytes beyond its capacity) */
+                if (fits)
+                    for (uint64_t b = all; b & 3u; b++)
+                        payload[b] = 0;
+            }
+        }
+        if (g >= ngroups || !fits)
+            return;
+    } else if (g >= ngroups || (*status & HYDK_STATUS_OVERFLOW))
         return;
     const void *tok = (const char *)jobs[slot].tokens + (size_t)g * jobs[slot].tok_cap * jobs[slot].rec_bytes;
     const uint4 *aux = (const uint4 *)(aux_all + G * aux_pitch);
@@ -2633,8 +2687,9 @@ __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restr
     uint32_t *win = s_win[wave];
     const int n = __builtin_amdgcn_readfirstlane((int)sym_count_all[G]);
     const uint32_t bits = group_bits_all[G];
-    const unsigned long long lo_bit = offsets_all[G] * 8ull, hi_bit = lo_bit + (unsigned long long)((bits + 7u) & ~7u);
-    /* words this section shares with its neighbours (ORed into; the scan kernel cleared them) */
+    const unsigned long long lo_bit = (SELF ? sec_lo : offsets_all[G]) * 8ull, hi_bit = lo_bit + (unsigned long long)((bits + 7u) & ~7u);
+    /* words this section shares with its neighbours (SELF: only its own bytes of them are stored; else ORed into — the scan
+     * kernel cleared them) */
     const uint32_t shared_lo = (lo_bit & 31ull) ? (uint32_t)(lo_bit >> 5) : 0xFFFFFFFFu;
     const uint32_t shared_hi = (hi_bit & 31ull) ? (uint32_t)((hi_bit - 1ull) >> 5) : 0xFFFFFFFFu;
     /* bit positions relative to the word that holds the section's first bit: they fit 32 bits */
@@ -2645,7 +2700,9 @@ __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restr
     bool bad = false;
     auto put = [&](uint32_t word, uint32_t v) {
         const uint32_t d = wbase + word;
-        if (d == shared_lo || d == shared_hi)
+        if (SELF && (d == shared_lo || d == shared_hi))
+            hydk_store_edge_word(payload, d, v, lo_bit >> 3, hi_bit >> 3);
+        else if (d == shared_lo || d == shared_hi)
             atomicOr(&W[d], v);
         else
             W[d] = v;
@@ -2669,7 +2726,7 @@ __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restr
                             * stages disagree about the group (a bug upstream).  Stop here instead of walking a window of
                             * 2^32 bits: the frame fails with an internal error */
             if (lane == 0)
-                atomicOr((uint32_t *)status, HYDK_STATUS_INCONSISTENT);
+                atomicOr(status, HYDK_STATUS_INCONSISTENT);
             bad = true;
             return;
         }
@@ -3164,9 +3221,12 @@ hipError_t launch_rans_lanes(const HydkLfJob *d_jobs, const uint32_t *sym_count,
     return hipGetLastError();
 }
 
+/* total != NULL: the launch covers every group of the frame (slot 0 onwards) and finds the sections' offsets itself; it writes
+ * offsets[], *total and the payload overflow status, and no scan kernel runs in front of it */
 hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, const uint16_t *aux, const uint16_t *flags,
-                            uint32_t aux_pitch, const uint32_t *final_state, const uint32_t *group_bits, const uint64_t *offsets,
-                            uint8_t *payload, int num_slots, const uint32_t *status, hipStream_t stream) {
+                            uint32_t aux_pitch, const uint32_t *final_state, const uint32_t *group_bits, uint64_t *offsets,
+                            uint8_t *payload, int num_slots, uint32_t *status, uint64_t *total, uint64_t payload_cap,
+                            hipStream_t stream) {
     /* virtual blocks per workgroup: HYDAMD_EMIT_SHARE (A/B; 1 = one workgroup per four groups, as until round 5) */
     static const int share = [] {
         const char *v = getenv("HYDAMD_EMIT_SHARE");
@@ -3174,8 +3234,13 @@ hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, 
         return n < 1 ? 1 : n > 16 ? 16 : n;
     }();
     const int vblocks = num_slots * 16;
-    hipLaunchKernelGGL(k_rans_emit, dim3((vblocks + share - 1) / share), dim3(kThreads), 0, stream, d_jobs, sym_count, aux, flags,
-                       aux_pitch, final_state, group_bits, offsets, payload, status, vblocks);
+    const dim3 grid((vblocks + share - 1) / share);
+    if (total)
+        hipLaunchKernelGGL(k_rans_emit<true>, grid, dim3(kThreads), 0, stream, d_jobs, sym_count, aux, flags, aux_pitch, final_state,
+                           group_bits, offsets, payload, status, vblocks, total, payload_cap);
+    else
+        hipLaunchKernelGGL(k_rans_emit<false>, grid, dim3(kThreads), 0, stream, d_jobs, sym_count, aux, flags, aux_pitch,
+                           final_state, group_bits, offsets, payload, status, vblocks, (uint64_t *)nullptr, (uint64_t)0);
     return hipGetLastError();
 }
 

@@ -29,12 +29,14 @@
  *                 heights and a parent walk.  Runs in a compact slot space (only the slots the
  *                 16509-entry alphabet can ever touch) with all candidates held in registers: no
  *                 LDS traffic or barrier inside the merge loop.
- *   k_lf_offsets  one workgroup per LF group: bits of each window (its token histogram times the code
- *                 lengths, plus its residue bits), their exclusive prefix sum; clears the words two
- *                 windows share.
+ *                 The same wavefront then turns the code lengths into the bits of each window (its
+ *                 token histogram times the lengths, plus its residue bits) and their exclusive prefix
+ *                 sum (lf_huffman.h lf_window_offsets_wave): no kernel of its own does that.
  *   k_lf_pack     one workgroup per window: per-value bit strings (<= 59 bits) ORed into an LDS
- *                 window at the window's bit offset, whole words stored, the two shared words ORed into
- *                 memory; LSB-first like HYDBitWriter (bitwriter.c:110-124).
+ *                 window at the window's bit offset, whole words stored; of the two words a window may
+ *                 share with its neighbours it replaces exactly its own bits (a bit mask: atomic AND,
+ *                 then atomic OR), so nothing clears them first; LSB-first like HYDBitWriter
+ *                 (bitwriter.c:110-124).
  *
  * The work is small (<= 196608 values per 4.2 Mpx LF group); it exists so that a frame's sections are
  * complete on the device and the host's per-frame serial work disappears.
@@ -72,7 +74,7 @@ __device__ __forceinline__ LfShape lf_shape(const HydkLfJob &job) {
     LfShape sh;
     sh.vbw = (job.width + 7) >> 3;
     sh.blocks = sh.vbw * ((job.height + 7) >> 3);
-    sh.n = 3 * sh.blocks;
+    sh.n = lf_values_of(job); /* 3 * blocks */
     sh.vbw_magic = sh.vbw > 1 ? (uint32_t)(0xFFFFFFFFu / (uint32_t)sh.vbw) + 1u : 0u;
     return sh;
 }
@@ -98,9 +100,9 @@ __device__ __forceinline__ void lf_hybrid(uint32_t v, uint32_t &token, uint32_t 
 }
 
 #define LF_DPP_KEEP(v, ctrl, rmask) ((uint32_t)__builtin_amdgcn_update_dpp((int)(v), (int)(v), ctrl, rmask, 0xF, false))
-#define LF_DPP_ZERO(v, ctrl, rmask) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, rmask, 0xF, false))
 
-/* inclusive scans over the wavefront: row_shr 1/2/4/8 inside each row of 16, then row_bcast 15 / 31 */
+/* inclusive maximum over the wavefront: row_shr 1/2/4/8 inside each row of 16, then row_bcast 15 / 31 (the inclusive sum is
+ * lf_huffman.h lf_wave_incl_sum) */
 __device__ __forceinline__ int wave_incl_max(int v) {
     int t;
     t = (int)LF_DPP_KEEP(v, 0x111, 0xF);
@@ -115,16 +117,6 @@ __device__ __forceinline__ int wave_incl_max(int v) {
     v = v > t ? v : t;
     t = (int)LF_DPP_KEEP(v, 0x143, 0xC);
     v = v > t ? v : t;
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {
-    v += LF_DPP_ZERO(v, 0x111, 0xF);
-    v += LF_DPP_ZERO(v, 0x112, 0xF);
-    v += LF_DPP_ZERO(v, 0x114, 0xF);
-    v += LF_DPP_ZERO(v, 0x118, 0xF);
-    v += LF_DPP_ZERO(v, 0x142, 0xA);
-    v += LF_DPP_ZERO(v, 0x143, 0xC);
     return v;
 }
 
@@ -427,7 +419,7 @@ __global__ __launch_bounds__(kLfThreads) void k_lf_tokens(const HydkLfJob *__res
         if (tid == 0)
             s_rbits = 0;
         uint32_t rb = lf_tokens_window(job, sh, recs_all + (size_t)slot * HYDK_LF_SYMBOLS, tb, s_rs, s_hist, s_tok);
-        rb = wave_incl_sum(rb);
+        rb = lf_wave_incl_sum(rb);
         if ((tid & 63) == 63 && rb)
             atomicAdd(&s_rbits, rb);
         __syncthreads();
@@ -446,71 +438,20 @@ __global__ __launch_bounds__(kLfThreads) void k_lf_tokens(const HydkLfJob *__res
 }
 
 /* grid = LF groups, block = 64: code lengths + canonical codes of each LF group's histogram */
-__global__ __launch_bounds__(64) void k_lf_codes(const uint32_t *__restrict__ hist_all, HydkLfStream *__restrict__ streams,
-                                                 LfWork *__restrict__ work) {
+__global__ __launch_bounds__(64) void k_lf_codes(const HydkLfJob *__restrict__ jobs, const uint32_t *__restrict__ hist_all,
+                                                 HydkLfStream *__restrict__ streams, LfWork *__restrict__ work) {
     if (!(HYDK_LF_PROBE & 1))
         __builtin_amdgcn_s_setprio(3); /* late work of a frame whose stream holds nothing else: see kernels.hip HYDK_URGENT */
     __shared__ LfHuffScratch s_huff;
     const int slot = blockIdx.x;
-    lf_huffman_wave(hist_all + (size_t)slot * HYDK_LF_CODES, work[slot].codes, streams + slot, s_huff, (int)threadIdx.x);
-}
-
-/* grid = LF groups, block = 256: bits of each window = sum over tokens of (count x code length) + its
- * residue bits; where each window's bits start; the words two windows share are cleared */
-__global__ __launch_bounds__(kLfThreads) void k_lf_offsets(const HydkLfJob *__restrict__ jobs, LfWork *__restrict__ work,
-                                                           HydkLfStream *__restrict__ streams, uint32_t *__restrict__ bits_all) {
-    if (!(HYDK_LF_PROBE & 1))
-        __builtin_amdgcn_s_setprio(3); /* late work of a frame whose stream holds nothing else: see kernels.hip HYDK_URGENT */
-    const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const LfShape sh = lf_shape(jobs[slot]);
-    const int windows = (sh.n + kEmitSpan - 1) / kEmitSpan; /* <= 220 < 256 */
-    LfWork &w = work[slot];
-    __shared__ uint32_t s_win[kMaxWindows];
-    __shared__ uint32_t s_wsum[kLfWaves];
-    /* a wave per window: lanes over the 384 tokens (6 each) */
-    uint32_t len6[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++)
-        len6[j] = w.codes[j * 64 + lane] >> 16;
-    for (int win = wave; win < windows; win += kLfWaves) {
-        uint32_t bits = 0;
-#pragma unroll
-        for (int j = 0; j < 6; j++)
-            bits += (uint32_t)w.win_hist[win][j * 64 + lane] * len6[j];
-        bits = wave_incl_sum(bits);
-        if (lane == 63)
-            s_win[win] = bits + w.win_residue_bits[win];
-    }
-    __syncthreads();
-    const uint32_t mine = tid < windows ? s_win[tid] : 0u;
-    const uint32_t inc = wave_incl_sum(mine);
-    if (lane == 63)
-        s_wsum[wave] = inc;
-    __syncthreads();
-    uint32_t off = inc - mine, total = 0;
-    for (int k = 0; k < kLfWaves; k++) {
-        if (k < wave)
-            off += s_wsum[k];
-        total += s_wsum[k];
-    }
-    uint32_t *out = bits_all + (size_t)slot * HYDK_LF_BITWORDS;
-    if (tid < windows) {
-        w.win_off[tid] = off;
-        /* the window's first word may hold the end of the window before, its last the start of the one
-         * after: k_lf_pack ORs into exactly these two */
-        if (mine) {
-            out[off >> 5] = 0;
-            out[(off + mine - 1u) >> 5] = 0;
-        }
-    }
-    if (tid == 0)
-        streams[slot].bit_count = total;
+    lf_code_and_offsets_wave(hist_all + (size_t)slot * HYDK_LF_CODES, work[slot], streams + slot, jobs[slot], s_huff, (int)threadIdx.x);
 }
 
 /* grid = (windows of 896 values, LF groups) */
 __global__ __launch_bounds__(kLfThreads) void k_lf_pack(const HydkLfJob *__restrict__ jobs,
                                                         const unsigned long long *__restrict__ recs_all,
-                                                        const LfWork *__restrict__ work, uint32_t *__restrict__ bits_all) {
+                                                        const LfWork *__restrict__ work,
+                                                        const HydkLfStream *__restrict__ streams, uint32_t *__restrict__ bits_all) {
     if (!(HYDK_LF_PROBE & 1))
         __builtin_amdgcn_s_setprio(3); /* late work of a frame whose stream holds nothing else: see kernels.hip HYDK_URGENT */
     const int slot = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -534,7 +475,7 @@ __global__ __launch_bounds__(kLfThreads) void k_lf_pack(const HydkLfJob *__restr
     unsigned long long val[4];
     uint32_t len[4];
     const uint32_t mine = lf_window_strings(sh, recs_all + (size_t)slot * HYDK_LF_SYMBOLS, tb, s_code, val, len);
-    const uint32_t inc = wave_incl_sum(mine);
+    const uint32_t inc = lf_wave_incl_sum(mine);
     if (lane == 63)
         s_wsum[wave] = inc;
     __syncthreads();
@@ -562,17 +503,29 @@ __global__ __launch_bounds__(kLfThreads) void k_lf_pack(const HydkLfJob *__restr
         pos += len[j];
     }
     __syncthreads();
-    /* whole words are stored; the first and the last word of the span may be shared with the neighbouring
-     * windows (k_lf_offsets cleared them): those are ORed into memory */
+    /* whole words are stored; the first and the last word of the span may be shared with the neighbouring windows, whose
+     * workgroups run in any order and find whatever an earlier frame left: each replaces exactly its own bits of such a word
+     * (the masks of neighbours are disjoint, so their ANDs and ORs commute).  The window that ends the stream owns the rest
+     * of its last word, which stays zero */
     if (!total)
         continue;
     const uint32_t end = (gbits & 31u) + total, last = (end - 1u) >> 5;
+    if ((gbits >> 5) + last >= (uint32_t)HYDK_LF_BITWORDS)
+        continue; /* offsets no code builder wrote (a measurement build that leaves the builder out): never outside the slot's words */
+    const bool ends_stream = gbits + total == streams[slot].bit_count;
     uint32_t *dst = bits_all + (size_t)slot * HYDK_LF_BITWORDS + (gbits >> 5);
     for (uint32_t w = tid; w <= last; w += kLfThreads) {
-        if (w == 0 || w == last)
-            atomicOr(&dst[w], s_bits[w]);
-        else
+        uint32_t mask = 0xFFFFFFFFu;
+        if (w == 0)
+            mask <<= gbits & 31u;
+        if (w == last && (end & 31u) && !ends_stream)
+            mask &= (1u << (end & 31u)) - 1u;
+        if (mask == 0xFFFFFFFFu)
             dst[w] = s_bits[w];
+        else {
+            atomicAnd(&dst[w], ~mask);
+            atomicOr(&dst[w], s_bits[w]);
+        }
     }
   }
 }
@@ -610,7 +563,8 @@ __global__ __launch_bounds__(256) void k_lf_gather(HydkLfStream *__restrict__ st
 __global__ __launch_bounds__(64) void k_lf_huffman(const uint32_t *__restrict__ hist, HydkLfStream *__restrict__ stream_out,
                                                    uint32_t *__restrict__ codes) {
     __shared__ LfHuffScratch s_huff;
-    lf_huffman_wave(hist, codes, stream_out, s_huff, (int)threadIdx.x);
+    uint32_t len6[kEntries];
+    lf_huffman_wave(hist, codes, stream_out, s_huff, (int)threadIdx.x, len6);
 }
 
 } // namespace
@@ -621,7 +575,7 @@ namespace hydk {
 size_t lf_work_bytes() { return sizeof(LfWork); }
 
 /* The LF coder for `num_slots` LF groups in three steps (every pointer addresses the first of the LF
- * groups): tokens; code construction; offsets + pack.  The middle step may instead ride in the entropy
+ * groups): tokens; code construction with the windows' offsets; pack.  The middle step may instead ride in the entropy
  * stage's launch (kernels.hip k_rans_lanes), which is why it can be left out here. */
 hipError_t launch_lf_front(const HydkLfJob *d_jobs, unsigned long long *recs, uint32_t *hist, void *work, int num_slots,
                            hipStream_t stream) {
@@ -630,16 +584,17 @@ hipError_t launch_lf_front(const HydkLfJob *d_jobs, unsigned long long *recs, ui
     return hipGetLastError();
 }
 
-hipError_t launch_lf_codes(const uint32_t *hist, HydkLfStream *streams, void *work, int num_slots, hipStream_t stream) {
-    hipLaunchKernelGGL(k_lf_codes, dim3(num_slots), dim3(64), 0, stream, hist, streams, (LfWork *)work);
+hipError_t launch_lf_codes(const HydkLfJob *d_jobs, const uint32_t *hist, HydkLfStream *streams, void *work, int num_slots,
+                           hipStream_t stream) {
+    hipLaunchKernelGGL(k_lf_codes, dim3(num_slots), dim3(64), 0, stream, d_jobs, hist, streams, (LfWork *)work);
     return hipGetLastError();
 }
 
 hipError_t launch_lf_back(const HydkLfJob *d_jobs, const unsigned long long *recs, HydkLfStream *streams, uint32_t *bits,
                           void *work, int num_slots, hipStream_t stream) {
     LfWork *w = (LfWork *)work;
-    hipLaunchKernelGGL(k_lf_offsets, dim3(num_slots), dim3(kLfThreads), 0, stream, d_jobs, w, streams, bits);
-    hipLaunchKernelGGL(k_lf_pack, dim3((kMaxWindows + HYDK_LF_WPB - 1) / HYDK_LF_WPB, num_slots), dim3(kLfThreads), 0, stream, d_jobs, recs, w, bits);
+    hipLaunchKernelGGL(k_lf_pack, dim3((kMaxWindows + HYDK_LF_WPB - 1) / HYDK_LF_WPB, num_slots), dim3(kLfThreads), 0, stream, d_jobs, recs, w,
+                       streams, bits);
     return hipGetLastError();
 }
 
@@ -647,7 +602,7 @@ hipError_t launch_lf_coder(const HydkLfJob *d_jobs, unsigned long long *recs, ui
                            uint32_t *bits, void *work, int num_slots, hipStream_t stream) {
     hipError_t e = launch_lf_front(d_jobs, recs, hist, work, num_slots, stream);
     if (e == hipSuccess)
-        e = launch_lf_codes(hist, streams, work, num_slots, stream);
+        e = launch_lf_codes(d_jobs, hist, streams, work, num_slots, stream);
     if (e == hipSuccess)
         e = launch_lf_back(d_jobs, recs, streams, bits, work, num_slots, stream);
     return e;

@@ -105,9 +105,10 @@ struct LfHuffScratch {
     uint32_t err;
 };
 
-/* run by ONE wavefront (lane = 0..63); hist / codes may live in LDS or in global memory */
+/* run by ONE wavefront (lane = 0..63); hist / codes may live in LDS or in global memory.  len6: the code lengths of the
+ * lane's six tokens (j * 64 + lane), for lf_window_offsets_wave */
 __device__ __forceinline__ void lf_huffman_wave(const uint32_t *hist, uint32_t *codes, HydkLfStream *st, LfHuffScratch &S,
-                                                int lane) {
+                                                int lane, uint32_t (&len6)[kEntries]) {
     const unsigned long long ltmask = (1ull << lane) - 1ull;
     uint16_t *s_par = S.par, *s_depth = S.depth;
     uint32_t *s_cnt = S.cnt, *s_first = S.first;
@@ -240,7 +241,6 @@ __device__ __forceinline__ void lf_huffman_wave(const uint32_t *hist, uint32_t *
             s_depth[HYDK_LF_CODES + m] = (uint16_t)(s_depth[HYDK_LF_CODES + s_par[HYDK_LF_CODES + m]] + 1);
     }
     wave_sync();
-    uint32_t len6[6];
 #pragma unroll
     for (int j = 0; j < 6; j++) {
         const int ci = j * 64 + lane;
@@ -293,6 +293,70 @@ __device__ __forceinline__ void lf_huffman_wave(const uint32_t *hist, uint32_t *
         st->run_pairs = pairs;
         st->error = s_err;
     }
+}
+
+/* inclusive sum over the wavefront in registers: row_shr 1/2/4/8 inside each row of 16, then row_bcast 15 / 31.  The LF
+ * coder's one sum scan: the code builder here and the token and pack kernels of lf_coder.hip use it */
+#define LF_DPP_ADD(v, ctrl, rmask) ((v) + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, rmask, 0xF, false))
+__device__ __forceinline__ uint32_t lf_wave_incl_sum(uint32_t v) {
+    v = LF_DPP_ADD(v, 0x111, 0xF);
+    v = LF_DPP_ADD(v, 0x112, 0xF);
+    v = LF_DPP_ADD(v, 0x114, 0xF);
+    v = LF_DPP_ADD(v, 0x118, 0xF);
+    v = LF_DPP_ADD(v, 0x142, 0xA);
+    v = LF_DPP_ADD(v, 0x143, 0xC);
+    return v;
+}
+
+/* Where each window's bits start, by the wavefront that has just built the code (registers and DPP only, no LDS): a
+ * window's bit count is its token histogram (k_lf_tokens) times the code lengths — six tokens per lane, summed over the
+ * wave — plus its residue bits; window k * 64 + i is kept by lane i, and the exclusive prefix over the at most 220 windows
+ * is four wave scans with a carry.  Writes win_off[] and the stream's bit count. */
+__device__ __forceinline__ void lf_window_offsets_wave(const uint32_t (&len6)[kEntries], LfWork &w, HydkLfStream *st, int windows,
+                                                       int lane) {
+    uint32_t carry = 0;
+#pragma unroll
+    for (int k = 0; k < (kMaxWindows + 63) / 64; k++) {
+        uint32_t mine = 0;
+#pragma unroll 4
+        for (int i = 0; i < 64; i++) {
+            if (k * 64 + i >= windows) /* (no early exit: a fixed trip count lets four windows' loads travel together) */
+                continue;
+            const uint16_t *row = w.win_hist[k * 64 + i];
+            uint32_t bits = 0;
+#pragma unroll
+            for (int j = 0; j < kEntries; j++)
+                bits += (uint32_t)row[j * 64 + lane] * len6[j];
+            bits = (uint32_t)__builtin_amdgcn_readlane((int)lf_wave_incl_sum(bits), 63);
+            mine = lane == i ? bits : mine;
+        }
+        const bool has = k * 64 + lane < windows;
+        if (has)
+            mine += w.win_residue_bits[k * 64 + lane];
+        const uint32_t inc = lf_wave_incl_sum(mine);
+        if (has)
+            w.win_off[k * 64 + lane] = carry + inc - mine;
+        carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+    }
+    if (lane == 0)
+        st->bit_count = carry;
+}
+
+/* An LF group's value sequence is 3 planes of vbw x vbh LF ints, cut into windows of kEmitSpan values.  The one place both
+ * numbers come from: the token and pack kernels walk the windows by lf_values_of (lf_coder.hip lf_shape), the code builder
+ * sums the offsets of lf_windows_of */
+__device__ __forceinline__ int lf_values_of(const HydkLfJob &job) {
+    return 3 * ((job.width + 7) >> 3) * ((job.height + 7) >> 3);
+}
+__device__ __forceinline__ int lf_windows_of(const HydkLfJob &job) { return (lf_values_of(job) + kEmitSpan - 1) / kEmitSpan; }
+
+/* the code of one LF group and, from it, where its windows start: what every place that builds the code runs (the chain
+ * launch's passengers, k_build_tables under HYDAMD_LF_CODES_RIDE=tables, k_lf_codes); the token kernel has run */
+__device__ __forceinline__ void lf_code_and_offsets_wave(const uint32_t *hist, LfWork &w, HydkLfStream *st, const HydkLfJob &job,
+                                                         LfHuffScratch &S, int lane) {
+    uint32_t len6[kEntries];
+    lf_huffman_wave(hist, w.codes, st, S, lane, len6);
+    lf_window_offsets_wave(len6, w, st, lf_windows_of(job), lane);
 }
 
 

@@ -292,7 +292,7 @@ HYDAMD_EXPORT int hydamd_lf_coder(HydAmdContext *ctx);
 /* code length per compact token, largest token + 1, number of (run, distance) pairs, bits of symbol data */
 HYDAMD_EXPORT int hydamd_read_lf_stream(HydAmdContext *ctx, int slot, uint8_t lengths[HYDAMD_LF_CODES], uint32_t *alphabet,
                                         uint32_t *run_pairs, uint32_t *bit_count);
-/* the symbol bits, LSB first; capacity >= (bit_count + 7) / 8 */
+/* the symbol bits, LSB first; capacity >= (bit_count + 7) / 8; bytes of dst beyond the stream's end are zero */
 HYDAMD_EXPORT int hydamd_read_lf_bits(HydAmdContext *ctx, int slot, uint8_t *dst, size_t capacity);
 /* The frame's LF streams in two copies instead of two per slot: the per-slot records (with the byte
  * offset of each slot's symbol data) and the symbol data of all slots back to back, 4-byte aligned,

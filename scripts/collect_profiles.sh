@@ -310,7 +310,7 @@ run dyn_lds txt bash -c '
   echo "# loop without scan + emit (skip 4), with and without the LF coder; q5: the chain without global traffic and bank conflicts (timing only)"
   for n in base csdynp1; do echo -n "$n (skip 4): "; HYDAMD_DEBUG_SKIP=4 v $n p; echo -n "$n (skip 4), LF coder off: "; HYDAMD_DEBUG_SKIP=4 v $n p --lf 0; done
   echo -n "csdynp1q5 (skip 4), LF coder off: "; HYDAMD_DEBUG_SKIP=4 v csdynp1q5 p --lf 0
-  echo "# the full loop; LF kernels dropped (HYDAMD_DEBUG_LF_DROP: 1 tokens, 2 code passengers, 4 offsets + pack, 8 gather) and timing-only token kernels (HYDK_LF_PROBE: 2 no histograms, 4 no records, 8 workgroups return at once)"
+  echo "# the full loop; LF kernels dropped (HYDAMD_DEBUG_LF_DROP: 1 tokens, 2 code passengers, 4 pack, 8 gather) and timing-only token kernels (HYDK_LF_PROBE: 2 no histograms, 4 no records, 8 workgroups return at once)"
   for n in base csdynp1; do echo -n "$n: "; v $n p; echo -n "$n, LF coder off: "; v $n p --lf 0; done
   for d in 1 2 4 8 15; do echo -n "csdynp1 drop $d: "; HYDAMD_DEBUG_LF_DROP=$d v csdynp1 p; done
   for n in lp2 lp4 lp8; do echo -n "$n: "; v $n p; done

@@ -19,7 +19,8 @@ prev_q, prev_end = None, None
 for q, name, s, e in rows:
     per_q[q] += 1
     if q == prev_q and per_q[q] > skip and ("k_" in name or "rocclr" in name):
-        key = name.split("(")[0][-40:]
+        # the LF coder's kernels live in an anonymous namespace: cut at the argument list, not at that bracket
+        key = name.replace("(anonymous namespace)::", "").split("(")[0][-40:]
         gap[key] += max(0, s - prev_end)
         dur[key] += e - s
         cnt[key] += 1
