@@ -43,8 +43,9 @@ namespace hydk {
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream);
 hipError_t launch_tables(const uint32_t *hist, HydkTables *tabs, const uint32_t *alpha_max, int nclusters, int first_slot,
-                         int num_slots, uint32_t alpha_floor, const uint32_t *alpha_floor_dev, const uint32_t *lf_hist,
-                         HydkLfStream *lf_streams, void *lf_work, const HydkLfJob *jobs_all, hipStream_t stream);
+                         int num_slots, uint32_t alpha_floor, const uint32_t *alpha_floor_dev, uint32_t *lf_hist,
+                         HydkLfStream *lf_streams, void *lf_work, unsigned long long *lf_recs, const HydkLfJob *jobs_all,
+                         hipStream_t stream);
 hipError_t launch_export(const HydkLfJob *d_jobs, const HydkTables *tabs, const uint32_t *group_bits, const HydkLfStream *lf_streams,
                          const uint8_t *payload, const uint64_t *hf_total, const uint8_t *lf_packed,
                          const unsigned long long *lf_total, const uint32_t *status, int num_slots, int lf_coded, uint8_t *dst,
@@ -66,7 +67,8 @@ hipError_t launch_lf_back(const HydkLfJob *d_jobs, const unsigned long long *rec
 hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, const uint16_t *aux, const uint16_t *flags,
                             uint32_t aux_pitch, const uint32_t *final_state, const uint32_t *group_bits, uint64_t *offsets,
                             uint8_t *payload, int num_slots, uint32_t *status, uint64_t *total, uint64_t payload_cap,
-                            hipStream_t stream);
+                            const unsigned long long *lf_recs, const void *lf_work, HydkLfStream *lf_streams, uint32_t *lf_packed,
+                            uint32_t lf_area_words, unsigned long long *lf_total, hipStream_t stream);
 hipError_t launch_frame_begin(const HydkLfJob *host_jobs, HydkLfJob *d_jobs, int count, uint32_t *accum, size_t accum_words,
                               hipStream_t stream);
 hipError_t launch_publish(const uint64_t *total, uint64_t *h_total, const unsigned long long *lf_total,
@@ -201,6 +203,7 @@ struct HydAmdContext {
     hipEvent_t lf_fork = nullptr, lf_join = nullptr;
     bool lf_pending = false;               /* the side stream holds work the main stream has not waited for */
     bool lf_need_gather = false;           /* LF groups were coded since the frame's LF streams were last packed */
+    bool lf_direct = false;                /* the frame's LF streams were packed straight into lf_packed: lf_bits does not hold them */
     bool lf_results_valid = false;         /* hydamd_sync_lf (or hydamd_sync) has seen the packed LF streams complete */
     hipEvent_t lf_ready = nullptr;         /* recorded behind the LF gather kernel and the copy of its byte count */
     int lf_slots = 0;                      /* slots covered by the last LF coder run */
@@ -1225,6 +1228,7 @@ int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets) {
     ctx->want_transform = ctx->want_entropy = 0;
     ctx->host_staged = 0;
     ctx->lf_need_gather = false;
+    ctx->lf_direct = false;
     ctx->lf_results_valid = false;
     ctx->lf_slots = 0;
     /* this frame's uploads may overwrite the staging arena only after everything queued so far has read it */
@@ -1472,6 +1476,16 @@ static int ensure_lf_stream(HydAmdContext *ctx) {
     return ST_OK;
 }
 
+/* A frame whose first LF groups were packed straight into lf_packed (hydamd_run_entropy's direct route) and that now codes
+ * more of them: the frame ends with a gather over all of its slots, so the earlier ones are staged in lf_bits after all
+ * (their records, codes and window offsets are still in place). */
+static int stage_direct_slots(HydAmdContext *ctx, hipStream_t where) {
+    if (ctx->lf_direct && ctx->lf_coded > 0)
+        HIP_TRY(ctx, hydk::launch_lf_back(ctx->d_jobs, ctx->lf_recs, ctx->lf_streams, ctx->lf_bits, ctx->lf_work, ctx->lf_coded, where));
+    ctx->lf_direct = false;
+    return ST_OK;
+}
+
 static int lf_range(HydAmdContext *ctx, int first, int count, bool forked) {
     if (forked) {
         const int st = ensure_lf_stream(ctx);
@@ -1484,6 +1498,11 @@ static int lf_range(HydAmdContext *ctx, int first, int count, bool forked) {
         HIP_TRY(ctx, hipEventRecord(ctx->lf_fork, ctx->stream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->lf_stream, ctx->lf_fork, 0));
     }
+    {
+        const int st = stage_direct_slots(ctx, where);
+        if (st != ST_OK)
+            return st;
+    }
     ScopedTimer timer(ctx, HYDAMD_K_LF, where);
     HIP_TRY(ctx, hydk::launch_lf_coder(ctx->d_jobs + first, ctx->lf_recs + (size_t)first * HYDK_LF_SYMBOLS,
                                        ctx->lf_hist + (size_t)first * HYDK_LF_CODES, ctx->lf_streams + first,
@@ -1491,6 +1510,7 @@ static int lf_range(HydAmdContext *ctx, int first, int count, bool forked) {
                                        ctx->lf_work + (size_t)first * hydk::lf_work_bytes(), count, where));
     ctx->lf_pending = ctx->lf_pending || forked;
     ctx->lf_need_gather = true;
+    ctx->lf_direct = false;
     return ST_OK;
 }
 
@@ -2308,10 +2328,23 @@ static constexpr int debug_skip() { return 0; }
 static void launch_chain_standins(HydAmdContext *, int) {}
 #endif /* HYD_TEST_HOOKS */
 
+/* HYDAMD_LF_CODES_RIDE=tables: the LF code builders ride in the table kernel's launch instead of the chain kernel's */
+static bool lf_codes_ride_tables() {
+    static const bool v = getenv("HYDAMD_LF_CODES_RIDE") && !strcmp(getenv("HYDAMD_LF_CODES_RIDE"), "tables");
+    return v;
+}
+
 /* K2 + the rANS chains for slots [first, first + count); with_lf_codes: the lane-form launch also builds the
- * LF coder's prefix codes of the same slots (their token kernel must be enqueued already) */
-static int entropy_range(HydAmdContext *ctx, int first, int count, bool with_lf_codes) {
+ * LF coder's prefix codes of the same slots; with_lf_tokens: their token workgroups ride in the table kernel's launch
+ * (else the token kernel must be enqueued already) */
+static int entropy_range(HydAmdContext *ctx, int first, int count, bool with_lf_codes, bool with_lf_tokens) {
     const size_t G = HYDK_GROUPS_PER_LFG, g0 = (size_t)first * G;
+    if (with_lf_tokens && (debug_skip() & 1)) { /* measurement builds only: no table launch to ride in */
+        ScopedTimer timer(ctx, HYDAMD_K_LF);
+        HIP_TRY(ctx, hydk::launch_lf_front(ctx->d_jobs + first, ctx->lf_recs + (size_t)first * HYDK_LF_SYMBOLS,
+                                           ctx->lf_hist + (size_t)first * HYDK_LF_CODES,
+                                           ctx->lf_work + (size_t)first * hydk::lf_work_bytes(), count, ctx->stream));
+    }
     {
         ScopedTimer timer(ctx, HYDAMD_K_TABLES);
         /* the LF code construction's passengers ride in the chain kernel's launch (2.5 ms long anyway).  HYDAMD_LF_CODES_RIDE=tables
@@ -2319,12 +2352,14 @@ static int entropy_range(HydAmdContext *ctx, int first, int count, bool with_lf_
          * pipelined loop (143.5 against 143.3 Gpixel/s) and 0.13 ms worse for one frame alone (the table kernel then lasts
          * 0.20 instead of 0.07 ms in front of the chains), so it stays an A/B switch */
         if (!(debug_skip() & 1)) {
-        static const bool ride_with_tables = getenv("HYDAMD_LF_CODES_RIDE") && !strcmp(getenv("HYDAMD_LF_CODES_RIDE"), "tables");
-        const bool here = with_lf_codes && ride_with_tables;
+        /* (the code builders need the finished token histogram: where they ride here, the token kernel ran in front) */
+        const bool here = with_lf_codes && !with_lf_tokens && lf_codes_ride_tables();
         HIP_TRY(ctx, hydk::launch_tables(ctx->hist, ctx->tables, ctx->alpha_max, ctx->nclusters, first, count,
                                          ctx->alpha_floor, ctx->alpha_floor_dev,
-                                         here ? ctx->lf_hist + (size_t)first * HYDK_LF_CODES : nullptr, ctx->lf_streams + first,
-                                         ctx->lf_work + (size_t)first * hydk::lf_work_bytes(), ctx->d_jobs, ctx->stream));
+                                         here || with_lf_tokens ? ctx->lf_hist + (size_t)first * HYDK_LF_CODES : nullptr,
+                                         ctx->lf_streams + first, ctx->lf_work + (size_t)first * hydk::lf_work_bytes(),
+                                         with_lf_tokens ? ctx->lf_recs + (size_t)first * HYDK_LF_SYMBOLS : nullptr, ctx->d_jobs,
+                                         ctx->stream));
         if (here)
             with_lf_codes = false;
         }
@@ -2385,10 +2420,17 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
     const int count = num_slots * HYDK_GROUPS_PER_LFG;
     ctx->results_valid = false;
     ctx->want_entropy = num_slots;
-    /* In-stream LF coder + lane-form entropy stage: the LF coder's 200 us of serial code construction per LF
-     * group rides in the chain kernel's launch instead of sitting in the stream on its own — tokens before
-     * the entropy stage, pack behind it (the windows' offsets come from the code builder). */
+    /* In-stream LF coder + lane-form entropy stage: none of the LF coder's steps is a launch of its own.  The token
+     * workgroups ride in the table kernel's launch (both read only the transform kernel's output), the 200 us of serial
+     * code construction per LF group in the chain kernel's, and the pack workgroups in the emit kernel's (both need only
+     * the chain launch; the windows' offsets come from the code builder).  Where this one call codes ALL LF groups of the
+     * launch group, the pack workgroups write straight into the packed LF area (every bit count is known when the chain
+     * launch ends): nothing is staged in lf_bits and no gather kernel runs.  Otherwise — a frame coded by several growing
+     * calls — the slots' streams are staged by a pack launch of their own and gathered once the last is coded.
+     * HYDAMD_LF_CODES_RIDE=tables keeps the token kernel in front of the table launch, whose code builders read its
+     * finished histogram. */
     int lf_first = -1, lf_count = 0;
+    bool lf_tokens_ride = false;
     if (num_slots > ctx->coded && ctx->lf_on_device == 2 && ctx->rans_lanes && ctx->lf_coded == ctx->coded && !ctx->lf_pending &&
         !(debug_skip() & 8)) {
         bool any_float = false;
@@ -2397,19 +2439,25 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
         if (!any_float) {
             lf_first = ctx->coded;
             lf_count = num_slots - ctx->coded;
-            ScopedTimer timer(ctx, HYDAMD_K_LF);
-            if (!(lf_drop() & 1))
-            HIP_TRY(ctx, hydk::launch_lf_front(ctx->d_jobs + lf_first, ctx->lf_recs + (size_t)lf_first * HYDK_LF_SYMBOLS,
-                                               ctx->lf_hist + (size_t)lf_first * HYDK_LF_CODES,
-                                               ctx->lf_work + (size_t)lf_first * hydk::lf_work_bytes(), lf_count, ctx->stream));
+            lf_tokens_ride = !lf_codes_ride_tables() && !(lf_drop() & 1);
+            if (!lf_tokens_ride && !(lf_drop() & 1)) {
+                ScopedTimer timer(ctx, HYDAMD_K_LF);
+                HIP_TRY(ctx, hydk::launch_lf_front(ctx->d_jobs + lf_first, ctx->lf_recs + (size_t)lf_first * HYDK_LF_SYMBOLS,
+                                                   ctx->lf_hist + (size_t)lf_first * HYDK_LF_CODES,
+                                                   ctx->lf_work + (size_t)lf_first * hydk::lf_work_bytes(), lf_count, ctx->stream));
+            }
         }
     }
     if (num_slots > ctx->coded) {
-        const int st = entropy_range(ctx, ctx->coded, num_slots - ctx->coded, lf_count > 0 && !(lf_drop() & 2));
+        const int st = entropy_range(ctx, ctx->coded, num_slots - ctx->coded, lf_count > 0 && !(lf_drop() & 2), lf_tokens_ride);
         if (st != ST_OK)
             return st;
         ctx->coded = num_slots;
     }
+    /* the pack workgroups ride in the emit launch and write the packed LF area at once (see above) */
+    bool lf_direct = lf_count > 0 && lf_first == 0 && lf_count == num_slots && !(lf_drop() & (4 | 8)) && !(debug_skip() & 4);
+    for (int i = 0; i < num_slots; i++)
+        lf_direct = lf_direct && ctx->slot_lane_chain[i];
     if (!(debug_skip() & 4)) {
         /* section sizes -> byte offsets, then the sections themselves: lane-form slots write their bits
          * straight into place, wave-form slots copy theirs out of the reversed bit buffers.  A frame whose slots are all
@@ -2421,7 +2469,9 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
         if (all_emit)
             HIP_TRY(ctx, hydk::launch_rans_emit(ctx->d_jobs, ctx->sym_count, ctx->rans_aux, ctx->rans_flags, ctx->tok_cap,
                                                 ctx->rans_final, ctx->group_bits, ctx->offsets, ctx->payload, num_slots,
-                                                ctx->status, ctx->total, ctx->payload_cap, ctx->stream));
+                                                ctx->status, ctx->total, ctx->payload_cap, ctx->lf_recs, ctx->lf_work,
+                                                ctx->lf_streams, lf_direct ? ctx->lf_packed : nullptr,
+                                                (uint32_t)((size_t)ctx->max_slots * HYDK_LF_BITWORDS), ctx->lf_total, ctx->stream));
         else
             HIP_TRY(ctx, hydk::launch_scan(ctx->group_bits, count, ctx->offsets, ctx->total, ctx->payload, ctx->payload_cap, 1,
                                            ctx->status, ctx->stream));
@@ -2435,7 +2485,8 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
                 HIP_TRY(ctx, hydk::launch_rans_emit(ctx->d_jobs + first, ctx->sym_count + g0, ctx->rans_aux + g0 * ctx->tok_cap,
                                                     ctx->rans_flags + g0 * (ctx->tok_cap / 16), ctx->tok_cap,
                                                     ctx->rans_final + g0, ctx->group_bits + g0, ctx->offsets + g0, ctx->payload,
-                                                    n, ctx->status, nullptr, 0, ctx->stream));
+                                                    n, ctx->status, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                                                    ctx->stream));
             else
                 HIP_TRY(ctx, hydk::launch_pack(ctx->bitbuf + g0 * ctx->bit_pitch_words, ctx->bit_pitch_words,
                                                ctx->group_bits + g0, ctx->offsets + g0, ctx->payload,
@@ -2443,14 +2494,28 @@ int hydamd_run_entropy(HydAmdContext *ctx, int num_slots) {
             first = last + 1;
         }
     }
-    if (lf_count > 0) {
+    if (lf_direct) {
+        /* the emit launch has left lf_packed, every stream's offset and the LF total: what the gather kernel leaves.  The
+         * closing publish launch below carries the total */
+        ctx->lf_coded = num_slots;
+        ctx->lf_slots = num_slots;
+        ctx->lf_need_gather = false;
+        ctx->lf_direct = true;
+        ctx->lf_total_unpublished = true;
+    } else if (lf_count > 0) {
         ScopedTimer timer(ctx, HYDAMD_K_LF);
+        {
+            const int st = stage_direct_slots(ctx, ctx->stream);
+            if (st != ST_OK)
+                return st;
+        }
         if (!(lf_drop() & 4))
         HIP_TRY(ctx, hydk::launch_lf_back(ctx->d_jobs + lf_first, ctx->lf_recs + (size_t)lf_first * HYDK_LF_SYMBOLS,
                                           ctx->lf_streams + lf_first, ctx->lf_bits + (size_t)lf_first * HYDK_LF_BITWORDS,
                                           ctx->lf_work + (size_t)lf_first * hydk::lf_work_bytes(), lf_count, ctx->stream));
         ctx->lf_coded = num_slots;
         ctx->lf_need_gather = true;
+        ctx->lf_direct = false;
     }
     {
         const int st = join_lf(ctx, num_slots, true);
@@ -2816,8 +2881,11 @@ int hydamd_read_lf_bits(HydAmdContext *ctx, int slot, uint8_t *dst, size_t capac
     HydkLfStream h;
     HIP_TRY(ctx, hipMemcpy(&h, ctx->lf_streams + slot, sizeof(h), hipMemcpyDeviceToHost));
     const size_t have = ((size_t)h.bit_count + 7u) / 8u, n = capacity < have ? capacity : have;
+    /* where the frame's route left the stream: staged in the slot's own words, or only in the packed area at its offset */
+    const uint8_t *src = ctx->lf_direct ? (const uint8_t *)ctx->lf_packed + h.offset
+                                        : (const uint8_t *)(ctx->lf_bits + (size_t)slot * HYDK_LF_BITWORDS);
     if (n)
-        HIP_TRY(ctx, hipMemcpy(dst, ctx->lf_bits + (size_t)slot * HYDK_LF_BITWORDS, n, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
     memset(dst + n, 0, capacity - n);
     return ST_OK;
 }

@@ -1383,6 +1383,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
 }
 
 #include "lf_huffman.h" /* the LF coder's code construction rides in the table kernel's (or the chain kernel's) launch, see below */
+#include "lf_windows.h" /* and its token and pack workgroups in the table kernel's and the emit kernel's */
 
 /* a group coded by several transform workgroups (k_transform_tokenize, plog > 0): part q's records sit at q * (tok_cap >> plog)
  * of the group's token array; moved down so that the array is the group's symbol stream in one piece, and the group's symbol
@@ -1452,15 +1453,43 @@ __global__ __launch_bounds__(kThreads) void k_join_parts(const HydkLfJob *__rest
  * LF group s's coefficient stream (lf_huffman.h: 200 us of one wavefront, which depends only on the LF token histograms
  * and not on this kernel's tables).  An A/B switch (HYDAMD_LF_CODES_RIDE=tables): by default the passengers ride in the
  * chain kernel's launch, which lasts 2.5 ms anyway.
+ * With lf_recs != NULL (never together with the code builders, which need the finished histogram) the launch carries the LF
+ * coder's TOKEN workgroups of the same LF groups instead: kLfWorkgroups per LF group behind the table workgroups, which stay
+ * first in the grid because the chains wait for them.  Both read only what the transform kernel left and write disjoint
+ * memory (lf_hist is the token histogram they add to, zero on entry like hist_all), so the token kernel's 170 us no longer
+ * stand in the stream in front of this kernel's 95.  The workgroup's LDS is one buffer that each role views as its own.
  * ======================================================================================== */
+struct TablesLds {
+    uint32_t freq[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
+    uint32_t cutoff[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
+    uint32_t other[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
+    uint32_t shift[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
+    uint32_t base[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
+    uint8_t under[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
+    uint8_t over[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
+    uint32_t alpha[HYDK_MAX_CLUSTERS];
+    uint32_t log_alpha, err;
+};
+template <typename A, typename B, typename C>
+constexpr size_t largest_of() { return sizeof(A) > sizeof(B) ? (sizeof(A) > sizeof(C) ? sizeof(A) : sizeof(C)) : (sizeof(B) > sizeof(C) ? sizeof(B) : sizeof(C)); }
+
 __global__ __launch_bounds__(kThreads) void k_build_tables(const uint32_t *hist_all, HydkTables *tabs,
                                                            const uint32_t *alpha_max_all, int nclusters,
                                                            uint32_t alpha_floor, const uint32_t *alpha_floor_dev,
-                                                           int first_slot, int num_slots, const uint32_t *lf_hist,
-                                                           HydkLfStream *lf_streams, void *lf_work, const HydkLfJob *__restrict__ jobs_all) {
+                                                           int first_slot, int num_slots, uint32_t *lf_hist,
+                                                           HydkLfStream *lf_streams, void *lf_work, const HydkLfJob *__restrict__ jobs_all,
+                                                           unsigned long long *lf_recs) {
+    static_assert(kThreads == kLfThreads, "the LF roles are workgroups of this kernel");
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[largest_of<TablesLds, LfHuffScratch, LfTokenLds>()];
+    if ((int)blockIdx.x >= num_slots && lf_recs) {
+        const int p = (int)blockIdx.x - num_slots, s = p / kLfWorkgroups;
+        lf_tokens_role(jobs_all[first_slot + s], lf_recs + (size_t)s * HYDK_LF_SYMBOLS, lf_hist + (size_t)s * HYDK_LF_CODES,
+                       ((LfWork *)lf_work)[s], p - s * kLfWorkgroups, *(LfTokenLds *)s_raw);
+        return;
+    }
     HYDK_URGENT();
     if ((int)blockIdx.x >= num_slots) {
-        __shared__ LfHuffScratch s_huff;
+        LfHuffScratch &s_huff = *(LfHuffScratch *)s_raw;
         const int s = (int)blockIdx.x - num_slots;
         if (threadIdx.x < 64)
             lf_code_and_offsets_wave(lf_hist + (size_t)s * HYDK_LF_CODES, ((LfWork *)lf_work)[s], lf_streams + s,
@@ -1470,15 +1499,16 @@ __global__ __launch_bounds__(kThreads) void k_build_tables(const uint32_t *hist_
     const unsigned slot = (unsigned)first_slot + blockIdx.x; /* all arrays are indexed by the frame's slot */
     const uint32_t *hist = hist_all + (size_t)slot * HYDK_MAX_CLUSTERS * HYDK_ALPHABET;
     HydkTables *tab = tabs + slot;
-    __shared__ uint32_t s_freq[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
-    __shared__ uint32_t s_cutoff[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
-    __shared__ uint32_t s_other[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
-    __shared__ uint32_t s_shift[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
-    __shared__ uint32_t s_base[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
-    __shared__ uint8_t s_under[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
-    __shared__ uint8_t s_over[HYDK_MAX_CLUSTERS][HYDK_ALPHABET];
-    __shared__ uint32_t s_alpha[HYDK_MAX_CLUSTERS];
-    __shared__ uint32_t s_log_alpha, s_err;
+    TablesLds &L = *(TablesLds *)s_raw;
+    uint32_t(&s_freq)[HYDK_MAX_CLUSTERS][HYDK_ALPHABET] = L.freq;
+    uint32_t(&s_cutoff)[HYDK_MAX_CLUSTERS][HYDK_ALPHABET] = L.cutoff;
+    uint32_t(&s_other)[HYDK_MAX_CLUSTERS][HYDK_ALPHABET] = L.other;
+    uint32_t(&s_shift)[HYDK_MAX_CLUSTERS][HYDK_ALPHABET] = L.shift;
+    uint32_t(&s_base)[HYDK_MAX_CLUSTERS][HYDK_ALPHABET] = L.base;
+    uint8_t(&s_under)[HYDK_MAX_CLUSTERS][HYDK_ALPHABET] = L.under;
+    uint8_t(&s_over)[HYDK_MAX_CLUSTERS][HYDK_ALPHABET] = L.over;
+    uint32_t(&s_alpha)[HYDK_MAX_CLUSTERS] = L.alpha;
+    uint32_t &s_log_alpha = L.log_alpha, &s_err = L.err;
 
     const int t = threadIdx.x;
     for (int i = t; i < HYDK_MAX_CLUSTERS * HYDK_ALPHABET; i += kThreads) {
@@ -2626,8 +2656,31 @@ __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restr
                                                         const uint16_t *aux_all, const uint16_t *flags_all, uint32_t aux_pitch,
                                                         const uint32_t *final_state_all, const uint32_t *group_bits_all,
                                                         uint64_t *offsets_all, uint8_t *payload, uint32_t *status, int vblocks,
-                                                        uint64_t *total, uint64_t payload_cap) {
-    __shared__ uint32_t s_win[4][kEmitWin];
+                                                        uint64_t *total, uint64_t payload_cap, int lf_slots,
+                                                        const unsigned long long *__restrict__ lf_recs, const void *lf_work,
+                                                        HydkLfStream *lf_streams, uint32_t *lf_packed, uint32_t lf_area_words,
+                                                        unsigned long long *lf_total) {
+    /* SELF with lf_slots > 0: behind the emit workgroups (the longer role, first in the grid) the launch carries the LF
+     * coder's PACK workgroups of the frame's lf_slots LF groups, kLfWorkgroups each.  Both need only what the chain launch
+     * and its code-building passengers left.  A pack workgroup writes its windows straight into the packed LF area: its
+     * slot's place there follows from the bit counts of the slots in front (lf_windows.h lf_packed_slot_offset), so no
+     * staged copy and no gather kernel.  The LDS is one buffer that each role views as its own. */
+    constexpr size_t kEmitLds = sizeof(uint32_t) * 4 * kEmitWin;
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[SELF && sizeof(LfPackLds) > kEmitLds ? sizeof(LfPackLds) : kEmitLds];
+    const int emit_wgs = (int)gridDim.x - (SELF ? lf_slots * kLfWorkgroups : 0);
+    if constexpr (SELF) {
+        if ((int)blockIdx.x >= emit_wgs) {
+            LfPackLds &L = *(LfPackLds *)s_raw;
+            const int p = (int)blockIdx.x - emit_wgs, s = p / kLfWorkgroups, wg = p - s * kLfWorkgroups;
+            const uint32_t off = lf_packed_slot_offset(lf_streams, s, lf_slots, lf_total, wg, L);
+            /* never outside the slot's own words (as where the streams are staged) nor beyond the area's end */
+            const uint32_t left = off < lf_area_words ? lf_area_words - off : 0u;
+            lf_pack_role(jobs[s], lf_recs + (size_t)s * HYDK_LF_SYMBOLS, ((const LfWork *)lf_work)[s], lf_streams[s], lf_packed + off,
+                         left < (uint32_t)HYDK_LF_BITWORDS ? left : (uint32_t)HYDK_LF_BITWORDS, wg, L);
+            return;
+        }
+    }
+    uint32_t(&s_win)[4][kEmitWin] = *(uint32_t(*)[4][kEmitWin])s_raw;
     HYDK_URGENT();
     /* a workgroup takes the virtual blocks blockIdx.x, blockIdx.x + gridDim.x, ... (four groups each, one per wavefront):
      * inside the pipelined loop a workgroup WAITS for its place — the transform kernels of fifteen other frames take
@@ -2834,7 +2887,7 @@ __global__ __launch_bounds__(kThreads) void k_rans_emit(const HydkLfJob *__restr
     if (lane == 0 && (cur & 31u))
         put(cur >> 5, carry);
     }; /* one_block */
-    for (int vb = blockIdx.x; vb < vblocks; vb += gridDim.x)
+    for (int vb = blockIdx.x; vb < vblocks; vb += emit_wgs)
         one_block(vb);
 }
 
@@ -3152,13 +3205,18 @@ hipError_t transform_footprint(int fmt, int storage, int xmode, int *lds_bytes, 
     return e;
 }
 
-/* lf_hist != NULL: the launch also builds the LF coder's prefix codes of the same LF groups (num_slots more workgroups);
- * lf_hist / lf_streams / lf_work already point at the first of them */
+/* lf_hist != NULL: the launch also carries LF coder work of the same LF groups; lf_hist / lf_streams / lf_work / lf_recs
+ * already point at the first of them.  lf_recs == NULL: the code builders (num_slots more workgroups; the token kernel
+ * has run).  lf_recs != NULL: the token workgroups (kLfWorkgroups per LF group), which fill lf_hist and lf_recs */
 hipError_t launch_tables(const uint32_t *hist, HydkTables *tabs, const uint32_t *alpha_max, int nclusters, int first_slot,
-                         int num_slots, uint32_t alpha_floor, const uint32_t *alpha_floor_dev, const uint32_t *lf_hist,
-                         HydkLfStream *lf_streams, void *lf_work, const HydkLfJob *jobs_all, hipStream_t stream) {
-    hipLaunchKernelGGL(k_build_tables, dim3(lf_hist ? 2 * num_slots : num_slots), dim3(kThreads), 0, stream, hist, tabs, alpha_max,
-                       nclusters, alpha_floor, alpha_floor_dev, first_slot, num_slots, lf_hist, lf_streams, lf_work, jobs_all);
+                         int num_slots, uint32_t alpha_floor, const uint32_t *alpha_floor_dev, uint32_t *lf_hist,
+                         HydkLfStream *lf_streams, void *lf_work, unsigned long long *lf_recs, const HydkLfJob *jobs_all,
+                         hipStream_t stream) {
+    if (!lf_hist)
+        lf_recs = nullptr;
+    const int riders = !lf_hist ? 0 : lf_recs ? kLfWorkgroups * num_slots : num_slots;
+    hipLaunchKernelGGL(k_build_tables, dim3(num_slots + riders), dim3(kThreads), 0, stream, hist, tabs, alpha_max,
+                       nclusters, alpha_floor, alpha_floor_dev, first_slot, num_slots, lf_hist, lf_streams, lf_work, jobs_all, lf_recs);
     return hipGetLastError();
 }
 
@@ -3222,11 +3280,17 @@ hipError_t launch_rans_lanes(const HydkLfJob *d_jobs, const uint32_t *sym_count,
 }
 
 /* total != NULL: the launch covers every group of the frame (slot 0 onwards) and finds the sections' offsets itself; it writes
- * offsets[], *total and the payload overflow status, and no scan kernel runs in front of it */
+ * offsets[], *total and the payload overflow status, and no scan kernel runs in front of it.
+ * lf_packed != NULL (only with total != NULL): the launch also packs the LF streams of the same num_slots LF groups, whose
+ * codes and window offsets the chain launch's passengers have left, straight into the packed LF area of lf_area_words
+ * words; it writes every lf_streams[].offset and *lf_total, as launch_lf_back + launch_lf_gather would */
 hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, const uint16_t *aux, const uint16_t *flags,
                             uint32_t aux_pitch, const uint32_t *final_state, const uint32_t *group_bits, uint64_t *offsets,
                             uint8_t *payload, int num_slots, uint32_t *status, uint64_t *total, uint64_t payload_cap,
-                            hipStream_t stream) {
+                            const unsigned long long *lf_recs, const void *lf_work, HydkLfStream *lf_streams, uint32_t *lf_packed,
+                            uint32_t lf_area_words, unsigned long long *lf_total, hipStream_t stream) {
+    if (lf_packed && !total)
+        return hipErrorInvalidValue;
     /* virtual blocks per workgroup: HYDAMD_EMIT_SHARE (A/B; 1 = one workgroup per four groups, as until round 5) */
     static const int share = [] {
         const char *v = getenv("HYDAMD_EMIT_SHARE");
@@ -3234,13 +3298,17 @@ hipError_t launch_rans_emit(const HydkLfJob *d_jobs, const uint32_t *sym_count, 
         return n < 1 ? 1 : n > 16 ? 16 : n;
     }();
     const int vblocks = num_slots * 16;
-    const dim3 grid((vblocks + share - 1) / share);
+    const int lf_slots = lf_packed ? num_slots : 0;
+    const dim3 grid((vblocks + share - 1) / share + lf_slots * kLfWorkgroups); /* the emit workgroups, then the pack workgroups */
     if (total)
         hipLaunchKernelGGL(k_rans_emit<true>, grid, dim3(kThreads), 0, stream, d_jobs, sym_count, aux, flags, aux_pitch, final_state,
-                           group_bits, offsets, payload, status, vblocks, total, payload_cap);
+                           group_bits, offsets, payload, status, vblocks, total, payload_cap, lf_slots, lf_recs, lf_work, lf_streams,
+                           lf_packed, lf_area_words, lf_total);
     else
         hipLaunchKernelGGL(k_rans_emit<false>, grid, dim3(kThreads), 0, stream, d_jobs, sym_count, aux, flags, aux_pitch,
-                           final_state, group_bits, offsets, payload, status, vblocks, (uint64_t *)nullptr, (uint64_t)0);
+                           final_state, group_bits, offsets, payload, status, vblocks, (uint64_t *)nullptr, (uint64_t)0, 0,
+                           (const unsigned long long *)nullptr, (const void *)nullptr, (HydkLfStream *)nullptr, (uint32_t *)nullptr, 0u,
+                           (unsigned long long *)nullptr);
     return hipGetLastError();
 }
 
