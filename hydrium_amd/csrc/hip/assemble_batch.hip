@@ -45,6 +45,7 @@
 #include <new>
 
 #include "../../../include/hydrium_amd.h"
+#include "hydk_batch_asm.h"
 #include "hydk_tiles.h"
 #include "hydk_common.h"
 #include "hydk_asm_writers.h"

@@ -29,6 +29,7 @@
 #include <new>
 
 #include "../../../include/hydrium_amd.h"
+#include "hydk_tile_asm.h"
 #include "hydk_tiles.h"
 
 namespace {

@@ -8,17 +8,17 @@
  * writes for that picture alone (libhydrium.c:172-203, encoder.c:968-1005), back to back in one device buffer with a
  * table of their offsets.
  *
- * Policy HERE, as in tiled.c wherever the two coincide: the PLAN — every byte that does not depend on the pixels, the
- * same for every frame of a batch — built once per object with the planners the other device-side assemblers use
- * (assembler.c's for shapes of several LF groups, tiled.c's shape planner for shapes of one); ONE context of
- * max_frames x n slots and one stream; the host waits once per batch (hydamd_sync, which is also where a batch that
- * outgrew the context's buffers is rerun), checks what the assembly left and repeats it if the batch was rerun; after a
- * failure the stream is drained before the call returns.
+ * This file's own: the PLAN — every byte that does not depend on the pixels, the same for every frame of a batch — built
+ * once per object with the planners the other device-side assemblers use (assembler.c's for shapes of several LF groups,
+ * tiled.c's shape planner for shapes of one); the argument checks; and the launch group, hydamd_encode_image_batch over
+ * max_frames x n slots.  Everything behind the launch group — reservation, assembly, the wait and its rerun, results and
+ * read-back, per-image outcomes — is the driver's, which the mixed-size batches share (batchrun.c).
  */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include "batchrun.h"
 #include "bitio.h"
 #include "frame.h"
 #include "hydrium_amd.h"
@@ -31,22 +31,6 @@
 #ifndef HYDRIUM_EXPORT
 #define HYDRIUM_EXPORT __attribute__((visibility("default")))
 #endif
-
-typedef struct HydkBatchAsm HydkBatchAsm; /* assemble_batch.hip */
-int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_bytes, HydkBatchAsm **out);
-void hydk_batch_destroy(HydkBatchAsm *a);
-const char *hydk_batch_error(HydkBatchAsm *a);
-uint64_t hydk_batch_fixed_bytes(HydkBatchAsm *a);
-int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t blob_cap, const void *extents, void *stream);
-int hydk_batch_reserve(HydkBatchAsm *a, uint64_t bytes, void *stream);
-const uint8_t *hydk_batch_out(HydkBatchAsm *a);
-const uint64_t *hydk_batch_offsets_dev(HydkBatchAsm *a);
-int hydk_batch_wait(HydkBatchAsm *a, void *stream);
-int hydk_batch_result(HydkBatchAsm *a, uint32_t *err, uint64_t *total, const uint64_t **offsets);
-int hydk_batch_read(HydkBatchAsm *a, uint64_t from, uint8_t *dst, size_t n);
-void hydk_batch_set_image_errors(HydkBatchAsm *a, int per_image);
-const uint64_t *hydk_batch_status(HydkBatchAsm *a);
-const uint32_t *hydk_batch_status_dev(HydkBatchAsm *a);
 
 /* k_pieces_copy takes at most 2040 pieces (HYDK_COPY_MAX_PIECES): a batch has F (3 n + 5) of them, and with F n <= 255
  * that is at most 3 x 255 + 5 x 255 = 2040 (frames of one LF group: 8 F) */
@@ -137,34 +121,19 @@ static int plan_one_lf_group(const HYDImageMetadata *md, const uint8_t *icc, siz
 struct HydAmdBatch {
     int device, max_frames;
     size_t W, H, n; /* n: LF groups of a frame */
-    HydAmdContext *ctx;
-    HydkBatchAsm *as;
-    int frames;     /* of the batch in flight / finished */
-    int in_flight, have_result;
-    size_t total;
-    uint64_t offsets[BATCH_MAX_SLOTS + 1];
-    uint32_t status[BATCH_MAX_SLOTS]; /* of the finished batch's frames */
-    unsigned reruns;
-    char err[256];
+    HydBatchRun run;
 };
 
 static char g_create_error[256];
 
-static int fail(HydAmdBatch *b, int code, const char *what, const char *detail) {
-    snprintf(b->err, sizeof(b->err), "%s%s%s", what, detail && *detail ? ": " : "", detail && *detail ? detail : "");
-    return code;
-}
+#define RUN(b) ((b) ? &(b)->run : NULL)
 
-HYDRIUM_EXPORT const char *hydamd_batch_error(HydAmdBatch *b) { return b ? b->err : g_create_error; }
+HYDRIUM_EXPORT const char *hydamd_batch_error(HydAmdBatch *b) { return b ? b->run.err : g_create_error; }
 
 HYDRIUM_EXPORT void hydamd_batch_destroy(HydAmdBatch *b) {
     if (!b)
         return;
-    if (b->ctx) {
-        (void)hydamd_sync(b->ctx);
-        hydk_batch_destroy(b->as);
-        hydamd_destroy(b->ctx);
-    }
+    hyd_batchrun_close(&b->run);
     free(b);
 }
 
@@ -207,16 +176,8 @@ HYDRIUM_EXPORT HydAmdBatch *hydamd_batch_create(int device, const HYDImageMetada
         err = "no usable HIP device";
         goto out;
     }
-    {
-        /* the bytes the plan is made of are written by an encoder object, which also checks the image's bounds */
-        HYDEncoder *e = hyd_encoder_new();
-        st = e ? hyd_set_metadata(e, md) : HYD_NOMEM;
-        if (st && e)
-            snprintf(g_create_error, sizeof(g_create_error), "%s", hyd_error_message_get(e));
-        hyd_encoder_destroy(e);
-        if (st)
-            goto out;
-    }
+    if ((st = hydk_plan_check_metadata(md, g_create_error, sizeof(g_create_error))) != 0)
+        goto out;
     if (n == 1) {
         st = plan_one_lf_group(md, icc, icc_size, &plan, &plan_len, &err);
     } else { /* one blob (the batch view), its LF groups in raster order */
@@ -238,25 +199,18 @@ HYDRIUM_EXPORT HydAmdBatch *hydamd_batch_create(int device, const HYDImageMetada
     b->W = md->width;
     b->H = md->height;
     b->n = n;
-    b->ctx = hydamd_create(device, (int)((size_t)max_frames * n), md->linear_light != 0, 0, &st);
-    if (!b->ctx) {
-        snprintf(g_create_error, sizeof(g_create_error), "%s", hydamd_error(NULL));
-        free(b);
-        b = NULL;
-        goto out;
-    }
-    if ((st = hydamd_set_lf_coder(b->ctx, 2)) != 0 || (st = hydamd_set_rans_waves(b->ctx, 5)) != 0) {
-        snprintf(g_create_error, sizeof(g_create_error), "%s", hydamd_error(b->ctx));
-    } else if ((st = hydk_batch_create(device, max_frames, plan, plan_len, &b->as)) != 0) {
-        snprintf(g_create_error, sizeof(g_create_error), "the batch assembler could not be created (status %d)", st);
-    }
+    st = hyd_batchrun_open(&b->run, device, (int)((size_t)max_frames * n), md->linear_light != 0, "hydamd_batch_result", g_create_error,
+                           sizeof(g_create_error));
+    if (!st)
+        st = hyd_batchrun_adopt(&b->run, hydk_batch_create(device, max_frames, plan, plan_len, &b->run.as), g_create_error,
+                                sizeof(g_create_error));
     if (st) {
-        hydamd_destroy(b->ctx);
         free(b);
         b = NULL;
         goto out;
     }
-    st = HYD_OK;
+    /* what the plan and the assembler's scratch add to every frame: fixed once the assembler of this one shape exists */
+    b->run.fixed = (uint64_t)max_frames * hydk_batch_fixed_bytes(b->run.as);
 out:
     if (err && !g_create_error[0])
         snprintf(g_create_error, sizeof(g_create_error), "%s", err);
@@ -267,185 +221,62 @@ out:
     return b;
 }
 
-/* after a failure once work was enqueued: nothing of this object is left running when the call returns */
-static void drain(HydAmdBatch *b) {
-    (void)hydamd_sync(b->ctx);
-    (void)hydk_batch_wait(b->as, hydamd_get_stream(b->ctx));
-    b->in_flight = 0;
-}
-
-/* The output holds whatever the context's buffers can: their bound for ALL the object's slots plus what the plan and
- * the assembler's scratch add per frame.  Replacing the buffer waits for the stream, so it is sized for max_frames and
- * reserved BEFORE a batch is enqueued (an object's first batch allocates, later ones find it there); it is looked at
- * again before every assembly, where only a context that has enlarged its buffers since (a rerun) makes it grow. */
-static int reserve_output(HydAmdBatch *b) {
-    const uint64_t want = (uint64_t)hydamd_blob_bound(b->ctx, (int)((size_t)b->max_frames * b->n)) +
-                          (uint64_t)b->max_frames * hydk_batch_fixed_bytes(b->as);
-    const int st = hydk_batch_reserve(b->as, want, hydamd_get_stream(b->ctx));
-    return st ? fail(b, st, "output buffer", hydk_batch_error(b->as)) : HYD_OK;
-}
-
-/* the batch's results as a view, and its assembly behind them */
-static int assemble(HydAmdBatch *b) {
-    const void *blob = NULL, *ext = NULL;
-    size_t cap = 0;
-    const int slots = (int)((size_t)b->frames * b->n);
-    void *stream = hydamd_get_stream(b->ctx);
-    int st = reserve_output(b);
-    if (st)
-        return st;
-    st = hydamd_export_batch_owned(b->ctx, slots, &blob, &cap, &ext);
-    if (st)
-        return fail(b, st, "batch view", hydamd_error(b->ctx));
-    st = hydk_batch_run(b->as, (uint32_t)b->frames, blob, cap, ext, stream);
-    return st ? fail(b, st, "batch assembly", hydk_batch_error(b->as)) : HYD_OK;
-}
-
 HYDRIUM_EXPORT int hydamd_encode_batch(HydAmdBatch *b, int frames, const void *const *src, ptrdiff_t row_stride, ptrdiff_t pixel_stride,
                                        int sample_fmt) {
     if (!b)
         return HYD_API_ERROR;
+    HydBatchRun *r = &b->run;
     if (frames < 1 || frames > b->max_frames)
-        return fail(b, HYD_API_ERROR, "frames must be between 1 and max_frames", NULL);
+        return hyd_batchrun_fail(r, HYD_API_ERROR, "frames must be between 1 and max_frames", NULL);
     if (!src)
-        return fail(b, HYD_API_ERROR, "null pixel pointer", NULL);
+        return hyd_batchrun_fail(r, HYD_API_ERROR, "null pixel pointer", NULL);
     for (int i = 0; i < 3 * frames; i++)
         if (!src[i])
-            return fail(b, HYD_API_ERROR, "null pixel pointer", NULL);
+            return hyd_batchrun_fail(r, HYD_API_ERROR, "null pixel pointer", NULL);
     if (!hyd_fmt_is_device(sample_fmt))
-        return fail(b, HYD_API_ERROR, "Invalid Sample Format", NULL);
+        return hyd_batchrun_fail(r, HYD_API_ERROR, "Invalid Sample Format", NULL);
     for (int f = 0; f < frames; f++)
         if (!hyd_fmt_layout_ok(sample_fmt, src + 3 * f, pixel_stride))
-            return fail(b, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
-    if (b->in_flight)
-        return fail(b, HYD_API_ERROR, "a batch is in flight: hydamd_batch_result first", NULL);
-    b->err[0] = 0;
-    b->have_result = 0;
-    b->frames = frames;
-    int st = reserve_output(b); /* nothing of this batch is in the stream yet */
+            return hyd_batchrun_fail(r, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
+    int st = hyd_batchrun_busy(r);
     if (st)
         return st;
-    b->in_flight = 1;
-    st = hydamd_encode_image_batch(b->ctx, frames, src, row_stride, pixel_stride, sample_fmt, b->W, b->H);
+    r->err[0] = 0;
+    r->have_result = 0;
+    r->frames = frames;
+    r->slots = (int)((size_t)frames * b->n);
+    if ((st = hyd_batchrun_reserve(r)) != 0) /* nothing of this batch is in the stream yet */
+        return st;
+    r->in_flight = 1;
+    st = hydamd_encode_image_batch(r->ctx, frames, src, row_stride, pixel_stride, sample_fmt, b->W, b->H);
     if (st)
-        st = fail(b, st, "batch", hydamd_error(b->ctx));
+        st = hyd_batchrun_fail(r, st, "batch", hydamd_error(r->ctx));
     else
-        st = assemble(b);
+        st = hyd_batchrun_assemble(r);
     if (st)
-        drain(b);
+        hyd_batchrun_drain(r);
     return st;
 }
 
-/* the batch in flight: wait, let hydamd_sync rerun it if it outgrew a buffer, and see its frames into their files */
-static int settle(HydAmdBatch *b) {
-    const unsigned before = hydamd_overflow_reruns(b->ctx);
-    int st = hydamd_sync(b->ctx);
-    if (st)
-        return fail(b, st, "batch", hydamd_error(b->ctx));
-    b->reruns += hydamd_overflow_reruns(b->ctx) - before;
-    for (int attempt = 0; attempt < 4; attempt++) {
-        uint32_t err = 0;
-        uint64_t total = 0;
-        const uint64_t *offsets = NULL;
-        hydk_batch_result(b->as, &err, &total, &offsets);
-        if (!err) {
-            b->total = (size_t)total;
-            memcpy(b->offsets, offsets, ((size_t)b->frames + 1) * sizeof(uint64_t));
-            for (int f = 0; f < b->frames; f++)
-                b->status[f] = (uint32_t)hydk_batch_status(b->as)[f];
-            return HYD_OK;
-        }
-        if (err & HYDK_ASM_E_NAN)
-            return fail(b, HYD_API_ERROR, "Invalid NaN Float", NULL);
-        if (err & HYDK_ASM_E_SPACE) /* the output was sized from the context's capacities */
-            return fail(b, HYD_INTERNAL_ERROR, "the batch's files are larger than the bound of their output buffer", NULL);
-        if (err & (HYDK_ASM_E_BLOB | HYDK_ASM_E_SLOT | HYDK_ASM_E_HEAD | HYDK_ASM_E_SIZE | HYDK_ASM_E_SCRATCH))
-            return fail(b, HYD_INTERNAL_ERROR, "batch assembly failed on the device", NULL);
-        /* RETRY: the assembly saw the first run's incomplete results (hydamd_sync has rerun the batch since): the view
-         * and the same launches again, into an output sized for the enlarged context */
-        if ((st = assemble(b)) != 0)
-            return st;
-        if ((st = hydk_batch_wait(b->as, hydamd_get_stream(b->ctx))) != 0)
-            return fail(b, st, "batch assembly", hydk_batch_error(b->as));
-    }
-    return fail(b, HYD_INTERNAL_ERROR, "a batch is still incomplete after its rerun", NULL);
-}
+HYDRIUM_EXPORT int hydamd_batch_result(HydAmdBatch *b, size_t *total_bytes) { return hyd_batchrun_result(RUN(b), total_bytes); }
 
-HYDRIUM_EXPORT int hydamd_batch_result(HydAmdBatch *b, size_t *total_bytes) {
-    if (!b)
-        return HYD_API_ERROR;
-    if (!b->have_result) {
-        if (!b->in_flight)
-            return fail(b, HYD_API_ERROR, "no batch in flight", NULL);
-        const int st = settle(b);
-        if (st) {
-            drain(b);
-            return st;
-        }
-        b->in_flight = 0;
-        b->have_result = 1;
-    }
-    if (total_bytes)
-        *total_bytes = b->total;
-    return HYD_OK;
-}
-
-HYDRIUM_EXPORT int hydamd_batch_offsets(HydAmdBatch *b, uint64_t *offsets) {
-    if (!b || !b->have_result)
-        return b ? fail(b, HYD_API_ERROR, "no finished batch: hydamd_batch_result first", NULL) : HYD_API_ERROR;
-    if (!offsets)
-        return fail(b, HYD_API_ERROR, "null output pointer", NULL);
-    memcpy(offsets, b->offsets, ((size_t)b->frames + 1) * sizeof(uint64_t));
-    return HYD_OK;
-}
+HYDRIUM_EXPORT int hydamd_batch_offsets(HydAmdBatch *b, uint64_t *offsets) { return hyd_batchrun_offsets(RUN(b), offsets); }
 
 HYDRIUM_EXPORT int hydamd_batch_read(HydAmdBatch *b, int frame, uint8_t *dst, size_t capacity) {
-    if (!b || !b->have_result)
-        return b ? fail(b, HYD_API_ERROR, "no finished batch: hydamd_batch_result first", NULL) : HYD_API_ERROR;
-    if (!dst)
-        return fail(b, HYD_API_ERROR, "null output pointer", NULL);
-    if (frame < -1 || frame >= b->frames)
-        return fail(b, HYD_API_ERROR, "no such frame in the batch", NULL);
-    const uint64_t from = frame < 0 ? 0 : b->offsets[frame], to = frame < 0 ? b->total : b->offsets[frame + 1];
-    if (capacity < to - from)
-        return fail(b, HYD_API_ERROR, "output buffer too small", NULL);
-    const int st = hydk_batch_read(b->as, from, dst, (size_t)(to - from));
-    return st ? fail(b, st, "read-back", hydk_batch_error(b->as)) : HYD_OK;
+    return hyd_batchrun_read(RUN(b), frame, dst, capacity);
 }
 
-HYDRIUM_EXPORT const uint8_t *hydamd_batch_device(HydAmdBatch *b) { return b && b->have_result ? hydk_batch_out(b->as) : NULL; }
+HYDRIUM_EXPORT const uint8_t *hydamd_batch_device(HydAmdBatch *b) { return hyd_batchrun_device(RUN(b)); }
 
-HYDRIUM_EXPORT const uint64_t *hydamd_batch_offsets_device(HydAmdBatch *b) {
-    return b && b->have_result ? hydk_batch_offsets_dev(b->as) : NULL;
-}
+HYDRIUM_EXPORT const uint64_t *hydamd_batch_offsets_device(HydAmdBatch *b) { return hyd_batchrun_offsets_device(RUN(b)); }
 
-/* per-image outcomes, as hydamd_mixed_set_image_errors (mixed.c) */
-HYDRIUM_EXPORT int hydamd_batch_set_image_errors(HydAmdBatch *b, int per_image) {
-    if (!b)
-        return HYD_API_ERROR;
-    if (b->in_flight)
-        return fail(b, HYD_API_ERROR, "a batch is in flight: hydamd_batch_result first", NULL);
-    const int st = hydamd_set_bad_sample_per_slot(b->ctx, per_image != 0);
-    if (st)
-        return fail(b, st, "image errors", hydamd_error(b->ctx));
-    hydk_batch_set_image_errors(b->as, per_image != 0);
-    return HYD_OK;
-}
+HYDRIUM_EXPORT int hydamd_batch_set_image_errors(HydAmdBatch *b, int per_image) { return hyd_batchrun_set_image_errors(RUN(b), per_image); }
 
-HYDRIUM_EXPORT int hydamd_batch_image_status(HydAmdBatch *b, uint32_t *status) {
-    if (!b || !b->have_result)
-        return b ? fail(b, HYD_API_ERROR, "no finished batch: hydamd_batch_result first", NULL) : HYD_API_ERROR;
-    if (!status)
-        return fail(b, HYD_API_ERROR, "null output pointer", NULL);
-    memcpy(status, b->status, (size_t)b->frames * sizeof(uint32_t));
-    return HYD_OK;
-}
+HYDRIUM_EXPORT int hydamd_batch_image_status(HydAmdBatch *b, uint32_t *status) { return hyd_batchrun_image_status(RUN(b), status); }
 
-HYDRIUM_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b) {
-    return b && b->have_result ? hydk_batch_status_dev(b->as) : NULL;
-}
+HYDRIUM_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b) { return hyd_batchrun_image_status_device(RUN(b)); }
 
-HYDRIUM_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b) { return b ? b->reruns : 0; }
+HYDRIUM_EXPORT unsigned hydamd_batch_overflow_reruns(HydAmdBatch *b) { return b ? b->run.reruns : 0; }
 
 /* ---------------------------------------------------------------------------------------------
  * CPU-only test hook: the plan of a batch of one-LF-group frames (plan_one_lf_group above, the product's own) and the

@@ -6,10 +6,10 @@
  * way), and hydk_tiles.h lays frames of different shapes side by side.  Here both serve a queue of pictures of many
  * sizes — thumbnails, crops, the output of a decoder — each at most 2048 x 2048 pixels, ONE LF group: the launch group is
  * tiled.c's (hydamd_begin_batch(ctx, 1, frames), one hydamd_encode_lf_group per image with its own pointers, strides and
- * size), the assembly and the protocol are batch.c's (csrc/hip/assemble_batch.hip: every frame a complete file — what the
- * reference writes for that picture alone with both tile_size_shift -1 — back to back in one device buffer, the table of
- * their offsets beside it; the host waits once per batch, hydamd_sync reruns a batch that outgrew the context's buffers
- * and the assembly is repeated behind it; after a failure the stream is drained before the call returns).
+ * size), the assembly is batch.c's (csrc/hip/assemble_batch.hip: every frame a complete file — what the reference writes
+ * for that picture alone with both tile_size_shift -1 — back to back in one device buffer, the table of their offsets
+ * beside it), and the protocol behind the launch group — reservation, the wait and its rerun, results, read-back, per-image
+ * outcomes — is the driver both batch objects share (batchrun.c).
  *
  * What is this file's own is the PLAN: no two batches need the same one.  It holds a shape record per DISTINCT size of
  * the batch (tiled.c's shape planner) and a frame record per image whose prefix is that image's file header and one-frame
@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "batchrun.h"
 #include "bitio.h"
 #include "frame.h"
 #include "hydrium_amd.h"
@@ -41,23 +42,6 @@
 
 #define MIXED_DEFAULT_FRAMES 32
 #define MIXED_MAX_SIDE 2048u /* one LF group */
-
-typedef struct HydkBatchAsm HydkBatchAsm; /* assemble_batch.hip */
-int hydk_batch_create(int device, int max_frames, const void *plan, size_t plan_bytes, HydkBatchAsm **out);
-int hydk_batch_create_frames(int device, int max_frames, int max_slots, HydkBatchAsm **out);
-void hydk_batch_destroy(HydkBatchAsm *a);
-const char *hydk_batch_error(HydkBatchAsm *a);
-int hydk_batch_set_plan(HydkBatchAsm *a, const void *plan, size_t bytes, void *stream);
-int hydk_batch_run(HydkBatchAsm *a, uint32_t frames, const void *blob, uint64_t blob_cap, const void *extents, void *stream);
-int hydk_batch_reserve(HydkBatchAsm *a, uint64_t bytes, void *stream);
-const uint8_t *hydk_batch_out(HydkBatchAsm *a);
-const uint64_t *hydk_batch_offsets_dev(HydkBatchAsm *a);
-int hydk_batch_wait(HydkBatchAsm *a, void *stream);
-int hydk_batch_result(HydkBatchAsm *a, uint32_t *err, uint64_t *total, const uint64_t **offsets);
-int hydk_batch_read(HydkBatchAsm *a, uint64_t from, uint8_t *dst, size_t n);
-void hydk_batch_set_image_errors(HydkBatchAsm *a, int per_image);
-const uint64_t *hydk_batch_status(HydkBatchAsm *a);
-const uint32_t *hydk_batch_status_dev(HydkBatchAsm *a);
 
 /* ---------------------------------------------------------------------------------------------
  * the plan
@@ -307,40 +291,22 @@ static int build_frames_plan(int n, const MixedSize *sz, int linear_light, int m
  * ------------------------------------------------------------------------------------------- */
 struct HydAmdMixed {
     int device, max_frames, linear_light;
-    int max_slots;  /* LF-group slots of the context; `several`: images of up to 28 LF groups (hydamd_mixed_create_slots) */
-    int several;
-    int slots;      /* LF groups of the batch in flight / finished */
-    HydAmdContext *ctx;
-    HydkBatchAsm *as;
-    int frames; /* of the batch in flight / finished */
-    int in_flight, have_result;
-    int planned;                             /* images of the plan on the device (0: none), their sizes: */
+    int several;    /* images of up to 28 LF groups (hydamd_mixed_create_slots) */
+    int planned;    /* images of the plan on the device (0: none), their sizes (run.fixed is that plan's): */
     MixedSize sizes[HYDK_TILE_MAX_FRAMES];
-    uint64_t fixed;                          /* that plan's share of the output reservation */
-    size_t total;
-    uint64_t offsets[HYDK_TILE_MAX_FRAMES + 1];
-    uint32_t status[HYDK_TILE_MAX_FRAMES];   /* of the finished batch's images */
-    unsigned reruns;
-    char err[256];
+    HydBatchRun run;
 };
 
 static char g_create_error[256];
 
-static int fail(HydAmdMixed *m, int code, const char *what, const char *detail) {
-    snprintf(m->err, sizeof(m->err), "%s%s%s", what, detail && *detail ? ": " : "", detail && *detail ? detail : "");
-    return code;
-}
+#define RUN(m) ((m) ? &(m)->run : NULL)
 
-HYDRIUM_EXPORT const char *hydamd_mixed_error(HydAmdMixed *m) { return m ? m->err : g_create_error; }
+HYDRIUM_EXPORT const char *hydamd_mixed_error(HydAmdMixed *m) { return m ? m->run.err : g_create_error; }
 
 HYDRIUM_EXPORT void hydamd_mixed_destroy(HydAmdMixed *m) {
     if (!m)
         return;
-    if (m->ctx) {
-        (void)hydamd_sync(m->ctx);
-        hydk_batch_destroy(m->as);
-        hydamd_destroy(m->ctx);
-    }
+    hyd_batchrun_close(&m->run);
     free(m);
 }
 
@@ -371,27 +337,17 @@ static HydAmdMixed *create(int device, int max_frames, int max_lf_groups, int li
     m->max_frames = max_frames ? max_frames : MIXED_DEFAULT_FRAMES;
     m->linear_light = linear_light != 0;
     m->several = max_lf_groups >= 0;
-    m->max_slots = m->several ? max_lf_groups : m->max_frames;
-    m->ctx = hydamd_create(device, m->max_slots, m->linear_light, 0, &st);
-    if (!m->ctx) {
-        snprintf(g_create_error, sizeof(g_create_error), "%s", hydamd_error(NULL));
-        free(m);
-        m = NULL;
-        goto out;
-    }
-    if ((st = hydamd_set_lf_coder(m->ctx, 2)) != 0 || (st = hydamd_set_rans_waves(m->ctx, 5)) != 0) {
-        snprintf(g_create_error, sizeof(g_create_error), "%s", hydamd_error(m->ctx));
-    } else if ((st = m->several ? hydk_batch_create_frames(device, m->max_frames, m->max_slots, &m->as)
-                                : hydk_batch_create(device, m->max_frames, NULL, 0, &m->as)) != 0) {
-        snprintf(g_create_error, sizeof(g_create_error), "the batch assembler could not be created (status %d)", st);
-    }
+    const int max_slots = m->several ? max_lf_groups : m->max_frames;
+    st = hyd_batchrun_open(&m->run, device, max_slots, m->linear_light, "hydamd_mixed_result", g_create_error, sizeof(g_create_error));
+    if (!st)
+        st = hyd_batchrun_adopt(&m->run,
+                                m->several ? hydk_batch_create_frames(device, m->max_frames, max_slots, &m->run.as)
+                                           : hydk_batch_create(device, m->max_frames, NULL, 0, &m->run.as),
+                                g_create_error, sizeof(g_create_error));
     if (st) {
-        hydamd_destroy(m->ctx);
         free(m);
         m = NULL;
-        goto out;
     }
-    st = HYD_OK;
 out:
     if (status)
         *status = st;
@@ -413,25 +369,9 @@ HYDRIUM_EXPORT HydAmdMixed *hydamd_mixed_create_slots(int device, int max_frames
     return create(device, max_frames, max_lf_groups, linear_light, status);
 }
 
-/* after a failure once work was enqueued: nothing of this object is left running when the call returns */
-static void drain(HydAmdMixed *m) {
-    (void)hydamd_sync(m->ctx);
-    (void)hydk_batch_wait(m->as, hydamd_get_stream(m->ctx));
-    m->in_flight = 0;
-}
-
-/* The output holds whatever the context's buffers can — their bound for ALL the object's slots, so that only a context
- * that has enlarged its buffers (a rerun) or a plan of larger prefixes makes it grow — plus what THIS batch's plan and
- * the assembler's scratch add.  Replacing the buffer waits for the stream, so it is reserved BEFORE a batch is enqueued,
- * and looked at again before every assembly. */
-static int reserve_output(HydAmdMixed *m) {
-    const uint64_t want = (uint64_t)hydamd_blob_bound(m->ctx, m->max_slots) + m->fixed;
-    const int st = hydk_batch_reserve(m->as, want, hydamd_get_stream(m->ctx));
-    return st ? fail(m, st, "output buffer", hydk_batch_error(m->as)) : HYD_OK;
-}
-
 /* the batch's plan on the device: the previous batch's when its list of sizes is the same */
 static int plan_batch(HydAmdMixed *m, int frames, const HydAmdImageDesc *images) {
+    HydBatchRun *r = &m->run;
     int same = frames == m->planned;
     for (int f = 0; f < frames && same; f++)
         same = m->sizes[f].w == images[f].width && m->sizes[f].h == images[f].height;
@@ -445,44 +385,29 @@ static int plan_batch(HydAmdMixed *m, int frames, const HydAmdImageDesc *images)
         m->sizes[f].w = (uint32_t)images[f].width;
         m->sizes[f].h = (uint32_t)images[f].height;
     }
-    int st = m->several ? build_frames_plan(frames, m->sizes, m->linear_light, m->max_frames, m->max_slots, &plan, &plan_len, &m->fixed, &err)
-                        : build_plan(frames, m->sizes, m->linear_light, &plan, &plan_len, &m->fixed, &err);
+    int st = m->several ? build_frames_plan(frames, m->sizes, m->linear_light, m->max_frames, r->max_slots, &plan, &plan_len, &r->fixed, &err)
+                        : build_plan(frames, m->sizes, m->linear_light, &plan, &plan_len, &r->fixed, &err);
     if (st)
-        return fail(m, st, "plan", err);
-    st = hydk_batch_set_plan(m->as, plan, plan_len, hydamd_get_stream(m->ctx));
+        return hyd_batchrun_fail(r, st, "plan", err);
+    st = hydk_batch_set_plan(r->as, plan, plan_len, hydamd_get_stream(r->ctx));
     free(plan);
     if (st)
-        return fail(m, st, "plan", hydk_batch_error(m->as));
+        return hyd_batchrun_fail(r, st, "plan", hydk_batch_error(r->as));
     m->planned = frames;
     return HYD_OK;
 }
 
-/* the batch's results as a view, and its assembly behind them */
-static int assemble(HydAmdMixed *m) {
-    const void *blob = NULL, *ext = NULL;
-    size_t cap = 0;
-    void *stream = hydamd_get_stream(m->ctx);
-    int st = reserve_output(m);
-    if (st)
-        return st;
-    st = hydamd_export_batch_owned(m->ctx, m->slots, &blob, &cap, &ext);
-    if (st)
-        return fail(m, st, "batch view", hydamd_error(m->ctx));
-    st = hydk_batch_run(m->as, (uint32_t)m->frames, blob, cap, ext, stream);
-    return st ? fail(m, st, "batch assembly", hydk_batch_error(m->as)) : HYD_OK;
-}
-
 /* the launch group of images of 1..28 LF groups: image after image, an image's LF groups in raster order, each with its
  * own pointers — computed from the image's strides as hydamd_encode_image does — and clipped to the image */
-static int enqueue_several(HydAmdMixed *m, const HydAmdImageDesc *images, const int *sample_fmts) {
+static int enqueue_several(HydBatchRun *r, const HydAmdImageDesc *images, const int *sample_fmts) {
     unsigned counts[HYDK_TILE_MAX_FRAMES];
-    for (int f = 0; f < m->frames; f++)
+    for (int f = 0; f < r->frames; f++)
         counts[f] = lf_groups_of(images[f].width, images[f].height);
-    int st = hydamd_begin_batch_frames(m->ctx, m->frames, counts);
+    int st = hydamd_begin_batch_frames(r->ctx, r->frames, counts);
     if (st)
-        return fail(m, st, "begin launch group", hydamd_error(m->ctx));
+        return hyd_batchrun_fail(r, st, "begin launch group", hydamd_error(r->ctx));
     int slot = 0;
-    for (int f = 0; f < m->frames; f++) {
+    for (int f = 0; f < r->frames; f++) {
         const HydAmdImageDesc *d = &images[f];
         const int sample_fmt = sample_fmts[f];
         const size_t lfx = (d->width + 2047) >> 11, lfy = (d->height + 2047) >> 11;
@@ -492,30 +417,31 @@ static int enqueue_several(HydAmdMixed *m, const HydAmdImageDesc *images, const 
                 hyd_fmt_origin(sample_fmt, d->src, d->row_stride, d->pixel_stride, tx * 2048, ty * 2048, p);
                 const size_t w = d->width - tx * 2048 < 2048 ? d->width - tx * 2048 : 2048;
                 const size_t h = d->height - ty * 2048 < 2048 ? d->height - ty * 2048 : 2048;
-                if ((st = hydamd_encode_lf_group(m->ctx, slot, p, d->row_stride, d->pixel_stride, sample_fmt, w, h, (unsigned)(ty * lfx + tx))) != 0)
-                    return fail(m, st, "image", hydamd_error(m->ctx));
+                if ((st = hydamd_encode_lf_group(r->ctx, slot, p, d->row_stride, d->pixel_stride, sample_fmt, w, h, (unsigned)(ty * lfx + tx))) != 0)
+                    return hyd_batchrun_fail(r, st, "image", hydamd_error(r->ctx));
             }
     }
-    if ((st = hydamd_finish_frame(m->ctx, m->slots)) != 0)
-        return fail(m, st, "launch group", hydamd_error(m->ctx));
-    return assemble(m);
+    if ((st = hydamd_finish_frame(r->ctx, r->slots)) != 0)
+        return hyd_batchrun_fail(r, st, "launch group", hydamd_error(r->ctx));
+    return hyd_batchrun_assemble(r);
 }
 
 /* the launch group: tiled.c's, every image an LF group of its own size in a slot of its own */
 static int enqueue(HydAmdMixed *m, const HydAmdImageDesc *images, const int *sample_fmts) {
+    HydBatchRun *r = &m->run;
     if (m->several)
-        return enqueue_several(m, images, sample_fmts);
-    int st = hydamd_begin_batch(m->ctx, 1, m->frames);
+        return enqueue_several(r, images, sample_fmts);
+    int st = hydamd_begin_batch(r->ctx, 1, r->frames);
     if (st)
-        return fail(m, st, "begin launch group", hydamd_error(m->ctx));
-    for (int f = 0; f < m->frames; f++) {
+        return hyd_batchrun_fail(r, st, "begin launch group", hydamd_error(r->ctx));
+    for (int f = 0; f < r->frames; f++) {
         const HydAmdImageDesc *d = &images[f];
-        if ((st = hydamd_encode_lf_group(m->ctx, f, d->src, d->row_stride, d->pixel_stride, sample_fmts[f], d->width, d->height, 0)) != 0)
-            return fail(m, st, "image", hydamd_error(m->ctx));
+        if ((st = hydamd_encode_lf_group(r->ctx, f, d->src, d->row_stride, d->pixel_stride, sample_fmts[f], d->width, d->height, 0)) != 0)
+            return hyd_batchrun_fail(r, st, "image", hydamd_error(r->ctx));
     }
-    if ((st = hydamd_finish_frame(m->ctx, m->frames)) != 0)
-        return fail(m, st, "launch group", hydamd_error(m->ctx));
-    return assemble(m);
+    if ((st = hydamd_finish_frame(r->ctx, r->frames)) != 0)
+        return hyd_batchrun_fail(r, st, "launch group", hydamd_error(r->ctx));
+    return hyd_batchrun_assemble(r);
 }
 
 /* every image in its own sample format: the layer underneath takes a format per LF group (the transform launch builds a
@@ -524,52 +450,54 @@ static int enqueue(HydAmdMixed *m, const HydAmdImageDesc *images, const int *sam
 HYDRIUM_EXPORT int hydamd_encode_mixed_formats(HydAmdMixed *m, int frames, const HydAmdImageDesc *images, const int *sample_fmts) {
     if (!m)
         return HYD_API_ERROR;
+    HydBatchRun *r = &m->run;
     if (frames < 1 || frames > m->max_frames)
-        return fail(m, HYD_API_ERROR, "frames must be between 1 and max_frames", NULL);
+        return hyd_batchrun_fail(r, HYD_API_ERROR, "frames must be between 1 and max_frames", NULL);
     if (!images)
-        return fail(m, HYD_API_ERROR, "null image descriptors", NULL);
+        return hyd_batchrun_fail(r, HYD_API_ERROR, "null image descriptors", NULL);
     int slots = 0;
     for (int f = 0; f < frames; f++) {
         if (!images[f].src[0] || !images[f].src[1] || !images[f].src[2])
-            return fail(m, HYD_API_ERROR, "null pixel pointer", NULL);
+            return hyd_batchrun_fail(r, HYD_API_ERROR, "null pixel pointer", NULL);
         if (m->several) {
             const uint32_t n = lf_groups_of(images[f].width, images[f].height);
             if (!images[f].width || !images[f].height)
-                return fail(m, HYD_API_ERROR, "every image of a mixed batch must be at least 1 pixel in each direction", NULL);
+                return hyd_batchrun_fail(r, HYD_API_ERROR, "every image of a mixed batch must be at least 1 pixel in each direction", NULL);
             if (!n)
-                return fail(m, HYD_API_ERROR, "an image of a mixed batch holds at most 28 LF groups of 2048 x 2048 pixels", NULL);
+                return hyd_batchrun_fail(r, HYD_API_ERROR, "an image of a mixed batch holds at most 28 LF groups of 2048 x 2048 pixels", NULL);
             slots += (int)n;
             continue;
         }
         slots++;
         if (!images[f].width || !images[f].height || images[f].width > MIXED_MAX_SIDE || images[f].height > MIXED_MAX_SIDE)
-            return fail(m, HYD_API_ERROR, "every image of a mixed batch must be between 1 and 2048 pixels in each direction", NULL);
+            return hyd_batchrun_fail(r, HYD_API_ERROR, "every image of a mixed batch must be between 1 and 2048 pixels in each direction", NULL);
     }
-    if (slots > m->max_slots)
-        return fail(m, HYD_API_ERROR, "the batch holds more LF groups than the object has slots", NULL);
+    if (slots > r->max_slots)
+        return hyd_batchrun_fail(r, HYD_API_ERROR, "the batch holds more LF groups than the object has slots", NULL);
     if (!sample_fmts)
-        return fail(m, HYD_API_ERROR, "null sample formats", NULL);
+        return hyd_batchrun_fail(r, HYD_API_ERROR, "null sample formats", NULL);
     for (int f = 0; f < frames; f++)
         if (!hyd_fmt_is_device(sample_fmts[f]))
-            return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
+            return hyd_batchrun_fail(r, HYD_API_ERROR, "Invalid Sample Format", NULL);
     for (int f = 0; f < frames; f++)
         if (!hyd_fmt_layout_ok(sample_fmts[f], images[f].src, images[f].pixel_stride))
-            return fail(m, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
-    if (m->in_flight)
-        return fail(m, HYD_API_ERROR, "a batch is in flight: hydamd_mixed_result first", NULL);
-    m->err[0] = 0;
-    m->have_result = 0;
-    m->frames = frames;
-    m->slots = slots;
-    int st = plan_batch(m, frames, images); /* nothing of this batch is in the stream yet but, at most, its plan */
-    if (!st && (st = reserve_output(m)) != 0) /* the plan's copy may be in the stream, out of the pinned buffer the next plan is written to */
-        (void)hydk_batch_wait(m->as, hydamd_get_stream(m->ctx));
+            return hyd_batchrun_fail(r, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
+    int st = hyd_batchrun_busy(r);
     if (st)
         return st;
-    m->in_flight = 1;
+    r->err[0] = 0;
+    r->have_result = 0;
+    r->frames = frames;
+    r->slots = slots;
+    st = plan_batch(m, frames, images); /* nothing of this batch is in the stream yet but, at most, its plan */
+    if (!st && (st = hyd_batchrun_reserve(r)) != 0) /* the plan's copy may be in the stream, out of the pinned buffer the next plan is written to */
+        (void)hydk_batch_wait(r->as, hydamd_get_stream(r->ctx));
+    if (st)
+        return st;
+    r->in_flight = 1;
     st = enqueue(m, images, sample_fmts);
     if (st)
-        drain(m);
+        hyd_batchrun_drain(r);
     return st;
 }
 
@@ -580,117 +508,25 @@ HYDRIUM_EXPORT int hydamd_encode_mixed(HydAmdMixed *m, int frames, const HydAmdI
     return hydamd_encode_mixed_formats(m, frames, images, fmts);
 }
 
-/* per-image outcomes: the context flags non-finite float samples per slot and codes them as 0.0, the assembly gives a
- * flagged image no bytes and a status word; off, a NaN fails the batch as hydamd_sync and the view's header report it */
-HYDRIUM_EXPORT int hydamd_mixed_set_image_errors(HydAmdMixed *m, int per_image) {
-    if (!m)
-        return HYD_API_ERROR;
-    if (m->in_flight)
-        return fail(m, HYD_API_ERROR, "a batch is in flight: hydamd_mixed_result first", NULL);
-    const int st = hydamd_set_bad_sample_per_slot(m->ctx, per_image != 0);
-    if (st)
-        return fail(m, st, "image errors", hydamd_error(m->ctx));
-    hydk_batch_set_image_errors(m->as, per_image != 0);
-    return HYD_OK;
-}
+HYDRIUM_EXPORT int hydamd_mixed_result(HydAmdMixed *m, size_t *total_bytes) { return hyd_batchrun_result(RUN(m), total_bytes); }
 
-/* the batch in flight: wait, let hydamd_sync rerun it if it outgrew a buffer, and see its frames into their files */
-static int settle(HydAmdMixed *m) {
-    const unsigned before = hydamd_overflow_reruns(m->ctx);
-    int st = hydamd_sync(m->ctx);
-    if (st)
-        return fail(m, st, "batch", hydamd_error(m->ctx));
-    m->reruns += hydamd_overflow_reruns(m->ctx) - before;
-    for (int attempt = 0; attempt < 4; attempt++) {
-        uint32_t err = 0;
-        uint64_t total = 0;
-        const uint64_t *offsets = NULL;
-        hydk_batch_result(m->as, &err, &total, &offsets);
-        if (!err) {
-            m->total = (size_t)total;
-            memcpy(m->offsets, offsets, ((size_t)m->frames + 1) * sizeof(uint64_t));
-            for (int f = 0; f < m->frames; f++)
-                m->status[f] = (uint32_t)hydk_batch_status(m->as)[f];
-            return HYD_OK;
-        }
-        if (err & HYDK_ASM_E_NAN)
-            return fail(m, HYD_API_ERROR, "Invalid NaN Float", NULL);
-        if (err & HYDK_ASM_E_SPACE) /* the output was sized from the context's capacities */
-            return fail(m, HYD_INTERNAL_ERROR, "the batch's files are larger than the bound of their output buffer", NULL);
-        if (err & (HYDK_ASM_E_BLOB | HYDK_ASM_E_SLOT | HYDK_ASM_E_HEAD | HYDK_ASM_E_SIZE | HYDK_ASM_E_SCRATCH))
-            return fail(m, HYD_INTERNAL_ERROR, "batch assembly failed on the device", NULL);
-        /* RETRY: the assembly saw the first run's incomplete results (hydamd_sync has rerun the batch since): the view
-         * and the same launches again, with the plan that is still on the device, into an output sized for the enlarged context */
-        if ((st = assemble(m)) != 0)
-            return st;
-        if ((st = hydk_batch_wait(m->as, hydamd_get_stream(m->ctx))) != 0)
-            return fail(m, st, "batch assembly", hydk_batch_error(m->as));
-    }
-    return fail(m, HYD_INTERNAL_ERROR, "a batch is still incomplete after its rerun", NULL);
-}
-
-HYDRIUM_EXPORT int hydamd_mixed_result(HydAmdMixed *m, size_t *total_bytes) {
-    if (!m)
-        return HYD_API_ERROR;
-    if (!m->have_result) {
-        if (!m->in_flight)
-            return fail(m, HYD_API_ERROR, "no batch in flight", NULL);
-        const int st = settle(m);
-        if (st) {
-            drain(m);
-            return st;
-        }
-        m->in_flight = 0;
-        m->have_result = 1;
-    }
-    if (total_bytes)
-        *total_bytes = m->total;
-    return HYD_OK;
-}
-
-HYDRIUM_EXPORT int hydamd_mixed_offsets(HydAmdMixed *m, uint64_t *offsets) {
-    if (!m || !m->have_result)
-        return m ? fail(m, HYD_API_ERROR, "no finished batch: hydamd_mixed_result first", NULL) : HYD_API_ERROR;
-    if (!offsets)
-        return fail(m, HYD_API_ERROR, "null output pointer", NULL);
-    memcpy(offsets, m->offsets, ((size_t)m->frames + 1) * sizeof(uint64_t));
-    return HYD_OK;
-}
+HYDRIUM_EXPORT int hydamd_mixed_offsets(HydAmdMixed *m, uint64_t *offsets) { return hyd_batchrun_offsets(RUN(m), offsets); }
 
 HYDRIUM_EXPORT int hydamd_mixed_read(HydAmdMixed *m, int frame, uint8_t *dst, size_t capacity) {
-    if (!m || !m->have_result)
-        return m ? fail(m, HYD_API_ERROR, "no finished batch: hydamd_mixed_result first", NULL) : HYD_API_ERROR;
-    if (!dst)
-        return fail(m, HYD_API_ERROR, "null output pointer", NULL);
-    if (frame < -1 || frame >= m->frames)
-        return fail(m, HYD_API_ERROR, "no such frame in the batch", NULL);
-    const uint64_t from = frame < 0 ? 0 : m->offsets[frame], to = frame < 0 ? m->total : m->offsets[frame + 1];
-    if (capacity < to - from)
-        return fail(m, HYD_API_ERROR, "output buffer too small", NULL);
-    const int st = hydk_batch_read(m->as, from, dst, (size_t)(to - from));
-    return st ? fail(m, st, "read-back", hydk_batch_error(m->as)) : HYD_OK;
+    return hyd_batchrun_read(RUN(m), frame, dst, capacity);
 }
 
-HYDRIUM_EXPORT const uint8_t *hydamd_mixed_device(HydAmdMixed *m) { return m && m->have_result ? hydk_batch_out(m->as) : NULL; }
+HYDRIUM_EXPORT const uint8_t *hydamd_mixed_device(HydAmdMixed *m) { return hyd_batchrun_device(RUN(m)); }
 
-HYDRIUM_EXPORT const uint64_t *hydamd_mixed_offsets_device(HydAmdMixed *m) {
-    return m && m->have_result ? hydk_batch_offsets_dev(m->as) : NULL;
-}
+HYDRIUM_EXPORT const uint64_t *hydamd_mixed_offsets_device(HydAmdMixed *m) { return hyd_batchrun_offsets_device(RUN(m)); }
 
-HYDRIUM_EXPORT int hydamd_mixed_image_status(HydAmdMixed *m, uint32_t *status) {
-    if (!m || !m->have_result)
-        return m ? fail(m, HYD_API_ERROR, "no finished batch: hydamd_mixed_result first", NULL) : HYD_API_ERROR;
-    if (!status)
-        return fail(m, HYD_API_ERROR, "null output pointer", NULL);
-    memcpy(status, m->status, (size_t)m->frames * sizeof(uint32_t));
-    return HYD_OK;
-}
+HYDRIUM_EXPORT int hydamd_mixed_set_image_errors(HydAmdMixed *m, int per_image) { return hyd_batchrun_set_image_errors(RUN(m), per_image); }
 
-HYDRIUM_EXPORT const uint32_t *hydamd_mixed_image_status_device(HydAmdMixed *m) {
-    return m && m->have_result ? hydk_batch_status_dev(m->as) : NULL;
-}
+HYDRIUM_EXPORT int hydamd_mixed_image_status(HydAmdMixed *m, uint32_t *status) { return hyd_batchrun_image_status(RUN(m), status); }
 
-HYDRIUM_EXPORT unsigned hydamd_mixed_overflow_reruns(HydAmdMixed *m) { return m ? m->reruns : 0; }
+HYDRIUM_EXPORT const uint32_t *hydamd_mixed_image_status_device(HydAmdMixed *m) { return hyd_batchrun_image_status_device(RUN(m)); }
+
+HYDRIUM_EXPORT unsigned hydamd_mixed_overflow_reruns(HydAmdMixed *m) { return m ? m->run.reruns : 0; }
 
 /* ---------------------------------------------------------------------------------------------
  * CPU-only test hook: the mixed plan (build_plan above, the product's own) and the batched layout (hydk_tiles.h compiled

@@ -1,7 +1,17 @@
 #include "planbuf.h"
 
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+int hydk_plan_check_metadata(const HYDImageMetadata *md, char *msg, size_t n) {
+    HYDEncoder *e = hyd_encoder_new();
+    const int st = e ? hyd_set_metadata(e, md) : HYD_NOMEM;
+    if (st && e)
+        snprintf(msg, n, "%s", hyd_error_message_get(e));
+    hyd_encoder_destroy(e);
+    return st;
+}
 
 size_t buf_reserve(Buf *b, size_t n) {
     const size_t at = (b->len + 15) & ~(size_t)15;

@@ -22,6 +22,10 @@ size_t buf_reserve(Buf *b, size_t n);
 /* a bit string (whole bytes + pending bits of a HydBits) as zero-padded words; returns its offset, *bits its length */
 size_t buf_add_bits(Buf *b, const HydBits *src, uint32_t *bits);
 
+/* the bytes a plan is made of are written by an encoder object, which also checks the image's bounds: what it says to
+ * `md` (its message in msg[n] when it refuses) */
+int hydk_plan_check_metadata(const HYDImageMetadata *md, char *msg, size_t n);
+
 /* the planners themselves, for the objects that build plans of their own (batch.c):
  * assembler.c — the plan of one frame (csrc/hip/hydk_assemble.h) from its description as hydamd_assembler_plan takes it;
  * *plan_out is malloc'ed.  The caller has checked the description (every LF group once, at most 255, not 128).

@@ -25,6 +25,7 @@
 #include "planbuf.h"
 #include "../hyd_sample_fmt.h"
 
+#include "../hip/hydk_tile_asm.h"
 #include "../hip/hydk_tiles.h"
 
 #ifndef HYDRIUM_EXPORT
@@ -32,19 +33,6 @@
 #endif
 
 #define TILED_DEFAULT_LAUNCH 32
-
-typedef struct HydkTileAsm HydkTileAsm; /* assemble_tiles.hip */
-int hydk_tiles_create(int device, int max_frames, const void *plan, size_t plan_bytes, HydkTileAsm **out);
-void hydk_tiles_destroy(HydkTileAsm *a);
-const char *hydk_tiles_error(HydkTileAsm *a);
-int hydk_tiles_run(HydkTileAsm *a, uint32_t first_frame, uint32_t frames, const void *blob, const void *extents, int first_group, void *stream);
-int hydk_tiles_result(HydkTileAsm *a, uint32_t *err, uint64_t *file_bytes, uint64_t *needed);
-int hydk_tiles_reserve(HydkTileAsm *a, uint64_t bytes, uint64_t keep, void *stream);
-const uint8_t *hydk_tiles_out(HydkTileAsm *a);
-uint64_t hydk_tiles_out_capacity(HydkTileAsm *a);
-int hydk_tiles_wait(HydkTileAsm *a, void *stream);
-int hydk_tiles_read(HydkTileAsm *a, uint8_t *dst, size_t n);
-uint64_t hydk_tiles_device_free(int device);
 
 /* ---------------------------------------------------------------------------------------------
  * the plan
@@ -255,16 +243,8 @@ HYDRIUM_EXPORT HydAmdTiled *hydamd_tiled_create(int device, const HYDImageMetada
         err = "no usable HIP device";
         goto out;
     }
-    {
-        /* the bytes the plan is made of are written by an encoder object, which also checks the image's bounds */
-        HYDEncoder *e = hyd_encoder_new();
-        st = e ? hyd_set_metadata(e, md) : HYD_NOMEM;
-        if (st && e)
-            snprintf(g_create_error, sizeof(g_create_error), "%s", hyd_error_message_get(e));
-        hyd_encoder_destroy(e);
-        if (st)
-            goto out;
-    }
+    if ((st = hydk_plan_check_metadata(md, g_create_error, sizeof(g_create_error))) != 0)
+        goto out;
     if ((st = build_plan(md, &g, &plan, &plan_len, &err)) != 0)
         goto out;
     t = calloc(1, sizeof(*t));

@@ -888,6 +888,32 @@ class MultiFrame:
         return int(self.d.hydamd_overflow_reruns(self.d.hydamd_multi_context(self.h, shard)))
 
 
+def _read_image(img, row_stride: Optional[int] = None, pixel_stride: Optional[int] = None, sample_fmt: Optional[int] = None):
+    """One image as (ptrs, row_stride, pixel_stride, height, width, sample_fmt), strides in samples: an Nv12 object, an
+    interleaved (H, W, C >= 3) tensor, a triple of (H, W) plane tensors — these say everything themselves — or device
+    addresses: three of them, with the caller's strides and format and no size (height and width None), or
+    (ptrs, row_stride, pixel_stride, width, height) with the caller's format."""
+    if isinstance(img, Nv12):  # V one byte behind U, pixel stride 1, the pitch of both planes
+        return img.pointers(), img.pitch, 1, img.height, img.width, img.sample_fmt
+    if hasattr(img, "data_ptr"):
+        p, isz, shape = img.data_ptr(), img.element_size(), img.shape
+        return [p, p + isz, p + 2 * isz], img.stride(0), img.stride(1), shape[0], shape[1], sample_fmt_of(img)
+    if hasattr(img[0], "data_ptr"):  # planes keep their shape: the size is theirs, never a bare pointer's
+        rs, ps, (h, w) = img[0].stride(0), img[0].stride(1), img[0].shape[:2]
+        if any(tuple(p.shape[:2]) != (h, w) or (p.stride(0), p.stride(1)) != (rs, ps) for p in img):
+            raise ValueError("the three planes of an image share one shape and one layout")
+        return [p.data_ptr() for p in img], rs, ps, h, w, sample_fmt_of(img[0])
+    if hasattr(img[0], "__len__"):
+        ptrs, row_stride, pixel_stride, w, h = img
+        if sample_fmt is None:
+            raise ValueError("device addresses need sample_fmt")
+    else:
+        ptrs, h, w = img, None, None
+        if row_stride is None or pixel_stride is None or sample_fmt is None:
+            raise ValueError("device addresses need row_stride, pixel_stride and sample_fmt")
+    return [int(p) if p is not None else None for p in ptrs], row_stride, pixel_stride, h, w, sample_fmt
+
+
 class TiledImage:
     """A tile-mode image (every tile a frame of its own) from device-resident pixels, frames built on the GPU
     (hydamd_tiled_*, csrc/host/tiled.c): tiles coded in launch groups of up to ``tiles_per_launch`` (0: the default, 32),
@@ -925,21 +951,7 @@ class TiledImage:
         pixel stride C), three (H, W) plane tensors, or three device addresses (then the strides, in samples, and the
         sample format are the caller's), or an Nv12 object.  Asynchronous: the pixels must stay alive and unchanged until
         result()."""
-        if isinstance(img, Nv12):
-            ptrs, row_stride, pixel_stride, sample_fmt = img.pointers(), img.pitch, 1, img.sample_fmt
-        elif hasattr(img, "data_ptr"):
-            isz = img.element_size()
-            ptrs = [img.data_ptr() + c * isz for c in range(3)]
-            row_stride, pixel_stride = img.stride(0), img.stride(1)
-            sample_fmt = sample_fmt_of(img)
-        elif hasattr(img[0], "data_ptr"):
-            ptrs = [p.data_ptr() for p in img]
-            row_stride, pixel_stride = img[0].stride(0), img[0].stride(1)
-            sample_fmt = sample_fmt_of(img[0])
-        else:
-            ptrs = [int(p) if p is not None else None for p in img]
-            if row_stride is None or pixel_stride is None or sample_fmt is None:
-                raise ValueError("device addresses need row_stride, pixel_stride and sample_fmt")
+        ptrs, row_stride, pixel_stride, _, _, sample_fmt = _read_image(img, row_stride, pixel_stride, sample_fmt)
         self._keep = img
         arr = (C.c_void_p * 3)(*ptrs)
         self._ck(self.d.hydamd_encode_image_tiled(self.h, arr, row_stride, pixel_stride, sample_fmt))
@@ -967,10 +979,91 @@ class TiledImage:
         return int(self.d.hydamd_tiled_device_bytes(self.h))
 
 
-class FrameBatch:
+class _DeviceBatch:
+    """What FrameBatch and MixedBatch share — everything but their constructors and encode(): the calls of one protocol
+    (csrc/host/batchrun.c), exported as hydamd_<_prefix>_*."""
+
+    _prefix = ""
+
+    def _c(self, name: str):
+        return getattr(self.d, f"hydamd_{self._prefix}_{name}")
+
+    def close(self):
+        if self.h:
+            self._c("destroy")(self.h)
+            self.h = None
+        self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _ck(self, code: int):
+        if code != 0:
+            raise DeviceError(code, (self._c("error")(self.h) or b"").decode())
+
+    def result(self) -> int:
+        """Waits for the batch; bytes of all its files."""
+        n = C.c_size_t(0)
+        try:
+            self._ck(self._c("result")(self.h, C.byref(n)))
+        finally:
+            self._keep = None
+        return int(n.value)
+
+    def offsets(self) -> np.ndarray:
+        """uint64[frames + 1]: file k is bytes offsets[k] .. offsets[k + 1] of the device buffer."""
+        self.result()
+        out = np.zeros(self.frames + 1, np.uint64)
+        self._ck(self._c("offsets")(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def read(self, k: Optional[int] = None):
+        """File k as a uint8 array; None: the list of all files (one copy from the device)."""
+        off = self.offsets()
+        if k is None:
+            buf = np.empty(max(int(off[-1]), 1), np.uint8)
+            self._ck(self._c("read")(self.h, -1, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
+            return [buf[int(off[i]):int(off[i + 1])] for i in range(self.frames)]
+        if not 0 <= k < self.frames:
+            raise IndexError("no such frame in the batch")
+        buf = np.empty(max(int(off[k + 1] - off[k]), 1), np.uint8)
+        self._ck(self._c("read")(self.h, k, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
+        return buf[: int(off[k + 1] - off[k])]
+
+    def device_ptr(self) -> int:
+        return C.cast(self._c("device")(self.h), C.c_void_p).value or 0
+
+    def offsets_device_ptr(self) -> int:
+        return C.cast(self._c("offsets_device")(self.h), C.c_void_p).value or 0
+
+    def set_image_errors(self, on: bool):
+        """An outcome per image (status()): an image with a non-finite float sample yields no bytes, the others their
+        files; off, such a sample fails the whole batch.  Not while a batch is in flight."""
+        self._ck(self._c("set_image_errors")(self.h, int(bool(on))))
+
+    def status(self) -> np.ndarray:
+        """uint32[frames]: 0 a file, IMAGE_BAD_SAMPLE a non-finite sample and no bytes."""
+        self.result()
+        out = np.zeros(max(self.frames, 1), np.uint32)
+        self._ck(self._c("image_status")(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[: self.frames]
+
+    def status_device_ptr(self) -> int:
+        return C.cast(self._c("image_status_device")(self.h), C.c_void_p).value or 0
+
+    def overflow_reruns(self) -> int:
+        return int(self._c("overflow_reruns")(self.h))
+
+
+class FrameBatch(_DeviceBatch):
     """Batches of up to ``max_frames`` one-frame images of one shape from device-resident pixels, every one a finished
     file built on the GPU (hydamd_batch_*, csrc/host/batch.c): the files back to back in one device buffer, the table of
     their offsets beside it."""
+
+    _prefix = "batch"
 
     def __init__(self, width: int, height: int, max_frames: int, linear_light: int = 0, device: int = 0,
                  icc: Optional[bytes] = None, image_errors: bool = False):
@@ -986,44 +1079,16 @@ class FrameBatch:
         if image_errors:
             self.set_image_errors(True)
 
-    def close(self):
-        if self.h:
-            self.d.hydamd_batch_destroy(self.h)
-            self.h = None
-        self._keep = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _ck(self, code: int):
-        if code != 0:
-            raise DeviceError(code, (self.d.hydamd_batch_error(self.h) or b"").decode())
-
     def encode(self, imgs, row_stride: Optional[int] = None, pixel_stride: Optional[int] = None, sample_fmt: Optional[int] = None):
         """imgs: one entry per frame, all of one layout — interleaved (H, W, C >= 3) torch tensors on the object's device
         (C > 3: the first three channels, pixel stride C), triples of (H, W) plane tensors, or triples of device addresses
         (then the strides, in samples, and the sample format are the caller's).  Asynchronous: the pixels must stay alive
         and unchanged until result()."""
         ptrs = []
-        for img in imgs:
-            if isinstance(img, Nv12):  # (one pitch and one matrix for all)
-                ptrs += img.pointers()
-                layout = (img.pitch, 1, img.sample_fmt)
-            elif hasattr(img, "data_ptr"):
-                isz = img.element_size()
-                ptrs += [img.data_ptr() + c * isz for c in range(3)]
-                layout = (img.stride(0), img.stride(1), sample_fmt_of(img))
-            elif hasattr(img[0], "data_ptr"):
-                ptrs += [p.data_ptr() for p in img]
-                layout = (img[0].stride(0), img[0].stride(1), sample_fmt_of(img[0]))
-            else:
-                if row_stride is None or pixel_stride is None or sample_fmt is None:
-                    raise ValueError("device addresses need row_stride, pixel_stride and sample_fmt")
-                ptrs += [int(p) if p is not None else None for p in img]
-                layout = (row_stride, pixel_stride, sample_fmt)
+        for img in imgs:  # (Nv12: one pitch and one matrix for all)
+            p, rs, ps, _, _, fmt = _read_image(img, row_stride, pixel_stride, sample_fmt)
+            ptrs += p
+            layout = (rs, ps, fmt)
             if (row_stride, pixel_stride, sample_fmt) == (None, None, None):
                 row_stride, pixel_stride, sample_fmt = layout
             elif layout != (row_stride, pixel_stride, sample_fmt):
@@ -1033,59 +1098,6 @@ class FrameBatch:
         self._ck(self.d.hydamd_encode_batch(self.h, len(imgs), arr, row_stride or 0, pixel_stride or 0,
                                             sample_fmt if sample_fmt is not None else -1))
         self.frames = len(imgs)
-
-    def result(self) -> int:
-        """Waits for the batch; bytes of all its files."""
-        n = C.c_size_t(0)
-        try:
-            self._ck(self.d.hydamd_batch_result(self.h, C.byref(n)))
-        finally:
-            self._keep = None
-        return int(n.value)
-
-    def offsets(self) -> np.ndarray:
-        """uint64[frames + 1]: file k is bytes offsets[k] .. offsets[k + 1] of the device buffer."""
-        self.result()
-        out = np.zeros(self.frames + 1, np.uint64)
-        self._ck(self.d.hydamd_batch_offsets(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return out
-
-    def read(self, k: Optional[int] = None):
-        """File k as a uint8 array; None: the list of all files (one copy from the device)."""
-        off = self.offsets()
-        if k is None:
-            buf = np.empty(max(int(off[-1]), 1), np.uint8)
-            self._ck(self.d.hydamd_batch_read(self.h, -1, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
-            return [buf[int(off[i]):int(off[i + 1])] for i in range(self.frames)]
-        if not 0 <= k < self.frames:
-            raise IndexError("no such frame in the batch")
-        buf = np.empty(max(int(off[k + 1] - off[k]), 1), np.uint8)
-        self._ck(self.d.hydamd_batch_read(self.h, k, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
-        return buf[: int(off[k + 1] - off[k])]
-
-    def device_ptr(self) -> int:
-        return C.cast(self.d.hydamd_batch_device(self.h), C.c_void_p).value or 0
-
-    def offsets_device_ptr(self) -> int:
-        return C.cast(self.d.hydamd_batch_offsets_device(self.h), C.c_void_p).value or 0
-
-    def set_image_errors(self, on: bool):
-        """An outcome per image (status()): an image with a non-finite float sample yields no bytes, the others their
-        files; off, such a sample fails the whole batch.  Not while a batch is in flight."""
-        self._ck(self.d.hydamd_batch_set_image_errors(self.h, int(bool(on))))
-
-    def status(self) -> np.ndarray:
-        """uint32[frames]: 0 a file, IMAGE_BAD_SAMPLE a non-finite sample and no bytes."""
-        self.result()
-        out = np.zeros(max(self.frames, 1), np.uint32)
-        self._ck(self.d.hydamd_batch_image_status(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out[: self.frames]
-
-    def status_device_ptr(self) -> int:
-        return C.cast(self.d.hydamd_batch_image_status_device(self.h), C.c_void_p).value or 0
-
-    def overflow_reruns(self) -> int:
-        return int(self.d.hydamd_batch_overflow_reruns(self.h))
 
 
 IMAGE_BAD_SAMPLE = 1  # include/hydrium_amd.h, HYDAMD_IMAGE_BAD_SAMPLE
@@ -1108,25 +1120,7 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
     fmts = []
     for k, img in enumerate(imgs):
         given = sample_fmts[k] if isinstance(sample_fmts, list) else sample_fmt
-        if isinstance(img, Nv12):  # V one byte behind U, pixel stride 1, the pitch of both planes
-            ptrs, rs, ps, h, w, fmt = img.pointers(), img.pitch, 1, img.height, img.width, img.sample_fmt
-        elif hasattr(img, "data_ptr"):
-            isz = img.element_size()
-            ptrs = [img.data_ptr() + c * isz for c in range(3)]
-            rs, ps, (h, w) = img.stride(0), img.stride(1), img.shape[:2]
-            fmt = sample_fmt_of(img)
-        elif hasattr(img[0], "data_ptr"):  # planes keep their shape: the size is theirs, never a bare pointer's
-            ptrs = [p.data_ptr() for p in img]
-            rs, ps, (h, w) = img[0].stride(0), img[0].stride(1), img[0].shape[:2]
-            if any(tuple(p.shape[:2]) != (h, w) or (p.stride(0), p.stride(1)) != (rs, ps) for p in img):
-                raise ValueError("the three planes of an image share one shape and one layout")
-            fmt = sample_fmt_of(img[0])
-        else:
-            ptrs, rs, ps, w, h = img
-            ptrs = [int(p) if p is not None else None for p in ptrs]
-            if given is None:
-                raise ValueError("device addresses need sample_fmt")
-            fmt = given
+        ptrs, rs, ps, h, w, fmt = _read_image(img, sample_fmt=given)
         if sample_fmts is None:
             if sample_fmt is None:
                 sample_fmt = fmt
@@ -1141,7 +1135,7 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
     return descs, fmts
 
 
-class MixedBatch:
+class MixedBatch(_DeviceBatch):
     """Batches of up to ``max_frames`` (0: the default, 32) one-frame images, EACH OF ITS OWN SIZE up to 2048 x 2048, from
     device-resident pixels, every one a finished file built on the GPU (hydamd_mixed_*, csrc/host/mixed.c): the files back
     to back in one device buffer, the table of their offsets beside it.  Conventions as FrameBatch's.
@@ -1149,6 +1143,8 @@ class MixedBatch:
     ``max_lf_groups`` (max_frames..255; None: as above, a slot per image): the LF-group slots of the object's context — an
     image may then hold up to 28 LF groups of 2048 x 2048 pixels, a batch up to max_lf_groups of them in all
     (hydamd_mixed_create_slots)."""
+
+    _prefix = "mixed"
 
     def __init__(self, max_frames: int = 0, linear_light: int = 0, device: int = 0, max_lf_groups: Optional[int] = None,
                  image_errors: bool = False):
@@ -1167,22 +1163,6 @@ class MixedBatch:
         if image_errors:
             self.set_image_errors(True)
 
-    def close(self):
-        if self.h:
-            self.d.hydamd_mixed_destroy(self.h)
-            self.h = None
-        self._keep = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _ck(self, code: int):
-        if code != 0:
-            raise DeviceError(code, (self.d.hydamd_mixed_error(self.h) or b"").decode())
-
     def encode(self, imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
         """imgs: one entry per image, each of its own size and layout — an interleaved (H, W, C >= 3) torch tensor on the
         object's device (any row pitch; C > 3: the first three channels, pixel stride C), a triple of (H, W) plane
@@ -1197,59 +1177,6 @@ class MixedBatch:
         else:
             self._ck(self.d.hydamd_encode_mixed_formats(self.h, len(imgs), descs, (C.c_int * max(len(fmts), 1))(*fmts)))
         self.frames = len(imgs)
-
-    def result(self) -> int:
-        """Waits for the batch; bytes of all its files."""
-        n = C.c_size_t(0)
-        try:
-            self._ck(self.d.hydamd_mixed_result(self.h, C.byref(n)))
-        finally:
-            self._keep = None
-        return int(n.value)
-
-    def offsets(self) -> np.ndarray:
-        """uint64[frames + 1]: file k is bytes offsets[k] .. offsets[k + 1] of the device buffer."""
-        self.result()
-        out = np.zeros(self.frames + 1, np.uint64)
-        self._ck(self.d.hydamd_mixed_offsets(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return out
-
-    def read(self, k: Optional[int] = None):
-        """File k as a uint8 array; None: the list of all files (one copy from the device)."""
-        off = self.offsets()
-        if k is None:
-            buf = np.empty(max(int(off[-1]), 1), np.uint8)
-            self._ck(self.d.hydamd_mixed_read(self.h, -1, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
-            return [buf[int(off[i]):int(off[i + 1])] for i in range(self.frames)]
-        if not 0 <= k < self.frames:
-            raise IndexError("no such frame in the batch")
-        buf = np.empty(max(int(off[k + 1] - off[k]), 1), np.uint8)
-        self._ck(self.d.hydamd_mixed_read(self.h, k, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.nbytes))
-        return buf[: int(off[k + 1] - off[k])]
-
-    def device_ptr(self) -> int:
-        return C.cast(self.d.hydamd_mixed_device(self.h), C.c_void_p).value or 0
-
-    def offsets_device_ptr(self) -> int:
-        return C.cast(self.d.hydamd_mixed_offsets_device(self.h), C.c_void_p).value or 0
-
-    def set_image_errors(self, on: bool):
-        """An outcome per image (status()): an image with a non-finite float sample yields no bytes, the others their
-        files; off, such a sample fails the whole batch.  Not while a batch is in flight."""
-        self._ck(self.d.hydamd_mixed_set_image_errors(self.h, int(bool(on))))
-
-    def status(self) -> np.ndarray:
-        """uint32[frames]: 0 a file, IMAGE_BAD_SAMPLE a non-finite sample and no bytes."""
-        self.result()
-        out = np.zeros(max(self.frames, 1), np.uint32)
-        self._ck(self.d.hydamd_mixed_image_status(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out[: self.frames]
-
-    def status_device_ptr(self) -> int:
-        return C.cast(self.d.hydamd_mixed_image_status_device(self.h), C.c_void_p).value or 0
-
-    def overflow_reruns(self) -> int:
-        return int(self.d.hydamd_mixed_overflow_reruns(self.h))
 
 
 def decode_token_records(rec: np.ndarray):
