@@ -323,13 +323,22 @@ static_assert(HYD_FMT_NV12_BT709 == HYDAMD_NV12_BT709 && HYD_FMT_NV12_BT709_FULL
                   HYDAMD_NV12_BT709 + HYDK_YUV_BT601 == HYDAMD_NV12_BT601 &&
                   HYDAMD_NV12_BT709 + HYDK_YUV_BT601_FULL == HYDAMD_NV12_BT601_FULL,
               "the NV12 formats are 16 + the kernels' matrix index");
+static_assert(HYD_FMT_NV12C_BT709 == HYDAMD_NV12C_BT709 && HYD_FMT_NV12C_BT709_FULL == HYDAMD_NV12C_BT709_FULL &&
+                  HYD_FMT_NV12C_BT601 == HYDAMD_NV12C_BT601 && HYD_FMT_NV12C_BT601_FULL == HYDAMD_NV12C_BT601_FULL &&
+                  HYD_FMT_NV12L_BT709 == HYDAMD_NV12L_BT709 && HYD_FMT_NV12L_BT709_FULL == HYDAMD_NV12L_BT709_FULL &&
+                  HYD_FMT_NV12L_BT601 == HYDAMD_NV12L_BT601 && HYD_FMT_NV12L_BT601_FULL == HYDAMD_NV12L_BT601_FULL &&
+                  HYDAMD_NV12C_BT709 == HYDAMD_NV12_BT709 + 16 * HYDK_CHROMA_CENTRE &&
+                  HYDAMD_NV12L_BT709 == HYDAMD_NV12_BT709 + 16 * HYDK_CHROMA_LEFT && HYD_FMT_NV12_FILTERS == HYDK_CHROMA_FILTERS,
+              "the NV12 family is 16 + the kernels' matrix index + 16 * the kernels' chroma filter");
 
-/* a public sample format's class (what job.fmt holds) and its storage form: the float class's three, NV12 of the 8-bit class */
-int fmt_class(int sample_fmt) { return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : hyd_fmt_is_nv12(sample_fmt) ? HYDK_FMT_U8 : sample_fmt; }
+/* a public sample format's class (what job.fmt holds) and its storage form: the float class's three, NV12 and NV12I (NV12
+ * with interpolated chroma) of the 8-bit class */
+int fmt_class(int sample_fmt) { return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : hyd_fmt_is_nv12_family(sample_fmt) ? HYDK_FMT_U8 : sample_fmt; }
 uint32_t fmt_storage(int sample_fmt) {
     return sample_fmt == HYD_FMT_FLOAT16    ? HYDK_STORE_F16
            : sample_fmt == HYD_FMT_BFLOAT16 ? HYDK_STORE_BF16
            : hyd_fmt_is_nv12(sample_fmt)    ? HYDK_STORE_NV12
+           : hyd_fmt_is_nv12_interp(sample_fmt) ? HYDK_STORE_NV12I
                                             : HYDK_STORE_F32;
 }
 /* the public format a recorded job reads */
@@ -337,6 +346,7 @@ int job_sample_fmt(const HydkLfJob &job) {
     return job.storage == HYDK_STORE_F16    ? HYD_FMT_FLOAT16
            : job.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16
            : job.storage == HYDK_STORE_NV12 ? HYD_FMT_NV12_BT709 + (int)job.matrix
+           : job.storage == HYDK_STORE_NV12I ? HYD_FMT_NV12_BT709 + (int)job.matrix + 16 * (int)job.filter
                                             : job.fmt;
 }
 
@@ -402,9 +412,11 @@ void bind_slot_buffers(HydAmdContext *ctx, int slot) {
 
 int widen_token_records(HydAmdContext *ctx);
 
-/* Record one LF group's job; the kernels run batched over all recorded slots in hydamd_finish_frame. */
+/* Record one LF group's job; the kernels run batched over all recorded slots in hydamd_finish_frame.  pic (formats with
+ * interpolated chroma only): {x0, y0, W, H}, where the LF group sits in its picture and the picture's size — NULL: the LF
+ * group is a picture of its own. */
 int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride,
-                    int sample_fmt, size_t width, size_t height, unsigned preset) {
+                    int sample_fmt, size_t width, size_t height, unsigned preset, const size_t *pic = nullptr) {
     if (width == 0 || height == 0 || width > 2048 || height > 2048)
         return fail(ctx, ST_API_ERROR, "LF group must be between 1 and 2048 pixels in each direction");
     if (!hyd_fmt_is_device(sample_fmt))
@@ -439,7 +451,15 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.pixel_stride = pixel_stride;
     job.fmt = fmt;
     job.storage = fmt_storage(sample_fmt);
-    job.matrix = hyd_fmt_is_nv12(sample_fmt) ? (uint32_t)hyd_fmt_nv12_matrix(sample_fmt) : 0u;
+    job.matrix = hyd_fmt_is_nv12_family(sample_fmt) ? (uint32_t)hyd_fmt_nv12_family_matrix(sample_fmt) : 0u;
+    if (job.storage == HYDK_STORE_NV12I) {
+        /* the picture's chroma plane and where src[1] points in it: all the kernel may read around this LF group */
+        job.filter = (uint32_t)hyd_fmt_nv12_filter(sample_fmt);
+        job.pic_cx0 = pic ? (int32_t)(pic[0] >> 1) : 0;
+        job.pic_cy0 = pic ? (int32_t)(pic[1] >> 1) : 0;
+        job.pic_cw = (int32_t)(((pic ? pic[2] : width) + 1) >> 1);
+        job.pic_ch = (int32_t)(((pic ? pic[3] : height) + 1) >> 1);
+    }
 #ifdef HYD_TEST_HOOKS
     /* HYDAMD_DEBUG_HALF_PER_SAMPLE (bit 0 interleaved, bit 1 planar): half-precision rows that qualify for the dword runs
      * read sample by sample instead — same bytes; what the runs are worth (scripts/half_formats_probe.py) */
@@ -452,7 +472,7 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.gcols = (int)((width + 255) >> 8);
     job.grows = (int)((height + 255) >> 8);
     job.scheme = ctx->scheme;
-    job.use_luts = fmt == HYDK_FMT_F32 ? 0 : ctx->use_luts + (job.storage == HYDK_STORE_NV12 ? HYDK_VARIANT_NV12 : 0);
+    job.use_luts = fmt == HYDK_FMT_F32 ? 0 : ctx->use_luts + (job.storage == HYDK_STORE_NV12 ? HYDK_VARIANT_NV12 : job.storage == HYDK_STORE_NV12I ? HYDK_VARIANT_NV12I : 0);
     job.preset = preset;
     while ((1u << job.preset_bits) < frame_groups) /* hyd_cllog2, encoder.c:940 */
         job.preset_bits++;
@@ -1256,6 +1276,30 @@ int hydamd_encode_lf_group(HydAmdContext *ctx, int slot, const void *const src[3
     return record_lf_group(ctx, slot, src, row_stride, pixel_stride, sample_fmt, width, height, preset);
 }
 
+/* The LF group at (x0, y0) of a PICTURE whose pixel (0, 0) src names: hyd_fmt_origin + hydamd_encode_lf_group for every
+ * format, and for the formats with interpolated chroma the picture travels with the job — the filter reads chroma across
+ * the LF group's edges and clamps at the picture's. */
+int hydamd_encode_lf_group_at(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
+                              ptrdiff_t pixel_stride, int sample_fmt, size_t pic_width, size_t pic_height, size_t x0, size_t y0,
+                              size_t width, size_t height, unsigned preset) {
+    int st = check_slot(ctx, slot);
+    if (st != ST_OK)
+        return st;
+    if (!src || !src[0] || !src[1] || !src[2])
+        return fail(ctx, ST_API_ERROR, "null pixel pointer");
+    if (!hyd_fmt_is_device(sample_fmt))
+        return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
+    if ((x0 | y0) & 255)
+        return fail(ctx, ST_API_ERROR, "an LF group starts at multiples of 256 in its picture");
+    if (pic_width > (size_t)1 << 30 || pic_height > (size_t)1 << 30 || x0 >= pic_width || y0 >= pic_height || width == 0 ||
+        height == 0 || width > pic_width - x0 || height > pic_height - y0)
+        return fail(ctx, ST_API_ERROR, "the LF group's rectangle must lie inside its picture");
+    const void *p[3];
+    hyd_fmt_origin(sample_fmt, src, row_stride, pixel_stride, x0, y0, p);
+    const size_t pic[4] = {x0, y0, pic_width, pic_height};
+    return record_lf_group(ctx, slot, p, row_stride, pixel_stride, sample_fmt, width, height, preset, pic);
+}
+
 int hydamd_encode_lf_group_host(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
                                 ptrdiff_t pixel_stride, int sample_fmt, size_t width, size_t height, unsigned preset) {
     int st = check_slot(ctx, slot);
@@ -1320,12 +1364,10 @@ int hydamd_encode_image(HydAmdContext *ctx, const void *const src[3], ptrdiff_t 
     int st = hydamd_begin_frame(ctx, (unsigned)(lfx * lfy));
     for (size_t ty = 0; ty < lfy && st == ST_OK; ty++)
         for (size_t tx = 0; tx < lfx && st == ST_OK; tx++) {
-            const void *p[3];
-            hyd_fmt_origin(sample_fmt, src, row_stride, pixel_stride, tx * 2048, ty * 2048, p);
             const size_t w = width - tx * 2048 < 2048 ? width - tx * 2048 : 2048;
             const size_t h = height - ty * 2048 < 2048 ? height - ty * 2048 : 2048;
-            st = hydamd_encode_lf_group(ctx, (int)(ty * lfx + tx), p, row_stride, pixel_stride, sample_fmt, w, h,
-                                        (unsigned)(ty * lfx + tx));
+            st = hydamd_encode_lf_group_at(ctx, (int)(ty * lfx + tx), src, row_stride, pixel_stride, sample_fmt, width, height,
+                                           tx * 2048, ty * 2048, w, h, (unsigned)(ty * lfx + tx));
         }
     if (st == ST_OK)
         st = hydamd_finish_frame(ctx, (int)(lfx * lfy));
@@ -1400,12 +1442,10 @@ int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const 
             return fail(ctx, ST_API_ERROR, "null pixel pointer");
         for (size_t ty = 0; ty < lfy && st == ST_OK; ty++)
             for (size_t tx = 0; tx < lfx && st == ST_OK; tx++) {
-                const void *p[3];
-                hyd_fmt_origin(sample_fmt, s3, row_stride, pixel_stride, tx * 2048, ty * 2048, p);
                 const size_t w = width - tx * 2048 < 2048 ? width - tx * 2048 : 2048;
                 const size_t h = height - ty * 2048 < 2048 ? height - ty * 2048 : 2048;
-                st = hydamd_encode_lf_group(ctx, (int)((size_t)f * n + ty * lfx + tx), p, row_stride, pixel_stride, sample_fmt, w, h,
-                                            (unsigned)(ty * lfx + tx));
+                st = hydamd_encode_lf_group_at(ctx, (int)((size_t)f * n + ty * lfx + tx), s3, row_stride, pixel_stride, sample_fmt,
+                                               width, height, tx * 2048, ty * 2048, w, h, (unsigned)(ty * lfx + tx));
             }
     }
     if (st == ST_OK)
@@ -2831,6 +2871,65 @@ __attribute__((visibility("default"))) int hydt_yuv_to_rgb_device(int device, in
     }
     if (e == hipSuccess)
         e = hipMemcpy(rgb, d_out, 3 * n, hipMemcpyDeviceToHost); /* (waits for the kernel) */
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the chroma interpolation (hydk_chroma.h) as the host compiler
+ * built it and as the device runs it.  filter: HYDK_CHROMA_CENTRE or _LEFT; uv: the chroma plane of a width x height picture,
+ * ceil(height / 2) rows of ceil(width / 2) U, V pairs, tightly packed; out receives height rows of width (U', V') pairs. */
+static bool chroma_probe_args(int filter, const uint8_t *uv, uint8_t *out, int width, int height) {
+    return (filter == HYDK_CHROMA_CENTRE || filter == HYDK_CHROMA_LEFT) && uv && out && width >= 1 && height >= 1 &&
+           width <= 4096 && height <= 4096;
+}
+
+__attribute__((visibility("default"))) int hydt_chroma_upsample_host(int filter, const uint8_t *uv, uint8_t *out, int width, int height) {
+    if (!chroma_probe_args(filter, uv, out, width, height))
+        return ST_API_ERROR;
+    const int cw = (width + 1) >> 1, ch = (height + 1) >> 1;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            uint32_t pair[2];
+            hydk_chroma_pair(filter, uv + 2 * (size_t)cw * (y >> 1), uv + 2 * (size_t)cw * hydk_chroma_vy(y, ch), cw, x, pair);
+            out[2 * ((size_t)y * width + x)] = (uint8_t)pair[0];
+            out[2 * ((size_t)y * width + x) + 1] = (uint8_t)pair[1];
+        }
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_chroma_upsample_probe(int filter, const uint8_t *uv, uint8_t *out, int width, int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i >= (size_t)width * height)
+        return;
+    const int cw = (width + 1) >> 1, ch = (height + 1) >> 1, x = (int)(i % (size_t)width), y = (int)(i / (size_t)width);
+    uint32_t pair[2];
+    hydk_chroma_pair(filter, uv + 2 * (size_t)cw * (y >> 1), uv + 2 * (size_t)cw * hydk_chroma_vy(y, ch), cw, x, pair);
+    out[2 * i] = (uint8_t)pair[0];
+    out[2 * i + 1] = (uint8_t)pair[1];
+}
+} /* namespace */
+
+/* one launch over the picture (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_chroma_upsample_device(int device, int filter, const uint8_t *uv, uint8_t *out, int width,
+                                                                       int height) {
+    if (!chroma_probe_args(filter, uv, out, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height, in_bytes = 2 * (size_t)((width + 1) >> 1) * ((height + 1) >> 1);
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_in, in_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&d_out, 2 * n);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_in, uv, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_chroma_upsample_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, filter, d_in, d_out, width,
+                           height);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpy(out, d_out, 2 * n, hipMemcpyDeviceToHost); /* (waits for the kernel) */
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return e == hipSuccess ? ST_OK : ST_API_ERROR;

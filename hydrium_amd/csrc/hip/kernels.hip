@@ -611,10 +611,13 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
-    static_assert(STORE == HYDK_STORE_F32 || (STORE == HYDK_STORE_NV12 ? FMT == HYDK_FMT_U8 : FMT == HYDK_FMT_F32),
-                  "the float class has the half-precision storage forms, the 8-bit class NV12");
+    static_assert(STORE == HYDK_STORE_F32 || (STORE == HYDK_STORE_NV12 || STORE == HYDK_STORE_NV12I ? FMT == HYDK_FMT_U8 : FMT == HYDK_FMT_F32),
+                  "the float class has the half-precision storage forms, the 8-bit class NV12 and NV12I");
     constexpr bool NV12 = STORE == HYDK_STORE_NV12;
-    constexpr bool HALF = STORE != HYDK_STORE_F32 && !NV12;
+    /* NV12I: the NV12 picture with interpolated chroma (hydk_chroma.h) — job.filter says centre- or left-sited, and the job
+     * knows the picture it is cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it */
+    constexpr bool NV12I = STORE == HYDK_STORE_NV12I;
+    constexpr bool HALF = STORE != HYDK_STORE_F32 && !NV12 && !NV12I;
     typedef typename std::conditional<HALF, uint16_t, typename SampleOf<FMT>::type>::type sample_t;
     constexpr bool LUTS = XMODE == kXybGather;
     constexpr int kWords = FMT == HYDK_FMT_U8 ? 6 : 12; /* dwords holding 8 packed RGB pixels */
@@ -627,7 +630,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     const unsigned bid = blockIdx.x >> plog, part = blockIdx.x & ((1u << plog) - 1u);
     const HydkLfJob job = jobs[bid >> 6];
     /* (an NV12 job names its variant as mode + HYDK_VARIANT_NV12: the 8-bit instances' own test turns it away as it stands) */
-    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE) + (NV12 ? HYDK_VARIANT_NV12 : 0)) ||
+    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE) + (NV12 ? HYDK_VARIANT_NV12 : NV12I ? HYDK_VARIANT_NV12I : 0)) ||
         (FMT == HYDK_FMT_F32 && job.storage != (uint32_t)STORE))
         return; /* another template instance of this launch round owns this LF group */
     if ((int)(bid & 63) >= job.gcols * job.grows)
@@ -706,7 +709,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     /* first cluster holding coefficient contexts, by scheme (encoder.c:862-901) */
     const int coef_cl_lo = job.scheme == 0 ? 3 : job.scheme == 3 ? 0 : 1;
 
-    const bool packed = !NV12 && job.pixel_stride == 3 &&
+    const bool packed = !NV12 && !NV12I && job.pixel_stride == 3 &&
                         (const char *)job.src[1] == (const char *)job.src[0] + sizeof(sample_t) &&
                         (const char *)job.src[2] == (const char *)job.src[0] + 2 * sizeof(sample_t) &&
                         (((uintptr_t)job.src[0] | (uintptr_t)(job.row_stride * (long long)sizeof(sample_t))) & 3) == 0 &&
@@ -739,13 +742,47 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     /* NV12: a block row is two dwords of Y and, from chroma row y >> 1, two dwords of U, V pairs (a pair serves two pixels, and
      * the block's first column is even) when both planes and the pitch are dword multiples; anything else reads byte by byte */
     const bool nvrun = NV12 && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)job.row_stride) & 3) == 0;
-    const HydkYuvMatrix yuv = hydk_yuv_matrix(NV12 ? (int)job.matrix : 0);
-    const bool fast = (NV12 ? nvrun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
+    const HydkYuvMatrix yuv = hydk_yuv_matrix(NV12 || NV12I ? (int)job.matrix : 0);
+    /* NV12I: a block row is two dwords of Y, two dwords of U, V pairs from chroma row y >> 1 and two from the other row the
+     * filter mixes in (above for an even y, below for an odd one, clamped to the PICTURE's chroma rows) — the six dwords an
+     * 8-bit row holds — and, as 16-bit loads beside them, the pair behind those four and (centre-sited) the pair before them.
+     * That is taken only where this whole window of pairs lies inside the picture's chroma row and planes and pitch are dword
+     * multiples; the picture's first and last chroma columns, odd widths and shifted bases fill the same window byte by byte
+     * with the clamps, at use (phase A below).  pcx: the picture's chroma column of the block's first pair. */
+    const int pcx = NV12I ? job.pic_cx0 + ((px0 + ab * 8) >> 1) : 0;
+    const bool irun = NV12I && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)job.row_stride) & 3) == 0 &&
+                      (job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1;
+    const bool fast = (NV12 ? nvrun : NV12I ? irun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
     uint32_t nxt[kWords];
+    uint32_t flank[2] = {0u, 0u}; /* NV12I: the window's first pair | its last pair << 16, of the near and of the far chroma row */
 #pragma unroll
     for (int k = 0; k < kWords; k++)
         nxt[k] = 0;
     auto prefetch = [&](int s) {
+        if (NV12I) {
+            if (fast && s * 8 + ar < gh) {
+                const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
+                /* the far row in picture coordinates, clamped there, and back relative to src[1] (may be -1: the LF group above) */
+                const long long fy = (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
+                const char *py = (const char *)job.src[0] + y * job.row_stride + x;
+                const char *pn = (const char *)job.src[1] + (y >> 1) * job.row_stride + x;
+                const char *pf = (const char *)job.src[1] + fy * job.row_stride + x;
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    nxt[k] = HYDK_GLOBAL(const uint32_t, py)[k];
+                    nxt[2 + k] = HYDK_GLOBAL(const uint32_t, pn)[k];
+                    nxt[4 + k] = HYDK_GLOBAL(const uint32_t, pf)[k];
+                }
+                uint32_t bn = 0, bf = 0; /* (left-sited chroma never looks before the window) */
+                if (job.filter == HYDK_CHROMA_CENTRE) {
+                    bn = HYDK_GLOBAL(const uint16_t, pn - 2)[0];
+                    bf = HYDK_GLOBAL(const uint16_t, pf - 2)[0];
+                }
+                flank[0] = bn | (uint32_t)HYDK_GLOBAL(const uint16_t, pn + 8)[0] << 16;
+                flank[1] = bf | (uint32_t)HYDK_GLOBAL(const uint16_t, pf + 8)[0] << 16;
+            }
+            return;
+        }
         if (HALF) {
             if (hfast && s * 8 + ar < gh) {
                 const long long row = (long long)(py0 + s * 8 + ar) * job.row_stride;
@@ -845,7 +882,42 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                     }
                 }
                 prefetch(s + 1);
-            } else if (fast) {
+            } else if (fast || NV12I) {
+                /* NV12I rows that did not come as dwords — the picture's first and last chroma columns, a ragged last block,
+                 * shifted bases, odd pitches — fill the same window byte by byte, here, every pair's column clamped to the
+                 * picture's chroma row and the far row to its chroma rows: the picture's pair (0, 0) lies pic_cy0 rows and
+                 * pic_cx0 pairs before src[1].  Window pair p is the picture's column clamp(pcx - 1 + p, 0, cw - 1), which is
+                 * what cx, and hx with its clamp, come to for every pixel of the block.  The rest is shared with the dword rows. */
+                const int nvalid = row_ok ? min(8, gw - ab * 8) : 0;
+                if (NV12I && !fast) {
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        nxt[k] = 0;
+                    flank[0] = flank[1] = 0;
+                    if (row_ok) {
+                        const uint8_t *py = (const uint8_t *)job.src[0] + (long long)y * job.row_stride + x0;
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            if (i < nvalid)
+                                nxt[i >> 2] |= (uint32_t)py[i] << (8 * (i & 3));
+                        const uint8_t *org = (const uint8_t *)job.src[1] - 2ll * job.pic_cx0;
+                        const uint8_t *rn = org + (long long)(y >> 1) * job.row_stride;
+                        const uint8_t *rf = org + ((long long)hydk_chroma_vy(2 * job.pic_cy0 + y, job.pic_ch) - job.pic_cy0) * job.row_stride;
+#pragma unroll
+                        for (int p = 0; p < 6; p++) {
+                            const int col = min(max(pcx - 1 + p, 0), job.pic_cw - 1);
+                            const uint32_t pn = (uint32_t)rn[2 * col] | (uint32_t)rn[2 * col + 1] << 8;
+                            const uint32_t pf = (uint32_t)rf[2 * col] | (uint32_t)rf[2 * col + 1] << 8;
+                            if (p == 0 || p == 5) {
+                                flank[0] |= pn << (p ? 16 : 0);
+                                flank[1] |= pf << (p ? 16 : 0);
+                            } else {
+                                nxt[2 + ((p - 1) >> 1)] |= pn << (16 * ((p - 1) & 1));
+                                nxt[4 + ((p - 1) >> 1)] |= pf << (16 * ((p - 1) & 1));
+                            }
+                        }
+                    }
+                }
                 /* NV12: the eight pixels of the four fetched dwords, converted and packed as an interleaved RGB row has them */
                 uint32_t cvt[kWords];
                 if (NV12) {
@@ -864,7 +936,36 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                         }
                     }
                 }
-                uint32_t(&w)[kWords] = NV12 ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
+                if (NV12I) {
+                    /* the vertical mix of the window's six pairs (index 0: the pair before the block's four; 5: the one
+                     * behind), then per pixel the horizontal mix with the neighbour its filter names, the conversion, the pack */
+                    uint32_t vu[6], vv[6];
+#pragma unroll
+                    for (int p = 0; p < 6; p++) {
+                        const uint32_t pn = p == 0 ? flank[0] : p == 5 ? flank[0] >> 16 : nxt[2 + ((p - 1) >> 1)] >> (16 * ((p - 1) & 1));
+                        const uint32_t pf = p == 0 ? flank[1] : p == 5 ? flank[1] >> 16 : nxt[4 + ((p - 1) >> 1)] >> (16 * ((p - 1) & 1));
+                        vu[p] = hydk_chroma_vmix(pn & 0xFF, pf & 0xFF);
+                        vv[p] = hydk_chroma_vmix((pn >> 8) & 0xFF, (pf >> 8) & 0xFF);
+                    }
+                    const int filter = (int)job.filter;
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        cvt[k] = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        const int j = 1 + (i >> 1), hc = (i & 1) ? j + 1 : j - 1, hl = j + (i & 1);
+                        const uint32_t u = hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]);
+                        const uint32_t v = hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]);
+                        uint32_t rgb[3];
+                        hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, u, v, rgb);
+#pragma unroll
+                        for (int ch = 0; ch < 3; ch++) {
+                            const int si = i * 3 + ch;
+                            cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
+                        }
+                    }
+                }
+                uint32_t(&w)[kWords] = NV12 || NV12I ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
                 /* which form of the transfer curve this wavefront's 16-bit samples need (wave-uniform) */
                 int curve = kCurveBoth;
                 if (FMT == HYDK_FMT_U16 && !LUTS) {
@@ -978,6 +1079,12 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
                         row_to_xyb(std::integral_constant<int, kCurveNone>());
                     else
                         row_to_xyb(std::integral_constant<int, kCurveBoth>());
+                    if (NV12I) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            if (i >= nvalid)
+                                xv[i] = yv[i] = bv[i] = 0.0f;
+                    }
                 } else {
 #pragma unroll
                     for (int i = 0; i < 8; i++)
@@ -3114,7 +3221,7 @@ namespace hydk {
 
 /* One launch per template instance that owns at least one LF group of this round; an instance
  * returns at once for the LF groups of another sample format.  fmt_mask: bits 0, 1 the integer classes' own samples, bits
- * 2 + HYDK_STORE_* the storage forms: the float class's three, and NV12 of the 8-bit class. */
+ * 2 + HYDK_STORE_* the storage forms: the float class's three, and NV12 and NV12I of the 8-bit class. */
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream) {
     const dim3 grid((num_slots * HYDK_GROUPS_PER_LFG) << plog), block(kThreads);
@@ -3157,6 +3264,18 @@ hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt
             HYDK_LAUNCH_K1_NV12(kXybGather);
 #undef HYDK_LAUNCH_K1_NV12
     }
+    /* NV12 with interpolated chroma: the same three modes, one instance each for both filters (a job field) */
+    if (fmt_mask & (1u << (HYDK_FMT_F32 + HYDK_STORE_NV12I))) {
+#define HYDK_LAUNCH_K1_NV12I(XM) \
+    hipLaunchKernelGGL((k_transform_tokenize<HYDK_FMT_U8, XM, HYDK_STORE_NV12I>), grid, block, 0, stream, d_jobs, status, part_info, plog)
+        if (xyb_arith(xmode) == kXybFastRcp)
+            HYDK_LAUNCH_K1_NV12I(kXybFastRcp);
+        else if (xyb_arith(xmode) == kXybIeeeDiv)
+            HYDK_LAUNCH_K1_NV12I(kXybIeeeDiv);
+        else
+            HYDK_LAUNCH_K1_NV12I(kXybGather);
+#undef HYDK_LAUNCH_K1_NV12I
+    }
 #undef HYDK_LAUNCH_K1_MODES
 #undef HYDK_LAUNCH_K1
     if (plog)
@@ -3180,6 +3299,13 @@ hipError_t transform_footprint(int fmt, int storage, int xmode, int *lds_bytes, 
             fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybIeeeDiv, HYDK_STORE_NV12>;
         else
             fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybGather, HYDK_STORE_NV12>;
+    } else if (fmt == HYDK_FMT_U8 && storage == HYDK_STORE_NV12I) {
+        if (xmode == kXybFastRcp)
+            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybFastRcp, HYDK_STORE_NV12I>;
+        else if (xmode == kXybIeeeDiv)
+            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybIeeeDiv, HYDK_STORE_NV12I>;
+        else
+            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybGather, HYDK_STORE_NV12I>;
     } else if (fmt == HYDK_FMT_U8) {
         if (xmode == kXybFastRcp)
             HYDK_K1_PTR(HYDK_FMT_U8, kXybFastRcp);

@@ -413,11 +413,11 @@ static int enqueue_several(HydBatchRun *r, const HydAmdImageDesc *images, const 
         const size_t lfx = (d->width + 2047) >> 11, lfy = (d->height + 2047) >> 11;
         for (size_t ty = 0; ty < lfy; ty++)
             for (size_t tx = 0; tx < lfx; tx++, slot++) {
-                const void *p[3];
-                hyd_fmt_origin(sample_fmt, d->src, d->row_stride, d->pixel_stride, tx * 2048, ty * 2048, p);
                 const size_t w = d->width - tx * 2048 < 2048 ? d->width - tx * 2048 : 2048;
                 const size_t h = d->height - ty * 2048 < 2048 ? d->height - ty * 2048 : 2048;
-                if ((st = hydamd_encode_lf_group(r->ctx, slot, p, d->row_stride, d->pixel_stride, sample_fmt, w, h, (unsigned)(ty * lfx + tx))) != 0)
+                /* (the image is the picture: interpolated chroma crosses its LF groups and clamps at its edges) */
+                if ((st = hydamd_encode_lf_group_at(r->ctx, slot, d->src, d->row_stride, d->pixel_stride, sample_fmt, d->width, d->height,
+                                                    tx * 2048, ty * 2048, w, h, (unsigned)(ty * lfx + tx))) != 0)
                     return hyd_batchrun_fail(r, st, "image", hydamd_error(r->ctx));
             }
     }

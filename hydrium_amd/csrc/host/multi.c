@@ -155,6 +155,9 @@ HYDRIUM_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *
         return fail(m, HYD_API_ERROR, "bad arguments", NULL);
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
+    /* a shard's buffer is only promised to hold its own rows, and the filter would read a neighbouring shard's chroma row */
+    if (hyd_fmt_is_nv12_interp(sample_fmt))
+        return fail(m, HYD_API_ERROR, HYD_FMT_NV12_SHARDED_MSG, NULL);
     for (int d = 0; d < f->n; d++)
         if (src[3 * d + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * d, pixel_stride))
             return fail(m, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
@@ -173,10 +176,9 @@ HYDRIUM_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *
             return fail(m, st, "begin frame", c);
         for (size_t i = 0; i < f->slots[d]; i++) {
             const size_t g = m->first[d] + i, tx = g % m->lfx, ty = g / m->lfx;
-            const void *p[3];
-            hyd_fmt_origin(sample_fmt, src + 3 * d, row_stride, pixel_stride, tx * 2048, ty * 2048, p);
             const size_t w = W - tx * 2048 < 2048 ? W - tx * 2048 : 2048, h = H - ty * 2048 < 2048 ? H - ty * 2048 : 2048;
-            if ((st = hydamd_encode_lf_group(c, (int)i, p, row_stride, pixel_stride, sample_fmt, w, h, (unsigned)g)) != 0)
+            if ((st = hydamd_encode_lf_group_at(c, (int)i, src + 3 * d, row_stride, pixel_stride, sample_fmt, W, H, tx * 2048, ty * 2048,
+                                                w, h, (unsigned)g)) != 0)
                 return fail(m, st, "LF group", c);
         }
         if ((st = hydamd_run_transform(c, (int)f->slots[d])) != 0)

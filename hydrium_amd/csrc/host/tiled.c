@@ -311,10 +311,10 @@ static int enqueue_group(HydAmdTiled *t) {
         return fail(t, st, "begin launch group", hydamd_error(t->ctx));
     for (size_t i = 0; i < n; i++) {
         const size_t k = t->next + i, tx = k % g->ntx, ty = k / g->ntx;
-        const void *p[3];
-        hyd_fmt_origin(t->fmt, t->src, t->row_stride, t->pixel_stride, tx * g->tw, ty * g->th, p);
         const size_t w = (tx + 1) * g->tw > g->W ? g->W - tx * g->tw : g->tw, h = (ty + 1) * g->th > g->H ? g->H - ty * g->th : g->th;
-        if ((st = hydamd_encode_lf_group(t->ctx, (int)i, p, t->row_stride, t->pixel_stride, t->fmt, w, h, 0)) != 0)
+        /* (tiles are frames, but the whole image is the picture: interpolated chroma is continuous across tiles) */
+        if ((st = hydamd_encode_lf_group_at(t->ctx, (int)i, t->src, t->row_stride, t->pixel_stride, t->fmt, g->W, g->H, tx * g->tw,
+                                            ty * g->th, w, h, 0)) != 0)
             return fail(t, st, "tile", hydamd_error(t->ctx));
     }
     if ((st = hydamd_finish_frame(t->ctx, (int)n)) != 0)

@@ -9,6 +9,11 @@
  * interleaved U, V pairs, under one of four matrices.  NV12 is a storage form of the 8-BIT class: a pixel becomes an
  * ordinary 8-bit RGB pixel right after the load (hip/hydk_yuv.h).  src[0] is the first Y sample, src[1] the first U sample,
  * src[2] == src[1] + 1, the pixel stride is 1 and the row stride is the pitch of both planes in bytes.
+ *
+ * The NV12 family has a second dimension, the chroma filter: sample format = 16 + matrix + 16 * filter.  Filter 0 (16 ... 19)
+ * is nearest neighbour; 1 (32 ... 35) interpolates centre-sited chroma, 2 (48 ... 51) left-sited chroma (hip/hydk_chroma.h).
+ * An interpolating format is NV12 in layout, size and origin; what it adds is that a sub-rectangle's pixels depend on the
+ * PICTURE around it, which hydamd_encode_lf_group_at carries.
  */
 #ifndef HYD_SAMPLE_FMT_H_
 #define HYD_SAMPLE_FMT_H_
@@ -24,13 +29,31 @@
 #define HYD_FMT_NV12_BT709_FULL 17
 #define HYD_FMT_NV12_BT601 18
 #define HYD_FMT_NV12_BT601_FULL 19
+#define HYD_FMT_NV12C_BT709 32 /* centre-sited chroma, interpolated */
+#define HYD_FMT_NV12C_BT709_FULL 33
+#define HYD_FMT_NV12C_BT601 34
+#define HYD_FMT_NV12C_BT601_FULL 35
+#define HYD_FMT_NV12L_BT709 48 /* left-sited chroma, interpolated */
+#define HYD_FMT_NV12L_BT709_FULL 49
+#define HYD_FMT_NV12L_BT601 50
+#define HYD_FMT_NV12L_BT601_FULL 51
+#define HYD_FMT_NV12_FILTERS 3
 
-/* YCbCr 4:2:0 in two planes, and which of the four matrices of hip/hydk_yuv.h (0 ... 3) */
+/* YCbCr 4:2:0 in two planes with nearest-neighbour chroma, and which of the four matrices of hip/hydk_yuv.h (0 ... 3) */
 static inline int hyd_fmt_is_nv12(int fmt) { return fmt >= HYD_FMT_NV12_BT709 && fmt <= HYD_FMT_NV12_BT601_FULL; }
 static inline int hyd_fmt_nv12_matrix(int fmt) { return fmt - HYD_FMT_NV12_BT709; }
+/* the NV12 FAMILY, 16 + matrix + 16 * filter: its layout, size and origin rules; then the filter (0 nearest, 1 centre-sited,
+ * 2 left-sited) and the matrix of one of its twelve numbers */
+static inline int hyd_fmt_is_nv12_family(int fmt) {
+    return fmt >= HYD_FMT_NV12_BT709 && fmt < HYD_FMT_NV12_BT709 + 16 * HYD_FMT_NV12_FILTERS && ((fmt - HYD_FMT_NV12_BT709) & 15) < 4;
+}
+static inline int hyd_fmt_nv12_filter(int fmt) { return (fmt - HYD_FMT_NV12_BT709) >> 4; }
+static inline int hyd_fmt_nv12_family_matrix(int fmt) { return (fmt - HYD_FMT_NV12_BT709) & 3; }
+/* the eight whose chroma is interpolated: a sub-rectangle's pixels depend on the picture around it */
+static inline int hyd_fmt_is_nv12_interp(int fmt) { return hyd_fmt_is_nv12_family(fmt) && hyd_fmt_nv12_filter(fmt) != 0; }
 
 /* what an entry point that reads DEVICE pixels takes */
-static inline int hyd_fmt_is_device(int fmt) { return (fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_BFLOAT16) || hyd_fmt_is_nv12(fmt); }
+static inline int hyd_fmt_is_device(int fmt) { return (fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_BFLOAT16) || hyd_fmt_is_nv12_family(fmt); }
 /* what an entry point that reads HOST pixels takes: the reference's three */
 static inline int hyd_fmt_is_host(int fmt) { return fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_FLOAT32; }
 /* float class: 8-byte token records, 72 histogram bins, the non-finite check */
@@ -43,6 +66,14 @@ static inline size_t hyd_fmt_bytes(int fmt) {
     case HYD_FMT_NV12_BT709_FULL:
     case HYD_FMT_NV12_BT601:
     case HYD_FMT_NV12_BT601_FULL:
+    case HYD_FMT_NV12C_BT709:
+    case HYD_FMT_NV12C_BT709_FULL:
+    case HYD_FMT_NV12C_BT601:
+    case HYD_FMT_NV12C_BT601_FULL:
+    case HYD_FMT_NV12L_BT709:
+    case HYD_FMT_NV12L_BT709_FULL:
+    case HYD_FMT_NV12L_BT601:
+    case HYD_FMT_NV12L_BT601_FULL:
         return 1;
     case HYD_FMT_UINT16:
     case HYD_FMT_FLOAT16:
@@ -55,11 +86,13 @@ static inline size_t hyd_fmt_bytes(int fmt) {
     }
 }
 
-/* NV12's layout: unit pixel stride and V one byte behind U; every other format takes any layout.  An entry point that
+/* NV12's layout (all three filters): unit pixel stride and V one byte behind U; every other format takes any layout.  An entry point that
  * finds 0 here fails with HYD_FMT_NV12_LAYOUT_MSG before it enqueues anything. */
 #define HYD_FMT_NV12_LAYOUT_MSG "NV12 wants pixel_stride 1 and V one byte behind U"
+/* what hydamd_encode_image_multi says to a format with interpolated chroma */
+#define HYD_FMT_NV12_SHARDED_MSG "interpolated chroma is not sharded: a shard does not hold its neighbour's chroma rows"
 static inline int hyd_fmt_layout_ok(int fmt, const void *const src[3], ptrdiff_t pixel_stride) {
-    return !hyd_fmt_is_nv12(fmt) || (pixel_stride == 1 && (const char *)src[2] == (const char *)src[1] + 1);
+    return !hyd_fmt_is_nv12_family(fmt) || (pixel_stride == 1 && (const char *)src[2] == (const char *)src[1] + 1);
 }
 
 /* The three origin pointers of the sub-rectangle at pixel (x0, y0) of a picture of a device format — an LF group, a tile, a
@@ -68,7 +101,7 @@ static inline int hyd_fmt_layout_ok(int fmt, const void *const src[3], ptrdiff_t
  * multiple of 256). */
 static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride, size_t x0,
                                   size_t y0, const void *origin[3]) {
-    if (hyd_fmt_is_nv12(fmt)) {
+    if (hyd_fmt_is_nv12_family(fmt)) {
         const ptrdiff_t chroma = (ptrdiff_t)(y0 / 2) * row_stride + (ptrdiff_t)x0;
         origin[0] = (const char *)src[0] + (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;
         origin[1] = (const char *)src[1] + chroma;

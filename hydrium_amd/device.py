@@ -34,6 +34,13 @@ NV12_BT709_FULL = 17  # BT.709, full range
 NV12_BT601 = 18       # BT.601, limited range: SD video
 NV12_BT601_FULL = 19  # BT.601, full range: what a JPEG decoder leaves (JFIF)
 NV12_FORMATS = (NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL)
+# the same pictures with INTERPOLATED chroma (HYDAMD_NV12C_*, HYDAMD_NV12L_*; csrc/hip/hydk_chroma.h): 16 + matrix + 16 * filter
+NV12C_BT709, NV12C_BT709_FULL, NV12C_BT601, NV12C_BT601_FULL = 32, 33, 34, 35  # centre-sited chroma: JPEG / JFIF, MPEG-1
+NV12L_BT709, NV12L_BT709_FULL, NV12L_BT601, NV12L_BT601_FULL = 48, 49, 50, 51  # left-sited: MPEG-2, H.264, HEVC, AV1 default
+NV12_CENTER_FORMATS = (NV12C_BT709, NV12C_BT709_FULL, NV12C_BT601, NV12C_BT601_FULL)
+NV12_LEFT_FORMATS = (NV12L_BT709, NV12L_BT709_FULL, NV12L_BT601, NV12L_BT601_FULL)
+NV12_FAMILY = NV12_FORMATS + NV12_CENTER_FORMATS + NV12_LEFT_FORMATS
+CHROMA_FILTERS = {"nearest": 0, "centre": 1, "center": 1, "left": 2}
 
 
 class Nv12:
@@ -42,11 +49,21 @@ class Nv12:
 
     ``y``: uint8 tensor (H, W) with unit column stride.  ``uv``: uint8 tensor (ceil(H / 2), ceil(W / 2), 2) with strides
     (pitch, 2, 1), U first; its pitch is the Y plane's (NV12 has one pitch).  ``matrix``: one of NV12_FORMATS.  A crop of a
-    larger surface must start on even coordinates (y[y0:, x0:] with uv[y0 // 2:, x0 // 2:])."""
+    larger surface must start on even coordinates (y[y0:, x0:] with uv[y0 // 2:, x0 // 2:]).
 
-    def __init__(self, y, uv, matrix: int = NV12_BT709):
-        if int(matrix) not in NV12_FORMATS:
-            raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL")
+    ``chroma``: "nearest" (every 2 x 2 block shares its pair), "centre" or "left" — interpolated, for centre- or left-sited
+    chroma, clamped at the edges of THIS picture (a crop's edges replicate).  Or give ``matrix`` as one of the twelve
+    numbers of NV12_FAMILY and leave ``chroma`` out."""
+
+    def __init__(self, y, uv, matrix: int = NV12_BT709, chroma=None):
+        if int(matrix) not in NV12_FAMILY:
+            raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL (or NV12C_*, NV12L_*)")
+        if chroma is not None:
+            if chroma not in CHROMA_FILTERS:
+                raise ValueError("chroma is 'nearest', 'centre' or 'left'")
+            if int(matrix) not in NV12_FORMATS and (int(matrix) - 16) >> 4 != CHROMA_FILTERS[chroma]:
+                raise ValueError("matrix names another chroma filter than chroma does")
+            matrix = 16 + (int(matrix) & 3) + 16 * CHROMA_FILTERS[chroma]
         if y.element_size() != 1 or uv.element_size() != 1 or y.dim() != 2 or uv.dim() != 3:
             raise ValueError("NV12 planes are 8-bit: y (H, W), uv (ceil(H / 2), ceil(W / 2), 2)")
         h, w = y.shape
@@ -61,12 +78,12 @@ class Nv12:
         self.pitch = int(y.stride(0) if h > 1 else uv.stride(0) if uv.shape[0] > 1 else max(y.stride(0), uv.stride(0)))
 
     @classmethod
-    def from_surface(cls, buf, width: int, height: int, pitch: int, chroma_offset: int, matrix: int = NV12_BT709):
+    def from_surface(cls, buf, width: int, height: int, pitch: int, chroma_offset: int, matrix: int = NV12_BT709, chroma=None):
         """A decoder's single allocation: ``buf`` a 1-D uint8 tensor, Y rows at 0, pitch, 2 * pitch ..., chroma rows at
         chroma_offset, chroma_offset + pitch ... (bytes)."""
         y = buf.as_strided((height, width), (pitch, 1), 0)
         uv = buf.as_strided((-(-height // 2), -(-width // 2), 2), (pitch, 2, 1), chroma_offset)
-        return cls(y, uv, matrix)
+        return cls(y, uv, matrix, chroma)
 
     @property
     def shape(self):
@@ -142,6 +159,7 @@ def dll(path: Optional[str] = None):
         lf_args = [vp, i, C.POINTER(vp), C.c_ssize_t, C.c_ssize_t, i, sz, sz, u]
         d.hydamd_encode_lf_group.argtypes = lf_args
         d.hydamd_encode_lf_group_host.argtypes = lf_args
+        d.hydamd_encode_lf_group_at.argtypes = [vp, i, C.POINTER(vp), C.c_ssize_t, C.c_ssize_t, i, sz, sz, sz, sz, sz, sz, u]
         d.hydamd_encode_image.argtypes = [vp, C.POINTER(vp), C.c_ssize_t, C.c_ssize_t, i, sz, sz]
         d.hydamd_debug_shader_clock_mhz.argtypes = [vp, C.POINTER(C.c_double)]
         d.hydamd_encode_image_batch.argtypes = [vp, i, C.POINTER(vp), C.c_ssize_t, C.c_ssize_t, i, sz, sz]
@@ -385,6 +403,14 @@ class DeviceContext:
         arr = (C.c_void_p * 3)(*ptrs)
         fn = self.d.hydamd_encode_lf_group_host if host else self.d.hydamd_encode_lf_group
         self._ck(fn(self.h, slot, arr, row_stride, pixel_stride, fmt, width, height, preset))
+
+    def encode_lf_group_at(self, slot: int, ptrs: Sequence[int], row_stride: int, pixel_stride: int, fmt: int, pic_width: int,
+                           pic_height: int, x0: int, y0: int, width: int, height: int, preset: int):
+        """The LF group at (x0, y0) of a picture whose first pixel ``ptrs`` name (hydamd_encode_lf_group_at): interpolated
+        chroma reads across the LF group's edges and clamps at the picture's."""
+        arr = (C.c_void_p * 3)(*ptrs)
+        self._ck(self.d.hydamd_encode_lf_group_at(self.h, slot, arr, row_stride, pixel_stride, fmt, pic_width, pic_height, x0, y0,
+                                                  width, height, preset))
 
     def finish_frame(self, num_slots: int):
         self._ck(self.d.hydamd_finish_frame(self.h, num_slots))
@@ -663,7 +689,7 @@ class DeviceContext:
 
     def transform_footprint(self, sample_fmt: int):
         """(static LDS bytes, registers per thread) of the transform kernel instance serving `sample_fmt` (0 u8, 1 u16, 2 f32, 3 f16, 4 bf16,
-        16 ... 19 NV12)."""
+        16 ... 19 NV12, 32 ... 35 and 48 ... 51 NV12 with interpolated chroma)."""
         lds, regs = C.c_int(0), C.c_int(0)
         self._ck(self.d.hydamd_debug_transform_footprint(self.h, int(sample_fmt), C.byref(lds), C.byref(regs)))
         return lds.value, regs.value
@@ -1127,7 +1153,7 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
             elif fmt != sample_fmt:
                 raise ValueError("the images of a batch share one sample format")
         elif isinstance(sample_fmts, list) and fmt != given:
-            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FORMATS:
+            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FAMILY:
                 raise ValueError("sample_fmts disagrees with a tensor's dtype")
             fmt = given  # not a format at all: the library refuses it (HYD_API_ERROR), nothing is enqueued
         fmts.append(fmt)

@@ -129,7 +129,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * hydamd_encode_image_batch, hydamd_encode_batch, hydamd_encode_mixed, hydamd_encode_mixed_formats,
  * hydamd_encode_image_tiled, hydamd_encode_image_multi and hydamd_debug_transform_footprint.  Entry points that read HOST
  * pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse both with "Invalid Sample Format", as they and every
- * other entry point refuse anything that is neither 0..4 nor an NV12 format (16..19, below).
+ * other entry point refuse anything that is neither 0..4 nor of the NV12 family (16..19, 32..35, 48..51, below).
  */
 #define HYDAMD_FLOAT16 3
 #define HYDAMD_BFLOAT16 4
@@ -142,7 +142,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  *   HYDAMD_NV12_BT709_FULL  BT.709 matrix, full range
  *   HYDAMD_NV12_BT601       BT.601 matrix, limited range: SD video
  *   HYDAMD_NV12_BT601_FULL  BT.601 matrix, full range: what a JPEG decoder leaves (JFIF)
- * (the numbers start at 16: 5..15 and everything from 20 up stay "Invalid Sample Format").
+ * (the numbers start at 16: 5..15, 20..31, 36..47 and everything from 52 up stay "Invalid Sample Format"; 32..35 and 48..51
+ * are the same pictures with interpolated chroma, further down).
  *
  * The file is byte for byte what the reference writes for the HYD_UINT8 picture this conversion produces.  For pixel (x, y):
  * Y = luma[y][x]; U, V = the chroma pair at (x >> 1, y >> 1) (nearest neighbour: every 2 x 2 block shares one pair);
@@ -172,7 +173,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Entry points that read HOST pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse all four with "Invalid
  * Sample Format".
  * Out of scope: NV21, planar I420, 4:2:2 and 4:4:4; 10- and 16-bit P010 / P016 (they need a fixed-point derivation of their
- * own); bilinear or siting-aware chroma upsampling; host-pointer NV12; any colour description other than the four above.
+ * own); host-pointer NV12; any colour description other than the four above.
  */
 #define HYDAMD_NV12_BT709 16
 #define HYDAMD_NV12_BT709_FULL 17
@@ -180,15 +181,64 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
 #define HYDAMD_NV12_BT601_FULL 19
 
 /*
+ * NV12 with INTERPOLATED chroma: sample_fmt = 16 + matrix + 16 * filter.  Filter 0 is the nearest-neighbour family above;
+ *   HYDAMD_NV12C_* (32..35)  centre-sited: the chroma sample sits in the middle of its 2 x 2 luma block (JPEG / JFIF, MPEG-1)
+ *   HYDAMD_NV12L_* (48..51)  left-sited: co-sited with even luma columns, midway between two luma rows (MPEG-2, and
+ *                            chroma_sample_loc_type 0: the default of H.264, HEVC and most AV1)
+ * with the four matrices in the same order.  Layout, strides, odd sizes, negative pitch and the layout error are NV12's.
+ *
+ * The file is byte for byte what the reference writes for the HYD_UINT8 picture this produces.  The PICTURE is W x H with a
+ * chroma plane of cw = ceil(W / 2) by ch = ceil(H / 2) pairs.  For pixel (x, y) in picture coordinates: cx = x >> 1,
+ * cy = y >> 1, vy = clamp(cy + (y odd ? 1 : -1), 0, ch - 1), and for U and V separately, C the component's plane:
+ *   centre, hx = clamp(cx + (x odd ? 1 : -1), 0, cw - 1):
+ *       C' = (9*C[cy][cx] + 3*C[cy][hx] + 3*C[vy][cx] + C[vy][hx] + 8) >> 4
+ *   left, x even:  C' = (3*C[cy][cx] + C[vy][cx] + 2) >> 2
+ *   left, x odd, hx = min(cx + 1, cw - 1):
+ *       C' = (3*(C[cy][cx] + C[cy][hx]) + C[vy][cx] + C[vy][hx] + 4) >> 3
+ * then R, G, B from Y[y][x], U', V' exactly as above.
+ *
+ * Clamping is at the edges of the PICTURE, not of an LF group or tile: inside a picture an LF group or tile reads its
+ * neighbours' chroma, and nothing is ever read outside the picture's chroma rows 0 ... ch - 1, bytes 0 ... 2 * cw - 1, or its
+ * Y rectangle.  A picture is what the caller names: the image of hydamd_encode_image, hydamd_encode_image_batch and
+ * hydamd_encode_batch; each HydAmdImageDesc of hydamd_encode_mixed* (a crop of a larger surface is a picture: its edges
+ * replicate although real neighbours exist in memory); the whole image of hydamd_encode_image_tiled (tiles are frames, the
+ * chroma is continuous across them).  hydamd_encode_lf_group_at names the picture of one LF group; plain
+ * hydamd_encode_lf_group treats the LF group as a picture of its own.
+ *
+ * Refused: hydamd_encode_image_multi ("interpolated chroma is not sharded: ..." — a shard's buffer is only promised to hold
+ * its own rows, and the filter would read a neighbouring shard's chroma row), and the host-pointer entry points as for NV12.
+ * Out of scope: top-left siting (BT.2020), other layouts (NV21, I420, 4:2:2, 4:4:4), 10-bit, cross-shard chroma,
+ * host-pointer input.
+ */
+#define HYDAMD_NV12C_BT709 32
+#define HYDAMD_NV12C_BT709_FULL 33
+#define HYDAMD_NV12C_BT601 34
+#define HYDAMD_NV12C_BT601_FULL 35
+#define HYDAMD_NV12L_BT709 48
+#define HYDAMD_NV12L_BT709_FULL 49
+#define HYDAMD_NV12L_BT601 50
+#define HYDAMD_NV12L_BT601_FULL 51
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
  * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_* formats (whose src and strides are described above).
+ * With HYDAMD_NV12C_* or HYDAMD_NV12L_* the LF group is a picture of its own: its chroma clamps at its own edges.
  */
 HYDAMD_EXPORT int hydamd_encode_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
                                          ptrdiff_t pixel_stride, int sample_fmt, size_t width, size_t height,
                                          unsigned preset);
+
+/* The same for the width x height LF group at pixel (x0, y0) of a pic_width x pic_height PICTURE whose first pixel src
+ * names (for NV12: its first Y and U samples).  For every format this finds the LF group's origin as the library does and
+ * is hydamd_encode_lf_group from there; for HYDAMD_NV12C_* and HYDAMD_NV12L_* it also records the picture, whose chroma the
+ * filter reads across the LF group's edges and at whose edges it clamps.  HYD_API_ERROR: x0 or y0 no multiple of 256, or a
+ * rectangle that does not lie inside the picture. */
+HYDAMD_EXPORT int hydamd_encode_lf_group_at(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
+                                            ptrdiff_t pixel_stride, int sample_fmt, size_t pic_width, size_t pic_height,
+                                            size_t x0, size_t y0, size_t width, size_t height, unsigned preset);
 
 /* A whole device-resident image in ONE call: hydamd_begin_frame, hydamd_encode_lf_group for every LF group in raster
  * order (slot = raster index = preset: the one-frame layout of the reference for tiles sent in raster order,
