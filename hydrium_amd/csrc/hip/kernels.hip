@@ -709,6 +709,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     /* first cluster holding coefficient contexts, by scheme (encoder.c:862-901) */
     const int coef_cl_lo = job.scheme == 0 ? 3 : job.scheme == 3 ? 0 : 1;
 
+    /* (which loader a layout gets, from here to hfast, is restated by loader() in tests/pixel_layouts.py: change them together) */
     const bool packed = !NV12 && !NV12I && job.pixel_stride == 3 &&
                         (const char *)job.src[1] == (const char *)job.src[0] + sizeof(sample_t) &&
                         (const char *)job.src[2] == (const char *)job.src[0] + 2 * sizeof(sample_t) &&

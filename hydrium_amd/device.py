@@ -501,6 +501,11 @@ class DeviceContext:
         self.finish_frame(n)
         return n
 
+    def encode_image(self, ptrs: Sequence[int], row_stride: int, pixel_stride: int, fmt: int, width: int, height: int):
+        """Enqueue a whole device-resident frame from three bare addresses and strides in samples (hydamd_encode_image):
+        every LF group in raster order, slot = raster index = preset."""
+        self._ck(self.d.hydamd_encode_image(self.h, (C.c_void_p * 3)(*ptrs), row_stride, pixel_stride, fmt, width, height))
+
     def encode_image_batch(self, imgs):
         """Enqueue a batch of interleaved (H, W, 3) torch CUDA tensors of one shape as one launch group
         (hydamd_encode_image_batch): frame k in slots k * n ... (k + 1) * n - 1.  Or of Nv12 objects of one shape, pitch
