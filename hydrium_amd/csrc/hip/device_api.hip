@@ -330,15 +330,32 @@ static_assert(HYD_FMT_NV12C_BT709 == HYDAMD_NV12C_BT709 && HYD_FMT_NV12C_BT709_F
                   HYDAMD_NV12C_BT709 == HYDAMD_NV12_BT709 + 16 * HYDK_CHROMA_CENTRE &&
                   HYDAMD_NV12L_BT709 == HYDAMD_NV12_BT709 + 16 * HYDK_CHROMA_LEFT && HYD_FMT_NV12_FILTERS == HYDK_CHROMA_FILTERS,
               "the NV12 family is 16 + the kernels' matrix index + 16 * the kernels' chroma filter");
+#define HYDAMD_P016_ROW(P, D)                                                                                                   \
+    (HYD_FMT_##P##_BT709 == HYDAMD_##P##_BT709 && HYD_FMT_##P##_BT709_FULL == HYDAMD_##P##_BT709_FULL &&                         \
+     HYD_FMT_##P##_BT601 == HYDAMD_##P##_BT601 && HYD_FMT_##P##_BT601_FULL == HYDAMD_##P##_BT601_FULL &&                         \
+     HYD_FMT_##P##C_BT709 == HYDAMD_##P##C_BT709 && HYD_FMT_##P##C_BT709_FULL == HYDAMD_##P##C_BT709_FULL &&                     \
+     HYD_FMT_##P##C_BT601 == HYDAMD_##P##C_BT601 && HYD_FMT_##P##C_BT601_FULL == HYDAMD_##P##C_BT601_FULL &&                     \
+     HYD_FMT_##P##L_BT709 == HYDAMD_##P##L_BT709 && HYD_FMT_##P##L_BT709_FULL == HYDAMD_##P##L_BT709_FULL &&                     \
+     HYD_FMT_##P##L_BT601 == HYDAMD_##P##L_BT601 && HYD_FMT_##P##L_BT601_FULL == HYDAMD_##P##L_BT601_FULL &&                     \
+     HYDAMD_##P##_BT709 == HYDAMD_NV12_BT709 + 64 * (D) && HYDAMD_##P##C_BT709 == HYDAMD_##P##_BT709 + 16 * HYDK_CHROMA_CENTRE && \
+     HYDAMD_##P##L_BT709 == HYDAMD_##P##_BT709 + 16 * HYDK_CHROMA_LEFT)
+static_assert(HYDAMD_P016_ROW(P010, HYDK_YUV16_P010) && HYDAMD_P016_ROW(P012, HYDK_YUV16_P012) && HYDAMD_P016_ROW(P016, HYDK_YUV16_P016) &&
+                  HYD_FMT_P016_DEPTHS == HYDK_YUV16_DEPTHS,
+              "the P016 family is 16 + the kernels' matrix index + 16 * the kernels' chroma filter + 64 * the kernels' depth");
+#undef HYDAMD_P016_ROW
 
 /* a public sample format's class (what job.fmt holds) and its storage form: the float class's three, NV12 and NV12I (NV12
- * with interpolated chroma) of the 8-bit class */
-int fmt_class(int sample_fmt) { return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : hyd_fmt_is_nv12_family(sample_fmt) ? HYDK_FMT_U8 : sample_fmt; }
+ * with interpolated chroma) of the 8-bit class, P016 and P016I (P010 / P012 / P016, the same in 16-bit words) of the 16-bit class */
+int fmt_class(int sample_fmt) {
+    return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : hyd_fmt_is_nv12_family(sample_fmt) ? HYDK_FMT_U8 : hyd_fmt_is_p016_family(sample_fmt) ? HYDK_FMT_U16 : sample_fmt;
+}
 uint32_t fmt_storage(int sample_fmt) {
     return sample_fmt == HYD_FMT_FLOAT16    ? HYDK_STORE_F16
            : sample_fmt == HYD_FMT_BFLOAT16 ? HYDK_STORE_BF16
            : hyd_fmt_is_nv12(sample_fmt)    ? HYDK_STORE_NV12
            : hyd_fmt_is_nv12_interp(sample_fmt) ? HYDK_STORE_NV12I
+           : hyd_fmt_is_p016_interp(sample_fmt) ? HYDK_STORE_P016I
+           : hyd_fmt_is_p016_family(sample_fmt) ? HYDK_STORE_P016
                                             : HYDK_STORE_F32;
 }
 /* the public format a recorded job reads */
@@ -347,6 +364,8 @@ int job_sample_fmt(const HydkLfJob &job) {
            : job.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16
            : job.storage == HYDK_STORE_NV12 ? HYD_FMT_NV12_BT709 + (int)job.matrix
            : job.storage == HYDK_STORE_NV12I ? HYD_FMT_NV12_BT709 + (int)job.matrix + 16 * (int)job.filter
+           : job.storage == HYDK_STORE_P016 || job.storage == HYDK_STORE_P016I
+               ? HYD_FMT_NV12_BT709 + (int)(job.matrix & 3u) + 16 * (int)job.filter + 64 * (int)(job.matrix >> 2)
                                             : job.fmt;
 }
 
@@ -422,7 +441,7 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
-        return fail(ctx, ST_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG);
+        return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
     /* half precision is a storage form of the float class: the job is a float job, and every `fmt == HYDK_FMT_F32` below
      * and in the kernels keeps meaning "float class".  NV12 is a storage form of the 8-bit class: 4-byte token records, the
      * 8-bit transfer table, and whatever form of the entropy stage is selected */
@@ -451,10 +470,12 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.pixel_stride = pixel_stride;
     job.fmt = fmt;
     job.storage = fmt_storage(sample_fmt);
-    job.matrix = hyd_fmt_is_nv12_family(sample_fmt) ? (uint32_t)hyd_fmt_nv12_family_matrix(sample_fmt) : 0u;
-    if (job.storage == HYDK_STORE_NV12I) {
+    job.matrix = hyd_fmt_is_nv12_family(sample_fmt) ? (uint32_t)hyd_fmt_nv12_family_matrix(sample_fmt)
+                 : hyd_fmt_is_p016_family(sample_fmt) ? (uint32_t)(hyd_fmt_p016_matrix(sample_fmt) + 4 * hyd_fmt_p016_depth(sample_fmt))
+                                                      : 0u;
+    if (job.storage == HYDK_STORE_NV12I || job.storage == HYDK_STORE_P016I) {
         /* the picture's chroma plane and where src[1] points in it: all the kernel may read around this LF group */
-        job.filter = (uint32_t)hyd_fmt_nv12_filter(sample_fmt);
+        job.filter = (uint32_t)(job.storage == HYDK_STORE_NV12I ? hyd_fmt_nv12_filter(sample_fmt) : hyd_fmt_p016_filter(sample_fmt));
         job.pic_cx0 = pic ? (int32_t)(pic[0] >> 1) : 0;
         job.pic_cy0 = pic ? (int32_t)(pic[1] >> 1) : 0;
         job.pic_cw = (int32_t)(((pic ? pic[2] : width) + 1) >> 1);
@@ -472,7 +493,12 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.gcols = (int)((width + 255) >> 8);
     job.grows = (int)((height + 255) >> 8);
     job.scheme = ctx->scheme;
-    job.use_luts = fmt == HYDK_FMT_F32 ? 0 : ctx->use_luts + (job.storage == HYDK_STORE_NV12 ? HYDK_VARIANT_NV12 : job.storage == HYDK_STORE_NV12I ? HYDK_VARIANT_NV12I : 0);
+    job.use_luts = fmt == HYDK_FMT_F32 ? 0
+                   : ctx->use_luts + (job.storage == HYDK_STORE_NV12    ? HYDK_VARIANT_NV12
+                                      : job.storage == HYDK_STORE_NV12I ? HYDK_VARIANT_NV12I
+                                      : job.storage == HYDK_STORE_P016  ? HYDK_VARIANT_P016
+                                      : job.storage == HYDK_STORE_P016I ? HYDK_VARIANT_P016I
+                                                                        : 0);
     job.preset = preset;
     while ((1u << job.preset_bits) < frame_groups) /* hyd_cllog2, encoder.c:940 */
         job.preset_bits++;
@@ -1360,7 +1386,7 @@ int hydamd_encode_image(HydAmdContext *ctx, const void *const src[3], ptrdiff_t 
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
-        return fail(ctx, ST_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG);
+        return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
     int st = hydamd_begin_frame(ctx, (unsigned)(lfx * lfy));
     for (size_t ty = 0; ty < lfy && st == ST_OK; ty++)
         for (size_t tx = 0; tx < lfx && st == ST_OK; tx++) {
@@ -1433,7 +1459,7 @@ int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const 
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     for (int f = 0; f < frames; f++)
         if (src[3 * (size_t)f + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * (size_t)f, pixel_stride))
-            return fail(ctx, ST_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG);
+            return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
     const size_t lfx = (width + 2047) >> 11, lfy = (height + 2047) >> 11, n = lfx * lfy;
     int st = hydamd_begin_batch(ctx, (unsigned)n, frames);
     for (int f = 0; f < frames && st == ST_OK; f++) {
@@ -2933,6 +2959,104 @@ __attribute__((visibility("default"))) int hydt_chroma_upsample_device(int devic
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return e == hipSuccess ? ST_OK : ST_API_ERROR;
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the 16-bit conversion and taps (hydk_yuv16.h) as the host compiler
+ * built them and as the device runs them; the four above in 16-bit words.  depth: HYDK_YUV16_P010 ... _P016 (1 ... 3). */
+static bool yuv16_probe_args(int depth, int matrix, const uint16_t *yuv, uint16_t *rgb) {
+    return depth >= HYDK_YUV16_P010 && depth <= HYDK_YUV16_P016 && matrix >= 0 && matrix < HYDK_YUV_MATRICES && yuv && rgb;
+}
+
+__attribute__((visibility("default"))) int hydt_yuv16_to_rgb_host(int depth, int matrix, const uint16_t *yuv, uint16_t *rgb, size_t n) {
+    if (!yuv16_probe_args(depth, matrix, yuv, rgb))
+        return ST_API_ERROR;
+    const HydkYuvMatrix m = hydk_yuv16_matrix(depth, matrix);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t out[3];
+        hydk_yuv16_to_rgb(m, yuv[3 * i], yuv[3 * i + 1], yuv[3 * i + 2], out);
+        for (int c = 0; c < 3; c++)
+            rgb[3 * i + c] = (uint16_t)out[c];
+    }
+    return ST_OK;
+}
+
+__attribute__((visibility("default"))) int hydt_chroma16_upsample_host(int filter, const uint16_t *uv, uint16_t *out, int width, int height) {
+    if (!chroma_probe_args(filter, (const uint8_t *)uv, (uint8_t *)out, width, height))
+        return ST_API_ERROR;
+    const int cw = (width + 1) >> 1, ch = (height + 1) >> 1;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            uint32_t pair[2];
+            hydk_chroma16_pair(filter, uv + 2 * (size_t)cw * (y >> 1), uv + 2 * (size_t)cw * hydk_chroma_vy(y, ch), cw, x, pair);
+            out[2 * ((size_t)y * width + x)] = (uint16_t)pair[0];
+            out[2 * ((size_t)y * width + x) + 1] = (uint16_t)pair[1];
+        }
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_yuv16_to_rgb_probe(int depth, int matrix, const uint16_t *yuv, uint16_t *rgb, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per triple */
+    if (i >= n)
+        return;
+    uint32_t out[3];
+    hydk_yuv16_to_rgb(hydk_yuv16_matrix(depth, matrix), yuv[3 * i], yuv[3 * i + 1], yuv[3 * i + 2], out);
+    for (int c = 0; c < 3; c++)
+        rgb[3 * i + c] = (uint16_t)out[c];
+}
+
+__global__ __launch_bounds__(256) void k_chroma16_upsample_probe(int filter, const uint16_t *uv, uint16_t *out, int width, int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i >= (size_t)width * height)
+        return;
+    const int cw = (width + 1) >> 1, ch = (height + 1) >> 1, x = (int)(i % (size_t)width), y = (int)(i / (size_t)width);
+    uint32_t pair[2];
+    hydk_chroma16_pair(filter, uv + 2 * (size_t)cw * (y >> 1), uv + 2 * (size_t)cw * hydk_chroma_vy(y, ch), cw, x, pair);
+    out[2 * i] = (uint16_t)pair[0];
+    out[2 * i + 1] = (uint16_t)pair[1];
+}
+
+/* in_words uint16 up, one launch (the conversion over n triples when depth != 0, else the taps over a width x height
+ * picture), out_words uint16 back; HYD_OK, or HYD_API_ERROR with nothing written */
+int probe16_round_trip(const uint16_t *in, size_t in_words, uint16_t *out, size_t out_words, int depth, int matrix_or_filter, size_t n,
+                       int width, int height) {
+    uint16_t *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_in, 2 * in_words);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&d_out, 2 * out_words);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_in, in, 2 * in_words, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        if (depth)
+            hipLaunchKernelGGL(k_yuv16_to_rgb_probe, grid, block, 0, nullptr, depth, matrix_or_filter, d_in, d_out, n);
+        else
+            hipLaunchKernelGGL(k_chroma16_upsample_probe, grid, block, 0, nullptr, matrix_or_filter, d_in, d_out, width, height);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpy(out, d_out, 2 * out_words, hipMemcpyDeviceToHost); /* (waits for the kernel) */
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+}
+} /* namespace */
+
+/* one launch over n triples (host arrays, n < 2^31) on `device` */
+__attribute__((visibility("default"))) int hydt_yuv16_to_rgb_device(int device, int depth, int matrix, const uint16_t *yuv, uint16_t *rgb,
+                                                                    size_t n) {
+    if (!yuv16_probe_args(depth, matrix, yuv, rgb) || n == 0 || n >= ((size_t)1 << 31) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    return probe16_round_trip(yuv, 3 * n, rgb, 3 * n, depth, matrix, n, 0, 0);
+}
+
+/* one launch over the picture (host arrays) on `device` */
+__attribute__((visibility("default"))) int hydt_chroma16_upsample_device(int device, int filter, const uint16_t *uv, uint16_t *out, int width,
+                                                                         int height) {
+    if (!chroma_probe_args(filter, (const uint8_t *)uv, (uint8_t *)out, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height;
+    return probe16_round_trip(uv, 2 * (size_t)((width + 1) >> 1) * ((height + 1) >> 1), out, 2 * n, 0, filter, n, width, height);
 }
 #endif
 

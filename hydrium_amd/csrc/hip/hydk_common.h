@@ -13,12 +13,15 @@
 #include "hydk_half.h" /* HYDK_STORE_*: how a float-class LF group's samples are stored */
 #include "hydk_yuv.h"  /* HYDK_STORE_NV12: an 8-bit-class LF group whose pixels are an NV12 picture */
 #include "hydk_chroma.h" /* HYDK_STORE_NV12I: the same picture with interpolated chroma */
+#include "hydk_yuv16.h" /* HYDK_STORE_P016, _P016I: a 16-bit-class LF group whose pixels are a P010 / P012 / P016 picture */
 
 /* sample CLASSES: what a job's fmt and the transform kernel's FMT name.  Half-precision pixels (hyd_sample_fmt.h: 3, 4) are
  * float-class jobs — fmt == HYDK_FMT_F32 means "float class" everywhere — whose storage field says how to load a sample;
  * NV12 pictures (16 ... 19) are 8-bit-class jobs of storage HYDK_STORE_NV12: 8-bit RGB from the load on (hydk_yuv.h) */
 #define HYDK_VARIANT_NV12 8 /* HydkLfJob.use_luts of an NV12 job: XYB mode + 8 */
 #define HYDK_VARIANT_NV12I 16 /* of an NV12 job with interpolated chroma (32 ... 35, 48 ... 51; HYDK_STORE_NV12I): XYB mode + 16 */
+#define HYDK_VARIANT_P016 32 /* of a P010 / P012 / P016 job with nearest chroma (HYDK_STORE_P016): XYB mode + 32 */
+#define HYDK_VARIANT_P016I 64 /* with interpolated chroma (HYDK_STORE_P016I): XYB mode + 64 */
 #define HYDK_FMT_U8 0
 #define HYDK_FMT_U16 1
 #define HYDK_FMT_F32 2
@@ -94,7 +97,7 @@ typedef struct HydkLfJob {
     int scheme;              /* HF clustering scheme 0..3 = 9 / 3 / 2 / 1 clusters per preset */
     int use_luts;            /* which transform kernel variant owns the job: the XYB mode it was recorded under (0, 1: curves in
                               * registers, 2: gathers from the uploaded LUTs), + HYDK_VARIANT_NV12 for storage HYDK_STORE_NV12,
-                              * + HYDK_VARIANT_NV12I for storage HYDK_STORE_NV12I */
+                              * + HYDK_VARIANT_NV12I for storage HYDK_STORE_NV12I, + HYDK_VARIANT_P016 / _P016I for theirs */
     unsigned preset;         /* HF preset id of this LF group (written in front of each group section) */
     unsigned short preset_bits; /* hyd_cllog2(LF groups of this LF group's frame): the width of that field (encoder.c:940) */
     unsigned short frame_first; /* the first slot of this LF group's frame: where the running alphabet maximum starts afresh */
@@ -119,9 +122,10 @@ typedef struct HydkLfJob {
                               * chroma plane, row_stride the pitch of both */
     uint32_t per_sample;     /* probe flavour only (HYDAMD_DEBUG_HALF_PER_SAMPLE, for A/B): bit 0 interleaved, bit 1 planar half rows
                               * go through the per-sample loader although they qualify for the dword runs; the product leaves 0 */
-    uint32_t matrix;         /* HYDK_STORE_NV12 and _NV12I: HYDK_YUV_* (0 ... 3), the YCbCr matrix and range */
-    uint32_t filter;         /* HYDK_STORE_NV12I only: HYDK_CHROMA_CENTRE or HYDK_CHROMA_LEFT (hydk_chroma.h) */
-    /* HYDK_STORE_NV12I only — the PICTURE this LF group is cut from: the chroma sample of the LF group's first pixel (x0 / 2,
+    uint32_t matrix;         /* HYDK_STORE_NV12 and _NV12I: HYDK_YUV_* (0 ... 3), the YCbCr matrix and range; HYDK_STORE_P016 and
+                              * _P016I: that + 4 * HYDK_YUV16_P01x (the depth; hydk_yuv16.h) */
+    uint32_t filter;         /* HYDK_STORE_NV12I and _P016I only: HYDK_CHROMA_CENTRE or HYDK_CHROMA_LEFT (hydk_chroma.h) */
+    /* HYDK_STORE_NV12I and _P016I only — the PICTURE this LF group is cut from: the chroma sample of the LF group's first pixel (x0 / 2,
      * y0 / 2; src[1] points at it) and the picture's chroma plane, ceil(W / 2) by ceil(H / 2).  The filter reads chroma rows
      * -pic_cy0 ... pic_ch - 1 - pic_cy0 and columns -pic_cx0 ... pic_cw - 1 - pic_cx0 relative to src[1], and nothing else */
     int32_t pic_cx0, pic_cy0, pic_cw, pic_ch;

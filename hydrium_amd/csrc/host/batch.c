@@ -237,7 +237,7 @@ HYDRIUM_EXPORT int hydamd_encode_batch(HydAmdBatch *b, int frames, const void *c
         return hyd_batchrun_fail(r, HYD_API_ERROR, "Invalid Sample Format", NULL);
     for (int f = 0; f < frames; f++)
         if (!hyd_fmt_layout_ok(sample_fmt, src + 3 * f, pixel_stride))
-            return hyd_batchrun_fail(r, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
+            return hyd_batchrun_fail(r, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmt), NULL);
     int st = hyd_batchrun_busy(r);
     if (st)
         return st;

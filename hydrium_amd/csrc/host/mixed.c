@@ -481,7 +481,7 @@ HYDRIUM_EXPORT int hydamd_encode_mixed_formats(HydAmdMixed *m, int frames, const
             return hyd_batchrun_fail(r, HYD_API_ERROR, "Invalid Sample Format", NULL);
     for (int f = 0; f < frames; f++)
         if (!hyd_fmt_layout_ok(sample_fmts[f], images[f].src, images[f].pixel_stride))
-            return hyd_batchrun_fail(r, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
+            return hyd_batchrun_fail(r, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmts[f]), NULL);
     int st = hyd_batchrun_busy(r);
     if (st)
         return st;

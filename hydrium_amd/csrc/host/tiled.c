@@ -332,7 +332,7 @@ HYDRIUM_EXPORT int hydamd_encode_image_tiled(HydAmdTiled *t, const void *const s
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(t, HYD_API_ERROR, "Invalid Sample Format", NULL);
     if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
-        return fail(t, HYD_API_ERROR, HYD_FMT_NV12_LAYOUT_MSG, NULL);
+        return fail(t, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmt), NULL);
     if (t->in_flight)
         return fail(t, HYD_API_ERROR, "an image is in flight: hydamd_tiled_result first", NULL);
     t->err[0] = 0;

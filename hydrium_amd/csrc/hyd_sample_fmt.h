@@ -14,6 +14,11 @@
  * is nearest neighbour; 1 (32 ... 35) interpolates centre-sited chroma, 2 (48 ... 51) left-sited chroma (hip/hydk_chroma.h).
  * An interpolating format is NV12 in layout, size and origin; what it adds is that a sub-rectangle's pixels depend on the
  * PICTURE around it, which hydamd_encode_lf_group_at carries.
+ *
+ * The family's third dimension is the sample depth: sample format = 16 + matrix + 16 * filter + 64 * depth.  Depth 0 is the
+ * 8-bit NV12 family above.  Depth 1, 2, 3 (P010, P012, P016: 80 ..., 144 ..., 208 ...) name the same two planes in 16-bit WORDS
+ * holding 10, 12 or 16 significant bits, MSB-aligned: a storage form of the 16-BIT class (hip/hydk_yuv16.h).  src[2] ==
+ * src[1] + 2 bytes, the pixel stride is 1 and the row stride is the pitch of both planes in words.  64 ... 79 name nothing.
  */
 #ifndef HYD_SAMPLE_FMT_H_
 #define HYD_SAMPLE_FMT_H_
@@ -38,6 +43,44 @@
 #define HYD_FMT_NV12L_BT601 50
 #define HYD_FMT_NV12L_BT601_FULL 51
 #define HYD_FMT_NV12_FILTERS 3
+/* P010 / P012 / P016: 16 + matrix + 16 * filter + 64 * depth, depth 1, 2, 3 = 10, 12, 16 significant bits in 16-bit words */
+#define HYD_FMT_P010_BT709 80
+#define HYD_FMT_P010_BT709_FULL 81
+#define HYD_FMT_P010_BT601 82
+#define HYD_FMT_P010_BT601_FULL 83
+#define HYD_FMT_P010C_BT709 96
+#define HYD_FMT_P010C_BT709_FULL 97
+#define HYD_FMT_P010C_BT601 98
+#define HYD_FMT_P010C_BT601_FULL 99
+#define HYD_FMT_P010L_BT709 112
+#define HYD_FMT_P010L_BT709_FULL 113
+#define HYD_FMT_P010L_BT601 114
+#define HYD_FMT_P010L_BT601_FULL 115
+#define HYD_FMT_P012_BT709 144
+#define HYD_FMT_P012_BT709_FULL 145
+#define HYD_FMT_P012_BT601 146
+#define HYD_FMT_P012_BT601_FULL 147
+#define HYD_FMT_P012C_BT709 160
+#define HYD_FMT_P012C_BT709_FULL 161
+#define HYD_FMT_P012C_BT601 162
+#define HYD_FMT_P012C_BT601_FULL 163
+#define HYD_FMT_P012L_BT709 176
+#define HYD_FMT_P012L_BT709_FULL 177
+#define HYD_FMT_P012L_BT601 178
+#define HYD_FMT_P012L_BT601_FULL 179
+#define HYD_FMT_P016_BT709 208
+#define HYD_FMT_P016_BT709_FULL 209
+#define HYD_FMT_P016_BT601 210
+#define HYD_FMT_P016_BT601_FULL 211
+#define HYD_FMT_P016C_BT709 224
+#define HYD_FMT_P016C_BT709_FULL 225
+#define HYD_FMT_P016C_BT601 226
+#define HYD_FMT_P016C_BT601_FULL 227
+#define HYD_FMT_P016L_BT709 240
+#define HYD_FMT_P016L_BT709_FULL 241
+#define HYD_FMT_P016L_BT601 242
+#define HYD_FMT_P016L_BT601_FULL 243
+#define HYD_FMT_P016_DEPTHS 3
 
 /* YCbCr 4:2:0 in two planes with nearest-neighbour chroma, and which of the four matrices of hip/hydk_yuv.h (0 ... 3) */
 static inline int hyd_fmt_is_nv12(int fmt) { return fmt >= HYD_FMT_NV12_BT709 && fmt <= HYD_FMT_NV12_BT601_FULL; }
@@ -52,8 +95,22 @@ static inline int hyd_fmt_nv12_family_matrix(int fmt) { return (fmt - HYD_FMT_NV
 /* the eight whose chroma is interpolated: a sub-rectangle's pixels depend on the picture around it */
 static inline int hyd_fmt_is_nv12_interp(int fmt) { return hyd_fmt_is_nv12_family(fmt) && hyd_fmt_nv12_filter(fmt) != 0; }
 
+/* the P016 FAMILY, the thirty-six numbers of depth 1 ... 3: 16-bit words in NV12's two planes.  Its depth index (1, 2, 3), the
+ * significant bits that names (10, 12, 16), and filter and matrix as the 8-bit family has them */
+static inline int hyd_fmt_is_p016_family(int fmt) {
+    return fmt >= HYD_FMT_P010_BT709 && fmt <= HYD_FMT_P016L_BT601_FULL && hyd_fmt_is_nv12_family(fmt & 63);
+}
+static inline int hyd_fmt_p016_depth(int fmt) { return (fmt - HYD_FMT_NV12_BT709) >> 6; }
+static inline int hyd_fmt_p016_bits(int fmt) { return hyd_fmt_p016_depth(fmt) == 1 ? 10 : hyd_fmt_p016_depth(fmt) == 2 ? 12 : 16; }
+static inline int hyd_fmt_p016_filter(int fmt) { return ((fmt - HYD_FMT_NV12_BT709) >> 4) & 3; }
+static inline int hyd_fmt_p016_matrix(int fmt) { return (fmt - HYD_FMT_NV12_BT709) & 3; }
+static inline int hyd_fmt_is_p016_interp(int fmt) { return hyd_fmt_is_p016_family(fmt) && hyd_fmt_p016_filter(fmt) != 0; }
+/* 4:2:0 in two planes at any depth (layout and origin rules in samples), and those of them whose chroma is interpolated */
+static inline int hyd_fmt_is_yuv420(int fmt) { return hyd_fmt_is_nv12_family(fmt) || hyd_fmt_is_p016_family(fmt); }
+static inline int hyd_fmt_is_yuv420_interp(int fmt) { return hyd_fmt_is_nv12_interp(fmt) || hyd_fmt_is_p016_interp(fmt); }
+
 /* what an entry point that reads DEVICE pixels takes */
-static inline int hyd_fmt_is_device(int fmt) { return (fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_BFLOAT16) || hyd_fmt_is_nv12_family(fmt); }
+static inline int hyd_fmt_is_device(int fmt) { return (fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_BFLOAT16) || hyd_fmt_is_yuv420(fmt); }
 /* what an entry point that reads HOST pixels takes: the reference's three */
 static inline int hyd_fmt_is_host(int fmt) { return fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_FLOAT32; }
 /* float class: 8-byte token records, 72 histogram bins, the non-finite check */
@@ -82,7 +139,7 @@ static inline size_t hyd_fmt_bytes(int fmt) {
     case HYD_FMT_FLOAT32:
         return 4;
     default:
-        return 0;
+        return hyd_fmt_is_p016_family(fmt) ? 2 : 0;
     }
 }
 
@@ -91,19 +148,27 @@ static inline size_t hyd_fmt_bytes(int fmt) {
 #define HYD_FMT_NV12_LAYOUT_MSG "NV12 wants pixel_stride 1 and V one byte behind U"
 /* what hydamd_encode_image_multi says to a format with interpolated chroma */
 #define HYD_FMT_NV12_SHARDED_MSG "interpolated chroma is not sharded: a shard does not hold its neighbour's chroma rows"
+/* the P016 family's: unit pixel stride, V one 16-bit sample behind U, all three addresses on 2-byte boundaries */
+#define HYD_FMT_P016_LAYOUT_MSG "P010/P016 wants pixel_stride 1 and V one sample behind U"
 static inline int hyd_fmt_layout_ok(int fmt, const void *const src[3], ptrdiff_t pixel_stride) {
+    if (hyd_fmt_is_p016_family(fmt))
+        return pixel_stride == 1 && (const char *)src[2] == (const char *)src[1] + 2 &&
+               (((size_t)src[0] | (size_t)src[1]) & 1) == 0;
     return !hyd_fmt_is_nv12_family(fmt) || (pixel_stride == 1 && (const char *)src[2] == (const char *)src[1] + 1);
 }
+/* what an entry point says when hyd_fmt_layout_ok is 0 */
+static inline const char *hyd_fmt_layout_msg(int fmt) { return hyd_fmt_is_p016_family(fmt) ? HYD_FMT_P016_LAYOUT_MSG : HYD_FMT_NV12_LAYOUT_MSG; }
 
 /* The three origin pointers of the sub-rectangle at pixel (x0, y0) of a picture of a device format — an LF group, a tile, a
  * shard's first row.  Strides are in samples.  NV12: the chroma plane has a row for every two picture rows and two bytes for
  * every two columns, so its origin is row y0 / 2, byte x0; x0 and y0 must be even (every origin the library computes is a
- * multiple of 256). */
+ * multiple of 256).  The P016 family: the same in 16-bit words. */
 static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride, size_t x0,
                                   size_t y0, const void *origin[3]) {
-    if (hyd_fmt_is_nv12_family(fmt)) {
-        const ptrdiff_t chroma = (ptrdiff_t)(y0 / 2) * row_stride + (ptrdiff_t)x0;
-        origin[0] = (const char *)src[0] + (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;
+    if (hyd_fmt_is_yuv420(fmt)) {
+        const ptrdiff_t bytes = (ptrdiff_t)hyd_fmt_bytes(fmt);
+        const ptrdiff_t chroma = ((ptrdiff_t)(y0 / 2) * row_stride + (ptrdiff_t)x0) * bytes;
+        origin[0] = (const char *)src[0] + ((ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0) * bytes;
         origin[1] = (const char *)src[1] + chroma;
         origin[2] = (const char *)src[2] + chroma;
         return;

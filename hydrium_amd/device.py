@@ -41,6 +41,15 @@ NV12_CENTER_FORMATS = (NV12C_BT709, NV12C_BT709_FULL, NV12C_BT601, NV12C_BT601_F
 NV12_LEFT_FORMATS = (NV12L_BT709, NV12L_BT709_FULL, NV12L_BT601, NV12L_BT601_FULL)
 NV12_FAMILY = NV12_FORMATS + NV12_CENTER_FORMATS + NV12_LEFT_FORMATS
 CHROMA_FILTERS = {"nearest": 0, "centre": 1, "center": 1, "left": 2}
+# device pixels only (HYDAMD_P010_*, HYDAMD_P012_*, HYDAMD_P016_*; csrc/hip/hydk_yuv16.h): the same two planes in 16-bit words
+# holding 10, 12 or 16 significant bits, MSB-aligned — 16 + matrix + 16 * filter + 64 * depth, depth 1, 2, 3
+P016_DEPTHS = {10: 1, 12: 2, 16: 3}
+for _bits, _depth in P016_DEPTHS.items():
+    for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
+        for _name, _matrix in (("BT709", 0), ("BT709_FULL", 1), ("BT601", 2), ("BT601_FULL", 3)):
+            globals()[f"P0{_bits}{_infix}_{_name}"] = 16 + _matrix + 16 * _filter + 64 * _depth
+P010_FORMATS, P012_FORMATS, P016_FORMATS = ((80, 81, 82, 83), (144, 145, 146, 147), (208, 209, 210, 211))  # nearest chroma
+P016_FAMILY = tuple(16 + m + 16 * f + 64 * d for d in (1, 2, 3) for f in (0, 1, 2) for m in (0, 1, 2, 3))
 
 
 class Nv12:
@@ -95,10 +104,76 @@ class Nv12:
         return [self.y.data_ptr(), u, u + 1]
 
 
+class P016(Nv12):
+    """A P010 / P012 / P016 picture in device memory — NV12's two planes in 16-bit words, the significant bits MSB-aligned —
+    accepted wherever an Nv12 object is.
+
+    ``y``: (H, W) tensor of a 2-byte integer dtype with unit column stride.  ``uv``: (ceil(H / 2), ceil(W / 2), 2) of the same
+    kind with strides (pitch, 2, 1) in words, U first; its pitch is the Y plane's.  ``matrix``: one of the four NV12_FORMATS
+    (the matrix and range), ``chroma`` as Nv12's, ``depth`` 10, 12 or 16 — or ``matrix`` one of the 36 numbers of P016_FAMILY,
+    which names all three.  The words are used as stored: low bits below the depth are not masked.  A crop starts on even
+    coordinates."""
+
+    def __init__(self, y, uv, matrix: int = NV12_BT709, chroma=None, depth: int = 10):
+        matrix = int(matrix)
+        if matrix in P016_FAMILY:
+            if chroma is not None and ((matrix - 16) >> 4) & 3 != CHROMA_FILTERS.get(chroma, -1):
+                raise ValueError("matrix names another chroma filter than chroma does")
+            fmt = matrix
+        else:
+            if matrix not in NV12_FORMATS:
+                raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL (or a P010 / P012 / P016 format)")
+            if depth not in P016_DEPTHS:
+                raise ValueError("depth is 10, 12 or 16")
+            if chroma is not None and chroma not in CHROMA_FILTERS:
+                raise ValueError("chroma is 'nearest', 'centre' or 'left'")
+            fmt = matrix + 16 * CHROMA_FILTERS[chroma or "nearest"] + 64 * P016_DEPTHS[depth]
+        names = [str(t.dtype).rpartition(".")[2] for t in (y, uv)]
+        if y.element_size() != 2 or uv.element_size() != 2 or y.dim() != 2 or uv.dim() != 3 or \
+                any(n.startswith(("float", "bfloat", "complex")) for n in names):
+            raise ValueError("P010 / P016 planes are 16-bit integers: y (H, W), uv (ceil(H / 2), ceil(W / 2), 2)")
+        h, w = y.shape
+        if h < 1 or w < 1 or tuple(uv.shape) != (-(-h // 2), -(-w // 2), 2):
+            raise ValueError("the chroma plane of an (H, W) picture is (ceil(H / 2), ceil(W / 2), 2)")
+        if y.stride(1) != 1 or (uv.stride(1), uv.stride(2)) != (2, 1):
+            raise ValueError("P010 / P016 planes have unit column stride: y (pitch, 1), uv (pitch, 2, 1)")
+        if uv.shape[0] > 1 and h > 1 and uv.stride(0) != y.stride(0):
+            raise ValueError("the two planes of a P010 / P016 picture share one pitch")
+        self.y, self.uv, self.sample_fmt = y, uv, fmt
+        self.height, self.width = int(h), int(w)
+        self.pitch = int(y.stride(0) if h > 1 else uv.stride(0) if uv.shape[0] > 1 else max(y.stride(0), uv.stride(0)))  # in words
+
+    @classmethod
+    def from_surface(cls, buf, width: int, height: int, pitch_bytes: int, chroma_offset_bytes: int, matrix: int = NV12_BT709,
+                     chroma=None, depth: int = 10):
+        """A decoder's single allocation: ``buf`` a 1-D tensor of 1- or 2-byte integers, Y rows at byte 0, pitch_bytes,
+        2 * pitch_bytes ..., chroma rows at chroma_offset_bytes, chroma_offset_bytes + pitch_bytes ...  The pitch and the
+        offset are whole words (even)."""
+        if pitch_bytes % 2 or chroma_offset_bytes % 2:
+            raise ValueError("the pitch and the chroma offset of a P010 / P016 surface are even numbers of bytes")
+        if buf.element_size() == 1:
+            if buf.dim() != 1 or buf.stride(0) != 1 or buf.data_ptr() % 2 or buf.numel() % 2:
+                raise ValueError("a byte buffer holding a P010 / P016 surface is contiguous, 2-byte aligned and of even size")
+            import torch
+
+            buf = buf.view(torch.int16)
+        elif buf.element_size() != 2:
+            raise ValueError("buf holds bytes or 16-bit words")
+        pitch = pitch_bytes // 2
+        y = buf.as_strided((height, width), (pitch, 1), 0)
+        uv = buf.as_strided((-(-height // 2), -(-width // 2), 2), (pitch, 2, 1), chroma_offset_bytes // 2)
+        return cls(y, uv, matrix, chroma, depth)
+
+    def pointers(self):
+        """src[0 ... 2] of the C API: Y, U, V = U + 2 bytes."""
+        u = self.uv.data_ptr()
+        return [self.y.data_ptr(), u, u + 2]
+
+
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
     float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
-    An Nv12 object: its own format."""
+    An Nv12 or P016 object: its own format."""
     if isinstance(t, Nv12):
         return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]
@@ -694,7 +769,7 @@ class DeviceContext:
 
     def transform_footprint(self, sample_fmt: int):
         """(static LDS bytes, registers per thread) of the transform kernel instance serving `sample_fmt` (0 u8, 1 u16, 2 f32, 3 f16, 4 bf16,
-        16 ... 19 NV12, 32 ... 35 and 48 ... 51 NV12 with interpolated chroma)."""
+        16 ... 19 NV12, 32 ... 35 and 48 ... 51 NV12 with interpolated chroma, 80 ... 243 the P010 / P012 / P016 family)."""
         lds, regs = C.c_int(0), C.c_int(0)
         self._ck(self.d.hydamd_debug_transform_footprint(self.h, int(sample_fmt), C.byref(lds), C.byref(regs)))
         return lds.value, regs.value
@@ -1158,7 +1233,7 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
             elif fmt != sample_fmt:
                 raise ValueError("the images of a batch share one sample format")
         elif isinstance(sample_fmts, list) and fmt != given:
-            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FAMILY:
+            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FAMILY + P016_FAMILY:
                 raise ValueError("sample_fmts disagrees with a tensor's dtype")
             fmt = given  # not a format at all: the library refuses it (HYD_API_ERROR), nothing is enqueued
         fmts.append(fmt)

@@ -129,7 +129,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * hydamd_encode_image_batch, hydamd_encode_batch, hydamd_encode_mixed, hydamd_encode_mixed_formats,
  * hydamd_encode_image_tiled, hydamd_encode_image_multi and hydamd_debug_transform_footprint.  Entry points that read HOST
  * pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse both with "Invalid Sample Format", as they and every
- * other entry point refuse anything that is neither 0..4 nor of the NV12 family (16..19, 32..35, 48..51, below).
+ * other entry point refuse anything that is neither 0..4 nor of the NV12 family (16..19, 32..35, 48..51, below) nor of the
+ * P010 / P012 / P016 family (80..83, 96..99, 112..115, 144..147, 160..163, 176..179, 208..211, 224..227, 240..243, below).
  */
 #define HYDAMD_FLOAT16 3
 #define HYDAMD_BFLOAT16 4
@@ -142,8 +143,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  *   HYDAMD_NV12_BT709_FULL  BT.709 matrix, full range
  *   HYDAMD_NV12_BT601       BT.601 matrix, limited range: SD video
  *   HYDAMD_NV12_BT601_FULL  BT.601 matrix, full range: what a JPEG decoder leaves (JFIF)
- * (the numbers start at 16: 5..15, 20..31, 36..47 and everything from 52 up stay "Invalid Sample Format"; 32..35 and 48..51
- * are the same pictures with interpolated chroma, further down).
+ * (the numbers start at 16: 5..15, 20..31, 36..47, 52..79 and whatever else no section here names stay "Invalid Sample
+ * Format"; 32..35 and 48..51 are the same pictures with interpolated chroma, 80 and up in 16-bit words, both further down).
  *
  * The file is byte for byte what the reference writes for the HYD_UINT8 picture this conversion produces.  For pixel (x, y):
  * Y = luma[y][x]; U, V = the chroma pair at (x >> 1, y >> 1) (nearest neighbour: every 2 x 2 block shares one pair);
@@ -172,8 +173,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * their neighbours' chroma: this cannot be checked.
  * Entry points that read HOST pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse all four with "Invalid
  * Sample Format".
- * Out of scope: NV21, planar I420, 4:2:2 and 4:4:4; 10- and 16-bit P010 / P016 (they need a fixed-point derivation of their
- * own); host-pointer NV12; any colour description other than the four above.
+ * Out of scope: NV21, planar I420, 4:2:2 and 4:4:4; host-pointer NV12; any colour description other than the four above.
+ * (10- to 16-bit P010 / P012 / P016 have a fixed-point derivation and formats of their own, further down.)
  */
 #define HYDAMD_NV12_BT709 16
 #define HYDAMD_NV12_BT709_FULL 17
@@ -207,8 +208,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  *
  * Refused: hydamd_encode_image_multi ("interpolated chroma is not sharded: ..." — a shard's buffer is only promised to hold
  * its own rows, and the filter would read a neighbouring shard's chroma row), and the host-pointer entry points as for NV12.
- * Out of scope: top-left siting (BT.2020), other layouts (NV21, I420, 4:2:2, 4:4:4), 10-bit, cross-shard chroma,
- * host-pointer input.
+ * Out of scope: top-left siting (BT.2020), other layouts (NV21, I420, 4:2:2, 4:4:4), cross-shard chroma, host-pointer input.
  */
 #define HYDAMD_NV12C_BT709 32
 #define HYDAMD_NV12C_BT709_FULL 33
@@ -220,11 +220,100 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
 #define HYDAMD_NV12L_BT601_FULL 51
 
 /*
+ * P010 / P012 / P016 DEVICE pixels: what a hardware decoder leaves for anything deeper than 8 bits (HEVC Main10, 10-bit AV1
+ * and VP9, 12-bit profiles) — NV12's two planes in 16-bit WORDS, the significant bits MSB-aligned (10 bits with 6 low bits
+ * zero, 12 with 4) — read by the transform kernel as they are, without an RGB16 copy.
+ *   sample_fmt = 16 + matrix + 16 * filter + 64 * depth
+ * matrix 0..3 and filter 0..2 as in the NV12 family (depth 0, whose numbers do not change); depth 1, 2, 3 = 10, 12, 16
+ * significant bits:
+ *                    nearest     centre (..C_)   left (..L_)
+ *   HYDAMD_P010_*    80..83       96..99         112..115
+ *   HYDAMD_P012_*   144..147     160..163        176..179
+ *   HYDAMD_P016_*   208..211     224..227        240..243
+ * 64..79, and every number in between that the table leaves out, stay "Invalid Sample Format".
+ *
+ * The file is byte for byte what the reference writes for the HYD_UINT16 picture this conversion produces.  U, V of a pixel
+ * are the pair at (x >> 1, y >> 1), or U', V' by the taps of the section above on 16-bit samples (clamped at the PICTURE's
+ * edges and continuous across LF groups and tiles, as there); then with the 16-bit words AS STORED — low bits are not masked,
+ * so a surface that carries noise below its depth is read as it stands —
+ *   c = Y - yo, d = U - 32768, e = V - 32768
+ *   R = clamp((cy*c         + crv*e + 2^19) >> 20, 0, 65535)
+ *   G = clamp((cy*c - cgu*d - cgv*e + 2^19) >> 20, 0, 65535)
+ *   B = clamp((cy*c + cbu*d         + 2^19) >> 20, 0, 65535)
+ * in 64-bit two's complement, >> an arithmetic shift.  The coefficients are floor(v * 2^20 + 0.5) of cy = sy, crv = 2(1-Kr) sc,
+ * cbu = 2(1-Kb) sc, cgu = 2(1-Kb) Kb/Kg sc, cgv = 2(1-Kr) Kr/Kg sc (Kr, Kb = 0.2126, 0.0722 or 0.299, 0.114; Kg = 1 - Kr - Kb).
+ * Limited range, at every depth (the standards scale the range with the depth, so MSB-aligned words need no depth):
+ * yo = 4096, sy = 65535 / (219 * 256), sc = 65535 / (224 * 256).  Full range: yo = 0, sy = sc = 65535 / ((2^n - 1) * 2^(16 - n))
+ * for n significant bits — 1 for n = 16.  The depth matters only there: it makes 10-bit code 1023 white.
+ *                      yo       cy      crv     cgu     cgv      cbu
+ *   BT709 (any depth)  4096  1225714  1887168  224481  560979  2223666
+ *   BT601 (any depth)  4096  1225714  1680093  412397  855788  2123484
+ *   P010 BT709_FULL       0  1049585  1652886  196613  491336  1947610
+ *   P010 BT601_FULL       0  1049585  1471518  361200  749547  1859865
+ *   P012 BT709_FULL       0  1048816  1651676  196469  490976  1946183
+ *   P012 BT601_FULL       0  1048816  1470440  360936  748998  1858502
+ *   P016 BT709_FULL       0  1048576  1651297  196424  490864  1945738
+ *   P016 BT601_FULL       0  1048576  1470104  360853  748826  1858077
+ * A coefficient is off by at most 2^-21, together at most 65535 * 2^-21 + 2 * 32768 * 2^-21 = 0.0625; with half a code of
+ * rounding the result is within 0.5625 of the clamped real-valued conversion for every (Y, U, V).
+ *
+ * How such a picture is named: as an NV12 picture, in 16-bit samples —
+ *   src[0]        the first Y word;  src[1] the first U word of chroma row 0;  src[2] must equal src[1] + 2 bytes
+ *   pixel_stride  must be 1
+ *   row_stride    the one pitch of both planes IN SAMPLES (16-bit words), as every stride of this API is; may be negative.
+ *                 Width and height may be odd: the chroma plane is ceil(h / 2) rows of ceil(w / 2) pairs.
+ * All three addresses are 2-byte aligned.  A bad layout is HYD_API_ERROR "P010/P016 wants pixel_stride 1 and V one sample
+ * behind U", nothing enqueued.  The library finds an LF group, tile or shard at even (x0, y0) at word y0 * row_stride + x0 of
+ * the Y plane and word (y0 / 2) * row_stride + x0 of the chroma plane.
+ *
+ * Accepted wherever NV12 is.  hydamd_encode_image_multi takes the nearest forms and refuses the interpolated 24 as it does
+ * NV12's; the host-pointer entry points refuse all 36 with "Invalid Sample Format".
+ * Out of scope: BT.2020 and the PQ / HLG transfer curves — the codestream this encoder writes signals sRGB or linear sRGB
+ * only, so HDR10 content would be mis-described whatever the matrix; planar I420 / I010; 4:2:2 and 4:4:4; host-pointer P010.
+ */
+#define HYDAMD_P010_BT709 80
+#define HYDAMD_P010_BT709_FULL 81
+#define HYDAMD_P010_BT601 82
+#define HYDAMD_P010_BT601_FULL 83
+#define HYDAMD_P010C_BT709 96
+#define HYDAMD_P010C_BT709_FULL 97
+#define HYDAMD_P010C_BT601 98
+#define HYDAMD_P010C_BT601_FULL 99
+#define HYDAMD_P010L_BT709 112
+#define HYDAMD_P010L_BT709_FULL 113
+#define HYDAMD_P010L_BT601 114
+#define HYDAMD_P010L_BT601_FULL 115
+#define HYDAMD_P012_BT709 144
+#define HYDAMD_P012_BT709_FULL 145
+#define HYDAMD_P012_BT601 146
+#define HYDAMD_P012_BT601_FULL 147
+#define HYDAMD_P012C_BT709 160
+#define HYDAMD_P012C_BT709_FULL 161
+#define HYDAMD_P012C_BT601 162
+#define HYDAMD_P012C_BT601_FULL 163
+#define HYDAMD_P012L_BT709 176
+#define HYDAMD_P012L_BT709_FULL 177
+#define HYDAMD_P012L_BT601 178
+#define HYDAMD_P012L_BT601_FULL 179
+#define HYDAMD_P016_BT709 208
+#define HYDAMD_P016_BT709_FULL 209
+#define HYDAMD_P016_BT601 210
+#define HYDAMD_P016_BT601_FULL 211
+#define HYDAMD_P016C_BT709 224
+#define HYDAMD_P016C_BT709_FULL 225
+#define HYDAMD_P016C_BT601 226
+#define HYDAMD_P016C_BT601_FULL 227
+#define HYDAMD_P016L_BT709 240
+#define HYDAMD_P016L_BT709_FULL 241
+#define HYDAMD_P016L_BT601 242
+#define HYDAMD_P016L_BT601_FULL 243
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_* formats (whose src and strides are described above).
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_* or HYDAMD_P01x_* formats (whose src and strides are described above).
  * With HYDAMD_NV12C_* or HYDAMD_NV12L_* the LF group is a picture of its own: its chroma clamps at its own edges.
  */
 HYDAMD_EXPORT int hydamd_encode_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
