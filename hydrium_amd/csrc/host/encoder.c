@@ -1406,14 +1406,14 @@ HYDRIUM_EXPORT int hydamd_frame_from_blobs(const HYDImageMetadata *md, int write
     unsigned max_alphabet = 0;
     for (size_t b = 0; b < nblobs; b++) { /* the headers: how many LF groups, how many bytes of HF sections */
         const int cls = hyd_read_blob(blobs[b], blob_sizes[b], 0, &view, NULL, &max_alphabet);
-        if (cls != HYD_BLOB_USABLE || (view.header->status & 1u)) {
+        if (cls != HYD_BLOB_USABLE || (view.header.status & 1u)) {
             if (err)
-                *err = cls == HYD_BLOB_NOT_USABLE && view.header && (view.header->status & HYDAMD_BLOB_RETRY)
+                *err = cls == HYD_BLOB_NOT_USABLE && view.has_header && (view.header.status & HYDAMD_BLOB_RETRY)
                            ? "a blob is incomplete (its frame outgrew a buffer): rerun that shard"
                            : cls != HYD_BLOB_USABLE ? bad : "Invalid NaN Float";
             return HYD_API_ERROR;
         }
-        slots += view.header->num_slots;
+        slots += view.header.num_slots;
         hf_total += view.hf_len;
     }
     const size_t lfg_x = (md->width + 2047) >> 11;
@@ -1441,9 +1441,10 @@ HYDRIUM_EXPORT int hydamd_frame_from_blobs(const HYDImageMetadata *md, int write
                                                    : cls == HYD_BLOB_LF_ERROR ? "LF code construction failed on the device" : bad;
             break;
         }
-        for (uint32_t i = 0; i < view.header->num_slots; i++, s++) {
-            tile_xy[2 * s] = (uint32_t)(view.slot[i].preset % lfg_x);
-            tile_xy[2 * s + 1] = (uint32_t)(view.slot[i].preset / lfg_x);
+        for (uint32_t i = 0; i < view.header.num_slots; i++, s++) {
+            const uint32_t preset = hyd_blob_slot_preset(&view, i);
+            tile_xy[2 * s] = (uint32_t)(preset % lfg_x);
+            tile_xy[2 * s + 1] = (uint32_t)(preset / lfg_x);
         }
         if (payload)
             memcpy(payload + hf_pos, view.hf, view.hf_len);

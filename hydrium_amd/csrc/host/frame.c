@@ -364,9 +364,11 @@ int hyd_write_lf_group(HydBits *out, const int32_t *dc, size_t vbw, size_t vbh, 
                 const int32_t n = y ? above[x] : w;
                 const int32_t nw = x && y ? above[x - 1] : w;
                 const int32_t lo = w < n ? w : n, hi = w < n ? n : w;
-                int32_t pred = w + n - nw;
+                /* 32-bit wrap-around, as the reference's int32 code behaves and lf_windows.h restates: float input far
+                 * outside [0, 1] brings LF ints of INT_MIN, whose sums and differences leave int32 */
+                int32_t pred = (int32_t)((uint32_t)w + (uint32_t)n - (uint32_t)nw);
                 pred = pred < lo ? lo : pred > hi ? hi : pred;
-                ret = hps_send(&s, 0, pack_signed(row[x] - pred));
+                ret = hps_send(&s, 0, pack_signed((int32_t)((uint32_t)row[x] - (uint32_t)pred)));
             }
         }
     }

@@ -4,6 +4,7 @@
  */
 #define _POSIX_C_SOURCE 200809L /* clock_gettime under -std=c99 */
 #include <pthread.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -88,13 +89,25 @@ int hyd_read_table_results(HydAmdContext *ctx, const HydFrameLfg *lfg, size_t co
     return ret;
 }
 
+/* a field of a record that lies at any byte address */
+#define BLOB_FIELD(dst, rec, type, member) memcpy(&(dst), (rec) + offsetof(type, member), sizeof(dst))
+
+uint32_t hyd_blob_slot_preset(const HydBlobView *view, uint32_t i) {
+    uint32_t preset;
+    BLOB_FIELD(preset, view->slots + (size_t)i * sizeof(HydAmdBlobSlot), HydAmdBlobSlot, preset);
+    return preset;
+}
+
 int hyd_read_blob(const void *blob, size_t size, size_t expected_slots, HydBlobView *view, HydLfgResult *res,
                   unsigned *max_alphabet) {
-    const HydAmdBlobHeader *h = blob;
     memset(view, 0, sizeof(*view));
-    if (!h || size < sizeof(*h))
+    if (!blob || size < sizeof(view->header))
         return HYD_BLOB_NOT_USABLE;
-    view->header = h;
+    /* a blob is a byte string: a caller may hold it at any address (a slice of a receive buffer), so the header is
+     * copied out and the slot records are read field by field, never through a pointer of their own type */
+    memcpy(&view->header, blob, sizeof(view->header));
+    view->has_header = 1;
+    const HydAmdBlobHeader *h = &view->header;
     if (h->magic != 0x42445948u || h->version != 1 || h->total_bytes > size || (h->status & HYDAMD_BLOB_RETRY) ||
         h->lf_coded != 1 || /* 0: LF ints not coded; 0x101: a view, for device assemblers only */
         (expected_slots && h->num_slots != expected_slots))
@@ -106,23 +119,28 @@ int hyd_read_blob(const void *blob, size_t size, size_t expected_slots, HydBlobV
     const uint64_t hf_off = sane ? (lf_off + h->lf_bytes + 15u) & ~(uint64_t)15u : 0;
     if (!sane || hf_off > h->total_bytes || hf_off + h->hf_bytes != h->total_bytes)
         return HYD_BLOB_MALFORMED;
-    view->slot = (const HydAmdBlobSlot *)(h + 1);
+    view->slots = (const uint8_t *)blob + sizeof(*h);
     view->hf = (const uint8_t *)blob + hf_off;
     view->hf_len = (size_t)h->hf_bytes;
     for (uint32_t i = 0; res && i < h->num_slots; i++) {
-        const HydAmdBlobSlot *rec = &view->slot[i];
-        if (rec->table_error)
+        const uint8_t *rec = view->slots + (size_t)i * sizeof(HydAmdBlobSlot);
+        uint32_t table_error, running;
+        HydAmdLfInfo lf;
+        BLOB_FIELD(table_error, rec, HydAmdBlobSlot, table_error);
+        BLOB_FIELD(lf, rec, HydAmdBlobSlot, lf);
+        if (table_error)
             return HYD_BLOB_TABLE_ERROR;
-        if (rec->lf.error)
+        if (lf.error)
             return HYD_BLOB_LF_ERROR;
-        if (lf_outside(&rec->lf, h->lf_bytes))
+        if (lf_outside(&lf, h->lf_bytes))
             return HYD_BLOB_LF_RANGE;
-        memcpy(res[i].freq, rec->freq, sizeof(res[i].freq));
-        memcpy(res[i].alphabet, rec->alphabet, sizeof(res[i].alphabet));
-        memcpy(res[i].bits, rec->group_bits, sizeof(res[i].bits));
-        take_lf_stream(&res[i], &rec->lf, (const uint8_t *)blob + lf_off);
-        if (rec->running_max_alphabet > *max_alphabet)
-            *max_alphabet = rec->running_max_alphabet;
+        BLOB_FIELD(res[i].freq, rec, HydAmdBlobSlot, freq);
+        BLOB_FIELD(res[i].alphabet, rec, HydAmdBlobSlot, alphabet);
+        BLOB_FIELD(res[i].bits, rec, HydAmdBlobSlot, group_bits);
+        take_lf_stream(&res[i], &lf, (const uint8_t *)blob + lf_off);
+        BLOB_FIELD(running, rec, HydAmdBlobSlot, running_max_alphabet);
+        if (running > *max_alphabet)
+            *max_alphabet = running;
     }
     return HYD_BLOB_USABLE;
 }
@@ -409,7 +427,7 @@ __attribute__((visibility("default"))) int hydt_blob_class(const void *blob, siz
     HydBlobView view;
     unsigned max_alphabet = 0;
     int cls = hyd_read_blob(blob, size, expected_slots, &view, NULL, &max_alphabet);
-    HydLfgResult *res = cls == HYD_BLOB_USABLE ? calloc(view.header->num_slots + 1, sizeof(HydLfgResult)) : NULL;
+    HydLfgResult *res = cls == HYD_BLOB_USABLE ? calloc(view.header.num_slots + 1, sizeof(HydLfgResult)) : NULL;
     if (res)
         cls = hyd_read_blob(blob, size, expected_slots, &view, res, &max_alphabet);
     free(res);

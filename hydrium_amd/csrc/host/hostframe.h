@@ -56,11 +56,13 @@ enum {
     HYD_BLOB_TABLE_ERROR, HYD_BLOB_LF_ERROR, HYD_BLOB_LF_RANGE /* a slot: the device's two error words, an LF stream outside lf_bytes */
 };
 typedef struct HydBlobView {
-    const HydAmdBlobHeader *header; /* NULL: the blob is shorter than one */
-    const HydAmdBlobSlot *slot;     /* [header->num_slots] */
-    const uint8_t *hf;              /* the packed HF sections */
+    HydAmdBlobHeader header; /* a copy: the blob is a byte string and may lie at any address */
+    int has_header;          /* 0: the blob is shorter than a header */
+    const uint8_t *slots;    /* header.num_slots records of sizeof(HydAmdBlobSlot) bytes, at any address: read field by field */
+    const uint8_t *hf;       /* the packed HF sections */
     size_t hf_len;
 } HydBlobView;
+uint32_t hyd_blob_slot_preset(const HydBlobView *view, uint32_t i);
 int hyd_read_blob(const void *blob, size_t size, size_t expected_slots, HydBlobView *view, HydLfgResult *res,
                   unsigned *max_alphabet);
 

@@ -464,7 +464,7 @@ int hydt_layout_from_streams_skip(const uint8_t *plan, const HydkTileFrame *fram
     HydkTileScratch *scratch = calloc(1, sizeof(*scratch));
     size_t lf_len = 0;
     for (size_t f = 0; f < nframes; f++)
-        lf_len += (((size_t)lf[f].bit_count + 7) >> 3) + 3 & ~(size_t)3;
+        lf_len += ((((size_t)lf[f].bit_count + 7) >> 3) + 3) & ~(size_t)3;
     uint8_t *lf_packed = calloc(lf_len + 16, 1);
     uint8_t *hf = calloc(payload_len + 16, 1);
     uint8_t *file = NULL;
