@@ -343,11 +343,23 @@ static_assert(HYDAMD_P016_ROW(P010, HYDK_YUV16_P010) && HYDAMD_P016_ROW(P012, HY
                   HYD_FMT_P016_DEPTHS == HYDK_YUV16_DEPTHS,
               "the P016 family is 16 + the kernels' matrix index + 16 * the kernels' chroma filter + 64 * the kernels' depth");
 #undef HYDAMD_P016_ROW
+#define HYDAMD_PLANAR_ROW(P)                                                                                    \
+    (HYD_FMT_##P##_BT709 == HYDAMD_##P##_BT709 && HYD_FMT_##P##_BT709_FULL == HYDAMD_##P##_BT709_FULL &&         \
+     HYD_FMT_##P##_BT601 == HYDAMD_##P##_BT601 && HYD_FMT_##P##_BT601_FULL == HYDAMD_##P##_BT601_FULL &&         \
+     HYDAMD_##P##_BT709 + HYDK_YUV_BT601_FULL == HYDAMD_##P##_BT601_FULL)
+static_assert(HYDAMD_PLANAR_ROW(I420) && HYDAMD_PLANAR_ROW(I422) && HYDAMD_PLANAR_ROW(I444) && HYDAMD_PLANAR_ROW(I420C) &&
+                  HYDAMD_PLANAR_ROW(I422C) && HYDAMD_PLANAR_ROW(I420L) && HYDAMD_PLANAR_ROW(I422L) &&
+                  HYDAMD_I422_BT709 == HYDAMD_I420_BT709 + 4 * HYDK_PLANAR_422 && HYDAMD_I444_BT709 == HYDAMD_I420_BT709 + 4 * HYDK_PLANAR_444 &&
+                  HYDAMD_I420C_BT709 == HYDAMD_I420_BT709 + 16 * HYDK_CHROMA_CENTRE && HYDAMD_I422L_BT709 == HYDAMD_I422_BT709 + 16 * HYDK_CHROMA_LEFT &&
+                  HYD_FMT_PLANAR_420 == HYDK_PLANAR_420 && HYD_FMT_PLANAR_422 == HYDK_PLANAR_422 && HYD_FMT_PLANAR_444 == HYDK_PLANAR_444,
+              "the planar family is 512 + the kernels' matrix index + 4 * the kernels' subsampling + 16 * the kernels' chroma filter");
+#undef HYDAMD_PLANAR_ROW
 
 /* a public sample format's class (what job.fmt holds) and its storage form: the float class's three, NV12 and NV12I (NV12
- * with interpolated chroma) of the 8-bit class, P016 and P016I (P010 / P012 / P016, the same in 16-bit words) of the 16-bit class */
+ * with interpolated chroma) of the 8-bit class, P016 and P016I (P010 / P012 / P016, the same in 16-bit words) of the 16-bit class,
+ * YUVP and YUVPI (planar YCbCr, nearest and interpolated) of the 8-bit class */
 int fmt_class(int sample_fmt) {
-    return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : hyd_fmt_is_nv12_family(sample_fmt) ? HYDK_FMT_U8 : hyd_fmt_is_p016_family(sample_fmt) ? HYDK_FMT_U16 : sample_fmt;
+    return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : hyd_fmt_is_nv12_family(sample_fmt) || hyd_fmt_is_planar_yuv(sample_fmt) ? HYDK_FMT_U8 : hyd_fmt_is_p016_family(sample_fmt) ? HYDK_FMT_U16 : sample_fmt;
 }
 uint32_t fmt_storage(int sample_fmt) {
     return sample_fmt == HYD_FMT_FLOAT16    ? HYDK_STORE_F16
@@ -356,6 +368,8 @@ uint32_t fmt_storage(int sample_fmt) {
            : hyd_fmt_is_nv12_interp(sample_fmt) ? HYDK_STORE_NV12I
            : hyd_fmt_is_p016_interp(sample_fmt) ? HYDK_STORE_P016I
            : hyd_fmt_is_p016_family(sample_fmt) ? HYDK_STORE_P016
+           : hyd_fmt_is_planar_interp(sample_fmt) ? HYDK_STORE_YUVPI
+           : hyd_fmt_is_planar_yuv(sample_fmt)    ? HYDK_STORE_YUVP
                                             : HYDK_STORE_F32;
 }
 /* the public format a recorded job reads */
@@ -366,6 +380,8 @@ int job_sample_fmt(const HydkLfJob &job) {
            : job.storage == HYDK_STORE_NV12I ? HYD_FMT_NV12_BT709 + (int)job.matrix + 16 * (int)job.filter
            : job.storage == HYDK_STORE_P016 || job.storage == HYDK_STORE_P016I
                ? HYD_FMT_NV12_BT709 + (int)(job.matrix & 3u) + 16 * (int)job.filter + 64 * (int)(job.matrix >> 2)
+           : job.storage == HYDK_STORE_YUVP || job.storage == HYDK_STORE_YUVPI
+               ? HYD_FMT_I420_BT709 + (int)job.matrix + 4 * (int)job.sub + 16 * (int)job.filter
                                             : job.fmt;
 }
 
@@ -442,6 +458,8 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
         return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
+    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, pic ? pic[2] : width))
+        return fail(ctx, ST_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG);
     /* half precision is a storage form of the float class: the job is a float job, and every `fmt == HYDK_FMT_F32` below
      * and in the kernels keeps meaning "float class".  NV12 is a storage form of the 8-bit class: 4-byte token records, the
      * 8-bit transfer table, and whatever form of the entropy stage is selected */
@@ -472,7 +490,19 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.storage = fmt_storage(sample_fmt);
     job.matrix = hyd_fmt_is_nv12_family(sample_fmt) ? (uint32_t)hyd_fmt_nv12_family_matrix(sample_fmt)
                  : hyd_fmt_is_p016_family(sample_fmt) ? (uint32_t)(hyd_fmt_p016_matrix(sample_fmt) + 4 * hyd_fmt_p016_depth(sample_fmt))
+                 : hyd_fmt_is_planar_yuv(sample_fmt)  ? (uint32_t)hyd_fmt_planar_matrix(sample_fmt)
                                                       : 0u;
+    if (job.storage == HYDK_STORE_YUVP || job.storage == HYDK_STORE_YUVPI)
+        job.sub = (uint32_t)hyd_fmt_planar_sub(sample_fmt);
+    if (job.storage == HYDK_STORE_YUVPI) {
+        /* each chroma plane of the picture in its own units, and where src[1] and src[2] point in it */
+        const int sx = hyd_fmt_planar_sx(sample_fmt), sy = hyd_fmt_planar_sy(sample_fmt);
+        job.filter = (uint32_t)hyd_fmt_planar_filter(sample_fmt);
+        job.pic_cx0 = pic ? (int32_t)(pic[0] >> sx) : 0;
+        job.pic_cy0 = pic ? (int32_t)(pic[1] >> sy) : 0;
+        job.pic_cw = (int32_t)(((pic ? pic[2] : width) + (size_t)sx) >> sx);
+        job.pic_ch = (int32_t)(((pic ? pic[3] : height) + (size_t)sy) >> sy);
+    }
     if (job.storage == HYDK_STORE_NV12I || job.storage == HYDK_STORE_P016I) {
         /* the picture's chroma plane and where src[1] points in it: all the kernel may read around this LF group */
         job.filter = (uint32_t)(job.storage == HYDK_STORE_NV12I ? hyd_fmt_nv12_filter(sample_fmt) : hyd_fmt_p016_filter(sample_fmt));
@@ -498,6 +528,8 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
                                       : job.storage == HYDK_STORE_NV12I ? HYDK_VARIANT_NV12I
                                       : job.storage == HYDK_STORE_P016  ? HYDK_VARIANT_P016
                                       : job.storage == HYDK_STORE_P016I ? HYDK_VARIANT_P016I
+                                      : job.storage == HYDK_STORE_YUVP  ? HYDK_VARIANT_YUVP
+                                      : job.storage == HYDK_STORE_YUVPI ? HYDK_VARIANT_YUVPI
                                                                         : 0);
     job.preset = preset;
     while ((1u << job.preset_bits) < frame_groups) /* hyd_cllog2, encoder.c:940 */
@@ -1387,6 +1419,8 @@ int hydamd_encode_image(HydAmdContext *ctx, const void *const src[3], ptrdiff_t 
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
         return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
+    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, width))
+        return fail(ctx, ST_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG);
     int st = hydamd_begin_frame(ctx, (unsigned)(lfx * lfy));
     for (size_t ty = 0; ty < lfy && st == ST_OK; ty++)
         for (size_t tx = 0; tx < lfx && st == ST_OK; tx++) {
@@ -1460,6 +1494,8 @@ int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const 
     for (int f = 0; f < frames; f++)
         if (src[3 * (size_t)f + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * (size_t)f, pixel_stride))
             return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
+    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, width))
+        return fail(ctx, ST_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG);
     const size_t lfx = (width + 2047) >> 11, lfy = (height + 2047) >> 11, n = lfx * lfy;
     int st = hydamd_begin_batch(ctx, (unsigned)n, frames);
     for (int f = 0; f < frames && st == ST_OK; f++) {
@@ -2956,6 +2992,61 @@ __attribute__((visibility("default"))) int hydt_chroma_upsample_device(int devic
     }
     if (e == hipSuccess)
         e = hipMemcpy(out, d_out, 2 * n, hipMemcpyDeviceToHost); /* (waits for the kernel) */
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the planar definition (hydk_planar_sample, hydk_chroma.h) as the
+ * host compiler built it and as the device runs it.  sub: HYDK_PLANAR_420 ... _444; filter: HYDK_CHROMA_NEAREST, _CENTRE or _LEFT
+ * (4:4:4: nearest only); plane: ONE chroma plane of a width x height picture, ch rows of cw samples, tightly packed; out
+ * receives height rows of width samples. */
+static bool planar_probe_args(int sub, int filter, const uint8_t *plane, uint8_t *out, int width, int height) {
+    return sub >= 0 && sub < HYDK_PLANAR_SUBS && filter >= 0 && filter < HYDK_CHROMA_FILTERS && (sub != HYDK_PLANAR_444 || filter == 0) &&
+           plane && out && width >= 1 && height >= 1 && width <= 4096 && height <= 4096;
+}
+
+__attribute__((visibility("default"))) int hydt_planar_upsample_host(int sub, int filter, const uint8_t *plane, uint8_t *out, int width,
+                                                                     int height) {
+    if (!planar_probe_args(sub, filter, plane, out, width, height))
+        return ST_API_ERROR;
+    const int cw = (width + hydk_planar_sx(sub)) >> hydk_planar_sx(sub), ch = (height + hydk_planar_sy(sub)) >> hydk_planar_sy(sub);
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            out[(size_t)y * width + x] = (uint8_t)hydk_planar_sample(sub, filter, plane, cw, cw, ch, x, y);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_planar_upsample_probe(int sub, int filter, const uint8_t *plane, uint8_t *out, int width, int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i >= (size_t)width * height)
+        return;
+    const int cw = (width + hydk_planar_sx(sub)) >> hydk_planar_sx(sub), ch = (height + hydk_planar_sy(sub)) >> hydk_planar_sy(sub);
+    out[i] = (uint8_t)hydk_planar_sample(sub, filter, plane, cw, cw, ch, (int)(i % (size_t)width), (int)(i / (size_t)width));
+}
+} /* namespace */
+
+/* one launch over the picture (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_planar_upsample_device(int device, int sub, int filter, const uint8_t *plane, uint8_t *out,
+                                                                       int width, int height) {
+    if (!planar_probe_args(sub, filter, plane, out, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height;
+    const size_t in_bytes = (size_t)((width + hydk_planar_sx(sub)) >> hydk_planar_sx(sub)) * ((height + hydk_planar_sy(sub)) >> hydk_planar_sy(sub));
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_in, in_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&d_out, n);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_in, plane, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_planar_upsample_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, sub, filter, d_in, d_out, width,
+                           height);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpy(out, d_out, n, hipMemcpyDeviceToHost); /* (waits for the kernel) */
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return e == hipSuccess ? ST_OK : ST_API_ERROR;

@@ -17,6 +17,18 @@
  * (3 v(cx) + v(hx) + 8) >> 4, (v(cx) + 2) >> 2, (v(cx) + v(hx) + 4) >> 3 — the same integers before the shift, so the same
  * result; the taps sum to the divisor, so a result stays in 0 ... 255.  Clamping is at the edges of the picture: no index
  * outside rows 0 ... ch - 1, columns 0 ... cw - 1 is ever formed.
+ *
+ * PLANAR chroma (three planes, hyd_sample_fmt.h 512 ...) uses the same taps on each plane by itself.  4:2:0 as above.  4:2:2 has
+ * a chroma row for every picture row, ch = H, so only the horizontal taps remain, with cx = x >> 1:
+ *
+ *   centre-sited, hx = clamp(cx + (x odd ? 1 : -1), 0, cw - 1):   C' = (3 C[y][cx] + C[y][hx] + 2) >> 2
+ *   left-sited, x even:                                           C' = C[y][cx]
+ *   left-sited, x odd, hx = min(cx + 1, cw - 1):                  C' = (C[y][cx] + C[y][hx] + 1) >> 1
+ *
+ * These are the 4:2:0 formulas with the far row equal to the near row: v(c) = 4 C[y][c], and (3 * 4a + 4b + 8) >> 4 =
+ * (3a + b + 2) >> 2, (4a + 2) >> 2 = a, (4a + 4b + 4) >> 3 = (a + b + 1) >> 1 exactly.  So 4:2:2 is
+ * hydk_chroma_hmix(filter, x & 1, hydk_chroma_vmix(a, a), hydk_chroma_vmix(b, b)) and the taps stay in this one place
+ * (hydk_planar_sample below, and the transform kernel's planar loader, which takes the near dword for the far one).
  */
 #ifndef HYD_CHROMA_UPSAMPLE_H_
 #define HYD_CHROMA_UPSAMPLE_H_
@@ -69,6 +81,36 @@ HYDK_CHROMA_FN void hydk_chroma_pair(int filter, const uint8_t *near, const uint
     for (int c = 0; c < 2; c++)
         uv[c] = hydk_chroma_hmix(filter, x & 1, hydk_chroma_vmix(near[2 * cx + c], far[2 * cx + c]),
                                  hydk_chroma_vmix(near[2 * hx + c], far[2 * hx + c]));
+}
+
+/* storage forms of an 8-bit-class LF group whose pixels are PLANAR YCbCr: src[0] the Y plane (pitch row_stride), src[1] and
+ * src[2] the U and V planes (pitch pixel_stride), HydkLfJob.sub the subsampling.  _YUVP: nearest chroma; _YUVPI: interpolated
+ * under HydkLfJob.filter, 4:2:0 and 4:2:2 */
+#define HYDK_STORE_YUVP 7
+#define HYDK_STORE_YUVPI 8
+
+/* subsamplings (HydkLfJob.sub; hyd_sample_fmt.h: ((sample format - 512) >> 2) & 3) */
+#define HYDK_PLANAR_420 0
+#define HYDK_PLANAR_422 1
+#define HYDK_PLANAR_444 2
+#define HYDK_PLANAR_SUBS 3
+/* log2 of the pixels one chroma sample spans across and down */
+HYDK_CHROMA_FN int hydk_planar_sx(int sub) { return sub != HYDK_PLANAR_444; }
+HYDK_CHROMA_FN int hydk_planar_sy(int sub) { return sub == HYDK_PLANAR_420; }
+
+/* U' or V' of pixel (x, y) out of ONE plane of a planar picture, read byte by byte with the clamps: the definition pixel by
+ * pixel.  plane: the PICTURE's sample (0, 0) of that plane, cw x ch samples, rows `pitch` bytes apart (either sign).  filter:
+ * HYDK_CHROMA_NEAREST, _CENTRE or _LEFT; 4:4:4 is nearest whatever it says.  Nothing outside the cw x ch samples is read. */
+HYDK_CHROMA_FN uint32_t hydk_planar_sample(int sub, int filter, const uint8_t *plane, long long pitch, int32_t cw, int32_t ch, int32_t x,
+                                           int32_t y) {
+    const int sx = hydk_planar_sx(sub), sy = hydk_planar_sy(sub);
+    const uint8_t *near = plane + (long long)(y >> sy) * pitch;
+    if (filter == HYDK_CHROMA_NEAREST || !sx)
+        return near[x >> sx];
+    /* 4:2:2: the far row is the near row */
+    const uint8_t *far = sy ? plane + (long long)hydk_chroma_vy(y, ch) * pitch : near;
+    const int32_t cx = x >> 1, hx = hydk_chroma_hx(filter, x, cw);
+    return hydk_chroma_hmix(filter, x & 1, hydk_chroma_vmix(near[cx], far[cx]), hydk_chroma_vmix(near[hx], far[hx]));
 }
 
 #endif /* HYD_CHROMA_UPSAMPLE_H_ */

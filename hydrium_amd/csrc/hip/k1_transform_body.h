@@ -1,20 +1,23 @@
 /*
- * k1_transform_body.h — the body of the transform kernel (kernels.hip, K1), included into k_transform_tokenize and into
- * k_transform_tokenize_p016 and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
+ * k1_transform_body.h — the body of the transform kernel (kernels.hip, K1), included into k_transform_tokenize, into
+ * k_transform_tokenize_p016 and into k_transform_tokenize_planar and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
  * and STORE, the kernel's parameters jobs, status, part_info and plog, and everything kernels.hip defines above its K1 section.
  * No include guard: it is function-body text, meant to be included once per kernel.
  */
     static_assert(STORE == HYDK_STORE_F32 || (STORE == HYDK_STORE_NV12 || STORE == HYDK_STORE_NV12I   ? FMT == HYDK_FMT_U8
+                                              : STORE == HYDK_STORE_YUVP || STORE == HYDK_STORE_YUVPI ? FMT == HYDK_FMT_U8
                                               : STORE == HYDK_STORE_P016 || STORE == HYDK_STORE_P016I ? FMT == HYDK_FMT_U16
                                                                                                       : FMT == HYDK_FMT_F32),
-                  "the float class has the half-precision storage forms, the 8-bit class NV12 and NV12I, the 16-bit class P016 and P016I");
+                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP and YUVPI, the 16-bit class P016 and P016I");
+    /* YUVP, YUVPI: planar YCbCr — U and V in planes of their own whose pitch is job.pixel_stride, subsampled as job.sub says */
+    constexpr bool YUVP = STORE == HYDK_STORE_YUVP, YUVPI = STORE == HYDK_STORE_YUVPI;
     /* P016, P016I: what NV12 and NV12I are, in 16-bit words — a block row is four dwords of Y and four of U, V pairs */
     constexpr bool P016 = STORE == HYDK_STORE_P016, P016I = STORE == HYDK_STORE_P016I;
     constexpr bool NV12 = STORE == HYDK_STORE_NV12;
     /* NV12I: the NV12 picture with interpolated chroma (hydk_chroma.h) — job.filter says centre- or left-sited, and the job
      * knows the picture it is cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it */
     constexpr bool NV12I = STORE == HYDK_STORE_NV12I;
-    constexpr bool HALF = STORE != HYDK_STORE_F32 && !NV12 && !NV12I && !P016 && !P016I;
+    constexpr bool HALF = STORE != HYDK_STORE_F32 && !NV12 && !NV12I && !P016 && !P016I && !YUVP && !YUVPI;
     typedef typename std::conditional<HALF, uint16_t, typename SampleOf<FMT>::type>::type sample_t;
     constexpr bool LUTS = XMODE == kXybGather;
     constexpr int kWords = FMT == HYDK_FMT_U8 ? 6 : 12; /* dwords holding 8 packed RGB pixels */
@@ -27,7 +30,7 @@
     const unsigned bid = blockIdx.x >> plog, part = blockIdx.x & ((1u << plog) - 1u);
     const HydkLfJob job = jobs[bid >> 6];
     /* (an NV12 job names its variant as mode + HYDK_VARIANT_NV12: the 8-bit instances' own test turns it away as it stands) */
-    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE) + (NV12 ? HYDK_VARIANT_NV12 : NV12I ? HYDK_VARIANT_NV12I : P016 ? HYDK_VARIANT_P016 : P016I ? HYDK_VARIANT_P016I : 0)) ||
+    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE) + (NV12 ? HYDK_VARIANT_NV12 : NV12I ? HYDK_VARIANT_NV12I : P016 ? HYDK_VARIANT_P016 : P016I ? HYDK_VARIANT_P016I : YUVP ? HYDK_VARIANT_YUVP : YUVPI ? HYDK_VARIANT_YUVPI : 0)) ||
         (FMT == HYDK_FMT_F32 && job.storage != (uint32_t)STORE))
         return; /* another template instance of this launch round owns this LF group */
     if ((int)(bid & 63) >= job.gcols * job.grows)
@@ -107,7 +110,7 @@
     const int coef_cl_lo = job.scheme == 0 ? 3 : job.scheme == 3 ? 0 : 1;
 
     /* (which loader a layout gets, from here to hfast, is restated by loader() in tests/pixel_layouts.py: change them together) */
-    const bool packed = !NV12 && !NV12I && !P016 && !P016I && job.pixel_stride == 3 &&
+    const bool packed = !NV12 && !NV12I && !P016 && !P016I && !YUVP && !YUVPI && job.pixel_stride == 3 &&
                         (const char *)job.src[1] == (const char *)job.src[0] + sizeof(sample_t) &&
                         (const char *)job.src[2] == (const char *)job.src[0] + 2 * sizeof(sample_t) &&
                         (((uintptr_t)job.src[0] | (uintptr_t)(job.row_stride * (long long)sizeof(sample_t))) & 3) == 0 &&
@@ -140,7 +143,7 @@
     /* NV12: a block row is two dwords of Y and, from chroma row y >> 1, two dwords of U, V pairs (a pair serves two pixels, and
      * the block's first column is even) when both planes and the pitch are dword multiples; anything else reads byte by byte */
     const bool nvrun = NV12 && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)job.row_stride) & 3) == 0;
-    const HydkYuvMatrix yuv = P016 || P016I ? hydk_yuv16_job_matrix(job.matrix) : hydk_yuv_matrix(NV12 || NV12I ? (int)job.matrix : 0);
+    const HydkYuvMatrix yuv = P016 || P016I ? hydk_yuv16_job_matrix(job.matrix) : hydk_yuv_matrix(NV12 || NV12I || YUVP || YUVPI ? (int)job.matrix : 0);
     /* P016, P016I: the same runs in 16-bit words — four dwords of Y, four dwords of pairs per chroma row, a dword per flank
      * pair — when both planes start on a dword and the pitch is an even number of words; anything else reads word by word */
     const bool prun = (P016 || P016I) && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1]) & 3) == 0 && (job.row_stride & 1) == 0;
@@ -150,11 +153,21 @@
      * That is taken only where this whole window of pairs lies inside the picture's chroma row and planes and pitch are dword
      * multiples; the picture's first and last chroma columns, odd widths and shifted bases fill the same window byte by byte
      * with the clamps, at use (phase A below).  pcx: the picture's chroma column of the block's first pair. */
-    const int pcx = NV12I || P016I ? job.pic_cx0 + ((px0 + ab * 8) >> 1) : 0;
+    const int pcx = NV12I || P016I || YUVPI ? job.pic_cx0 + ((px0 + ab * 8) >> 1) : 0;
     const bool irun = NV12I && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)job.row_stride) & 3) == 0 &&
                       (job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1;
     const bool pirun = P016I && prun && (job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1;
-    const bool fast = (NV12 ? nvrun : NV12I ? irun : P016 ? prun : P016I ? pirun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
+    /* YUVP: a block row is two dwords of Y and, from each chroma plane, the dword of four samples that serves its eight pixels
+     * (the block's chroma column is a multiple of 4) — two dwords of eight for 4:4:4 — when the three planes and both pitches
+     * are dword multiples; anything else reads byte by byte.  YUVPI: two dwords of Y, and of U and of V the near dword and the
+     * dword of the other row the filter mixes in (4:2:2 has no other row: far is near, loaded once) — the six dwords an 8-bit
+     * row holds — with the sample before and the one behind each as byte loads; taken only where that window lies inside the
+     * picture's chroma row (irun's test), the rest fills the same registers byte by byte with the clamps, at use. */
+    const int psx = YUVP || YUVPI ? hydk_planar_sx((int)job.sub) : 0, psy = YUVP || YUVPI ? hydk_planar_sy((int)job.sub) : 0;
+    const bool ylrun = (YUVP || YUVPI) && (((uintptr_t)job.src[0] | (uintptr_t)job.row_stride | (uintptr_t)job.src[1] |
+                                             (uintptr_t)job.src[2] | (uintptr_t)job.pixel_stride) & 3) == 0;
+    const bool ylirun = YUVPI && ylrun && (job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1;
+    const bool fast = (NV12 ? nvrun : NV12I ? irun : P016 ? prun : P016I ? pirun : YUVP ? ylrun : YUVPI ? ylirun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
     uint32_t nxt[kWords];
     /* NV12I: the window's first pair | its last pair << 16, of the near and of the far chroma row.  P016I (a pair is a dword):
      * the near row's first and last pair, then the far row's */
@@ -190,6 +203,65 @@
                     flank[1] = HYDK_GLOBAL(const uint32_t, pn + 16)[0];
                     flank[kFlank - 2] = bf;
                     flank[kFlank - 1] = HYDK_GLOBAL(const uint32_t, pf + 16)[0];
+                }
+            }
+            return;
+        }
+        if (YUVP) {
+            if (fast && s * 8 + ar < gh) {
+                const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
+                const char *py = (const char *)job.src[0] + y * job.row_stride + x;
+                const long long co = (y >> psy) * job.pixel_stride + (x >> psx);
+                const char *pu = (const char *)job.src[1] + co, *pv = (const char *)job.src[2] + co;
+                nxt[0] = HYDK_GLOBAL(const uint32_t, py)[0];
+                nxt[1] = HYDK_GLOBAL(const uint32_t, py)[1];
+                if (psx) {
+                    nxt[2] = HYDK_GLOBAL(const uint32_t, pu)[0];
+                    nxt[3] = HYDK_GLOBAL(const uint32_t, pv)[0];
+                } else {
+                    nxt[2] = HYDK_GLOBAL(const uint32_t, pu)[0];
+                    nxt[3] = HYDK_GLOBAL(const uint32_t, pu)[1];
+                    nxt[4] = HYDK_GLOBAL(const uint32_t, pv)[0];
+                    nxt[5] = HYDK_GLOBAL(const uint32_t, pv)[1];
+                }
+            }
+            return;
+        }
+        if (YUVPI) {
+            if (fast && s * 8 + ar < gh) {
+                const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
+                /* the far row in the picture's chroma rows, clamped there, and back relative to src[1] (4:2:2: the near row) */
+                const long long ny = y >> psy;
+                const long long fy = psy ? (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0 : ny;
+                const char *py = (const char *)job.src[0] + y * job.row_stride + x;
+                const long long on = ny * job.pixel_stride + (x >> 1), of = fy * job.pixel_stride + (x >> 1);
+                const char *un = (const char *)job.src[1] + on, *vn = (const char *)job.src[2] + on;
+                nxt[0] = HYDK_GLOBAL(const uint32_t, py)[0];
+                nxt[1] = HYDK_GLOBAL(const uint32_t, py)[1];
+                nxt[2] = HYDK_GLOBAL(const uint32_t, un)[0];
+                nxt[4] = HYDK_GLOBAL(const uint32_t, vn)[0];
+                /* before | behind << 8 of the near row, the same << 16 of the far row (left-sited chroma never looks before) */
+                uint32_t fu = (uint32_t)HYDK_GLOBAL(const uint8_t, un)[4] << 8, fv = (uint32_t)HYDK_GLOBAL(const uint8_t, vn)[4] << 8;
+                if (job.filter == HYDK_CHROMA_CENTRE) {
+                    fu |= HYDK_GLOBAL(const uint8_t, un - 1)[0];
+                    fv |= HYDK_GLOBAL(const uint8_t, vn - 1)[0];
+                }
+                if (psy) {
+                    const char *uf = (const char *)job.src[1] + of, *vf = (const char *)job.src[2] + of;
+                    nxt[3] = HYDK_GLOBAL(const uint32_t, uf)[0];
+                    nxt[5] = HYDK_GLOBAL(const uint32_t, vf)[0];
+                    uint32_t gu = (uint32_t)HYDK_GLOBAL(const uint8_t, uf)[4] << 8, gv = (uint32_t)HYDK_GLOBAL(const uint8_t, vf)[4] << 8;
+                    if (job.filter == HYDK_CHROMA_CENTRE) {
+                        gu |= HYDK_GLOBAL(const uint8_t, uf - 1)[0];
+                        gv |= HYDK_GLOBAL(const uint8_t, vf - 1)[0];
+                    }
+                    flank[0] = fu | gu << 16;
+                    flank[1] = fv | gv << 16;
+                } else {
+                    nxt[3] = nxt[2];
+                    nxt[5] = nxt[4];
+                    flank[0] = fu | fu << 16;
+                    flank[1] = fv | fv << 16;
                 }
             }
             return;
@@ -317,7 +389,7 @@
                     }
                 }
                 prefetch(s + 1);
-            } else if (fast || NV12I || P016I) {
+            } else if (fast || NV12I || P016I || YUVPI) {
                 /* NV12I rows that did not come as dwords — the picture's first and last chroma columns, a ragged last block,
                  * shifted bases, odd pitches — fill the same window byte by byte, here, every pair's column clamped to the
                  * picture's chroma row and the far row to its chroma rows: the picture's pair (0, 0) lies pic_cy0 rows and
@@ -386,8 +458,91 @@
                             flank[k] = 0;
                     }
                 }
+                /* YUVPI rows that did not come as dwords: each plane's window of six samples filled byte by byte, the same clamps,
+                 * into the registers the dword rows use.  The picture's sample (0, 0) lies pic_cy0 rows and pic_cx0 bytes before
+                 * src[1] and src[2] */
+                if (YUVPI && !fast) {
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        nxt[k] = 0;
+                    flank[0] = flank[1] = 0;
+                    if (row_ok) {
+                        const uint8_t *py = (const uint8_t *)job.src[0] + (long long)y * job.row_stride + x0;
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            if (i < nvalid)
+                                nxt[i >> 2] |= (uint32_t)py[i] << (8 * (i & 3));
+                        const long long ny = y >> psy;
+                        const long long fy = psy ? (long long)hydk_chroma_vy(2 * job.pic_cy0 + y, job.pic_ch) - job.pic_cy0 : ny;
+                        const long long on = ny * job.pixel_stride - job.pic_cx0, of = fy * job.pixel_stride - job.pic_cx0;
+                        const uint8_t *un = (const uint8_t *)job.src[1] + on, *uf = (const uint8_t *)job.src[1] + of;
+                        const uint8_t *vn = (const uint8_t *)job.src[2] + on, *vf = (const uint8_t *)job.src[2] + of;
+#pragma unroll
+                        for (int p = 0; p < 6; p++) {
+                            const int col = min(max(pcx - 1 + p, 0), job.pic_cw - 1);
+                            const uint32_t a = un[col], b = uf[col], c = vn[col], d = vf[col];
+                            if (p == 0 || p == 5) {
+                                flank[0] |= (a | b << 16) << (p ? 8 : 0);
+                                flank[1] |= (c | d << 16) << (p ? 8 : 0);
+                            } else {
+                                nxt[2] |= a << (8 * (p - 1));
+                                nxt[3] |= b << (8 * (p - 1));
+                                nxt[4] |= c << (8 * (p - 1));
+                                nxt[5] |= d << (8 * (p - 1));
+                            }
+                        }
+                    }
+                }
                 /* NV12: the eight pixels of the four fetched dwords, converted and packed as an interleaved RGB row has them */
                 uint32_t cvt[kWords];
+                if (YUVP) { /* a pixel's U and V: byte i >> 1 of one dword each, or (4:4:4) byte i of two dwords each */
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        cvt[k] = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        const uint32_t u2 = (nxt[2] >> (8 * (i >> 1))) & 0xFF, v2 = (nxt[3] >> (8 * (i >> 1))) & 0xFF;
+                        const uint32_t u4 = (nxt[2 + (i >> 2)] >> (8 * (i & 3))) & 0xFF, v4 = (nxt[4 + (i >> 2)] >> (8 * (i & 3))) & 0xFF;
+                        uint32_t rgb[3];
+                        hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, psx ? u2 : u4, psx ? v2 : v4, rgb);
+#pragma unroll
+                        for (int ch = 0; ch < 3; ch++) {
+                            const int si = i * 3 + ch;
+                            cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
+                        }
+                    }
+                }
+                if (YUVPI) {
+                    /* NV12I's vertical mix, horizontal mix, conversion and pack, the window's samples taken plane by plane */
+                    uint32_t vu[6], vv[6];
+#pragma unroll
+                    for (int p = 0; p < 6; p++) {
+                        const int sh = 8 * (p - 1);
+                        const uint32_t a = p == 0 ? flank[0] : p == 5 ? flank[0] >> 8 : nxt[2] >> sh;
+                        const uint32_t b = p == 0 ? flank[0] >> 16 : p == 5 ? flank[0] >> 24 : nxt[3] >> sh;
+                        const uint32_t c = p == 0 ? flank[1] : p == 5 ? flank[1] >> 8 : nxt[4] >> sh;
+                        const uint32_t d = p == 0 ? flank[1] >> 16 : p == 5 ? flank[1] >> 24 : nxt[5] >> sh;
+                        vu[p] = hydk_chroma_vmix(a & 0xFF, b & 0xFF);
+                        vv[p] = hydk_chroma_vmix(c & 0xFF, d & 0xFF);
+                    }
+                    const int filter = (int)job.filter;
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        cvt[k] = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        const int j = 1 + (i >> 1), hc = (i & 1) ? j + 1 : j - 1, hl = j + (i & 1);
+                        const uint32_t u = hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]);
+                        const uint32_t v = hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]);
+                        uint32_t rgb[3];
+                        hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, u, v, rgb);
+#pragma unroll
+                        for (int ch = 0; ch < 3; ch++) {
+                            const int si = i * 3 + ch;
+                            cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
+                        }
+                    }
+                }
                 if (P016) { /* eight pixels of four Y dwords and four pair dwords (U | V << 16), as an interleaved RGB16 row */
 #pragma unroll
                     for (int k = 0; k < kWords; k++)
@@ -475,7 +630,7 @@
                         }
                     }
                 }
-                uint32_t(&w)[kWords] = NV12 || NV12I || P016 || P016I ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
+                uint32_t(&w)[kWords] = NV12 || NV12I || P016 || P016I || YUVP || YUVPI ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
                 /* which form of the transfer curve this wavefront's 16-bit samples need (wave-uniform) */
                 int curve = kCurveBoth;
                 if (FMT == HYDK_FMT_U16 && !LUTS) {
@@ -589,7 +744,7 @@
                         row_to_xyb(std::integral_constant<int, kCurveNone>());
                     else
                         row_to_xyb(std::integral_constant<int, kCurveBoth>());
-                    if (NV12I || P016I) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
+                    if (NV12I || P016I || YUVPI) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
 #pragma unroll
                         for (int i = 0; i < 8; i++)
                             if (i >= nvalid)
@@ -609,9 +764,12 @@
                 for (int i = 0; i < 8; i++) {
                     xv[i] = yv[i] = bv[i] = 0.0f; /* edge padding is XYB = 0 (format.c:182-191) */
                     if (i < nvalid) {
-                        const long long off = (long long)y * job.row_stride + (long long)(x0 + i) * job.pixel_stride;
-                        /* (NV12: the pixel's Y; its U and V sit in chroma row y >> 1 at the even byte x & ~1 and behind it) */
-                        const long long offc = NV12 || P016 ? (long long)(y >> 1) * job.row_stride + (long long)((x0 + i) & ~1) : off;
+                        const long long off = (long long)y * job.row_stride + (long long)(x0 + i) * (YUVP ? 1ll : job.pixel_stride);
+                        /* (NV12: the pixel's Y; its U and V sit in chroma row y >> 1 at the even byte x & ~1 and behind it.
+                         * YUVP: in row y >> sy, byte x >> sx of their own planes, whose pitch the pixel stride carries) */
+                        const long long offc = YUVP            ? (long long)(y >> psy) * job.pixel_stride + (long long)((x0 + i) >> psx)
+                                               : NV12 || P016 ? (long long)(y >> 1) * job.row_stride + (long long)((x0 + i) & ~1)
+                                                              : off;
                         const sample_t sr = ((const sample_t *)job.src[0])[off];
                         const sample_t sg = ((const sample_t *)job.src[1])[offc];
                         const sample_t sb = ((const sample_t *)job.src[2])[offc];
@@ -627,7 +785,7 @@
                             float_pixel(fr, fg, fb, xv[i], yv[i], bv[i]);
                         } else {
                             uint32_t rgb[3] = {(uint32_t)sr, (uint32_t)sg, (uint32_t)sb};
-                            if (NV12)
+                            if (NV12 || YUVP)
                                 hydk_yuv_to_rgb(yuv, (uint32_t)sr, (uint32_t)sg, (uint32_t)sb, rgb);
                             if (P016)
                                 hydk_yuv16_to_rgb(yuv, (uint32_t)sr, (uint32_t)sg, (uint32_t)sb, rgb);

@@ -613,11 +613,14 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
  * The P016 and P016I instances are k_transform_tokenize_p016's — kernel symbols of their own: what is asked of "the 16-bit
  * instances" by symbol name (one per XYB mode, their LDS under HYDK_K1_CHANSEQ) keeps meaning the RGB16 ones.  Both kernels
  * are the one text of k1_transform_body.h, included into each: a shared __device__ function, inlined, compiled the existing
- * instances to other code than they had. */
+ * instances to other code than they had.
+ * The 8-bit class's planar YCbCr forms, HYDK_STORE_YUVP and HYDK_STORE_YUVPI (three planes, 4:2:0, 4:2:2 and 4:4:4; hydk_chroma.h),
+ * are k_transform_tokenize_planar's, for the same reason: "the 8-bit instances" by symbol name stay what they were. */
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
     static_assert(STORE != HYDK_STORE_P016 && STORE != HYDK_STORE_P016I, "the P016 instances are k_transform_tokenize_p016's");
+    static_assert(STORE != HYDK_STORE_YUVP && STORE != HYDK_STORE_YUVPI, "the planar instances are k_transform_tokenize_planar's");
 #include "k1_transform_body.h"
 }
 
@@ -628,6 +631,15 @@ __global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_p016(const H
                                                                          uint2 *part_info, int plog) {
     static_assert(STORE == HYDK_STORE_P016 || STORE == HYDK_STORE_P016I, "the RGB16 instances are k_transform_tokenize's");
     constexpr int FMT = HYDK_FMT_U16;
+#include "k1_transform_body.h"
+}
+
+/* Planar YCbCr, nearest (YUVP) and interpolated (YUVPI): four waves per SIMD as the P016 instances, for the same footprint. */
+template <int XMODE, int STORE>
+__global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_planar(const HydkLfJob *__restrict__ jobs, uint32_t *status,
+                                                                           uint2 *part_info, int plog) {
+    static_assert(STORE == HYDK_STORE_YUVP || STORE == HYDK_STORE_YUVPI, "RGB8, NV12 and NV12I are k_transform_tokenize's");
+    constexpr int FMT = HYDK_FMT_U8;
 #include "k1_transform_body.h"
 }
 
@@ -2363,7 +2375,8 @@ namespace hydk {
 
 /* One launch per template instance that owns at least one LF group of this round; an instance
  * returns at once for the LF groups of another sample format.  fmt_mask: bits 0, 1 the integer classes' own samples, bits
- * 2 + HYDK_STORE_* the storage forms: the float class's three, NV12 and NV12I of the 8-bit class, P016 and P016I of the 16-bit. */
+ * 2 + HYDK_STORE_* the storage forms: the float class's three, NV12, NV12I, YUVP and YUVPI of the 8-bit class, P016 and P016I of
+ * the 16-bit. */
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream) {
     const dim3 grid((num_slots * HYDK_GROUPS_PER_LFG) << plog), block(kThreads);
@@ -2431,6 +2444,19 @@ hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt
     HYDK_LAUNCH_K1_P016(HYDK_STORE_P016)
     HYDK_LAUNCH_K1_P016(HYDK_STORE_P016I)
 #undef HYDK_LAUNCH_K1_P016
+    /* planar YCbCr of the 8-bit class, nearest and interpolated: three modes each, under their own kernel name */
+#define HYDK_LAUNCH_K1_PLANAR(STORE)                                                                                                          \
+    if (fmt_mask & (1u << (HYDK_FMT_F32 + (STORE)))) {                                                                                        \
+        if (xyb_arith(xmode) == kXybFastRcp)                                                                                                  \
+            hipLaunchKernelGGL((k_transform_tokenize_planar<kXybFastRcp, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog); \
+        else if (xyb_arith(xmode) == kXybIeeeDiv)                                                                                             \
+            hipLaunchKernelGGL((k_transform_tokenize_planar<kXybIeeeDiv, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog); \
+        else                                                                                                                                  \
+            hipLaunchKernelGGL((k_transform_tokenize_planar<kXybGather, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog);  \
+    }
+    HYDK_LAUNCH_K1_PLANAR(HYDK_STORE_YUVP)
+    HYDK_LAUNCH_K1_PLANAR(HYDK_STORE_YUVPI)
+#undef HYDK_LAUNCH_K1_PLANAR
 #undef HYDK_LAUNCH_K1_MODES
 #undef HYDK_LAUNCH_K1
     if (plog)
@@ -2475,6 +2501,20 @@ hipError_t transform_footprint(int fmt, int storage, int xmode, int *lds_bytes, 
             fn = (const void *)k_transform_tokenize_p016<kXybIeeeDiv, HYDK_STORE_P016I>;
         else
             fn = (const void *)k_transform_tokenize_p016<kXybGather, HYDK_STORE_P016I>;
+    } else if (fmt == HYDK_FMT_U8 && storage == HYDK_STORE_YUVP) {
+        if (xmode == kXybFastRcp)
+            fn = (const void *)k_transform_tokenize_planar<kXybFastRcp, HYDK_STORE_YUVP>;
+        else if (xmode == kXybIeeeDiv)
+            fn = (const void *)k_transform_tokenize_planar<kXybIeeeDiv, HYDK_STORE_YUVP>;
+        else
+            fn = (const void *)k_transform_tokenize_planar<kXybGather, HYDK_STORE_YUVP>;
+    } else if (fmt == HYDK_FMT_U8 && storage == HYDK_STORE_YUVPI) {
+        if (xmode == kXybFastRcp)
+            fn = (const void *)k_transform_tokenize_planar<kXybFastRcp, HYDK_STORE_YUVPI>;
+        else if (xmode == kXybIeeeDiv)
+            fn = (const void *)k_transform_tokenize_planar<kXybIeeeDiv, HYDK_STORE_YUVPI>;
+        else
+            fn = (const void *)k_transform_tokenize_planar<kXybGather, HYDK_STORE_YUVPI>;
     } else if (fmt == HYDK_FMT_U8) {
         if (xmode == kXybFastRcp)
             HYDK_K1_PTR(HYDK_FMT_U8, kXybFastRcp);

@@ -238,6 +238,8 @@ HYDRIUM_EXPORT int hydamd_encode_batch(HydAmdBatch *b, int frames, const void *c
     for (int f = 0; f < frames; f++)
         if (!hyd_fmt_layout_ok(sample_fmt, src + 3 * f, pixel_stride))
             return hyd_batchrun_fail(r, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmt), NULL);
+    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, b->W))
+        return hyd_batchrun_fail(r, HYD_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG, NULL);
     int st = hyd_batchrun_busy(r);
     if (st)
         return st;

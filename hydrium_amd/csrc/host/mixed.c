@@ -482,6 +482,9 @@ HYDRIUM_EXPORT int hydamd_encode_mixed_formats(HydAmdMixed *m, int frames, const
     for (int f = 0; f < frames; f++)
         if (!hyd_fmt_layout_ok(sample_fmts[f], images[f].src, images[f].pixel_stride))
             return hyd_batchrun_fail(r, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmts[f]), NULL);
+    for (int f = 0; f < frames; f++)
+        if (!hyd_fmt_pitch_ok(sample_fmts[f], images[f].pixel_stride, images[f].width))
+            return hyd_batchrun_fail(r, HYD_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG, NULL);
     int st = hyd_batchrun_busy(r);
     if (st)
         return st;

@@ -156,11 +156,14 @@ HYDRIUM_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *
     if (!hyd_fmt_is_device(sample_fmt))
         return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
     /* a shard's buffer is only promised to hold its own rows, and the filter would read a neighbouring shard's chroma row */
-    if (hyd_fmt_is_yuv420_interp(sample_fmt))
+    /* (a planar 4:2:2 window has no other row, but its columns cross into an LF group that another shard owns) */
+    if (hyd_fmt_is_yuv420_interp(sample_fmt) || hyd_fmt_is_planar_interp(sample_fmt))
         return fail(m, HYD_API_ERROR, HYD_FMT_NV12_SHARDED_MSG, NULL);
     for (int d = 0; d < f->n; d++)
         if (src[3 * d + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * d, pixel_stride))
             return fail(m, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmt), NULL);
+    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, m->md.width))
+        return fail(m, HYD_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG, NULL);
     if (m->in_flight)
         return fail(m, HYD_API_ERROR, "a frame is in flight: hydamd_multi_result first", NULL);
     const size_t W = m->md.width, H = m->md.height;

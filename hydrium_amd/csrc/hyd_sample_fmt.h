@@ -19,6 +19,14 @@
  * 8-bit NV12 family above.  Depth 1, 2, 3 (P010, P012, P016: 80 ..., 144 ..., 208 ...) name the same two planes in 16-bit WORDS
  * holding 10, 12 or 16 significant bits, MSB-aligned: a storage form of the 16-BIT class (hip/hydk_yuv16.h).  src[2] ==
  * src[1] + 2 bytes, the pixel stride is 1 and the row stride is the pitch of both planes in words.  64 ... 79 name nothing.
+ *
+ * 512 ... 551 name PLANAR YCbCr in device memory, 8 bits a sample in three planes of their own: sample format = 512 + matrix +
+ * 4 * subsampling + 16 * filter.  Subsampling 0 is 4:2:0 (I420; YV12 with src[1] and src[2] swapped), 1 is 4:2:2 (I422), 2 is
+ * 4:4:4 (I444, filter 0 only); 3 names nothing.  Matrix and filter are the NV12 family's.  A storage form of the 8-BIT class
+ * as NV12 is.  src[0] is the first Y sample, src[1] and src[2] the first U and V samples — independent pointers; the row
+ * stride is the pitch of the Y plane, whose pixel stride is 1 by definition, and THE PIXEL STRIDE IS THE ONE PITCH OF BOTH
+ * CHROMA PLANES, in bytes, of either sign (hyd_fmt_pitch_ok).  The chroma planes are cw x ch: cw = ceil(W / 2) for 4:2:0 and
+ * 4:2:2 and W for 4:4:4, ch = ceil(H / 2) for 4:2:0 and H otherwise.  + 64 * depth is kept for deeper planes and names nothing.
  */
 #ifndef HYD_SAMPLE_FMT_H_
 #define HYD_SAMPLE_FMT_H_
@@ -81,6 +89,38 @@
 #define HYD_FMT_P016L_BT601 242
 #define HYD_FMT_P016L_BT601_FULL 243
 #define HYD_FMT_P016_DEPTHS 3
+/* planar YCbCr, 8 bits in three planes: 512 + matrix + 4 * subsampling (0 4:2:0, 1 4:2:2, 2 4:4:4) + 16 * filter */
+#define HYD_FMT_I420_BT709 512
+#define HYD_FMT_I420_BT709_FULL 513
+#define HYD_FMT_I420_BT601 514
+#define HYD_FMT_I420_BT601_FULL 515
+#define HYD_FMT_I422_BT709 516
+#define HYD_FMT_I422_BT709_FULL 517
+#define HYD_FMT_I422_BT601 518
+#define HYD_FMT_I422_BT601_FULL 519
+#define HYD_FMT_I444_BT709 520
+#define HYD_FMT_I444_BT709_FULL 521
+#define HYD_FMT_I444_BT601 522
+#define HYD_FMT_I444_BT601_FULL 523
+#define HYD_FMT_I420C_BT709 528
+#define HYD_FMT_I420C_BT709_FULL 529
+#define HYD_FMT_I420C_BT601 530
+#define HYD_FMT_I420C_BT601_FULL 531
+#define HYD_FMT_I422C_BT709 532
+#define HYD_FMT_I422C_BT709_FULL 533
+#define HYD_FMT_I422C_BT601 534
+#define HYD_FMT_I422C_BT601_FULL 535
+#define HYD_FMT_I420L_BT709 544
+#define HYD_FMT_I420L_BT709_FULL 545
+#define HYD_FMT_I420L_BT601 546
+#define HYD_FMT_I420L_BT601_FULL 547
+#define HYD_FMT_I422L_BT709 548
+#define HYD_FMT_I422L_BT709_FULL 549
+#define HYD_FMT_I422L_BT601 550
+#define HYD_FMT_I422L_BT601_FULL 551
+#define HYD_FMT_PLANAR_420 0
+#define HYD_FMT_PLANAR_422 1
+#define HYD_FMT_PLANAR_444 2
 
 /* YCbCr 4:2:0 in two planes with nearest-neighbour chroma, and which of the four matrices of hip/hydk_yuv.h (0 ... 3) */
 static inline int hyd_fmt_is_nv12(int fmt) { return fmt >= HYD_FMT_NV12_BT709 && fmt <= HYD_FMT_NV12_BT601_FULL; }
@@ -109,8 +149,25 @@ static inline int hyd_fmt_is_p016_interp(int fmt) { return hyd_fmt_is_p016_famil
 static inline int hyd_fmt_is_yuv420(int fmt) { return hyd_fmt_is_nv12_family(fmt) || hyd_fmt_is_p016_family(fmt); }
 static inline int hyd_fmt_is_yuv420_interp(int fmt) { return hyd_fmt_is_nv12_interp(fmt) || hyd_fmt_is_p016_interp(fmt); }
 
+
+/* the PLANAR family, twenty-eight numbers: its subsampling (HYD_FMT_PLANAR_*), filter and matrix, and the sixteen whose chroma
+ * is interpolated.  4:4:4 has nothing to interpolate: filter 0 only */
+static inline int hyd_fmt_planar_sub(int fmt) { return ((fmt - HYD_FMT_I420_BT709) >> 2) & 3; }
+static inline int hyd_fmt_planar_filter(int fmt) { return (fmt - HYD_FMT_I420_BT709) >> 4; }
+static inline int hyd_fmt_planar_matrix(int fmt) { return (fmt - HYD_FMT_I420_BT709) & 3; }
+static inline int hyd_fmt_is_planar_yuv(int fmt) {
+    return fmt >= HYD_FMT_I420_BT709 && fmt <= HYD_FMT_I422L_BT601_FULL && hyd_fmt_planar_sub(fmt) <= HYD_FMT_PLANAR_444 &&
+           (hyd_fmt_planar_sub(fmt) != HYD_FMT_PLANAR_444 || hyd_fmt_planar_filter(fmt) == 0);
+}
+static inline int hyd_fmt_is_planar_interp(int fmt) { return hyd_fmt_is_planar_yuv(fmt) && hyd_fmt_planar_filter(fmt) != 0; }
+/* log2 of the pixels a chroma sample spans across and down */
+static inline int hyd_fmt_planar_sx(int fmt) { return hyd_fmt_planar_sub(fmt) != HYD_FMT_PLANAR_444; }
+static inline int hyd_fmt_planar_sy(int fmt) { return hyd_fmt_planar_sub(fmt) == HYD_FMT_PLANAR_420; }
+
 /* what an entry point that reads DEVICE pixels takes */
-static inline int hyd_fmt_is_device(int fmt) { return (fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_BFLOAT16) || hyd_fmt_is_yuv420(fmt); }
+static inline int hyd_fmt_is_device(int fmt) {
+    return (fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_BFLOAT16) || hyd_fmt_is_yuv420(fmt) || hyd_fmt_is_planar_yuv(fmt);
+}
 /* what an entry point that reads HOST pixels takes: the reference's three */
 static inline int hyd_fmt_is_host(int fmt) { return fmt >= HYD_FMT_UINT8 && fmt <= HYD_FMT_FLOAT32; }
 /* float class: 8-byte token records, 72 histogram bins, the non-finite check */
@@ -139,7 +196,7 @@ static inline size_t hyd_fmt_bytes(int fmt) {
     case HYD_FMT_FLOAT32:
         return 4;
     default:
-        return hyd_fmt_is_p016_family(fmt) ? 2 : 0;
+        return hyd_fmt_is_p016_family(fmt) ? 2 : hyd_fmt_is_planar_yuv(fmt) ? 1 : 0;
     }
 }
 
@@ -156,19 +213,37 @@ static inline int hyd_fmt_layout_ok(int fmt, const void *const src[3], ptrdiff_t
                (((size_t)src[0] | (size_t)src[1]) & 1) == 0;
     return !hyd_fmt_is_nv12_family(fmt) || (pixel_stride == 1 && (const char *)src[2] == (const char *)src[1] + 1);
 }
+/* The planar family has no layout to hold (three free pointers), but its pixel_stride argument is the chroma planes' pitch: a
+ * pitch shorter than a chroma row of the picture the call names, `width` pixels across — the habitual pixel_stride 1 — fails
+ * with HYD_FMT_PLANAR_PITCH_MSG before anything is enqueued.  Every other format passes. */
+#define HYD_FMT_PLANAR_PITCH_MSG "planar YCbCr wants the chroma planes' pitch in pixel_stride"
+static inline int hyd_fmt_pitch_ok(int fmt, ptrdiff_t pixel_stride, size_t width) {
+    if (!hyd_fmt_is_planar_yuv(fmt))
+        return 1;
+    const size_t pitch = pixel_stride < 0 ? (size_t)0 - (size_t)pixel_stride : (size_t)pixel_stride;
+    return pitch >= (hyd_fmt_planar_sx(fmt) ? (width + 1) >> 1 : width);
+}
 /* what an entry point says when hyd_fmt_layout_ok is 0 */
 static inline const char *hyd_fmt_layout_msg(int fmt) { return hyd_fmt_is_p016_family(fmt) ? HYD_FMT_P016_LAYOUT_MSG : HYD_FMT_NV12_LAYOUT_MSG; }
 
 /* The three origin pointers of the sub-rectangle at pixel (x0, y0) of a picture of a device format — an LF group, a tile, a
  * shard's first row.  Strides are in samples.  NV12: the chroma plane has a row for every two picture rows and two bytes for
  * every two columns, so its origin is row y0 / 2, byte x0; x0 and y0 must be even (every origin the library computes is a
- * multiple of 256).  The P016 family: the same in 16-bit words. */
+ * multiple of 256).  The P016 family: the same in 16-bit words.  The planar family: Y at row y0, byte x0 of its plane; U and V
+ * at row y0 >> sy, byte x0 >> sx of theirs, whose pitch is pixel_stride; x0 must be even, and y0 for 4:2:0. */
 static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride, size_t x0,
                                   size_t y0, const void *origin[3]) {
     if (hyd_fmt_is_yuv420(fmt)) {
         const ptrdiff_t bytes = (ptrdiff_t)hyd_fmt_bytes(fmt);
         const ptrdiff_t chroma = ((ptrdiff_t)(y0 / 2) * row_stride + (ptrdiff_t)x0) * bytes;
         origin[0] = (const char *)src[0] + ((ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0) * bytes;
+        origin[1] = (const char *)src[1] + chroma;
+        origin[2] = (const char *)src[2] + chroma;
+        return;
+    }
+    if (hyd_fmt_is_planar_yuv(fmt)) {
+        const ptrdiff_t chroma = (ptrdiff_t)(y0 >> hyd_fmt_planar_sy(fmt)) * pixel_stride + (ptrdiff_t)(x0 >> hyd_fmt_planar_sx(fmt));
+        origin[0] = (const char *)src[0] + ((ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0);
         origin[1] = (const char *)src[1] + chroma;
         origin[2] = (const char *)src[2] + chroma;
         return;

@@ -50,6 +50,31 @@ for _bits, _depth in P016_DEPTHS.items():
             globals()[f"P0{_bits}{_infix}_{_name}"] = 16 + _matrix + 16 * _filter + 64 * _depth
 P010_FORMATS, P012_FORMATS, P016_FORMATS = ((80, 81, 82, 83), (144, 145, 146, 147), (208, 209, 210, 211))  # nearest chroma
 P016_FAMILY = tuple(16 + m + 16 * f + 64 * d for d in (1, 2, 3) for f in (0, 1, 2) for m in (0, 1, 2, 3))
+# device pixels only (HYDAMD_I420_*, HYDAMD_I422_*, HYDAMD_I444_* and their C / L forms): PLANAR YCbCr, 8 bits in three planes of
+# their own — 512 + matrix + 4 * subsampling + 16 * filter; 4:4:4 has nearest chroma only
+PLANAR_SUBSAMPLINGS = {"420": 0, "422": 1, "444": 2}
+for _sub_name, _sub in PLANAR_SUBSAMPLINGS.items():
+    for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
+        if _sub == 2 and _filter:
+            continue
+        for _name, _matrix in (("BT709", 0), ("BT709_FULL", 1), ("BT601", 2), ("BT601_FULL", 3)):
+            globals()[f"I{_sub_name}{_infix}_{_name}"] = 512 + _matrix + 4 * _sub + 16 * _filter
+PLANAR_FAMILY = tuple(512 + m + 4 * s + 16 * f for f in (0, 1, 2) for s in (0, 1, 2) for m in (0, 1, 2, 3) if not (s == 2 and f))
+
+
+def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
+    """The sample format of a planar YCbCr picture: ``matrix`` one of NV12_FORMATS (the matrix and range), ``subsampling``
+    "420", "422" or "444", ``chroma`` None / "nearest", "centre" or "left" ("444" has nothing to interpolate)."""
+    if int(matrix) not in NV12_FORMATS:
+        raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL")
+    if str(subsampling) not in PLANAR_SUBSAMPLINGS:
+        raise ValueError("subsampling is '420', '422' or '444'")
+    if chroma is not None and chroma not in CHROMA_FILTERS:
+        raise ValueError("chroma is 'nearest', 'centre' or 'left'")
+    sub, filt = PLANAR_SUBSAMPLINGS[str(subsampling)], CHROMA_FILTERS[chroma or "nearest"]
+    if sub == 2 and filt:
+        raise ValueError("4:4:4 has a chroma sample for every pixel: no chroma filter")
+    return 512 + (int(matrix) - NV12_BT709) + 4 * sub + 16 * filt
 
 
 class Nv12:
@@ -97,6 +122,8 @@ class Nv12:
     @property
     def shape(self):
         return (self.height, self.width, 3)
+
+    pixel_stride = 1  # what the C API's pixel_stride argument takes for this picture
 
     def pointers(self):
         """src[0 ... 2] of the C API: Y, U, V = U + 1."""
@@ -170,10 +197,48 @@ class P016(Nv12):
         return [self.y.data_ptr(), u, u + 2]
 
 
+class PlanarYuv(Nv12):
+    """A planar YCbCr picture in device memory — I420, I422 or I444: 8-bit Y, U and V planes of their own — accepted wherever
+    an Nv12 object is.
+
+    ``y``: uint8 tensor (H, W) with unit column stride.  ``u``, ``v``: uint8 tensors (ch, cw) with unit column stride and ONE
+    row stride, which need not be half of y's; they may sit in separate allocations, and swapped they read YV12.  cw =
+    ceil(W / 2) for "420" and "422" and W for "444"; ch = ceil(H / 2) for "420" and H otherwise.  ``matrix``: one of
+    NV12_FORMATS; ``subsampling``: "420", "422" or "444"; ``chroma``: as Nv12's ("444": nearest only).  A crop starts on even
+    x, and on even y for "420".  The C API takes the chroma planes' pitch in its pixel_stride argument."""
+
+    def __init__(self, y, u, v, matrix: int = NV12_BT709, subsampling="420", chroma=None):
+        fmt = planar_fmt(matrix, subsampling, chroma)
+        sub = PLANAR_SUBSAMPLINGS[str(subsampling)]
+        names = [str(t.dtype).rpartition(".")[2] for t in (y, u, v)]
+        if any(t.element_size() != 1 or t.dim() != 2 for t in (y, u, v)) or any(n.startswith(("float", "bool")) for n in names):
+            raise ValueError("planar YCbCr planes are 8-bit: y (H, W), u and v (ch, cw)")
+        h, w = y.shape
+        cw, ch = (w if sub == 2 else -(-w // 2)), (-(-h // 2) if sub == 0 else h)
+        if h < 1 or w < 1 or tuple(u.shape) != (ch, cw) or tuple(v.shape) != (ch, cw):
+            raise ValueError(f"the chroma planes of an (H, W) picture of subsampling {subsampling} are ({ch}, {cw})")
+        if y.stride(1) != 1 or u.stride(1) != 1 or v.stride(1) != 1:
+            raise ValueError("planar YCbCr planes have unit column stride")
+        if ch > 1 and u.stride(0) != v.stride(0):
+            raise ValueError("the U and V planes share one pitch")
+        self.y, self.u, self.v, self.sample_fmt = y, u, v, fmt
+        self.height, self.width = int(h), int(w)
+        self.pitch = int(y.stride(0)) if h > 1 else max(int(y.stride(0)), w)
+        self.pixel_stride = int(u.stride(0)) if ch > 1 else max(int(u.stride(0)), int(v.stride(0)), cw)  # the chroma pitch
+
+    @classmethod
+    def from_surface(cls, *args, **kwargs):
+        raise TypeError("PlanarYuv takes its three planes")
+
+    def pointers(self):
+        """src[0 ... 2] of the C API: Y, U, V."""
+        return [self.y.data_ptr(), self.u.data_ptr(), self.v.data_ptr()]
+
+
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
     float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
-    An Nv12 or P016 object: its own format."""
+    An Nv12, P016 or PlanarYuv object: its own format."""
     if isinstance(t, Nv12):
         return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]
@@ -556,7 +621,7 @@ class DeviceContext:
         if num_slots_check and n > self.max_lf_groups:
             raise ValueError("context has too few LF-group slots for this image")
         if isinstance(img, Nv12):
-            self._ck(self.d.hydamd_encode_image(self.h, (C.c_void_p * 3)(*img.pointers()), img.pitch, 1, fmt, w, h))
+            self._ck(self.d.hydamd_encode_image(self.h, (C.c_void_p * 3)(*img.pointers()), img.pitch, img.pixel_stride, fmt, w, h))
             return n
         isz = img.element_size()
         if not getattr(self, "per_lf_group_calls", False):
@@ -593,10 +658,10 @@ class DeviceContext:
         ptrs = []
         if isinstance(imgs[0], Nv12):
             for t in imgs:
-                assert isinstance(t, Nv12) and (t.shape, t.pitch, t.sample_fmt) == (imgs[0].shape, imgs[0].pitch, fmt)
+                assert isinstance(t, Nv12) and (t.shape, t.pitch, t.pixel_stride, t.sample_fmt) == (imgs[0].shape, imgs[0].pitch, imgs[0].pixel_stride, fmt)
                 ptrs += t.pointers()
             arr = (C.c_void_p * len(ptrs))(*ptrs)
-            self._ck(self.d.hydamd_encode_image_batch(self.h, len(imgs), arr, imgs[0].pitch, 1, fmt, w, h))
+            self._ck(self.d.hydamd_encode_image_batch(self.h, len(imgs), arr, imgs[0].pitch, imgs[0].pixel_stride, fmt, w, h))
             return n * len(imgs)
         isz = imgs[0].element_size()
         for t in imgs:
@@ -956,11 +1021,11 @@ class MultiFrame:
         if origins and isinstance(origins[0], Nv12):
             flat, o0 = [], origins[0]
             for o in origins:
-                if not isinstance(o, Nv12) or (o.pitch, o.sample_fmt) != (o0.pitch, o0.sample_fmt):
+                if not isinstance(o, Nv12) or (o.pitch, o.pixel_stride, o.sample_fmt) != (o0.pitch, o0.pixel_stride, o0.sample_fmt):
                     raise ValueError("the shards of a frame share one layout and sample format")
                 flat += o.pointers()
             arr = (C.c_void_p * len(flat))(*flat)
-            self._ck(self.d.hydamd_encode_image_multi(self.h, arr, o0.pitch, 1, o0.sample_fmt, assembling_shard))
+            self._ck(self.d.hydamd_encode_image_multi(self.h, arr, o0.pitch, o0.pixel_stride, o0.sample_fmt, assembling_shard))
             return
         ptrs, isz, fmt = [], None, None
         for o in origins:
@@ -999,8 +1064,8 @@ def _read_image(img, row_stride: Optional[int] = None, pixel_stride: Optional[in
     interleaved (H, W, C >= 3) tensor, a triple of (H, W) plane tensors — these say everything themselves — or device
     addresses: three of them, with the caller's strides and format and no size (height and width None), or
     (ptrs, row_stride, pixel_stride, width, height) with the caller's format."""
-    if isinstance(img, Nv12):  # V one byte behind U, pixel stride 1, the pitch of both planes
-        return img.pointers(), img.pitch, 1, img.height, img.width, img.sample_fmt
+    if isinstance(img, Nv12):  # V one byte behind U, pixel stride 1, the pitch of both planes (PlanarYuv: the chroma planes' pitch)
+        return img.pointers(), img.pitch, img.pixel_stride, img.height, img.width, img.sample_fmt
     if hasattr(img, "data_ptr"):
         p, isz, shape = img.data_ptr(), img.element_size(), img.shape
         return [p, p + isz, p + 2 * isz], img.stride(0), img.stride(1), shape[0], shape[1], sample_fmt_of(img)
@@ -1233,7 +1298,7 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
             elif fmt != sample_fmt:
                 raise ValueError("the images of a batch share one sample format")
         elif isinstance(sample_fmts, list) and fmt != given:
-            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FAMILY + P016_FAMILY:
+            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FAMILY + P016_FAMILY + PLANAR_FAMILY:
                 raise ValueError("sample_fmts disagrees with a tensor's dtype")
             fmt = given  # not a format at all: the library refuses it (HYD_API_ERROR), nothing is enqueued
         fmts.append(fmt)

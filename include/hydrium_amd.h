@@ -130,7 +130,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * hydamd_encode_image_tiled, hydamd_encode_image_multi and hydamd_debug_transform_footprint.  Entry points that read HOST
  * pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse both with "Invalid Sample Format", as they and every
  * other entry point refuse anything that is neither 0..4 nor of the NV12 family (16..19, 32..35, 48..51, below) nor of the
- * P010 / P012 / P016 family (80..83, 96..99, 112..115, 144..147, 160..163, 176..179, 208..211, 224..227, 240..243, below).
+ * P010 / P012 / P016 family (80..83, 96..99, 112..115, 144..147, 160..163, 176..179, 208..211, 224..227, 240..243, below)
+ * nor of the planar YCbCr family (512..523, 528..535, 544..551, below).
  */
 #define HYDAMD_FLOAT16 3
 #define HYDAMD_BFLOAT16 4
@@ -173,8 +174,9 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * their neighbours' chroma: this cannot be checked.
  * Entry points that read HOST pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse all four with "Invalid
  * Sample Format".
- * Out of scope: NV21, planar I420, 4:2:2 and 4:4:4; host-pointer NV12; any colour description other than the four above.
- * (10- to 16-bit P010 / P012 / P016 have a fixed-point derivation and formats of their own, further down.)
+ * Out of scope: NV21; host-pointer NV12; any colour description other than the four above.
+ * (10- to 16-bit P010 / P012 / P016 have a fixed-point derivation and formats of their own, further down; so have planar
+ * I420, I422 and I444.)
  */
 #define HYDAMD_NV12_BT709 16
 #define HYDAMD_NV12_BT709_FULL 17
@@ -208,7 +210,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  *
  * Refused: hydamd_encode_image_multi ("interpolated chroma is not sharded: ..." — a shard's buffer is only promised to hold
  * its own rows, and the filter would read a neighbouring shard's chroma row), and the host-pointer entry points as for NV12.
- * Out of scope: top-left siting (BT.2020), other layouts (NV21, I420, 4:2:2, 4:4:4), cross-shard chroma, host-pointer input.
+ * Out of scope: top-left siting (BT.2020), other two-plane layouts (NV21, NV16), cross-shard chroma, host-pointer input.
+ * (Planar I420 and I422 take the same two filters: HYDAMD_I420C_* ... further down.)
  */
 #define HYDAMD_NV12C_BT709 32
 #define HYDAMD_NV12C_BT709_FULL 33
@@ -269,7 +272,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever NV12 is.  hydamd_encode_image_multi takes the nearest forms and refuses the interpolated 24 as it does
  * NV12's; the host-pointer entry points refuse all 36 with "Invalid Sample Format".
  * Out of scope: BT.2020 and the PQ / HLG transfer curves — the codestream this encoder writes signals sRGB or linear sRGB
- * only, so HDR10 content would be mis-described whatever the matrix; planar I420 / I010; 4:2:2 and 4:4:4; host-pointer P010.
+ * only, so HDR10 content would be mis-described whatever the matrix; planar I010 and deeper; 16-bit 4:2:2 and 4:4:4;
+ * host-pointer P010.
  */
 #define HYDAMD_P010_BT709 80
 #define HYDAMD_P010_BT709_FULL 81
@@ -309,12 +313,85 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
 #define HYDAMD_P016L_BT601_FULL 243
 
 /*
+ * PLANAR YCbCr DEVICE pixels: I420, I422 and I444 — 8 bits a sample, Y, U and V each in a plane of its own.  What rocJPEG's
+ * planar output, rocDecode's 4:4:4 surfaces and every software decoder (yuv420p, yuvj422p, yuv444p) leave; YV12 is I420 with
+ * src[1] and src[2] swapped.  Read by the transform kernel as they are, without an RGB or NV12 copy.
+ *   sample_fmt = 512 + matrix + 4 * subsampling + 16 * filter
+ * matrix 0..3 and filter 0..2 as in the NV12 family; subsampling 0 = 4:2:0, 1 = 4:2:2, 2 = 4:4:4 (filter 0 only):
+ *                     nearest      centre-sited   left-sited
+ *   HYDAMD_I420_*    512..515     528..531 (C)    544..547 (L)
+ *   HYDAMD_I422_*    516..519     532..535 (C)    548..551 (L)
+ *   HYDAMD_I444_*    520..523
+ * 28 numbers.  524..527, 536..543, 552 and up name nothing; + 64 * depth is kept for deeper planes and names nothing now.
+ * A JPEG is BT601_FULL, centre-sited: HYDAMD_I420C_BT601_FULL, HYDAMD_I422C_BT601_FULL or HYDAMD_I444_BT601_FULL.
+ *
+ * How such a picture is named, wherever a sample_fmt names device pixels and in a HydAmdImageDesc:
+ *   src[0]        the first Y sample
+ *   src[1], [2]   the first U and the first V sample: independent pointers, possibly in separate allocations
+ *   row_stride    the pitch of the Y plane in bytes; may be negative.  Y's pixel stride is 1 by definition
+ *   pixel_stride  THE ONE PITCH OF BOTH CHROMA PLANES in bytes; may be negative, independently of row_stride
+ * The chroma planes are cw x ch samples: cw = ceil(W / 2) for 4:2:0 and 4:2:2 and W for 4:4:4; ch = ceil(H / 2) for 4:2:0 and
+ * H otherwise.  Odd sizes work as NV12's.  |pixel_stride| < cw of the picture the call names (the LF group's width for plain
+ * hydamd_encode_lf_group) is HYD_API_ERROR "planar YCbCr wants the chroma planes' pitch in pixel_stride", nothing enqueued:
+ * that is what the habitual pixel_stride 1 meets.
+ * The library finds an LF group, tile or shard at pixel (x0, y0) at src[0] + y0 * row_stride + x0 and, with sx = 0 for 4:4:4
+ * and 1 otherwise, sy = 1 for 4:2:0 and 0 otherwise, at src[1 or 2] + (y0 >> sy) * pixel_stride + (x0 >> sx).  A caller's own
+ * crop must start on even x0, and on even y0 for 4:2:0, as NV12's.
+ *
+ * The file is byte for byte what the reference writes for the HYD_UINT8 picture this conversion produces.  Nearest: U and V
+ * of pixel (x, y) are C[y >> sy][x >> sx] of each plane.  4:2:0 with filter 1 or 2: the taps of the NV12C / NV12L section,
+ * applied to each plane as it stands.  4:2:2: the horizontal taps alone, with cx = x >> 1 —
+ *   centre-sited, hx = clamp(cx + (x odd ? 1 : -1), 0, cw - 1):   C' = (3 C[y][cx] + C[y][hx] + 2) >> 2
+ *   left-sited, x even:                                           C' = C[y][cx]
+ *   left-sited, x odd, hx = min(cx + 1, cw - 1):                  C' = (C[y][cx] + C[y][hx] + 1) >> 1
+ * (the 4:2:0 taps with the far row equal to the near one).  Then R, G, B by the NV12 section's formula and table, within 0.51
+ * of the real-valued conversion of (Y, U', V').  Clamping is at the edges of the PICTURE: chroma is continuous across LF
+ * groups and tiles, hydamd_encode_lf_group_at carries the picture, and nothing outside a plane's cw x ch samples or the Y
+ * rectangle is ever read.
+ *
+ * Accepted wherever NV12 is, and beside NV12, P010 and RGB pictures in one hydamd_encode_mixed_formats launch group.
+ * hydamd_encode_image_multi takes the 12 nearest forms and refuses the 16 interpolated ones as it does NV12's (a 4:2:2 window
+ * also crosses into an LF group another shard owns); the host-pointer entry points refuse all 28 with "Invalid Sample Format".
+ * Out of scope: I010 and deeper planes; NV21 and NV16; packed YUY2 / UYVY / AYUV; U and V planes of different pitches;
+ * top-left siting; host-pointer input; cross-shard interpolation.
+ */
+#define HYDAMD_I420_BT709 512
+#define HYDAMD_I420_BT709_FULL 513
+#define HYDAMD_I420_BT601 514
+#define HYDAMD_I420_BT601_FULL 515
+#define HYDAMD_I422_BT709 516
+#define HYDAMD_I422_BT709_FULL 517
+#define HYDAMD_I422_BT601 518
+#define HYDAMD_I422_BT601_FULL 519
+#define HYDAMD_I444_BT709 520
+#define HYDAMD_I444_BT709_FULL 521
+#define HYDAMD_I444_BT601 522
+#define HYDAMD_I444_BT601_FULL 523
+#define HYDAMD_I420C_BT709 528
+#define HYDAMD_I420C_BT709_FULL 529
+#define HYDAMD_I420C_BT601 530
+#define HYDAMD_I420C_BT601_FULL 531
+#define HYDAMD_I422C_BT709 532
+#define HYDAMD_I422C_BT709_FULL 533
+#define HYDAMD_I422C_BT601 534
+#define HYDAMD_I422C_BT601_FULL 535
+#define HYDAMD_I420L_BT709 544
+#define HYDAMD_I420L_BT709_FULL 545
+#define HYDAMD_I420L_BT601 546
+#define HYDAMD_I420L_BT601_FULL 547
+#define HYDAMD_I422L_BT709 548
+#define HYDAMD_I422L_BT709_FULL 549
+#define HYDAMD_I422L_BT601 550
+#define HYDAMD_I422L_BT601_FULL 551
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_* or HYDAMD_P01x_* formats (whose src and strides are described above).
- * With HYDAMD_NV12C_* or HYDAMD_NV12L_* the LF group is a picture of its own: its chroma clamps at its own edges.
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_* or HYDAMD_I4xx_* formats (whose src and strides are
+ * described above).  With an interpolating format (HYDAMD_NV12C_*, HYDAMD_NV12L_*, their P01x and I42x forms) the LF group is a
+ * picture of its own: its chroma clamps at its own edges.
  */
 HYDAMD_EXPORT int hydamd_encode_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
                                          ptrdiff_t pixel_stride, int sample_fmt, size_t width, size_t height,
@@ -322,7 +399,7 @@ HYDAMD_EXPORT int hydamd_encode_lf_group(HydAmdContext *ctx, int slot, const voi
 
 /* The same for the width x height LF group at pixel (x0, y0) of a pic_width x pic_height PICTURE whose first pixel src
  * names (for NV12: its first Y and U samples).  For every format this finds the LF group's origin as the library does and
- * is hydamd_encode_lf_group from there; for HYDAMD_NV12C_* and HYDAMD_NV12L_* it also records the picture, whose chroma the
+ * is hydamd_encode_lf_group from there; for the interpolating formats (above) it also records the picture, whose chroma the
  * filter reads across the LF group's edges and at whose edges it clamps.  HYD_API_ERROR: x0 or y0 no multiple of 256, or a
  * rectangle that does not lie inside the picture. */
 HYDAMD_EXPORT int hydamd_encode_lf_group_at(HydAmdContext *ctx, int slot, const void *const src[3], ptrdiff_t row_stride,
@@ -849,7 +926,7 @@ HYDAMD_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b);
  *                                its assembly and returns; the pixels stay borrowed until hydamd_mixed_result, the
  *                                descriptors only for the call.  The output buffer is sized before anything is
  *                                enqueued, from the batch's plan and the context's capacities.
- *   hydamd_encode_mixed_formats  the same with image k's samples in sample_fmts[k] (HYD_UINT8 / HYD_UINT16 / HYD_FLOAT32 / HYDAMD_FLOAT16 / HYDAMD_BFLOAT16 / HYDAMD_NV12_*):
+ *   hydamd_encode_mixed_formats  the same with image k's samples in sample_fmts[k] (HYD_UINT8 / HYD_UINT16 / HYD_FLOAT32 / HYDAMD_FLOAT16 / HYDAMD_BFLOAT16 / HYDAMD_NV12_* / HYDAMD_P01x_* / HYDAMD_I4xx_*):
  *                                8-bit, 16-bit and float pictures side by side in one launch group, every file what the
  *                                reference writes for that picture in its format.  A bad entry is HYD_API_ERROR "Invalid
  *                                Sample Format" with nothing enqueued.  The plan and its reuse depend on sizes only.
@@ -880,7 +957,7 @@ HYDAMD_EXPORT const uint32_t *hydamd_batch_image_status_device(HydAmdBatch *b);
  * closing the throughput gap to the padded-classes upper reference that profiles/mixed_batch.txt records.
  */
 typedef struct HydAmdImageDesc {
-    const void *src[3];                 /* device pointers: R, G, B of the image's first pixel (HYDAMD_NV12_*: Y, U, U + 1) */
+    const void *src[3];                 /* device pointers: R, G, B of the image's first pixel (HYDAMD_NV12_*: Y, U, U + 1; planar YCbCr: Y, U, V, and pixel_stride the chroma pitch) */
     ptrdiff_t row_stride, pixel_stride; /* in samples, as hyd_send_tile's */
     size_t width, height;               /* 1..2048 each; hydamd_mixed_create_slots: >= 1, at most 28 LF groups of 2048 x 2048 */
 } HydAmdImageDesc;
