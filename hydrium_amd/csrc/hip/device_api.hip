@@ -355,34 +355,9 @@ static_assert(HYDAMD_PLANAR_ROW(I420) && HYDAMD_PLANAR_ROW(I422) && HYDAMD_PLANA
               "the planar family is 512 + the kernels' matrix index + 4 * the kernels' subsampling + 16 * the kernels' chroma filter");
 #undef HYDAMD_PLANAR_ROW
 
-/* a public sample format's class (what job.fmt holds) and its storage form: the float class's three, NV12 and NV12I (NV12
- * with interpolated chroma) of the 8-bit class, P016 and P016I (P010 / P012 / P016, the same in 16-bit words) of the 16-bit class,
- * YUVP and YUVPI (planar YCbCr, nearest and interpolated) of the 8-bit class */
-int fmt_class(int sample_fmt) {
-    return hyd_fmt_is_float(sample_fmt) ? HYDK_FMT_F32 : hyd_fmt_is_nv12_family(sample_fmt) || hyd_fmt_is_planar_yuv(sample_fmt) ? HYDK_FMT_U8 : hyd_fmt_is_p016_family(sample_fmt) ? HYDK_FMT_U16 : sample_fmt;
-}
-uint32_t fmt_storage(int sample_fmt) {
-    return sample_fmt == HYD_FMT_FLOAT16    ? HYDK_STORE_F16
-           : sample_fmt == HYD_FMT_BFLOAT16 ? HYDK_STORE_BF16
-           : hyd_fmt_is_nv12(sample_fmt)    ? HYDK_STORE_NV12
-           : hyd_fmt_is_nv12_interp(sample_fmt) ? HYDK_STORE_NV12I
-           : hyd_fmt_is_p016_interp(sample_fmt) ? HYDK_STORE_P016I
-           : hyd_fmt_is_p016_family(sample_fmt) ? HYDK_STORE_P016
-           : hyd_fmt_is_planar_interp(sample_fmt) ? HYDK_STORE_YUVPI
-           : hyd_fmt_is_planar_yuv(sample_fmt)    ? HYDK_STORE_YUVP
-                                            : HYDK_STORE_F32;
-}
-/* the public format a recorded job reads */
+/* the public format a recorded job reads (hydk_store.h: the encode of what record_lf_group decoded) */
 int job_sample_fmt(const HydkLfJob &job) {
-    return job.storage == HYDK_STORE_F16    ? HYD_FMT_FLOAT16
-           : job.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16
-           : job.storage == HYDK_STORE_NV12 ? HYD_FMT_NV12_BT709 + (int)job.matrix
-           : job.storage == HYDK_STORE_NV12I ? HYD_FMT_NV12_BT709 + (int)job.matrix + 16 * (int)job.filter
-           : job.storage == HYDK_STORE_P016 || job.storage == HYDK_STORE_P016I
-               ? HYD_FMT_NV12_BT709 + (int)(job.matrix & 3u) + 16 * (int)job.filter + 64 * (int)(job.matrix >> 2)
-           : job.storage == HYDK_STORE_YUVP || job.storage == HYDK_STORE_YUVPI
-               ? HYD_FMT_I420_BT709 + (int)job.matrix + 4 * (int)job.sub + 16 * (int)job.filter
-                                            : job.fmt;
+    return hydk_encode_fmt(HydkSampleForm{1, job.fmt, job.storage, job.matrix, job.filter, job.sub, 0, 0});
 }
 
 /* forms 1-3 (several chains per wavefront, by rows) were replaced by form 5: select it, and say so once */
@@ -463,7 +438,8 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     /* half precision is a storage form of the float class: the job is a float job, and every `fmt == HYDK_FMT_F32` below
      * and in the kernels keeps meaning "float class".  NV12 is a storage form of the 8-bit class: 4-byte token records, the
      * 8-bit transfer table, and whatever form of the entropy stage is selected */
-    const int fmt = fmt_class(sample_fmt);
+    const HydkSampleForm form = hydk_decode_fmt(sample_fmt);
+    const int fmt = form.cls;
     /* the slot's frame: the whole launch group, or one frame of a batch — presets and the alphabet maximum restart with it */
     unsigned frame_first = 0, frame_groups = ctx->num_presets;
     if (ctx->slots_per_frame > 0) {
@@ -487,29 +463,17 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.row_stride = row_stride;
     job.pixel_stride = pixel_stride;
     job.fmt = fmt;
-    job.storage = fmt_storage(sample_fmt);
-    job.matrix = hyd_fmt_is_nv12_family(sample_fmt) ? (uint32_t)hyd_fmt_nv12_family_matrix(sample_fmt)
-                 : hyd_fmt_is_p016_family(sample_fmt) ? (uint32_t)(hyd_fmt_p016_matrix(sample_fmt) + 4 * hyd_fmt_p016_depth(sample_fmt))
-                 : hyd_fmt_is_planar_yuv(sample_fmt)  ? (uint32_t)hyd_fmt_planar_matrix(sample_fmt)
-                                                      : 0u;
-    if (job.storage == HYDK_STORE_YUVP || job.storage == HYDK_STORE_YUVPI)
-        job.sub = (uint32_t)hyd_fmt_planar_sub(sample_fmt);
-    if (job.storage == HYDK_STORE_YUVPI) {
-        /* each chroma plane of the picture in its own units, and where src[1] and src[2] point in it */
-        const int sx = hyd_fmt_planar_sx(sample_fmt), sy = hyd_fmt_planar_sy(sample_fmt);
-        job.filter = (uint32_t)hyd_fmt_planar_filter(sample_fmt);
-        job.pic_cx0 = pic ? (int32_t)(pic[0] >> sx) : 0;
-        job.pic_cy0 = pic ? (int32_t)(pic[1] >> sy) : 0;
-        job.pic_cw = (int32_t)(((pic ? pic[2] : width) + (size_t)sx) >> sx);
-        job.pic_ch = (int32_t)(((pic ? pic[3] : height) + (size_t)sy) >> sy);
-    }
-    if (job.storage == HYDK_STORE_NV12I || job.storage == HYDK_STORE_P016I) {
-        /* the picture's chroma plane and where src[1] points in it: all the kernel may read around this LF group */
-        job.filter = (uint32_t)(job.storage == HYDK_STORE_NV12I ? hyd_fmt_nv12_filter(sample_fmt) : hyd_fmt_p016_filter(sample_fmt));
-        job.pic_cx0 = pic ? (int32_t)(pic[0] >> 1) : 0;
-        job.pic_cy0 = pic ? (int32_t)(pic[1] >> 1) : 0;
-        job.pic_cw = (int32_t)(((pic ? pic[2] : width) + 1) >> 1);
-        job.pic_ch = (int32_t)(((pic ? pic[3] : height) + 1) >> 1);
+    job.storage = form.storage;
+    job.matrix = form.matrix;
+    job.filter = form.filter;
+    job.sub = form.sub;
+    if (hydk_store_form((int)form.storage).interp) {
+        /* the picture's chroma plane (each plane's, in its own units) and where src[1] (and src[2]) point in it: all the kernel
+         * may read around this LF group */
+        job.pic_cx0 = pic ? (int32_t)(pic[0] >> form.sx) : 0;
+        job.pic_cy0 = pic ? (int32_t)(pic[1] >> form.sy) : 0;
+        job.pic_cw = (int32_t)(((pic ? pic[2] : width) + (size_t)form.sx) >> form.sx);
+        job.pic_ch = (int32_t)(((pic ? pic[3] : height) + (size_t)form.sy) >> form.sy);
     }
 #ifdef HYD_TEST_HOOKS
     /* HYDAMD_DEBUG_HALF_PER_SAMPLE (bit 0 interleaved, bit 1 planar): half-precision rows that qualify for the dword runs
@@ -523,14 +487,7 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.gcols = (int)((width + 255) >> 8);
     job.grows = (int)((height + 255) >> 8);
     job.scheme = ctx->scheme;
-    job.use_luts = fmt == HYDK_FMT_F32 ? 0
-                   : ctx->use_luts + (job.storage == HYDK_STORE_NV12    ? HYDK_VARIANT_NV12
-                                      : job.storage == HYDK_STORE_NV12I ? HYDK_VARIANT_NV12I
-                                      : job.storage == HYDK_STORE_P016  ? HYDK_VARIANT_P016
-                                      : job.storage == HYDK_STORE_P016I ? HYDK_VARIANT_P016I
-                                      : job.storage == HYDK_STORE_YUVP  ? HYDK_VARIANT_YUVP
-                                      : job.storage == HYDK_STORE_YUVPI ? HYDK_VARIANT_YUVPI
-                                                                        : 0);
+    job.use_luts = fmt == HYDK_FMT_F32 ? 0 : ctx->use_luts + hydk_store_form((int)form.storage).variant;
     job.preset = preset;
     while ((1u << job.preset_bits) < frame_groups) /* hyd_cllog2, encoder.c:940 */
         job.preset_bits++;
@@ -2860,6 +2817,29 @@ __attribute__((visibility("default"))) int hydt_widen_half_host(int storage, con
 }
 
 namespace {
+/* What every device-side probe entry below does: in_bytes up, one launch — launch(d_in, d_out) — out_bytes back (which waits
+ * for the kernel), both buffers freed; HYD_OK, or HYD_API_ERROR with nothing written */
+extern "C++" template <typename Launch>
+int probe_round_trip(const void *in, size_t in_bytes, void *out, size_t out_bytes, Launch launch) {
+    void *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc(&d_in, in_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&d_out, out_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch(d_in, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+}
+/* one thread per element */
+extern "C++" dim3 probe_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
 __global__ __launch_bounds__(256) void k_widen_half_probe(int storage, const uint16_t *in, uint32_t *out) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x; /* grid = 256 workgroups: one thread per 16-bit pattern */
     out[i] = hydk_widen_half(storage, in[i]);
@@ -2871,22 +2851,9 @@ __attribute__((visibility("default"))) int hydt_widen_half_device(int device, in
     if ((storage != HYDK_STORE_F16 && storage != HYDK_STORE_BF16) || !in || !out || hipSetDevice(device) != hipSuccess)
         return ST_API_ERROR;
     constexpr size_t kN = 65536;
-    uint16_t *d_in = nullptr;
-    uint32_t *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, kN * sizeof(uint16_t));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_out, kN * sizeof(uint32_t));
-    if (e == hipSuccess)
-        e = hipMemcpy(d_in, in, kN * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_widen_half_probe, dim3(kN / 256), dim3(256), 0, nullptr, storage, d_in, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpy(out, d_out, kN * sizeof(uint32_t), hipMemcpyDeviceToHost); /* (waits for the kernel) */
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+    return probe_round_trip(in, kN * sizeof(uint16_t), out, kN * sizeof(uint32_t), [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_widen_half_probe, probe_grid(kN), dim3(256), 0, nullptr, storage, (const uint16_t *)d_in, (uint32_t *)d_out);
+    });
 }
 
 /* Test hooks (probe flavour only, not declared in include/): the YCbCr conversion (hydk_yuv.h) as the host compiler built it
@@ -2921,21 +2888,9 @@ __attribute__((visibility("default"))) int hydt_yuv_to_rgb_device(int device, in
     if (matrix < 0 || matrix >= HYDK_YUV_MATRICES || !yuv || !rgb || n == 0 || n >= ((size_t)1 << 31) ||
         hipSetDevice(device) != hipSuccess)
         return ST_API_ERROR;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, 3 * n);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_out, 3 * n);
-    if (e == hipSuccess)
-        e = hipMemcpy(d_in, yuv, 3 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_yuv_to_rgb_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, matrix, d_in, d_out, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpy(rgb, d_out, 3 * n, hipMemcpyDeviceToHost); /* (waits for the kernel) */
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+    return probe_round_trip(yuv, 3 * n, rgb, 3 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_yuv_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, matrix, (const uint8_t *)d_in, (uint8_t *)d_out, n);
+    });
 }
 
 /* Test hooks (probe flavour only, not declared in include/): the chroma interpolation (hydk_chroma.h) as the host compiler
@@ -2979,22 +2934,10 @@ __attribute__((visibility("default"))) int hydt_chroma_upsample_device(int devic
     if (!chroma_probe_args(filter, uv, out, width, height) || hipSetDevice(device) != hipSuccess)
         return ST_API_ERROR;
     const size_t n = (size_t)width * height, in_bytes = 2 * (size_t)((width + 1) >> 1) * ((height + 1) >> 1);
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, in_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_out, 2 * n);
-    if (e == hipSuccess)
-        e = hipMemcpy(d_in, uv, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_chroma_upsample_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, filter, d_in, d_out, width,
-                           height);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpy(out, d_out, 2 * n, hipMemcpyDeviceToHost); /* (waits for the kernel) */
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+    return probe_round_trip(uv, in_bytes, out, 2 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_chroma_upsample_probe, probe_grid(n), dim3(256), 0, nullptr, filter, (const uint8_t *)d_in, (uint8_t *)d_out,
+                           width, height);
+    });
 }
 
 /* Test hooks (probe flavour only, not declared in include/): the planar definition (hydk_planar_sample, hydk_chroma.h) as the
@@ -3034,22 +2977,10 @@ __attribute__((visibility("default"))) int hydt_planar_upsample_device(int devic
         return ST_API_ERROR;
     const size_t n = (size_t)width * height;
     const size_t in_bytes = (size_t)((width + hydk_planar_sx(sub)) >> hydk_planar_sx(sub)) * ((height + hydk_planar_sy(sub)) >> hydk_planar_sy(sub));
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, in_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_out, n);
-    if (e == hipSuccess)
-        e = hipMemcpy(d_in, plane, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_planar_upsample_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, sub, filter, d_in, d_out, width,
-                           height);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpy(out, d_out, n, hipMemcpyDeviceToHost); /* (waits for the kernel) */
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return e == hipSuccess ? ST_OK : ST_API_ERROR;
+    return probe_round_trip(plane, in_bytes, out, n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_planar_upsample_probe, probe_grid(n), dim3(256), 0, nullptr, sub, filter, (const uint8_t *)d_in, (uint8_t *)d_out,
+                           width, height);
+    });
 }
 
 /* Test hooks (probe flavour only, not declared in include/): the 16-bit conversion and taps (hydk_yuv16.h) as the host compiler
@@ -3106,31 +3037,6 @@ __global__ __launch_bounds__(256) void k_chroma16_upsample_probe(int filter, con
     out[2 * i] = (uint16_t)pair[0];
     out[2 * i + 1] = (uint16_t)pair[1];
 }
-
-/* in_words uint16 up, one launch (the conversion over n triples when depth != 0, else the taps over a width x height
- * picture), out_words uint16 back; HYD_OK, or HYD_API_ERROR with nothing written */
-int probe16_round_trip(const uint16_t *in, size_t in_words, uint16_t *out, size_t out_words, int depth, int matrix_or_filter, size_t n,
-                       int width, int height) {
-    uint16_t *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, 2 * in_words);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_out, 2 * out_words);
-    if (e == hipSuccess)
-        e = hipMemcpy(d_in, in, 2 * in_words, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        if (depth)
-            hipLaunchKernelGGL(k_yuv16_to_rgb_probe, grid, block, 0, nullptr, depth, matrix_or_filter, d_in, d_out, n);
-        else
-            hipLaunchKernelGGL(k_chroma16_upsample_probe, grid, block, 0, nullptr, matrix_or_filter, d_in, d_out, width, height);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpy(out, d_out, 2 * out_words, hipMemcpyDeviceToHost); /* (waits for the kernel) */
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return e == hipSuccess ? ST_OK : ST_API_ERROR;
-}
 } /* namespace */
 
 /* one launch over n triples (host arrays, n < 2^31) on `device` */
@@ -3138,7 +3044,9 @@ __attribute__((visibility("default"))) int hydt_yuv16_to_rgb_device(int device, 
                                                                     size_t n) {
     if (!yuv16_probe_args(depth, matrix, yuv, rgb) || n == 0 || n >= ((size_t)1 << 31) || hipSetDevice(device) != hipSuccess)
         return ST_API_ERROR;
-    return probe16_round_trip(yuv, 3 * n, rgb, 3 * n, depth, matrix, n, 0, 0);
+    return probe_round_trip(yuv, 6 * n, rgb, 6 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_yuv16_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, depth, matrix, (const uint16_t *)d_in, (uint16_t *)d_out, n);
+    });
 }
 
 /* one launch over the picture (host arrays) on `device` */
@@ -3147,7 +3055,10 @@ __attribute__((visibility("default"))) int hydt_chroma16_upsample_device(int dev
     if (!chroma_probe_args(filter, (const uint8_t *)uv, (uint8_t *)out, width, height) || hipSetDevice(device) != hipSuccess)
         return ST_API_ERROR;
     const size_t n = (size_t)width * height;
-    return probe16_round_trip(uv, 2 * (size_t)((width + 1) >> 1) * ((height + 1) >> 1), out, 2 * n, 0, filter, n, width, height);
+    return probe_round_trip(uv, 4 * (size_t)((width + 1) >> 1) * ((height + 1) >> 1), out, 4 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_chroma16_upsample_probe, probe_grid(n), dim3(256), 0, nullptr, filter, (const uint16_t *)d_in, (uint16_t *)d_out,
+                           width, height);
+    });
 }
 #endif
 
@@ -3234,10 +3145,11 @@ int hydamd_read_lf_streams(HydAmdContext *ctx, int first_slot, int count, HydAmd
 }
 
 int hydamd_debug_transform_footprint(HydAmdContext *ctx, int sample_fmt, int *lds_bytes, int *registers) {
-    if (!ctx || !lds_bytes || !registers || !hyd_fmt_is_device(sample_fmt))
+    const HydkSampleForm form = hydk_decode_fmt(sample_fmt);
+    if (!ctx || !lds_bytes || !registers || !form.ok)
         return ST_API_ERROR;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hydk::transform_footprint(fmt_class(sample_fmt), (int)fmt_storage(sample_fmt), ctx->use_luts, lds_bytes, registers));
+    HIP_TRY(ctx, hydk::transform_footprint(form.cls, (int)form.storage, ctx->use_luts, lds_bytes, registers));
     return ST_OK;
 }
 

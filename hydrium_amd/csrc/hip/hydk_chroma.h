@@ -35,15 +35,13 @@
 
 #include <stdint.h>
 
+#include "hydk_store.h" /* HYDK_STORE_NV12I, _YUVP, _YUVPI */
+
 #ifdef __HIPCC__
 #define HYDK_CHROMA_FN __host__ __device__ static inline
 #else
 #define HYDK_CHROMA_FN static inline
 #endif
-
-/* storage form of an 8-bit-class LF group (HydkLfJob.storage) beside HYDK_STORE_NV12: an NV12 picture whose chroma is
- * interpolated under HydkLfJob.filter */
-#define HYDK_STORE_NV12I 4
 
 /* filters (HydkLfJob.filter; hyd_sample_fmt.h: (sample format - 16) >> 4) */
 #define HYDK_CHROMA_NEAREST 0
@@ -83,13 +81,7 @@ HYDK_CHROMA_FN void hydk_chroma_pair(int filter, const uint8_t *near, const uint
                                  hydk_chroma_vmix(near[2 * hx + c], far[2 * hx + c]));
 }
 
-/* storage forms of an 8-bit-class LF group whose pixels are PLANAR YCbCr: src[0] the Y plane (pitch row_stride), src[1] and
- * src[2] the U and V planes (pitch pixel_stride), HydkLfJob.sub the subsampling.  _YUVP: nearest chroma; _YUVPI: interpolated
- * under HydkLfJob.filter, 4:2:0 and 4:2:2 */
-#define HYDK_STORE_YUVP 7
-#define HYDK_STORE_YUVPI 8
-
-/* subsamplings (HydkLfJob.sub; hyd_sample_fmt.h: ((sample format - 512) >> 2) & 3) */
+/* subsamplings of the planar forms, HYDK_STORE_YUVP and _YUVPI (HydkLfJob.sub; hyd_sample_fmt.h: ((sample format - 512) >> 2) & 3) */
 #define HYDK_PLANAR_420 0
 #define HYDK_PLANAR_422 1
 #define HYDK_PLANAR_444 2

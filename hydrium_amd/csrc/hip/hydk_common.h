@@ -10,23 +10,11 @@
 
 #include <stdint.h>
 
-#include "hydk_half.h" /* HYDK_STORE_*: how a float-class LF group's samples are stored */
-#include "hydk_yuv.h"  /* HYDK_STORE_NV12: an 8-bit-class LF group whose pixels are an NV12 picture */
-#include "hydk_chroma.h" /* HYDK_STORE_NV12I: the same picture with interpolated chroma */
-#include "hydk_yuv16.h" /* HYDK_STORE_P016, _P016I: a 16-bit-class LF group whose pixels are a P010 / P012 / P016 picture */
-
-/* sample CLASSES: what a job's fmt and the transform kernel's FMT name.  Half-precision pixels (hyd_sample_fmt.h: 3, 4) are
- * float-class jobs — fmt == HYDK_FMT_F32 means "float class" everywhere — whose storage field says how to load a sample;
- * NV12 pictures (16 ... 19) are 8-bit-class jobs of storage HYDK_STORE_NV12: 8-bit RGB from the load on (hydk_yuv.h) */
-#define HYDK_VARIANT_NV12 8 /* HydkLfJob.use_luts of an NV12 job: XYB mode + 8 */
-#define HYDK_VARIANT_NV12I 16 /* of an NV12 job with interpolated chroma (32 ... 35, 48 ... 51; HYDK_STORE_NV12I): XYB mode + 16 */
-#define HYDK_VARIANT_P016 32 /* of a P010 / P012 / P016 job with nearest chroma (HYDK_STORE_P016): XYB mode + 32 */
-#define HYDK_VARIANT_P016I 64 /* with interpolated chroma (HYDK_STORE_P016I): XYB mode + 64 */
-#define HYDK_VARIANT_YUVP 128 /* of a planar YCbCr job with nearest chroma (512 ...; HYDK_STORE_YUVP): XYB mode + 128 */
-#define HYDK_VARIANT_YUVPI 256 /* with interpolated chroma (HYDK_STORE_YUVPI): XYB mode + 256 */
-#define HYDK_FMT_U8 0
-#define HYDK_FMT_U16 1
-#define HYDK_FMT_F32 2
+#include "hydk_store.h" /* HYDK_FMT_*, HYDK_STORE_*, HYDK_VARIANT_*: sample classes and the storage forms of an LF group's pixels */
+#include "hydk_half.h"  /* what the kernels do to a loaded sample: half precision widened, */
+#include "hydk_yuv.h"   /* YCbCr of 8 bits to RGB, */
+#include "hydk_chroma.h" /* chroma interpolated, */
+#include "hydk_yuv16.h" /* and both in 16-bit words */
 
 #define HYDK_GROUPS_PER_LFG 64        /* 8 x 8 groups of 256 px in a 2048 px LF group */
 #define HYDK_BLOCKS_PER_GROUP 1024    /* 32 x 32 varblocks */

@@ -11,16 +11,13 @@
 
 #include <stdint.h>
 
+#include "hydk_store.h" /* HYDK_STORE_F32, _F16, _BF16: the storage forms of a float-class LF group */
+
 #ifdef __HIPCC__
 #define HYDK_HALF_FN __host__ __device__ static inline
 #else
 #define HYDK_HALF_FN static inline
 #endif
-
-/* storage forms of a float-class LF group (HydkLfJob.storage) */
-#define HYDK_STORE_F32 0
-#define HYDK_STORE_F16 1
-#define HYDK_STORE_BF16 2
 
 /* bfloat16 is the upper half of a float32 */
 HYDK_HALF_FN uint32_t hydk_widen_bf16(uint32_t bits) { return (bits & 0xFFFFu) << 16; }

@@ -1,0 +1,111 @@
+/*
+ * hydk_store.h — the storage forms of an LF group's pixels, in one table: what HydkLfJob.storage names, what each form is made
+ * of, and the two directions between a public sample format (hyd_sample_fmt.h) and a job's fields.  Plain C / C++ for host and
+ * device, no HIP needed; in C++ hydk_store_form is constexpr, so a kernel derives its compile-time switches from the table.
+ */
+#ifndef HYD_STORE_FORMS_H_
+#define HYD_STORE_FORMS_H_
+
+#include <stdint.h>
+
+#include "../hyd_sample_fmt.h"
+
+#ifdef __cplusplus
+#define HYDK_STORE_FN constexpr static inline
+#else
+#define HYDK_STORE_FN static inline
+#endif
+
+/* sample CLASSES: what a job's fmt and the transform kernel's FMT name.  fmt == HYDK_FMT_F32 means "float class" everywhere */
+#define HYDK_FMT_U8 0
+#define HYDK_FMT_U16 1
+#define HYDK_FMT_F32 2
+
+/* storage forms (HydkLfJob.storage).  0 is what a zeroed job says: the class's own samples — RGB of 8 or 16 bits, float32 */
+#define HYDK_STORE_F32 0
+#define HYDK_STORE_F16 1   /* float class: 2-byte samples, widened exactly on load (hydk_half.h) */
+#define HYDK_STORE_BF16 2
+#define HYDK_STORE_NV12 3  /* 8-bit class: a Y plane and a half-resolution plane of U, V pairs, nearest chroma (hydk_yuv.h) */
+#define HYDK_STORE_NV12I 4 /* the same picture, chroma interpolated under HydkLfJob.filter (hydk_chroma.h) */
+#define HYDK_STORE_P016 5  /* 16-bit class: P010 / P012 / P016, NV12's two planes in 16-bit words (hydk_yuv16.h) */
+#define HYDK_STORE_P016I 6
+#define HYDK_STORE_YUVP 7  /* 8-bit class: planar YCbCr — src[1], src[2] the U and V planes (pitch pixel_stride), HydkLfJob.sub the subsampling */
+#define HYDK_STORE_YUVPI 8
+#define HYDK_STORE_FORMS 9
+
+/* HydkLfJob.use_luts of a YCbCr job is the XYB mode + its form's variant bit: the RGB instances' own test turns it away */
+#define HYDK_VARIANT_NV12 8
+#define HYDK_VARIANT_NV12I 16
+#define HYDK_VARIANT_P016 32
+#define HYDK_VARIANT_P016I 64
+#define HYDK_VARIANT_YUVP 128
+#define HYDK_VARIANT_YUVPI 256
+
+typedef struct HydkStoreForm {
+    int cls;           /* HYDK_FMT_*; form 0 belongs to every class */
+    int ycbcr;         /* a pixel is converted to RGB of its class right after the load */
+    int bits;          /* of a stored sample */
+    int chroma_planes; /* YCbCr: 1 — (U, V) pairs interleaved in one plane; 2 — a plane each */
+    int interp;        /* chroma interpolated: the job carries filter and the picture (pic_*) */
+    int variant;       /* HYDK_VARIANT_* */
+} HydkStoreForm;
+
+HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
+    const HydkStoreForm forms[HYDK_STORE_FORMS] = {
+        {HYDK_FMT_F32, 0, 32, 0, 0, 0},
+        {HYDK_FMT_F32, 0, 16, 0, 0, 0},
+        {HYDK_FMT_F32, 0, 16, 0, 0, 0},
+        {HYDK_FMT_U8, 1, 8, 1, 0, HYDK_VARIANT_NV12},
+        {HYDK_FMT_U8, 1, 8, 1, 1, HYDK_VARIANT_NV12I},
+        {HYDK_FMT_U16, 1, 16, 1, 0, HYDK_VARIANT_P016},
+        {HYDK_FMT_U16, 1, 16, 1, 1, HYDK_VARIANT_P016I},
+        {HYDK_FMT_U8, 1, 8, 2, 0, HYDK_VARIANT_YUVP},
+        {HYDK_FMT_U8, 1, 8, 2, 1, HYDK_VARIANT_YUVPI},
+    };
+    return forms[storage >= 0 && storage < HYDK_STORE_FORMS ? storage : 0];
+}
+
+/* A public sample format taken apart into what a job holds.  ok: hyd_fmt_is_device accepts it (else every field is 0).
+ * matrix: HYDK_YUV_* (0 ... 3), + 4 * depth (HYDK_YUV16_P01x) for the 16-bit forms; filter: HYDK_CHROMA_*; sub: HYDK_PLANAR_*;
+ * sx, sy: log2 of the pixels one chroma sample spans across and down. */
+typedef struct HydkSampleForm {
+    int ok, cls;
+    uint32_t storage, matrix, filter, sub;
+    int sx, sy;
+} HydkSampleForm;
+
+static inline HydkSampleForm hydk_decode_fmt(int f) {
+    HydkSampleForm d = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (!hyd_fmt_is_device(f))
+        return d;
+    d.ok = 1;
+    if (hyd_fmt_is_yuv420(f)) {
+        d.filter = (uint32_t)hyd_fmt_p016_filter(f);
+        d.matrix = (uint32_t)(hyd_fmt_p016_matrix(f) + 4 * hyd_fmt_p016_depth(f)); /* (depth 0: the 8-bit family) */
+        d.storage = (uint32_t)((hyd_fmt_p016_depth(f) ? HYDK_STORE_P016 : HYDK_STORE_NV12) + (d.filter != 0));
+        d.sx = d.sy = 1;
+    } else if (hyd_fmt_is_planar_yuv(f)) {
+        d.filter = (uint32_t)hyd_fmt_planar_filter(f);
+        d.matrix = (uint32_t)hyd_fmt_planar_matrix(f);
+        d.sub = (uint32_t)hyd_fmt_planar_sub(f);
+        d.storage = (uint32_t)(HYDK_STORE_YUVP + (d.filter != 0));
+        d.sx = hyd_fmt_planar_sx(f);
+        d.sy = hyd_fmt_planar_sy(f);
+    } else if (f > HYD_FMT_FLOAT32) {
+        d.storage = (uint32_t)(f == HYD_FMT_FLOAT16 ? HYDK_STORE_F16 : HYDK_STORE_BF16);
+    }
+    d.cls = d.storage > HYDK_STORE_F32 ? hydk_store_form((int)d.storage).cls : f;
+    return d;
+}
+
+/* and back: the public format of a job's cls (fmt), storage, matrix, filter and sub */
+static inline int hydk_encode_fmt(HydkSampleForm d) {
+    const HydkStoreForm form = hydk_store_form((int)d.storage);
+    if (!form.ycbcr)
+        return d.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : d.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : d.cls;
+    if (form.chroma_planes == 2)
+        return HYD_FMT_I420_BT709 + (int)d.matrix + 4 * (int)d.sub + 16 * (int)d.filter;
+    return HYD_FMT_NV12_BT709 + (int)(d.matrix & 3u) + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2);
+}
+
+#endif /* HYD_STORE_FORMS_H_ */

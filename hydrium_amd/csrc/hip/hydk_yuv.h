@@ -20,6 +20,8 @@
 
 #include <stdint.h>
 
+#include "hydk_store.h" /* HYDK_STORE_NV12 */
+
 #ifdef __HIPCC__
 #define HYDK_YUV_FN __host__ __device__ static inline
 #else
@@ -30,9 +32,6 @@
 #else
 #define HYDK_YUV_MUL(a, b) ((a) * (b))
 #endif
-
-/* storage form of an 8-bit-class LF group (HydkLfJob.storage) beside hydk_half.h's three: an NV12 picture */
-#define HYDK_STORE_NV12 3
 
 /* matrices (HydkLfJob.matrix; hyd_sample_fmt.h: sample format - 16) */
 #define HYDK_YUV_BT709 0

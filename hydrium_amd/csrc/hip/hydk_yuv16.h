@@ -26,11 +26,6 @@
 #include "hydk_chroma.h"
 #include "hydk_yuv.h"
 
-/* storage forms of a 16-bit-class LF group (HydkLfJob.storage): a P010 / P012 / P016 picture with nearest chroma, and the same
- * picture whose chroma is interpolated under HydkLfJob.filter */
-#define HYDK_STORE_P016 5
-#define HYDK_STORE_P016I 6
-
 /* depths (HydkLfJob.matrix of these storage forms is matrix + 4 * depth; hyd_sample_fmt.h: (sample format - 16) >> 6) */
 #define HYDK_YUV16_P010 1
 #define HYDK_YUV16_P012 2

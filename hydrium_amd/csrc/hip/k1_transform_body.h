@@ -4,20 +4,19 @@
  * and STORE, the kernel's parameters jobs, status, part_info and plog, and everything kernels.hip defines above its K1 section.
  * No include guard: it is function-body text, meant to be included once per kernel.
  */
-    static_assert(STORE == HYDK_STORE_F32 || (STORE == HYDK_STORE_NV12 || STORE == HYDK_STORE_NV12I   ? FMT == HYDK_FMT_U8
-                                              : STORE == HYDK_STORE_YUVP || STORE == HYDK_STORE_YUVPI ? FMT == HYDK_FMT_U8
-                                              : STORE == HYDK_STORE_P016 || STORE == HYDK_STORE_P016I ? FMT == HYDK_FMT_U16
-                                                                                                      : FMT == HYDK_FMT_F32),
+    /* What STORE is made of (hydk_store.h).  YUV: a YCbCr form — a pixel becomes an RGB pixel of its class right after the load.
+     * TWO_PLANES: U and V in planes of their own, whose pitch is job.pixel_stride, subsampled as job.sub says (planar YCbCr);
+     * else (U, V) pairs in one half-resolution plane of the Y plane's pitch (NV12; P010 / P012 / P016 in 16-bit words).
+     * INTERP: chroma interpolated (hydk_chroma.h) — job.filter says centre- or left-sited, and the job knows the picture it is
+     * cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it.  HALF: 2-byte floats, widened on load */
+    constexpr HydkStoreForm FORM = hydk_store_form(STORE);
+    static_assert(STORE == HYDK_STORE_F32 || FORM.cls == FMT,
                   "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP and YUVPI, the 16-bit class P016 and P016I");
-    /* YUVP, YUVPI: planar YCbCr — U and V in planes of their own whose pitch is job.pixel_stride, subsampled as job.sub says */
-    constexpr bool YUVP = STORE == HYDK_STORE_YUVP, YUVPI = STORE == HYDK_STORE_YUVPI;
-    /* P016, P016I: what NV12 and NV12I are, in 16-bit words — a block row is four dwords of Y and four of U, V pairs */
-    constexpr bool P016 = STORE == HYDK_STORE_P016, P016I = STORE == HYDK_STORE_P016I;
-    constexpr bool NV12 = STORE == HYDK_STORE_NV12;
-    /* NV12I: the NV12 picture with interpolated chroma (hydk_chroma.h) — job.filter says centre- or left-sited, and the job
-     * knows the picture it is cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it */
-    constexpr bool NV12I = STORE == HYDK_STORE_NV12I;
-    constexpr bool HALF = STORE != HYDK_STORE_F32 && !NV12 && !NV12I && !P016 && !P016I && !YUVP && !YUVPI;
+    constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, INTERP = FORM.interp;
+    constexpr bool HALF = FMT == HYDK_FMT_F32 && STORE != HYDK_STORE_F32;
+    /* the two-plane forms by name: YUVPI keeps a prefetch, an edge fill and an interpolate loop of its own (through the shared
+     * ones its instances measured a few tenths of a percent slower, profiles/ycbcr_loader.txt) */
+    constexpr bool YUVP = TWO_PLANES && !INTERP, YUVPI = TWO_PLANES && INTERP;
     typedef typename std::conditional<HALF, uint16_t, typename SampleOf<FMT>::type>::type sample_t;
     constexpr bool LUTS = XMODE == kXybGather;
     constexpr int kWords = FMT == HYDK_FMT_U8 ? 6 : 12; /* dwords holding 8 packed RGB pixels */
@@ -29,8 +28,8 @@
      * its symbols in its own share of the group's token array and k_join_parts closes the gaps (round 5) */
     const unsigned bid = blockIdx.x >> plog, part = blockIdx.x & ((1u << plog) - 1u);
     const HydkLfJob job = jobs[bid >> 6];
-    /* (an NV12 job names its variant as mode + HYDK_VARIANT_NV12: the 8-bit instances' own test turns it away as it stands) */
-    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE) + (NV12 ? HYDK_VARIANT_NV12 : NV12I ? HYDK_VARIANT_NV12I : P016 ? HYDK_VARIANT_P016 : P016I ? HYDK_VARIANT_P016I : YUVP ? HYDK_VARIANT_YUVP : YUVPI ? HYDK_VARIANT_YUVPI : 0)) ||
+    /* (a YCbCr job names its variant as mode + its form's variant bit: the RGB instances' own test turns it away as it stands) */
+    if (job.fmt != FMT || (FMT != HYDK_FMT_F32 && job.use_luts != xyb_arith(XMODE) + FORM.variant) ||
         (FMT == HYDK_FMT_F32 && job.storage != (uint32_t)STORE))
         return; /* another template instance of this launch round owns this LF group */
     if ((int)(bid & 63) >= job.gcols * job.grows)
@@ -110,7 +109,7 @@
     const int coef_cl_lo = job.scheme == 0 ? 3 : job.scheme == 3 ? 0 : 1;
 
     /* (which loader a layout gets, from here to hfast, is restated by loader() in tests/pixel_layouts.py: change them together) */
-    const bool packed = !NV12 && !NV12I && !P016 && !P016I && !YUVP && !YUVPI && job.pixel_stride == 3 &&
+    const bool packed = !YUV && job.pixel_stride == 3 &&
                         (const char *)job.src[1] == (const char *)job.src[0] + sizeof(sample_t) &&
                         (const char *)job.src[2] == (const char *)job.src[0] + 2 * sizeof(sample_t) &&
                         (((uintptr_t)job.src[0] | (uintptr_t)(job.row_stride * (long long)sizeof(sample_t))) & 3) == 0 &&
@@ -140,69 +139,94 @@
             hrun = 2;
     }
     const bool hfast = HALF && hrun != 0 && ab < gbw && ab * 8 + 8 <= gw;
-    /* NV12: a block row is two dwords of Y and, from chroma row y >> 1, two dwords of U, V pairs (a pair serves two pixels, and
-     * the block's first column is even) when both planes and the pitch are dword multiples; anything else reads byte by byte */
-    const bool nvrun = NV12 && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)job.row_stride) & 3) == 0;
-    const HydkYuvMatrix yuv = P016 || P016I ? hydk_yuv16_job_matrix(job.matrix) : hydk_yuv_matrix(NV12 || NV12I || YUVP || YUVPI ? (int)job.matrix : 0);
-    /* P016, P016I: the same runs in 16-bit words — four dwords of Y, four dwords of pairs per chroma row, a dword per flank
-     * pair — when both planes start on a dword and the pitch is an even number of words; anything else reads word by word */
-    const bool prun = (P016 || P016I) && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1]) & 3) == 0 && (job.row_stride & 1) == 0;
-    /* NV12I: a block row is two dwords of Y, two dwords of U, V pairs from chroma row y >> 1 and two from the other row the
-     * filter mixes in (above for an even y, below for an odd one, clamped to the PICTURE's chroma rows) — the six dwords an
-     * 8-bit row holds — and, as 16-bit loads beside them, the pair behind those four and (centre-sited) the pair before them.
-     * That is taken only where this whole window of pairs lies inside the picture's chroma row and planes and pitch are dword
-     * multiples; the picture's first and last chroma columns, odd widths and shifted bases fill the same window byte by byte
-     * with the clamps, at use (phase A below).  pcx: the picture's chroma column of the block's first pair. */
-    const int pcx = NV12I || P016I || YUVPI ? job.pic_cx0 + ((px0 + ab * 8) >> 1) : 0;
-    const bool irun = NV12I && (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)job.row_stride) & 3) == 0 &&
-                      (job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1;
-    const bool pirun = P016I && prun && (job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1;
-    /* YUVP: a block row is two dwords of Y and, from each chroma plane, the dword of four samples that serves its eight pixels
-     * (the block's chroma column is a multiple of 4) — two dwords of eight for 4:4:4 — when the three planes and both pitches
-     * are dword multiples; anything else reads byte by byte.  YUVPI: two dwords of Y, and of U and of V the near dword and the
-     * dword of the other row the filter mixes in (4:2:2 has no other row: far is near, loaded once) — the six dwords an 8-bit
-     * row holds — with the sample before and the one behind each as byte loads; taken only where that window lies inside the
-     * picture's chroma row (irun's test), the rest fills the same registers byte by byte with the clamps, at use. */
-    const int psx = YUVP || YUVPI ? hydk_planar_sx((int)job.sub) : 0, psy = YUVP || YUVPI ? hydk_planar_sy((int)job.sub) : 0;
-    const bool ylrun = (YUVP || YUVPI) && (((uintptr_t)job.src[0] | (uintptr_t)job.row_stride | (uintptr_t)job.src[1] |
-                                             (uintptr_t)job.src[2] | (uintptr_t)job.pixel_stride) & 3) == 0;
-    const bool ylirun = YUVPI && ylrun && (job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1;
-    const bool fast = (NV12 ? nvrun : NV12I ? irun : P016 ? prun : P016I ? pirun : YUVP ? ylrun : YUVPI ? ylirun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
+    /* YCbCr, every form: a block row is fetched as a WINDOW of dwords — its eight Y samples in nxt[0 ... kYW), and the chroma that
+     * serves them — when planes and pitches are dword multiples (a block's first column is a multiple of 8, its chroma column
+     * even); anything else reads sample by sample.  SB: bits of a sample; a dword holds kSPD samples or kPPD (U, V) pairs */
+    constexpr int SB = FMT == HYDK_FMT_U8 ? 8 : 16, kSPD = 32 / SB, kPPD = kSPD / 2, kYW = 8 / kSPD;
+    constexpr uint32_t kSMask = (1u << SB) - 1u;
+    const HydkYuvMatrix yuv = YUV && SB == 16 ? hydk_yuv16_job_matrix(job.matrix) : hydk_yuv_matrix(YUV ? (int)job.matrix : 0);
+    const int pcx = INTERP ? job.pic_cx0 + ((px0 + ab * 8) >> 1) : 0;
+    /* log2 of the pixels one chroma sample spans across and down: the job's subsampling for two planes, 4:2:0 for pairs */
+    const int csx = TWO_PLANES ? hydk_planar_sx((int)job.sub) : (int)YUV, csy = TWO_PLANES ? hydk_planar_sy((int)job.sub) : (int)YUV;
+    /* pairs in one plane (nvrun, prun): kYW dwords of Y and, from chroma row y >> 1, kYW dwords holding the block's four pairs */
+    const bool prun = YUV && !TWO_PLANES &&
+                      (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)(job.row_stride * (SB / 8))) & 3) == 0;
+    /* two planes (ylrun): two dwords of Y and, from each chroma plane, the dword of four samples that serves its eight pixels
+     * (the block's chroma column is a multiple of 4) — two dwords of eight for 4:4:4 */
+    const bool ylrun = TWO_PLANES && (((uintptr_t)job.src[0] | (uintptr_t)job.row_stride | (uintptr_t)job.src[1] |
+                                       (uintptr_t)job.src[2] | (uintptr_t)job.pixel_stride) & 3) == 0;
+    /* interpolated chroma (irun, pirun, ylirun): beside the near row's four chroma samples the window holds the same four of the
+     * far row — the one the filter mixes in: above for an even y, below for an odd one, clamped to the PICTURE's chroma rows;
+     * 4:2:2 has no other row: far is near — and of both rows the sample behind those four and (centre-sited) the one before
+     * them: six columns, p = 0 ... 5.  It comes as dwords only where all six lie inside the picture's chroma row; the picture's
+     * first and last chroma columns, a ragged last block and shifted bases or pitches fill the same window sample by sample with
+     * the clamps, at use (phase A below).  pcx: the picture's chroma column of the block's first pixel. */
+    const bool irun = (TWO_PLANES ? ylrun : prun) && (!INTERP || ((job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1));
+    const bool fast = (YUV ? irun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
     uint32_t nxt[kWords];
-    /* NV12I: the window's first pair | its last pair << 16, of the near and of the far chroma row.  P016I (a pair is a dword):
-     * the near row's first and last pair, then the far row's */
-    constexpr int kFlank = P016I ? 4 : 2;
+    /* the window's columns 0 and 5, which sit in no dword of the four between them (YUVPI: of U and of V, column 0 | column 5
+     * << 8 of the near row, the same << 16 of the far row) */
+    constexpr int kFlank = YUV && !TWO_PLANES ? 4 / kPPD : 2;
     uint32_t flank[kFlank] = {};
 #pragma unroll
     for (int k = 0; k < kWords; k++)
         nxt[k] = 0;
+    /* The window accessor of the forms with pairs in one plane (NV12I, P016I; nearest: columns 1 ... 4 of the near row alone):
+     * where chroma sample c (0: U, 1: V) of row r (0: near, 1: far) and column p sits — all the shared loops below know of a
+     * form.  nxt[kYW ...] holds the near row's columns 1 ... 4 as loaded, nxt[2 kYW ...] the far row's; flank columns 0 and 5
+     * of the near row, then of the far row, packed as pairs are. */
+    auto win_word = [&](int r, int p) -> uint32_t & {
+        const bool edge = p == 0 || p == 5;
+        const int k = edge ? 2 * r + (p == 5) : p - 1;
+        return edge ? flank[k / kPPD] : nxt[(1 + r) * kYW + k / kPPD];
+    };
+    auto win_shift = [](int c, int r, int p) -> int {
+        const bool edge = p == 0 || p == 5;
+        return 2 * SB * ((edge ? 2 * r + (p == 5) : p - 1) % kPPD) + SB * c;
+    };
+    auto win_get = [&](int c, int r, int p) -> uint32_t { return (win_word(r, p) >> win_shift(c, r, p)) & kSMask; };
+    auto win_put = [&](int c, int r, int p, uint32_t v) { win_word(r, p) |= v << win_shift(c, r, p); };
+    /* nearest chroma: sample c of pixel i's own column.  Two planes (YUVP): byte i >> 1 of nxt[2] (U) or nxt[3] (V), or (4:4:4, a
+     * sample a pixel) byte i of the two dwords a plane at nxt[2 + 2 c] */
+    auto near_get = [&](int c, int i) -> uint32_t {
+        if (!TWO_PLANES)
+            return win_get(c, 0, 1 + (i >> 1));
+        const uint32_t s2 = (nxt[2 + c] >> (8 * (i >> 1))) & 0xFF, s4 = (nxt[2 + 2 * c + (i >> 2)] >> (8 * (i & 3))) & 0xFF;
+        return csx ? s2 : s4;
+    };
+    /* the far chroma row of the LF group's row y: in picture coordinates, clamped there, and back relative to src[1] (may be -1:
+     * the LF group above) */
+    auto far_row = [&](long long y) -> long long {
+        return (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
+    };
     auto prefetch = [&](int s) {
-        if (P016 || P016I) {
+        if (YUV && !TWO_PLANES) {
             if (fast && s * 8 + ar < gh) {
+                typedef typename std::conditional<SB == 8, uint16_t, uint32_t>::type pair_t;
                 const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
-                const char *py = (const char *)job.src[0] + (y * job.row_stride + x) * 2;
-                const char *pn = (const char *)job.src[1] + ((y >> 1) * job.row_stride + x) * 2;
+                const char *py = (const char *)job.src[0] + (y * job.row_stride + x) * (SB / 8);
+                const char *pn = (const char *)job.src[1] + ((y >> 1) * job.row_stride + x) * (SB / 8);
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
+                for (int k = 0; k < kYW; k++) {
                     nxt[k] = HYDK_GLOBAL(const uint32_t, py)[k];
-                    nxt[4 + k] = HYDK_GLOBAL(const uint32_t, pn)[k];
+                    nxt[kYW + k] = HYDK_GLOBAL(const uint32_t, pn)[k];
                 }
-                if (P016I) {
-                    /* the far row in picture coordinates, clamped there, and back relative to src[1] (as NV12I's) */
-                    const long long fy = (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
-                    const char *pf = (const char *)job.src[1] + (fy * job.row_stride + x) * 2;
+                if (INTERP) {
+                    const char *pf = (const char *)job.src[1] + (far_row(y) * job.row_stride + x) * (SB / 8);
 #pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        nxt[8 + k] = HYDK_GLOBAL(const uint32_t, pf)[k];
-                    uint32_t bn = 0, bf = 0; /* (left-sited chroma never looks before the window) */
-                    if (job.filter == HYDK_CHROMA_CENTRE) {
-                        bn = HYDK_GLOBAL(const uint32_t, pn - 4)[0];
-                        bf = HYDK_GLOBAL(const uint32_t, pf - 4)[0];
+                    for (int k = 0; k < kYW; k++)
+                        nxt[2 * kYW + k] = HYDK_GLOBAL(const uint32_t, pf)[k];
+                    uint32_t fl[4] = {0, HYDK_GLOBAL(const pair_t, pn)[4], 0, HYDK_GLOBAL(const pair_t, pf)[4]};
+                    if (job.filter == HYDK_CHROMA_CENTRE) { /* (left-sited chroma never looks before the window) */
+                        fl[0] = HYDK_GLOBAL(const pair_t, pn - sizeof(pair_t))[0];
+                        fl[2] = HYDK_GLOBAL(const pair_t, pf - sizeof(pair_t))[0];
                     }
-                    flank[0] = bn;
-                    flank[1] = HYDK_GLOBAL(const uint32_t, pn + 16)[0];
-                    flank[kFlank - 2] = bf;
-                    flank[kFlank - 1] = HYDK_GLOBAL(const uint32_t, pf + 16)[0];
+#pragma unroll
+                    for (int k = 0; k < kFlank; k++)
+                        flank[k] = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) /* columns 0, 5 of the near row, then of the far row: win_word's order */
+                        flank[k / kPPD] |= fl[k] << (2 * SB * (k % kPPD));
                 }
             }
             return;
@@ -211,11 +235,11 @@
             if (fast && s * 8 + ar < gh) {
                 const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
                 const char *py = (const char *)job.src[0] + y * job.row_stride + x;
-                const long long co = (y >> psy) * job.pixel_stride + (x >> psx);
+                const long long co = (y >> csy) * job.pixel_stride + (x >> csx);
                 const char *pu = (const char *)job.src[1] + co, *pv = (const char *)job.src[2] + co;
                 nxt[0] = HYDK_GLOBAL(const uint32_t, py)[0];
                 nxt[1] = HYDK_GLOBAL(const uint32_t, py)[1];
-                if (psx) {
+                if (csx) {
                     nxt[2] = HYDK_GLOBAL(const uint32_t, pu)[0];
                     nxt[3] = HYDK_GLOBAL(const uint32_t, pv)[0];
                 } else {
@@ -231,8 +255,8 @@
             if (fast && s * 8 + ar < gh) {
                 const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
                 /* the far row in the picture's chroma rows, clamped there, and back relative to src[1] (4:2:2: the near row) */
-                const long long ny = y >> psy;
-                const long long fy = psy ? (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0 : ny;
+                const long long ny = y >> csy;
+                const long long fy = csy ? (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0 : ny;
                 const char *py = (const char *)job.src[0] + y * job.row_stride + x;
                 const long long on = ny * job.pixel_stride + (x >> 1), of = fy * job.pixel_stride + (x >> 1);
                 const char *un = (const char *)job.src[1] + on, *vn = (const char *)job.src[2] + on;
@@ -246,7 +270,7 @@
                     fu |= HYDK_GLOBAL(const uint8_t, un - 1)[0];
                     fv |= HYDK_GLOBAL(const uint8_t, vn - 1)[0];
                 }
-                if (psy) {
+                if (csy) {
                     const char *uf = (const char *)job.src[1] + of, *vf = (const char *)job.src[2] + of;
                     nxt[3] = HYDK_GLOBAL(const uint32_t, uf)[0];
                     nxt[5] = HYDK_GLOBAL(const uint32_t, vf)[0];
@@ -266,30 +290,6 @@
             }
             return;
         }
-        if (NV12I) {
-            if (fast && s * 8 + ar < gh) {
-                const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
-                /* the far row in picture coordinates, clamped there, and back relative to src[1] (may be -1: the LF group above) */
-                const long long fy = (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
-                const char *py = (const char *)job.src[0] + y * job.row_stride + x;
-                const char *pn = (const char *)job.src[1] + (y >> 1) * job.row_stride + x;
-                const char *pf = (const char *)job.src[1] + fy * job.row_stride + x;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    nxt[k] = HYDK_GLOBAL(const uint32_t, py)[k];
-                    nxt[2 + k] = HYDK_GLOBAL(const uint32_t, pn)[k];
-                    nxt[4 + k] = HYDK_GLOBAL(const uint32_t, pf)[k];
-                }
-                uint32_t bn = 0, bf = 0; /* (left-sited chroma never looks before the window) */
-                if (job.filter == HYDK_CHROMA_CENTRE) {
-                    bn = HYDK_GLOBAL(const uint16_t, pn - 2)[0];
-                    bf = HYDK_GLOBAL(const uint16_t, pf - 2)[0];
-                }
-                flank[0] = bn | (uint32_t)HYDK_GLOBAL(const uint16_t, pn + 8)[0] << 16;
-                flank[1] = bf | (uint32_t)HYDK_GLOBAL(const uint16_t, pf + 8)[0] << 16;
-            }
-            return;
-        }
         if (HALF) {
             if (hfast && s * 8 + ar < gh) {
                 const long long row = (long long)(py0 + s * 8 + ar) * job.row_stride;
@@ -306,19 +306,6 @@
                         for (int k = 0; k < 4; k++)
                             nxt[4 * c + k] = HYDK_GLOBAL(const uint32_t, p)[k];
                     }
-                }
-            }
-            return;
-        }
-        if (NV12) {
-            if (fast && s * 8 + ar < gh) {
-                const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
-                const char *py = (const char *)job.src[0] + y * job.row_stride + x;
-                const char *pc = (const char *)job.src[1] + (y >> 1) * job.row_stride + x;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    nxt[k] = HYDK_GLOBAL(const uint32_t, py)[k];
-                    nxt[2 + k] = HYDK_GLOBAL(const uint32_t, pc)[k];
                 }
             }
             return;
@@ -389,73 +376,44 @@
                     }
                 }
                 prefetch(s + 1);
-            } else if (fast || NV12I || P016I || YUVPI) {
-                /* NV12I rows that did not come as dwords — the picture's first and last chroma columns, a ragged last block,
-                 * shifted bases, odd pitches — fill the same window byte by byte, here, every pair's column clamped to the
-                 * picture's chroma row and the far row to its chroma rows: the picture's pair (0, 0) lies pic_cy0 rows and
-                 * pic_cx0 pairs before src[1].  Window pair p is the picture's column clamp(pcx - 1 + p, 0, cw - 1), which is
-                 * what cx, and hx with its clamp, come to for every pixel of the block.  The rest is shared with the dword rows. */
+            } else if (fast || INTERP) {
                 const int nvalid = row_ok ? min(8, gw - ab * 8) : 0;
-                if (NV12I && !fast) {
+                /* Interpolated rows that did not come as dwords — the picture's first and last chroma columns, a ragged last
+                 * block, shifted bases, odd pitches — fill the same window sample by sample, here, every column clamped to the
+                 * picture's chroma row and the far row to its chroma rows: the picture's chroma sample (0, 0) lies pic_cy0 rows
+                 * and pic_cx0 columns before src[1] (and src[2]).  Window column p is the picture's clamp(pcx - 1 + p, 0, cw - 1),
+                 * which is what cx, and hx with its clamp, come to for every pixel of the block.  The rest is shared with the
+                 * dword rows. */
+                if (INTERP && !YUVPI && !fast) {
 #pragma unroll
                     for (int k = 0; k < kWords; k++)
                         nxt[k] = 0;
-                    flank[0] = flank[1] = 0;
+#pragma unroll
+                    for (int k = 0; k < kFlank; k++)
+                        flank[k] = 0;
                     if (row_ok) {
-                        const uint8_t *py = (const uint8_t *)job.src[0] + (long long)y * job.row_stride + x0;
+                        const sample_t *py = (const sample_t *)job.src[0] + (long long)y * job.row_stride + x0;
 #pragma unroll
                         for (int i = 0; i < 8; i++)
                             if (i < nvalid)
-                                nxt[i >> 2] |= (uint32_t)py[i] << (8 * (i & 3));
-                        const uint8_t *org = (const uint8_t *)job.src[1] - 2ll * job.pic_cx0;
-                        const uint8_t *rn = org + (long long)(y >> 1) * job.row_stride;
-                        const uint8_t *rf = org + ((long long)hydk_chroma_vy(2 * job.pic_cy0 + y, job.pic_ch) - job.pic_cy0) * job.row_stride;
+                                nxt[i / kSPD] |= (uint32_t)py[i] << (SB * (i % kSPD));
+                        /* column 0 of the picture's near and far chroma row, U and V */
+                        const long long rows[2] = {y >> 1, far_row(y)};
+                        const sample_t *col0[2][2];
+#pragma unroll
+                        for (int r = 0; r < 2; r++)
+#pragma unroll
+                            for (int c = 0; c < 2; c++)
+                                col0[r][c] = (const sample_t *)job.src[1] + c + rows[r] * job.row_stride - 2ll * job.pic_cx0;
 #pragma unroll
                         for (int p = 0; p < 6; p++) {
                             const int col = min(max(pcx - 1 + p, 0), job.pic_cw - 1);
-                            const uint32_t pn = (uint32_t)rn[2 * col] | (uint32_t)rn[2 * col + 1] << 8;
-                            const uint32_t pf = (uint32_t)rf[2 * col] | (uint32_t)rf[2 * col + 1] << 8;
-                            if (p == 0 || p == 5) {
-                                flank[0] |= pn << (p ? 16 : 0);
-                                flank[1] |= pf << (p ? 16 : 0);
-                            } else {
-                                nxt[2 + ((p - 1) >> 1)] |= pn << (16 * ((p - 1) & 1));
-                                nxt[4 + ((p - 1) >> 1)] |= pf << (16 * ((p - 1) & 1));
-                            }
+#pragma unroll
+                            for (int r = 0; r < 2; r++)
+#pragma unroll
+                                for (int c = 0; c < 2; c++)
+                                    win_put(c, r, p, col0[r][c][2 * col]);
                         }
-                    }
-                }
-                /* P016I rows that did not come as dwords: the same window filled word by word, the same clamps */
-                if (P016I && !fast) {
-#pragma unroll
-                    for (int k = 0; k < kWords; k++)
-                        nxt[k] = 0;
-                    if (row_ok) {
-                        const uint16_t *py = (const uint16_t *)job.src[0] + (long long)y * job.row_stride + x0;
-#pragma unroll
-                        for (int i = 0; i < 8; i++)
-                            if (i < nvalid)
-                                nxt[i >> 1] |= (uint32_t)py[i] << (16 * (i & 1));
-                        const uint16_t *org = (const uint16_t *)job.src[1] - 2ll * job.pic_cx0;
-                        const uint16_t *rn = org + (long long)(y >> 1) * job.row_stride;
-                        const uint16_t *rf = org + ((long long)hydk_chroma_vy(2 * job.pic_cy0 + y, job.pic_ch) - job.pic_cy0) * job.row_stride;
-#pragma unroll
-                        for (int p = 0; p < 6; p++) {
-                            const int col = min(max(pcx - 1 + p, 0), job.pic_cw - 1);
-                            const uint32_t pn = (uint32_t)rn[2 * col] | (uint32_t)rn[2 * col + 1] << 16;
-                            const uint32_t pf = (uint32_t)rf[2 * col] | (uint32_t)rf[2 * col + 1] << 16;
-                            if (p == 0 || p == 5) {
-                                flank[p ? 1 : 0] = pn;
-                                flank[kFlank - (p ? 1 : 2)] = pf;
-                            } else {
-                                nxt[4 + (p - 1)] = pn;
-                                nxt[8 + (p - 1)] = pf;
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < kFlank; k++)
-                            flank[k] = 0;
                     }
                 }
                 /* YUVPI rows that did not come as dwords: each plane's window of six samples filled byte by byte, the same clamps,
@@ -472,8 +430,8 @@
                         for (int i = 0; i < 8; i++)
                             if (i < nvalid)
                                 nxt[i >> 2] |= (uint32_t)py[i] << (8 * (i & 3));
-                        const long long ny = y >> psy;
-                        const long long fy = psy ? (long long)hydk_chroma_vy(2 * job.pic_cy0 + y, job.pic_ch) - job.pic_cy0 : ny;
+                        const long long ny = y >> csy;
+                        const long long fy = csy ? (long long)hydk_chroma_vy(2 * job.pic_cy0 + y, job.pic_ch) - job.pic_cy0 : ny;
                         const long long on = ny * job.pixel_stride - job.pic_cx0, of = fy * job.pixel_stride - job.pic_cx0;
                         const uint8_t *un = (const uint8_t *)job.src[1] + on, *uf = (const uint8_t *)job.src[1] + of;
                         const uint8_t *vn = (const uint8_t *)job.src[2] + on, *vf = (const uint8_t *)job.src[2] + of;
@@ -493,144 +451,75 @@
                         }
                     }
                 }
-                /* NV12: the eight pixels of the four fetched dwords, converted and packed as an interleaved RGB row has them */
+                /* YCbCr: the eight pixels of the window, converted and packed as an interleaved RGB row of the class has them */
                 uint32_t cvt[kWords];
-                if (YUVP) { /* a pixel's U and V: byte i >> 1 of one dword each, or (4:4:4) byte i of two dwords each */
+                if (YUV) {
 #pragma unroll
                     for (int k = 0; k < kWords; k++)
                         cvt[k] = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const uint32_t u2 = (nxt[2] >> (8 * (i >> 1))) & 0xFF, v2 = (nxt[3] >> (8 * (i >> 1))) & 0xFF;
-                        const uint32_t u4 = (nxt[2 + (i >> 2)] >> (8 * (i & 3))) & 0xFF, v4 = (nxt[4 + (i >> 2)] >> (8 * (i & 3))) & 0xFF;
+                    auto convert = [&](int i, uint32_t u, uint32_t v) {
+                        const uint32_t luma = (nxt[i / kSPD] >> (SB * (i % kSPD))) & kSMask;
                         uint32_t rgb[3];
-                        hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, psx ? u2 : u4, psx ? v2 : v4, rgb);
+                        if (SB == 8)
+                            hydk_yuv_to_rgb(yuv, luma, u, v, rgb);
+                        else
+                            hydk_yuv16_to_rgb(yuv, luma, u, v, rgb);
 #pragma unroll
                         for (int ch = 0; ch < 3; ch++) {
                             const int si = i * 3 + ch;
-                            cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
+                            cvt[si / kSPD] |= rgb[ch] << (SB * (si % kSPD));
                         }
+                    };
+                    if (YUVPI) {
+                        /* NV12I's vertical mix, horizontal mix, conversion and pack, the window's samples taken plane by plane */
+                        uint32_t vu[6], vv[6];
+#pragma unroll
+                        for (int p = 0; p < 6; p++) {
+                            const int sh = 8 * (p - 1);
+                            const uint32_t a = p == 0 ? flank[0] : p == 5 ? flank[0] >> 8 : nxt[2] >> sh;
+                            const uint32_t b = p == 0 ? flank[0] >> 16 : p == 5 ? flank[0] >> 24 : nxt[3] >> sh;
+                            const uint32_t c = p == 0 ? flank[1] : p == 5 ? flank[1] >> 8 : nxt[4] >> sh;
+                            const uint32_t d = p == 0 ? flank[1] >> 16 : p == 5 ? flank[1] >> 24 : nxt[5] >> sh;
+                            vu[p] = hydk_chroma_vmix(a & 0xFF, b & 0xFF);
+                            vv[p] = hydk_chroma_vmix(c & 0xFF, d & 0xFF);
+                        }
+                        const int filter = (int)job.filter;
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            const int j = 1 + (i >> 1), hc = (i & 1) ? j + 1 : j - 1, hl = j + (i & 1);
+                            const uint32_t u = hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]);
+                            const uint32_t v = hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]);
+                            uint32_t rgb[3];
+                            hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, u, v, rgb);
+#pragma unroll
+                            for (int ch = 0; ch < 3; ch++) {
+                                const int si = i * 3 + ch;
+                                cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
+                            }
+                        }
+                    } else if (INTERP) {
+                        /* the vertical mix of the window's six columns, then per pixel the horizontal mix with the neighbour its
+                         * filter names, the conversion, the pack */
+                        uint32_t vu[6], vv[6];
+#pragma unroll
+                        for (int p = 0; p < 6; p++) {
+                            vu[p] = hydk_chroma_vmix(win_get(0, 0, p), win_get(0, 1, p));
+                            vv[p] = hydk_chroma_vmix(win_get(1, 0, p), win_get(1, 1, p));
+                        }
+                        const int filter = (int)job.filter;
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            const int j = 1 + (i >> 1), hc = (i & 1) ? j + 1 : j - 1, hl = j + (i & 1);
+                            convert(i, hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]),
+                                    hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]));
+                        }
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            convert(i, near_get(0, i), near_get(1, i));
                     }
                 }
-                if (YUVPI) {
-                    /* NV12I's vertical mix, horizontal mix, conversion and pack, the window's samples taken plane by plane */
-                    uint32_t vu[6], vv[6];
-#pragma unroll
-                    for (int p = 0; p < 6; p++) {
-                        const int sh = 8 * (p - 1);
-                        const uint32_t a = p == 0 ? flank[0] : p == 5 ? flank[0] >> 8 : nxt[2] >> sh;
-                        const uint32_t b = p == 0 ? flank[0] >> 16 : p == 5 ? flank[0] >> 24 : nxt[3] >> sh;
-                        const uint32_t c = p == 0 ? flank[1] : p == 5 ? flank[1] >> 8 : nxt[4] >> sh;
-                        const uint32_t d = p == 0 ? flank[1] >> 16 : p == 5 ? flank[1] >> 24 : nxt[5] >> sh;
-                        vu[p] = hydk_chroma_vmix(a & 0xFF, b & 0xFF);
-                        vv[p] = hydk_chroma_vmix(c & 0xFF, d & 0xFF);
-                    }
-                    const int filter = (int)job.filter;
-#pragma unroll
-                    for (int k = 0; k < kWords; k++)
-                        cvt[k] = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const int j = 1 + (i >> 1), hc = (i & 1) ? j + 1 : j - 1, hl = j + (i & 1);
-                        const uint32_t u = hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]);
-                        const uint32_t v = hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]);
-                        uint32_t rgb[3];
-                        hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, u, v, rgb);
-#pragma unroll
-                        for (int ch = 0; ch < 3; ch++) {
-                            const int si = i * 3 + ch;
-                            cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
-                        }
-                    }
-                }
-                if (P016) { /* eight pixels of four Y dwords and four pair dwords (U | V << 16), as an interleaved RGB16 row */
-#pragma unroll
-                    for (int k = 0; k < kWords; k++)
-                        cvt[k] = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        uint32_t rgb[3];
-                        hydk_yuv16_to_rgb(yuv, (nxt[i >> 1] >> (16 * (i & 1))) & 0xFFFF, nxt[4 + (i >> 1)] & 0xFFFF, nxt[4 + (i >> 1)] >> 16, rgb);
-#pragma unroll
-                        for (int ch = 0; ch < 3; ch++) {
-                            const int si = i * 3 + ch;
-                            cvt[si >> 1] |= rgb[ch] << (16 * (si & 1));
-                        }
-                    }
-                }
-                if (P016I) { /* NV12I's vertical mix, horizontal mix, conversion and pack on 16-bit samples */
-                    uint32_t vu[6], vv[6];
-#pragma unroll
-                    for (int p = 0; p < 6; p++) {
-                        const uint32_t pn = p == 0 ? flank[0] : p == 5 ? flank[1] : nxt[4 + (p - 1)];
-                        const uint32_t pf = p == 0 ? flank[kFlank - 2] : p == 5 ? flank[kFlank - 1] : nxt[8 + (p - 1)];
-                        vu[p] = hydk_chroma_vmix(pn & 0xFFFF, pf & 0xFFFF);
-                        vv[p] = hydk_chroma_vmix(pn >> 16, pf >> 16);
-                    }
-                    const int filter = (int)job.filter;
-#pragma unroll
-                    for (int k = 0; k < kWords; k++)
-                        cvt[k] = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const int j = 1 + (i >> 1), hc = (i & 1) ? j + 1 : j - 1, hl = j + (i & 1);
-                        const uint32_t u = hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]);
-                        const uint32_t v = hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]);
-                        uint32_t rgb[3];
-                        hydk_yuv16_to_rgb(yuv, (nxt[i >> 1] >> (16 * (i & 1))) & 0xFFFF, u, v, rgb);
-#pragma unroll
-                        for (int ch = 0; ch < 3; ch++) {
-                            const int si = i * 3 + ch;
-                            cvt[si >> 1] |= rgb[ch] << (16 * (si & 1));
-                        }
-                    }
-                }
-                if (NV12) {
-#pragma unroll
-                    for (int k = 0; k < kWords; k++)
-                        cvt[k] = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        uint32_t rgb[3];
-                        hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, (nxt[2 + (i >> 2)] >> (8 * (i & 2))) & 0xFF,
-                                        (nxt[2 + (i >> 2)] >> (8 * (i & 2) + 8)) & 0xFF, rgb);
-#pragma unroll
-                        for (int ch = 0; ch < 3; ch++) {
-                            const int si = i * 3 + ch;
-                            cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
-                        }
-                    }
-                }
-                if (NV12I) {
-                    /* the vertical mix of the window's six pairs (index 0: the pair before the block's four; 5: the one
-                     * behind), then per pixel the horizontal mix with the neighbour its filter names, the conversion, the pack */
-                    uint32_t vu[6], vv[6];
-#pragma unroll
-                    for (int p = 0; p < 6; p++) {
-                        const uint32_t pn = p == 0 ? flank[0] : p == 5 ? flank[0] >> 16 : nxt[2 + ((p - 1) >> 1)] >> (16 * ((p - 1) & 1));
-                        const uint32_t pf = p == 0 ? flank[1] : p == 5 ? flank[1] >> 16 : nxt[4 + ((p - 1) >> 1)] >> (16 * ((p - 1) & 1));
-                        vu[p] = hydk_chroma_vmix(pn & 0xFF, pf & 0xFF);
-                        vv[p] = hydk_chroma_vmix((pn >> 8) & 0xFF, (pf >> 8) & 0xFF);
-                    }
-                    const int filter = (int)job.filter;
-#pragma unroll
-                    for (int k = 0; k < kWords; k++)
-                        cvt[k] = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const int j = 1 + (i >> 1), hc = (i & 1) ? j + 1 : j - 1, hl = j + (i & 1);
-                        const uint32_t u = hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]);
-                        const uint32_t v = hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]);
-                        uint32_t rgb[3];
-                        hydk_yuv_to_rgb(yuv, (nxt[i >> 2] >> (8 * (i & 3))) & 0xFF, u, v, rgb);
-#pragma unroll
-                        for (int ch = 0; ch < 3; ch++) {
-                            const int si = i * 3 + ch;
-                            cvt[si >> 2] |= rgb[ch] << (8 * (si & 3));
-                        }
-                    }
-                }
-                uint32_t(&w)[kWords] = NV12 || NV12I || P016 || P016I || YUVP || YUVPI ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
+                uint32_t(&w)[kWords] = YUV ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
                 /* which form of the transfer curve this wavefront's 16-bit samples need (wave-uniform) */
                 int curve = kCurveBoth;
                 if (FMT == HYDK_FMT_U16 && !LUTS) {
@@ -744,7 +633,7 @@
                         row_to_xyb(std::integral_constant<int, kCurveNone>());
                     else
                         row_to_xyb(std::integral_constant<int, kCurveBoth>());
-                    if (NV12I || P016I || YUVPI) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
+                    if (INTERP) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
 #pragma unroll
                         for (int i = 0; i < 8; i++)
                             if (i >= nvalid)
@@ -764,12 +653,12 @@
                 for (int i = 0; i < 8; i++) {
                     xv[i] = yv[i] = bv[i] = 0.0f; /* edge padding is XYB = 0 (format.c:182-191) */
                     if (i < nvalid) {
-                        const long long off = (long long)y * job.row_stride + (long long)(x0 + i) * (YUVP ? 1ll : job.pixel_stride);
-                        /* (NV12: the pixel's Y; its U and V sit in chroma row y >> 1 at the even byte x & ~1 and behind it.
-                         * YUVP: in row y >> sy, byte x >> sx of their own planes, whose pitch the pixel stride carries) */
-                        const long long offc = YUVP            ? (long long)(y >> psy) * job.pixel_stride + (long long)((x0 + i) >> psx)
-                                               : NV12 || P016 ? (long long)(y >> 1) * job.row_stride + (long long)((x0 + i) & ~1)
-                                                              : off;
+                        const long long off = (long long)y * job.row_stride + (long long)(x0 + i) * (TWO_PLANES ? 1ll : job.pixel_stride);
+                        /* (pairs in one plane: the pixel's Y; its U and V sit in chroma row y >> 1 at the even sample x & ~1 and
+                         * behind it.  Two planes: in row y >> sy, byte x >> sx of their own planes, whose pitch the pixel stride carries) */
+                        const long long offc = TWO_PLANES ? (long long)(y >> csy) * job.pixel_stride + (long long)((x0 + i) >> csx)
+                                               : YUV      ? (long long)(y >> 1) * job.row_stride + (long long)((x0 + i) & ~1)
+                                                          : off;
                         const sample_t sr = ((const sample_t *)job.src[0])[off];
                         const sample_t sg = ((const sample_t *)job.src[1])[offc];
                         const sample_t sb = ((const sample_t *)job.src[2])[offc];
@@ -785,9 +674,9 @@
                             float_pixel(fr, fg, fb, xv[i], yv[i], bv[i]);
                         } else {
                             uint32_t rgb[3] = {(uint32_t)sr, (uint32_t)sg, (uint32_t)sb};
-                            if (NV12 || YUVP)
+                            if (YUV && SB == 8)
                                 hydk_yuv_to_rgb(yuv, (uint32_t)sr, (uint32_t)sg, (uint32_t)sb, rgb);
-                            if (P016)
+                            if (YUV && SB == 16)
                                 hydk_yuv16_to_rgb(yuv, (uint32_t)sr, (uint32_t)sg, (uint32_t)sb, rgb);
 #pragma unroll
                             for (int ch = 0; ch < 3; ch++) {

@@ -2373,164 +2373,70 @@ __global__ void k_lut_selftest(const uint16_t *in_lut16, const float *bias_lut, 
  * ---------------------------------------------------------------------------------------- */
 namespace hydk {
 
+typedef void (*K1Fn)(const HydkLfJob *, uint32_t *, uint2 *, int);
+
+/* The K1 instance that owns the jobs of one sample class and storage form under an XYB mode: the one place that knows which
+ * instances exist.  The RGB classes take all five modes; the YCbCr forms the mode's arithmetic (the all-register variants, 3
+ * and 4: dense content, differ from 0 and 1 in where a curve value comes from, never in its bits); the float class IeeeDiv only. */
+template <int XM>
+static K1Fn k1_of_mode(int fmt, int storage) {
+    constexpr int A = xyb_arith(XM);
+    switch (storage) {
+    case HYDK_STORE_F16:
+        return k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, HYDK_STORE_F16>;
+    case HYDK_STORE_BF16:
+        return k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, HYDK_STORE_BF16>;
+    case HYDK_STORE_NV12:
+        return k_transform_tokenize<HYDK_FMT_U8, A, HYDK_STORE_NV12>;
+    case HYDK_STORE_NV12I:
+        return k_transform_tokenize<HYDK_FMT_U8, A, HYDK_STORE_NV12I>;
+    case HYDK_STORE_P016:
+        return k_transform_tokenize_p016<A, HYDK_STORE_P016>;
+    case HYDK_STORE_P016I:
+        return k_transform_tokenize_p016<A, HYDK_STORE_P016I>;
+    case HYDK_STORE_YUVP:
+        return k_transform_tokenize_planar<A, HYDK_STORE_YUVP>;
+    case HYDK_STORE_YUVPI:
+        return k_transform_tokenize_planar<A, HYDK_STORE_YUVPI>;
+    }
+    return fmt == HYDK_FMT_U8    ? k_transform_tokenize<HYDK_FMT_U8, XM>
+           : fmt == HYDK_FMT_U16 ? k_transform_tokenize<HYDK_FMT_U16, XM>
+                                 : k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv>;
+}
+static K1Fn k1_instance(int fmt, int storage, int xmode) {
+    switch (xmode) {
+    case kXybFastRcp:
+        return k1_of_mode<kXybFastRcp>(fmt, storage);
+    case kXybIeeeDiv:
+        return k1_of_mode<kXybIeeeDiv>(fmt, storage);
+    case kXybFastRcpRegs:
+        return k1_of_mode<kXybFastRcpRegs>(fmt, storage);
+    case kXybIeeeDivRegs:
+        return k1_of_mode<kXybIeeeDivRegs>(fmt, storage);
+    }
+    return k1_of_mode<kXybGather>(fmt, storage);
+}
+
 /* One launch per template instance that owns at least one LF group of this round; an instance
  * returns at once for the LF groups of another sample format.  fmt_mask: bits 0, 1 the integer classes' own samples, bits
- * 2 + HYDK_STORE_* the storage forms: the float class's three, NV12, NV12I, YUVP and YUVPI of the 8-bit class, P016 and P016I of
- * the 16-bit. */
+ * 2 + HYDK_STORE_* the storage forms (hydk_store.h); launched in the order of the bits. */
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream) {
     const dim3 grid((num_slots * HYDK_GROUPS_PER_LFG) << plog), block(kThreads);
-#define HYDK_LAUNCH_K1(FMT, XM) hipLaunchKernelGGL((k_transform_tokenize<FMT, XM>), grid, block, 0, stream, d_jobs, status, part_info, plog)
-#define HYDK_LAUNCH_K1_MODES(FMT)              \
-    do {                                       \
-        if (xmode == kXybFastRcp)              \
-            HYDK_LAUNCH_K1(FMT, kXybFastRcp);  \
-        else if (xmode == kXybIeeeDiv)         \
-            HYDK_LAUNCH_K1(FMT, kXybIeeeDiv);  \
-        else if (xmode == kXybFastRcpRegs)     \
-            HYDK_LAUNCH_K1(FMT, kXybFastRcpRegs); \
-        else if (xmode == kXybIeeeDivRegs)     \
-            HYDK_LAUNCH_K1(FMT, kXybIeeeDivRegs); \
-        else                                   \
-            HYDK_LAUNCH_K1(FMT, kXybGather);   \
-    } while (0)
-    if (fmt_mask & (1u << HYDK_FMT_U8))
-        HYDK_LAUNCH_K1_MODES(HYDK_FMT_U8);
-    if (fmt_mask & (1u << HYDK_FMT_U16))
-        HYDK_LAUNCH_K1_MODES(HYDK_FMT_U16);
-    /* the float class: one instance per storage form (bit HYDK_FMT_F32 + HYDK_STORE_* of the mask) */
-#define HYDK_LAUNCH_K1_FLOAT(STORE)                       \
-    if (fmt_mask & (1u << (HYDK_FMT_F32 + (STORE))))      \
-    hipLaunchKernelGGL((k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog)
-    HYDK_LAUNCH_K1_FLOAT(HYDK_STORE_F32);
-    HYDK_LAUNCH_K1_FLOAT(HYDK_STORE_F16);
-    HYDK_LAUNCH_K1_FLOAT(HYDK_STORE_BF16);
-#undef HYDK_LAUNCH_K1_FLOAT
-    /* NV12: the 8-bit class's three XYB modes; the all-register variants (3, 4: dense content) differ from 0 and 1 in where a
-     * curve value comes from, never in its bits, and NV12 keeps to the three */
-    if (fmt_mask & (1u << (HYDK_FMT_F32 + HYDK_STORE_NV12))) {
-#define HYDK_LAUNCH_K1_NV12(XM) \
-    hipLaunchKernelGGL((k_transform_tokenize<HYDK_FMT_U8, XM, HYDK_STORE_NV12>), grid, block, 0, stream, d_jobs, status, part_info, plog)
-        if (xyb_arith(xmode) == kXybFastRcp)
-            HYDK_LAUNCH_K1_NV12(kXybFastRcp);
-        else if (xyb_arith(xmode) == kXybIeeeDiv)
-            HYDK_LAUNCH_K1_NV12(kXybIeeeDiv);
-        else
-            HYDK_LAUNCH_K1_NV12(kXybGather);
-#undef HYDK_LAUNCH_K1_NV12
-    }
-    /* NV12 with interpolated chroma: the same three modes, one instance each for both filters (a job field) */
-    if (fmt_mask & (1u << (HYDK_FMT_F32 + HYDK_STORE_NV12I))) {
-#define HYDK_LAUNCH_K1_NV12I(XM) \
-    hipLaunchKernelGGL((k_transform_tokenize<HYDK_FMT_U8, XM, HYDK_STORE_NV12I>), grid, block, 0, stream, d_jobs, status, part_info, plog)
-        if (xyb_arith(xmode) == kXybFastRcp)
-            HYDK_LAUNCH_K1_NV12I(kXybFastRcp);
-        else if (xyb_arith(xmode) == kXybIeeeDiv)
-            HYDK_LAUNCH_K1_NV12I(kXybIeeeDiv);
-        else
-            HYDK_LAUNCH_K1_NV12I(kXybGather);
-#undef HYDK_LAUNCH_K1_NV12I
-    }
-    /* P016 and P016I of the 16-bit class: three modes each, under their own kernel name */
-#define HYDK_LAUNCH_K1_P016(STORE)                                                                                                          \
-    if (fmt_mask & (1u << (HYDK_FMT_F32 + (STORE)))) {                                                                                      \
-        if (xyb_arith(xmode) == kXybFastRcp)                                                                                                \
-            hipLaunchKernelGGL((k_transform_tokenize_p016<kXybFastRcp, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog); \
-        else if (xyb_arith(xmode) == kXybIeeeDiv)                                                                                           \
-            hipLaunchKernelGGL((k_transform_tokenize_p016<kXybIeeeDiv, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog); \
-        else                                                                                                                                \
-            hipLaunchKernelGGL((k_transform_tokenize_p016<kXybGather, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog);  \
-    }
-    HYDK_LAUNCH_K1_P016(HYDK_STORE_P016)
-    HYDK_LAUNCH_K1_P016(HYDK_STORE_P016I)
-#undef HYDK_LAUNCH_K1_P016
-    /* planar YCbCr of the 8-bit class, nearest and interpolated: three modes each, under their own kernel name */
-#define HYDK_LAUNCH_K1_PLANAR(STORE)                                                                                                          \
-    if (fmt_mask & (1u << (HYDK_FMT_F32 + (STORE)))) {                                                                                        \
-        if (xyb_arith(xmode) == kXybFastRcp)                                                                                                  \
-            hipLaunchKernelGGL((k_transform_tokenize_planar<kXybFastRcp, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog); \
-        else if (xyb_arith(xmode) == kXybIeeeDiv)                                                                                             \
-            hipLaunchKernelGGL((k_transform_tokenize_planar<kXybIeeeDiv, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog); \
-        else                                                                                                                                  \
-            hipLaunchKernelGGL((k_transform_tokenize_planar<kXybGather, STORE>), grid, block, 0, stream, d_jobs, status, part_info, plog);  \
-    }
-    HYDK_LAUNCH_K1_PLANAR(HYDK_STORE_YUVP)
-    HYDK_LAUNCH_K1_PLANAR(HYDK_STORE_YUVPI)
-#undef HYDK_LAUNCH_K1_PLANAR
-#undef HYDK_LAUNCH_K1_MODES
-#undef HYDK_LAUNCH_K1
+    for (int bit = 0; bit < HYDK_FMT_F32 + HYDK_STORE_FORMS; bit++)
+        if (fmt_mask & (1u << bit)) {
+            const int storage = bit < HYDK_FMT_F32 ? HYDK_STORE_F32 : bit - HYDK_FMT_F32;
+            const K1Fn k1 = k1_instance(bit < HYDK_FMT_F32 ? bit : hydk_store_form(storage).cls, storage, xmode);
+            hipLaunchKernelGGL(k1, grid, block, 0, stream, d_jobs, status, part_info, plog);
+        }
     if (plog)
         hipLaunchKernelGGL(k_join_parts, dim3(num_slots * HYDK_GROUPS_PER_LFG), block, 0, stream, d_jobs, part_info, plog, status);
     return hipGetLastError();
 }
 
+/* xmode: the context's XYB mode, 0 ... 2 */
 hipError_t transform_footprint(int fmt, int storage, int xmode, int *lds_bytes, int *registers) {
-    const void *fn = nullptr;
-#define HYDK_K1_PTR(FMT, XM) fn = (const void *)k_transform_tokenize<FMT, XM>
-    if (fmt == HYDK_FMT_F32 && storage == HYDK_STORE_F16)
-        fn = (const void *)k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, HYDK_STORE_F16>;
-    else if (fmt == HYDK_FMT_F32 && storage == HYDK_STORE_BF16)
-        fn = (const void *)k_transform_tokenize<HYDK_FMT_F32, kXybIeeeDiv, HYDK_STORE_BF16>;
-    else if (fmt == HYDK_FMT_F32)
-        HYDK_K1_PTR(HYDK_FMT_F32, kXybIeeeDiv);
-    else if (fmt == HYDK_FMT_U8 && storage == HYDK_STORE_NV12) {
-        if (xmode == kXybFastRcp)
-            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybFastRcp, HYDK_STORE_NV12>;
-        else if (xmode == kXybIeeeDiv)
-            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybIeeeDiv, HYDK_STORE_NV12>;
-        else
-            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybGather, HYDK_STORE_NV12>;
-    } else if (fmt == HYDK_FMT_U8 && storage == HYDK_STORE_NV12I) {
-        if (xmode == kXybFastRcp)
-            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybFastRcp, HYDK_STORE_NV12I>;
-        else if (xmode == kXybIeeeDiv)
-            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybIeeeDiv, HYDK_STORE_NV12I>;
-        else
-            fn = (const void *)k_transform_tokenize<HYDK_FMT_U8, kXybGather, HYDK_STORE_NV12I>;
-    } else if (fmt == HYDK_FMT_U16 && storage == HYDK_STORE_P016) {
-        if (xmode == kXybFastRcp)
-            fn = (const void *)k_transform_tokenize_p016<kXybFastRcp, HYDK_STORE_P016>;
-        else if (xmode == kXybIeeeDiv)
-            fn = (const void *)k_transform_tokenize_p016<kXybIeeeDiv, HYDK_STORE_P016>;
-        else
-            fn = (const void *)k_transform_tokenize_p016<kXybGather, HYDK_STORE_P016>;
-    } else if (fmt == HYDK_FMT_U16 && storage == HYDK_STORE_P016I) {
-        if (xmode == kXybFastRcp)
-            fn = (const void *)k_transform_tokenize_p016<kXybFastRcp, HYDK_STORE_P016I>;
-        else if (xmode == kXybIeeeDiv)
-            fn = (const void *)k_transform_tokenize_p016<kXybIeeeDiv, HYDK_STORE_P016I>;
-        else
-            fn = (const void *)k_transform_tokenize_p016<kXybGather, HYDK_STORE_P016I>;
-    } else if (fmt == HYDK_FMT_U8 && storage == HYDK_STORE_YUVP) {
-        if (xmode == kXybFastRcp)
-            fn = (const void *)k_transform_tokenize_planar<kXybFastRcp, HYDK_STORE_YUVP>;
-        else if (xmode == kXybIeeeDiv)
-            fn = (const void *)k_transform_tokenize_planar<kXybIeeeDiv, HYDK_STORE_YUVP>;
-        else
-            fn = (const void *)k_transform_tokenize_planar<kXybGather, HYDK_STORE_YUVP>;
-    } else if (fmt == HYDK_FMT_U8 && storage == HYDK_STORE_YUVPI) {
-        if (xmode == kXybFastRcp)
-            fn = (const void *)k_transform_tokenize_planar<kXybFastRcp, HYDK_STORE_YUVPI>;
-        else if (xmode == kXybIeeeDiv)
-            fn = (const void *)k_transform_tokenize_planar<kXybIeeeDiv, HYDK_STORE_YUVPI>;
-        else
-            fn = (const void *)k_transform_tokenize_planar<kXybGather, HYDK_STORE_YUVPI>;
-    } else if (fmt == HYDK_FMT_U8) {
-        if (xmode == kXybFastRcp)
-            HYDK_K1_PTR(HYDK_FMT_U8, kXybFastRcp);
-        else if (xmode == kXybIeeeDiv)
-            HYDK_K1_PTR(HYDK_FMT_U8, kXybIeeeDiv);
-        else
-            HYDK_K1_PTR(HYDK_FMT_U8, kXybGather);
-    } else {
-        if (xmode == kXybFastRcp)
-            HYDK_K1_PTR(HYDK_FMT_U16, kXybFastRcp);
-        else if (xmode == kXybIeeeDiv)
-            HYDK_K1_PTR(HYDK_FMT_U16, kXybIeeeDiv);
-        else
-            HYDK_K1_PTR(HYDK_FMT_U16, kXybGather);
-    }
-#undef HYDK_K1_PTR
+    const void *fn = (const void *)k1_instance(fmt, storage, xmode);
     hipFuncAttributes attr;
     const hipError_t e = hipFuncGetAttributes(&attr, fn);
     if (e == hipSuccess) {

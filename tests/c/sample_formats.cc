@@ -1,6 +1,6 @@
 /*
  * sample_formats.cc — the sample-format headers that host and device share (csrc/hyd_sample_fmt.h, csrc/hip/hydk_half.h,
- * hydk_yuv.h, hydk_yuv16.h, hydk_chroma.h) as plain C++, no HIP header in sight, built by tests/test_host_sanitizers.py with
+ * hydk_yuv.h, hydk_yuv16.h, hydk_chroma.h, hydk_store.h) as plain C++, no HIP header in sight, built by tests/test_host_sanitizers.py with
  * -fsanitize=address,undefined and held to the numpy models (tests/yuv_model.py, p016_model.py, chroma_model.py,
  * pixel_layouts.widen_half_bits).  Each mode writes its results to OUT as raw native-endian arrays:
  *
@@ -10,7 +10,7 @@
  *   sample_formats chroma OUT IN       IN: u32 cases, then per case u32 bits (8, 16), filter, w, h and the chroma plane
  *                                      ceil(h / 2) x ceil(w / 2) x 2 samples; OUT: per case h x w x 2 samples
  *   sample_formats formats OUT         int32[FMT_HI - FMT_LO][12] predicates of csrc/hyd_sample_fmt.h, then int64[cases][3]
- *                                      origin offsets
+ *                                      origin offsets; before it writes, the round trip of csrc/hip/hydk_store.h
  * Every chroma plane is a malloc of exactly its samples: a tap that leaves the plane meets the redzone.
  */
 #include <cstdint>
@@ -23,6 +23,7 @@
 #include "hip/hydk_yuv.h"
 #include "hip/hydk_chroma.h"
 #include "hip/hydk_yuv16.h"
+#include "hip/hydk_store.h"
 
 static void die(const char *what) {
     std::fprintf(stderr, "sample_formats: %s\n", what);
@@ -145,7 +146,43 @@ static void chroma(std::FILE *out, const char *in) {
 
 enum { FMT_LO = -8, FMT_HI = 264 };
 
+/* csrc/hip/hydk_store.h: every format a device entry point takes encodes back to itself after the decode, and every other
+ * number of 0 ... 1023 is refused: these two hold whatever the decode is built from.  The field checks below compare it with
+ * the hyd_fmt_* predicates it calls itself — a guard against a slip in the table, not an independent definition (what a
+ * job's fields mean is held to the reference's files by the GPU suites of the four families) */
+static void round_trip() {
+    for (int fmt = 0; fmt < 1024; fmt++) {
+        const HydkSampleForm d = hydk_decode_fmt(fmt);
+        if (!hyd_fmt_is_device(fmt)) {
+            if (d.ok || d.cls || d.storage || d.matrix || d.filter || d.sub)
+                die("hydk_decode_fmt takes a number that names no device format");
+            continue;
+        }
+        if (!d.ok || hydk_encode_fmt(d) != fmt)
+            die("a device format does not come back from hydk_decode_fmt and hydk_encode_fmt");
+        const HydkStoreForm form = hydk_store_form((int)d.storage);
+        const int yuv = hyd_fmt_is_yuv420(fmt) || hyd_fmt_is_planar_yuv(fmt);
+        if (d.cls != (hyd_fmt_is_float(fmt) ? HYDK_FMT_F32 : hyd_fmt_bytes(fmt) == 1 ? HYDK_FMT_U8 : HYDK_FMT_U16) ||
+            (d.storage != HYDK_STORE_F32 && form.cls != d.cls))
+            die("hydk_decode_fmt: class");
+        if (form.ycbcr != yuv || form.interp != (hyd_fmt_is_yuv420_interp(fmt) || hyd_fmt_is_planar_interp(fmt)) ||
+            (yuv && form.bits != 8 * (int)hyd_fmt_bytes(fmt)) || (yuv && form.chroma_planes != (hyd_fmt_is_planar_yuv(fmt) ? 2 : 1)) ||
+            (!yuv && d.storage != (uint32_t)(fmt == HYD_FMT_FLOAT16 ? HYDK_STORE_F16 : fmt == HYD_FMT_BFLOAT16 ? HYDK_STORE_BF16 : HYDK_STORE_F32)))
+            die("hydk_decode_fmt: storage form");
+        if (hyd_fmt_is_planar_yuv(fmt) &&
+            (d.matrix != (uint32_t)hyd_fmt_planar_matrix(fmt) || d.filter != (uint32_t)hyd_fmt_planar_filter(fmt) ||
+             d.sub != (uint32_t)hyd_fmt_planar_sub(fmt) || d.sx != hyd_fmt_planar_sx(fmt) || d.sy != hyd_fmt_planar_sy(fmt)))
+            die("hydk_decode_fmt: planar fields");
+        if (hyd_fmt_is_yuv420(fmt) && (d.matrix != (uint32_t)(hyd_fmt_p016_matrix(fmt) + 4 * hyd_fmt_p016_depth(fmt)) ||
+                                       d.filter != (uint32_t)hyd_fmt_p016_filter(fmt) || d.sub || d.sx != 1 || d.sy != 1))
+            die("hydk_decode_fmt: 4:2:0 fields");
+        if (!yuv && (d.matrix || d.filter || d.sub || d.sx || d.sy))
+            die("hydk_decode_fmt: an RGB format has no YCbCr fields");
+    }
+}
+
 static void formats(std::FILE *out) {
+    round_trip();
     for (int fmt = FMT_LO; fmt < FMT_HI; fmt++) {
         const int32_t row[12] = {hyd_fmt_is_nv12(fmt),        hyd_fmt_is_nv12_family(fmt),   hyd_fmt_is_nv12_interp(fmt), hyd_fmt_is_p016_family(fmt),
                                  hyd_fmt_is_p016_interp(fmt), hyd_fmt_is_yuv420(fmt),        hyd_fmt_is_yuv420_interp(fmt), hyd_fmt_is_device(fmt),

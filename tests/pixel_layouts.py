@@ -11,7 +11,7 @@ with 0 it reads what a cleared allocation holds.  MARGIN bytes of filler lie bef
 device allocator gives; the GPU tests assert it before they add the offsets.
 
 loader(sample_fmt, channel_addresses, row_stride, pixel_stride) restates which loader k_transform_tokenize picks for a
-layout (hydrium_amd/csrc/hip/kernels.hip, from `const bool packed` to `hfast`).  The kernel decides from address bits, not
+layout (hydrium_amd/csrc/hip/k1_transform_body.h, from `const bool packed` to `hfast`).  The kernel decides from address bits, not
 from anything the API names; the two are changed together.
 """
 import numpy as np

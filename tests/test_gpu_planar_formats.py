@@ -12,8 +12,9 @@ import planar_model as plm
 import yuv_model as ym
 from conftest import has_gpu
 from hydrium_amd import api, build as hbuild
-from test_gpu_chroma_filters import _frame_of
-from test_gpu_mixed_batch import _check, _check_on_device, _reference_of
+from test_gpu_chroma_filters import _frame_of, _nv12 as _nv12i, _want as _nv12i_want
+from test_gpu_half_formats import _half
+from test_gpu_mixed_batch import _check, _check_on_device, _image, _reference, _reference_of
 from test_gpu_p016_formats import _p016, _want as _p016_want
 from test_gpu_yuv_formats import _nv12, _want as _nv12_want
 from test_planar_formats import check_upsample, hook
@@ -231,6 +232,9 @@ def test_encode_image_and_a_frame_batch_of_three_frames():
 
 
 def test_planar_beside_nv12_p010_and_rgb8_in_one_launch():
+    """and, in the same round, one picture of each of the eleven forms the transform kernel has an instance for, 27 x 19 with
+    pitches rounded up to a dword: an interpolated form's blocks 1 and 2 take the dword window, block 0 (the picture's first
+    chroma column) and block 3 (ragged, odd width) the edge fill"""
     import torch
     from hydrium_amd import device
 
@@ -238,7 +242,17 @@ def test_planar_beside_nv12_p010_and_rgb8_in_one_launch():
             _p016("photo", 200, 120, 80, 34), torch.from_numpy(_model("photo", 232, 188, I420C, 31)).cuda()]
     wants = [_want("photo", 232, 188, I420C, 31), _want("photo", 200, 120, I444, 32), _nv12_want("photo", 232, 188, 17, 33),
              _p016_want("photo", 200, 120, 80, 34), _want("photo", 232, 188, I420C, 31)]
-    with device.MixedBatch(5) as mb:
+    w, h, pitch = 27, 19, 28
+    f16, bf16 = _half("photo", w, h, "float16", 45), _half("photo", w, h, "bfloat16", 46)
+    rgb16 = _image("photo", w, h, 16, 43)[0]
+    imgs += [_planar("photo", w, h, I420, 35), _planar("photo", w, h, I420C, 36), _nv12("photo", w, h, 17, 37, pitch),
+             _nv12i("photo", w, h, 33, 38, pitch), _p016("photo", w, h, 80, 39, pitch), _p016("photo", w, h, 96, 40, pitch),
+             _image("photo", w, h, 8, 42)[0], rgb16 if rgb16.dtype == torch.int16 else rgb16.view(torch.int16),
+             _image("photo", w, h, 32, 44)[0], f16[0], bf16[0]]
+    wants += [_want("photo", w, h, I420, 35), _want("photo", w, h, I420C, 36), _nv12_want("photo", w, h, 17, 37),
+              _nv12i_want("photo", w, h, 33, 38), _p016_want("photo", w, h, 80, 39), _p016_want("photo", w, h, 96, 40),
+              _reference("photo", w, h, 8, 42), _reference("photo", w, h, 16, 43), _reference("photo", w, h, 32, 44), f16[1], bf16[1]]
+    with device.MixedBatch(len(imgs)) as mb:
         mb.encode(imgs, sample_fmts="each")
         _check_on_device(mb, wants)
         mb.encode(imgs[::-1], sample_fmts="each")

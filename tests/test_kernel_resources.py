@@ -6,33 +6,12 @@ the kernel itself, half a SIMD lost to every other kernel's wavefronts.  Five ro
 allocation was the use.  This test pins the numbers the design's co-residency arithmetic rests on, so that a toolchain or source
 change that moves them is seen here and not three probes later."""
 import os
-import re
-import subprocess
 import sys
-import tempfile
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _descriptors(flags=()):
-    from hydrium_amd import build as hb
-
-    if not os.path.exists(hb.HIPCC):
-        pytest.skip("no hipcc")
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "k.s")
-        subprocess.run([hb.HIPCC] + hb.HIP_FLAGS + list(flags) + ["--cuda-device-only", "-S", "-o", out, os.path.join(hb.CSRC, "hip", "kernels.hip")],
-                       check=True, capture_output=True)
-        text = open(out).read()
-    res = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
-        body = m.group(2)
-        res[m.group(1)] = {k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", body).group(1))
-                           for k in ("group_segment_fixed_size", "next_free_vgpr", "private_segment_fixed_size")}
-    return res
+from kernel_descriptors import kernel_descriptors as _descriptors  # noqa: E402
 
 
 def _one(res, prefix):

@@ -16,11 +16,11 @@ import pytest
 import chroma_model as cm
 import planar_model as plm
 import yuv_model as ym
+from kernel_descriptors import kernel_descriptors
 from hydrium_amd import api, build as hbuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOOK_SIZES = [(1, 1), (2, 1), (3, 2), (33, 9), (200, 120)]
-_cache = {}
 
 
 def random_plane(sub, w, h, seed=512):
@@ -288,28 +288,10 @@ def test_the_drop_in_api_refuses_the_formats():
 
 
 # ---- the code object ----
-def _kernel_descriptors():
-    """{mangled name: descriptor fields} of every kernel hipcc cross-compiles from kernels.hip in the default build; made once"""
-    if "kernels" not in _cache:
-        if not os.path.exists(hbuild.HIPCC):
-            pytest.skip("no hipcc")
-        import tempfile
-
-        with tempfile.TemporaryDirectory() as tmp:
-            out = os.path.join(tmp, "k.s")
-            subprocess.run([hbuild.HIPCC] + hbuild.HIP_FLAGS + ["--cuda-device-only", "-S", "-o", out, os.path.join(hbuild.CSRC, "hip", "kernels.hip")],
-                           check=True, capture_output=True)
-            text = open(out).read()
-        _cache["kernels"] = {m.group(1): {k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", m.group(2)).group(1))
-                                          for k in ("group_segment_fixed_size", "next_free_vgpr", "private_segment_fixed_size")}
-                             for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S)}
-    return _cache["kernels"]
-
-
 def test_the_six_new_instances_have_symbols_of_their_own_and_keep_the_transform_kernels_contract():
     """k_transform_tokenize_planar<mode, HYDK_STORE_YUVP | _YUVPI>: none under the RGB8 / NV12 or the P016 instances' names, no
     scratch, and the co-residency line the NV12 instances are held to (26 granules of 1280 bytes of static LDS, 128 registers)"""
-    res = _kernel_descriptors()
+    res = kernel_descriptors()
     new = {k: v for k, v in res.items() if "k_transform_tokenize_planar" in k}
     assert sorted(re.match(r"_Z27k_transform_tokenize_planarILi(\d)ELi(\d)EE", k).groups() for k in new) == \
         [(mode, store) for mode in "012" for store in "78"], sorted(res)

@@ -5,13 +5,12 @@ formats (they name device pixels); and what the three NV12 instances of the tran
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import yuv_model as ym
+from kernel_descriptors import kernel_descriptors
 from hydrium_amd import api, build as hbuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -195,18 +194,7 @@ def test_the_drop_in_api_refuses_the_nv12_formats():
 # ---- the code object ----
 def _transform_instances():
     """{mangled name: descriptor fields} of every k_transform_tokenize instance hipcc cross-compiles from kernels.hip"""
-    if not os.path.exists(hbuild.HIPCC):
-        pytest.skip("no hipcc")
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "k.s")
-        subprocess.run([hbuild.HIPCC] + hbuild.HIP_FLAGS + ["--cuda-device-only", "-S", "-o", out, os.path.join(hbuild.CSRC, "hip", "kernels.hip")],
-                       check=True, capture_output=True)
-        text = open(out).read()
-    res = {}
-    for m in re.finditer(r"\.amdhsa_kernel (_Z20k_transform_tokenize\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
-        res[m.group(1)] = {k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", m.group(2)).group(1))
-                           for k in ("group_segment_fixed_size", "next_free_vgpr", "private_segment_fixed_size")}
-    return res
+    return {k: v for k, v in kernel_descriptors().items() if k.startswith("_Z20k_transform_tokenize")}
 
 
 def test_the_three_nv12_instances_keep_the_transform_kernels_contract():
