@@ -353,6 +353,18 @@ static_assert(HYDAMD_PLANAR_ROW(I420) && HYDAMD_PLANAR_ROW(I422) && HYDAMD_PLANA
                   HYDAMD_I420C_BT709 == HYDAMD_I420_BT709 + 16 * HYDK_CHROMA_CENTRE && HYDAMD_I422L_BT709 == HYDAMD_I422_BT709 + 16 * HYDK_CHROMA_LEFT &&
                   HYD_FMT_PLANAR_420 == HYDK_PLANAR_420 && HYD_FMT_PLANAR_422 == HYDK_PLANAR_422 && HYD_FMT_PLANAR_444 == HYDK_PLANAR_444,
               "the planar family is 512 + the kernels' matrix index + 4 * the kernels' subsampling + 16 * the kernels' chroma filter");
+#define HYDAMD_PLANAR16_ROW(P, S, F, D)                                                                                  \
+    (HYDAMD_PLANAR_ROW(P) && HYDAMD_##P##_BT709 == HYD_FMT_PLANAR16_BASE + 4 * (S) + 16 * (F) + 64 * (D))
+#define HYDAMD_PLANAR16_DEPTH(B, D)                                                                                               \
+    (HYDAMD_PLANAR16_ROW(I0##B, HYDK_PLANAR_420, HYDK_CHROMA_NEAREST, D) && HYDAMD_PLANAR16_ROW(I2##B, HYDK_PLANAR_422, HYDK_CHROMA_NEAREST, D) && \
+     HYDAMD_PLANAR16_ROW(I4##B, HYDK_PLANAR_444, HYDK_CHROMA_NEAREST, D) && HYDAMD_PLANAR16_ROW(I0##B##C, HYDK_PLANAR_420, HYDK_CHROMA_CENTRE, D) &&  \
+     HYDAMD_PLANAR16_ROW(I2##B##C, HYDK_PLANAR_422, HYDK_CHROMA_CENTRE, D) && HYDAMD_PLANAR16_ROW(I0##B##L, HYDK_PLANAR_420, HYDK_CHROMA_LEFT, D) &&  \
+     HYDAMD_PLANAR16_ROW(I2##B##L, HYDK_PLANAR_422, HYDK_CHROMA_LEFT, D))
+static_assert(HYDAMD_PLANAR16_DEPTH(10, HYDK_YUV16_P010) && HYDAMD_PLANAR16_DEPTH(12, HYDK_YUV16_P012) && HYDAMD_PLANAR16_DEPTH(16, HYDK_YUV16_P016),
+              "the planar16 family is 2048 + the kernels' matrix index + 4 * subsampling + 16 * chroma filter + 64 * the kernels' depth");
+static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_FORMS == 13, "the job did not grow; launch_transform's mask has 13 bits");
+#undef HYDAMD_PLANAR16_DEPTH
+#undef HYDAMD_PLANAR16_ROW
 #undef HYDAMD_PLANAR_ROW
 
 /* the public format a recorded job reads (hydk_store.h: the encode of what record_lf_group decoded) */
@@ -2980,6 +2992,56 @@ __attribute__((visibility("default"))) int hydt_planar_upsample_device(int devic
     return probe_round_trip(plane, in_bytes, out, n, [&](void *d_in, void *d_out) {
         hipLaunchKernelGGL(k_planar_upsample_probe, probe_grid(n), dim3(256), 0, nullptr, sub, filter, (const uint8_t *)d_in, (uint8_t *)d_out,
                            width, height);
+    });
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the planar definition of 16-bit words (hydk_planar16_pixel,
+ * hydk_yuvp16.h) as the host compiler built it and as the device runs it.  sub, filter as hydt_planar_upsample_host's; depth
+ * HYDK_YUV16_P010 ... _P016; matrix HYDK_YUV_*; planes: the Y plane of a width x height picture (height rows of width words), then
+ * its U and its V plane (ch rows of cw words each), tightly packed; rgb receives height rows of width (R, G, B) word triples. */
+static bool planar16_probe_args(int sub, int filter, int depth, int matrix, const uint16_t *planes, uint16_t *rgb, int width, int height) {
+    return planar_probe_args(sub, filter, (const uint8_t *)planes, (uint8_t *)rgb, width, height) && depth >= HYDK_YUV16_P010 &&
+           depth <= HYDK_YUV16_P016 && matrix >= 0 && matrix < HYDK_YUV_MATRICES;
+}
+/* pixel i of the picture out of the three packed planes */
+__host__ __device__ static inline void planar16_probe_pixel(int sub, int filter, int depth, int matrix, const uint16_t *planes, uint16_t *rgb,
+                                                            int width, int height, size_t i) {
+    const int cw = (width + hydk_planar_sx(sub)) >> hydk_planar_sx(sub), ch = (height + hydk_planar_sy(sub)) >> hydk_planar_sy(sub);
+    const uint16_t *u = planes + (size_t)width * height, *v = u + (size_t)cw * ch;
+    uint32_t out[3];
+    hydk_planar16_pixel(sub, filter, depth, matrix, planes, width, u, v, cw, cw, ch, (int)(i % (size_t)width), (int)(i / (size_t)width), out);
+    for (int c = 0; c < 3; c++)
+        rgb[3 * i + c] = (uint16_t)out[c];
+}
+
+__attribute__((visibility("default"))) int hydt_planar16_to_rgb_host(int sub, int filter, int depth, int matrix, const uint16_t *planes,
+                                                                     uint16_t *rgb, int width, int height) {
+    if (!planar16_probe_args(sub, filter, depth, matrix, planes, rgb, width, height))
+        return ST_API_ERROR;
+    for (size_t i = 0; i < (size_t)width * height; i++)
+        planar16_probe_pixel(sub, filter, depth, matrix, planes, rgb, width, height, i);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_planar16_to_rgb_probe(int sub, int filter, int depth, int matrix, const uint16_t *planes, uint16_t *rgb,
+                                                               int width, int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i < (size_t)width * height)
+        planar16_probe_pixel(sub, filter, depth, matrix, planes, rgb, width, height, i);
+}
+} /* namespace */
+
+/* one launch over the picture (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_planar16_to_rgb_device(int device, int sub, int filter, int depth, int matrix,
+                                                                       const uint16_t *planes, uint16_t *rgb, int width, int height) {
+    if (!planar16_probe_args(sub, filter, depth, matrix, planes, rgb, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height;
+    const size_t chroma = (size_t)((width + hydk_planar_sx(sub)) >> hydk_planar_sx(sub)) * ((height + hydk_planar_sy(sub)) >> hydk_planar_sy(sub));
+    return probe_round_trip(planes, 2 * (n + 2 * chroma), rgb, 6 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_planar16_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, sub, filter, depth, matrix, (const uint16_t *)d_in,
+                           (uint16_t *)d_out, width, height);
     });
 }
 

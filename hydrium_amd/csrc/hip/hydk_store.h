@@ -31,7 +31,9 @@
 #define HYDK_STORE_P016I 6
 #define HYDK_STORE_YUVP 7  /* 8-bit class: planar YCbCr — src[1], src[2] the U and V planes (pitch pixel_stride), HydkLfJob.sub the subsampling */
 #define HYDK_STORE_YUVPI 8
-#define HYDK_STORE_FORMS 9
+#define HYDK_STORE_YUVP16 9  /* 16-bit class: the same three planes in 16-bit words of 10, 12 or 16 bits, LSB-aligned (hydk_yuvp16.h) */
+#define HYDK_STORE_YUVP16I 10
+#define HYDK_STORE_FORMS 11
 
 /* HydkLfJob.use_luts of a YCbCr job is the XYB mode + its form's variant bit: the RGB instances' own test turns it away */
 #define HYDK_VARIANT_NV12 8
@@ -40,6 +42,8 @@
 #define HYDK_VARIANT_P016I 64
 #define HYDK_VARIANT_YUVP 128
 #define HYDK_VARIANT_YUVPI 256
+#define HYDK_VARIANT_YUVP16 512
+#define HYDK_VARIANT_YUVP16I 1024
 
 typedef struct HydkStoreForm {
     int cls;           /* HYDK_FMT_*; form 0 belongs to every class */
@@ -61,6 +65,8 @@ HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
         {HYDK_FMT_U16, 1, 16, 1, 1, HYDK_VARIANT_P016I},
         {HYDK_FMT_U8, 1, 8, 2, 0, HYDK_VARIANT_YUVP},
         {HYDK_FMT_U8, 1, 8, 2, 1, HYDK_VARIANT_YUVPI},
+        {HYDK_FMT_U16, 1, 16, 2, 0, HYDK_VARIANT_YUVP16},
+        {HYDK_FMT_U16, 1, 16, 2, 1, HYDK_VARIANT_YUVP16I},
     };
     return forms[storage >= 0 && storage < HYDK_STORE_FORMS ? storage : 0];
 }
@@ -91,6 +97,13 @@ static inline HydkSampleForm hydk_decode_fmt(int f) {
         d.storage = (uint32_t)(HYDK_STORE_YUVP + (d.filter != 0));
         d.sx = hyd_fmt_planar_sx(f);
         d.sy = hyd_fmt_planar_sy(f);
+    } else if (hyd_fmt_is_planar16(f)) {
+        d.filter = (uint32_t)hyd_fmt_planar16_filter(f);
+        d.matrix = (uint32_t)(hyd_fmt_planar16_matrix(f) + 4 * hyd_fmt_planar16_depth(f));
+        d.sub = (uint32_t)hyd_fmt_planar16_sub(f);
+        d.storage = (uint32_t)(HYDK_STORE_YUVP16 + (d.filter != 0));
+        d.sx = hyd_fmt_planar16_sx(f);
+        d.sy = hyd_fmt_planar16_sy(f);
     } else if (f > HYD_FMT_FLOAT32) {
         d.storage = (uint32_t)(f == HYD_FMT_FLOAT16 ? HYDK_STORE_F16 : HYDK_STORE_BF16);
     }
@@ -103,6 +116,8 @@ static inline int hydk_encode_fmt(HydkSampleForm d) {
     const HydkStoreForm form = hydk_store_form((int)d.storage);
     if (!form.ycbcr)
         return d.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : d.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : d.cls;
+    if (form.chroma_planes == 2 && form.bits == 16)
+        return HYD_FMT_PLANAR16_BASE + (int)(d.matrix & 3u) + 4 * (int)d.sub + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2);
     if (form.chroma_planes == 2)
         return HYD_FMT_I420_BT709 + (int)d.matrix + 4 * (int)d.sub + 16 * (int)d.filter;
     return HYD_FMT_NV12_BT709 + (int)(d.matrix & 3u) + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2);

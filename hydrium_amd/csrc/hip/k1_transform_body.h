@@ -1,6 +1,6 @@
 /*
  * k1_transform_body.h — the body of the transform kernel (kernels.hip, K1), included into k_transform_tokenize, into
- * k_transform_tokenize_p016 and into k_transform_tokenize_planar and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
+ * k_transform_tokenize_p016, into k_transform_tokenize_planar and into k_transform_tokenize_yuvp16 and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
  * and STORE, the kernel's parameters jobs, status, part_info and plog, and everything kernels.hip defines above its K1 section.
  * No include guard: it is function-body text, meant to be included once per kernel.
  */
@@ -11,12 +11,14 @@
      * cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it.  HALF: 2-byte floats, widened on load */
     constexpr HydkStoreForm FORM = hydk_store_form(STORE);
     static_assert(STORE == HYDK_STORE_F32 || FORM.cls == FMT,
-                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP and YUVPI, the 16-bit class P016 and P016I");
+                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP and YUVPI, the 16-bit class P016, P016I, YUVP16 and YUVP16I");
     constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, INTERP = FORM.interp;
     constexpr bool HALF = FMT == HYDK_FMT_F32 && STORE != HYDK_STORE_F32;
     /* the two-plane forms by name: YUVPI keeps a prefetch, an edge fill and an interpolate loop of its own (through the shared
      * ones its instances measured a few tenths of a percent slower, profiles/ycbcr_loader.txt) */
-    constexpr bool YUVP = TWO_PLANES && !INTERP, YUVPI = TWO_PLANES && INTERP;
+    constexpr bool YUVP = TWO_PLANES && !INTERP && FMT == HYDK_FMT_U8, YUVPI = TWO_PLANES && INTERP && FMT == HYDK_FMT_U8;
+    /* the two-plane forms of 16-bit words, nearest and interpolated: windows of their own beside the 8-bit ones (hydk_yuvp16.h) */
+    constexpr bool YP16 = TWO_PLANES && FMT == HYDK_FMT_U16;
     typedef typename std::conditional<HALF, uint16_t, typename SampleOf<FMT>::type>::type sample_t;
     constexpr bool LUTS = XMODE == kXybGather;
     constexpr int kWords = FMT == HYDK_FMT_U8 ? 6 : 12; /* dwords holding 8 packed RGB pixels */
@@ -152,9 +154,11 @@
     const bool prun = YUV && !TWO_PLANES &&
                       (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)(job.row_stride * (SB / 8))) & 3) == 0;
     /* two planes (ylrun): two dwords of Y and, from each chroma plane, the dword of four samples that serves its eight pixels
-     * (the block's chroma column is a multiple of 4) — two dwords of eight for 4:4:4 */
-    const bool ylrun = TWO_PLANES && (((uintptr_t)job.src[0] | (uintptr_t)job.row_stride | (uintptr_t)job.src[1] |
-                                       (uintptr_t)job.src[2] | (uintptr_t)job.pixel_stride) & 3) == 0;
+     * (the block's chroma column is a multiple of 4) — two dwords of eight for 4:4:4.  16-bit words (YP16): four dwords of Y and
+     * two from each chroma plane — four for 4:4:4, kWords in all — where the three bases and both pitches IN BYTES are dword
+     * multiples */
+    const bool ylrun = TWO_PLANES && (((uintptr_t)job.src[0] | (uintptr_t)(job.row_stride * (SB / 8)) | (uintptr_t)job.src[1] |
+                                       (uintptr_t)job.src[2] | (uintptr_t)(job.pixel_stride * (SB / 8))) & 3) == 0;
     /* interpolated chroma (irun, pirun, ylirun): beside the near row's four chroma samples the window holds the same four of the
      * far row — the one the filter mixes in: above for an even y, below for an odd one, clamped to the PICTURE's chroma rows;
      * 4:2:2 has no other row: far is near — and of both rows the sample behind those four and (centre-sited) the one before
@@ -165,8 +169,8 @@
     const bool fast = (YUV ? irun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
     uint32_t nxt[kWords];
     /* the window's columns 0 and 5, which sit in no dword of the four between them (YUVPI: of U and of V, column 0 | column 5
-     * << 8 of the near row, the same << 16 of the far row) */
-    constexpr int kFlank = YUV && !TWO_PLANES ? 4 / kPPD : 2;
+     * << 8 of the near row, the same << 16 of the far row; YP16: column 0 | column 5 << 16 of U near, U far, V near, V far) */
+    constexpr int kFlank = YUV && !TWO_PLANES ? 4 / kPPD : YP16 ? 4 : 2;
     uint32_t flank[kFlank] = {};
 #pragma unroll
     for (int k = 0; k < kWords; k++)
@@ -187,10 +191,15 @@
     auto win_get = [&](int c, int r, int p) -> uint32_t { return (win_word(r, p) >> win_shift(c, r, p)) & kSMask; };
     auto win_put = [&](int c, int r, int p, uint32_t v) { win_word(r, p) |= v << win_shift(c, r, p); };
     /* nearest chroma: sample c of pixel i's own column.  Two planes (YUVP): byte i >> 1 of nxt[2] (U) or nxt[3] (V), or (4:4:4, a
-     * sample a pixel) byte i of the two dwords a plane at nxt[2 + 2 c] */
+     * sample a pixel) byte i of the two dwords a plane at nxt[2 + 2 c].  YP16: word i >> 1, or (4:4:4) word i, of the dwords at
+     * nxt[4 + 4 c] */
     auto near_get = [&](int c, int i) -> uint32_t {
         if (!TWO_PLANES)
             return win_get(c, 0, 1 + (i >> 1));
+        if (YP16) {
+            const uint32_t s2 = (nxt[4 + 4 * c + (i >> 2)] >> (16 * ((i >> 1) & 1))) & 0xFFFF, s4 = (nxt[4 + 4 * c + (i >> 1)] >> (16 * (i & 1))) & 0xFFFF;
+            return csx ? s2 : s4;
+        }
         const uint32_t s2 = (nxt[2 + c] >> (8 * (i >> 1))) & 0xFF, s4 = (nxt[2 + 2 * c + (i >> 2)] >> (8 * (i & 3))) & 0xFF;
         return csx ? s2 : s4;
     };
@@ -290,6 +299,68 @@
             }
             return;
         }
+        if (YP16) {
+            /* the words as stored: the depth shift waits until they are used (phase A), so that nothing here waits for a load */
+            if (fast && s * 8 + ar < gh) {
+                /* (the lane's row and block pass through an empty statement the compiler cannot see through, so the five addresses
+                 * are made anew for every strip: carried from strip to strip as 64-bit pointers they cost the registers that left
+                 * some builds of tests/kernel_variants.py with scratch) */
+                int lane_row = ar, lane_block = ab;
+                asm volatile("" : "+v"(lane_row), "+v"(lane_block));
+                const long long y = py0 + s * 8 + lane_row, x = px0 + lane_block * 8;
+                const long long ny = y >> csy, on = (ny * job.pixel_stride + (x >> csx)) * 2;
+                const char *py = (const char *)job.src[0] + (y * job.row_stride + x) * 2;
+                const char *un = (const char *)job.src[1] + on, *vn = (const char *)job.src[2] + on;
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    nxt[k] = HYDK_GLOBAL(const uint32_t, py)[k];
+                if (!INTERP) {
+                    /* U at nxt[4], V at nxt[8]: two dwords each, and two more for 4:4:4 */
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        nxt[4 + k] = HYDK_GLOBAL(const uint32_t, un)[k];
+                        nxt[8 + k] = HYDK_GLOBAL(const uint32_t, vn)[k];
+                    }
+                    if (!csx) {
+#pragma unroll
+                        for (int k = 2; k < 4; k++) {
+                            nxt[4 + k] = HYDK_GLOBAL(const uint32_t, un)[k];
+                            nxt[8 + k] = HYDK_GLOBAL(const uint32_t, vn)[k];
+                        }
+                    }
+                } else {
+                    /* near and far dwords of U at nxt[4], nxt[6], of V at nxt[8], nxt[10]; 4:2:2 has no far row: it is filled in at use */
+                    const bool centre = job.filter == HYDK_CHROMA_CENTRE; /* (left-sited chroma never looks before the window) */
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        nxt[4 + k] = HYDK_GLOBAL(const uint32_t, un)[k];
+                        nxt[8 + k] = HYDK_GLOBAL(const uint32_t, vn)[k];
+                    }
+                    flank[0] = (uint32_t)HYDK_GLOBAL(const uint16_t, un)[4] << 16;
+                    flank[2] = (uint32_t)HYDK_GLOBAL(const uint16_t, vn)[4] << 16;
+                    if (centre) {
+                        flank[0] |= HYDK_GLOBAL(const uint16_t, un - 2)[0];
+                        flank[2] |= HYDK_GLOBAL(const uint16_t, vn - 2)[0];
+                    }
+                    if (csy) {
+                        const long long of = (far_row(y) * job.pixel_stride + (x >> 1)) * 2;
+                        const char *uf = (const char *)job.src[1] + of, *vf = (const char *)job.src[2] + of;
+#pragma unroll
+                        for (int k = 0; k < 2; k++) {
+                            nxt[6 + k] = HYDK_GLOBAL(const uint32_t, uf)[k];
+                            nxt[10 + k] = HYDK_GLOBAL(const uint32_t, vf)[k];
+                        }
+                        flank[1] = (uint32_t)HYDK_GLOBAL(const uint16_t, uf)[4] << 16;
+                        flank[3] = (uint32_t)HYDK_GLOBAL(const uint16_t, vf)[4] << 16;
+                        if (centre) {
+                            flank[1] |= HYDK_GLOBAL(const uint16_t, uf - 2)[0];
+                            flank[3] |= HYDK_GLOBAL(const uint16_t, vf - 2)[0];
+                        }
+                    }
+                }
+            }
+            return;
+        }
         if (HALF) {
             if (hfast && s * 8 + ar < gh) {
                 const long long row = (long long)(py0 + s * 8 + ar) * job.row_stride;
@@ -384,7 +455,7 @@
                  * and pic_cx0 columns before src[1] (and src[2]).  Window column p is the picture's clamp(pcx - 1 + p, 0, cw - 1),
                  * which is what cx, and hx with its clamp, come to for every pixel of the block.  The rest is shared with the
                  * dword rows. */
-                if (INTERP && !YUVPI && !fast) {
+                if (INTERP && !TWO_PLANES && !fast) {
 #pragma unroll
                     for (int k = 0; k < kWords; k++)
                         nxt[k] = 0;
@@ -451,6 +522,58 @@
                         }
                     }
                 }
+                /* YP16 rows that did not come as dwords: each plane's window of six words filled word by word, the same clamps, into
+                 * the registers the dword rows use, as stored */
+                if (YP16 && INTERP && !fast) {
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        nxt[k] = 0;
+#pragma unroll
+                    for (int k = 0; k < kFlank; k++)
+                        flank[k] = 0;
+                    if (row_ok) {
+                        const uint16_t *py = (const uint16_t *)job.src[0] + (long long)y * job.row_stride + x0;
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            if (i < nvalid)
+                                nxt[i >> 1] |= (uint32_t)py[i] << (16 * (i & 1));
+                        const long long ny = y >> csy, fy = csy ? far_row(y) : ny;
+                        const long long on = ny * job.pixel_stride - job.pic_cx0, of = fy * job.pixel_stride - job.pic_cx0;
+                        const uint16_t *un = (const uint16_t *)job.src[1] + on, *uf = (const uint16_t *)job.src[1] + of;
+                        const uint16_t *vn = (const uint16_t *)job.src[2] + on, *vf = (const uint16_t *)job.src[2] + of;
+#pragma unroll
+                        for (int p = 0; p < 6; p++) {
+                            const int col = min(max(pcx - 1 + p, 0), job.pic_cw - 1);
+                            const uint32_t four[4] = {un[col], uf[col], vn[col], vf[col]};
+#pragma unroll
+                            for (int q = 0; q < 4; q++) {
+                                if (p == 0 || p == 5)
+                                    flank[q] |= four[q] << (p ? 16 : 0);
+                                else
+                                    nxt[4 + 2 * q + ((p - 1) >> 1)] |= four[q] << (16 * ((p - 1) & 1));
+                            }
+                        }
+                    }
+                }
+                /* YP16, dword rows and filled rows alike: the stored words become samples before any tap sees them (hydk_yuvp16.h);
+                 * the depth is the job's, so the shift is uniform over the wavefront.  4:2:2: the far row is the near row */
+                if (YP16) {
+                    const int shift = hydk_yuvp16_shift((int)(job.matrix >> 2));
+                    if (INTERP && !csy) {
+#pragma unroll
+                        for (int k = 0; k < 2; k++) {
+                            nxt[6 + k] = nxt[4 + k];
+                            nxt[10 + k] = nxt[8 + k];
+                            flank[1 + 2 * k] = flank[2 * k];
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        nxt[k] = hydk_yuvp16_sample2(shift, nxt[k]);
+#pragma unroll
+                    for (int k = 0; k < kFlank; k++)
+                        flank[k] = hydk_yuvp16_sample2(shift, flank[k]);
+                }
                 /* YCbCr: the eight pixels of the window, converted and packed as an interleaved RGB row of the class has them */
                 uint32_t cvt[kWords];
                 if (YUV) {
@@ -470,7 +593,27 @@
                             cvt[si / kSPD] |= rgb[ch] << (SB * (si % kSPD));
                         }
                     };
-                    if (YUVPI) {
+                    if (YP16 && INTERP) {
+                        /* the same two mixes, the window's words taken plane by plane */
+                        uint32_t vu[6], vv[6];
+#pragma unroll
+                        for (int p = 0; p < 6; p++) {
+                            const int k = (p - 1) >> 1, sh = 16 * ((p - 1) & 1);
+                            const uint32_t a = p == 0 ? flank[0] : p == 5 ? flank[0] >> 16 : nxt[4 + k] >> sh;
+                            const uint32_t b = p == 0 ? flank[1] : p == 5 ? flank[1] >> 16 : nxt[6 + k] >> sh;
+                            const uint32_t c = p == 0 ? flank[2] : p == 5 ? flank[2] >> 16 : nxt[8 + k] >> sh;
+                            const uint32_t d = p == 0 ? flank[3] : p == 5 ? flank[3] >> 16 : nxt[10 + k] >> sh;
+                            vu[p] = hydk_chroma_vmix(a & 0xFFFF, b & 0xFFFF);
+                            vv[p] = hydk_chroma_vmix(c & 0xFFFF, d & 0xFFFF);
+                        }
+                        const int filter = (int)job.filter;
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            const int j = 1 + (i >> 1), hc = (i & 1) ? j + 1 : j - 1, hl = j + (i & 1);
+                            convert(i, hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]),
+                                    hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]));
+                        }
+                    } else if (YUVPI) {
                         /* NV12I's vertical mix, horizontal mix, conversion and pack, the window's samples taken plane by plane */
                         uint32_t vu[6], vv[6];
 #pragma unroll
@@ -659,9 +802,15 @@
                         const long long offc = TWO_PLANES ? (long long)(y >> csy) * job.pixel_stride + (long long)((x0 + i) >> csx)
                                                : YUV      ? (long long)(y >> 1) * job.row_stride + (long long)((x0 + i) & ~1)
                                                           : off;
-                        const sample_t sr = ((const sample_t *)job.src[0])[off];
-                        const sample_t sg = ((const sample_t *)job.src[1])[offc];
-                        const sample_t sb = ((const sample_t *)job.src[2])[offc];
+                        sample_t sr = ((const sample_t *)job.src[0])[off];
+                        sample_t sg = ((const sample_t *)job.src[1])[offc];
+                        sample_t sb = ((const sample_t *)job.src[2])[offc];
+                        if (YP16) { /* the stored words become samples (hydk_yuvp16.h) */
+                            const int shift = hydk_yuvp16_shift((int)(job.matrix >> 2));
+                            sr = (sample_t)hydk_yuvp16_sample(shift, (uint32_t)sr);
+                            sg = (sample_t)hydk_yuvp16_sample(shift, (uint32_t)sg);
+                            sb = (sample_t)hydk_yuvp16_sample(shift, (uint32_t)sb);
+                        }
                         if (FMT == HYDK_FMT_F32) {
                             float fr, fg, fb;
                             if (HALF) {

@@ -615,12 +615,15 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
  * are the one text of k1_transform_body.h, included into each: a shared __device__ function, inlined, compiled the existing
  * instances to other code than they had.
  * The 8-bit class's planar YCbCr forms, HYDK_STORE_YUVP and HYDK_STORE_YUVPI (three planes, 4:2:0, 4:2:2 and 4:4:4; hydk_chroma.h),
- * are k_transform_tokenize_planar's, for the same reason: "the 8-bit instances" by symbol name stay what they were. */
+ * are k_transform_tokenize_planar's, for the same reason: "the 8-bit instances" by symbol name stay what they were.
+ * The same three planes in 16-bit words, HYDK_STORE_YUVP16 and HYDK_STORE_YUVP16I (hydk_yuvp16.h), are k_transform_tokenize_yuvp16's:
+ * a name that holds neither the planar nor the P016 kernel's, so that what is asked of those by name stays theirs. */
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
     static_assert(STORE != HYDK_STORE_P016 && STORE != HYDK_STORE_P016I, "the P016 instances are k_transform_tokenize_p016's");
     static_assert(STORE != HYDK_STORE_YUVP && STORE != HYDK_STORE_YUVPI, "the planar instances are k_transform_tokenize_planar's");
+    static_assert(STORE != HYDK_STORE_YUVP16 && STORE != HYDK_STORE_YUVP16I, "the 16-bit planar instances are k_transform_tokenize_yuvp16's");
 #include "k1_transform_body.h"
 }
 
@@ -640,6 +643,15 @@ __global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_planar(const
                                                                            uint2 *part_info, int plog) {
     static_assert(STORE == HYDK_STORE_YUVP || STORE == HYDK_STORE_YUVPI, "RGB8, NV12 and NV12I are k_transform_tokenize's");
     constexpr int FMT = HYDK_FMT_U8;
+#include "k1_transform_body.h"
+}
+
+/* Planar YCbCr of 16-bit words, nearest (YUVP16) and interpolated (YUVP16I): four waves per SIMD as the P016 instances. */
+template <int XMODE, int STORE>
+__global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_yuvp16(const HydkLfJob *__restrict__ jobs, uint32_t *status,
+                                                                           uint2 *part_info, int plog) {
+    static_assert(STORE == HYDK_STORE_YUVP16 || STORE == HYDK_STORE_YUVP16I, "P016 and P016I are k_transform_tokenize_p016's");
+    constexpr int FMT = HYDK_FMT_U16;
 #include "k1_transform_body.h"
 }
 
@@ -2398,6 +2410,10 @@ static K1Fn k1_of_mode(int fmt, int storage) {
         return k_transform_tokenize_planar<A, HYDK_STORE_YUVP>;
     case HYDK_STORE_YUVPI:
         return k_transform_tokenize_planar<A, HYDK_STORE_YUVPI>;
+    case HYDK_STORE_YUVP16:
+        return k_transform_tokenize_yuvp16<A, HYDK_STORE_YUVP16>;
+    case HYDK_STORE_YUVP16I:
+        return k_transform_tokenize_yuvp16<A, HYDK_STORE_YUVP16I>;
     }
     return fmt == HYDK_FMT_U8    ? k_transform_tokenize<HYDK_FMT_U8, XM>
            : fmt == HYDK_FMT_U16 ? k_transform_tokenize<HYDK_FMT_U16, XM>

@@ -157,7 +157,7 @@ HYDRIUM_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *
         return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
     /* a shard's buffer is only promised to hold its own rows, and the filter would read a neighbouring shard's chroma row */
     /* (a planar 4:2:2 window has no other row, but its columns cross into an LF group that another shard owns) */
-    if (hyd_fmt_is_yuv420_interp(sample_fmt) || hyd_fmt_is_planar_interp(sample_fmt))
+    if (hyd_fmt_is_yuv420_interp(sample_fmt) || hyd_fmt_is_planar_interp(sample_fmt) || hyd_fmt_is_planar16_interp(sample_fmt))
         return fail(m, HYD_API_ERROR, HYD_FMT_NV12_SHARDED_MSG, NULL);
     for (int d = 0; d < f->n; d++)
         if (src[3 * d + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * d, pixel_stride))

@@ -60,6 +60,16 @@ for _sub_name, _sub in PLANAR_SUBSAMPLINGS.items():
         for _name, _matrix in (("BT709", 0), ("BT709_FULL", 1), ("BT601", 2), ("BT601_FULL", 3)):
             globals()[f"I{_sub_name}{_infix}_{_name}"] = 512 + _matrix + 4 * _sub + 16 * _filter
 PLANAR_FAMILY = tuple(512 + m + 4 * s + 16 * f for f in (0, 1, 2) for s in (0, 1, 2) for m in (0, 1, 2, 3) if not (s == 2 and f))
+# device pixels only (HYDAMD_I010_* ... HYDAMD_I416_*): the same three planes in 16-bit words of 10, 12 or 16 significant bits,
+# LSB-aligned — 2048 + matrix + 4 * subsampling + 16 * filter + 64 * depth, depth 1, 2, 3 (libyuv's names: I010, I210, I410 ...)
+for _bits, _depth in P016_DEPTHS.items():
+    for _sub_name, _sub in PLANAR_SUBSAMPLINGS.items():
+        for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
+            if _sub == 2 and _filter:
+                continue
+            for _name, _matrix in (("BT709", 0), ("BT709_FULL", 1), ("BT601", 2), ("BT601_FULL", 3)):
+                globals()[f"I{_sub_name[2]}{_bits}{_infix}_{_name}"] = 2048 + _matrix + 4 * _sub + 16 * _filter + 64 * _depth
+PLANAR16_FAMILY = tuple(f - 512 + 2048 + 64 * d for d in (1, 2, 3) for f in PLANAR_FAMILY)
 
 
 def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
@@ -75,6 +85,13 @@ def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
     if sub == 2 and filt:
         raise ValueError("4:4:4 has a chroma sample for every pixel: no chroma filter")
     return 512 + (int(matrix) - NV12_BT709) + 4 * sub + 16 * filt
+
+
+def planar16_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None, depth: int = 10) -> int:
+    """The sample format of a planar YCbCr picture of 16-bit words: planar_fmt's arguments and ``depth`` 10, 12 or 16."""
+    if depth not in P016_DEPTHS:
+        raise ValueError("depth is 10, 12 or 16")
+    return planar_fmt(matrix, subsampling, chroma) - 512 + 2048 + 64 * P016_DEPTHS[depth]
 
 
 class Nv12:
@@ -209,10 +226,14 @@ class PlanarYuv(Nv12):
 
     def __init__(self, y, u, v, matrix: int = NV12_BT709, subsampling="420", chroma=None):
         fmt = planar_fmt(matrix, subsampling, chroma)
-        sub = PLANAR_SUBSAMPLINGS[str(subsampling)]
         names = [str(t.dtype).rpartition(".")[2] for t in (y, u, v)]
         if any(t.element_size() != 1 or t.dim() != 2 for t in (y, u, v)) or any(n.startswith(("float", "bool")) for n in names):
             raise ValueError("planar YCbCr planes are 8-bit: y (H, W), u and v (ch, cw)")
+        self._planes(y, u, v, fmt, subsampling)
+
+    def _planes(self, y, u, v, fmt, subsampling):
+        """the shape, stride and pitch rules of three planes of one sample width"""
+        sub = PLANAR_SUBSAMPLINGS[str(subsampling)]
         h, w = y.shape
         cw, ch = (w if sub == 2 else -(-w // 2)), (-(-h // 2) if sub == 0 else h)
         if h < 1 or w < 1 or tuple(u.shape) != (ch, cw) or tuple(v.shape) != (ch, cw):
@@ -235,10 +256,24 @@ class PlanarYuv(Nv12):
         return [self.y.data_ptr(), self.u.data_ptr(), self.v.data_ptr()]
 
 
+class PlanarYuv16(PlanarYuv):
+    """A planar YCbCr picture of 16-bit words in device memory — I010, I210, I410, I012 ... I416: PlanarYuv's three planes as
+    tensors of a 2-byte integer dtype, ``depth`` 10, 12 or 16 significant bits LSB-aligned (bits above the depth are ignored) —
+    accepted wherever an Nv12 object is.  Shapes, strides and the one chroma pitch as PlanarYuv's, in words; the C API takes the
+    chroma planes' pitch in words in its pixel_stride argument."""
+
+    def __init__(self, y, u, v, matrix: int = NV12_BT709, subsampling="420", chroma=None, depth: int = 10):
+        fmt = planar16_fmt(matrix, subsampling, chroma, depth)
+        names = [str(t.dtype).rpartition(".")[2] for t in (y, u, v)]
+        if any(t.element_size() != 2 or t.dim() != 2 for t in (y, u, v)) or any(n.startswith(("float", "bfloat", "complex")) for n in names):
+            raise ValueError("planar YCbCr planes of 10 to 16 bits are 16-bit integers: y (H, W), u and v (ch, cw)")
+        self._planes(y, u, v, fmt, subsampling)
+
+
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
     float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
-    An Nv12, P016 or PlanarYuv object: its own format."""
+    An Nv12, P016, PlanarYuv or PlanarYuv16 object: its own format."""
     if isinstance(t, Nv12):
         return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]
@@ -1298,7 +1333,7 @@ def mixed_descriptors(imgs, sample_fmt: Optional[int] = None, sample_fmts=None):
             elif fmt != sample_fmt:
                 raise ValueError("the images of a batch share one sample format")
         elif isinstance(sample_fmts, list) and fmt != given:
-            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FAMILY + P016_FAMILY + PLANAR_FAMILY:
+            if given in (0, 1, 2, FLOAT16, BFLOAT16) + NV12_FAMILY + P016_FAMILY + PLANAR_FAMILY + PLANAR16_FAMILY:
                 raise ValueError("sample_fmts disagrees with a tensor's dtype")
             fmt = given  # not a format at all: the library refuses it (HYD_API_ERROR), nothing is enqueued
         fmts.append(fmt)

@@ -131,7 +131,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * pointers — hyd_send_tile, hydamd_encode_lf_group_host — refuse both with "Invalid Sample Format", as they and every
  * other entry point refuse anything that is neither 0..4 nor of the NV12 family (16..19, 32..35, 48..51, below) nor of the
  * P010 / P012 / P016 family (80..83, 96..99, 112..115, 144..147, 160..163, 176..179, 208..211, 224..227, 240..243, below)
- * nor of the planar YCbCr family (512..523, 528..535, 544..551, below).
+ * nor of the planar YCbCr family (512..523, 528..535, 544..551, below) nor of the planar YCbCr family of 16-bit words
+ * (2112..2151, 2176..2215, 2240..2279 less the planar family's gaps, below).
  */
 #define HYDAMD_FLOAT16 3
 #define HYDAMD_BFLOAT16 4
@@ -272,8 +273,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever NV12 is.  hydamd_encode_image_multi takes the nearest forms and refuses the interpolated 24 as it does
  * NV12's; the host-pointer entry points refuse all 36 with "Invalid Sample Format".
  * Out of scope: BT.2020 and the PQ / HLG transfer curves — the codestream this encoder writes signals sRGB or linear sRGB
- * only, so HDR10 content would be mis-described whatever the matrix; planar I010 and deeper; 16-bit 4:2:2 and 4:4:4;
- * host-pointer P010.
+ * only, so HDR10 content would be mis-described whatever the matrix; two-plane 16-bit 4:2:2 and 4:4:4 (P210, P410: the planar
+ * forms I210 ... I416 are further down, HYDAMD_I010_* ...); host-pointer P010.
  */
 #define HYDAMD_P010_BT709 80
 #define HYDAMD_P010_BT709_FULL 81
@@ -322,7 +323,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  *   HYDAMD_I420_*    512..515     528..531 (C)    544..547 (L)
  *   HYDAMD_I422_*    516..519     532..535 (C)    548..551 (L)
  *   HYDAMD_I444_*    520..523
- * 28 numbers.  524..527, 536..543, 552 and up name nothing; + 64 * depth is kept for deeper planes and names nothing now.
+ * 28 numbers.  524..527, 536..543, 552 and up name nothing, 512 + ... + 64 * depth included: planes deeper than 8 bits have
+ * numbers of their own at 2048 (HYDAMD_I010_* ..., the next section).
  * A JPEG is BT601_FULL, centre-sited: HYDAMD_I420C_BT601_FULL, HYDAMD_I422C_BT601_FULL or HYDAMD_I444_BT601_FULL.
  *
  * How such a picture is named, wherever a sample_fmt names device pixels and in a HydAmdImageDesc:
@@ -352,8 +354,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever NV12 is, and beside NV12, P010 and RGB pictures in one hydamd_encode_mixed_formats launch group.
  * hydamd_encode_image_multi takes the 12 nearest forms and refuses the 16 interpolated ones as it does NV12's (a 4:2:2 window
  * also crosses into an LF group another shard owns); the host-pointer entry points refuse all 28 with "Invalid Sample Format".
- * Out of scope: I010 and deeper planes; NV21 and NV16; packed YUY2 / UYVY / AYUV; U and V planes of different pitches;
- * top-left siting; host-pointer input; cross-shard interpolation.
+ * Out of scope: NV21 and NV16; packed YUY2 / UYVY / AYUV; U and V planes of different pitches; top-left siting; host-pointer
+ * input; cross-shard interpolation.  (I010 and deeper planes: the next section.)
  */
 #define HYDAMD_I420_BT709 512
 #define HYDAMD_I420_BT709_FULL 513
@@ -385,11 +387,141 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
 #define HYDAMD_I422L_BT601_FULL 551
 
 /*
+ * PLANAR YCbCr DEVICE pixels OF 16-BIT WORDS: I010, I210, I410, I012, I212, I412, I016, I216 and I416 — the planar family's three
+ * planes with 10, 12 or 16 significant bits a sample, LSB-ALIGNED in 16-bit words.  What every software decoder leaves for HEVC
+ * Main10, 10-bit AV1 and VP9 and ProRes (yuv420p10le, yuv422p10le, yuv444p12le ...) and how rocDecode hands out 4:4:4 surfaces
+ * above 8 bits; the first 16-bit route for 4:2:2 and 4:4:4 of any layout.  Read by the transform kernel as they are.
+ *   sample_fmt = 2048 + matrix + 4 * subsampling + 16 * filter + 64 * depth
+ * matrix 0..3, subsampling 0..2 and filter 0..2 as in the planar family; depth 1, 2, 3 = 10, 12, 16 significant bits as in the
+ * P010 family:
+ *                     nearest       centre-sited    left-sited
+ *   HYDAMD_I010_*    2112..2115    2128..2131 (C)   2144..2147 (L)
+ *   HYDAMD_I210_*    2116..2119    2132..2135 (C)   2148..2151 (L)
+ *   HYDAMD_I410_*    2120..2123
+ *   HYDAMD_I012_*    2176..2179    2192..2195 (C)   2208..2211 (L)
+ *   HYDAMD_I212_*    2180..2183    2196..2199 (C)   2212..2215 (L)
+ *   HYDAMD_I412_*    2184..2187
+ *   HYDAMD_I016_*    2240..2243    2256..2259 (C)   2272..2275 (L)
+ *   HYDAMD_I216_*    2244..2247    2260..2263 (C)   2276..2279 (L)
+ *   HYDAMD_I416_*    2248..2251
+ * 84 numbers, 28 a depth; the gaps are the planar family's.  2048..2111 (depth 0) name nothing — 8-bit planes stay at 512 — nor
+ * does 2280 and up.
+ *
+ * How such a picture is named: as a planar picture, everything in SAMPLES (16-bit words), as every stride of this API is —
+ *   src[0], [1], [2]  the first Y, U and V word: independent pointers, each 2-byte aligned
+ *   row_stride        the pitch of the Y plane in words; may be negative
+ *   pixel_stride      THE ONE PITCH OF BOTH CHROMA PLANES in words; may be negative, independently of row_stride
+ * Plane sizes, odd sizes, crop rules, the origin of an LF group, tile or shard (in words) and what a picture is for the
+ * interpolating forms are the planar family's.  |pixel_stride| < cw is HYD_API_ERROR "planar YCbCr wants the chroma planes'
+ * pitch in pixel_stride"; an address that is not 2-byte aligned is HYD_API_ERROR "planar YCbCr of 16-bit words wants its three
+ * planes on 2-byte boundaries"; nothing is enqueued by either.
+ *
+ * The file is byte for byte what the reference writes for the HYD_UINT16 picture this produces.  A stored word w of a picture of
+ * n significant bits stands for the sample
+ *   s = (w << (16 - n)) & 0xFFFF
+ * — bits above the depth are shifted out and not trusted, so every word means something; depth 16 takes the word as stored,
+ * so an MSB-aligned planar surface of any depth and limited range goes in as HYDAMD_I*16_*.  From there the picture is the
+ * P010 / P012 / P016 picture of the same depth and matrix on the planar family's geometry: nearest takes C[y >> sy][x >> sx] of
+ * each plane; filters 1 and 2 apply the taps of the NV12C / NV12L section to the SHIFTED samples of each plane by itself, 4:2:2
+ * with the far row equal to the near one; then R, G, B by the P010 section's formula and table, unchanged.
+ *
+ * Accepted wherever the planar family is, and beside every other family in one hydamd_encode_mixed_formats launch group.
+ * hydamd_encode_image_multi takes the 36 nearest forms and refuses the 48 interpolated ones as it does NV12's; the host-pointer
+ * entry points refuse all 84 with "Invalid Sample Format".
+ * Out of scope: BT.2020 and PQ / HLG (see the P010 section); MSB-aligned planes with full range at 10 or 12 bits; U and V planes
+ * of different pitches; NV16 / NV21, packed YUY2 / UYVY / Y210; top-left siting; host-pointer input; cross-shard interpolation.
+ */
+#define HYDAMD_I010_BT709 2112
+#define HYDAMD_I010_BT709_FULL 2113
+#define HYDAMD_I010_BT601 2114
+#define HYDAMD_I010_BT601_FULL 2115
+#define HYDAMD_I210_BT709 2116
+#define HYDAMD_I210_BT709_FULL 2117
+#define HYDAMD_I210_BT601 2118
+#define HYDAMD_I210_BT601_FULL 2119
+#define HYDAMD_I410_BT709 2120
+#define HYDAMD_I410_BT709_FULL 2121
+#define HYDAMD_I410_BT601 2122
+#define HYDAMD_I410_BT601_FULL 2123
+#define HYDAMD_I010C_BT709 2128
+#define HYDAMD_I010C_BT709_FULL 2129
+#define HYDAMD_I010C_BT601 2130
+#define HYDAMD_I010C_BT601_FULL 2131
+#define HYDAMD_I210C_BT709 2132
+#define HYDAMD_I210C_BT709_FULL 2133
+#define HYDAMD_I210C_BT601 2134
+#define HYDAMD_I210C_BT601_FULL 2135
+#define HYDAMD_I010L_BT709 2144
+#define HYDAMD_I010L_BT709_FULL 2145
+#define HYDAMD_I010L_BT601 2146
+#define HYDAMD_I010L_BT601_FULL 2147
+#define HYDAMD_I210L_BT709 2148
+#define HYDAMD_I210L_BT709_FULL 2149
+#define HYDAMD_I210L_BT601 2150
+#define HYDAMD_I210L_BT601_FULL 2151
+#define HYDAMD_I012_BT709 2176
+#define HYDAMD_I012_BT709_FULL 2177
+#define HYDAMD_I012_BT601 2178
+#define HYDAMD_I012_BT601_FULL 2179
+#define HYDAMD_I212_BT709 2180
+#define HYDAMD_I212_BT709_FULL 2181
+#define HYDAMD_I212_BT601 2182
+#define HYDAMD_I212_BT601_FULL 2183
+#define HYDAMD_I412_BT709 2184
+#define HYDAMD_I412_BT709_FULL 2185
+#define HYDAMD_I412_BT601 2186
+#define HYDAMD_I412_BT601_FULL 2187
+#define HYDAMD_I012C_BT709 2192
+#define HYDAMD_I012C_BT709_FULL 2193
+#define HYDAMD_I012C_BT601 2194
+#define HYDAMD_I012C_BT601_FULL 2195
+#define HYDAMD_I212C_BT709 2196
+#define HYDAMD_I212C_BT709_FULL 2197
+#define HYDAMD_I212C_BT601 2198
+#define HYDAMD_I212C_BT601_FULL 2199
+#define HYDAMD_I012L_BT709 2208
+#define HYDAMD_I012L_BT709_FULL 2209
+#define HYDAMD_I012L_BT601 2210
+#define HYDAMD_I012L_BT601_FULL 2211
+#define HYDAMD_I212L_BT709 2212
+#define HYDAMD_I212L_BT709_FULL 2213
+#define HYDAMD_I212L_BT601 2214
+#define HYDAMD_I212L_BT601_FULL 2215
+#define HYDAMD_I016_BT709 2240
+#define HYDAMD_I016_BT709_FULL 2241
+#define HYDAMD_I016_BT601 2242
+#define HYDAMD_I016_BT601_FULL 2243
+#define HYDAMD_I216_BT709 2244
+#define HYDAMD_I216_BT709_FULL 2245
+#define HYDAMD_I216_BT601 2246
+#define HYDAMD_I216_BT601_FULL 2247
+#define HYDAMD_I416_BT709 2248
+#define HYDAMD_I416_BT709_FULL 2249
+#define HYDAMD_I416_BT601 2250
+#define HYDAMD_I416_BT601_FULL 2251
+#define HYDAMD_I016C_BT709 2256
+#define HYDAMD_I016C_BT709_FULL 2257
+#define HYDAMD_I016C_BT601 2258
+#define HYDAMD_I016C_BT601_FULL 2259
+#define HYDAMD_I216C_BT709 2260
+#define HYDAMD_I216C_BT709_FULL 2261
+#define HYDAMD_I216C_BT601 2262
+#define HYDAMD_I216C_BT601_FULL 2263
+#define HYDAMD_I016L_BT709 2272
+#define HYDAMD_I016L_BT709_FULL 2273
+#define HYDAMD_I016L_BT601 2274
+#define HYDAMD_I016L_BT601_FULL 2275
+#define HYDAMD_I216L_BT709 2276
+#define HYDAMD_I216L_BT709_FULL 2277
+#define HYDAMD_I216L_BT601 2278
+#define HYDAMD_I216L_BT601_FULL 2279
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_* or HYDAMD_I4xx_* formats (whose src and strides are
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_* or HYDAMD_Ixnn_* formats (whose src and strides are
  * described above).  With an interpolating format (HYDAMD_NV12C_*, HYDAMD_NV12L_*, their P01x and I42x forms) the LF group is a
  * picture of its own: its chroma clamps at its own edges.
  */
