@@ -317,55 +317,36 @@ void host_input_lut(uint16_t *lut, size_t size, int linear_light) {
 static_assert(HYD_FMT_UINT8 == HYDK_FMT_U8 && HYD_FMT_UINT16 == HYDK_FMT_U16 && HYD_FMT_FLOAT32 == HYDK_FMT_F32 &&
                   HYD_FMT_FLOAT16 == HYDAMD_FLOAT16 && HYD_FMT_BFLOAT16 == HYDAMD_BFLOAT16,
               "the public formats' integer classes are the kernels' classes");
-static_assert(HYD_FMT_NV12_BT709 == HYDAMD_NV12_BT709 && HYD_FMT_NV12_BT709_FULL == HYDAMD_NV12_BT709_FULL &&
-                  HYD_FMT_NV12_BT601 == HYDAMD_NV12_BT601 && HYD_FMT_NV12_BT601_FULL == HYDAMD_NV12_BT601_FULL &&
-                  HYDAMD_NV12_BT709 + HYDK_YUV_BT709_FULL == HYDAMD_NV12_BT709_FULL &&
-                  HYDAMD_NV12_BT709 + HYDK_YUV_BT601 == HYDAMD_NV12_BT601 &&
-                  HYDAMD_NV12_BT709 + HYDK_YUV_BT601_FULL == HYDAMD_NV12_BT601_FULL,
-              "the NV12 formats are 16 + the kernels' matrix index");
-static_assert(HYD_FMT_NV12C_BT709 == HYDAMD_NV12C_BT709 && HYD_FMT_NV12C_BT709_FULL == HYDAMD_NV12C_BT709_FULL &&
-                  HYD_FMT_NV12C_BT601 == HYDAMD_NV12C_BT601 && HYD_FMT_NV12C_BT601_FULL == HYDAMD_NV12C_BT601_FULL &&
-                  HYD_FMT_NV12L_BT709 == HYDAMD_NV12L_BT709 && HYD_FMT_NV12L_BT709_FULL == HYDAMD_NV12L_BT709_FULL &&
-                  HYD_FMT_NV12L_BT601 == HYDAMD_NV12L_BT601 && HYD_FMT_NV12L_BT601_FULL == HYDAMD_NV12L_BT601_FULL &&
-                  HYDAMD_NV12C_BT709 == HYDAMD_NV12_BT709 + 16 * HYDK_CHROMA_CENTRE &&
-                  HYDAMD_NV12L_BT709 == HYDAMD_NV12_BT709 + 16 * HYDK_CHROMA_LEFT && HYD_FMT_NV12_FILTERS == HYDK_CHROMA_FILTERS,
-              "the NV12 family is 16 + the kernels' matrix index + 16 * the kernels' chroma filter");
-#define HYDAMD_P016_ROW(P, D)                                                                                                   \
-    (HYD_FMT_##P##_BT709 == HYDAMD_##P##_BT709 && HYD_FMT_##P##_BT709_FULL == HYDAMD_##P##_BT709_FULL &&                         \
-     HYD_FMT_##P##_BT601 == HYDAMD_##P##_BT601 && HYD_FMT_##P##_BT601_FULL == HYDAMD_##P##_BT601_FULL &&                         \
-     HYD_FMT_##P##C_BT709 == HYDAMD_##P##C_BT709 && HYD_FMT_##P##C_BT709_FULL == HYDAMD_##P##C_BT709_FULL &&                     \
-     HYD_FMT_##P##C_BT601 == HYDAMD_##P##C_BT601 && HYD_FMT_##P##C_BT601_FULL == HYDAMD_##P##C_BT601_FULL &&                     \
-     HYD_FMT_##P##L_BT709 == HYDAMD_##P##L_BT709 && HYD_FMT_##P##L_BT709_FULL == HYDAMD_##P##L_BT709_FULL &&                     \
-     HYD_FMT_##P##L_BT601 == HYDAMD_##P##L_BT601 && HYD_FMT_##P##L_BT601_FULL == HYDAMD_##P##L_BT601_FULL &&                     \
-     HYDAMD_##P##_BT709 == HYDAMD_NV12_BT709 + 64 * (D) && HYDAMD_##P##C_BT709 == HYDAMD_##P##_BT709 + 16 * HYDK_CHROMA_CENTRE && \
-     HYDAMD_##P##L_BT709 == HYDAMD_##P##_BT709 + 16 * HYDK_CHROMA_LEFT)
-static_assert(HYDAMD_P016_ROW(P010, HYDK_YUV16_P010) && HYDAMD_P016_ROW(P012, HYDK_YUV16_P012) && HYDAMD_P016_ROW(P016, HYDK_YUV16_P016) &&
-                  HYD_FMT_P016_DEPTHS == HYDK_YUV16_DEPTHS,
-              "the P016 family is 16 + the kernels' matrix index + 16 * the kernels' chroma filter + 64 * the kernels' depth");
-#undef HYDAMD_P016_ROW
-#define HYDAMD_PLANAR_ROW(P)                                                                                    \
-    (HYD_FMT_##P##_BT709 == HYDAMD_##P##_BT709 && HYD_FMT_##P##_BT709_FULL == HYDAMD_##P##_BT709_FULL &&         \
-     HYD_FMT_##P##_BT601 == HYDAMD_##P##_BT601 && HYD_FMT_##P##_BT601_FULL == HYDAMD_##P##_BT601_FULL &&         \
-     HYDAMD_##P##_BT709 + HYDK_YUV_BT601_FULL == HYDAMD_##P##_BT601_FULL)
-static_assert(HYDAMD_PLANAR_ROW(I420) && HYDAMD_PLANAR_ROW(I422) && HYDAMD_PLANAR_ROW(I444) && HYDAMD_PLANAR_ROW(I420C) &&
-                  HYDAMD_PLANAR_ROW(I422C) && HYDAMD_PLANAR_ROW(I420L) && HYDAMD_PLANAR_ROW(I422L) &&
-                  HYDAMD_I422_BT709 == HYDAMD_I420_BT709 + 4 * HYDK_PLANAR_422 && HYDAMD_I444_BT709 == HYDAMD_I420_BT709 + 4 * HYDK_PLANAR_444 &&
-                  HYDAMD_I420C_BT709 == HYDAMD_I420_BT709 + 16 * HYDK_CHROMA_CENTRE && HYDAMD_I422L_BT709 == HYDAMD_I422_BT709 + 16 * HYDK_CHROMA_LEFT &&
-                  HYD_FMT_PLANAR_420 == HYDK_PLANAR_420 && HYD_FMT_PLANAR_422 == HYDK_PLANAR_422 && HYD_FMT_PLANAR_444 == HYDK_PLANAR_444,
-              "the planar family is 512 + the kernels' matrix index + 4 * the kernels' subsampling + 16 * the kernels' chroma filter");
-#define HYDAMD_PLANAR16_ROW(P, S, F, D)                                                                                  \
-    (HYDAMD_PLANAR_ROW(P) && HYDAMD_##P##_BT709 == HYD_FMT_PLANAR16_BASE + 4 * (S) + 16 * (F) + 64 * (D))
-#define HYDAMD_PLANAR16_DEPTH(B, D)                                                                                               \
-    (HYDAMD_PLANAR16_ROW(I0##B, HYDK_PLANAR_420, HYDK_CHROMA_NEAREST, D) && HYDAMD_PLANAR16_ROW(I2##B, HYDK_PLANAR_422, HYDK_CHROMA_NEAREST, D) && \
-     HYDAMD_PLANAR16_ROW(I4##B, HYDK_PLANAR_444, HYDK_CHROMA_NEAREST, D) && HYDAMD_PLANAR16_ROW(I0##B##C, HYDK_PLANAR_420, HYDK_CHROMA_CENTRE, D) &&  \
-     HYDAMD_PLANAR16_ROW(I2##B##C, HYDK_PLANAR_422, HYDK_CHROMA_CENTRE, D) && HYDAMD_PLANAR16_ROW(I0##B##L, HYDK_PLANAR_420, HYDK_CHROMA_LEFT, D) &&  \
-     HYDAMD_PLANAR16_ROW(I2##B##L, HYDK_PLANAR_422, HYDK_CHROMA_LEFT, D))
-static_assert(HYDAMD_PLANAR16_DEPTH(10, HYDK_YUV16_P010) && HYDAMD_PLANAR16_DEPTH(12, HYDK_YUV16_P012) && HYDAMD_PLANAR16_DEPTH(16, HYDK_YUV16_P016),
-              "the planar16 family is 2048 + the kernels' matrix index + 4 * subsampling + 16 * chroma filter + 64 * the kernels' depth");
+/* every public YCbCr name against what hyd_fmt_describe says of its number, in the kernels' constants: a stem's four matrices */
+constexpr bool fmt_names(int bt709, int bt709_full, int bt601, int bt601_full, int layout, int depth, int sub, int filter) {
+    const HydFmt d = hyd_fmt_describe(bt709);
+    return d.device && d.layout == layout && d.depth == depth && d.sub == sub && d.filter == filter && d.matrix == HYDK_YUV_BT709 &&
+           bt709_full == bt709 + HYDK_YUV_BT709_FULL && bt601 == bt709 + HYDK_YUV_BT601 && bt601_full == bt709 + HYDK_YUV_BT601_FULL &&
+           hyd_fmt_describe(bt601_full).matrix == HYDK_YUV_BT601_FULL;
+}
+#define HYDAMD_FMT_STEM(P, ...) fmt_names(HYDAMD_##P##_BT709, HYDAMD_##P##_BT709_FULL, HYDAMD_##P##_BT601, HYDAMD_##P##_BT601_FULL, __VA_ARGS__)
+#define HYDAMD_FMT_FILTERS(P, ...)                                                                                          \
+    (HYDAMD_FMT_STEM(P, __VA_ARGS__, HYDK_CHROMA_NEAREST) && HYDAMD_FMT_STEM(P##C, __VA_ARGS__, HYDK_CHROMA_CENTRE) && \
+     HYDAMD_FMT_STEM(P##L, __VA_ARGS__, HYDK_CHROMA_LEFT))
+#define HYDAMD_FMT_PLANES(B, D)                                                                                                      \
+    (HYDAMD_FMT_FILTERS(I0##B, HYD_LAYOUT_PLANES, D, HYDK_PLANAR_420) && HYDAMD_FMT_FILTERS(I2##B, HYD_LAYOUT_PLANES, D, HYDK_PLANAR_422) && \
+     HYDAMD_FMT_STEM(I4##B, HYD_LAYOUT_PLANES, D, HYDK_PLANAR_444, HYDK_CHROMA_NEAREST))
+static_assert(HYDAMD_FMT_FILTERS(NV12, HYD_LAYOUT_PAIRS, 0, HYDK_PLANAR_420) && HYDAMD_FMT_FILTERS(P010, HYD_LAYOUT_PAIRS, HYDK_YUV16_P010, HYDK_PLANAR_420) &&
+                  HYDAMD_FMT_FILTERS(P012, HYD_LAYOUT_PAIRS, HYDK_YUV16_P012, HYDK_PLANAR_420) &&
+                  HYDAMD_FMT_FILTERS(P016, HYD_LAYOUT_PAIRS, HYDK_YUV16_P016, HYDK_PLANAR_420),
+              "(U, V) pairs: 16 + the kernels' matrix index + 16 * the kernels' chroma filter + 64 * the kernels' depth");
+static_assert(HYDAMD_FMT_FILTERS(I420, HYD_LAYOUT_PLANES, 0, HYDK_PLANAR_420) && HYDAMD_FMT_FILTERS(I422, HYD_LAYOUT_PLANES, 0, HYDK_PLANAR_422) &&
+                  HYDAMD_FMT_STEM(I444, HYD_LAYOUT_PLANES, 0, HYDK_PLANAR_444, HYDK_CHROMA_NEAREST),
+              "a plane each: 512 + the kernels' matrix index + 4 * the kernels' subsampling + 16 * the kernels' chroma filter");
+static_assert(HYDAMD_FMT_PLANES(10, HYDK_YUV16_P010) && HYDAMD_FMT_PLANES(12, HYDK_YUV16_P012) && HYDAMD_FMT_PLANES(16, HYDK_YUV16_P016),
+              "a plane each of 16-bit words: 2048 + the kernels' matrix index + 4 * subsampling + 16 * chroma filter + 64 * the kernels' depth");
+static_assert(hyd_fmt_describe(HYDAMD_NV12_BT709).bits == 8 && hyd_fmt_describe(HYDAMD_P010_BT709).bits == 10 && hyd_fmt_describe(HYDAMD_I212_BT709).bits == 12 &&
+                  hyd_fmt_describe(HYDAMD_I416_BT709).bits == 16 && HYDK_CHROMA_FILTERS == 3 && HYDK_YUV16_DEPTHS == 3,
+              "a depth's significant bits; three filters and three deeper depths, as hyd_fmt_describe has them");
 static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_FORMS == 13, "the job did not grow; launch_transform's mask has 13 bits");
-#undef HYDAMD_PLANAR16_DEPTH
-#undef HYDAMD_PLANAR16_ROW
-#undef HYDAMD_PLANAR_ROW
+#undef HYDAMD_FMT_PLANES
+#undef HYDAMD_FMT_FILTERS
+#undef HYDAMD_FMT_STEM
 
 /* the public format a recorded job reads (hydk_store.h: the encode of what record_lf_group decoded) */
 int job_sample_fmt(const HydkLfJob &job) {
@@ -441,12 +422,8 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
                     int sample_fmt, size_t width, size_t height, unsigned preset, const size_t *pic = nullptr) {
     if (width == 0 || height == 0 || width > 2048 || height > 2048)
         return fail(ctx, ST_API_ERROR, "LF group must be between 1 and 2048 pixels in each direction");
-    if (!hyd_fmt_is_device(sample_fmt))
-        return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
-    if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
-        return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
-    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, pic ? pic[2] : width))
-        return fail(ctx, ST_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG);
+    if (const char *refusal = hyd_fmt_refusal(sample_fmt, src, pixel_stride, pic ? pic[2] : width))
+        return fail(ctx, ST_API_ERROR, refusal);
     /* half precision is a storage form of the float class: the job is a float job, and every `fmt == HYDK_FMT_F32` below
      * and in the kernels keeps meaning "float class".  NV12 is a storage form of the 8-bit class: 4-byte token records, the
      * 8-bit transfer table, and whatever form of the entropy stage is selected */
@@ -584,7 +561,7 @@ int ensure_staging(HydAmdContext *ctx, size_t tile_bytes) {
             const char *old_base = ctx->d_arena + (size_t)i * ctx->arena_tile;
             if (!job.width || (const char *)job.src[0] != old_base)
                 continue; /* not a host-staged slot */
-            const size_t ss = hyd_fmt_bytes(job_sample_fmt(job));
+            const size_t ss = (size_t)hyd_fmt_describe(job_sample_fmt(job)).bytes;
             char *base = fresh + (size_t)i * tile_bytes;
             HIP_TRY(ctx, hipMemcpy(base, old_base, (size_t)job.width * job.height * 3 * ss, hipMemcpyDeviceToDevice));
             job.src[0] = base;
@@ -1314,7 +1291,7 @@ int hydamd_encode_lf_group_at(HydAmdContext *ctx, int slot, const void *const sr
         return st;
     if (!src || !src[0] || !src[1] || !src[2])
         return fail(ctx, ST_API_ERROR, "null pixel pointer");
-    if (!hyd_fmt_is_device(sample_fmt))
+    if (!hyd_fmt_describe(sample_fmt).device)
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     if ((x0 | y0) & 255)
         return fail(ctx, ST_API_ERROR, "an LF group starts at multiples of 256 in its picture");
@@ -1336,10 +1313,10 @@ int hydamd_encode_lf_group_host(HydAmdContext *ctx, int slot, const void *const 
         return fail(ctx, ST_API_ERROR, "null pixel pointer");
     if (width == 0 || height == 0 || width > 2048 || height > 2048)
         return fail(ctx, ST_API_ERROR, "LF group must be between 1 and 2048 pixels in each direction");
-    if (!hyd_fmt_is_host(sample_fmt)) /* host pixels come in the reference's three formats */
+    if (!hyd_fmt_describe(sample_fmt).host) /* host pixels come in the reference's three formats */
         return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t ss = hyd_fmt_bytes(sample_fmt);
+    const size_t ss = (size_t)hyd_fmt_describe(sample_fmt).bytes;
     const size_t bytes = width * height * 3 * ss;
     /* size for full 2048x2048 tiles of this sample type so that later tiles never reallocate */
     st = ensure_staging(ctx, (size_t)2048 * 2048 * 3 * ss);
@@ -1384,12 +1361,8 @@ int hydamd_encode_image(HydAmdContext *ctx, const void *const src[3], ptrdiff_t 
     const size_t lfx = (width + 2047) >> 11, lfy = (height + 2047) >> 11;
     if (lfx * lfy > (size_t)ctx->max_slots)
         return fail(ctx, ST_API_ERROR, "context has too few LF-group slots for this image");
-    if (!hyd_fmt_is_device(sample_fmt))
-        return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
-    if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
-        return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
-    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, width))
-        return fail(ctx, ST_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG);
+    if (const char *refusal = hyd_fmt_refusal(sample_fmt, src, pixel_stride, width))
+        return fail(ctx, ST_API_ERROR, refusal);
     int st = hydamd_begin_frame(ctx, (unsigned)(lfx * lfy));
     for (size_t ty = 0; ty < lfy && st == ST_OK; ty++)
         for (size_t tx = 0; tx < lfx && st == ST_OK; tx++) {
@@ -1458,13 +1431,11 @@ int hydamd_encode_image_batch(HydAmdContext *ctx, int frames, const void *const 
         return fail(ctx, ST_API_ERROR, "null pixel pointer");
     if (width == 0 || height == 0)
         return fail(ctx, ST_API_ERROR, "empty image");
-    if (!hyd_fmt_is_device(sample_fmt))
-        return fail(ctx, ST_API_ERROR, "Invalid Sample Format");
-    for (int f = 0; f < frames; f++)
-        if (src[3 * (size_t)f + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * (size_t)f, pixel_stride))
-            return fail(ctx, ST_API_ERROR, hyd_fmt_layout_msg(sample_fmt));
-    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, width))
-        return fail(ctx, ST_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG);
+    const char *refusal = nullptr; /* every frame that has pointers to its layout, then the pitch */
+    for (int f = 0; f < frames && !refusal; f++)
+        refusal = hyd_fmt_refusal(sample_fmt, src[3 * (size_t)f + 1] ? src + 3 * (size_t)f : nullptr, pixel_stride, 0);
+    if (refusal || (refusal = hyd_fmt_refusal(sample_fmt, nullptr, pixel_stride, width)))
+        return fail(ctx, ST_API_ERROR, refusal);
     const size_t lfx = (width + 2047) >> 11, lfy = (height + 2047) >> 11, n = lfx * lfy;
     int st = hydamd_begin_batch(ctx, (unsigned)n, frames);
     for (int f = 0; f < frames && st == ST_OK; f++) {

@@ -71,7 +71,7 @@ HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
     return forms[storage >= 0 && storage < HYDK_STORE_FORMS ? storage : 0];
 }
 
-/* A public sample format taken apart into what a job holds.  ok: hyd_fmt_is_device accepts it (else every field is 0).
+/* A public sample format taken apart into what a job holds.  ok: a device entry point takes it (else every field is 0).
  * matrix: HYDK_YUV_* (0 ... 3), + 4 * depth (HYDK_YUV16_P01x) for the 16-bit forms; filter: HYDK_CHROMA_*; sub: HYDK_PLANAR_*;
  * sx, sy: log2 of the pixels one chroma sample spans across and down. */
 typedef struct HydkSampleForm {
@@ -81,33 +81,13 @@ typedef struct HydkSampleForm {
 } HydkSampleForm;
 
 static inline HydkSampleForm hydk_decode_fmt(int f) {
-    HydkSampleForm d = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (!hyd_fmt_is_device(f))
-        return d;
-    d.ok = 1;
-    if (hyd_fmt_is_yuv420(f)) {
-        d.filter = (uint32_t)hyd_fmt_p016_filter(f);
-        d.matrix = (uint32_t)(hyd_fmt_p016_matrix(f) + 4 * hyd_fmt_p016_depth(f)); /* (depth 0: the 8-bit family) */
-        d.storage = (uint32_t)((hyd_fmt_p016_depth(f) ? HYDK_STORE_P016 : HYDK_STORE_NV12) + (d.filter != 0));
-        d.sx = d.sy = 1;
-    } else if (hyd_fmt_is_planar_yuv(f)) {
-        d.filter = (uint32_t)hyd_fmt_planar_filter(f);
-        d.matrix = (uint32_t)hyd_fmt_planar_matrix(f);
-        d.sub = (uint32_t)hyd_fmt_planar_sub(f);
-        d.storage = (uint32_t)(HYDK_STORE_YUVP + (d.filter != 0));
-        d.sx = hyd_fmt_planar_sx(f);
-        d.sy = hyd_fmt_planar_sy(f);
-    } else if (hyd_fmt_is_planar16(f)) {
-        d.filter = (uint32_t)hyd_fmt_planar16_filter(f);
-        d.matrix = (uint32_t)(hyd_fmt_planar16_matrix(f) + 4 * hyd_fmt_planar16_depth(f));
-        d.sub = (uint32_t)hyd_fmt_planar16_sub(f);
-        d.storage = (uint32_t)(HYDK_STORE_YUVP16 + (d.filter != 0));
-        d.sx = hyd_fmt_planar16_sx(f);
-        d.sy = hyd_fmt_planar16_sy(f);
-    } else if (f > HYD_FMT_FLOAT32) {
+    const HydFmt fmt = hyd_fmt_describe(f);
+    HydkSampleForm d = {fmt.device, 0, 0, (uint32_t)(fmt.matrix + 4 * fmt.depth), (uint32_t)fmt.filter, (uint32_t)fmt.sub, fmt.sx, fmt.sy};
+    if (fmt.layout != HYD_LAYOUT_RGB) /* the YCbCr forms in the table's order: pairs then planes, bytes then words, nearest then interpolated */
+        d.storage = (uint32_t)(HYDK_STORE_NV12 + 4 * (fmt.layout == HYD_LAYOUT_PLANES) + 2 * (fmt.bytes == 2) + (fmt.filter != 0));
+    else if (f == HYD_FMT_FLOAT16 || f == HYD_FMT_BFLOAT16)
         d.storage = (uint32_t)(f == HYD_FMT_FLOAT16 ? HYDK_STORE_F16 : HYDK_STORE_BF16);
-    }
-    d.cls = d.storage > HYDK_STORE_F32 ? hydk_store_form((int)d.storage).cls : f;
+    d.cls = d.storage > HYDK_STORE_F32 ? hydk_store_form((int)d.storage).cls : fmt.device ? f : 0;
     return d;
 }
 
@@ -116,11 +96,8 @@ static inline int hydk_encode_fmt(HydkSampleForm d) {
     const HydkStoreForm form = hydk_store_form((int)d.storage);
     if (!form.ycbcr)
         return d.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : d.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : d.cls;
-    if (form.chroma_planes == 2 && form.bits == 16)
-        return HYD_FMT_PLANAR16_BASE + (int)(d.matrix & 3u) + 4 * (int)d.sub + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2);
-    if (form.chroma_planes == 2)
-        return HYD_FMT_I420_BT709 + (int)d.matrix + 4 * (int)d.sub + 16 * (int)d.filter;
-    return HYD_FMT_NV12_BT709 + (int)(d.matrix & 3u) + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2);
+    const int base = form.chroma_planes == 1 ? HYD_FMT_BASE_PAIRS : form.bits == 16 ? HYD_FMT_BASE_PLANES16 : HYD_FMT_BASE_PLANES;
+    return base + (int)(d.matrix & 3u) + 4 * (int)d.sub + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2);
 }
 
 #endif /* HYD_STORE_FORMS_H_ */

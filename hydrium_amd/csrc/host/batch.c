@@ -233,13 +233,11 @@ HYDRIUM_EXPORT int hydamd_encode_batch(HydAmdBatch *b, int frames, const void *c
     for (int i = 0; i < 3 * frames; i++)
         if (!src[i])
             return hyd_batchrun_fail(r, HYD_API_ERROR, "null pixel pointer", NULL);
-    if (!hyd_fmt_is_device(sample_fmt))
-        return hyd_batchrun_fail(r, HYD_API_ERROR, "Invalid Sample Format", NULL);
-    for (int f = 0; f < frames; f++)
-        if (!hyd_fmt_layout_ok(sample_fmt, src + 3 * f, pixel_stride))
-            return hyd_batchrun_fail(r, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmt), NULL);
-    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, b->W))
-        return hyd_batchrun_fail(r, HYD_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG, NULL);
+    const char *refusal = NULL; /* every frame to its layout, then the pitch */
+    for (int f = 0; f < frames && !refusal; f++)
+        refusal = hyd_fmt_refusal(sample_fmt, src + 3 * f, pixel_stride, 0);
+    if (refusal || (refusal = hyd_fmt_refusal(sample_fmt, NULL, pixel_stride, b->W)) != NULL)
+        return hyd_batchrun_fail(r, HYD_API_ERROR, refusal, NULL);
     int st = hyd_batchrun_busy(r);
     if (st)
         return st;

@@ -1063,7 +1063,7 @@ HYDRIUM_EXPORT HYDStatusCode hyd_send_tile(HYDEncoder *e, const void *const buff
                                            ptrdiff_t row_stride, ptrdiff_t pixel_stride, int is_last,
                                            HYDSampleFormat sample_fmt) {
     int ret;
-    if (!hyd_fmt_is_host((int)sample_fmt)) /* host pixels: the reference's three formats (HYDAMD_FLOAT16 and _BFLOAT16 name device pixels) */
+    if (!hyd_fmt_describe((int)sample_fmt).host) /* host pixels: the reference's three formats (HYDAMD_FLOAT16 and _BFLOAT16 name device pixels) */
         return FAIL(e, HYD_API_ERROR, "Invalid Sample Format");
     if (!e->have_metadata)
         return FAIL(e, HYD_API_ERROR, "metadata was never set");

@@ -476,15 +476,15 @@ HYDRIUM_EXPORT int hydamd_encode_mixed_formats(HydAmdMixed *m, int frames, const
         return hyd_batchrun_fail(r, HYD_API_ERROR, "the batch holds more LF groups than the object has slots", NULL);
     if (!sample_fmts)
         return hyd_batchrun_fail(r, HYD_API_ERROR, "null sample formats", NULL);
-    for (int f = 0; f < frames; f++)
-        if (!hyd_fmt_is_device(sample_fmts[f]))
-            return hyd_batchrun_fail(r, HYD_API_ERROR, "Invalid Sample Format", NULL);
-    for (int f = 0; f < frames; f++)
-        if (!hyd_fmt_layout_ok(sample_fmts[f], images[f].src, images[f].pixel_stride))
-            return hyd_batchrun_fail(r, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmts[f]), NULL);
-    for (int f = 0; f < frames; f++)
-        if (!hyd_fmt_pitch_ok(sample_fmts[f], images[f].pixel_stride, images[f].width))
-            return hyd_batchrun_fail(r, HYD_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG, NULL);
+    const char *refusal = NULL; /* every image's format, then every image's layout, then every image's pitch */
+    for (int f = 0; f < frames && !refusal; f++)
+        refusal = hyd_fmt_refusal(sample_fmts[f], NULL, 0, 0);
+    for (int f = 0; f < frames && !refusal; f++)
+        refusal = hyd_fmt_refusal(sample_fmts[f], images[f].src, images[f].pixel_stride, 0);
+    for (int f = 0; f < frames && !refusal; f++)
+        refusal = hyd_fmt_refusal(sample_fmts[f], NULL, images[f].pixel_stride, images[f].width);
+    if (refusal)
+        return hyd_batchrun_fail(r, HYD_API_ERROR, refusal, NULL);
     int st = hyd_batchrun_busy(r);
     if (st)
         return st;

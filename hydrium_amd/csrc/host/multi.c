@@ -153,17 +153,15 @@ HYDRIUM_EXPORT int hydamd_encode_image_multi(HydAmdMulti *m, const void *const *
     HydShardFrame *f = &m->f;
     if (!src || assembling_shard < 0 || assembling_shard >= f->n)
         return fail(m, HYD_API_ERROR, "bad arguments", NULL);
-    if (!hyd_fmt_is_device(sample_fmt))
-        return fail(m, HYD_API_ERROR, "Invalid Sample Format", NULL);
+    const char *refusal = hyd_fmt_refusal(sample_fmt, NULL, pixel_stride, 0); /* the format alone */
     /* a shard's buffer is only promised to hold its own rows, and the filter would read a neighbouring shard's chroma row */
     /* (a planar 4:2:2 window has no other row, but its columns cross into an LF group that another shard owns) */
-    if (hyd_fmt_is_yuv420_interp(sample_fmt) || hyd_fmt_is_planar_interp(sample_fmt) || hyd_fmt_is_planar16_interp(sample_fmt))
-        return fail(m, HYD_API_ERROR, HYD_FMT_NV12_SHARDED_MSG, NULL);
-    for (int d = 0; d < f->n; d++)
-        if (src[3 * d + 1] && !hyd_fmt_layout_ok(sample_fmt, src + 3 * d, pixel_stride))
-            return fail(m, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmt), NULL);
-    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, m->md.width))
-        return fail(m, HYD_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG, NULL);
+    if (!refusal && hyd_fmt_describe(sample_fmt).filter != 0)
+        refusal = HYD_FMT_NV12_SHARDED_MSG;
+    for (int d = 0; d < f->n && !refusal; d++) /* every shard that has pointers to its layout, then the pitch */
+        refusal = hyd_fmt_refusal(sample_fmt, src[3 * d + 1] ? src + 3 * d : NULL, pixel_stride, 0);
+    if (refusal || (refusal = hyd_fmt_refusal(sample_fmt, NULL, pixel_stride, m->md.width)) != NULL)
+        return fail(m, HYD_API_ERROR, refusal, NULL);
     if (m->in_flight)
         return fail(m, HYD_API_ERROR, "a frame is in flight: hydamd_multi_result first", NULL);
     const size_t W = m->md.width, H = m->md.height;

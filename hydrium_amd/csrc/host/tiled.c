@@ -329,12 +329,9 @@ HYDRIUM_EXPORT int hydamd_encode_image_tiled(HydAmdTiled *t, const void *const s
         return HYD_API_ERROR;
     if (!src || !src[0] || !src[1] || !src[2])
         return fail(t, HYD_API_ERROR, "null pixel pointer", NULL);
-    if (!hyd_fmt_is_device(sample_fmt))
-        return fail(t, HYD_API_ERROR, "Invalid Sample Format", NULL);
-    if (!hyd_fmt_layout_ok(sample_fmt, src, pixel_stride))
-        return fail(t, HYD_API_ERROR, hyd_fmt_layout_msg(sample_fmt), NULL);
-    if (!hyd_fmt_pitch_ok(sample_fmt, pixel_stride, t->g.W))
-        return fail(t, HYD_API_ERROR, HYD_FMT_PLANAR_PITCH_MSG, NULL);
+    const char *refusal = hyd_fmt_refusal(sample_fmt, src, pixel_stride, t->g.W);
+    if (refusal)
+        return fail(t, HYD_API_ERROR, refusal, NULL);
     if (t->in_flight)
         return fail(t, HYD_API_ERROR, "an image is in flight: hydamd_tiled_result first", NULL);
     t->err[0] = 0;

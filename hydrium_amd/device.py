@@ -27,49 +27,43 @@ FMT_OF_DTYPE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float
 # device pixels only (include/hydrium_amd.h, HYDAMD_FLOAT16 / HYDAMD_BFLOAT16): half-precision samples, widened exactly on load
 FLOAT16 = 3
 BFLOAT16 = 4
-# device pixels only (HYDAMD_NV12_*): a decoder's NV12 surface — an 8-bit Y plane and a half-resolution plane of U, V pairs —
-# under one of four matrices; converted in fixed point right after the load (csrc/hip/hydk_yuv.h)
-NV12_BT709 = 16       # BT.709, limited range: HD video
-NV12_BT709_FULL = 17  # BT.709, full range
-NV12_BT601 = 18       # BT.601, limited range: SD video
-NV12_BT601_FULL = 19  # BT.601, full range: what a JPEG decoder leaves (JFIF)
-NV12_FORMATS = (NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL)
-# the same pictures with INTERPOLATED chroma (HYDAMD_NV12C_*, HYDAMD_NV12L_*; csrc/hip/hydk_chroma.h): 16 + matrix + 16 * filter
-NV12C_BT709, NV12C_BT709_FULL, NV12C_BT601, NV12C_BT601_FULL = 32, 33, 34, 35  # centre-sited chroma: JPEG / JFIF, MPEG-1
-NV12L_BT709, NV12L_BT709_FULL, NV12L_BT601, NV12L_BT601_FULL = 48, 49, 50, 51  # left-sited: MPEG-2, H.264, HEVC, AV1 default
-NV12_CENTER_FORMATS = (NV12C_BT709, NV12C_BT709_FULL, NV12C_BT601, NV12C_BT601_FULL)
-NV12_LEFT_FORMATS = (NV12L_BT709, NV12L_BT709_FULL, NV12L_BT601, NV12L_BT601_FULL)
-NV12_FAMILY = NV12_FORMATS + NV12_CENTER_FORMATS + NV12_LEFT_FORMATS
+# device pixels only: YCbCr pictures, converted in fixed point right after the load.  ONE RULE names them all (csrc/hyd_sample_fmt.h):
+# sample format = base + matrix + 4 * subsampling + 16 * filter + 64 * depth.  Base 16: a Y plane and a half-resolution plane of
+# (U, V) pairs — NV12 at depth 0, P010 / P012 / P016 (16-bit words, MSB-aligned) at depth 1, 2, 3; base 512: PLANAR, 8 bits in three
+# planes of their own (I420, I422, I444); base 2048: the same three planes in 16-bit words of 10, 12 or 16 bits, LSB-aligned (libyuv's
+# names: I010, I210, I410 ...).  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
+# full (what a JPEG decoder leaves: JFIF).  filter: nearest, or INTERPOLATED for centre-sited chroma (C: JPEG / JFIF, MPEG-1) or
+# left-sited (L: MPEG-2, H.264, HEVC, AV1 default) — csrc/hip/hydk_chroma.h; 4:4:4 has nearest chroma only.
 CHROMA_FILTERS = {"nearest": 0, "centre": 1, "center": 1, "left": 2}
-# device pixels only (HYDAMD_P010_*, HYDAMD_P012_*, HYDAMD_P016_*; csrc/hip/hydk_yuv16.h): the same two planes in 16-bit words
-# holding 10, 12 or 16 significant bits, MSB-aligned — 16 + matrix + 16 * filter + 64 * depth, depth 1, 2, 3
 P016_DEPTHS = {10: 1, 12: 2, 16: 3}
-for _bits, _depth in P016_DEPTHS.items():
-    for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
-        for _name, _matrix in (("BT709", 0), ("BT709_FULL", 1), ("BT601", 2), ("BT601_FULL", 3)):
-            globals()[f"P0{_bits}{_infix}_{_name}"] = 16 + _matrix + 16 * _filter + 64 * _depth
-P010_FORMATS, P012_FORMATS, P016_FORMATS = ((80, 81, 82, 83), (144, 145, 146, 147), (208, 209, 210, 211))  # nearest chroma
-P016_FAMILY = tuple(16 + m + 16 * f + 64 * d for d in (1, 2, 3) for f in (0, 1, 2) for m in (0, 1, 2, 3))
-# device pixels only (HYDAMD_I420_*, HYDAMD_I422_*, HYDAMD_I444_* and their C / L forms): PLANAR YCbCr, 8 bits in three planes of
-# their own — 512 + matrix + 4 * subsampling + 16 * filter; 4:4:4 has nearest chroma only
 PLANAR_SUBSAMPLINGS = {"420": 0, "422": 1, "444": 2}
-for _sub_name, _sub in PLANAR_SUBSAMPLINGS.items():
+
+
+def ycbcr_fmt(base: int, matrix: int = 0, sub: int = 0, filt: int = 0, depth: int = 0) -> int:
+    return base + matrix + 4 * sub + 16 * filt + 64 * depth
+
+
+def ycbcr_fields(fmt: int):
+    """(base, matrix, subsampling, filter, depth) of a YCbCr sample format"""
+    base = 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
+    n = int(fmt) - base
+    return base, n & 3, (n >> 2) & 3, (n >> 4) & 3, n >> 6
+
+
+_stems = [("NV12", 16, 0, 0)] + [(f"P0{b}", 16, 0, d) for b, d in P016_DEPTHS.items()] + \
+    [(f"I{s}", 512, k, 0) for s, k in PLANAR_SUBSAMPLINGS.items()] + \
+    [(f"I{s[2]}{b}", 2048, k, d) for b, d in P016_DEPTHS.items() for s, k in PLANAR_SUBSAMPLINGS.items()]
+for _stem, _base, _sub, _depth in _stems:  # NV12_BT709 = 16 ... I416_BT601_FULL = 2251, as include/hydrium_amd.h has them
     for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
-        if _sub == 2 and _filter:
-            continue
-        for _name, _matrix in (("BT709", 0), ("BT709_FULL", 1), ("BT601", 2), ("BT601_FULL", 3)):
-            globals()[f"I{_sub_name}{_infix}_{_name}"] = 512 + _matrix + 4 * _sub + 16 * _filter
-PLANAR_FAMILY = tuple(512 + m + 4 * s + 16 * f for f in (0, 1, 2) for s in (0, 1, 2) for m in (0, 1, 2, 3) if not (s == 2 and f))
-# device pixels only (HYDAMD_I010_* ... HYDAMD_I416_*): the same three planes in 16-bit words of 10, 12 or 16 significant bits,
-# LSB-aligned — 2048 + matrix + 4 * subsampling + 16 * filter + 64 * depth, depth 1, 2, 3 (libyuv's names: I010, I210, I410 ...)
-for _bits, _depth in P016_DEPTHS.items():
-    for _sub_name, _sub in PLANAR_SUBSAMPLINGS.items():
-        for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
-            if _sub == 2 and _filter:
-                continue
-            for _name, _matrix in (("BT709", 0), ("BT709_FULL", 1), ("BT601", 2), ("BT601_FULL", 3)):
-                globals()[f"I{_sub_name[2]}{_bits}{_infix}_{_name}"] = 2048 + _matrix + 4 * _sub + 16 * _filter + 64 * _depth
-PLANAR16_FAMILY = tuple(f - 512 + 2048 + 64 * d for d in (1, 2, 3) for f in PLANAR_FAMILY)
+        for _matrix, _name in enumerate(("BT709", "BT709_FULL", "BT601", "BT601_FULL")):
+            if not (_sub == 2 and _filter):
+                globals()[f"{_stem}{_infix}_{_name}"] = ycbcr_fmt(_base, _matrix, _sub, _filter, _depth)
+NV12_FORMATS, NV12_CENTER_FORMATS, NV12_LEFT_FORMATS = (tuple(ycbcr_fmt(16, m, 0, f) for m in range(4)) for f in range(3))
+NV12_FAMILY = NV12_FORMATS + NV12_CENTER_FORMATS + NV12_LEFT_FORMATS
+P010_FORMATS, P012_FORMATS, P016_FORMATS = (tuple(ycbcr_fmt(16, m, 0, 0, d) for m in range(4)) for d in (1, 2, 3))  # nearest chroma
+P016_FAMILY = tuple(ycbcr_fmt(16, m, 0, f, d) for d in (1, 2, 3) for f in range(3) for m in range(4))
+PLANAR_FAMILY = tuple(ycbcr_fmt(512, m, s, f) for f in range(3) for s in range(3) for m in range(4) if not (s == 2 and f))
+PLANAR16_FAMILY = tuple(ycbcr_fmt(2048, *ycbcr_fields(f)[1:4], d) for d in (1, 2, 3) for f in PLANAR_FAMILY)
 
 
 def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
@@ -84,14 +78,14 @@ def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
     sub, filt = PLANAR_SUBSAMPLINGS[str(subsampling)], CHROMA_FILTERS[chroma or "nearest"]
     if sub == 2 and filt:
         raise ValueError("4:4:4 has a chroma sample for every pixel: no chroma filter")
-    return 512 + (int(matrix) - NV12_BT709) + 4 * sub + 16 * filt
+    return ycbcr_fmt(512, ycbcr_fields(matrix)[1], sub, filt)
 
 
 def planar16_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None, depth: int = 10) -> int:
     """The sample format of a planar YCbCr picture of 16-bit words: planar_fmt's arguments and ``depth`` 10, 12 or 16."""
     if depth not in P016_DEPTHS:
         raise ValueError("depth is 10, 12 or 16")
-    return planar_fmt(matrix, subsampling, chroma) - 512 + 2048 + 64 * P016_DEPTHS[depth]
+    return ycbcr_fmt(2048, *ycbcr_fields(planar_fmt(matrix, subsampling, chroma))[1:4], P016_DEPTHS[depth])
 
 
 class Nv12:
@@ -112,9 +106,9 @@ class Nv12:
         if chroma is not None:
             if chroma not in CHROMA_FILTERS:
                 raise ValueError("chroma is 'nearest', 'centre' or 'left'")
-            if int(matrix) not in NV12_FORMATS and (int(matrix) - 16) >> 4 != CHROMA_FILTERS[chroma]:
+            if int(matrix) not in NV12_FORMATS and ycbcr_fields(matrix)[3] != CHROMA_FILTERS[chroma]:
                 raise ValueError("matrix names another chroma filter than chroma does")
-            matrix = 16 + (int(matrix) & 3) + 16 * CHROMA_FILTERS[chroma]
+            matrix = ycbcr_fmt(16, ycbcr_fields(matrix)[1], 0, CHROMA_FILTERS[chroma])
         if y.element_size() != 1 or uv.element_size() != 1 or y.dim() != 2 or uv.dim() != 3:
             raise ValueError("NV12 planes are 8-bit: y (H, W), uv (ceil(H / 2), ceil(W / 2), 2)")
         h, w = y.shape
@@ -161,7 +155,7 @@ class P016(Nv12):
     def __init__(self, y, uv, matrix: int = NV12_BT709, chroma=None, depth: int = 10):
         matrix = int(matrix)
         if matrix in P016_FAMILY:
-            if chroma is not None and ((matrix - 16) >> 4) & 3 != CHROMA_FILTERS.get(chroma, -1):
+            if chroma is not None and ycbcr_fields(matrix)[3] != CHROMA_FILTERS.get(chroma, -1):
                 raise ValueError("matrix names another chroma filter than chroma does")
             fmt = matrix
         else:
@@ -171,7 +165,7 @@ class P016(Nv12):
                 raise ValueError("depth is 10, 12 or 16")
             if chroma is not None and chroma not in CHROMA_FILTERS:
                 raise ValueError("chroma is 'nearest', 'centre' or 'left'")
-            fmt = matrix + 16 * CHROMA_FILTERS[chroma or "nearest"] + 64 * P016_DEPTHS[depth]
+            fmt = ycbcr_fmt(16, ycbcr_fields(matrix)[1], 0, CHROMA_FILTERS[chroma or "nearest"], P016_DEPTHS[depth])
         names = [str(t.dtype).rpartition(".")[2] for t in (y, uv)]
         if y.element_size() != 2 or uv.element_size() != 2 or y.dim() != 2 or uv.dim() != 3 or \
                 any(n.startswith(("float", "bfloat", "complex")) for n in names):

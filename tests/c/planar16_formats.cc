@@ -4,13 +4,9 @@
  * tests/test_planar16_formats.py with -fsanitize=address,undefined and held to the numpy model (tests/planar16_model.py).  Each
  * mode writes its results to OUT as raw native-endian arrays:
  *
- *   planar16_formats formats OUT    int32[FMT_HI - FMT_LO][24]: the twelve predicates tests/c/planar_formats.cc prints, then
- *                                   is_planar16, sub, filter, matrix, depth, bits, sx, sy, is_planar16_interp (0 where the number
- *                                   is no such format), then zeros; then int32[4096][10] for 0 ... 4095: ok, the format encoded
- *                                   back from its decoded fields (-1 where not ok), cls, storage, matrix, filter, sub, sx, sy, the
- *                                   storage form's variant; then int64[3 subsamplings][4 sign pairs][3] origin offsets IN BYTES;
- *                                   then int32[2 widths][3 subsamplings][3 pitches][2 signs] of the pitch helper; then int32[8] of
- *                                   the alignment check, the three planes 0 or 1 byte off (bit c of the index: plane c)
+ *   planar16_formats geometry OUT   int64[3 subsamplings][4 sign pairs][3] origin offsets IN BYTES; then int32[2 widths][3 subsamplings]
+ *                                   [3 pitches][2 signs] of the pitch rule; then int32[8] of the alignment check, the three planes 0
+ *                                   or 1 byte off (bit c of the index: plane c).  What the numbers mean: sample_formats.cc's dump
  *   planar16_formats planes OUT IN  IN: u32 cases, then per case u32 subsampling, filter, depth, matrix, w, h and the Y, U and V
  *                                   planes as 16-bit words; OUT: per case h x w x 3 words
  * Every plane is a malloc of exactly its samples: a tap that leaves the plane meets the redzone.
@@ -20,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/hydrium_amd.h"
 #include "hyd_sample_fmt.h"
 #include "hip/hydk_store.h"
 #include "hip/hydk_yuvp16.h"
@@ -55,43 +52,10 @@ static uint32_t rd32(const uint8_t **p) {
     return v;
 }
 
-enum { FMT_LO = -8, FMT_HI = 4101 };
+static int pitch_ok(int fmt, ptrdiff_t pitch, size_t width) { return hyd_fmt_refusal(fmt, nullptr, pitch, width) == nullptr; }
+static int layout_ok(int fmt, const void *const src[3], ptrdiff_t pixel_stride) { return hyd_fmt_refusal(fmt, src, pixel_stride, 0) == nullptr; }
 
-static void formats(std::FILE *out) {
-    for (int fmt = FMT_LO; fmt < FMT_HI; fmt++) {
-        const int planar = hyd_fmt_is_planar_yuv(fmt), p16 = hyd_fmt_is_planar16(fmt);
-        const int32_t row[24] = {planar,
-                                 planar ? hyd_fmt_planar_sub(fmt) : 0,
-                                 planar ? hyd_fmt_planar_filter(fmt) : 0,
-                                 planar ? hyd_fmt_planar_matrix(fmt) : 0,
-                                 hyd_fmt_is_planar_interp(fmt),
-                                 (int32_t)hyd_fmt_bytes(fmt),
-                                 hyd_fmt_is_device(fmt),
-                                 hyd_fmt_is_host(fmt),
-                                 hyd_fmt_is_nv12(fmt) | hyd_fmt_is_nv12_family(fmt) | hyd_fmt_is_nv12_interp(fmt),
-                                 hyd_fmt_is_p016_family(fmt) | hyd_fmt_is_p016_interp(fmt),
-                                 hyd_fmt_is_yuv420(fmt) | hyd_fmt_is_yuv420_interp(fmt),
-                                 hyd_fmt_is_float(fmt),
-                                 p16,
-                                 p16 ? hyd_fmt_planar16_sub(fmt) : 0,
-                                 p16 ? hyd_fmt_planar16_filter(fmt) : 0,
-                                 p16 ? hyd_fmt_planar16_matrix(fmt) : 0,
-                                 p16 ? hyd_fmt_planar16_depth(fmt) : 0,
-                                 p16 ? hyd_fmt_planar16_bits(fmt) : 0,
-                                 p16 ? hyd_fmt_planar16_sx(fmt) : 0,
-                                 p16 ? hyd_fmt_planar16_sy(fmt) : 0,
-                                 hyd_fmt_is_planar16_interp(fmt),
-                                 0,
-                                 0,
-                                 0};
-        put(out, row, sizeof(row));
-    }
-    for (int fmt = 0; fmt < 4096; fmt++) {
-        const HydkSampleForm d = hydk_decode_fmt(fmt);
-        const int32_t row[10] = {d.ok, d.ok ? hydk_encode_fmt(d) : -1, d.cls, (int32_t)d.storage, (int32_t)d.matrix, (int32_t)d.filter,
-                                 (int32_t)d.sub, d.sx, d.sy, hydk_store_form((int)d.storage).variant};
-        put(out, row, sizeof(row));
-    }
+static void geometry(std::FILE *out) {
     /* origins of the sub-rectangle at (256, 512) of a picture with Y pitch +-1024 and chroma pitch +-520 words: offsets in bytes
      * from the three plane pointers, which sit in allocations of their own */
     const size_t x0 = 256, y0 = 512;
@@ -99,7 +63,7 @@ static void formats(std::FILE *out) {
     for (int c = 0; c < 3; c++)
         if (!(planes[c] = (char *)std::malloc(64)))
             die("out of memory");
-    const int some[3] = {HYD_FMT_I010C_BT601_FULL, HYD_FMT_I212L_BT709, HYD_FMT_I416_BT601};
+    const int some[3] = {HYDAMD_I010C_BT601_FULL, HYDAMD_I212L_BT709, HYDAMD_I416_BT601};
     for (int k = 0; k < 3; k++)
         for (int ysign = 1; ysign >= -1; ysign -= 2)
             for (int csign = 1; csign >= -1; csign -= 2) {
@@ -111,25 +75,26 @@ static void formats(std::FILE *out) {
                     put(out, &off, sizeof(off));
                 }
             }
-    /* the pitch helper around cw, for an odd and an even width */
+    /* the pitch rule around cw, for an odd and an even width */
     const size_t widths[2] = {199, 200};
     for (int i = 0; i < 2; i++)
         for (int k = 0; k < 3; k++) {
-            const ptrdiff_t cw = (ptrdiff_t)(hyd_fmt_planar16_sub(some[k]) == HYD_FMT_PLANAR_444 ? widths[i] : (widths[i] + 1) / 2);
+            const ptrdiff_t cw = (ptrdiff_t)(hyd_fmt_describe(some[k]).sub == HYD_FMT_SUB_444 ? widths[i] : (widths[i] + 1) / 2);
             for (ptrdiff_t pitch = cw - 1; pitch <= cw + 1; pitch++)
                 for (int sign = 1; sign >= -1; sign -= 2) {
-                    const int32_t ok = hyd_fmt_pitch_ok(some[k], sign * pitch, widths[i]);
+                    const int32_t ok = pitch_ok(some[k], sign * pitch, widths[i]);
                     put(out, &ok, sizeof(ok));
                 }
-            if (hyd_fmt_pitch_ok(some[k], 1, widths[i]) || hyd_fmt_pitch_ok(some[k], 0, widths[i]))
-                die("hyd_fmt_pitch_ok refuses the pixel strides 0 and 1");
+            if (pitch_ok(some[k], 1, widths[i]) || pitch_ok(some[k], 0, widths[i]))
+                die("the pitch rule refuses the pixel strides 0 and 1");
         }
     /* the alignment check: every plane on a 2-byte boundary, whatever the pixel stride says */
     for (int k = 0; k < 8; k++) {
         const void *const src[3] = {planes[0] + (k & 1), planes[1] + ((k >> 1) & 1), planes[2] + ((k >> 2) & 1)};
-        const int32_t ok = hyd_fmt_layout_ok(some[k % 3], src, 520) && hyd_fmt_layout_ok(some[k % 3], src, 1);
+        const int32_t ok = layout_ok(some[k % 3], src, 520) && layout_ok(some[k % 3], src, 1);
         put(out, &ok, sizeof(ok));
-        if (std::strcmp(hyd_fmt_layout_msg(some[k % 3]), HYD_FMT_PLANAR16_ALIGN_MSG) || !hyd_fmt_layout_ok(HYD_FMT_I420_BT709, src, 520))
+        const char *said = hyd_fmt_refusal(some[k % 3], src, 520, 0);
+        if ((said && std::strcmp(said, HYD_FMT_PLANAR16_ALIGN_MSG)) || !layout_ok(HYDAMD_I420_BT709, src, 520))
             die("the alignment message is the family's own, and the 8-bit planes have no alignment to hold");
     }
     for (int c = 0; c < 3; c++)
@@ -196,8 +161,8 @@ int main(int argc, char **argv) {
     std::FILE *out = std::fopen(argv[2], "wb");
     if (!out)
         die("cannot open the output");
-    if (!std::strcmp(argv[1], "formats") && argc == 3)
-        formats(out);
+    if (!std::strcmp(argv[1], "geometry") && argc == 3)
+        geometry(out);
     else if (!std::strcmp(argv[1], "planes") && argc == 4)
         planes(out, argv[3]);
     else

@@ -4,8 +4,8 @@
  * -fsanitize=address,undefined and held to the numpy model (tests/planar_model.py).  Each mode writes its results to OUT as
  * raw native-endian arrays:
  *
- *   planar_formats formats OUT      int32[FMT_HI - FMT_LO][12] predicates; then int64[3 subsamplings][2 chroma pitches][3] origin
- *                                   offsets; then int32[2 widths][3 subsamplings][3 pitches][2 signs] of the pitch helper
+ *   planar_formats geometry OUT     int64[3 subsamplings][2 chroma pitches][3] origin offsets; then int32[2 widths][3 subsamplings]
+ *                                   [3 pitches][2 signs] of the pitch rule (what the numbers mean: sample_formats.cc's dump)
  *   planar_formats planes OUT IN    IN: u32 cases, then per case u32 subsampling, filter, w, h and ONE chroma plane of ch x cw
  *                                   bytes; OUT: per case h x w bytes
  * Every chroma plane is a malloc of exactly its samples: a tap that leaves the plane meets the redzone.
@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/hydrium_amd.h"
 #include "hyd_sample_fmt.h"
 #include "hip/hydk_chroma.h"
 
@@ -49,25 +50,9 @@ static uint32_t rd32(const uint8_t **p) {
     return v;
 }
 
-enum { FMT_LO = -8, FMT_HI = 1101 };
+static int pitch_ok(int fmt, ptrdiff_t pitch, size_t width) { return hyd_fmt_refusal(fmt, nullptr, pitch, width) == nullptr; }
 
-static void formats(std::FILE *out) {
-    for (int fmt = FMT_LO; fmt < FMT_HI; fmt++) {
-        const int planar = hyd_fmt_is_planar_yuv(fmt);
-        const int32_t row[12] = {planar,
-                                 planar ? hyd_fmt_planar_sub(fmt) : 0,
-                                 planar ? hyd_fmt_planar_filter(fmt) : 0,
-                                 planar ? hyd_fmt_planar_matrix(fmt) : 0,
-                                 hyd_fmt_is_planar_interp(fmt),
-                                 (int32_t)hyd_fmt_bytes(fmt),
-                                 hyd_fmt_is_device(fmt),
-                                 hyd_fmt_is_host(fmt),
-                                 hyd_fmt_is_nv12(fmt) | hyd_fmt_is_nv12_family(fmt) | hyd_fmt_is_nv12_interp(fmt),
-                                 hyd_fmt_is_p016_family(fmt) | hyd_fmt_is_p016_interp(fmt),
-                                 hyd_fmt_is_yuv420(fmt) | hyd_fmt_is_yuv420_interp(fmt),
-                                 hyd_fmt_is_float(fmt)};
-        put(out, row, sizeof(row));
-    }
+static void geometry(std::FILE *out) {
     /* origins of the sub-rectangle at (256, 512) of a picture with Y pitch 1024 and chroma pitch 520, then -520: offsets from
      * the three plane pointers, which sit in allocations of their own */
     const size_t x0 = 256, y0 = 512;
@@ -75,14 +60,14 @@ static void formats(std::FILE *out) {
     for (int c = 0; c < 3; c++)
         if (!(planes[c] = (char *)std::malloc(64)))
             die("out of memory");
-    const int some[3] = {HYD_FMT_I420C_BT601_FULL, HYD_FMT_I422L_BT709, HYD_FMT_I444_BT601};
+    const int some[3] = {HYDAMD_I420C_BT601_FULL, HYDAMD_I422L_BT709, HYDAMD_I444_BT601};
     for (int k = 0; k < 3; k++)
         for (int sign = 1; sign >= -1; sign -= 2) {
             const void *const src[3] = {planes[0], planes[1], planes[2]};
             const void *origin[3];
             hyd_fmt_origin(some[k], src, 1024, sign * 520, x0, y0, origin);
-            if (!hyd_fmt_layout_ok(some[k], src, sign * 520) || !hyd_fmt_layout_ok(some[k], src, 1))
-                die("hyd_fmt_layout_ok has nothing to hold a planar picture to");
+            if (hyd_fmt_refusal(some[k], src, sign * 520, 0) || hyd_fmt_refusal(some[k], src, 1, 0))
+                die("hyd_fmt_refusal has no layout to hold a planar picture to");
             for (int c = 0; c < 3; c++) {
                 const int64_t off = (int64_t)((intptr_t)origin[c] - (intptr_t)src[c]);
                 put(out, &off, sizeof(off));
@@ -90,20 +75,19 @@ static void formats(std::FILE *out) {
         }
     for (int c = 0; c < 3; c++)
         std::free(planes[c]);
-    /* the pitch helper around cw, for an odd and an even width */
+    /* the pitch rule around cw, for an odd and an even width */
     const size_t widths[2] = {199, 200};
     for (int i = 0; i < 2; i++)
         for (int k = 0; k < 3; k++) {
-            const ptrdiff_t cw = (ptrdiff_t)(hyd_fmt_planar_sub(some[k]) == HYD_FMT_PLANAR_444 ? widths[i] : (widths[i] + 1) / 2);
+            const ptrdiff_t cw = (ptrdiff_t)(hyd_fmt_describe(some[k]).sub == HYD_FMT_SUB_444 ? widths[i] : (widths[i] + 1) / 2);
             for (ptrdiff_t pitch = cw - 1; pitch <= cw + 1; pitch++)
                 for (int sign = 1; sign >= -1; sign -= 2) {
-                    const int32_t ok = hyd_fmt_pitch_ok(some[k], sign * pitch, widths[i]);
+                    const int32_t ok = pitch_ok(some[k], sign * pitch, widths[i]);
                     put(out, &ok, sizeof(ok));
                 }
-            if (!hyd_fmt_pitch_ok(HYD_FMT_UINT8, 1, widths[i]) || !hyd_fmt_pitch_ok(HYD_FMT_NV12C_BT709, 1, widths[i]) ||
-                !hyd_fmt_pitch_ok(HYD_FMT_P010_BT709, 1, widths[i]) || hyd_fmt_pitch_ok(some[k], 1, widths[i]) ||
-                hyd_fmt_pitch_ok(some[k], 0, widths[i]))
-                die("hyd_fmt_pitch_ok holds the planar family alone, and refuses it the pixel strides 0 and 1");
+            if (!pitch_ok(HYD_FMT_UINT8, 1, widths[i]) || !pitch_ok(HYDAMD_NV12C_BT709, 1, widths[i]) || !pitch_ok(HYDAMD_P010_BT709, 1, widths[i]) ||
+                pitch_ok(some[k], 1, widths[i]) || pitch_ok(some[k], 0, widths[i]))
+                die("the pitch rule holds the planar families alone, and refuses them the pixel strides 0 and 1");
         }
 }
 
@@ -151,8 +135,8 @@ int main(int argc, char **argv) {
     std::FILE *out = std::fopen(argv[2], "wb");
     if (!out)
         die("cannot open the output");
-    if (!std::strcmp(argv[1], "formats") && argc == 3)
-        formats(out);
+    if (!std::strcmp(argv[1], "geometry") && argc == 3)
+        geometry(out);
     else if (!std::strcmp(argv[1], "planes") && argc == 4)
         planes(out, argv[3]);
     else

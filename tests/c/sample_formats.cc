@@ -9,8 +9,11 @@
  *   sample_formats yuv16 OUT IN        IN: uint16[n][3]; OUT: uint16[n][3] for each of the twelve table rows, depth slowest
  *   sample_formats chroma OUT IN       IN: u32 cases, then per case u32 bits (8, 16), filter, w, h and the chroma plane
  *                                      ceil(h / 2) x ceil(w / 2) x 2 samples; OUT: per case h x w x 2 samples
- *   sample_formats formats OUT         int32[FMT_HI - FMT_LO][12] predicates of csrc/hyd_sample_fmt.h, then int64[cases][3]
- *                                      origin offsets; before it writes, the round trip of csrc/hip/hydk_store.h
+ *   sample_formats formats OUT         int32[FMT_HI - FMT_LO][18] for every number -8 ... 4100: the twelve fields of hyd_fmt_describe
+ *                                      in the struct's order, then of hydk_decode_fmt ok, the format encoded back (-1 where not
+ *                                      ok), cls, storage, matrix and the storage form's variant; then int64[cases][3] origin
+ *                                      offsets; before it writes, the round trip of csrc/hip/hydk_store.h and the cases of
+ *                                      hyd_fmt_refusal
  * Every chroma plane is a malloc of exactly its samples: a tap that leaves the plane meets the redzone.
  */
 #include <cstdint>
@@ -18,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/hydrium_amd.h"
 #include "hyd_sample_fmt.h"
 #include "hip/hydk_half.h"
 #include "hip/hydk_yuv.h"
@@ -144,51 +148,82 @@ static void chroma(std::FILE *out, const char *in) {
     std::free(raw);
 }
 
-enum { FMT_LO = -8, FMT_HI = 264 };
+enum { FMT_LO = -8, FMT_HI = 4101 };
 
 /* csrc/hip/hydk_store.h: every format a device entry point takes encodes back to itself after the decode, and every other
- * number of 0 ... 1023 is refused: these two hold whatever the decode is built from.  The field checks below compare it with
- * the hyd_fmt_* predicates it calls itself — a guard against a slip in the table, not an independent definition (what a
- * job's fields mean is held to the reference's files by the GPU suites of the four families) */
+ * number of -8 ... 4100 is refused.  A job's fields are the descriptor's, for every family (the descriptor itself is held to
+ * tests/format_model.py, number by number, by the Python side) */
 static void round_trip() {
-    for (int fmt = 0; fmt < 1024; fmt++) {
+    for (int fmt = FMT_LO; fmt < FMT_HI; fmt++) {
+        const HydFmt f = hyd_fmt_describe(fmt);
         const HydkSampleForm d = hydk_decode_fmt(fmt);
-        if (!hyd_fmt_is_device(fmt)) {
-            if (d.ok || d.cls || d.storage || d.matrix || d.filter || d.sub)
+        if (!f.device) {
+            if (d.ok || d.cls || d.storage || d.matrix || d.filter || d.sub || d.sx || d.sy)
                 die("hydk_decode_fmt takes a number that names no device format");
             continue;
         }
-        if (!d.ok || hydk_encode_fmt(d) != fmt)
+        if (d.ok != 1 || hydk_encode_fmt(d) != fmt)
             die("a device format does not come back from hydk_decode_fmt and hydk_encode_fmt");
         const HydkStoreForm form = hydk_store_form((int)d.storage);
-        const int yuv = hyd_fmt_is_yuv420(fmt) || hyd_fmt_is_planar_yuv(fmt);
-        if (d.cls != (hyd_fmt_is_float(fmt) ? HYDK_FMT_F32 : hyd_fmt_bytes(fmt) == 1 ? HYDK_FMT_U8 : HYDK_FMT_U16) ||
-            (d.storage != HYDK_STORE_F32 && form.cls != d.cls))
+        const int yuv = f.layout != HYD_LAYOUT_RGB;
+        if (d.cls != (f.is_float ? HYDK_FMT_F32 : f.bytes == 1 ? HYDK_FMT_U8 : HYDK_FMT_U16) || (d.storage != HYDK_STORE_F32 && form.cls != d.cls))
             die("hydk_decode_fmt: class");
-        if (form.ycbcr != yuv || form.interp != (hyd_fmt_is_yuv420_interp(fmt) || hyd_fmt_is_planar_interp(fmt)) ||
-            (yuv && form.bits != 8 * (int)hyd_fmt_bytes(fmt)) || (yuv && form.chroma_planes != (hyd_fmt_is_planar_yuv(fmt) ? 2 : 1)) ||
+        if (form.ycbcr != yuv || form.interp != (f.filter != 0) || (yuv && form.bits != 8 * f.bytes) || (yuv && form.chroma_planes != f.layout) ||
             (!yuv && d.storage != (uint32_t)(fmt == HYD_FMT_FLOAT16 ? HYDK_STORE_F16 : fmt == HYD_FMT_BFLOAT16 ? HYDK_STORE_BF16 : HYDK_STORE_F32)))
             die("hydk_decode_fmt: storage form");
-        if (hyd_fmt_is_planar_yuv(fmt) &&
-            (d.matrix != (uint32_t)hyd_fmt_planar_matrix(fmt) || d.filter != (uint32_t)hyd_fmt_planar_filter(fmt) ||
-             d.sub != (uint32_t)hyd_fmt_planar_sub(fmt) || d.sx != hyd_fmt_planar_sx(fmt) || d.sy != hyd_fmt_planar_sy(fmt)))
-            die("hydk_decode_fmt: planar fields");
-        if (hyd_fmt_is_yuv420(fmt) && (d.matrix != (uint32_t)(hyd_fmt_p016_matrix(fmt) + 4 * hyd_fmt_p016_depth(fmt)) ||
-                                       d.filter != (uint32_t)hyd_fmt_p016_filter(fmt) || d.sub || d.sx != 1 || d.sy != 1))
+        if (d.matrix != (uint32_t)(f.matrix + 4 * f.depth) || d.filter != (uint32_t)f.filter || d.sub != (uint32_t)f.sub || d.sx != f.sx || d.sy != f.sy)
+            die("hydk_decode_fmt: a job's YCbCr fields are the descriptor's");
+        if (f.layout == HYD_LAYOUT_PAIRS && (d.sub || d.sx != 1 || d.sy != 1))
             die("hydk_decode_fmt: 4:2:0 fields");
         if (!yuv && (d.matrix || d.filter || d.sub || d.sx || d.sy))
             die("hydk_decode_fmt: an RGB format has no YCbCr fields");
     }
 }
 
+/* hyd_fmt_refusal: one case per family for each rule it can break alone, and the one family that can break two */
+static void want(const char *got, const char *message, const char *what) {
+    if (got != message && (!got || !message || std::strcmp(got, message)))
+        die(what);
+}
+
+static void refusals() {
+    alignas(8) static char buf[64];
+    const void *const rgb[3] = {buf, buf + 1, buf + 2}, *const nv12[3] = {buf, buf + 32, buf + 33}, *const p016[3] = {buf, buf + 32, buf + 34};
+    const void *const planes[3] = {buf, buf + 16, buf + 32}, *const odd[3] = {buf, buf + 16, buf + 33};
+    want(hyd_fmt_refusal(5, rgb, 3, 200), "Invalid Sample Format", "a number that names nothing");
+    want(hyd_fmt_refusal(2111, nullptr, 0, 0), "Invalid Sample Format", "a number that names nothing, asked of the format alone");
+    for (int fmt = HYD_FMT_UINT8; fmt <= HYDAMD_BFLOAT16; fmt++)
+        want(hyd_fmt_refusal(fmt, odd, 0, 200), nullptr, "an RGB-like format takes any layout");
+    want(hyd_fmt_refusal(HYDAMD_NV12C_BT601, nv12, 1, 200), nullptr, "NV12 as it should be");
+    want(hyd_fmt_refusal(HYDAMD_NV12C_BT601, nv12, 2, 200), HYD_FMT_NV12_LAYOUT_MSG, "NV12: pixel stride");
+    want(hyd_fmt_refusal(HYDAMD_NV12_BT709, p016, 1, 200), HYD_FMT_NV12_LAYOUT_MSG, "NV12: V two bytes behind U");
+    want(hyd_fmt_refusal(HYDAMD_NV12_BT709, p016, 1, 0), HYD_FMT_NV12_LAYOUT_MSG, "NV12: the layout alone");
+    want(hyd_fmt_refusal(HYDAMD_NV12_BT709, nullptr, 2, 200), nullptr, "NV12: no layout asked, and no pitch to hold");
+    want(hyd_fmt_refusal(HYDAMD_P010L_BT709, p016, 1, 200), nullptr, "P010 as it should be");
+    want(hyd_fmt_refusal(HYDAMD_P010L_BT709, p016, 2, 200), HYD_FMT_P016_LAYOUT_MSG, "P010: pixel stride");
+    want(hyd_fmt_refusal(HYDAMD_P016_BT601_FULL, nv12, 1, 200), HYD_FMT_P016_LAYOUT_MSG, "P016: V one byte behind U");
+    const void *const p016_odd[3] = {buf + 1, buf + 32, buf + 34}, *const p016_odd_uv[3] = {buf, buf + 33, buf + 35};
+    want(hyd_fmt_refusal(HYDAMD_P012_BT709, p016_odd, 1, 200), HYD_FMT_P016_LAYOUT_MSG, "P012: an odd Y address");
+    want(hyd_fmt_refusal(HYDAMD_P012_BT709, p016_odd_uv, 1, 200), HYD_FMT_P016_LAYOUT_MSG, "P012: an odd chroma address");
+    want(hyd_fmt_refusal(HYDAMD_I422C_BT709, odd, 100, 200), nullptr, "planar 8-bit: any three addresses");
+    want(hyd_fmt_refusal(HYDAMD_I422C_BT709, odd, 99, 200), HYD_FMT_PLANAR_PITCH_MSG, "planar 8-bit: pitch");
+    want(hyd_fmt_refusal(HYDAMD_I444_BT709, planes, -199, 200), HYD_FMT_PLANAR_PITCH_MSG, "planar 4:4:4: pitch");
+    want(hyd_fmt_refusal(HYDAMD_I444_BT709, planes, -199, 0), nullptr, "planar: no width, no pitch too short");
+    want(hyd_fmt_refusal(HYDAMD_I210_BT601, planes, 100, 200), nullptr, "planar16 as it should be");
+    want(hyd_fmt_refusal(HYDAMD_I210_BT601, odd, 100, 200), HYD_FMT_PLANAR16_ALIGN_MSG, "planar16: alignment");
+    want(hyd_fmt_refusal(HYDAMD_I210_BT601, planes, 99, 200), HYD_FMT_PLANAR_PITCH_MSG, "planar16: pitch");
+    want(hyd_fmt_refusal(HYDAMD_I210_BT601, odd, 99, 200), HYD_FMT_PLANAR16_ALIGN_MSG, "planar16, an odd address and a short pitch: the alignment message wins");
+    want(hyd_fmt_refusal(HYDAMD_I210_BT601, nullptr, 99, 200), HYD_FMT_PLANAR_PITCH_MSG, "planar16: the pitch alone");
+}
+
 static void formats(std::FILE *out) {
     round_trip();
+    refusals();
     for (int fmt = FMT_LO; fmt < FMT_HI; fmt++) {
-        const int32_t row[12] = {hyd_fmt_is_nv12(fmt),        hyd_fmt_is_nv12_family(fmt),   hyd_fmt_is_nv12_interp(fmt), hyd_fmt_is_p016_family(fmt),
-                                 hyd_fmt_is_p016_interp(fmt), hyd_fmt_is_yuv420(fmt),        hyd_fmt_is_yuv420_interp(fmt), hyd_fmt_is_device(fmt),
-                                 hyd_fmt_is_host(fmt),        hyd_fmt_is_float(fmt),         (int32_t)hyd_fmt_bytes(fmt),
-                                 hyd_fmt_is_p016_family(fmt) ? hyd_fmt_p016_bits(fmt) * 256 + hyd_fmt_p016_filter(fmt) * 16 + hyd_fmt_p016_matrix(fmt)
-                                 : hyd_fmt_is_nv12_family(fmt) ? hyd_fmt_nv12_filter(fmt) * 16 + hyd_fmt_nv12_family_matrix(fmt) : -1};
+        const HydFmt f = hyd_fmt_describe(fmt);
+        const HydkSampleForm d = hydk_decode_fmt(fmt);
+        const int32_t row[18] = {f.device, f.host,   f.is_float, f.bytes, f.layout, f.matrix, f.filter, f.sub, f.sx, f.sy, f.depth, f.bits,
+                                 d.ok, d.ok ? hydk_encode_fmt(d) : -1, d.cls, (int32_t)d.storage, (int32_t)d.matrix, hydk_store_form((int)d.storage).variant};
         put(out, row, sizeof(row));
     }
     /* origins of the sub-rectangle at (256, 512) of a picture of pitch 1024: offsets from the three plane pointers */
@@ -197,15 +232,16 @@ static void formats(std::FILE *out) {
     char *picture = (char *)std::malloc((size_t)pitch * 1024 * 3 * 4);
     if (!picture)
         die("out of memory");
-    const int some[] = {HYD_FMT_UINT8, HYD_FMT_UINT16, HYD_FMT_FLOAT32, HYD_FMT_FLOAT16, HYD_FMT_BFLOAT16, HYD_FMT_NV12_BT601, HYD_FMT_NV12L_BT709,
-                        HYD_FMT_P010_BT709, HYD_FMT_P016L_BT601_FULL};
+    const int some[] = {HYD_FMT_UINT8, HYD_FMT_UINT16, HYD_FMT_FLOAT32, HYDAMD_FLOAT16, HYDAMD_BFLOAT16, HYDAMD_NV12_BT601, HYDAMD_NV12L_BT709,
+                        HYDAMD_P010_BT709, HYDAMD_P016L_BT601_FULL};
     for (size_t k = 0; k < sizeof(some) / sizeof(some[0]); k++) {
-        const int yuv = hyd_fmt_is_yuv420(some[k]);
-        const void *const src[3] = {picture, picture + 64, picture + 64 + (ptrdiff_t)hyd_fmt_bytes(some[k])};
+        const HydFmt f = hyd_fmt_describe(some[k]);
+        const int yuv = f.layout == HYD_LAYOUT_PAIRS;
+        const void *const src[3] = {picture, picture + 64, picture + 64 + f.bytes};
         const void *origin[3];
         hyd_fmt_origin(some[k], src, pitch, yuv ? 1 : pixel, x0, y0, origin);
-        if (!hyd_fmt_layout_ok(some[k], src, yuv ? 1 : pixel) || (yuv && hyd_fmt_layout_ok(some[k], src, 2)))
-            die("hyd_fmt_layout_ok");
+        if (hyd_fmt_refusal(some[k], src, yuv ? 1 : pixel, 0) || (yuv && !hyd_fmt_refusal(some[k], src, 2, 0)))
+            die("hyd_fmt_refusal: the layout");
         for (int c = 0; c < 3; c++) {
             const int64_t off = (const char *)origin[c] - (const char *)src[c];
             put(out, &off, sizeof(off));

@@ -429,29 +429,11 @@ def test_every_list_of_the_section_writers_and_the_shard_checks(program):
 
 # ---- the shared sample-format headers as plain C++ under the same sanitizers ------------------------------------------------------
 @pytest.fixture(scope="module")
-def formats_program(tmp_path_factory):
-    """tests/c/sample_formats.cc: hyd_sample_fmt.h, hydk_half.h, hydk_yuv.h, hydk_yuv16.h and hydk_chroma.h with g++, no HIP header"""
-    d = str(tmp_path_factory.mktemp("sample_formats"))
-    exe = os.path.join(d, "sample_formats")
-    cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Wno-unused-parameter", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", f"-I{hbuild.CSRC}", os.path.join(ROOT, "tests", "c", "sample_formats.cc"), "-o", exe]
-    made = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert made.returncode == 0 and not made.stderr, made.stderr  # no warning either
+def formats_program():
+    """tests/c/sample_formats.cc: hyd_sample_fmt.h, hydk_half.h, hydk_yuv.h, hydk_yuv16.h, hydk_chroma.h and hydk_store.h with g++, no HIP header"""
+    import format_dump
 
-    def run(mode, *args, data=None):
-        """the mode's output file, whole; exit status 0 and an empty stderr"""
-        out = os.path.join(d, mode + ".out")
-        if data is not None:
-            with open(os.path.join(d, mode + ".in"), "wb") as f:
-                f.write(data)
-            args = (os.path.join(d, mode + ".in"),)
-        ran = subprocess.run([exe, mode, out, *map(str, args)], capture_output=True, text=True, timeout=300)
-        assert (ran.returncode, ran.stderr) == (0, ""), (mode, ran.returncode, ran.stderr[-4000:])
-        got = np.fromfile(out, np.uint8)
-        os.remove(out)
-        return got
-
-    return run
+    return format_dump.sanitized_program("sample_formats")
 
 
 def test_every_half_and_bfloat16_bit_pattern(formats_program):
@@ -519,16 +501,27 @@ def test_the_chroma_taps_at_the_edges_of_the_smallest_pictures(formats_program):
 
 
 def test_the_predicates_and_origins_of_the_sample_formats(formats_program):
+    """the whole descriptor of every number -8 ... 4100 against tests/format_model.py, which is written from the prose; what the
+    decode of csrc/hip/hydk_store.h makes of it; and every (number, predicate) pair the NV12 and P016 families pinned before"""
     import chroma_model as cm
+    import format_dump
+    import format_model as fm
     import p016_model as pm
     import yuv_model as ym
 
-    lo, hi = -8, 264
-    got = formats_program("formats")
-    rows = got[:(hi - lo) * 48].view(np.int32).reshape(hi - lo, 12)
-    origins = got[(hi - lo) * 48:].view(np.int64).reshape(-1, 3)
+    rows, origins = format_dump.formats()
+    assert sorted(rows) == list(range(-8, 4101)) and len(rows) == 4109
+    for fmt, (d, job) in rows.items():
+        want = fm.describe(fmt)
+        assert d == want, (fmt, d, want)
+        cls, storage, variant = fm.storage_of(fmt)
+        assert job == (want.device, fmt if want.device else -1, cls, storage, want.matrix + 4 * want.depth, variant), (fmt, job)
+    assert [f for f, (d, _) in rows.items() if d.device] == sorted(fm.ALL) and sum(d.device for d, _ in rows.values()) == 165
+    assert [f for f, (d, _) in rows.items() if d.host] == [0, 1, 2]
+    # the twelve predicates of the two-plane families, as they were held for -8 ... 263, read off the descriptor
     nv12 = {cm.sample_fmt(m, f): (f, m) for f in cm.FILTERS for m in ym.MATRICES}
-    for fmt, row in zip(range(lo, hi), rows.tolist()):
+    for fmt in range(-8, 264):
+        d = rows[fmt][0]
         p016 = fmt in pm.FAMILY
         interp = (fmt in nv12 and nv12[fmt][0] != 0) or (p016 and pm.filter_of(fmt) != 0)
         size = 1 if fmt == 0 or fmt in nv12 else 2 if fmt in (1, 3, 4) or p016 else 4 if fmt == 2 else 0
@@ -536,7 +529,14 @@ def test_the_predicates_and_origins_of_the_sample_formats(formats_program):
             nv12[fmt][0] * 16 + nv12[fmt][1] if fmt in nv12 else -1
         want = [fmt in nv12 and nv12[fmt][0] == 0, fmt in nv12, fmt in nv12 and interp, p016, p016 and interp, fmt in nv12 or p016, interp,
                 0 <= fmt <= 4 or fmt in nv12 or p016, 0 <= fmt <= 2, 2 <= fmt <= 4, size, what]
-        assert row == [int(x) for x in want], (fmt, row, want)
+        pairs, deep = d.layout == fm.PAIRS, d.depth != 0
+        got = [pairs and not deep and d.filter == 0, pairs and not deep, pairs and not deep and d.filter != 0, pairs and deep,
+               pairs and deep and d.filter != 0, pairs, pairs and d.filter != 0, d.device, d.host, d.is_float, d.bytes,
+               (d.bits * 256 if deep else 0) + d.filter * 16 + d.matrix if pairs else -1]
+        assert [int(x) for x in got] == [int(x) for x in want], (fmt, d, want)
+        assert not pairs or (d.sub, d.sx, d.sy) == (0, 1, 1)
+    for fmt in (5, 7, 15, 20, 31, 36, 47, 52, 64, 79, 84, 128, 244, 263, -1, -8):  # the two families' own lists of numbers that name nothing
+        assert rows[fmt][0] == fm.NOTHING, fmt
     x0, y0, pitch, pixel = 256, 512, 1024, 3
     want = []
     for fmt, size in ((0, 1), (1, 2), (2, 4), (3, 2), (4, 2)):
@@ -544,6 +544,53 @@ def test_the_predicates_and_origins_of_the_sample_formats(formats_program):
     for fmt, size in ((18, 1), (48, 1), (80, 2), (243, 2)):
         want.append([(y0 * pitch + x0) * size] + [(y0 // 2 * pitch + x0) * size] * 2)
     assert origins.tolist() == want
+
+
+def test_the_family_models_are_the_format_models():
+    """format_model's lists are the four family models' and the Python layer's tuples, 5 + 12 + 36 + 28 + 84 = 165, and each
+    family model reads a number's fields as format_model.describe does"""
+    import chroma_model as cm
+    import format_model as fm
+    import p016_model as pm
+    import planar16_model as m16
+    import planar_model as plm
+    import yuv_model as ym
+    from hydrium_amd import device
+
+    assert sorted(fm.NV12_FAMILY) == sorted(device.NV12_FAMILY) == sorted(cm.sample_fmt(m, f) for f in cm.FILTERS for m in ym.MATRICES)
+    assert sorted(fm.P016_FAMILY) == sorted(device.P016_FAMILY) == sorted(pm.FAMILY)
+    assert sorted(fm.PLANAR_FAMILY) == sorted(device.PLANAR_FAMILY) == sorted(plm.FAMILY)
+    assert sorted(fm.PLANAR16_FAMILY) == sorted(device.PLANAR16_FAMILY) == sorted(m16.FAMILY)
+    assert fm.RGB_FORMATS == (0, 1, 2, device.FLOAT16, device.BFLOAT16)
+    assert sum(len(f) for f in fm.FAMILIES) == 165
+    for fmt in range(fm.LO, fm.HI):
+        d = fm.describe(fmt)
+        assert (fmt in pm.FAMILY, plm.is_format(fmt), m16.is_format(fmt)) == \
+            (d.layout == fm.PAIRS and d.depth > 0, d.layout == fm.PLANES and d.depth == 0, d.layout == fm.PLANES and d.depth > 0), fmt
+        if fmt in pm.FAMILY:
+            assert (pm.matrix_of(fmt), pm.filter_of(fmt), pm.depth_of(fmt), pm.BITS[pm.depth_of(fmt)]) == (d.matrix, d.filter, d.depth, d.bits)
+        if plm.is_format(fmt):
+            assert (plm.matrix_of(fmt), plm.filter_of(fmt), plm.sub_of(fmt), *plm.shifts(plm.sub_of(fmt))) == (d.matrix, d.filter, d.sub, d.sx, d.sy)
+            assert plm.predicate_row(fmt) == (1, d.sub, d.filter, d.matrix, int(d.filter != 0), d.bytes, d.device, d.host)
+        if m16.is_format(fmt):
+            assert (m16.matrix_of(fmt), m16.filter_of(fmt), m16.sub_of(fmt), m16.depth_of(fmt), m16.bits_of(fmt), *plm.shifts(m16.sub_of(fmt))) == \
+                (d.matrix, d.filter, d.sub, d.depth, d.bits, d.sx, d.sy)
+        if d.layout != fm.RGB:
+            assert getattr(device, fm.public_name(fmt)) == fmt
+
+
+def test_every_public_ycbcr_name_is_spelled_by_the_descriptor_of_its_number():
+    """include/hydrium_amd.h: layout and depth give the stem, the filter the C / L infix, the matrix the suffix"""
+    import re
+
+    import format_dump
+    import format_model as fm
+
+    text = open(os.path.join(ROOT, "include", "hydrium_amd.h")).read()
+    found = {n: int(v) for n, v in re.findall(r"^#define HYDAMD_((?:NV12|P01[026]|I4(?:20|22|44)|I[024]1[026])[CL]?_BT\w+) (\d+)\s*$", text, re.M)}
+    assert sorted(found.values()) == sorted(fm.ALL[5:]) and len(found) == 160
+    for name, fmt in found.items():
+        assert fm.public_name(fmt, format_dump.described(fmt)) == name, (name, fmt)
 
 
 # ---- the closing count -------------------------------------------------------------------------------------------------------

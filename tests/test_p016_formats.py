@@ -207,9 +207,13 @@ def test_the_headers_constants_are_the_python_layers():
     assert not any(n.startswith("HYDAMD_NV12") for n in want)
     assert not set(device.P016_FAMILY) & (set(range(64, 80)) | set(device.NV12_FAMILY) | {0, 1, 2, 3, 4})
     assert "P01" not in open(os.path.join(ROOT, "include", "libhydrium", "libhydrium.h")).read()
-    # the C side's copy of the numbers and its predicates, as the host compiler reads csrc/hyd_sample_fmt.h
-    c_side = {n: int(v) for n, v in re.findall(r"^#define HYD_FMT_(P01[026][CL]?_BT\w+) (\d+)\s*$", open(os.path.join(hbuild.CSRC, "hyd_sample_fmt.h")).read(), re.M)}
-    assert {"HYDAMD_" + n: v for n, v in c_side.items()} == want
+    # the C side's reading of each number (hyd_fmt_describe under sanitizers) spells the public name: layout and depth the
+    # stem, the filter the infix, the matrix the suffix
+    import format_dump
+    import format_model as fm
+
+    assert {"HYDAMD_" + fm.public_name(v, format_dump.described(v)): v for v in want.values()} == want
+    assert all(format_dump.described(v) == fm.describe(v) and format_dump.described(v).device for v in want.values())
 
 
 def _surface16(w, h, pitch=None, extra=0):

@@ -8,12 +8,13 @@ import ctypes as C
 import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import chroma_model as cm
+import format_dump
+import format_model as fm
 import p016_model as p16
 import planar16_model as m16
 import planar_model as plm
@@ -119,38 +120,14 @@ def test_the_hooks_are_in_the_probe_flavour_only():
 
 
 # ---- the headers as plain C++ under address and UB sanitizers ----
-def sanitized_program(tmp_path_factory, stem):
-    """tests/c/<stem>.cc with g++ under address and UB sanitizers, no HIP header, no warning: run(mode, data) -> its output bytes"""
-    d = str(tmp_path_factory.mktemp(stem))
-    exe = os.path.join(d, stem)
-    source = os.path.join(ROOT, "tests", "c", stem + ".cc")
-    assert "hip_runtime" not in open(source).read()
-    cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-I", hbuild.CSRC, source, "-o", exe]
-    made = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert made.returncode == 0 and not made.stderr, made.stderr  # no warning either
-
-    def run(mode, data=None):
-        out, args = os.path.join(d, mode + ".out"), []
-        if data is not None:
-            with open(os.path.join(d, mode + ".in"), "wb") as f:
-                f.write(data)
-            args = [os.path.join(d, mode + ".in")]
-        ran = subprocess.run([exe, mode, out] + args, capture_output=True, text=True, timeout=300)
-        assert (ran.returncode, ran.stderr) == (0, ""), (mode, ran.returncode, ran.stderr[-4000:])
-        return np.fromfile(out, np.uint8)
-
-    return run
-
-
 @pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    return sanitized_program(tmp_path_factory, "planar16_formats")
+def program():
+    return format_dump.sanitized_program("planar16_formats")
 
 
-def test_the_predicates_the_round_trip_origins_pitches_and_alignment(program, tmp_path_factory):
+def test_the_predicates_the_round_trip_origins_pitches_and_alignment(program):
     lo, hi = -8, 4101
-    got = program("formats")
+    got = program("geometry")
     at = 0
 
     def take(dtype, *shape):
@@ -160,43 +137,47 @@ def test_the_predicates_the_round_trip_origins_pitches_and_alignment(program, tm
         at += n
         return a
 
-    rows, trips = take(np.int32, hi - lo, 24), take(np.int32, 4096, 10)
     origins, pitches, aligned = take(np.int64, 3, 2, 2, 3), take(np.int32, 2, 3, 3, 2), take(np.int32, 8)
     assert at == got.size
-    # (a) every predicate for -8 ... 4100, old and new
+    rows, _ = format_dump.formats()  # hyd_fmt_describe and hydk_decode_fmt of every number, from the sanitized sample_formats program
+    # (a) every predicate for -8 ... 4100, the 8-bit planar family's and this family's, read off the descriptor
     family = []
-    for fmt, row in zip(range(lo, hi), rows.tolist()):
-        assert tuple(row[:8]) == m16.older_row(fmt), (fmt, row)
-        assert tuple(row[12:21]) == m16.predicate_row(fmt) and row[21:] == [0, 0, 0], (fmt, row)
-        if row[12]:
+    for fmt in range(lo, hi):
+        d, _ = rows[fmt]
+        assert d == fm.describe(fmt), (fmt, d)
+        planes = d.layout == fm.PLANES
+        planar, p16 = planes and d.depth == 0, planes and d.depth > 0
+        older = (int(planar), d.sub if planar else 0, d.filter if planar else 0, d.matrix if planar else 0, int(planar and d.filter != 0),
+                 d.bytes, d.device, d.host)
+        assert older == m16.older_row(fmt), (fmt, d)
+        newer = (1, d.sub, d.filter, d.matrix, d.depth, d.bits, d.sx, d.sy, int(d.filter != 0)) if p16 else (0,) * 9
+        assert newer == m16.predicate_row(fmt), (fmt, d)
+        if p16:
             family.append(fmt)
-            assert row[:5] == [0] * 5 and row[8:12] == [0] * 4, (fmt, row)  # not the 8-bit planar family's, nor NV12's, P016's, the float class's
-        assert row[11] == int(2 <= fmt <= 4)
-    assert tuple(family) == tuple(sorted(m16.FAMILY)) and len(family) == 84 and family[0] == 2112
+            assert not planar and d.layout != fm.PAIRS and not d.is_float and not d.host, (fmt, d)  # not the 8-bit planar family's, nor NV12's, P016's, the float class's
+        assert d.is_float == int(2 <= fmt <= 4)
+    assert tuple(family) == tuple(sorted(m16.FAMILY)) == tuple(sorted(fm.PLANAR16_FAMILY)) and len(family) == 84 and family[0] == 2112
     per_depth = list(range(0, 12)) + list(range(16, 24)) + list(range(32, 40))
     assert family == [2048 + 64 * d + k for d in (1, 2, 3) for k in per_depth]
     for fmt in (2048, 2060, 2111, 2124, 2127, 2136, 2143, 2152, 2175, 2188, 2216, 2239, 2252, 2280, 2304, 4096, 4100, 576, 640, 1024, 1100):
-        assert rows[fmt - lo].tolist() == [0] * 24, fmt
-    # every row of -8 ... 1100 is what the older program prints
-    older = sanitized_program(tmp_path_factory, "planar_formats")("formats")
-    assert np.array_equal(older[:1109 * 48].view(np.int32).reshape(1109, 12), rows[:1109, :12])
-    # (b) decode and encode: 0 ... 4095 round-trips exactly where a format is a device format, and nowhere else
-    for fmt, t in enumerate(trips.tolist()):
-        device_fmt = bool(rows[fmt - lo, 6])
-        assert t[0] == int(device_fmt) and t[1] == (fmt if device_fmt else -1), (fmt, t)
+        assert rows[fmt] == (fm.NOTHING, (0, -1, 0, 0, 0, 0)), fmt
+    # (b) decode and encode: -8 ... 4100 round-trips exactly where a format is a device format, and nowhere else
+    for fmt in range(lo, hi):
+        d, (ok, back, cls, storage, matrix, variant) = rows[fmt]
+        assert ok == d.device and back == (fmt if d.device else -1), (fmt, rows[fmt])
         if m16.is_format(fmt):
-            sx, sy = plm.shifts(m16.sub_of(fmt))
             filt = m16.filter_of(fmt)
-            assert t[2:] == [1, 9 + (filt != 0), m16.matrix_of(fmt) + 4 * m16.depth_of(fmt), filt, m16.sub_of(fmt), sx, sy, 1024 if filt else 512], (fmt, t)
-        elif not device_fmt:
-            assert t[2:9] == [0] * 7
+            assert (cls, storage, matrix, variant) == (1, 9 + (filt != 0), m16.matrix_of(fmt) + 4 * m16.depth_of(fmt), 1024 if filt else 512), (fmt, rows[fmt])
+            assert (d.filter, d.sub, d.sx, d.sy) == (filt, m16.sub_of(fmt), *plm.shifts(m16.sub_of(fmt)))  # what the job's fields are copied from
+        elif not d.device:
+            assert (cls, storage, matrix, variant) == (0, 0, 0, 0) and d == fm.NOTHING
     # (c) origins at (256, 512), in bytes: I010C, I212L, I416 under Y pitch +-1024 and chroma pitch +-520 words
     for k, (sx, sy) in enumerate(((1, 1), (1, 0), (0, 0))):
         for i, yp in enumerate((1024, -1024)):
             for j, cp in enumerate((520, -520)):
                 chroma = 2 * ((512 >> sy) * cp + (256 >> sx))
                 assert origins[k, i, j].tolist() == [2 * (512 * yp + 256), chroma, chroma], (k, i, j)
-    # (d) the pitch helper at |pitch| = cw - 1, cw, cw + 1, both signs, W = 199 and 200
+    # (d) the pitch rule at |pitch| = cw - 1, cw, cw + 1, both signs, W = 199 and 200
     assert pitches.tolist() == [[[[0, 0], [1, 1], [1, 1]]] * 3] * 2
     # (e) the alignment check: only three even addresses pass
     assert aligned.tolist() == [1, 0, 0, 0, 0, 0, 0, 0]
@@ -240,8 +221,9 @@ def test_the_headers_constants_are_the_python_layers():
     assert not set(device.PLANAR16_FAMILY) & (set(device.NV12_FAMILY) | set(device.P016_FAMILY) | set(device.PLANAR_FAMILY) | set(range(2112)))
     assert "I010" not in open(os.path.join(ROOT, "include", "libhydrium", "libhydrium.h")).read()
     fmt_h = open(os.path.join(hbuild.CSRC, "hyd_sample_fmt.h")).read()
-    c_side = {n: int(v) for n, v in re.findall(r"^#define HYD_FMT_(I[024]1[026][CL]?_BT\w+) (\d+)\s*$", fmt_h, re.M)}
-    assert {"HYDAMD_" + n: v for n, v in c_side.items()} == want
+    # the C side's reading of each number spells the public name: layout and depth the stem, the filter the infix, the matrix the suffix
+    assert {"HYDAMD_" + fm.public_name(v, format_dump.described(v)): v for v in want.values()} == want
+    assert all(format_dump.described(v) == fm.describe(v) and format_dump.described(v).device for v in want.values())
     message = re.search(r'#define HYD_FMT_PLANAR16_ALIGN_MSG "([^"]+)"', fmt_h).group(1)
     assert fmt_h.count('"' + message + '"') == 1 and " ".join(message.split()) in " ".join(text.replace(" *", " ").split())
     with pytest.raises(ValueError, match="depth"):

@@ -8,12 +8,13 @@ import ctypes as C
 import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import chroma_model as cm
+import format_dump
+import format_model as fm
 import planar_model as plm
 import yuv_model as ym
 from kernel_descriptors import kernel_descriptors
@@ -106,61 +107,46 @@ def test_the_hooks_are_in_the_probe_flavour_only():
 
 # ---- the headers as plain C++ under address and UB sanitizers ----
 @pytest.fixture(scope="module")
-def planar_program(tmp_path_factory):
+def planar_program():
     """tests/c/planar_formats.cc: hyd_sample_fmt.h and hydk_chroma.h with g++, no HIP header, no warning"""
-    d = str(tmp_path_factory.mktemp("planar_formats"))
-    exe = os.path.join(d, "planar_formats")
-    source = os.path.join(ROOT, "tests", "c", "planar_formats.cc")
-    assert "hip_runtime" not in open(source).read()
-    cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-I", hbuild.CSRC, source, "-o", exe]
-    made = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert made.returncode == 0 and not made.stderr, made.stderr  # no warning either
-
-    def run(mode, data=None):
-        """the mode's output file, whole; exit status 0 and an empty stderr"""
-        out, args = os.path.join(d, mode + ".out"), []
-        if data is not None:
-            with open(os.path.join(d, mode + ".in"), "wb") as f:
-                f.write(data)
-            args = [os.path.join(d, mode + ".in")]
-        ran = subprocess.run([exe, mode, out] + args, capture_output=True, text=True, timeout=300)
-        assert (ran.returncode, ran.stderr) == (0, ""), (mode, ran.returncode, ran.stderr[-4000:])
-        return np.fromfile(out, np.uint8)
-
-    return run
+    return format_dump.sanitized_program("planar_formats")
 
 
 def test_the_predicates_origins_and_the_pitch_helper(planar_program):
     lo, hi = -8, 1101
-    got = planar_program("formats")
-    rows = got[:(hi - lo) * 48].view(np.int32).reshape(hi - lo, 12)
-    rest = got[(hi - lo) * 48:]
-    origins = rest[:3 * 2 * 3 * 8].view(np.int64).reshape(3, 2, 3)
-    pitches = rest[3 * 2 * 3 * 8:].view(np.int32).reshape(2, 3, 3, 2)
-    # (a) every predicate for -8 ... 1100
+    got = planar_program("geometry")
+    origins = got[:3 * 2 * 3 * 8].view(np.int64).reshape(3, 2, 3)
+    pitches = got[3 * 2 * 3 * 8:].view(np.int32).reshape(2, 3, 3, 2)
+    # (a) every predicate for -8 ... 1100, read off the descriptor the C side gives each number (format_dump: held to
+    # format_model.describe on all of -8 ... 4100 by tests/test_host_sanitizers.py)
     family = []
-    for fmt, row in zip(range(lo, hi), rows.tolist()):
+    for fmt in range(lo, hi):
+        d = format_dump.described(fmt)
+        assert d == fm.describe(fmt), (fmt, d)
+        planar = d.layout == fm.PLANES and d.depth == 0
         want = plm.predicate_row(fmt)
-        assert tuple(row[:8]) == want, (fmt, row, want)
+        row = (int(planar), d.sub if planar else 0, d.filter if planar else 0, d.matrix if planar else 0, int(planar and d.filter != 0),
+               d.bytes, d.device, d.host)
+        assert row == want, (fmt, row, want)
         if want[0]:
             family.append(fmt)
-            assert row[8:] == [0, 0, 0, 0], (fmt, row)  # the NV12, P016 and yuv420 predicates and the float class: not theirs
-        assert row[11] == int(2 <= fmt <= 4)
-    assert tuple(family) == tuple(sorted(plm.FAMILY)) and len(family) == 28
+            assert (d.sx, d.sy) == plm.shifts(d.sub) and (d.is_float, d.bits) == (0, 8), (fmt, d)  # not the float class, no (U, V) pairs
+        assert d.is_float == int(2 <= fmt <= 4)
+    assert tuple(family) == tuple(sorted(plm.FAMILY)) == tuple(sorted(fm.PLANAR_FAMILY)) and len(family) == 28
     assert family == list(range(512, 524)) + list(range(528, 536)) + list(range(544, 552))
     for fmt in (524, 527, 536, 543, 552, 559, 560, 575, 576, 640, 1024, 1100, 511, 264):
-        assert rows[fmt - lo].tolist()[:8] == [0, 0, 0, 0, 0, 0, 0, 0], fmt
+        assert format_dump.described(fmt) == fm.NOTHING, fmt
     # the numbers earlier families pin stay what they were
     for fmt in (5, 7, 15, 20, 31, 36, 47, 52, 64, 79, 84, 128, 244):
-        assert rows[fmt - lo].tolist()[5:8] == [0, 0, 0], fmt
-    assert [rows[f - lo, 6] for f in (0, 1, 2, 3, 4, 16, 35, 51, 80, 243)] == [1] * 10
+        d = format_dump.described(fmt)
+        assert (d.bytes, d.device, d.host) == (0, 0, 0), fmt
+    assert [format_dump.described(f).device for f in (0, 1, 2, 3, 4, 16, 35, 51, 80, 243)] == [1] * 10
     # (b) origins at (256, 512), Y pitch 1024, chroma pitch 520 and -520: I420C, I422L, I444
     for k, (sx, sy) in enumerate(((1, 1), (1, 0), (0, 0))):
         for j, cp in enumerate((520, -520)):
             chroma = (512 >> sy) * cp + (256 >> sx)
             assert origins[k, j].tolist() == [512 * 1024 + 256, chroma, chroma], (k, j)
-    # (c) the pitch helper at |pitch| = cw - 1, cw, cw + 1, both signs, W = 199 and 200
+    # (c) the pitch rule at |pitch| = cw - 1, cw, cw + 1, both signs, W = 199 and 200
     assert pitches.tolist() == [[[[0, 0], [1, 1], [1, 1]]] * 3] * 2
 
 
@@ -197,10 +183,12 @@ def test_the_headers_constants_are_the_python_layers():
     assert sorted(device.PLANAR_FAMILY) == sorted(plm.FAMILY) == sorted(want.values())
     assert not set(device.PLANAR_FAMILY) & (set(device.NV12_FAMILY) | set(device.P016_FAMILY) | set(range(264)))
     assert "I420" not in open(os.path.join(ROOT, "include", "libhydrium", "libhydrium.h")).read()
-    c_side = {n: int(v) for n, v in re.findall(r"^#define HYD_FMT_(I4(?:20|22|44)[CL]?_BT\w+) (\d+)\s*$", open(os.path.join(hbuild.CSRC, "hyd_sample_fmt.h")).read(), re.M)}
-    assert {"HYDAMD_" + n: v for n, v in c_side.items()} == want
-    for text in (text, open(os.path.join(hbuild.CSRC, "hyd_sample_fmt.h")).read()):
-        assert "planar YCbCr wants the chroma planes' pitch in pixel_stride" in text
+    # the C side's reading of each number spells the public name: layout and depth the stem, the filter the infix, the matrix the suffix
+    assert {"HYDAMD_" + fm.public_name(v, format_dump.described(v)): v for v in want.values()} == want
+    assert all(format_dump.described(v) == fm.describe(v) and format_dump.described(v).device for v in want.values())
+    fmt_h = open(os.path.join(hbuild.CSRC, "hyd_sample_fmt.h")).read()
+    assert fmt_h.count('"planar YCbCr wants the chroma planes\' pitch in pixel_stride"') == 1
+    assert "planar YCbCr wants the chroma planes' pitch in pixel_stride" in text
 
 
 def test_planar_yuv_names_its_format_and_fills_a_descriptor():
