@@ -343,7 +343,9 @@ static_assert(HYDAMD_FMT_PLANES(10, HYDK_YUV16_P010) && HYDAMD_FMT_PLANES(12, HY
 static_assert(hyd_fmt_describe(HYDAMD_NV12_BT709).bits == 8 && hyd_fmt_describe(HYDAMD_P010_BT709).bits == 10 && hyd_fmt_describe(HYDAMD_I212_BT709).bits == 12 &&
                   hyd_fmt_describe(HYDAMD_I416_BT709).bits == 16 && HYDK_CHROMA_FILTERS == 3 && HYDK_YUV16_DEPTHS == 3,
               "a depth's significant bits; three filters and three deeper depths, as hyd_fmt_describe has them");
-static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_FORMS == 13, "the job did not grow; launch_transform's mask has 13 bits");
+static_assert(HYDAMD_FMT_FILTERS(YUY2, HYD_LAYOUT_PACKED, 0, HYDK_PLANAR_422) && HYDAMD_YUY2_BT709 == HYD_FMT_BASE_PACKED,
+              "packed 4:2:2: 8192 + the kernels' matrix index + 16 * the kernels' chroma filter");
+static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_FORMS == 15, "the job did not grow; launch_transform's mask has 15 bits");
 #undef HYDAMD_FMT_PLANES
 #undef HYDAMD_FMT_FILTERS
 #undef HYDAMD_FMT_STEM
@@ -456,6 +458,8 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.matrix = form.matrix;
     job.filter = form.filter;
     job.sub = form.sub;
+    if (hyd_fmt_describe(sample_fmt).layout == HYD_LAYOUT_PACKED) /* the byte order, which the pointers name and the number does not */
+        job.sub = (uint32_t)hyd_fmt_packed_order(src);
     if (hydk_store_form((int)form.storage).interp) {
         /* the picture's chroma plane (each plane's, in its own units) and where src[1] (and src[2]) point in it: all the kernel
          * may read around this LF group */
@@ -2963,6 +2967,53 @@ __attribute__((visibility("default"))) int hydt_planar_upsample_device(int devic
     return probe_round_trip(plane, in_bytes, out, n, [&](void *d_in, void *d_out) {
         hipLaunchKernelGGL(k_planar_upsample_probe, probe_grid(n), dim3(256), 0, nullptr, sub, filter, (const uint8_t *)d_in, (uint8_t *)d_out,
                            width, height);
+    });
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the packed 4:2:2 definition (hydk_yuy2_pixel, hydk_yuy2.h) as the host
+ * compiler built it and as the device runs it.  order: HYD_PACKED_YUYV ... _VYUY; filter HYDK_CHROMA_*; matrix HYDK_YUV_*; surface:
+ * height rows of 4 * ceil(width / 2) bytes, tightly packed; rgb receives height rows of width (R, G, B) byte triples. */
+static bool packed_probe_args(int order, int filter, int matrix, const uint8_t *surface, uint8_t *rgb, int width, int height) {
+    return order >= HYD_PACKED_YUYV && order <= HYD_PACKED_VYUY && filter >= 0 && filter < HYDK_CHROMA_FILTERS && matrix >= 0 &&
+           matrix < HYDK_YUV_MATRICES && surface && rgb && width >= 1 && height >= 1 && width <= 4096 && height <= 4096;
+}
+__host__ __device__ static inline void packed_probe_pixel(int order, int filter, int matrix, const uint8_t *surface, uint8_t *rgb, int width, size_t i) {
+    /* the three pointers a caller of that byte order gives: Y, U, V of the first group */
+    const int yo = hydk_yuy2_y_offset(order), c0 = 1 - yo, c1 = 3 - yo;
+    const uint8_t *yp = surface + yo, *up = surface + (hydk_yuy2_v_first(order) ? c1 : c0), *vp = surface + (hydk_yuy2_v_first(order) ? c0 : c1);
+    uint32_t out[3];
+    hydk_yuy2_pixel(filter, matrix, yp, up, vp, 4ll * ((width + 1) >> 1), width, (int)(i % (size_t)width), (int)(i / (size_t)width), out);
+    for (int c = 0; c < 3; c++)
+        rgb[3 * i + c] = (uint8_t)out[c];
+}
+
+__attribute__((visibility("default"))) int hydt_packed_to_rgb_host(int order, int filter, int matrix, const uint8_t *surface, uint8_t *rgb,
+                                                                   int width, int height) {
+    if (!packed_probe_args(order, filter, matrix, surface, rgb, width, height))
+        return ST_API_ERROR;
+    for (size_t i = 0; i < (size_t)width * height; i++)
+        packed_probe_pixel(order, filter, matrix, surface, rgb, width, i);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_packed_to_rgb_probe(int order, int filter, int matrix, const uint8_t *surface, uint8_t *rgb, int width,
+                                                             int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i < (size_t)width * height)
+        packed_probe_pixel(order, filter, matrix, surface, rgb, width, i);
+}
+} /* namespace */
+
+/* one launch over the picture (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_packed_to_rgb_device(int device, int order, int filter, int matrix, const uint8_t *surface,
+                                                                     uint8_t *rgb, int width, int height) {
+    if (!packed_probe_args(order, filter, matrix, surface, rgb, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height;
+    return probe_round_trip(surface, 4 * (size_t)((width + 1) >> 1) * height, rgb, 3 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_packed_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, order, filter, matrix, (const uint8_t *)d_in,
+                           (uint8_t *)d_out, width, height);
     });
 }
 

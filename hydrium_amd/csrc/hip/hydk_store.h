@@ -33,7 +33,9 @@
 #define HYDK_STORE_YUVPI 8
 #define HYDK_STORE_YUVP16 9  /* 16-bit class: the same three planes in 16-bit words of 10, 12 or 16 bits, LSB-aligned (hydk_yuvp16.h) */
 #define HYDK_STORE_YUVP16I 10
-#define HYDK_STORE_FORMS 11
+#define HYDK_STORE_YUY2 11  /* 8-bit class: packed 4:2:2 — Y, U and V bytes in one plane, HydkLfJob.sub the byte order (HYD_PACKED_*; hydk_yuy2.h) */
+#define HYDK_STORE_YUY2I 12
+#define HYDK_STORE_FORMS 13
 
 /* HydkLfJob.use_luts of a YCbCr job is the XYB mode + its form's variant bit: the RGB instances' own test turns it away */
 #define HYDK_VARIANT_NV12 8
@@ -44,12 +46,14 @@
 #define HYDK_VARIANT_YUVPI 256
 #define HYDK_VARIANT_YUVP16 512
 #define HYDK_VARIANT_YUVP16I 1024
+#define HYDK_VARIANT_YUY2 2048
+#define HYDK_VARIANT_YUY2I 4096
 
 typedef struct HydkStoreForm {
     int cls;           /* HYDK_FMT_*; form 0 belongs to every class */
     int ycbcr;         /* a pixel is converted to RGB of its class right after the load */
     int bits;          /* of a stored sample */
-    int chroma_planes; /* YCbCr: 1 — (U, V) pairs interleaved in one plane; 2 — a plane each */
+    int chroma_planes; /* YCbCr: 1 — (U, V) pairs interleaved in one plane; 2 — a plane each; 0 — none: U and V sit among the Y bytes */
     int interp;        /* chroma interpolated: the job carries filter and the picture (pic_*) */
     int variant;       /* HYDK_VARIANT_* */
 } HydkStoreForm;
@@ -67,12 +71,15 @@ HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
         {HYDK_FMT_U8, 1, 8, 2, 1, HYDK_VARIANT_YUVPI},
         {HYDK_FMT_U16, 1, 16, 2, 0, HYDK_VARIANT_YUVP16},
         {HYDK_FMT_U16, 1, 16, 2, 1, HYDK_VARIANT_YUVP16I},
+        {HYDK_FMT_U8, 1, 8, 0, 0, HYDK_VARIANT_YUY2},
+        {HYDK_FMT_U8, 1, 8, 0, 1, HYDK_VARIANT_YUY2I},
     };
     return forms[storage >= 0 && storage < HYDK_STORE_FORMS ? storage : 0];
 }
 
 /* A public sample format taken apart into what a job holds.  ok: a device entry point takes it (else every field is 0).
- * matrix: HYDK_YUV_* (0 ... 3), + 4 * depth (HYDK_YUV16_P01x) for the 16-bit forms; filter: HYDK_CHROMA_*; sub: HYDK_PLANAR_*;
+ * matrix: HYDK_YUV_* (0 ... 3), + 4 * depth (HYDK_YUV16_P01x) for the 16-bit forms; filter: HYDK_CHROMA_*; sub: HYDK_PLANAR_*
+ * (packed 4:2:2: HYDK_PLANAR_422 here; a recorded job's sub holds the byte order instead, which the public number does not name);
  * sx, sy: log2 of the pixels one chroma sample spans across and down. */
 typedef struct HydkSampleForm {
     int ok, cls;
@@ -83,7 +90,9 @@ typedef struct HydkSampleForm {
 static inline HydkSampleForm hydk_decode_fmt(int f) {
     const HydFmt fmt = hyd_fmt_describe(f);
     HydkSampleForm d = {fmt.device, 0, 0, (uint32_t)(fmt.matrix + 4 * fmt.depth), (uint32_t)fmt.filter, (uint32_t)fmt.sub, fmt.sx, fmt.sy};
-    if (fmt.layout != HYD_LAYOUT_RGB) /* the YCbCr forms in the table's order: pairs then planes, bytes then words, nearest then interpolated */
+    if (fmt.layout == HYD_LAYOUT_PACKED)
+        d.storage = (uint32_t)(HYDK_STORE_YUY2 + (fmt.filter != 0));
+    else if (fmt.layout != HYD_LAYOUT_RGB) /* the YCbCr forms in the table's order: pairs then planes, bytes then words, nearest then interpolated */
         d.storage = (uint32_t)(HYDK_STORE_NV12 + 4 * (fmt.layout == HYD_LAYOUT_PLANES) + 2 * (fmt.bytes == 2) + (fmt.filter != 0));
     else if (f == HYD_FMT_FLOAT16 || f == HYD_FMT_BFLOAT16)
         d.storage = (uint32_t)(f == HYD_FMT_FLOAT16 ? HYDK_STORE_F16 : HYDK_STORE_BF16);
@@ -96,6 +105,8 @@ static inline int hydk_encode_fmt(HydkSampleForm d) {
     const HydkStoreForm form = hydk_store_form((int)d.storage);
     if (!form.ycbcr)
         return d.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : d.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : d.cls;
+    if (form.chroma_planes == 0) /* (sub: the byte order in a job, 4:2:2 in a decoded format; neither is in the number) */
+        return HYD_FMT_BASE_PACKED + (int)(d.matrix & 3u) + 16 * (int)d.filter;
     const int base = form.chroma_planes == 1 ? HYD_FMT_BASE_PAIRS : form.bits == 16 ? HYD_FMT_BASE_PLANES16 : HYD_FMT_BASE_PLANES;
     return base + (int)(d.matrix & 3u) + 4 * (int)d.sub + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2);
 }

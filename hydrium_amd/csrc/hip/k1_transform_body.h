@@ -1,18 +1,19 @@
 /*
  * k1_transform_body.h — the body of the transform kernel (kernels.hip, K1), included into k_transform_tokenize, into
- * k_transform_tokenize_p016, into k_transform_tokenize_planar and into k_transform_tokenize_yuvp16 and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
+ * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16 and into k_transform_tokenize_yuy2 and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
  * and STORE, the kernel's parameters jobs, status, part_info and plog, and everything kernels.hip defines above its K1 section.
  * No include guard: it is function-body text, meant to be included once per kernel.
  */
     /* What STORE is made of (hydk_store.h).  YUV: a YCbCr form — a pixel becomes an RGB pixel of its class right after the load.
      * TWO_PLANES: U and V in planes of their own, whose pitch is job.pixel_stride, subsampled as job.sub says (planar YCbCr);
      * else (U, V) pairs in one half-resolution plane of the Y plane's pitch (NV12; P010 / P012 / P016 in 16-bit words).
+     * PK: no chroma plane at all — packed 4:2:2, U and V among the Y bytes of one plane in the byte order job.sub names (hydk_yuy2.h).
      * INTERP: chroma interpolated (hydk_chroma.h) — job.filter says centre- or left-sited, and the job knows the picture it is
      * cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it.  HALF: 2-byte floats, widened on load */
     constexpr HydkStoreForm FORM = hydk_store_form(STORE);
     static_assert(STORE == HYDK_STORE_F32 || FORM.cls == FMT,
-                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP and YUVPI, the 16-bit class P016, P016I, YUVP16 and YUVP16I");
-    constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, INTERP = FORM.interp;
+                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16 and YUVP16I");
+    constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, PK = YUV && FORM.chroma_planes == 0, INTERP = FORM.interp;
     constexpr bool HALF = FMT == HYDK_FMT_F32 && STORE != HYDK_STORE_F32;
     /* the two-plane forms by name: YUVPI keeps a prefetch, an edge fill and an interpolate loop of its own (through the shared
      * ones its instances measured a few tenths of a percent slower, profiles/ycbcr_loader.txt) */
@@ -149,10 +150,15 @@
     const HydkYuvMatrix yuv = YUV && SB == 16 ? hydk_yuv16_job_matrix(job.matrix) : hydk_yuv_matrix(YUV ? (int)job.matrix : 0);
     const int pcx = INTERP ? job.pic_cx0 + ((px0 + ab * 8) >> 1) : 0;
     /* log2 of the pixels one chroma sample spans across and down: the job's subsampling for two planes, 4:2:0 for pairs */
-    const int csx = TWO_PLANES ? hydk_planar_sx((int)job.sub) : (int)YUV, csy = TWO_PLANES ? hydk_planar_sy((int)job.sub) : (int)YUV;
+    const int csx = TWO_PLANES ? hydk_planar_sx((int)job.sub) : (int)YUV, csy = TWO_PLANES ? hydk_planar_sy((int)job.sub) : (int)(YUV && !PK);
     /* pairs in one plane (nvrun, prun): kYW dwords of Y and, from chroma row y >> 1, kYW dwords holding the block's four pairs */
-    const bool prun = YUV && !TWO_PLANES &&
+    const bool prun = YUV && !TWO_PLANES && !PK &&
                       (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)(job.row_stride * (SB / 8))) & 3) == 0;
+    /* packed 4:2:2 (pkrun): a block row is four GROUPS — 16 bytes, four dwords — from the row's one plane, when the first group (Y's
+     * place in its pair of bytes before src[0]) and the pitch are dword multiples; Y and the four (U, V) pairs are picked out of the
+     * registers at use, by the byte order (wave-uniform).  pk_y: 0 — Y is the first byte of a pair, 1 — the second; pk_vu: V before U */
+    const int pk_y = PK ? hydk_yuy2_y_offset((int)job.sub) : 0, pk_vu = PK ? hydk_yuy2_v_first((int)job.sub) : 0;
+    const bool pkrun = PK && ((((uintptr_t)job.src[0] - (uintptr_t)pk_y) | (uintptr_t)job.row_stride) & 3) == 0;
     /* two planes (ylrun): two dwords of Y and, from each chroma plane, the dword of four samples that serves its eight pixels
      * (the block's chroma column is a multiple of 4) — two dwords of eight for 4:4:4.  16-bit words (YP16): four dwords of Y and
      * two from each chroma plane — four for 4:4:4, kWords in all — where the three bases and both pitches IN BYTES are dword
@@ -165,7 +171,7 @@
      * them: six columns, p = 0 ... 5.  It comes as dwords only where all six lie inside the picture's chroma row; the picture's
      * first and last chroma columns, a ragged last block and shifted bases or pitches fill the same window sample by sample with
      * the clamps, at use (phase A below).  pcx: the picture's chroma column of the block's first pixel. */
-    const bool irun = (TWO_PLANES ? ylrun : prun) && (!INTERP || ((job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1));
+    const bool irun = (TWO_PLANES ? ylrun : PK ? pkrun : prun) && (!INTERP || ((job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1));
     const bool fast = (YUV ? irun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
     uint32_t nxt[kWords];
     /* the window's columns 0 and 5, which sit in no dword of the four between them (YUVPI: of U and of V, column 0 | column 5
@@ -194,6 +200,8 @@
      * sample a pixel) byte i of the two dwords a plane at nxt[2 + 2 c].  YP16: word i >> 1, or (4:4:4) word i, of the dwords at
      * nxt[4 + 4 c] */
     auto near_get = [&](int c, int i) -> uint32_t {
+        if (PK) /* (unpacked at use into YUVP's 4:2:2 places: four U bytes in nxt[2], four V bytes in nxt[3]) */
+            return (nxt[2 + c] >> (8 * (i >> 1))) & 0xFF;
         if (!TWO_PLANES)
             return win_get(c, 0, 1 + (i >> 1));
         if (YP16) {
@@ -209,6 +217,22 @@
         return (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
     };
     auto prefetch = [&](int s) {
+        if (PK) {
+            /* the four groups as stored in nxt[0 ... 3]; interpolated: the group behind them in flank[1] and (centre-sited) the one
+             * before them in flank[0], whole dwords too: irun says that both lie inside the picture's row */
+            if (fast && s * 8 + ar < gh) {
+                const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
+                const char *pg = (const char *)job.src[0] - pk_y + y * job.row_stride + 2 * x;
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    nxt[k] = HYDK_GLOBAL(const uint32_t, pg)[k];
+                if (INTERP) {
+                    flank[1] = HYDK_GLOBAL(const uint32_t, pg)[4];
+                    flank[0] = job.filter == HYDK_CHROMA_CENTRE ? HYDK_GLOBAL(const uint32_t, pg - 4)[0] : 0u; /* (left-sited chroma never looks before) */
+                }
+            }
+            return;
+        }
         if (YUV && !TWO_PLANES) {
             if (fast && s * 8 + ar < gh) {
                 typedef typename std::conditional<SB == 8, uint16_t, uint32_t>::type pair_t;
@@ -455,7 +479,7 @@
                  * and pic_cx0 columns before src[1] (and src[2]).  Window column p is the picture's clamp(pcx - 1 + p, 0, cw - 1),
                  * which is what cx, and hx with its clamp, come to for every pixel of the block.  The rest is shared with the
                  * dword rows. */
-                if (INTERP && !TWO_PLANES && !fast) {
+                if (INTERP && !TWO_PLANES && !PK && !fast) {
 #pragma unroll
                     for (int k = 0; k < kWords; k++)
                         nxt[k] = 0;
@@ -520,6 +544,66 @@
                                 nxt[5] |= d << (8 * (p - 1));
                             }
                         }
+                    }
+                }
+                /* Packed 4:2:2.  Dword rows: the four groups become YUVP's window — eight Y bytes in nxt[0], nxt[1], four U bytes and
+                 * four V bytes — by byte permutes whose selectors are the byte order's (uniform over the wavefront): out of a pair of
+                 * groups {lo, hi}, bytes 0, 2, 4, 6 are the Y samples of YUYV and the chroma of UYVY, bytes 1, 3, 5, 7 the other; then
+                 * the same split tells the first chroma component from the second.  Interpolated: YUVPI's window — U near and far in
+                 * nxt[2], nxt[3], V in nxt[4], nxt[5], far = near as 4:2:2 has it there, columns 0 and 5 in flank[] — so that the mix
+                 * below is YUVPI's.  Rows that did not come as dwords (a base or pitch off the dword, the picture's first and last
+                 * chroma column, a ragged last block) fill the same window byte by byte with the clamps: group col of the picture's
+                 * row lies 4 (col - pic_cx0) bytes from src[1] and src[2]. */
+                if (PK && fast) {
+                    const uint32_t even = 0x06040200u, odd = 0x07050301u;
+                    const uint32_t sel_y = pk_y ? odd : even, sel_c = pk_y ? even : odd;
+                    const uint32_t ca = __builtin_amdgcn_perm(nxt[1], nxt[0], sel_c), cb = __builtin_amdgcn_perm(nxt[3], nxt[2], sel_c);
+                    const uint32_t y0 = __builtin_amdgcn_perm(nxt[1], nxt[0], sel_y), y1 = __builtin_amdgcn_perm(nxt[3], nxt[2], sel_y);
+                    const uint32_t c0 = __builtin_amdgcn_perm(cb, ca, even), c1 = __builtin_amdgcn_perm(cb, ca, odd);
+                    const uint32_t u4 = pk_vu ? c1 : c0, v4 = pk_vu ? c0 : c1;
+                    nxt[0] = y0;
+                    nxt[1] = y1;
+                    if (!INTERP) {
+                        nxt[2] = u4;
+                        nxt[3] = v4;
+                    } else {
+                        /* (c0, c1) of the groups before and behind: bytes 0, 1 before, 2, 3 behind */
+                        const uint32_t cf = __builtin_amdgcn_perm(flank[1], flank[0], sel_c);
+                        const uint32_t f0 = (cf & 0xFFu) | ((cf >> 8) & 0xFF00u), f1 = ((cf >> 8) & 0xFFu) | ((cf >> 16) & 0xFF00u);
+                        const uint32_t fu = pk_vu ? f1 : f0, fv = pk_vu ? f0 : f1;
+                        nxt[2] = nxt[3] = u4;
+                        nxt[4] = nxt[5] = v4;
+                        flank[0] = fu | fu << 16;
+                        flank[1] = fv | fv << 16;
+                    }
+                }
+                if (PK && INTERP && !fast) {
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        nxt[k] = 0;
+                    flank[0] = flank[1] = 0;
+                    if (row_ok) {
+                        const uint8_t *py = (const uint8_t *)job.src[0] + (long long)y * job.row_stride + 2ll * x0;
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            if (i < nvalid)
+                                nxt[i >> 2] |= (uint32_t)py[2 * i] << (8 * (i & 3));
+                        const long long on = (long long)y * job.row_stride - 4ll * job.pic_cx0;
+                        const uint8_t *un = (const uint8_t *)job.src[1] + on, *vn = (const uint8_t *)job.src[2] + on;
+#pragma unroll
+                        for (int p = 0; p < 6; p++) {
+                            const int col = min(max(pcx - 1 + p, 0), job.pic_cw - 1);
+                            const uint32_t a = un[4 * col], c = vn[4 * col];
+                            if (p == 0 || p == 5) {
+                                flank[0] |= (a | a << 16) << (p ? 8 : 0);
+                                flank[1] |= (c | c << 16) << (p ? 8 : 0);
+                            } else {
+                                nxt[2] |= a << (8 * (p - 1));
+                                nxt[4] |= c << (8 * (p - 1));
+                            }
+                        }
+                        nxt[3] = nxt[2];
+                        nxt[5] = nxt[4];
                     }
                 }
                 /* YP16 rows that did not come as dwords: each plane's window of six words filled word by word, the same clamps, into
@@ -613,7 +697,7 @@
                             convert(i, hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]),
                                     hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]));
                         }
-                    } else if (YUVPI) {
+                    } else if (YUVPI || (PK && INTERP)) {
                         /* NV12I's vertical mix, horizontal mix, conversion and pack, the window's samples taken plane by plane */
                         uint32_t vu[6], vv[6];
 #pragma unroll
@@ -796,10 +880,12 @@
                 for (int i = 0; i < 8; i++) {
                     xv[i] = yv[i] = bv[i] = 0.0f; /* edge padding is XYB = 0 (format.c:182-191) */
                     if (i < nvalid) {
+                        /* (packed 4:2:2: a Y every 2 bytes — the pixel stride — and a U and a V every 4, all in row y of the one plane) */
                         const long long off = (long long)y * job.row_stride + (long long)(x0 + i) * (TWO_PLANES ? 1ll : job.pixel_stride);
                         /* (pairs in one plane: the pixel's Y; its U and V sit in chroma row y >> 1 at the even sample x & ~1 and
                          * behind it.  Two planes: in row y >> sy, byte x >> sx of their own planes, whose pitch the pixel stride carries) */
                         const long long offc = TWO_PLANES ? (long long)(y >> csy) * job.pixel_stride + (long long)((x0 + i) >> csx)
+                                               : PK       ? (long long)y * job.row_stride + 4ll * ((x0 + i) >> 1)
                                                : YUV      ? (long long)(y >> 1) * job.row_stride + (long long)((x0 + i) & ~1)
                                                           : off;
                         sample_t sr = ((const sample_t *)job.src[0])[off];

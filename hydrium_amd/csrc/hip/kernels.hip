@@ -617,13 +617,16 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
  * The 8-bit class's planar YCbCr forms, HYDK_STORE_YUVP and HYDK_STORE_YUVPI (three planes, 4:2:0, 4:2:2 and 4:4:4; hydk_chroma.h),
  * are k_transform_tokenize_planar's, for the same reason: "the 8-bit instances" by symbol name stay what they were.
  * The same three planes in 16-bit words, HYDK_STORE_YUVP16 and HYDK_STORE_YUVP16I (hydk_yuvp16.h), are k_transform_tokenize_yuvp16's:
- * a name that holds neither the planar nor the P016 kernel's, so that what is asked of those by name stays theirs. */
+ * a name that holds neither the planar nor the P016 kernel's, so that what is asked of those by name stays theirs.
+ * Packed 4:2:2, HYDK_STORE_YUY2 and HYDK_STORE_YUY2I (YUYV, UYVY, YVYU, VYUY in one plane; hydk_yuy2.h), are k_transform_tokenize_yuy2's,
+ * on the same grounds. */
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
     static_assert(STORE != HYDK_STORE_P016 && STORE != HYDK_STORE_P016I, "the P016 instances are k_transform_tokenize_p016's");
     static_assert(STORE != HYDK_STORE_YUVP && STORE != HYDK_STORE_YUVPI, "the planar instances are k_transform_tokenize_planar's");
     static_assert(STORE != HYDK_STORE_YUVP16 && STORE != HYDK_STORE_YUVP16I, "the 16-bit planar instances are k_transform_tokenize_yuvp16's");
+    static_assert(STORE != HYDK_STORE_YUY2 && STORE != HYDK_STORE_YUY2I, "the packed 4:2:2 instances are k_transform_tokenize_yuy2's");
 #include "k1_transform_body.h"
 }
 
@@ -652,6 +655,15 @@ __global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_yuvp16(const
                                                                            uint2 *part_info, int plog) {
     static_assert(STORE == HYDK_STORE_YUVP16 || STORE == HYDK_STORE_YUVP16I, "P016 and P016I are k_transform_tokenize_p016's");
     constexpr int FMT = HYDK_FMT_U16;
+#include "k1_transform_body.h"
+}
+
+/* Packed 4:2:2 YCbCr, nearest (YUY2) and interpolated (YUY2I), every byte order: four waves per SIMD as the planar instances. */
+template <int XMODE, int STORE>
+__global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_yuy2(const HydkLfJob *__restrict__ jobs, uint32_t *status,
+                                                                         uint2 *part_info, int plog) {
+    static_assert(STORE == HYDK_STORE_YUY2 || STORE == HYDK_STORE_YUY2I, "YUVP and YUVPI are k_transform_tokenize_planar's");
+    constexpr int FMT = HYDK_FMT_U8;
 #include "k1_transform_body.h"
 }
 
@@ -2414,6 +2426,10 @@ static K1Fn k1_of_mode(int fmt, int storage) {
         return k_transform_tokenize_yuvp16<A, HYDK_STORE_YUVP16>;
     case HYDK_STORE_YUVP16I:
         return k_transform_tokenize_yuvp16<A, HYDK_STORE_YUVP16I>;
+    case HYDK_STORE_YUY2:
+        return k_transform_tokenize_yuy2<A, HYDK_STORE_YUY2>;
+    case HYDK_STORE_YUY2I:
+        return k_transform_tokenize_yuy2<A, HYDK_STORE_YUY2I>;
     }
     return fmt == HYDK_FMT_U8    ? k_transform_tokenize<HYDK_FMT_U8, XM>
            : fmt == HYDK_FMT_U16 ? k_transform_tokenize<HYDK_FMT_U16, XM>

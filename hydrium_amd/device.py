@@ -31,7 +31,8 @@ BFLOAT16 = 4
 # sample format = base + matrix + 4 * subsampling + 16 * filter + 64 * depth.  Base 16: a Y plane and a half-resolution plane of
 # (U, V) pairs — NV12 at depth 0, P010 / P012 / P016 (16-bit words, MSB-aligned) at depth 1, 2, 3; base 512: PLANAR, 8 bits in three
 # planes of their own (I420, I422, I444); base 2048: the same three planes in 16-bit words of 10, 12 or 16 bits, LSB-aligned (libyuv's
-# names: I010, I210, I410 ...).  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
+# names: I010, I210, I410 ...); base 8192: PACKED 4:2:2, 8 bits in one plane of Y, U, Y, V groups (YUY2 / UYVY / YVYU / VYUY: the byte order
+# is what the three pointers spell), subsampling and depth 0.  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
 # full (what a JPEG decoder leaves: JFIF).  filter: nearest, or INTERPOLATED for centre-sited chroma (C: JPEG / JFIF, MPEG-1) or
 # left-sited (L: MPEG-2, H.264, HEVC, AV1 default) — csrc/hip/hydk_chroma.h; 4:4:4 has nearest chroma only.
 CHROMA_FILTERS = {"nearest": 0, "centre": 1, "center": 1, "left": 2}
@@ -45,15 +46,15 @@ def ycbcr_fmt(base: int, matrix: int = 0, sub: int = 0, filt: int = 0, depth: in
 
 def ycbcr_fields(fmt: int):
     """(base, matrix, subsampling, filter, depth) of a YCbCr sample format"""
-    base = 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
+    base = 8192 if fmt >= 8192 else 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
     n = int(fmt) - base
     return base, n & 3, (n >> 2) & 3, (n >> 4) & 3, n >> 6
 
 
 _stems = [("NV12", 16, 0, 0)] + [(f"P0{b}", 16, 0, d) for b, d in P016_DEPTHS.items()] + \
     [(f"I{s}", 512, k, 0) for s, k in PLANAR_SUBSAMPLINGS.items()] + \
-    [(f"I{s[2]}{b}", 2048, k, d) for b, d in P016_DEPTHS.items() for s, k in PLANAR_SUBSAMPLINGS.items()]
-for _stem, _base, _sub, _depth in _stems:  # NV12_BT709 = 16 ... I416_BT601_FULL = 2251, as include/hydrium_amd.h has them
+    [(f"I{s[2]}{b}", 2048, k, d) for b, d in P016_DEPTHS.items() for s, k in PLANAR_SUBSAMPLINGS.items()] + [("YUY2", 8192, 0, 0)]
+for _stem, _base, _sub, _depth in _stems:  # NV12_BT709 = 16 ... I416_BT601_FULL = 2251, YUY2_BT709 = 8192 ..., as include/hydrium_amd.h has them
     for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
         for _matrix, _name in enumerate(("BT709", "BT709_FULL", "BT601", "BT601_FULL")):
             if not (_sub == 2 and _filter):
@@ -64,6 +65,9 @@ P010_FORMATS, P012_FORMATS, P016_FORMATS = (tuple(ycbcr_fmt(16, m, 0, 0, d) for 
 P016_FAMILY = tuple(ycbcr_fmt(16, m, 0, f, d) for d in (1, 2, 3) for f in range(3) for m in range(4))
 PLANAR_FAMILY = tuple(ycbcr_fmt(512, m, s, f) for f in range(3) for s in range(3) for m in range(4) if not (s == 2 and f))
 PLANAR16_FAMILY = tuple(ycbcr_fmt(2048, *ycbcr_fields(f)[1:4], d) for d in (1, 2, 3) for f in PLANAR_FAMILY)
+PACKED_FAMILY = tuple(ycbcr_fmt(8192, m, 0, f) for f in range(3) for m in range(4))
+# (U, V) byte offsets from the first Y byte, by byte order (include/hydrium_amd.h: the order is read off the pointers)
+PACKED_ORDERS = {"yuyv": (1, 3), "yuy2": (1, 3), "yvyu": (3, 1), "uyvy": (-1, 1), "vyuy": (1, -1)}
 
 
 def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
@@ -250,6 +254,56 @@ class PlanarYuv(Nv12):
         return [self.y.data_ptr(), self.u.data_ptr(), self.v.data_ptr()]
 
 
+class PackedYuv(Nv12):
+    """A packed 4:2:2 YCbCr picture in device memory — YUY2 (YUYV), UYVY, YVYU or VYUY: one plane of 4-byte groups, two pixels
+    each — accepted wherever an Nv12 object is.  What rocJPEG's native output is for a 4:2:2 JPEG (order "yuyv", matrix
+    NV12_BT601_FULL, chroma "centre").
+
+    ``surface``: 2-D uint8 tensor of H rows with unit element stride, at least 4 * ceil(width / 2) bytes a row; its row stride is
+    the pitch.  ``width``: the picture's width in pixels.  ``matrix``: one of NV12_FORMATS (the matrix and range) — or one of the
+    twelve numbers of PACKED_FAMILY, with ``chroma`` left out; ``order``: "yuyv" (or "yuy2"), "uyvy", "yvyu", "vyuy"; ``chroma``:
+    as Nv12's.  A crop starts on even x: surface[y0:, 2 * x0:]."""
+
+    pixel_stride = 2  # the distance between two Y samples
+
+    def __init__(self, surface, width: int, matrix: int = NV12_BT709, order: str = "yuyv", chroma=None):
+        matrix = int(matrix)
+        if chroma is not None and chroma not in CHROMA_FILTERS:
+            raise ValueError("chroma is 'nearest', 'centre' or 'left'")
+        if matrix in PACKED_FAMILY:
+            if chroma is not None and ycbcr_fields(matrix)[3] != CHROMA_FILTERS[chroma]:
+                raise ValueError("matrix names another chroma filter than chroma does")
+            fmt = matrix
+        elif matrix in NV12_FORMATS:
+            fmt = ycbcr_fmt(8192, ycbcr_fields(matrix)[1], 0, CHROMA_FILTERS[chroma or "nearest"])
+        else:
+            raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL (or a YUY2 format)")
+        if str(order).lower() not in PACKED_ORDERS:
+            raise ValueError("order is 'yuyv', 'uyvy', 'yvyu' or 'vyuy'")
+        name = str(surface.dtype).rpartition(".")[2]
+        if surface.element_size() != 1 or surface.dim() != 2 or name.startswith(("float", "bool")):
+            raise ValueError("a packed 4:2:2 surface is 8-bit: (H, at least 4 * ceil(width / 2)) bytes")
+        h, row = surface.shape
+        width = int(width)
+        if h < 1 or width < 1 or row < 4 * -(-width // 2):
+            raise ValueError("a row of a packed 4:2:2 picture is 4 * ceil(width / 2) bytes")
+        if surface.stride(1) != 1:
+            raise ValueError("a packed 4:2:2 surface has unit element stride")
+        self.surface, self.sample_fmt, self.order = surface, fmt, str(order).lower()
+        self.height, self.width = int(h), width
+        self.pitch = int(surface.stride(0)) if h > 1 else max(int(surface.stride(0)), 4 * -(-width // 2))
+
+    @classmethod
+    def from_surface(cls, *args, **kwargs):
+        raise TypeError("PackedYuv takes its surface")
+
+    def pointers(self):
+        """src[0 ... 2] of the C API: the first Y, U and V byte, all in the first group."""
+        du, dv = PACKED_ORDERS[self.order]
+        y = self.surface.data_ptr() + (1 if du < 0 or dv < 0 else 0)
+        return [y, y + du, y + dv]
+
+
 class PlanarYuv16(PlanarYuv):
     """A planar YCbCr picture of 16-bit words in device memory — I010, I210, I410, I012 ... I416: PlanarYuv's three planes as
     tensors of a 2-byte integer dtype, ``depth`` 10, 12 or 16 significant bits LSB-aligned (bits above the depth are ignored) —
@@ -267,7 +321,7 @@ class PlanarYuv16(PlanarYuv):
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
     float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
-    An Nv12, P016, PlanarYuv or PlanarYuv16 object: its own format."""
+    An Nv12, P016, PlanarYuv, PlanarYuv16 or PackedYuv object: its own format."""
     if isinstance(t, Nv12):
         return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]

@@ -354,8 +354,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever NV12 is, and beside NV12, P010 and RGB pictures in one hydamd_encode_mixed_formats launch group.
  * hydamd_encode_image_multi takes the 12 nearest forms and refuses the 16 interpolated ones as it does NV12's (a 4:2:2 window
  * also crosses into an LF group another shard owns); the host-pointer entry points refuse all 28 with "Invalid Sample Format".
- * Out of scope: NV21 and NV16; packed YUY2 / UYVY / AYUV; U and V planes of different pitches; top-left siting; host-pointer
- * input; cross-shard interpolation.  (I010 and deeper planes: the next section.)
+ * Out of scope: NV21 and NV16; packed AYUV; U and V planes of different pitches; top-left siting; host-pointer
+ * input; cross-shard interpolation.  (I010 and deeper planes: the next section; packed YUY2 / UYVY: the one after it.)
  */
 #define HYDAMD_I420_BT709 512
 #define HYDAMD_I420_BT709_FULL 513
@@ -429,7 +429,8 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * hydamd_encode_image_multi takes the 36 nearest forms and refuses the 48 interpolated ones as it does NV12's; the host-pointer
  * entry points refuse all 84 with "Invalid Sample Format".
  * Out of scope: BT.2020 and PQ / HLG (see the P010 section); MSB-aligned planes with full range at 10 or 12 bits; U and V planes
- * of different pitches; NV16 / NV21, packed YUY2 / UYVY / Y210; top-left siting; host-pointer input; cross-shard interpolation.
+ * of different pitches; NV16 / NV21, packed Y210 / Y216 (8-bit YUY2 / UYVY: the next section); top-left siting; host-pointer input;
+ * cross-shard interpolation.
  */
 #define HYDAMD_I010_BT709 2112
 #define HYDAMD_I010_BT709_FULL 2113
@@ -517,11 +518,60 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
 #define HYDAMD_I216L_BT601_FULL 2279
 
 /*
+ * PACKED 4:2:2 YCbCr DEVICE pixels: YUY2 (YUYV), UYVY, YVYU and VYUY — 8 bits a sample, Y, U and V in ONE plane of 4-byte groups,
+ * two pixels a group.  What rocJPEG's native output is for a 4:2:2 JPEG ("for ROCJPEG_CSS_422 write YUYV (packed) to first
+ * channel"), what capture cards and V4L2 devices deliver and what rocDecode's YUYV surfaces hold.  Read by the transform kernel
+ * as it is, without a planar or RGB copy.
+ *   sample_fmt = 8192 + matrix + 16 * filter
+ * matrix 0..3 and filter 0..2 as in the NV12 family:
+ *                     nearest       centre-sited    left-sited
+ *   HYDAMD_YUY2_*    8192..8195    8208..8211 (C)   8224..8227 (L)
+ * 12 numbers.  The subsampling bits (4 *) are 0: 8196..8207, 8212..8223 and 8228..8239 name nothing; nor does 8240 and up (filter 3,
+ * and 64 * depth, which is left free for Y210 / Y216).  A 4:2:2 JPEG is HYDAMD_YUY2C_BT601_FULL; video is left-sited.
+ *
+ * How such a picture is named — THE BYTE ORDER IS READ OFF THE POINTERS, not off the number:
+ *   src[0]        the first Y byte
+ *   src[1], [2]   the first U and the first V byte, both of the group src[0] lies in:
+ *                 (src[1] - src[0], src[2] - src[0]) = (1, 3) YUYV / YUY2, (3, 1) YVYU, (-1, 1) UYVY, (1, -1) VYUY
+ *   pixel_stride  2, the distance between two Y samples
+ *   row_stride    the pitch of the surface in bytes; may be negative
+ * Anything else is HYD_API_ERROR "YUY2/UYVY wants pixel_stride 2 and U and V in the bytes beside Y", nothing enqueued.
+ * A row is 4 * ceil(W / 2) bytes: for odd W the last group's second Y byte belongs to the row, may be read and is no pixel.
+ * Nothing outside those bytes of rows 0 .. H - 1 is ever read.  The library finds an LF group, tile or shard at pixel (x0, y0)
+ * by adding y0 * row_stride + 2 * x0 to ALL THREE pointers; a caller's own crop must start on even x0.
+ *
+ * The picture is the HYDAMD_I422* picture whose planes are the de-interleaved bytes: Y[y][x] is the byte at 2 x from src[0] in
+ * row y, U[y][cx] and V[y][cx] the bytes at 4 cx from src[1] and src[2], cw = ceil(W / 2).  Nearest chroma and the centre- and
+ * left-sited horizontal taps are the planar section's, the conversion and its 0.51 bound the NV12 section's.  Clamping is at the
+ * edges of the PICTURE: chroma is continuous across LF groups and tiles, hydamd_encode_lf_group_at carries the picture, and plain
+ * hydamd_encode_lf_group treats the LF group as a picture of its own.  The file is byte for byte what the reference writes for the
+ * HYD_UINT8 picture this produces, and so what this library writes for the same planes given as HYDAMD_I422*.
+ *
+ * Accepted wherever NV12 is, and beside every other family — and pictures of different byte orders — in one
+ * hydamd_encode_mixed_formats launch group.  hydamd_encode_image_multi takes the 4 nearest forms and refuses the 8 interpolated
+ * ones as it does I422C / I422L; the host-pointer entry points refuse all 12 with "Invalid Sample Format".
+ * Out of scope: Y210 / Y216 and AYUV / Y410 (the depth bits are reserved for them); 4:4:0 planes, rocJPEG's other native form
+ * (subsampling 3 of the planar family names nothing); host-pointer input; cross-shard interpolation.
+ */
+#define HYDAMD_YUY2_BT709 8192
+#define HYDAMD_YUY2_BT709_FULL 8193
+#define HYDAMD_YUY2_BT601 8194
+#define HYDAMD_YUY2_BT601_FULL 8195
+#define HYDAMD_YUY2C_BT709 8208
+#define HYDAMD_YUY2C_BT709_FULL 8209
+#define HYDAMD_YUY2C_BT601 8210
+#define HYDAMD_YUY2C_BT601_FULL 8211
+#define HYDAMD_YUY2L_BT709 8224
+#define HYDAMD_YUY2L_BT709_FULL 8225
+#define HYDAMD_YUY2L_BT601 8226
+#define HYDAMD_YUY2L_BT601_FULL 8227
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_* or HYDAMD_Ixnn_* formats (whose src and strides are
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_* or HYDAMD_YUY2_* formats (whose src and strides are
  * described above).  With an interpolating format (HYDAMD_NV12C_*, HYDAMD_NV12L_*, their P01x and I42x forms) the LF group is a
  * picture of its own: its chroma clamps at its own edges.
  */
