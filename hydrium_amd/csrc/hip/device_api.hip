@@ -345,7 +345,10 @@ static_assert(hyd_fmt_describe(HYDAMD_NV12_BT709).bits == 8 && hyd_fmt_describe(
               "a depth's significant bits; three filters and three deeper depths, as hyd_fmt_describe has them");
 static_assert(HYDAMD_FMT_FILTERS(YUY2, HYD_LAYOUT_PACKED, 0, HYDK_PLANAR_422) && HYDAMD_YUY2_BT709 == HYD_FMT_BASE_PACKED,
               "packed 4:2:2: 8192 + the kernels' matrix index + 16 * the kernels' chroma filter");
-static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_FORMS == 15, "the job did not grow; launch_transform's mask has 15 bits");
+static_assert(HYDAMD_FMT_FILTERS(Y210, HYD_LAYOUT_PACKED, HYDK_YUV16_P010, HYDK_PLANAR_422) && HYDAMD_FMT_FILTERS(Y212, HYD_LAYOUT_PACKED, HYDK_YUV16_P012, HYDK_PLANAR_422) &&
+                  HYDAMD_FMT_FILTERS(Y216, HYD_LAYOUT_PACKED, HYDK_YUV16_P016, HYDK_PLANAR_422) && HYDAMD_Y210_BT709 == HYD_FMT_BASE_PACKED16 + 64,
+              "packed 4:2:2 of 16-bit words: 32768 + the kernels' matrix index + 16 * the kernels' chroma filter + 64 * the kernels' depth");
+static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_FORMS == 17, "the job did not grow; launch_transform's mask has 17 bits");
 #undef HYDAMD_FMT_PLANES
 #undef HYDAMD_FMT_FILTERS
 #undef HYDAMD_FMT_STEM
@@ -458,8 +461,8 @@ int record_lf_group(HydAmdContext *ctx, int slot, const void *const src[3], ptrd
     job.matrix = form.matrix;
     job.filter = form.filter;
     job.sub = form.sub;
-    if (hyd_fmt_describe(sample_fmt).layout == HYD_LAYOUT_PACKED) /* the byte order, which the pointers name and the number does not */
-        job.sub = (uint32_t)hyd_fmt_packed_order(src);
+    if (hyd_fmt_describe(sample_fmt).layout == HYD_LAYOUT_PACKED) /* the byte or word order, which the pointers name and the number does not */
+        job.sub = (uint32_t)hyd_fmt_packed_order(src, hyd_fmt_describe(sample_fmt).bytes);
     if (hydk_store_form((int)form.storage).interp) {
         /* the picture's chroma plane (each plane's, in its own units) and where src[1] (and src[2]) point in it: all the kernel
          * may read around this LF group */
@@ -3014,6 +3017,55 @@ __attribute__((visibility("default"))) int hydt_packed_to_rgb_device(int device,
     return probe_round_trip(surface, 4 * (size_t)((width + 1) >> 1) * height, rgb, 3 * n, [&](void *d_in, void *d_out) {
         hipLaunchKernelGGL(k_packed_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, order, filter, matrix, (const uint8_t *)d_in,
                            (uint8_t *)d_out, width, height);
+    });
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the definition of packed 4:2:2 in 16-bit words (hydk_y216_pixel,
+ * hydk_y216.h) as the host compiler built it and as the device runs it.  order, filter as hydt_packed_to_rgb_host's; depth
+ * HYDK_YUV16_P010 ... _P016; matrix HYDK_YUV_*; surface: height rows of 4 * ceil(width / 2) words, tightly packed; rgb receives
+ * height rows of width (R, G, B) word triples. */
+static bool packed16_probe_args(int order, int filter, int depth, int matrix, const uint16_t *surface, uint16_t *rgb, int width, int height) {
+    return packed_probe_args(order, filter, matrix, (const uint8_t *)surface, (uint8_t *)rgb, width, height) && depth >= HYDK_YUV16_P010 &&
+           depth <= HYDK_YUV16_P016;
+}
+__host__ __device__ static inline void packed16_probe_pixel(int order, int filter, int depth, int matrix, const uint16_t *surface, uint16_t *rgb,
+                                                            int width, size_t i) {
+    /* the three pointers a caller of that word order gives: Y, U, V of the first group */
+    const int yo = hydk_yuy2_y_offset(order), c0 = 1 - yo, c1 = 3 - yo;
+    const uint16_t *yp = surface + yo, *up = surface + (hydk_yuy2_v_first(order) ? c1 : c0), *vp = surface + (hydk_yuy2_v_first(order) ? c0 : c1);
+    uint32_t out[3];
+    hydk_y216_pixel(filter, depth, matrix, yp, up, vp, 4ll * ((width + 1) >> 1), width, (int)(i % (size_t)width), (int)(i / (size_t)width), out);
+    for (int c = 0; c < 3; c++)
+        rgb[3 * i + c] = (uint16_t)out[c];
+}
+
+__attribute__((visibility("default"))) int hydt_packed16_to_rgb_host(int order, int filter, int depth, int matrix, const uint16_t *surface,
+                                                                     uint16_t *rgb, int width, int height) {
+    if (!packed16_probe_args(order, filter, depth, matrix, surface, rgb, width, height))
+        return ST_API_ERROR;
+    for (size_t i = 0; i < (size_t)width * height; i++)
+        packed16_probe_pixel(order, filter, depth, matrix, surface, rgb, width, i);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_packed16_to_rgb_probe(int order, int filter, int depth, int matrix, const uint16_t *surface, uint16_t *rgb,
+                                                               int width, int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i < (size_t)width * height)
+        packed16_probe_pixel(order, filter, depth, matrix, surface, rgb, width, i);
+}
+} /* namespace */
+
+/* one launch over the picture (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_packed16_to_rgb_device(int device, int order, int filter, int depth, int matrix,
+                                                                       const uint16_t *surface, uint16_t *rgb, int width, int height) {
+    if (!packed16_probe_args(order, filter, depth, matrix, surface, rgb, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height;
+    return probe_round_trip(surface, 8 * (size_t)((width + 1) >> 1) * height, rgb, 6 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_packed16_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, order, filter, depth, matrix, (const uint16_t *)d_in,
+                           (uint16_t *)d_out, width, height);
     });
 }
 

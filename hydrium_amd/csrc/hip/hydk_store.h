@@ -35,7 +35,9 @@
 #define HYDK_STORE_YUVP16I 10
 #define HYDK_STORE_YUY2 11  /* 8-bit class: packed 4:2:2 — Y, U and V bytes in one plane, HydkLfJob.sub the byte order (HYD_PACKED_*; hydk_yuy2.h) */
 #define HYDK_STORE_YUY2I 12
-#define HYDK_STORE_FORMS 13
+#define HYDK_STORE_Y216 13  /* 16-bit class: the same groups in 16-bit words, MSB-aligned — Y210 / Y212 / Y216, HydkLfJob.sub the word order (hydk_y216.h) */
+#define HYDK_STORE_Y216I 14
+#define HYDK_STORE_FORMS 15
 
 /* HydkLfJob.use_luts of a YCbCr job is the XYB mode + its form's variant bit: the RGB instances' own test turns it away */
 #define HYDK_VARIANT_NV12 8
@@ -48,12 +50,14 @@
 #define HYDK_VARIANT_YUVP16I 1024
 #define HYDK_VARIANT_YUY2 2048
 #define HYDK_VARIANT_YUY2I 4096
+#define HYDK_VARIANT_Y216 8192
+#define HYDK_VARIANT_Y216I 16384
 
 typedef struct HydkStoreForm {
     int cls;           /* HYDK_FMT_*; form 0 belongs to every class */
     int ycbcr;         /* a pixel is converted to RGB of its class right after the load */
     int bits;          /* of a stored sample */
-    int chroma_planes; /* YCbCr: 1 — (U, V) pairs interleaved in one plane; 2 — a plane each; 0 — none: U and V sit among the Y bytes */
+    int chroma_planes; /* YCbCr: 1 — (U, V) pairs interleaved in one plane; 2 — a plane each; 0 — none: U and V sit among the Y samples */
     int interp;        /* chroma interpolated: the job carries filter and the picture (pic_*) */
     int variant;       /* HYDK_VARIANT_* */
 } HydkStoreForm;
@@ -73,6 +77,8 @@ HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
         {HYDK_FMT_U16, 1, 16, 2, 1, HYDK_VARIANT_YUVP16I},
         {HYDK_FMT_U8, 1, 8, 0, 0, HYDK_VARIANT_YUY2},
         {HYDK_FMT_U8, 1, 8, 0, 1, HYDK_VARIANT_YUY2I},
+        {HYDK_FMT_U16, 1, 16, 0, 0, HYDK_VARIANT_Y216},
+        {HYDK_FMT_U16, 1, 16, 0, 1, HYDK_VARIANT_Y216I},
     };
     return forms[storage >= 0 && storage < HYDK_STORE_FORMS ? storage : 0];
 }
@@ -91,7 +97,7 @@ static inline HydkSampleForm hydk_decode_fmt(int f) {
     const HydFmt fmt = hyd_fmt_describe(f);
     HydkSampleForm d = {fmt.device, 0, 0, (uint32_t)(fmt.matrix + 4 * fmt.depth), (uint32_t)fmt.filter, (uint32_t)fmt.sub, fmt.sx, fmt.sy};
     if (fmt.layout == HYD_LAYOUT_PACKED)
-        d.storage = (uint32_t)(HYDK_STORE_YUY2 + (fmt.filter != 0));
+        d.storage = (uint32_t)((fmt.bytes == 2 ? HYDK_STORE_Y216 : HYDK_STORE_YUY2) + (fmt.filter != 0));
     else if (fmt.layout != HYD_LAYOUT_RGB) /* the YCbCr forms in the table's order: pairs then planes, bytes then words, nearest then interpolated */
         d.storage = (uint32_t)(HYDK_STORE_NV12 + 4 * (fmt.layout == HYD_LAYOUT_PLANES) + 2 * (fmt.bytes == 2) + (fmt.filter != 0));
     else if (f == HYD_FMT_FLOAT16 || f == HYD_FMT_BFLOAT16)
@@ -106,7 +112,8 @@ static inline int hydk_encode_fmt(HydkSampleForm d) {
     if (!form.ycbcr)
         return d.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : d.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : d.cls;
     if (form.chroma_planes == 0) /* (sub: the byte order in a job, 4:2:2 in a decoded format; neither is in the number) */
-        return HYD_FMT_BASE_PACKED + (int)(d.matrix & 3u) + 16 * (int)d.filter;
+        return form.bits == 16 ? HYD_FMT_BASE_PACKED16 + (int)(d.matrix & 3u) + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2)
+                               : HYD_FMT_BASE_PACKED + (int)(d.matrix & 3u) + 16 * (int)d.filter;
     const int base = form.chroma_planes == 1 ? HYD_FMT_BASE_PAIRS : form.bits == 16 ? HYD_FMT_BASE_PLANES16 : HYD_FMT_BASE_PLANES;
     return base + (int)(d.matrix & 3u) + 4 * (int)d.sub + 16 * (int)d.filter + 64 * (int)(d.matrix >> 2);
 }

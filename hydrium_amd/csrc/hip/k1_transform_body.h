@@ -1,18 +1,19 @@
 /*
  * k1_transform_body.h — the body of the transform kernel (kernels.hip, K1), included into k_transform_tokenize, into
- * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16 and into k_transform_tokenize_yuy2 and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
+ * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16, into k_transform_tokenize_yuy2 and into k_transform_tokenize_y216 and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
  * and STORE, the kernel's parameters jobs, status, part_info and plog, and everything kernels.hip defines above its K1 section.
  * No include guard: it is function-body text, meant to be included once per kernel.
  */
     /* What STORE is made of (hydk_store.h).  YUV: a YCbCr form — a pixel becomes an RGB pixel of its class right after the load.
      * TWO_PLANES: U and V in planes of their own, whose pitch is job.pixel_stride, subsampled as job.sub says (planar YCbCr);
      * else (U, V) pairs in one half-resolution plane of the Y plane's pitch (NV12; P010 / P012 / P016 in 16-bit words).
-     * PK: no chroma plane at all — packed 4:2:2, U and V among the Y bytes of one plane in the byte order job.sub names (hydk_yuy2.h).
+     * PK: no chroma plane at all — packed 4:2:2, U and V among the Y bytes of one plane in the byte order job.sub names (hydk_yuy2.h),
+     * or among the Y words of one plane of 16-bit words (hydk_y216.h).
      * INTERP: chroma interpolated (hydk_chroma.h) — job.filter says centre- or left-sited, and the job knows the picture it is
      * cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it.  HALF: 2-byte floats, widened on load */
     constexpr HydkStoreForm FORM = hydk_store_form(STORE);
     static_assert(STORE == HYDK_STORE_F32 || FORM.cls == FMT,
-                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16 and YUVP16I");
+                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16, YUVP16I, Y216 and Y216I");
     constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, PK = YUV && FORM.chroma_planes == 0, INTERP = FORM.interp;
     constexpr bool HALF = FMT == HYDK_FMT_F32 && STORE != HYDK_STORE_F32;
     /* the two-plane forms by name: YUVPI keeps a prefetch, an edge fill and an interpolate loop of its own (through the shared
@@ -20,6 +21,8 @@
     constexpr bool YUVP = TWO_PLANES && !INTERP && FMT == HYDK_FMT_U8, YUVPI = TWO_PLANES && INTERP && FMT == HYDK_FMT_U8;
     /* the two-plane forms of 16-bit words, nearest and interpolated: windows of their own beside the 8-bit ones (hydk_yuvp16.h) */
     constexpr bool YP16 = TWO_PLANES && FMT == HYDK_FMT_U16;
+    /* packed 4:2:2 by sample size: bytes (YUY2, YUY2I) unpack into YUVP's and YUVPI's registers, words (Y216, Y216I) into YP16's */
+    constexpr bool PK8 = PK && FMT == HYDK_FMT_U8, PK16 = PK && FMT == HYDK_FMT_U16;
     typedef typename std::conditional<HALF, uint16_t, typename SampleOf<FMT>::type>::type sample_t;
     constexpr bool LUTS = XMODE == kXybGather;
     constexpr int kWords = FMT == HYDK_FMT_U8 ? 6 : 12; /* dwords holding 8 packed RGB pixels */
@@ -156,9 +159,13 @@
                       (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)(job.row_stride * (SB / 8))) & 3) == 0;
     /* packed 4:2:2 (pkrun): a block row is four GROUPS — 16 bytes, four dwords — from the row's one plane, when the first group (Y's
      * place in its pair of bytes before src[0]) and the pitch are dword multiples; Y and the four (U, V) pairs are picked out of the
-     * registers at use, by the byte order (wave-uniform).  pk_y: 0 — Y is the first byte of a pair, 1 — the second; pk_vu: V before U */
+     * registers at use, by the byte order (wave-uniform).  pk_y: 0 — Y is the first byte of a pair, 1 — the second; pk_vu: V before U.
+     * 16-bit words (PK16): the four groups are 32 bytes, EIGHT DWORDS, under the same test with the pitch in bytes.  The test asks for
+     * dword multiples and no more, as every other form's does: a crop at an odd group, or a pitch of an even number of words that
+     * is no multiple of eight, keeps the dword and would lose 16 bytes.  The eight dword loads of one address are fused by the
+     * compiler into two global_load_dwordx4, which the hardware takes at dword alignment */
     const int pk_y = PK ? hydk_yuy2_y_offset((int)job.sub) : 0, pk_vu = PK ? hydk_yuy2_v_first((int)job.sub) : 0;
-    const bool pkrun = PK && ((((uintptr_t)job.src[0] - (uintptr_t)pk_y) | (uintptr_t)job.row_stride) & 3) == 0;
+    const bool pkrun = PK && ((((uintptr_t)job.src[0] - (uintptr_t)(pk_y * (SB / 8))) | (uintptr_t)(job.row_stride * (SB / 8))) & 3) == 0;
     /* two planes (ylrun): two dwords of Y and, from each chroma plane, the dword of four samples that serves its eight pixels
      * (the block's chroma column is a multiple of 4) — two dwords of eight for 4:4:4.  16-bit words (YP16): four dwords of Y and
      * two from each chroma plane — four for 4:4:4, kWords in all — where the three bases and both pitches IN BYTES are dword
@@ -200,11 +207,11 @@
      * sample a pixel) byte i of the two dwords a plane at nxt[2 + 2 c].  YP16: word i >> 1, or (4:4:4) word i, of the dwords at
      * nxt[4 + 4 c] */
     auto near_get = [&](int c, int i) -> uint32_t {
-        if (PK) /* (unpacked at use into YUVP's 4:2:2 places: four U bytes in nxt[2], four V bytes in nxt[3]) */
+        if (PK8) /* (unpacked at use into YUVP's 4:2:2 places: four U bytes in nxt[2], four V bytes in nxt[3]) */
             return (nxt[2 + c] >> (8 * (i >> 1))) & 0xFF;
-        if (!TWO_PLANES)
+        if (!TWO_PLANES && !PK16)
             return win_get(c, 0, 1 + (i >> 1));
-        if (YP16) {
+        if (YP16 || PK16) { /* (PK16: unpacked at use into YP16's 4:2:2 places, csx = 1) */
             const uint32_t s2 = (nxt[4 + 4 * c + (i >> 2)] >> (16 * ((i >> 1) & 1))) & 0xFFFF, s4 = (nxt[4 + 4 * c + (i >> 1)] >> (16 * (i & 1))) & 0xFFFF;
             return csx ? s2 : s4;
         }
@@ -217,7 +224,31 @@
         return (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
     };
     auto prefetch = [&](int s) {
-        if (PK) {
+        if (PK16) {
+            /* the four groups as stored in nxt[0 ... 7]; interpolated: the group behind them in nxt[8], nxt[9] and (centre-sited) the
+             * one before them in nxt[10], nxt[11], whole dwords too: irun says that both lie inside the picture's row */
+            if (fast && s * 8 + ar < gh) {
+                /* (the lane's row and block pass through an empty statement, as YP16's do and for its reason: the address is made
+                 * anew for every strip and not carried as a 64-bit pointer, which cost the nearest instances their last register) */
+                int lane_row = ar, lane_block = ab;
+                asm volatile("" : "+v"(lane_row), "+v"(lane_block));
+                const long long y = py0 + s * 8 + lane_row, x = px0 + lane_block * 8;
+                const char *pg = (const char *)job.src[0] + (y * job.row_stride + 2 * x - pk_y) * 2;
+#pragma unroll
+                for (int k = 0; k < 8; k++)
+                    nxt[k] = HYDK_GLOBAL(const uint32_t, pg)[k];
+                if (INTERP) {
+                    const bool centre = job.filter == HYDK_CHROMA_CENTRE; /* (left-sited chroma never looks before) */
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        nxt[8 + k] = HYDK_GLOBAL(const uint32_t, pg)[8 + k];
+                        nxt[10 + k] = centre ? HYDK_GLOBAL(const uint32_t, pg - 8)[k] : 0u;
+                    }
+                }
+            }
+            return;
+        }
+        if (PK8) {
             /* the four groups as stored in nxt[0 ... 3]; interpolated: the group behind them in flank[1] and (centre-sited) the one
              * before them in flank[0], whole dwords too: irun says that both lie inside the picture's row */
             if (fast && s * 8 + ar < gh) {
@@ -471,7 +502,7 @@
                     }
                 }
                 prefetch(s + 1);
-            } else if (fast || INTERP) {
+            } else if (fast || INTERP || PK16) { /* (PK16: nearest rows that did not come as dwords fill the window too) */
                 const int nvalid = row_ok ? min(8, gw - ab * 8) : 0;
                 /* Interpolated rows that did not come as dwords — the picture's first and last chroma columns, a ragged last
                  * block, shifted bases, odd pitches — fill the same window sample by sample, here, every column clamped to the
@@ -554,7 +585,7 @@
                  * below is YUVPI's.  Rows that did not come as dwords (a base or pitch off the dword, the picture's first and last
                  * chroma column, a ragged last block) fill the same window byte by byte with the clamps: group col of the picture's
                  * row lies 4 (col - pic_cx0) bytes from src[1] and src[2]. */
-                if (PK && fast) {
+                if (PK8 && fast) {
                     const uint32_t even = 0x06040200u, odd = 0x07050301u;
                     const uint32_t sel_y = pk_y ? odd : even, sel_c = pk_y ? even : odd;
                     const uint32_t ca = __builtin_amdgcn_perm(nxt[1], nxt[0], sel_c), cb = __builtin_amdgcn_perm(nxt[3], nxt[2], sel_c);
@@ -577,7 +608,7 @@
                         flank[1] = fv | fv << 16;
                     }
                 }
-                if (PK && INTERP && !fast) {
+                if (PK8 && INTERP && !fast) {
 #pragma unroll
                     for (int k = 0; k < kWords; k++)
                         nxt[k] = 0;
@@ -604,6 +635,81 @@
                         }
                         nxt[3] = nxt[2];
                         nxt[5] = nxt[4];
+                    }
+                }
+                /* Packed 4:2:2 of 16-bit words.  Dword rows: the four groups become YP16's 4:2:2 window — eight Y words in nxt[0 ... 3],
+                 * four U words in nxt[4], nxt[5], four V words in nxt[8], nxt[9] — by 16-bit permutes whose selectors are the word
+                 * order's (uniform over the wavefront): of a group's two dwords the low halves are the Y samples of Y210's own order
+                 * and the chroma of the orders with Y second, the high halves the other; then the same split tells the first chroma
+                 * component from the second.  Interpolated: columns 0 and 5 (the groups before and behind) go to flank[] as YP16I has
+                 * them, column 0 | column 5 << 16 of U in flank[0], of V in flank[2].  Rows that did not come as dwords (a first
+                 * group or pitch off the dword, the picture's first and last chroma column, a ragged last block) fill the same
+                 * window word by word with the clamps: group col of the picture's row lies 4 (col - pic_cx0) words from src[1] and
+                 * src[2].  Nearest rows take that way too (the per-sample loop at the end is never theirs: with it the nearest
+                 * instances needed a 129th register).  Either way the far row is the near row, as 4:2:2 has it, and the words count as stored: no shift. */
+                if (PK16 && fast) {
+                    const uint32_t low = 0x05040100u, high = 0x07060302u;
+                    const uint32_t sel_y = pk_y ? high : low, sel_c = pk_y ? low : high;
+                    const uint32_t sel_u = pk_vu ? high : low, sel_v = pk_vu ? low : high;
+                    uint32_t yd[4], cd[4]; /* per group: its two Y words; its first | second << 16 chroma word */
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        yd[k] = __builtin_amdgcn_perm(nxt[2 * k + 1], nxt[2 * k], sel_y);
+                        cd[k] = __builtin_amdgcn_perm(nxt[2 * k + 1], nxt[2 * k], sel_c);
+                    }
+                    if (INTERP) {
+                        constexpr int kB = PK16 ? 8 : 0; /* (PK16 has twelve dwords; an index every other form can hold, for its compile) */
+                        const uint32_t behind = __builtin_amdgcn_perm(nxt[kB + 1], nxt[kB], sel_c), before = __builtin_amdgcn_perm(nxt[kB + 3], nxt[kB + 2], sel_c);
+                        flank[0] = __builtin_amdgcn_perm(behind, before, sel_u);
+                        flank[2] = __builtin_amdgcn_perm(behind, before, sel_v);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        nxt[k] = yd[k];
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        nxt[4 + k] = __builtin_amdgcn_perm(cd[2 * k + 1], cd[2 * k], sel_u);
+                        nxt[8 + k] = __builtin_amdgcn_perm(cd[2 * k + 1], cd[2 * k], sel_v);
+                    }
+                }
+                if (PK16 && !fast) {
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        nxt[k] = 0;
+#pragma unroll
+                    for (int k = 0; k < kFlank; k++)
+                        flank[k] = 0;
+                    if (row_ok) {
+                        const uint16_t *py = (const uint16_t *)job.src[0] + (long long)y * job.row_stride + 2ll * x0;
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            if (i < nvalid)
+                                nxt[i >> 1] |= (uint32_t)py[2 * i] << (16 * (i & 1));
+                        const long long on = (long long)y * job.row_stride;
+                        const uint16_t *un = (const uint16_t *)job.src[1] + on, *vn = (const uint16_t *)job.src[2] + on;
+#pragma unroll
+                        for (int p = 0; p < 6; p++) {
+                            /* nearest: a pixel's own group, columns 1 ... 4 as far as the row has pixels; the job carries no picture */
+                            if (!INTERP && (p == 0 || p == 5 || 2 * (p - 1) >= nvalid))
+                                continue;
+                            const int col = INTERP ? min(max(pcx - 1 + p, 0), job.pic_cw - 1) - job.pic_cx0 : (x0 >> 1) + p - 1;
+                            const uint32_t a = un[4 * col], c = vn[4 * col];
+                            if (p == 0 || p == 5) {
+                                flank[0] |= a << (p ? 16 : 0);
+                                flank[2] |= c << (p ? 16 : 0);
+                            } else {
+                                nxt[4 + ((p - 1) >> 1)] |= a << (16 * ((p - 1) & 1));
+                                nxt[8 + ((p - 1) >> 1)] |= c << (16 * ((p - 1) & 1));
+                            }
+                        }
+                    }
+                }
+                if (PK16 && INTERP) {
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        nxt[6 + k] = nxt[4 + k];
+                        nxt[10 + k] = nxt[8 + k];
+                        flank[1 + 2 * k] = flank[2 * k];
                     }
                 }
                 /* YP16 rows that did not come as dwords: each plane's window of six words filled word by word, the same clamps, into
@@ -677,7 +783,7 @@
                             cvt[si / kSPD] |= rgb[ch] << (SB * (si % kSPD));
                         }
                     };
-                    if (YP16 && INTERP) {
+                    if ((YP16 || PK16) && INTERP) {
                         /* the same two mixes, the window's words taken plane by plane */
                         uint32_t vu[6], vv[6];
 #pragma unroll
@@ -697,7 +803,7 @@
                             convert(i, hydk_chroma_hmix(filter, i & 1, vu[j], filter == HYDK_CHROMA_CENTRE ? vu[hc] : vu[hl]),
                                     hydk_chroma_hmix(filter, i & 1, vv[j], filter == HYDK_CHROMA_CENTRE ? vv[hc] : vv[hl]));
                         }
-                    } else if (YUVPI || (PK && INTERP)) {
+                    } else if (YUVPI || (PK8 && INTERP)) {
                         /* NV12I's vertical mix, horizontal mix, conversion and pack, the window's samples taken plane by plane */
                         uint32_t vu[6], vv[6];
 #pragma unroll
@@ -860,7 +966,7 @@
                         row_to_xyb(std::integral_constant<int, kCurveNone>());
                     else
                         row_to_xyb(std::integral_constant<int, kCurveBoth>());
-                    if (INTERP) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
+                    if (INTERP || PK16) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
 #pragma unroll
                         for (int i = 0; i < 8; i++)
                             if (i >= nvalid)
@@ -880,7 +986,7 @@
                 for (int i = 0; i < 8; i++) {
                     xv[i] = yv[i] = bv[i] = 0.0f; /* edge padding is XYB = 0 (format.c:182-191) */
                     if (i < nvalid) {
-                        /* (packed 4:2:2: a Y every 2 bytes — the pixel stride — and a U and a V every 4, all in row y of the one plane) */
+                        /* (packed 4:2:2: a Y every 2 samples — the pixel stride — and a U and a V every 4, all in row y of the one plane) */
                         const long long off = (long long)y * job.row_stride + (long long)(x0 + i) * (TWO_PLANES ? 1ll : job.pixel_stride);
                         /* (pairs in one plane: the pixel's Y; its U and V sit in chroma row y >> 1 at the even sample x & ~1 and
                          * behind it.  Two planes: in row y >> sy, byte x >> sx of their own planes, whose pitch the pixel stride carries) */

@@ -619,7 +619,8 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
  * The same three planes in 16-bit words, HYDK_STORE_YUVP16 and HYDK_STORE_YUVP16I (hydk_yuvp16.h), are k_transform_tokenize_yuvp16's:
  * a name that holds neither the planar nor the P016 kernel's, so that what is asked of those by name stays theirs.
  * Packed 4:2:2, HYDK_STORE_YUY2 and HYDK_STORE_YUY2I (YUYV, UYVY, YVYU, VYUY in one plane; hydk_yuy2.h), are k_transform_tokenize_yuy2's,
- * on the same grounds. */
+ * on the same grounds; and the same groups in 16-bit words, HYDK_STORE_Y216 and HYDK_STORE_Y216I (Y210, Y212, Y216; hydk_y216.h), are
+ * k_transform_tokenize_y216's. */
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
@@ -627,6 +628,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     static_assert(STORE != HYDK_STORE_YUVP && STORE != HYDK_STORE_YUVPI, "the planar instances are k_transform_tokenize_planar's");
     static_assert(STORE != HYDK_STORE_YUVP16 && STORE != HYDK_STORE_YUVP16I, "the 16-bit planar instances are k_transform_tokenize_yuvp16's");
     static_assert(STORE != HYDK_STORE_YUY2 && STORE != HYDK_STORE_YUY2I, "the packed 4:2:2 instances are k_transform_tokenize_yuy2's");
+    static_assert(STORE != HYDK_STORE_Y216 && STORE != HYDK_STORE_Y216I, "the packed 4:2:2 instances of 16-bit words are k_transform_tokenize_y216's");
 #include "k1_transform_body.h"
 }
 
@@ -664,6 +666,16 @@ __global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_yuy2(const H
                                                                          uint2 *part_info, int plog) {
     static_assert(STORE == HYDK_STORE_YUY2 || STORE == HYDK_STORE_YUY2I, "YUVP and YUVPI are k_transform_tokenize_planar's");
     constexpr int FMT = HYDK_FMT_U8;
+#include "k1_transform_body.h"
+}
+
+/* Packed 4:2:2 YCbCr of 16-bit words, nearest (Y216) and interpolated (Y216I), every depth and word order: four waves per SIMD
+ * as the byte instances. */
+template <int XMODE, int STORE>
+__global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_y216(const HydkLfJob *__restrict__ jobs, uint32_t *status,
+                                                                         uint2 *part_info, int plog) {
+    static_assert(STORE == HYDK_STORE_Y216 || STORE == HYDK_STORE_Y216I, "YUY2 and YUY2I are k_transform_tokenize_yuy2's");
+    constexpr int FMT = HYDK_FMT_U16;
 #include "k1_transform_body.h"
 }
 
@@ -2430,6 +2442,10 @@ static K1Fn k1_of_mode(int fmt, int storage) {
         return k_transform_tokenize_yuy2<A, HYDK_STORE_YUY2>;
     case HYDK_STORE_YUY2I:
         return k_transform_tokenize_yuy2<A, HYDK_STORE_YUY2I>;
+    case HYDK_STORE_Y216:
+        return k_transform_tokenize_y216<A, HYDK_STORE_Y216>;
+    case HYDK_STORE_Y216I:
+        return k_transform_tokenize_y216<A, HYDK_STORE_Y216I>;
     }
     return fmt == HYDK_FMT_U8    ? k_transform_tokenize<HYDK_FMT_U8, XM>
            : fmt == HYDK_FMT_U16 ? k_transform_tokenize<HYDK_FMT_U16, XM>

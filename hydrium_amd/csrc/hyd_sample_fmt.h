@@ -36,12 +36,20 @@
  * class.  All three addresses sit on 2-byte boundaries (HYD_FMT_PLANAR16_ALIGN_MSG).
  *
  * 8192 ... 8227 name PACKED 4:2:2 YCbCr in device memory (YUY2 / YUYV, UYVY, YVYU, VYUY): sample format = 8192 + matrix + 16 * filter,
- * the subsampling bits 0 and no depth (64 * depth is left free for Y210 / Y216).  One plane of 4-byte groups, each two pixels: two Y
+ * the subsampling bits 0 and no depth (8192 + 64 * depth names nothing: deeper packed words are at 32768).  One plane of 4-byte groups, each two pixels: two Y
  * bytes, a U and a V.  THE BYTE ORDER IS READ OFF THE POINTERS, not off the number: src[0] is the first Y byte, src[1] and src[2]
  * the U and the V byte of the same group — (src[1] - src[0], src[2] - src[0]) is (1, 3) YUYV, (3, 1) YVYU, (-1, 1) UYVY or
  * (1, -1) VYUY; the pixel stride is 2, the distance of two Y samples, and the row stride the pitch in bytes, of either sign
  * (HYD_FMT_PACKED_LAYOUT_MSG).  A storage form of the 8-BIT class; the picture is the I422 picture of the de-interleaved bytes
  * (hip/hydk_yuy2.h).
+ *
+ * 32832 ... 32995 name PACKED 4:2:2 YCbCr OF 16-BIT WORDS in device memory (Y210, Y212, Y216): sample format = 32768 + matrix +
+ * 16 * filter + 64 * depth, depth 1, 2, 3 = 10, 12 or 16 significant bits, MSB-ALIGNED as P010's are and counted as stored; the
+ * subsampling bits are 0 and depth 0 (32768 ... 32831) names nothing.  One plane of groups of four words, each two pixels: two Y
+ * words, a U and a V.  THE WORD ORDER IS READ OFF THE POINTERS as the byte order of YUY2 is, with the differences in WORDS:
+ * (1, 3) Y210's own order, (3, 1), (-1, 1) or (1, -1); the pixel stride is 2, the row stride the pitch in words, of either sign,
+ * and all three addresses sit on 2-byte boundaries (HYD_FMT_PACKED16_LAYOUT_MSG).  A storage form of the 16-BIT class; the picture
+ * is the 4:2:2 picture of the de-interleaved words under the P01x conversion of that depth (hip/hydk_y216.h).
  */
 #ifndef HYD_SAMPLE_FMT_H_
 #define HYD_SAMPLE_FMT_H_
@@ -57,16 +65,18 @@
 
 /* THE RULE: a YCbCr sample format = base + matrix + 4 * subsampling + 16 * filter + 64 * depth.  The base names the layout and
  * the alignment of the bits in a word: 16 — (U, V) pairs in one plane, MSB-aligned; 512 — a plane each, 8 bits; 2048 — a plane
- * each in 16-bit words, LSB-aligned; 8192 — Y, U and V bytes packed in one plane, 4:2:2 (the subsampling bits are 0, depth 0 only). */
+ * each in 16-bit words, LSB-aligned; 8192 — Y, U and V bytes packed in one plane, 4:2:2 (the subsampling bits are 0, depth 0 only);
+ * 32768 — the same groups in 16-bit words, MSB-aligned (the subsampling bits are 0, depth 1 ... 3 only). */
 #define HYD_FMT_BASE_PAIRS 16
 #define HYD_FMT_BASE_PLANES 512
 #define HYD_FMT_BASE_PLANES16 2048
 #define HYD_FMT_BASE_PACKED 8192
+#define HYD_FMT_BASE_PACKED16 32768
 /* HydFmt.layout */
 #define HYD_LAYOUT_RGB 0    /* three samples a pixel, any strides */
 #define HYD_LAYOUT_PAIRS 1  /* a Y plane and a plane of (U, V) pairs */
 #define HYD_LAYOUT_PLANES 2 /* Y, U and V planes of their own */
-#define HYD_LAYOUT_PACKED 3 /* Y and chroma in one plane: groups of Y, U, Y, V bytes in one of four orders */
+#define HYD_LAYOUT_PACKED 3 /* Y and chroma in one plane: groups of Y, U, Y, V bytes (or 16-bit words: HydFmt.bytes) in one of four orders */
 /* HydFmt.sub */
 #define HYD_FMT_SUB_420 0
 #define HYD_FMT_SUB_422 1
@@ -101,6 +111,21 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
         d.is_float = fmt >= HYD_FMT_FLOAT32;
         d.bytes = fmt == HYD_FMT_UINT8 ? 1 : fmt == HYD_FMT_FLOAT32 ? 4 : 2;
         d.bits = 8 * d.bytes;
+        return d;
+    }
+    if (fmt >= HYD_FMT_BASE_PACKED16) { /* 32768 + matrix + 16 * filter + 64 * depth: no subsampling bits, depth 1 ... 3 */
+        const int n = fmt - HYD_FMT_BASE_PACKED16, depth = n >> 6;
+        if ((n & 12) || (n & 48) == 48 || depth < 1 || depth > 3)
+            return d;
+        d.device = 1;
+        d.bytes = 2;
+        d.layout = HYD_LAYOUT_PACKED;
+        d.matrix = n & 3;
+        d.filter = (n >> 4) & 3;
+        d.sub = HYD_FMT_SUB_422;
+        d.sx = 1;
+        d.depth = depth;
+        d.bits = depth == 1 ? 10 : depth == 2 ? 12 : 16;
         return d;
     }
     if (fmt >= HYD_FMT_BASE_PACKED) { /* 8192 + matrix + 16 * filter: no subsampling bits, no depth */
@@ -138,7 +163,8 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
 /* What an entry point that reads device pixels fails with before it enqueues anything, or NULL: "Invalid Sample Format"; then
  * the layout of src — pairs want unit pixel stride and V one sample behind U (and words on 2-byte boundaries), planes of
  * 16-bit words want their three addresses on 2-byte boundaries, packed 4:2:2 wants pixel stride 2 and U and V in the bytes beside
- * Y in one of the four orders, every other format takes any layout; then the chroma pitch —
+ * Y in one of the four orders (packed words: the same in words, on 2-byte boundaries), every other format takes any layout; then
+ * the chroma pitch —
  * a plane each has no layout to hold (three free pointers), but its pixel_stride argument is the chroma planes' pitch in
  * samples, of either sign: one shorter than a chroma row of the picture the call names, `width` pixels across — the habitual
  * pixel_stride 1 — is refused.  src NULL: the layout is not looked at (a caller with several pictures holds each to its
@@ -148,19 +174,28 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
 #define HYD_FMT_PLANAR16_ALIGN_MSG "planar YCbCr of 16-bit words wants its three planes on 2-byte boundaries"
 #define HYD_FMT_PLANAR_PITCH_MSG "planar YCbCr wants the chroma planes' pitch in pixel_stride"
 #define HYD_FMT_PACKED_LAYOUT_MSG "YUY2/UYVY wants pixel_stride 2 and U and V in the bytes beside Y"
+#define HYD_FMT_PACKED16_LAYOUT_MSG "Y210/Y216 wants pixel_stride 2 and U and V in the words beside Y"
 /* what hydamd_encode_image_multi says to a format with interpolated chroma */
 #define HYD_FMT_NV12_SHARDED_MSG "interpolated chroma is not sharded: a shard does not hold its neighbour's chroma rows"
 /* The byte order of a packed 4:2:2 picture, read off its pointers: 0 YUYV (U at +1, V at +3), 1 YVYU (+3, +1), 2 UYVY (-1, +1),
- * 3 VYUY (+1, -1) — bit 1: Y is the second byte of a pair, bit 0: V comes before U; -1: no such group. */
+ * 3 VYUY (+1, -1) — bit 1: Y is the second byte of a pair, bit 0: V comes before U; -1: no such group.  bytes: of a sample (1 YUY2,
+ * 2 Y210 / Y212 / Y216) — the differences are in samples, and every address is a multiple of it. */
 #define HYD_PACKED_YUYV 0
 #define HYD_PACKED_YVYU 1
 #define HYD_PACKED_UYVY 2
 #define HYD_PACKED_VYUY 3
-static inline int hyd_fmt_packed_order(const void *const src[3]) {
+static inline int hyd_fmt_packed_order(const void *const src[3], int bytes) {
     /* (the addresses as integers: three pointers that are no group at all need not point into one object) */
-    const ptrdiff_t u = (ptrdiff_t)((size_t)src[1] - (size_t)src[0]), v = (ptrdiff_t)((size_t)src[2] - (size_t)src[0]);
+    const ptrdiff_t du = (ptrdiff_t)((size_t)src[1] - (size_t)src[0]), dv = (ptrdiff_t)((size_t)src[2] - (size_t)src[0]);
+    if (bytes != 1 && (bytes != 2 || (((size_t)src[0] | (size_t)src[1] | (size_t)src[2]) & 1u)))
+        return -1;
+    const ptrdiff_t u = du / bytes, v = dv / bytes; /* (exact: aligned addresses differ by whole samples) */
     return u == 1 && v == 3 ? HYD_PACKED_YUYV : u == 3 && v == 1 ? HYD_PACKED_YVYU : u == -1 && v == 1 ? HYD_PACKED_UYVY : u == 1 && v == -1 ? HYD_PACKED_VYUY : -1;
 }
+#ifdef __cplusplus
+/* (the order of bytes, as C++ callers of the 8-bit family have spelled it since before there were words) */
+static inline int hyd_fmt_packed_order(const void *const src[3]) { return hyd_fmt_packed_order(src, 1); }
+#endif
 static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptrdiff_t pixel_stride, size_t width) {
     const HydFmt d = hyd_fmt_describe(fmt);
     if (!d.device)
@@ -172,8 +207,8 @@ static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptr
         if (((size_t)src[0] | (size_t)src[1] | (size_t)src[2]) & (size_t)(d.bytes - 1))
             return HYD_FMT_PLANAR16_ALIGN_MSG;
     } else if (src && d.layout == HYD_LAYOUT_PACKED) {
-        if (pixel_stride != 2 || hyd_fmt_packed_order(src) < 0)
-            return HYD_FMT_PACKED_LAYOUT_MSG;
+        if (pixel_stride != 2 || hyd_fmt_packed_order(src, d.bytes) < 0)
+            return d.bytes == 2 ? HYD_FMT_PACKED16_LAYOUT_MSG : HYD_FMT_PACKED_LAYOUT_MSG;
     }
     if (d.layout == HYD_LAYOUT_PLANES) {
         const size_t pitch = pixel_stride < 0 ? (size_t)0 - (size_t)pixel_stride : (size_t)pixel_stride;
@@ -186,8 +221,8 @@ static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptr
 /* The three origin pointers of the sub-rectangle at pixel (x0, y0) of a picture of a device format — an LF group, a tile, a
  * shard's first row.  Strides are in samples.  YCbCr: Y at row y0, sample x0 of its plane; the chroma at row y0 >> sy of
  * theirs.  Pairs: the one chroma plane has the Y plane's pitch and two samples for every two columns, so sample x0 of the row.
- * A plane each: the pitch is pixel_stride, sample x0 >> sx.  Packed 4:2:2: all three pointers move by y0 rows and 2 x0 bytes, the
- * group of pixel x0.  x0 must be even, and y0 where sy is 1 (every origin the library computes is a multiple of 256). */
+ * A plane each: the pitch is pixel_stride, sample x0 >> sx.  Packed 4:2:2: all three pointers move by y0 rows and 2 x0 samples
+ * (bytes, or 16-bit words), the group of pixel x0.  x0 must be even, and y0 where sy is 1 (every origin the library computes is a multiple of 256). */
 static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride, size_t x0,
                                   size_t y0, const void *origin[3]) {
     const HydFmt d = hyd_fmt_describe(fmt);

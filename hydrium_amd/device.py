@@ -32,7 +32,8 @@ BFLOAT16 = 4
 # (U, V) pairs — NV12 at depth 0, P010 / P012 / P016 (16-bit words, MSB-aligned) at depth 1, 2, 3; base 512: PLANAR, 8 bits in three
 # planes of their own (I420, I422, I444); base 2048: the same three planes in 16-bit words of 10, 12 or 16 bits, LSB-aligned (libyuv's
 # names: I010, I210, I410 ...); base 8192: PACKED 4:2:2, 8 bits in one plane of Y, U, Y, V groups (YUY2 / UYVY / YVYU / VYUY: the byte order
-# is what the three pointers spell), subsampling and depth 0.  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
+# is what the three pointers spell), subsampling and depth 0; base 32768: the same groups in 16-bit words of 10, 12 or 16 bits, MSB-aligned
+# (Y210 / Y212 / Y216), subsampling 0 and depth 1, 2, 3.  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
 # full (what a JPEG decoder leaves: JFIF).  filter: nearest, or INTERPOLATED for centre-sited chroma (C: JPEG / JFIF, MPEG-1) or
 # left-sited (L: MPEG-2, H.264, HEVC, AV1 default) — csrc/hip/hydk_chroma.h; 4:4:4 has nearest chroma only.
 CHROMA_FILTERS = {"nearest": 0, "centre": 1, "center": 1, "left": 2}
@@ -46,15 +47,16 @@ def ycbcr_fmt(base: int, matrix: int = 0, sub: int = 0, filt: int = 0, depth: in
 
 def ycbcr_fields(fmt: int):
     """(base, matrix, subsampling, filter, depth) of a YCbCr sample format"""
-    base = 8192 if fmt >= 8192 else 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
+    base = 32768 if fmt >= 32768 else 8192 if fmt >= 8192 else 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
     n = int(fmt) - base
     return base, n & 3, (n >> 2) & 3, (n >> 4) & 3, n >> 6
 
 
 _stems = [("NV12", 16, 0, 0)] + [(f"P0{b}", 16, 0, d) for b, d in P016_DEPTHS.items()] + \
     [(f"I{s}", 512, k, 0) for s, k in PLANAR_SUBSAMPLINGS.items()] + \
-    [(f"I{s[2]}{b}", 2048, k, d) for b, d in P016_DEPTHS.items() for s, k in PLANAR_SUBSAMPLINGS.items()] + [("YUY2", 8192, 0, 0)]
-for _stem, _base, _sub, _depth in _stems:  # NV12_BT709 = 16 ... I416_BT601_FULL = 2251, YUY2_BT709 = 8192 ..., as include/hydrium_amd.h has them
+    [(f"I{s[2]}{b}", 2048, k, d) for b, d in P016_DEPTHS.items() for s, k in PLANAR_SUBSAMPLINGS.items()] + [("YUY2", 8192, 0, 0)] + \
+    [(f"Y2{b}", 32768, 0, d) for b, d in P016_DEPTHS.items()]
+for _stem, _base, _sub, _depth in _stems:  # NV12_BT709 = 16 ... I416_BT601_FULL = 2251, YUY2_BT709 = 8192 ..., Y210_BT709 = 32832 ..., as include/hydrium_amd.h has them
     for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
         for _matrix, _name in enumerate(("BT709", "BT709_FULL", "BT601", "BT601_FULL")):
             if not (_sub == 2 and _filter):
@@ -68,6 +70,10 @@ PLANAR16_FAMILY = tuple(ycbcr_fmt(2048, *ycbcr_fields(f)[1:4], d) for d in (1, 2
 PACKED_FAMILY = tuple(ycbcr_fmt(8192, m, 0, f) for f in range(3) for m in range(4))
 # (U, V) byte offsets from the first Y byte, by byte order (include/hydrium_amd.h: the order is read off the pointers)
 PACKED_ORDERS = {"yuyv": (1, 3), "yuy2": (1, 3), "yvyu": (3, 1), "uyvy": (-1, 1), "vyuy": (1, -1)}
+# packed 4:2:2 in 16-bit words, Y210 / Y212 / Y216: the same four orders, the offsets in words ("y210": Y210's own, Y U Y V)
+PACKED16_FAMILY = tuple(ycbcr_fmt(32768, m, 0, f, d) for d in (1, 2, 3) for f in range(3) for m in range(4))
+PACKED16_ORDERS = dict(PACKED_ORDERS, y210=(1, 3), y212=(1, 3), y216=(1, 3))
+del PACKED16_ORDERS["yuy2"]
 
 
 def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
@@ -304,6 +310,59 @@ class PackedYuv(Nv12):
         return [y, y + du, y + dv]
 
 
+class PackedYuv16(PackedYuv):
+    """A packed 4:2:2 YCbCr picture of 16-bit words in device memory — Y210, Y212 or Y216, what a VA-API or D3D decoder leaves for
+    4:2:2 10-bit HEVC and ffmpeg's y210le / y212le / y216le: one plane of groups of four words, two pixels each, ``depth`` 10, 12
+    or 16 significant bits MSB-aligned (the low bits count as stored) — accepted wherever a PackedYuv object is.
+
+    ``surface``: 2-D tensor of a 2-byte integer dtype, H rows with unit element stride, at least 4 * ceil(width / 2) words a
+    row; its row stride is the pitch, in words.  ``width``: the picture's width in pixels.  ``matrix``: one of NV12_FORMATS (the
+    matrix and range) — or one of the 36 numbers of PACKED16_FAMILY, with ``chroma`` and ``depth`` left out; ``order``: "yuyv"
+    (or "y210": Y U Y V, the formats' own), "uyvy", "yvyu", "vyuy"; ``chroma``: as Nv12's (video is "left").  A crop starts on
+    even x: surface[y0:, 2 * x0:]."""
+
+    def __init__(self, surface, width: int, matrix: int = NV12_BT709, order: str = "yuyv", chroma=None, depth: Optional[int] = None):
+        matrix = int(matrix)
+        if chroma is not None and chroma not in CHROMA_FILTERS:
+            raise ValueError("chroma is 'nearest', 'centre' or 'left'")
+        if depth is not None and depth not in P016_DEPTHS:
+            raise ValueError("depth is 10, 12 or 16")
+        if matrix in PACKED16_FAMILY:
+            if chroma is not None and ycbcr_fields(matrix)[3] != CHROMA_FILTERS[chroma]:
+                raise ValueError("matrix names another chroma filter than chroma does")
+            if depth is not None and ycbcr_fields(matrix)[4] != P016_DEPTHS[depth]:
+                raise ValueError("matrix names another depth than depth does")
+            fmt = matrix
+        elif matrix in NV12_FORMATS:
+            fmt = ycbcr_fmt(32768, ycbcr_fields(matrix)[1], 0, CHROMA_FILTERS[chroma or "nearest"], P016_DEPTHS[10 if depth is None else depth])
+        else:
+            raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL (or a Y210 / Y212 / Y216 format)")
+        if str(order).lower() not in PACKED16_ORDERS:
+            raise ValueError("order is 'yuyv' (or 'y210'), 'uyvy', 'yvyu' or 'vyuy'")
+        name = str(surface.dtype).rpartition(".")[2]
+        if surface.element_size() != 2 or surface.dim() != 2 or name.startswith(("float", "bfloat", "complex")):
+            raise ValueError("a packed 4:2:2 surface of 16-bit words is (H, at least 4 * ceil(width / 2)) words of a 2-byte integer dtype")
+        h, row = surface.shape
+        width = int(width)
+        if h < 1 or width < 1 or row < 4 * -(-width // 2):
+            raise ValueError("a row of a packed 4:2:2 picture is 4 * ceil(width / 2) words")
+        if surface.stride(1) != 1:
+            raise ValueError("a packed 4:2:2 surface has unit element stride")
+        self.surface, self.sample_fmt, self.order = surface, fmt, str(order).lower()
+        self.height, self.width = int(h), width
+        self.pitch = int(surface.stride(0)) if h > 1 else max(int(surface.stride(0)), 4 * -(-width // 2))  # in words
+
+    @classmethod
+    def from_surface(cls, *args, **kwargs):
+        raise TypeError("PackedYuv16 takes its surface")
+
+    def pointers(self):
+        """src[0 ... 2] of the C API: the first Y, U and V word, all in the first group."""
+        du, dv = PACKED16_ORDERS[self.order]
+        y = self.surface.data_ptr() + (2 if du < 0 or dv < 0 else 0)
+        return [y, y + 2 * du, y + 2 * dv]
+
+
 class PlanarYuv16(PlanarYuv):
     """A planar YCbCr picture of 16-bit words in device memory — I010, I210, I410, I012 ... I416: PlanarYuv's three planes as
     tensors of a 2-byte integer dtype, ``depth`` 10, 12 or 16 significant bits LSB-aligned (bits above the depth are ignored) —
@@ -321,7 +380,7 @@ class PlanarYuv16(PlanarYuv):
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
     float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
-    An Nv12, P016, PlanarYuv, PlanarYuv16 or PackedYuv object: its own format."""
+    An Nv12, P016, PlanarYuv, PlanarYuv16, PackedYuv or PackedYuv16 object: its own format."""
     if isinstance(t, Nv12):
         return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]

@@ -429,7 +429,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * hydamd_encode_image_multi takes the 36 nearest forms and refuses the 48 interpolated ones as it does NV12's; the host-pointer
  * entry points refuse all 84 with "Invalid Sample Format".
  * Out of scope: BT.2020 and PQ / HLG (see the P010 section); MSB-aligned planes with full range at 10 or 12 bits; U and V planes
- * of different pitches; NV16 / NV21, packed Y210 / Y216 (8-bit YUY2 / UYVY: the next section); top-left siting; host-pointer input;
+ * of different pitches; NV16 / NV21 (packed 8-bit YUY2 / UYVY: the next section; packed Y210 / Y216: the one after it); top-left siting; host-pointer input;
  * cross-shard interpolation.
  */
 #define HYDAMD_I010_BT709 2112
@@ -527,7 +527,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  *                     nearest       centre-sited    left-sited
  *   HYDAMD_YUY2_*    8192..8195    8208..8211 (C)   8224..8227 (L)
  * 12 numbers.  The subsampling bits (4 *) are 0: 8196..8207, 8212..8223 and 8228..8239 name nothing; nor does 8240 and up (filter 3,
- * and 64 * depth, which is left free for Y210 / Y216).  A 4:2:2 JPEG is HYDAMD_YUY2C_BT601_FULL; video is left-sited.
+ * and 64 * depth: packed words of 10 to 16 bits have a base of their own, 32768, the next section).  A 4:2:2 JPEG is HYDAMD_YUY2C_BT601_FULL; video is left-sited.
  *
  * How such a picture is named — THE BYTE ORDER IS READ OFF THE POINTERS, not off the number:
  *   src[0]        the first Y byte
@@ -550,7 +550,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever NV12 is, and beside every other family — and pictures of different byte orders — in one
  * hydamd_encode_mixed_formats launch group.  hydamd_encode_image_multi takes the 4 nearest forms and refuses the 8 interpolated
  * ones as it does I422C / I422L; the host-pointer entry points refuse all 12 with "Invalid Sample Format".
- * Out of scope: Y210 / Y216 and AYUV / Y410 (the depth bits are reserved for them); 4:4:0 planes, rocJPEG's other native form
+ * Out of scope: AYUV / Y410 (packed 4:4:4); 4:4:0 planes, rocJPEG's other native form
  * (subsampling 3 of the planar family names nothing); host-pointer input; cross-shard interpolation.
  */
 #define HYDAMD_YUY2_BT709 8192
@@ -567,11 +567,59 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
 #define HYDAMD_YUY2L_BT601_FULL 8227
 
 /*
+ * PACKED 4:2:2 YCbCr OF 16-BIT WORDS, DEVICE pixels: Y210, Y212 and Y216 — 10, 12 or 16 significant bits a sample, MSB-aligned as
+ * P010's are, Y, U and V in ONE plane of groups of four words, two pixels a group.  What a VA-API or D3D decoder leaves for 4:2:2
+ * 10-bit HEVC, ffmpeg's y210le / y212le / y216le, the layout of 10-bit capture and broadcast ingest.  Read by the transform kernel
+ * as it is, without a de-interleaved or RGB copy.
+ *   sample_fmt = 32768 + matrix + 16 * filter + 64 * depth
+ * matrix 0..3 and filter 0..2 as in the NV12 family, depth 1, 2, 3 = 10, 12, 16 bits as in the P010 family:
+ *                     nearest         centre-sited      left-sited
+ *   HYDAMD_Y210_*    32832..32835    32848..32851 (C)   32864..32867 (L)
+ *   HYDAMD_Y212_*    32896..32899    32912..32915 (C)   32928..32931 (L)
+ *   HYDAMD_Y216_*    32960..32963    32976..32979 (C)   32992..32995 (L)
+ * 36 numbers.  Depth 0 (32768..32831: the 8-bit family stays at 8192), the subsampling bits (4 *), filter 3 and 33024 and up name
+ * nothing.  HEVC, H.264 and AV1 video is left-sited.
+ *
+ * How such a picture is named — everything in 16-BIT SAMPLES, and THE WORD ORDER IS READ OFF THE POINTERS, not off the number:
+ *   src[0]        the first Y word
+ *   src[1], [2]   the first U and the first V word, both of the group src[0] lies in: (src[1] - src[0], src[2] - src[0]) in words
+ *                 = (1, 3) Y210's own order Y U Y V, (3, 1) Y V Y U, (-1, 1) U Y V Y, (1, -1) V Y U Y
+ *   pixel_stride  2, the distance between two Y words
+ *   row_stride    the pitch of the surface in words; may be negative
+ * All three addresses sit on 2-byte boundaries.  Anything else is HYD_API_ERROR "Y210/Y216 wants pixel_stride 2 and U and V in the
+ * words beside Y", nothing enqueued.  A row is 4 * ceil(W / 2) words: for odd W the last group's second Y word belongs to the row,
+ * may be read and is no pixel.  Nothing outside those words of rows 0 .. H - 1 is ever read.  The library finds an LF group, tile or
+ * shard at pixel (x0, y0) by adding y0 * row_stride + 2 * x0 words to ALL THREE pointers; a caller's own crop must start on even x0.
+ *
+ * The words count AS STORED — the low 6 (Y210) or 4 (Y212) bits are not masked, the P010 section's rule — and the picture is the
+ * 4:2:2 picture of the de-interleaved words: Y[y][x] is the word at 2 x from src[0] in row y, U[y][cx] and V[y][cx] the words at
+ * 4 cx from src[1] and src[2], cw = ceil(W / 2).  Nearest chroma and the centre- and left-sited horizontal taps are the planar
+ * section's, the conversion, its depth-dependent full-range matrices and its 0.5625 bound the P010 section's.  So a Y216 picture is
+ * the HYDAMD_I216* picture of its de-interleaved words, and a Y210 picture whose low six bits are zero the HYDAMD_I210* picture of
+ * the words shifted right by six.  Clamping is at the edges of the PICTURE, as for YUY2.  The file is byte for byte what the
+ * reference writes for the HYD_UINT16 picture this produces.
+ *
+ * Accepted wherever YUY2 is, and beside every other family — and pictures of different word orders — in one
+ * hydamd_encode_mixed_formats launch group.  hydamd_encode_image_multi takes the 12 nearest forms and refuses the 24 interpolated
+ * ones as it does YUY2C / YUY2L; the host-pointer entry points refuse all 36 with "Invalid Sample Format".
+ * Out of scope: Y410 / Y416 and AYUV (packed 4:4:4); v210; NV16 / NV24 / P210; LSB-aligned packed words; host-pointer input;
+ * cross-shard interpolation.
+ */
+#define HYDAMD_PACKED16_STEM(P, F, D) \
+    HYDAMD_##P##_BT709 = 32768 + 16 * (F) + 64 * (D), HYDAMD_##P##_BT709_FULL, HYDAMD_##P##_BT601, HYDAMD_##P##_BT601_FULL
+enum {
+    HYDAMD_PACKED16_STEM(Y210, 0, 1), HYDAMD_PACKED16_STEM(Y210C, 1, 1), HYDAMD_PACKED16_STEM(Y210L, 2, 1),
+    HYDAMD_PACKED16_STEM(Y212, 0, 2), HYDAMD_PACKED16_STEM(Y212C, 1, 2), HYDAMD_PACKED16_STEM(Y212L, 2, 2),
+    HYDAMD_PACKED16_STEM(Y216, 0, 3), HYDAMD_PACKED16_STEM(Y216C, 1, 3), HYDAMD_PACKED16_STEM(Y216L, 2, 3)
+};
+#undef HYDAMD_PACKED16_STEM
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_* or HYDAMD_YUY2_* formats (whose src and strides are
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_*, HYDAMD_YUY2_* or HYDAMD_Y21x_* formats (whose src and strides are
  * described above).  With an interpolating format (HYDAMD_NV12C_*, HYDAMD_NV12L_*, their P01x and I42x forms) the LF group is a
  * picture of its own: its chroma clamps at its own edges.
  */
