@@ -348,7 +348,11 @@ static_assert(HYDAMD_FMT_FILTERS(YUY2, HYD_LAYOUT_PACKED, 0, HYDK_PLANAR_422) &&
 static_assert(HYDAMD_FMT_FILTERS(Y210, HYD_LAYOUT_PACKED, HYDK_YUV16_P010, HYDK_PLANAR_422) && HYDAMD_FMT_FILTERS(Y212, HYD_LAYOUT_PACKED, HYDK_YUV16_P012, HYDK_PLANAR_422) &&
                   HYDAMD_FMT_FILTERS(Y216, HYD_LAYOUT_PACKED, HYDK_YUV16_P016, HYDK_PLANAR_422) && HYDAMD_Y210_BT709 == HYD_FMT_BASE_PACKED16 + 64,
               "packed 4:2:2 of 16-bit words: 32768 + the kernels' matrix index + 16 * the kernels' chroma filter + 64 * the kernels' depth");
-static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_FORMS == 17, "the job did not grow; launch_transform's mask has 17 bits");
+static_assert(HYDAMD_FMT_STEM(Y410, HYD_LAYOUT_DWORD, HYDK_YUV16_P010, HYDK_PLANAR_444, HYDK_CHROMA_NEAREST) && HYDAMD_RGB10A2 == HYD_FMT_BASE_DWORD &&
+                  HYDAMD_BGR10A2 == HYD_FMT_BASE_DWORD + 1 && hyd_fmt_describe(HYDAMD_BGR10A2).layout == HYD_LAYOUT_DWORD && hyd_fmt_describe(HYDAMD_RGB10A2).bits == 10 &&
+                  hyd_fmt_describe(HYDAMD_Y410_BT709).bytes == 4,
+              "a dword a pixel: 131072 and 131073 the RGB orders, 131072 + the kernels' matrix index + 4 * 4:4:4 + 64 * the kernels' depth Y410");
+static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_COUNT == 19 && HYDK_STORE_FORMS == HYDK_STORE_RGB10, "the job did not grow; launch_transform's mask has 19 bits");
 #undef HYDAMD_FMT_PLANES
 #undef HYDAMD_FMT_FILTERS
 #undef HYDAMD_FMT_STEM
@@ -3066,6 +3070,49 @@ __attribute__((visibility("default"))) int hydt_packed16_to_rgb_device(int devic
     return probe_round_trip(surface, 8 * (size_t)((width + 1) >> 1) * height, rgb, 6 * n, [&](void *d_in, void *d_out) {
         hipLaunchKernelGGL(k_packed16_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, order, filter, depth, matrix, (const uint16_t *)d_in,
                            (uint16_t *)d_out, width, height);
+    });
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the definition of a pixel in one dword of three 10-bit fields
+ * (hydk_dword_pixel, hydk_rgb10.h — the two functions under it are the ones the transform kernel's loader calls on its dwords) as the
+ * host compiler built it and as the device runs it.  ycbcr 0: `which` is the RGB order (0 R low, 1 B low); 1: Y410, `which` its
+ * matrix HYDK_YUV_*; surface: height rows of width dwords, tightly packed; rgb receives height rows of width (R, G, B) word triples. */
+static bool dword_probe_args(int ycbcr, int which, const uint32_t *surface, uint16_t *rgb, int width, int height) {
+    return (ycbcr == 0 || ycbcr == 1) && which >= 0 && which < (ycbcr ? HYDK_YUV_MATRICES : 2) && surface && rgb && width >= 1 && height >= 1 &&
+           width <= 4096 && height <= 4096;
+}
+__host__ __device__ static inline void dword_probe_pixel(int ycbcr, int which, const uint32_t *surface, uint16_t *rgb, int width, size_t i) {
+    uint32_t out[3];
+    hydk_dword_pixel(ycbcr, which, surface, width, (int)(i % (size_t)width), (int)(i / (size_t)width), out);
+    for (int c = 0; c < 3; c++)
+        rgb[3 * i + c] = (uint16_t)out[c];
+}
+
+__attribute__((visibility("default"))) int hydt_dword_to_rgb_host(int ycbcr, int which, const uint32_t *surface, uint16_t *rgb, int width, int height) {
+    if (!dword_probe_args(ycbcr, which, surface, rgb, width, height))
+        return ST_API_ERROR;
+    for (size_t i = 0; i < (size_t)width * height; i++)
+        dword_probe_pixel(ycbcr, which, surface, rgb, width, i);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_dword_to_rgb_probe(int ycbcr, int which, const uint32_t *surface, uint16_t *rgb, int width, int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i < (size_t)width * height)
+        dword_probe_pixel(ycbcr, which, surface, rgb, width, i);
+}
+} /* namespace */
+
+/* one launch over the picture (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_dword_to_rgb_device(int device, int ycbcr, int which, const uint32_t *surface, uint16_t *rgb,
+                                                                    int width, int height) {
+    if (!dword_probe_args(ycbcr, which, surface, rgb, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height;
+    return probe_round_trip(surface, 4 * n, rgb, 6 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_dword_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, ycbcr, which, (const uint32_t *)d_in, (uint16_t *)d_out, width,
+                           height);
     });
 }
 

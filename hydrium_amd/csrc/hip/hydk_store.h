@@ -37,7 +37,10 @@
 #define HYDK_STORE_YUY2I 12
 #define HYDK_STORE_Y216 13  /* 16-bit class: the same groups in 16-bit words, MSB-aligned — Y210 / Y212 / Y216, HydkLfJob.sub the word order (hydk_y216.h) */
 #define HYDK_STORE_Y216I 14
-#define HYDK_STORE_FORMS 15
+#define HYDK_STORE_FORMS 15 /* the forms of ADDRESSABLE samples — floats, bytes, words — end here, as they have since Y216: what pointers and strides can spell */
+#define HYDK_STORE_RGB10 15 /* 16-bit class: a pixel is one dword of three 10-bit fields, RGB — HydkLfJob.sub the field order, 0 R low, 1 B low (hydk_rgb10.h) */
+#define HYDK_STORE_Y410 16  /* 16-bit class: the same dword holding U, Y, V — 4:4:4, nearest by nature, depth P010 */
+#define HYDK_STORE_COUNT 17 /* all of them: the table's size and the bits of launch_transform's mask above the two integer classes' */
 
 /* HydkLfJob.use_luts of a YCbCr job is the XYB mode + its form's variant bit: the RGB instances' own test turns it away */
 #define HYDK_VARIANT_NV12 8
@@ -52,6 +55,8 @@
 #define HYDK_VARIANT_YUY2I 4096
 #define HYDK_VARIANT_Y216 8192
 #define HYDK_VARIANT_Y216I 16384
+#define HYDK_VARIANT_RGB10 32768
+#define HYDK_VARIANT_Y410 65536
 
 typedef struct HydkStoreForm {
     int cls;           /* HYDK_FMT_*; form 0 belongs to every class */
@@ -63,7 +68,7 @@ typedef struct HydkStoreForm {
 } HydkStoreForm;
 
 HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
-    const HydkStoreForm forms[HYDK_STORE_FORMS] = {
+    const HydkStoreForm forms[HYDK_STORE_COUNT] = {
         {HYDK_FMT_F32, 0, 32, 0, 0, 0},
         {HYDK_FMT_F32, 0, 16, 0, 0, 0},
         {HYDK_FMT_F32, 0, 16, 0, 0, 0},
@@ -79,13 +84,16 @@ HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
         {HYDK_FMT_U8, 1, 8, 0, 1, HYDK_VARIANT_YUY2I},
         {HYDK_FMT_U16, 1, 16, 0, 0, HYDK_VARIANT_Y216},
         {HYDK_FMT_U16, 1, 16, 0, 1, HYDK_VARIANT_Y216I},
+        {HYDK_FMT_U16, 0, 10, 0, 0, HYDK_VARIANT_RGB10},
+        {HYDK_FMT_U16, 1, 10, 0, 0, HYDK_VARIANT_Y410},
     };
-    return forms[storage >= 0 && storage < HYDK_STORE_FORMS ? storage : 0];
+    return forms[storage >= 0 && storage < HYDK_STORE_COUNT ? storage : 0];
 }
 
 /* A public sample format taken apart into what a job holds.  ok: a device entry point takes it (else every field is 0).
  * matrix: HYDK_YUV_* (0 ... 3), + 4 * depth (HYDK_YUV16_P01x) for the 16-bit forms; filter: HYDK_CHROMA_*; sub: HYDK_PLANAR_*
- * (packed 4:2:2: HYDK_PLANAR_422 here; a recorded job's sub holds the byte order instead, which the public number does not name);
+ * (packed 4:2:2: HYDK_PLANAR_422 here; a recorded job's sub holds the byte order instead, which the public number does not name;
+ * HYDK_STORE_RGB10: the field order, which the number does name);
  * sx, sy: log2 of the pixels one chroma sample spans across and down. */
 typedef struct HydkSampleForm {
     int ok, cls;
@@ -96,7 +104,11 @@ typedef struct HydkSampleForm {
 static inline HydkSampleForm hydk_decode_fmt(int f) {
     const HydFmt fmt = hyd_fmt_describe(f);
     HydkSampleForm d = {fmt.device, 0, 0, (uint32_t)(fmt.matrix + 4 * fmt.depth), (uint32_t)fmt.filter, (uint32_t)fmt.sub, fmt.sx, fmt.sy};
-    if (fmt.layout == HYD_LAYOUT_PACKED)
+    if (fmt.layout == HYD_LAYOUT_DWORD) {
+        d.storage = (uint32_t)(fmt.depth ? HYDK_STORE_Y410 : HYDK_STORE_RGB10);
+        if (!fmt.depth)
+            d.sub = (uint32_t)(f - HYD_FMT_BASE_DWORD);
+    } else if (fmt.layout == HYD_LAYOUT_PACKED)
         d.storage = (uint32_t)((fmt.bytes == 2 ? HYDK_STORE_Y216 : HYDK_STORE_YUY2) + (fmt.filter != 0));
     else if (fmt.layout != HYD_LAYOUT_RGB) /* the YCbCr forms in the table's order: pairs then planes, bytes then words, nearest then interpolated */
         d.storage = (uint32_t)(HYDK_STORE_NV12 + 4 * (fmt.layout == HYD_LAYOUT_PLANES) + 2 * (fmt.bytes == 2) + (fmt.filter != 0));
@@ -109,6 +121,10 @@ static inline HydkSampleForm hydk_decode_fmt(int f) {
 /* and back: the public format of a job's cls (fmt), storage, matrix, filter and sub */
 static inline int hydk_encode_fmt(HydkSampleForm d) {
     const HydkStoreForm form = hydk_store_form((int)d.storage);
+    if (d.storage == HYDK_STORE_RGB10)
+        return HYD_FMT_BASE_DWORD + (int)(d.sub & 1u);
+    if (d.storage == HYDK_STORE_Y410)
+        return HYD_FMT_BASE_DWORD + (int)(d.matrix & 3u) + 4 * HYD_FMT_SUB_444 + 64 * (int)(d.matrix >> 2);
     if (!form.ycbcr)
         return d.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : d.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : d.cls;
     if (form.chroma_planes == 0) /* (sub: the byte order in a job, 4:2:2 in a decoded format; neither is in the number) */

@@ -1,6 +1,6 @@
 /*
  * k1_transform_body.h — the body of the transform kernel (kernels.hip, K1), included into k_transform_tokenize, into
- * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16, into k_transform_tokenize_yuy2 and into k_transform_tokenize_y216 and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
+ * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16, into k_transform_tokenize_yuy2, into k_transform_tokenize_y216 and into k_transform_tokenize_dword and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
  * and STORE, the kernel's parameters jobs, status, part_info and plog, and everything kernels.hip defines above its K1 section.
  * No include guard: it is function-body text, meant to be included once per kernel.
  */
@@ -10,11 +10,14 @@
      * PK: no chroma plane at all — packed 4:2:2, U and V among the Y bytes of one plane in the byte order job.sub names (hydk_yuy2.h),
      * or among the Y words of one plane of 16-bit words (hydk_y216.h).
      * INTERP: chroma interpolated (hydk_chroma.h) — job.filter says centre- or left-sited, and the job knows the picture it is
-     * cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it.  HALF: 2-byte floats, widened on load */
+     * cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it.  HALF: 2-byte floats, widened on load.
+     * DW: a pixel is one dword of three 10-bit fields (hydk_rgb10.h) — RGB10, which is no YCbCr form, and Y410, which is one with
+     * neither planes nor groups: every pixel carries its own chroma */
     constexpr HydkStoreForm FORM = hydk_store_form(STORE);
     static_assert(STORE == HYDK_STORE_F32 || FORM.cls == FMT,
-                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16, YUVP16I, Y216 and Y216I");
-    constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, PK = YUV && FORM.chroma_planes == 0, INTERP = FORM.interp;
+                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16, YUVP16I, Y216, Y216I, RGB10 and Y410");
+    constexpr bool DW = STORE == HYDK_STORE_RGB10 || STORE == HYDK_STORE_Y410;
+    constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, PK = YUV && FORM.chroma_planes == 0 && !DW, INTERP = FORM.interp;
     constexpr bool HALF = FMT == HYDK_FMT_F32 && STORE != HYDK_STORE_F32;
     /* the two-plane forms by name: YUVPI keeps a prefetch, an edge fill and an interpolate loop of its own (through the shared
      * ones its instances measured a few tenths of a percent slower, profiles/ycbcr_loader.txt) */
@@ -155,7 +158,7 @@
     /* log2 of the pixels one chroma sample spans across and down: the job's subsampling for two planes, 4:2:0 for pairs */
     const int csx = TWO_PLANES ? hydk_planar_sx((int)job.sub) : (int)YUV, csy = TWO_PLANES ? hydk_planar_sy((int)job.sub) : (int)(YUV && !PK);
     /* pairs in one plane (nvrun, prun): kYW dwords of Y and, from chroma row y >> 1, kYW dwords holding the block's four pairs */
-    const bool prun = YUV && !TWO_PLANES && !PK &&
+    const bool prun = YUV && !TWO_PLANES && !PK && !DW &&
                       (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)(job.row_stride * (SB / 8))) & 3) == 0;
     /* packed 4:2:2 (pkrun): a block row is four GROUPS — 16 bytes, four dwords — from the row's one plane, when the first group (Y's
      * place in its pair of bytes before src[0]) and the pitch are dword multiples; Y and the four (U, V) pairs are picked out of the
@@ -179,7 +182,9 @@
      * first and last chroma columns, a ragged last block and shifted bases or pitches fill the same window sample by sample with
      * the clamps, at use (phase A below).  pcx: the picture's chroma column of the block's first pixel. */
     const bool irun = (TWO_PLANES ? ylrun : PK ? pkrun : prun) && (!INTERP || ((job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1));
-    const bool fast = (YUV ? irun : packed) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
+    /* (a dword a pixel, DW: a block row is eight dwords of the row's one plane, 32 bytes; src[0] is dword-aligned and the pitch counts
+     * dwords — hyd_fmt_refusal lets nothing else through — so every whole block row comes that way) */
+    const bool fast = (DW || (YUV ? irun : packed)) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
     uint32_t nxt[kWords];
     /* the window's columns 0 and 5, which sit in no dword of the four between them (YUVPI: of U and of V, column 0 | column 5
      * << 8 of the near row, the same << 16 of the far row; YP16: column 0 | column 5 << 16 of U near, U far, V near, V far) */
@@ -224,6 +229,21 @@
         return (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
     };
     auto prefetch = [&](int s) {
+        if (DW) {
+            /* the eight pixels as stored in nxt[0 ... 7]: eight dword loads of one address, which the compiler fuses into two
+             * global_load_dwordx4 as it does PK16's (the hardware takes them at dword alignment); the fields come out at use */
+            if (fast && s * 8 + ar < gh) {
+                /* (the lane's row and block pass through an empty statement, as PK16's do and for its reason) */
+                int lane_row = ar, lane_block = ab;
+                asm volatile("" : "+v"(lane_row), "+v"(lane_block));
+                const long long y = py0 + s * 8 + lane_row, x = px0 + lane_block * 8;
+                const char *pd = (const char *)job.src[0] + (y * job.row_stride + x) * 4;
+#pragma unroll
+                for (int k = 0; k < 8; k++)
+                    nxt[k] = HYDK_GLOBAL(const uint32_t, pd)[k];
+            }
+            return;
+        }
         if (PK16) {
             /* the four groups as stored in nxt[0 ... 7]; interpolated: the group behind them in nxt[8], nxt[9] and (centre-sited) the
              * one before them in nxt[10], nxt[11], whole dwords too: irun says that both lie inside the picture's row */
@@ -502,7 +522,7 @@
                     }
                 }
                 prefetch(s + 1);
-            } else if (fast || INTERP || PK16) { /* (PK16: nearest rows that did not come as dwords fill the window too) */
+            } else if (fast || INTERP || PK16 || DW) { /* (PK16, DW: nearest rows that did not come as dwords fill the window too) */
                 const int nvalid = row_ok ? min(8, gw - ab * 8) : 0;
                 /* Interpolated rows that did not come as dwords — the picture's first and last chroma columns, a ragged last
                  * block, shifted bases, odd pitches — fill the same window sample by sample, here, every column clamped to the
@@ -712,6 +732,24 @@
                         flank[1 + 2 * k] = flank[2 * k];
                     }
                 }
+                /* A dword a pixel.  Rows that did not come as dwords — a ragged last block, and rows past the picture's last — fill
+                 * nxt[0 ... 7] pixel by pixel with the pixels the row has, and zero elsewhere: nothing outside the W dwords of a row
+                 * is read.  Either way three 10-bit fields come out of each dword (v_bfe_u32) and become an interleaved RGB16 row as
+                 * hydk_rgb10.h defines it: the RGB orders widen each field, the low and the high one changing places by job.sub
+                 * (uniform over the wavefront); Y410 shifts by 6 and takes the shared 16-bit conversion.  The per-sample loop at the
+                 * end is never theirs. */
+                if (DW && !fast) {
+#pragma unroll
+                    for (int k = 0; k < kWords; k++)
+                        nxt[k] = 0;
+                    if (row_ok) {
+                        const uint32_t *pd = (const uint32_t *)job.src[0] + (long long)y * job.row_stride + x0;
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            if (i < nvalid)
+                                nxt[i] = pd[i];
+                    }
+                }
                 /* YP16 rows that did not come as dwords: each plane's window of six words filled word by word, the same clamps, into
                  * the registers the dword rows use, as stored */
                 if (YP16 && INTERP && !fast) {
@@ -766,7 +804,7 @@
                 }
                 /* YCbCr: the eight pixels of the window, converted and packed as an interleaved RGB row of the class has them */
                 uint32_t cvt[kWords];
-                if (YUV) {
+                if (YUV || DW) {
 #pragma unroll
                     for (int k = 0; k < kWords; k++)
                         cvt[k] = 0;
@@ -783,7 +821,23 @@
                             cvt[si / kSPD] |= rgb[ch] << (SB * (si % kSPD));
                         }
                     };
-                    if ((YP16 || PK16) && INTERP) {
+                    if (DW) {
+                        /* pixel i is dword i: its three fields to an RGB16 pixel, packed as convert packs */
+                        const int order = (int)job.sub;
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            uint32_t rgb[3];
+                            if (YUV)
+                                hydk_y410_to_rgb(yuv, nxt[i < kWords ? i : 0], rgb);
+                            else
+                                hydk_rgb10_to_rgb(order, nxt[i < kWords ? i : 0], rgb);
+#pragma unroll
+                            for (int ch = 0; ch < 3; ch++) {
+                                const int si = i * 3 + ch;
+                                cvt[si / kSPD] |= rgb[ch] << (SB * (si % kSPD));
+                            }
+                        }
+                    } else if ((YP16 || PK16) && INTERP) {
                         /* the same two mixes, the window's words taken plane by plane */
                         uint32_t vu[6], vv[6];
 #pragma unroll
@@ -852,7 +906,7 @@
                             convert(i, near_get(0, i), near_get(1, i));
                     }
                 }
-                uint32_t(&w)[kWords] = YUV ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
+                uint32_t(&w)[kWords] = YUV || DW ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
                 /* which form of the transfer curve this wavefront's 16-bit samples need (wave-uniform) */
                 int curve = kCurveBoth;
                 if (FMT == HYDK_FMT_U16 && !LUTS) {
@@ -966,7 +1020,7 @@
                         row_to_xyb(std::integral_constant<int, kCurveNone>());
                     else
                         row_to_xyb(std::integral_constant<int, kCurveBoth>());
-                    if (INTERP || PK16) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
+                    if (INTERP || PK16 || DW) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
 #pragma unroll
                         for (int i = 0; i < 8; i++)
                             if (i >= nvalid)

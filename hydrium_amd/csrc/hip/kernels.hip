@@ -620,7 +620,8 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
  * a name that holds neither the planar nor the P016 kernel's, so that what is asked of those by name stays theirs.
  * Packed 4:2:2, HYDK_STORE_YUY2 and HYDK_STORE_YUY2I (YUYV, UYVY, YVYU, VYUY in one plane; hydk_yuy2.h), are k_transform_tokenize_yuy2's,
  * on the same grounds; and the same groups in 16-bit words, HYDK_STORE_Y216 and HYDK_STORE_Y216I (Y210, Y212, Y216; hydk_y216.h), are
- * k_transform_tokenize_y216's. */
+ * k_transform_tokenize_y216's.  A pixel in one dword of three 10-bit fields, HYDK_STORE_RGB10 and HYDK_STORE_Y410 (RGB10A2, BGR10A2, Y410;
+ * hydk_rgb10.h), are k_transform_tokenize_dword's. */
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
@@ -629,6 +630,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     static_assert(STORE != HYDK_STORE_YUVP16 && STORE != HYDK_STORE_YUVP16I, "the 16-bit planar instances are k_transform_tokenize_yuvp16's");
     static_assert(STORE != HYDK_STORE_YUY2 && STORE != HYDK_STORE_YUY2I, "the packed 4:2:2 instances are k_transform_tokenize_yuy2's");
     static_assert(STORE != HYDK_STORE_Y216 && STORE != HYDK_STORE_Y216I, "the packed 4:2:2 instances of 16-bit words are k_transform_tokenize_y216's");
+    static_assert(STORE != HYDK_STORE_RGB10 && STORE != HYDK_STORE_Y410, "the instances of a dword a pixel are k_transform_tokenize_dword's");
 #include "k1_transform_body.h"
 }
 
@@ -675,6 +677,16 @@ template <int XMODE, int STORE>
 __global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_y216(const HydkLfJob *__restrict__ jobs, uint32_t *status,
                                                                          uint2 *part_info, int plog) {
     static_assert(STORE == HYDK_STORE_Y216 || STORE == HYDK_STORE_Y216I, "YUY2 and YUY2I are k_transform_tokenize_yuy2's");
+    constexpr int FMT = HYDK_FMT_U16;
+#include "k1_transform_body.h"
+}
+
+/* A pixel in one dword of three 10-bit fields, RGB in either order (RGB10) and YCbCr 4:4:4 (Y410): four waves per SIMD as the
+ * other storage forms of the 16-bit class. */
+template <int XMODE, int STORE>
+__global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_dword(const HydkLfJob *__restrict__ jobs, uint32_t *status,
+                                                                          uint2 *part_info, int plog) {
+    static_assert(STORE == HYDK_STORE_RGB10 || STORE == HYDK_STORE_Y410, "Y216 and Y216I are k_transform_tokenize_y216's");
     constexpr int FMT = HYDK_FMT_U16;
 #include "k1_transform_body.h"
 }
@@ -2446,6 +2458,10 @@ static K1Fn k1_of_mode(int fmt, int storage) {
         return k_transform_tokenize_y216<A, HYDK_STORE_Y216>;
     case HYDK_STORE_Y216I:
         return k_transform_tokenize_y216<A, HYDK_STORE_Y216I>;
+    case HYDK_STORE_RGB10:
+        return k_transform_tokenize_dword<A, HYDK_STORE_RGB10>;
+    case HYDK_STORE_Y410:
+        return k_transform_tokenize_dword<A, HYDK_STORE_Y410>;
     }
     return fmt == HYDK_FMT_U8    ? k_transform_tokenize<HYDK_FMT_U8, XM>
            : fmt == HYDK_FMT_U16 ? k_transform_tokenize<HYDK_FMT_U16, XM>
@@ -2471,7 +2487,7 @@ static K1Fn k1_instance(int fmt, int storage, int xmode) {
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream) {
     const dim3 grid((num_slots * HYDK_GROUPS_PER_LFG) << plog), block(kThreads);
-    for (int bit = 0; bit < HYDK_FMT_F32 + HYDK_STORE_FORMS; bit++)
+    for (int bit = 0; bit < HYDK_FMT_F32 + HYDK_STORE_COUNT; bit++)
         if (fmt_mask & (1u << bit)) {
             const int storage = bit < HYDK_FMT_F32 ? HYDK_STORE_F32 : bit - HYDK_FMT_F32;
             const K1Fn k1 = k1_instance(bit < HYDK_FMT_F32 ? bit : hydk_store_form(storage).cls, storage, xmode);

@@ -50,6 +50,15 @@
  * (1, 3) Y210's own order, (3, 1), (-1, 1) or (1, -1); the pixel stride is 2, the row stride the pitch in words, of either sign,
  * and all three addresses sit on 2-byte boundaries (HYD_FMT_PACKED16_LAYOUT_MSG).  A storage form of the 16-BIT class; the picture
  * is the 4:2:2 picture of the de-interleaved words under the P01x conversion of that depth (hip/hydk_y216.h).
+ *
+ * 131072, 131073 and 131144 ... 131147 name pictures whose PIXEL IS ONE 32-BIT WORD of three 10-bit fields and two spare bits, in
+ * device memory (hip/hydk_rgb10.h).  131072 RGB10A2: R in bits 0 ... 9, G in 10 ... 19, B in 20 ... 29 (Vulkan A2B10G10R10, DXGI
+ * R10G10B10A2, DRM XBGR2101010); 131073 BGR10A2: B low, R high (Vulkan A2R10G10B10, DRM XRGB2101010) — the two sit at the base's
+ * depth-0 corner as 0 ... 4 sit at the bottom of the table.  131144 ... 131147 Y410 (DRM XVYU2101010): 131072 + matrix + 4 * 2
+ * (4:4:4) + 64 * 1 (10 bits), U in bits 0 ... 9, Y in 10 ... 19, V in 20 ... 29.  Bits 30 and 31 never matter.  A SAMPLE IS THE
+ * DWORD: src[0] == src[1] == src[2], the first dword, on a 4-byte boundary; the pixel stride is 1 and the row stride the pitch in
+ * dwords, of either sign (HYD_FMT_DWORD_LAYOUT_MSG).  Storage forms of the 16-BIT class: an RGB field v stands for the 16-bit
+ * sample nearest to v / 1023, a Y410 field for the P010 sample v << 6, so that a Y410 picture is the I410 picture of its fields.
  */
 #ifndef HYD_SAMPLE_FMT_H_
 #define HYD_SAMPLE_FMT_H_
@@ -66,17 +75,21 @@
 /* THE RULE: a YCbCr sample format = base + matrix + 4 * subsampling + 16 * filter + 64 * depth.  The base names the layout and
  * the alignment of the bits in a word: 16 — (U, V) pairs in one plane, MSB-aligned; 512 — a plane each, 8 bits; 2048 — a plane
  * each in 16-bit words, LSB-aligned; 8192 — Y, U and V bytes packed in one plane, 4:2:2 (the subsampling bits are 0, depth 0 only);
- * 32768 — the same groups in 16-bit words, MSB-aligned (the subsampling bits are 0, depth 1 ... 3 only). */
+ * 32768 — the same groups in 16-bit words, MSB-aligned (the subsampling bits are 0, depth 1 ... 3 only); 131072 — Y, U and V as
+ * 10-bit fields of one dword a pixel, 4:4:4 (subsampling 2, filter 0, depth 1 only), and at its depth-0 corner the two RGB orders of
+ * the same dword. */
 #define HYD_FMT_BASE_PAIRS 16
 #define HYD_FMT_BASE_PLANES 512
 #define HYD_FMT_BASE_PLANES16 2048
 #define HYD_FMT_BASE_PACKED 8192
 #define HYD_FMT_BASE_PACKED16 32768
+#define HYD_FMT_BASE_DWORD 131072
 /* HydFmt.layout */
 #define HYD_LAYOUT_RGB 0    /* three samples a pixel, any strides */
 #define HYD_LAYOUT_PAIRS 1  /* a Y plane and a plane of (U, V) pairs */
 #define HYD_LAYOUT_PLANES 2 /* Y, U and V planes of their own */
 #define HYD_LAYOUT_PACKED 3 /* Y and chroma in one plane: groups of Y, U, Y, V bytes (or 16-bit words: HydFmt.bytes) in one of four orders */
+#define HYD_LAYOUT_DWORD 4  /* a pixel is one dword of three 10-bit fields: one pointer three times over, a sample is the dword */
 /* HydFmt.sub */
 #define HYD_FMT_SUB_420 0
 #define HYD_FMT_SUB_422 1
@@ -111,6 +124,21 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
         d.is_float = fmt >= HYD_FMT_FLOAT32;
         d.bytes = fmt == HYD_FMT_UINT8 ? 1 : fmt == HYD_FMT_FLOAT32 ? 4 : 2;
         d.bits = 8 * d.bytes;
+        return d;
+    }
+    if (fmt >= HYD_FMT_BASE_DWORD) { /* 131072, 131073: the RGB orders; 131072 + matrix + 4 * 2 + 64 * 1: Y410 */
+        const int n = fmt - HYD_FMT_BASE_DWORD;
+        if (n > 1 && (n < 72 || n > 75))
+            return d;
+        d.device = 1;
+        d.bytes = 4;
+        d.layout = HYD_LAYOUT_DWORD;
+        d.bits = 10;
+        if (n > 1) {
+            d.matrix = n & 3;
+            d.sub = HYD_FMT_SUB_444;
+            d.depth = 1;
+        }
         return d;
     }
     if (fmt >= HYD_FMT_BASE_PACKED16) { /* 32768 + matrix + 16 * filter + 64 * depth: no subsampling bits, depth 1 ... 3 */
@@ -163,7 +191,8 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
 /* What an entry point that reads device pixels fails with before it enqueues anything, or NULL: "Invalid Sample Format"; then
  * the layout of src — pairs want unit pixel stride and V one sample behind U (and words on 2-byte boundaries), planes of
  * 16-bit words want their three addresses on 2-byte boundaries, packed 4:2:2 wants pixel stride 2 and U and V in the bytes beside
- * Y in one of the four orders (packed words: the same in words, on 2-byte boundaries), every other format takes any layout; then
+ * Y in one of the four orders (packed words: the same in words, on 2-byte boundaries), a dword a pixel wants pixel stride 1 and
+ * one dword-aligned pointer three times over, every other format takes any layout; then
  * the chroma pitch —
  * a plane each has no layout to hold (three free pointers), but its pixel_stride argument is the chroma planes' pitch in
  * samples, of either sign: one shorter than a chroma row of the picture the call names, `width` pixels across — the habitual
@@ -175,6 +204,7 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
 #define HYD_FMT_PLANAR_PITCH_MSG "planar YCbCr wants the chroma planes' pitch in pixel_stride"
 #define HYD_FMT_PACKED_LAYOUT_MSG "YUY2/UYVY wants pixel_stride 2 and U and V in the bytes beside Y"
 #define HYD_FMT_PACKED16_LAYOUT_MSG "Y210/Y216 wants pixel_stride 2 and U and V in the words beside Y"
+#define HYD_FMT_DWORD_LAYOUT_MSG "RGB10A2/Y410 wants pixel_stride 1 and three equal pointers on a 4-byte boundary"
 /* what hydamd_encode_image_multi says to a format with interpolated chroma */
 #define HYD_FMT_NV12_SHARDED_MSG "interpolated chroma is not sharded: a shard does not hold its neighbour's chroma rows"
 /* The byte order of a packed 4:2:2 picture, read off its pointers: 0 YUYV (U at +1, V at +3), 1 YVYU (+3, +1), 2 UYVY (-1, +1),
@@ -209,6 +239,9 @@ static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptr
     } else if (src && d.layout == HYD_LAYOUT_PACKED) {
         if (pixel_stride != 2 || hyd_fmt_packed_order(src, d.bytes) < 0)
             return d.bytes == 2 ? HYD_FMT_PACKED16_LAYOUT_MSG : HYD_FMT_PACKED_LAYOUT_MSG;
+    } else if (src && d.layout == HYD_LAYOUT_DWORD) {
+        if (pixel_stride != 1 || src[1] != src[0] || src[2] != src[0] || ((size_t)src[0] & 3u))
+            return HYD_FMT_DWORD_LAYOUT_MSG;
     }
     if (d.layout == HYD_LAYOUT_PLANES) {
         const size_t pitch = pixel_stride < 0 ? (size_t)0 - (size_t)pixel_stride : (size_t)pixel_stride;
@@ -222,7 +255,8 @@ static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptr
  * shard's first row.  Strides are in samples.  YCbCr: Y at row y0, sample x0 of its plane; the chroma at row y0 >> sy of
  * theirs.  Pairs: the one chroma plane has the Y plane's pitch and two samples for every two columns, so sample x0 of the row.
  * A plane each: the pitch is pixel_stride, sample x0 >> sx.  Packed 4:2:2: all three pointers move by y0 rows and 2 x0 samples
- * (bytes, or 16-bit words), the group of pixel x0.  x0 must be even, and y0 where sy is 1 (every origin the library computes is a multiple of 256). */
+ * (bytes, or 16-bit words), the group of pixel x0.  x0 must be even, and y0 where sy is 1 (every origin the library computes is a multiple of 256).
+ * A dword a pixel: all three pointers move by y0 rows and x0 dwords; any x0 and y0, since 4:4:4 has no parity to keep. */
 static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride, size_t x0,
                                   size_t y0, const void *origin[3]) {
     const HydFmt d = hyd_fmt_describe(fmt);
@@ -230,6 +264,8 @@ static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t r
     ptrdiff_t luma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0 * pixel_stride, chroma = luma;
     if (d.layout == HYD_LAYOUT_PACKED) {
         luma = chroma = (ptrdiff_t)y0 * row_stride + 2 * (ptrdiff_t)x0;
+    } else if (d.layout == HYD_LAYOUT_DWORD) {
+        luma = chroma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;
     } else if (d.layout != HYD_LAYOUT_RGB) {
         luma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;
         chroma = (ptrdiff_t)(y0 >> d.sy) * (pairs ? row_stride : pixel_stride) + (ptrdiff_t)(pairs ? x0 : x0 >> d.sx);

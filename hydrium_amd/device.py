@@ -33,7 +33,8 @@ BFLOAT16 = 4
 # planes of their own (I420, I422, I444); base 2048: the same three planes in 16-bit words of 10, 12 or 16 bits, LSB-aligned (libyuv's
 # names: I010, I210, I410 ...); base 8192: PACKED 4:2:2, 8 bits in one plane of Y, U, Y, V groups (YUY2 / UYVY / YVYU / VYUY: the byte order
 # is what the three pointers spell), subsampling and depth 0; base 32768: the same groups in 16-bit words of 10, 12 or 16 bits, MSB-aligned
-# (Y210 / Y212 / Y216), subsampling 0 and depth 1, 2, 3.  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
+# (Y210 / Y212 / Y216), subsampling 0 and depth 1, 2, 3; base 131072: ONE DWORD A PIXEL, three 10-bit fields — Y410 at subsampling 2 (4:4:4)
+# and depth 1, and at the base's depth-0 corner RGB10A2 (131072) and BGR10A2 (131073), which are no YCbCr.  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
 # full (what a JPEG decoder leaves: JFIF).  filter: nearest, or INTERPOLATED for centre-sited chroma (C: JPEG / JFIF, MPEG-1) or
 # left-sited (L: MPEG-2, H.264, HEVC, AV1 default) — csrc/hip/hydk_chroma.h; 4:4:4 has nearest chroma only.
 CHROMA_FILTERS = {"nearest": 0, "centre": 1, "center": 1, "left": 2}
@@ -47,7 +48,7 @@ def ycbcr_fmt(base: int, matrix: int = 0, sub: int = 0, filt: int = 0, depth: in
 
 def ycbcr_fields(fmt: int):
     """(base, matrix, subsampling, filter, depth) of a YCbCr sample format"""
-    base = 32768 if fmt >= 32768 else 8192 if fmt >= 8192 else 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
+    base = 131072 if fmt >= 131072 else 32768 if fmt >= 32768 else 8192 if fmt >= 8192 else 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
     n = int(fmt) - base
     return base, n & 3, (n >> 2) & 3, (n >> 4) & 3, n >> 6
 
@@ -55,7 +56,7 @@ def ycbcr_fields(fmt: int):
 _stems = [("NV12", 16, 0, 0)] + [(f"P0{b}", 16, 0, d) for b, d in P016_DEPTHS.items()] + \
     [(f"I{s}", 512, k, 0) for s, k in PLANAR_SUBSAMPLINGS.items()] + \
     [(f"I{s[2]}{b}", 2048, k, d) for b, d in P016_DEPTHS.items() for s, k in PLANAR_SUBSAMPLINGS.items()] + [("YUY2", 8192, 0, 0)] + \
-    [(f"Y2{b}", 32768, 0, d) for b, d in P016_DEPTHS.items()]
+    [(f"Y2{b}", 32768, 0, d) for b, d in P016_DEPTHS.items()] + [("Y410", 131072, 2, 1)]
 for _stem, _base, _sub, _depth in _stems:  # NV12_BT709 = 16 ... I416_BT601_FULL = 2251, YUY2_BT709 = 8192 ..., Y210_BT709 = 32832 ..., as include/hydrium_amd.h has them
     for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
         for _matrix, _name in enumerate(("BT709", "BT709_FULL", "BT601", "BT601_FULL")):
@@ -74,6 +75,11 @@ PACKED_ORDERS = {"yuyv": (1, 3), "yuy2": (1, 3), "yvyu": (3, 1), "uyvy": (-1, 1)
 PACKED16_FAMILY = tuple(ycbcr_fmt(32768, m, 0, f, d) for d in (1, 2, 3) for f in range(3) for m in range(4))
 PACKED16_ORDERS = dict(PACKED_ORDERS, y210=(1, 3), y212=(1, 3), y216=(1, 3))
 del PACKED16_ORDERS["yuy2"]
+# one dword a pixel: the two RGB orders, then Y410's four matrices (Y410_BT709 = 131144 ...)
+RGB10A2, BGR10A2 = 131072, 131073
+RGB10_ORDERS = {"rgb": RGB10A2, "bgr": BGR10A2}
+Y410_FORMATS = tuple(ycbcr_fmt(131072, m, 2, 0, 1) for m in range(4))
+DWORD_FAMILY = (RGB10A2, BGR10A2) + Y410_FORMATS
 
 
 def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
@@ -363,6 +369,63 @@ class PackedYuv16(PackedYuv):
         return [y, y + 2 * du, y + 2 * dv]
 
 
+class Rgb10(Nv12):
+    """An RGB picture of one dword a pixel in device memory — RGB10A2 or BGR10A2: three 10-bit fields and two spare bits, the
+    render-target and scan-out format of HDR and deep-colour pipelines (Vulkan A2B10G10R10 / A2R10G10B10, DXGI R10G10B10A2, DRM
+    XBGR2101010 / XRGB2101010) — accepted wherever a PackedYuv16 object is.  A field v stands for the 16-bit sample nearest to
+    v / 1023; bits 30 and 31 are ignored.
+
+    ``surface``: 2-D tensor of a 4-byte integer dtype, H rows with unit element stride, at least ``width`` dwords a row; its row
+    stride is the pitch, in dwords.  ``width``: the picture's width in pixels.  ``order``: "rgb" — R in bits 0 ... 9 — or "bgr" —
+    B in bits 0 ... 9.  A crop starts anywhere: surface[y0:, x0:]."""
+
+    pixel_stride = 1  # a sample is the dword
+
+    def __init__(self, surface, width: int, order: str = "rgb"):
+        if str(order).lower() not in RGB10_ORDERS:
+            raise ValueError("order is 'rgb' or 'bgr'")
+        self._surface(surface, width, RGB10_ORDERS[str(order).lower()])
+        self.order = str(order).lower()
+
+    def _surface(self, surface, width, fmt):
+        """the shape, stride and pitch rules of a surface of one dword a pixel"""
+        name = str(surface.dtype).rpartition(".")[2]
+        if surface.element_size() != 4 or surface.dim() != 2 or name.startswith(("float", "complex")):
+            raise ValueError("a surface of one dword a pixel is (H, at least width) dwords of a 4-byte integer dtype")
+        h, row = surface.shape
+        width = int(width)
+        if h < 1 or width < 1 or row < width:
+            raise ValueError("a row of a picture of one dword a pixel is width dwords")
+        if surface.stride(1) != 1:
+            raise ValueError("a surface of one dword a pixel has unit element stride")
+        self.surface, self.sample_fmt = surface, int(fmt)
+        self.height, self.width = int(h), width
+        self.pitch = int(surface.stride(0)) if h > 1 else max(int(surface.stride(0)), width)  # in dwords
+
+    @classmethod
+    def from_surface(cls, *args, **kwargs):
+        raise TypeError(f"{cls.__name__} takes its surface")
+
+    def pointers(self):
+        """src[0 ... 2] of the C API: the first dword, three times over."""
+        p = self.surface.data_ptr()
+        return [p, p, p]
+
+
+class Y410(Rgb10):
+    """A Y410 picture in device memory — packed 4:4:4 YCbCr of 10 bits, one dword a pixel with U in bits 0 ... 9, Y in 10 ... 19
+    and V in 20 ... 29 (DRM XVYU2101010): what a VA-API or D3D decoder leaves for 4:4:4 10-bit HEVC — accepted wherever an Rgb10
+    object is.  The picture is the I410 picture of the three fields.
+
+    ``surface``, ``width``: as Rgb10's.  ``matrix``: one of NV12_FORMATS (the matrix and range) or one of Y410_FORMATS."""
+
+    def __init__(self, surface, width: int, matrix: int = NV12_BT709):
+        matrix = int(matrix)
+        if matrix not in Y410_FORMATS and matrix not in NV12_FORMATS:
+            raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL (or a Y410 format)")
+        self._surface(surface, width, Y410_FORMATS[ycbcr_fields(matrix)[1]])
+
+
 class PlanarYuv16(PlanarYuv):
     """A planar YCbCr picture of 16-bit words in device memory — I010, I210, I410, I012 ... I416: PlanarYuv's three planes as
     tensors of a 2-byte integer dtype, ``depth`` 10, 12 or 16 significant bits LSB-aligned (bits above the depth are ignored) —
@@ -380,7 +443,7 @@ class PlanarYuv16(PlanarYuv):
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
     float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
-    An Nv12, P016, PlanarYuv, PlanarYuv16, PackedYuv or PackedYuv16 object: its own format."""
+    An Nv12, P016, PlanarYuv, PlanarYuv16, PackedYuv, PackedYuv16, Rgb10 or Y410 object: its own format."""
     if isinstance(t, Nv12):
         return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]

@@ -550,7 +550,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever NV12 is, and beside every other family — and pictures of different byte orders — in one
  * hydamd_encode_mixed_formats launch group.  hydamd_encode_image_multi takes the 4 nearest forms and refuses the 8 interpolated
  * ones as it does I422C / I422L; the host-pointer entry points refuse all 12 with "Invalid Sample Format".
- * Out of scope: AYUV / Y410 (packed 4:4:4); 4:4:0 planes, rocJPEG's other native form
+ * Out of scope: AYUV (packed 4:4:4 of bytes; Y410 is the section after the next); 4:4:0 planes, rocJPEG's other native form
  * (subsampling 3 of the planar family names nothing); host-pointer input; cross-shard interpolation.
  */
 #define HYDAMD_YUY2_BT709 8192
@@ -602,7 +602,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever YUY2 is, and beside every other family — and pictures of different word orders — in one
  * hydamd_encode_mixed_formats launch group.  hydamd_encode_image_multi takes the 12 nearest forms and refuses the 24 interpolated
  * ones as it does YUY2C / YUY2L; the host-pointer entry points refuse all 36 with "Invalid Sample Format".
- * Out of scope: Y410 / Y416 and AYUV (packed 4:4:4); v210; NV16 / NV24 / P210; LSB-aligned packed words; host-pointer input;
+ * Out of scope: Y416 and AYUV (packed 4:4:4 of words and bytes; Y410 is the next section); v210; NV16 / NV24 / P210; LSB-aligned packed words; host-pointer input;
  * cross-shard interpolation.
  */
 #define HYDAMD_PACKED16_STEM(P, F, D) \
@@ -615,11 +615,51 @@ enum {
 #undef HYDAMD_PACKED16_STEM
 
 /*
+ * ONE DWORD A PIXEL, DEVICE pixels: RGB10A2, BGR10A2 and Y410 — a pixel is one 32-bit word of three 10-bit fields and two spare
+ * bits.  RGB10A2 is the render-target and scan-out format of HDR and deep-colour pipelines (Vulkan A2B10G10R10_UNORM_PACK32, DXGI
+ * R10G10B10A2_UNORM, DRM XBGR2101010), BGR10A2 its other order (Vulkan A2R10G10B10_UNORM_PACK32, DRM XRGB2101010), Y410 (DRM
+ * XVYU2101010) what a VA-API or D3D decoder leaves for 4:4:4 10-bit HEVC.  Read by the transform kernel as it is, without an
+ * unpacked RGB16 copy of three times the bytes.
+ *   HYDAMD_RGB10A2   131072          R in bits 0..9, G in 10..19, B in 20..29
+ *   HYDAMD_BGR10A2   131073          B in bits 0..9, G in 10..19, R in 20..29
+ *   HYDAMD_Y410_*    131144..131147  = 131072 + matrix + 4 * 2 (4:4:4) + 64 * 1 (10 bits); U in bits 0..9, Y in 10..19, V in 20..29
+ * Six numbers; every other number from 131072 up names nothing.  Bits 30 and 31 are ignored.
+ *
+ * How such a picture is named — A SAMPLE IS THE DWORD:
+ *   src[0] == src[1] == src[2]   the first dword, on a 4-byte boundary
+ *   pixel_stride                 1
+ *   row_stride                   the pitch of the surface in dwords; may be negative
+ * Anything else is HYD_API_ERROR "RGB10A2/Y410 wants pixel_stride 1 and three equal pointers on a 4-byte boundary", nothing
+ * enqueued.  A row is W dwords and nothing outside the W dwords of rows 0 .. H - 1 is ever read.  The library finds an LF group, tile
+ * or shard at pixel (x0, y0) by adding y0 * row_stride + x0 dwords to all three pointers; a caller's own crop may start anywhere.
+ *
+ * Both are storage forms of the 16-bit class.  An RGB field v (0..1023) stands for the HYD_UINT16 sample nearest to v / 1023,
+ * (v * 65535 + 511) / 1023 in integers — 0 is 0, 1023 is 65535, no value is a tie — and the picture is the HYD_UINT16 picture of
+ * those samples.  A Y410 field v stands for the P010 sample v << 6, and from there the conversion, its matrices and its 0.5625 bound
+ * are the P010 section's: a Y410 picture is the HYDAMD_I410_* picture of its three fields.  The file is byte for byte what the
+ * reference writes for the HYD_UINT16 picture this produces.  An HDR10 swap chain's PQ-coded numbers would be coded AS sRGB, as the
+ * P010 section says of BT.2020 video: the codestream this encoder writes signals sRGB or linear sRGB and nothing else.
+ *
+ * Accepted wherever Y210 is, and beside every other family in one hydamd_encode_mixed_formats launch group.  There is no chroma
+ * filter, so hydamd_encode_image_multi takes all six; the host-pointer entry points refuse all six with "Invalid Sample Format".
+ * Out of scope: Y416 and AYUV (packed 4:4:4 of words and bytes); R11G11B10F; v210; PQ / HLG / BT.2020; an alpha in bits 30..31;
+ * host-pointer input.
+ */
+enum {
+    HYDAMD_RGB10A2 = 131072,
+    HYDAMD_BGR10A2 = 131073,
+    HYDAMD_Y410_BT709 = 131072 + 4 * 2 + 64 * 1,
+    HYDAMD_Y410_BT709_FULL,
+    HYDAMD_Y410_BT601,
+    HYDAMD_Y410_BT601_FULL
+};
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_*, HYDAMD_YUY2_* or HYDAMD_Y21x_* formats (whose src and strides are
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_*, HYDAMD_YUY2_*, HYDAMD_Y21x_*, HYDAMD_RGB10A2, HYDAMD_BGR10A2 or HYDAMD_Y410_* formats (whose src and strides are
  * described above).  With an interpolating format (HYDAMD_NV12C_*, HYDAMD_NV12L_*, their P01x and I42x forms) the LF group is a
  * picture of its own: its chroma clamps at its own edges.
  */
