@@ -352,7 +352,13 @@ static_assert(HYDAMD_FMT_STEM(Y410, HYD_LAYOUT_DWORD, HYDK_YUV16_P010, HYDK_PLAN
                   HYDAMD_BGR10A2 == HYD_FMT_BASE_DWORD + 1 && hyd_fmt_describe(HYDAMD_BGR10A2).layout == HYD_LAYOUT_DWORD && hyd_fmt_describe(HYDAMD_RGB10A2).bits == 10 &&
                   hyd_fmt_describe(HYDAMD_Y410_BT709).bytes == 4,
               "a dword a pixel: 131072 and 131073 the RGB orders, 131072 + the kernels' matrix index + 4 * 4:4:4 + 64 * the kernels' depth Y410");
-static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_COUNT == 19 && HYDK_STORE_FORMS == HYDK_STORE_RGB10, "the job did not grow; launch_transform's mask has 19 bits");
+static_assert(HYDAMD_FMT_STEM(AYUV, HYD_LAYOUT_QUAD, 0, HYDK_PLANAR_444, HYDK_CHROMA_NEAREST) && HYDAMD_FMT_STEM(Y412, HYD_LAYOUT_QUAD, HYDK_YUV16_P012, HYDK_PLANAR_444, HYDK_CHROMA_NEAREST) &&
+                  HYDAMD_FMT_STEM(Y416, HYD_LAYOUT_QUAD, HYDK_YUV16_P016, HYDK_PLANAR_444, HYDK_CHROMA_NEAREST) && HYDAMD_AYUV_BT709 == HYD_FMT_BASE_QUAD + 4 * 2 &&
+                  hyd_fmt_describe(HYDAMD_AYUV_BT709).bytes == 4 && hyd_fmt_describe(HYDAMD_Y412_BT709).bytes == 8 && hyd_fmt_describe(HYDAMD_Y412_BT709).bits == 12 &&
+                  !hyd_fmt_describe(HYD_FMT_BASE_QUAD + 4 * 2 + 64).device,
+              "four samples a pixel: 524288 + the kernels' matrix index + 4 * 4:4:4 + 64 * the kernels' depth, bytes at depth 0, words at 2 and 3, nothing at 1");
+static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_COUNT == 19 && HYDK_STORE_FORMS == HYDK_STORE_RGB10 && HYDK_FMT_F32 + HYDK_STORE_TABLE == 21,
+              "the job did not grow; launch_transform's mask has 21 bits");
 #undef HYDAMD_FMT_PLANES
 #undef HYDAMD_FMT_FILTERS
 #undef HYDAMD_FMT_STEM
@@ -3113,6 +3119,53 @@ __attribute__((visibility("default"))) int hydt_dword_to_rgb_device(int device, 
     return probe_round_trip(surface, 4 * n, rgb, 6 * n, [&](void *d_in, void *d_out) {
         hipLaunchKernelGGL(k_dword_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, ycbcr, which, (const uint32_t *)d_in, (uint16_t *)d_out, width,
                            height);
+    });
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the definition of a pixel in one group of four samples
+ * (hydk_quad_pixel, hydk_quad.h — the two functions under it are the ones the transform kernel's loader calls on its dwords) as the
+ * host compiler built it and as the device runs it.  depth 0: AYUV, surface height rows of width dwords and rgb height rows of
+ * width (R, G, B) BYTE triples; HYDK_YUV16_P012 or _P016: Y412 / Y416, surface height rows of width qwords (as dwords) and rgb
+ * WORD triples; matrix HYDK_YUV_*; tightly packed. */
+static bool quad_probe_args(int depth, int matrix, const uint32_t *surface, void *rgb, int width, int height) {
+    return (depth == 0 || depth == HYDK_YUV16_P012 || depth == HYDK_YUV16_P016) && matrix >= 0 && matrix < HYDK_YUV_MATRICES && surface && rgb &&
+           width >= 1 && height >= 1 && width <= 4096 && height <= 4096;
+}
+__host__ __device__ static inline void quad_probe_pixel(int depth, int matrix, const uint32_t *surface, void *rgb, int width, size_t i) {
+    uint32_t out[3];
+    hydk_quad_pixel(depth, matrix, surface, width, (int)(i % (size_t)width), (int)(i / (size_t)width), out);
+    for (int c = 0; c < 3; c++) {
+        if (depth)
+            ((uint16_t *)rgb)[3 * i + c] = (uint16_t)out[c];
+        else
+            ((uint8_t *)rgb)[3 * i + c] = (uint8_t)out[c];
+    }
+}
+
+__attribute__((visibility("default"))) int hydt_quad_to_rgb_host(int depth, int matrix, const uint32_t *surface, void *rgb, int width, int height) {
+    if (!quad_probe_args(depth, matrix, surface, rgb, width, height))
+        return ST_API_ERROR;
+    for (size_t i = 0; i < (size_t)width * height; i++)
+        quad_probe_pixel(depth, matrix, surface, rgb, width, i);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_quad_to_rgb_probe(int depth, int matrix, const uint32_t *surface, void *rgb, int width, int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i < (size_t)width * height)
+        quad_probe_pixel(depth, matrix, surface, rgb, width, i);
+}
+} /* namespace */
+
+/* one launch over the picture (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_quad_to_rgb_device(int device, int depth, int matrix, const uint32_t *surface, void *rgb,
+                                                                   int width, int height) {
+    if (!quad_probe_args(depth, matrix, surface, rgb, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height;
+    return probe_round_trip(surface, (depth ? 8 : 4) * n, rgb, (depth ? 6 : 3) * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_quad_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, depth, matrix, (const uint32_t *)d_in, d_out, width, height);
     });
 }
 

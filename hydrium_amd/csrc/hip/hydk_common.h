@@ -18,7 +18,8 @@
 #include "hydk_yuvp16.h" /* in two planes or (LSB-aligned) in three, */
 #include "hydk_yuy2.h"  /* and 8-bit 4:2:2 packed in one plane, */
 #include "hydk_y216.h"  /* or packed in 16-bit words; */
-#include "hydk_rgb10.h" /* and a pixel in one dword of three 10-bit fields, RGB or YCbCr */
+#include "hydk_rgb10.h" /* and a pixel in one dword of three 10-bit fields, RGB or YCbCr, */
+#include "hydk_quad.h"  /* or in one group of four bytes or words, YCbCr 4:4:4 */
 
 #define HYDK_GROUPS_PER_LFG 64        /* 8 x 8 groups of 256 px in a 2048 px LF group */
 #define HYDK_BLOCKS_PER_GROUP 1024    /* 32 x 32 varblocks */
@@ -83,9 +84,9 @@ typedef struct HydkTables {
 typedef struct HydkLfJob {
     const void *src[3];      /* R, G, B sample pointers of the LF group's first pixel (device memory) */
     long long row_stride;    /* in samples; HYDK_STORE_YUY2 and _YUY2I: the pitch of the one plane in bytes; _Y216 and _Y216I: in words;
-                              * _RGB10 and _Y410: in dwords (src[0 ... 2] are one pointer) */
+                              * _RGB10 and _Y410: in dwords (src[0 ... 2] are one pointer); _AYUV and _Y416: in pixels, dwords and qwords (the same) */
     long long pixel_stride;  /* in samples; HYDK_STORE_YUVP, _YUVPI, _YUVP16 and _YUVP16I: the pitch of the U and of the V plane in samples;
-                              * HYDK_STORE_YUY2, _YUY2I, _Y216 and _Y216I: 2; _RGB10 and _Y410: 1 */
+                              * HYDK_STORE_YUY2, _YUY2I, _Y216 and _Y216I: 2; _RGB10, _Y410, _AYUV and _Y416: 1 */
     int fmt;                 /* HYDK_FMT_* */
     int linear_light;
     int width, height;       /* LF group size in pixels */
@@ -93,7 +94,7 @@ typedef struct HydkLfJob {
     int scheme;              /* HF clustering scheme 0..3 = 9 / 3 / 2 / 1 clusters per preset */
     int use_luts;            /* which transform kernel variant owns the job: the XYB mode it was recorded under (0, 1: curves in
                               * registers, 2: gathers from the uploaded LUTs), + HYDK_VARIANT_NV12 for storage HYDK_STORE_NV12,
-                              * + HYDK_VARIANT_NV12I for storage HYDK_STORE_NV12I, + HYDK_VARIANT_P016 / _P016I / _YUVP / _YUVPI / _YUVP16 / _YUVP16I / _YUY2 / _YUY2I / _Y216 / _Y216I / _RGB10 / _Y410 for theirs */
+                              * + HYDK_VARIANT_NV12I for storage HYDK_STORE_NV12I, + HYDK_VARIANT_P016 / _P016I / _YUVP / _YUVPI / _YUVP16 / _YUVP16I / _YUY2 / _YUY2I / _Y216 / _Y216I / _RGB10 / _Y410 / _AYUV / _Y416 for theirs */
     unsigned preset;         /* HF preset id of this LF group (written in front of each group section) */
     unsigned short preset_bits; /* hyd_cllog2(LF groups of this LF group's frame): the width of that field (encoder.c:940) */
     unsigned short frame_first; /* the first slot of this LF group's frame: where the running alphabet maximum starts afresh */
@@ -118,8 +119,8 @@ typedef struct HydkLfJob {
                               * chroma plane, row_stride the pitch of both */
     uint32_t per_sample;     /* probe flavour only (HYDAMD_DEBUG_HALF_PER_SAMPLE, for A/B): bit 0 interleaved, bit 1 planar half rows
                               * go through the per-sample loader although they qualify for the dword runs; the product leaves 0 */
-    uint32_t matrix;         /* HYDK_STORE_NV12, _NV12I, _YUVP, _YUVPI, _YUY2 and _YUY2I: HYDK_YUV_* (0 ... 3), the YCbCr matrix and range; HYDK_STORE_P016,
-                              * _P016I, _YUVP16, _YUVP16I, _Y216, _Y216I and _Y410: that + 4 * HYDK_YUV16_P01x (the depth; hydk_yuv16.h) */
+    uint32_t matrix;         /* HYDK_STORE_NV12, _NV12I, _YUVP, _YUVPI, _YUY2, _YUY2I and _AYUV: HYDK_YUV_* (0 ... 3), the YCbCr matrix and range; HYDK_STORE_P016,
+                              * _P016I, _YUVP16, _YUVP16I, _Y216, _Y216I, _Y410 and _Y416: that + 4 * HYDK_YUV16_P01x (the depth; hydk_yuv16.h) */
     uint32_t filter;         /* HYDK_STORE_NV12I, _P016I, _YUVPI, _YUVP16I, _YUY2I and _Y216I only: HYDK_CHROMA_CENTRE or HYDK_CHROMA_LEFT (hydk_chroma.h) */
     /* HYDK_STORE_NV12I, _P016I and _YUVPI only — the PICTURE this LF group is cut from: the chroma sample of the LF group's first pixel (x0 / 2,
      * y0 / 2; src[1] points at it) and the picture's chroma plane, ceil(W / 2) by ceil(H / 2).  The filter reads chroma rows

@@ -40,7 +40,10 @@
 #define HYDK_STORE_FORMS 15 /* the forms of ADDRESSABLE samples — floats, bytes, words — end here, as they have since Y216: what pointers and strides can spell */
 #define HYDK_STORE_RGB10 15 /* 16-bit class: a pixel is one dword of three 10-bit fields, RGB — HydkLfJob.sub the field order, 0 R low, 1 B low (hydk_rgb10.h) */
 #define HYDK_STORE_Y410 16  /* 16-bit class: the same dword holding U, Y, V — 4:4:4, nearest by nature, depth P010 */
-#define HYDK_STORE_COUNT 17 /* all of them: the table's size and the bits of launch_transform's mask above the two integer classes' */
+#define HYDK_STORE_COUNT 17 /* (what "all of them" came to with the dword forms; pinned since, as HYDK_STORE_FORMS is) */
+#define HYDK_STORE_AYUV 17  /* 8-bit class: a pixel is one dword of the bytes V, U, Y and an ignored fourth — 4:4:4, nearest by nature (hydk_quad.h) */
+#define HYDK_STORE_Y416 18  /* 16-bit class: a pixel is one qword of the words U, Y, V and an ignored fourth, MSB-aligned — Y412 / Y416, the depth in matrix as P01x's */
+#define HYDK_STORE_TABLE 19 /* all of them: the table's size and the bits of launch_transform's mask above the two integer classes' */
 
 /* HydkLfJob.use_luts of a YCbCr job is the XYB mode + its form's variant bit: the RGB instances' own test turns it away */
 #define HYDK_VARIANT_NV12 8
@@ -57,6 +60,8 @@
 #define HYDK_VARIANT_Y216I 16384
 #define HYDK_VARIANT_RGB10 32768
 #define HYDK_VARIANT_Y410 65536
+#define HYDK_VARIANT_AYUV 131072
+#define HYDK_VARIANT_Y416 262144
 
 typedef struct HydkStoreForm {
     int cls;           /* HYDK_FMT_*; form 0 belongs to every class */
@@ -68,7 +73,7 @@ typedef struct HydkStoreForm {
 } HydkStoreForm;
 
 HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
-    const HydkStoreForm forms[HYDK_STORE_COUNT] = {
+    const HydkStoreForm forms[HYDK_STORE_TABLE] = {
         {HYDK_FMT_F32, 0, 32, 0, 0, 0},
         {HYDK_FMT_F32, 0, 16, 0, 0, 0},
         {HYDK_FMT_F32, 0, 16, 0, 0, 0},
@@ -86,8 +91,10 @@ HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
         {HYDK_FMT_U16, 1, 16, 0, 1, HYDK_VARIANT_Y216I},
         {HYDK_FMT_U16, 0, 10, 0, 0, HYDK_VARIANT_RGB10},
         {HYDK_FMT_U16, 1, 10, 0, 0, HYDK_VARIANT_Y410},
+        {HYDK_FMT_U8, 1, 8, 0, 0, HYDK_VARIANT_AYUV},
+        {HYDK_FMT_U16, 1, 16, 0, 0, HYDK_VARIANT_Y416},
     };
-    return forms[storage >= 0 && storage < HYDK_STORE_COUNT ? storage : 0];
+    return forms[storage >= 0 && storage < HYDK_STORE_TABLE ? storage : 0];
 }
 
 /* A public sample format taken apart into what a job holds.  ok: a device entry point takes it (else every field is 0).
@@ -104,7 +111,9 @@ typedef struct HydkSampleForm {
 static inline HydkSampleForm hydk_decode_fmt(int f) {
     const HydFmt fmt = hyd_fmt_describe(f);
     HydkSampleForm d = {fmt.device, 0, 0, (uint32_t)(fmt.matrix + 4 * fmt.depth), (uint32_t)fmt.filter, (uint32_t)fmt.sub, fmt.sx, fmt.sy};
-    if (fmt.layout == HYD_LAYOUT_DWORD) {
+    if (fmt.layout == HYD_LAYOUT_QUAD)
+        d.storage = (uint32_t)(fmt.depth ? HYDK_STORE_Y416 : HYDK_STORE_AYUV);
+    else if (fmt.layout == HYD_LAYOUT_DWORD) {
         d.storage = (uint32_t)(fmt.depth ? HYDK_STORE_Y410 : HYDK_STORE_RGB10);
         if (!fmt.depth)
             d.sub = (uint32_t)(f - HYD_FMT_BASE_DWORD);
@@ -125,6 +134,8 @@ static inline int hydk_encode_fmt(HydkSampleForm d) {
         return HYD_FMT_BASE_DWORD + (int)(d.sub & 1u);
     if (d.storage == HYDK_STORE_Y410)
         return HYD_FMT_BASE_DWORD + (int)(d.matrix & 3u) + 4 * HYD_FMT_SUB_444 + 64 * (int)(d.matrix >> 2);
+    if (d.storage == HYDK_STORE_AYUV || d.storage == HYDK_STORE_Y416) /* (AYUV's matrix holds no depth: 0) */
+        return HYD_FMT_BASE_QUAD + (int)(d.matrix & 3u) + 4 * HYD_FMT_SUB_444 + 64 * (int)(d.matrix >> 2);
     if (!form.ycbcr)
         return d.storage == HYDK_STORE_F16 ? HYD_FMT_FLOAT16 : d.storage == HYDK_STORE_BF16 ? HYD_FMT_BFLOAT16 : d.cls;
     if (form.chroma_planes == 0) /* (sub: the byte order in a job, 4:2:2 in a decoded format; neither is in the number) */

@@ -1,6 +1,6 @@
 /*
  * k1_transform_body.h — the body of the transform kernel (kernels.hip, K1), included into k_transform_tokenize, into
- * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16, into k_transform_tokenize_yuy2, into k_transform_tokenize_y216 and into k_transform_tokenize_dword and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
+ * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16, into k_transform_tokenize_yuy2, into k_transform_tokenize_y216, into k_transform_tokenize_dword and into k_transform_tokenize_quad and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
  * and STORE, the kernel's parameters jobs, status, part_info and plog, and everything kernels.hip defines above its K1 section.
  * No include guard: it is function-body text, meant to be included once per kernel.
  */
@@ -12,12 +12,15 @@
      * INTERP: chroma interpolated (hydk_chroma.h) — job.filter says centre- or left-sited, and the job knows the picture it is
      * cut from, since a pixel's chroma neighbours may lie in another LF group or tile of it.  HALF: 2-byte floats, widened on load.
      * DW: a pixel is one dword of three 10-bit fields (hydk_rgb10.h) — RGB10, which is no YCbCr form, and Y410, which is one with
-     * neither planes nor groups: every pixel carries its own chroma */
+     * neither planes nor groups: every pixel carries its own chroma.
+     * QD: a pixel is one group of four samples, the fourth ignored (hydk_quad.h) — AYUV, bytes in a dword, and Y416, words in a qword:
+     * YCbCr 4:4:4 as Y410 is, of whole samples, so neither PK nor DW */
     constexpr HydkStoreForm FORM = hydk_store_form(STORE);
     static_assert(STORE == HYDK_STORE_F32 || FORM.cls == FMT,
-                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16, YUVP16I, Y216, Y216I, RGB10 and Y410");
+                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16, YUVP16I, Y216, Y216I, RGB10 and Y410; AYUV is of the 8-bit class and Y416 of the 16-bit class");
     constexpr bool DW = STORE == HYDK_STORE_RGB10 || STORE == HYDK_STORE_Y410;
-    constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, PK = YUV && FORM.chroma_planes == 0 && !DW, INTERP = FORM.interp;
+    constexpr bool QD = STORE == HYDK_STORE_AYUV || STORE == HYDK_STORE_Y416;
+    constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, PK = YUV && FORM.chroma_planes == 0 && !DW && !QD, INTERP = FORM.interp;
     constexpr bool HALF = FMT == HYDK_FMT_F32 && STORE != HYDK_STORE_F32;
     /* the two-plane forms by name: YUVPI keeps a prefetch, an edge fill and an interpolate loop of its own (through the shared
      * ones its instances measured a few tenths of a percent slower, profiles/ycbcr_loader.txt) */
@@ -29,6 +32,9 @@
     typedef typename std::conditional<HALF, uint16_t, typename SampleOf<FMT>::type>::type sample_t;
     constexpr bool LUTS = XMODE == kXybGather;
     constexpr int kWords = FMT == HYDK_FMT_U8 ? 6 : 12; /* dwords holding 8 packed RGB pixels */
+    /* dwords of the prefetched block row: QD keeps its eight pixels as stored, the fourth sample with them — 8 dwords of bytes, 16 of
+     * words — and drops it at use; every other form's window is the kWords of the packed row */
+    constexpr int kWin = QD ? (FMT == HYDK_FMT_U8 ? 8 : 16) : kWords;
 #if HYDK_K1_PRIO
     __builtin_amdgcn_s_setprio(HYDK_K1_PRIO);
 #endif
@@ -98,8 +104,19 @@
 
     for (int i = t; i < HYDK_MAX_CLUSTERS * kHistW; i += kThreads)
         s_hist[i] = 0;
-    if (FMT == HYDK_FMT_U8)
-        s_lut8[t] = job.in_lut8[t];
+    /* The 8-bit transfer table.  QD's 8-bit instance (AYUV) keeps it in no array of its own: a block of s_rowpass is kS0Block = 64 + 8
+     * floats, and words 64 ... 71 of a block are padding that no row pass, column pass or token walk touches — 32 bytes, sixteen
+     * entries; the table's 256 sit in the padding of channel 0's blocks 0 ... 15, entry v at 16-bit index 128 + v + ((v & 0xF0) << 3)
+     * (byte (v >> 4) * 4 * kS0Block + 256 + 2 * (v & 15)).  That keeps the instance at the static LDS of the 16-bit class. */
+    static_assert(kS0Block == 72, "lut8's index is spelled for blocks of 64 + 8 floats");
+    auto lut8_at = [](uint32_t v) -> uint32_t { return 128u + v + ((v & 0xF0u) << 3); };
+    auto lut8 = [&](uint32_t v) -> uint32_t { return QD ? (uint32_t)((const uint16_t *)s_rowpass)[lut8_at(v)] : (uint32_t)s_lut8[v]; };
+    if (FMT == HYDK_FMT_U8) {
+        if (QD)
+            ((uint16_t *)s_rowpass)[lut8_at((uint32_t)t)] = job.in_lut8[t];
+        else
+            s_lut8[t] = job.in_lut8[t];
+    }
     if (t < 64) {
         /* t as a natural index (kv, kh): where it sits in zig-zag order; t as a zig-zag position: its contexts */
         const int j = t;
@@ -158,7 +175,7 @@
     /* log2 of the pixels one chroma sample spans across and down: the job's subsampling for two planes, 4:2:0 for pairs */
     const int csx = TWO_PLANES ? hydk_planar_sx((int)job.sub) : (int)YUV, csy = TWO_PLANES ? hydk_planar_sy((int)job.sub) : (int)(YUV && !PK);
     /* pairs in one plane (nvrun, prun): kYW dwords of Y and, from chroma row y >> 1, kYW dwords holding the block's four pairs */
-    const bool prun = YUV && !TWO_PLANES && !PK && !DW &&
+    const bool prun = YUV && !TWO_PLANES && !PK && !DW && !QD &&
                       (((uintptr_t)job.src[0] | (uintptr_t)job.src[1] | (uintptr_t)(job.row_stride * (SB / 8))) & 3) == 0;
     /* packed 4:2:2 (pkrun): a block row is four GROUPS — 16 bytes, four dwords — from the row's one plane, when the first group (Y's
      * place in its pair of bytes before src[0]) and the pitch are dword multiples; Y and the four (U, V) pairs are picked out of the
@@ -183,15 +200,16 @@
      * the clamps, at use (phase A below).  pcx: the picture's chroma column of the block's first pixel. */
     const bool irun = (TWO_PLANES ? ylrun : PK ? pkrun : prun) && (!INTERP || ((job.filter == HYDK_CHROMA_CENTRE ? pcx >= 1 : pcx >= 0) && pcx + 4 <= job.pic_cw - 1));
     /* (a dword a pixel, DW: a block row is eight dwords of the row's one plane, 32 bytes; src[0] is dword-aligned and the pitch counts
-     * dwords — hyd_fmt_refusal lets nothing else through — so every whole block row comes that way) */
-    const bool fast = (DW || (YUV ? irun : packed)) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
-    uint32_t nxt[kWords];
+     * dwords — hyd_fmt_refusal lets nothing else through — so every whole block row comes that way.  A group of four a pixel, QD: the same of
+     * eight dwords (AYUV) or eight qwords (Y416), src[0] on a boundary of the pixel's size and the pitch in pixels) */
+    const bool fast = (DW || QD || (YUV ? irun : packed)) && ab < gbw && ab * 8 + 8 <= gw; /* whole block row comes as aligned dwords */
+    uint32_t nxt[kWin];
     /* the window's columns 0 and 5, which sit in no dword of the four between them (YUVPI: of U and of V, column 0 | column 5
      * << 8 of the near row, the same << 16 of the far row; YP16: column 0 | column 5 << 16 of U near, U far, V near, V far) */
     constexpr int kFlank = YUV && !TWO_PLANES ? 4 / kPPD : YP16 ? 4 : 2;
     uint32_t flank[kFlank] = {};
 #pragma unroll
-    for (int k = 0; k < kWords; k++)
+    for (int k = 0; k < kWin; k++)
         nxt[k] = 0;
     /* The window accessor of the forms with pairs in one plane (NV12I, P016I; nearest: columns 1 ... 4 of the near row alone):
      * where chroma sample c (0: U, 1: V) of row r (0: near, 1: far) and column p sits — all the shared loops below know of a
@@ -229,6 +247,22 @@
         return (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
     };
     auto prefetch = [&](int s) {
+        if (QD) {
+            /* the eight pixels as stored in nxt[0 ... kWin): kWin dword loads of one address, which the compiler fuses into two (AYUV) or
+             * four (Y416) global_load_dwordx4 as it does DW's; the hardware takes them at dword alignment, and hyd_fmt_refusal
+             * guarantees the pixel's own; the samples come out at use */
+            if (fast && s * 8 + ar < gh) {
+                /* (the lane's row and block pass through an empty statement, as DW's do and for its reason) */
+                int lane_row = ar, lane_block = ab;
+                asm volatile("" : "+v"(lane_row), "+v"(lane_block));
+                const long long y = py0 + s * 8 + lane_row, x = px0 + lane_block * 8;
+                const char *pq = (const char *)job.src[0] + (y * job.row_stride + x) * (kWin / 2);
+#pragma unroll
+                for (int k = 0; k < kWin; k++)
+                    nxt[k] = HYDK_GLOBAL(const uint32_t, pq)[k];
+            }
+            return;
+        }
         if (DW) {
             /* the eight pixels as stored in nxt[0 ... 7]: eight dword loads of one address, which the compiler fuses into two
              * global_load_dwordx4 as it does PK16's (the hardware takes them at dword alignment); the fields come out at use */
@@ -522,7 +556,7 @@
                     }
                 }
                 prefetch(s + 1);
-            } else if (fast || INTERP || PK16 || DW) { /* (PK16, DW: nearest rows that did not come as dwords fill the window too) */
+            } else if (fast || INTERP || PK16 || DW || QD) { /* (PK16, DW, QD: nearest rows that did not come as dwords fill the window too) */
                 const int nvalid = row_ok ? min(8, gw - ab * 8) : 0;
                 /* Interpolated rows that did not come as dwords — the picture's first and last chroma columns, a ragged last
                  * block, shifted bases, odd pitches — fill the same window sample by sample, here, every column clamped to the
@@ -750,6 +784,24 @@
                                 nxt[i] = pd[i];
                     }
                 }
+                /* A group of four a pixel.  Rows that did not come as dwords — a ragged last block, and rows past the picture's last —
+                 * fill nxt pixel by pixel, a dword or a qword each, with the pixels the row has, and zero elsewhere: nothing outside
+                 * the W pixels of a row is read.  Either way Y, U and V come out of each pixel as hydk_quad.h defines it — three
+                 * bytes of a dword under the 8-bit conversion, three words of two dwords under the 16-bit one — and become an
+                 * interleaved RGB row of the class; the fourth sample is in the registers and in no expression. */
+                if (QD && !fast) {
+#pragma unroll
+                    for (int k = 0; k < kWin; k++)
+                        nxt[k] = 0;
+                    if (row_ok) {
+                        constexpr int kDPP = kWin / 8; /* dwords a pixel */
+                        const uint32_t *pq = (const uint32_t *)job.src[0] + ((long long)y * job.row_stride + x0) * kDPP;
+#pragma unroll
+                        for (int k = 0; k < kWin; k++)
+                            if (k / kDPP < nvalid)
+                                nxt[k] = pq[k];
+                    }
+                }
                 /* YP16 rows that did not come as dwords: each plane's window of six words filled word by word, the same clamps, into
                  * the registers the dword rows use, as stored */
                 if (YP16 && INTERP && !fast) {
@@ -821,7 +873,22 @@
                             cvt[si / kSPD] |= rgb[ch] << (SB * (si % kSPD));
                         }
                     };
-                    if (DW) {
+                    if (QD) {
+                        /* pixel i is dword i, or dwords 2 i and 2 i + 1: packed as convert packs */
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            uint32_t rgb[3];
+                            if (SB == 8)
+                                hydk_ayuv_to_rgb(yuv, nxt[i < kWin ? i : 0], rgb);
+                            else
+                                hydk_y416_to_rgb(yuv, nxt[2 * i < kWin ? 2 * i : 0], nxt[2 * i + 1 < kWin ? 2 * i + 1 : 0], rgb);
+#pragma unroll
+                            for (int ch = 0; ch < 3; ch++) {
+                                const int si = i * 3 + ch;
+                                cvt[si / kSPD] |= rgb[ch] << (SB * (si % kSPD));
+                            }
+                        }
+                    } else if (DW) {
                         /* pixel i is dword i: its three fields to an RGB16 pixel, packed as convert packs */
                         const int order = (int)job.sub;
 #pragma unroll
@@ -906,7 +973,7 @@
                             convert(i, near_get(0, i), near_get(1, i));
                     }
                 }
-                uint32_t(&w)[kWords] = YUV || DW ? cvt : nxt; /* this strip's pixels, fetched a strip ago */
+                uint32_t(&w)[kWords] = YUV || DW ? cvt : reinterpret_cast<uint32_t(&)[kWords]>(nxt); /* this strip's pixels, fetched a strip ago (QD's wider window is never w) */
                 /* which form of the transfer curve this wavefront's 16-bit samples need (wave-uniform) */
                 int curve = kCurveBoth;
                 if (FMT == HYDK_FMT_U16 && !LUTS) {
@@ -935,7 +1002,7 @@
 #pragma unroll
                                 for (int k = 0; k < 3 * P; k++) {
                                     const int si = i0 * 3 + k;
-                                    lin[k] = s_lut8[(w[si >> 2] >> (8 * (si & 3))) & 0xFF];
+                                    lin[k] = lut8((w[si >> 2] >> (8 * (si & 3))) & 0xFF);
                                 }
                             } else {
 #pragma unroll
@@ -998,7 +1065,7 @@
                         for (int ch = 0; ch < 3; ch++) {
                             const int si = i * 3 + ch;
                             if (FMT == HYDK_FMT_U8)
-                                rgb[ch] = s_lut8[(w[si >> 2] >> (8 * (si & 3))) & 0xFF];
+                                rgb[ch] = lut8((w[si >> 2] >> (8 * (si & 3))) & 0xFF);
                             else {
                                 const uint32_t v = (w[si >> 1] >> (16 * (si & 1))) & 0xFFFF;
                                 rgb[ch] = LUTS ? (uint32_t)job.in_lut16[v] : (xyb_gmask(XMODE) >> ch & 1) ? (uint32_t)HYDK_GLOBAL(const uint16_t, job.in_lut16)[v] : input_lut16_eval_as<CURVE>(v);
@@ -1020,7 +1087,7 @@
                         row_to_xyb(std::integral_constant<int, kCurveNone>());
                     else
                         row_to_xyb(std::integral_constant<int, kCurveBoth>());
-                    if (INTERP || PK16 || DW) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
+                    if (INTERP || PK16 || DW || QD) { /* (a ragged last block: edge padding is XYB = 0, format.c:182-191) */
 #pragma unroll
                         for (int i = 0; i < 8; i++)
                             if (i >= nvalid)
@@ -1076,7 +1143,7 @@
 #pragma unroll
                             for (int ch = 0; ch < 3; ch++) {
                                 if (FMT == HYDK_FMT_U8)
-                                    rgb[ch] = s_lut8[rgb[ch]];
+                                    rgb[ch] = lut8(rgb[ch]);
                                 else
                                     rgb[ch] = LUTS ? job.in_lut16[rgb[ch]] : input_lut16_eval(rgb[ch], job.linear_light);
                             }

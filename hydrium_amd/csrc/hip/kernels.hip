@@ -621,7 +621,8 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
  * Packed 4:2:2, HYDK_STORE_YUY2 and HYDK_STORE_YUY2I (YUYV, UYVY, YVYU, VYUY in one plane; hydk_yuy2.h), are k_transform_tokenize_yuy2's,
  * on the same grounds; and the same groups in 16-bit words, HYDK_STORE_Y216 and HYDK_STORE_Y216I (Y210, Y212, Y216; hydk_y216.h), are
  * k_transform_tokenize_y216's.  A pixel in one dword of three 10-bit fields, HYDK_STORE_RGB10 and HYDK_STORE_Y410 (RGB10A2, BGR10A2, Y410;
- * hydk_rgb10.h), are k_transform_tokenize_dword's. */
+ * hydk_rgb10.h), are k_transform_tokenize_dword's.  A pixel in one group of four samples, HYDK_STORE_AYUV of the 8-bit class and HYDK_STORE_Y416
+ * of the 16-bit class (AYUV, Y412, Y416; hydk_quad.h), are k_transform_tokenize_quad's. */
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
@@ -631,6 +632,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     static_assert(STORE != HYDK_STORE_YUY2 && STORE != HYDK_STORE_YUY2I, "the packed 4:2:2 instances are k_transform_tokenize_yuy2's");
     static_assert(STORE != HYDK_STORE_Y216 && STORE != HYDK_STORE_Y216I, "the packed 4:2:2 instances of 16-bit words are k_transform_tokenize_y216's");
     static_assert(STORE != HYDK_STORE_RGB10 && STORE != HYDK_STORE_Y410, "the instances of a dword a pixel are k_transform_tokenize_dword's");
+    static_assert(STORE != HYDK_STORE_AYUV && STORE != HYDK_STORE_Y416, "the instances of four samples a pixel are k_transform_tokenize_quad's");
 #include "k1_transform_body.h"
 }
 
@@ -688,6 +690,16 @@ __global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_dword(const 
                                                                           uint2 *part_info, int plog) {
     static_assert(STORE == HYDK_STORE_RGB10 || STORE == HYDK_STORE_Y410, "Y216 and Y216I are k_transform_tokenize_y216's");
     constexpr int FMT = HYDK_FMT_U16;
+#include "k1_transform_body.h"
+}
+
+/* A pixel in one group of four samples, the fourth ignored — bytes in a dword (AYUV, the 8-bit class) and words in a qword (Y416,
+ * the 16-bit class), YCbCr 4:4:4: four waves per SIMD as the other YCbCr forms of either class. */
+template <int XMODE, int STORE>
+__global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_quad(const HydkLfJob *__restrict__ jobs, uint32_t *status,
+                                                                         uint2 *part_info, int plog) {
+    static_assert(STORE == HYDK_STORE_AYUV || STORE == HYDK_STORE_Y416, "RGB10 and Y410 are k_transform_tokenize_dword's");
+    constexpr int FMT = STORE == HYDK_STORE_AYUV ? HYDK_FMT_U8 : HYDK_FMT_U16;
 #include "k1_transform_body.h"
 }
 
@@ -2462,6 +2474,10 @@ static K1Fn k1_of_mode(int fmt, int storage) {
         return k_transform_tokenize_dword<A, HYDK_STORE_RGB10>;
     case HYDK_STORE_Y410:
         return k_transform_tokenize_dword<A, HYDK_STORE_Y410>;
+    case HYDK_STORE_AYUV:
+        return k_transform_tokenize_quad<A, HYDK_STORE_AYUV>;
+    case HYDK_STORE_Y416:
+        return k_transform_tokenize_quad<A, HYDK_STORE_Y416>;
     }
     return fmt == HYDK_FMT_U8    ? k_transform_tokenize<HYDK_FMT_U8, XM>
            : fmt == HYDK_FMT_U16 ? k_transform_tokenize<HYDK_FMT_U16, XM>
@@ -2487,7 +2503,7 @@ static K1Fn k1_instance(int fmt, int storage, int xmode) {
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream) {
     const dim3 grid((num_slots * HYDK_GROUPS_PER_LFG) << plog), block(kThreads);
-    for (int bit = 0; bit < HYDK_FMT_F32 + HYDK_STORE_COUNT; bit++)
+    for (int bit = 0; bit < HYDK_FMT_F32 + HYDK_STORE_TABLE; bit++)
         if (fmt_mask & (1u << bit)) {
             const int storage = bit < HYDK_FMT_F32 ? HYDK_STORE_F32 : bit - HYDK_FMT_F32;
             const K1Fn k1 = k1_instance(bit < HYDK_FMT_F32 ? bit : hydk_store_form(storage).cls, storage, xmode);

@@ -59,6 +59,16 @@
  * DWORD: src[0] == src[1] == src[2], the first dword, on a 4-byte boundary; the pixel stride is 1 and the row stride the pitch in
  * dwords, of either sign (HYD_FMT_DWORD_LAYOUT_MSG).  Storage forms of the 16-BIT class: an RGB field v stands for the 16-bit
  * sample nearest to v / 1023, a Y410 field for the P010 sample v << 6, so that a Y410 picture is the I410 picture of its fields.
+ *
+ * 524296 ... 524299, 524424 ... 524427 and 524488 ... 524491 name pictures whose PIXEL IS ONE GROUP OF FOUR SAMPLES — Y, U, V and a
+ * fourth that is ignored — in device memory, 4:4:4 (hip/hydk_quad.h): 524288 + matrix + 4 * 2 + 64 * depth.  Depth 0, AYUV (VA-API
+ * AYUV / XYUV, DRM XYUV8888, ffmpeg vuya / vuyx): a dword of the bytes V, U, Y, A — V in bits 0 ... 7, U in 8 ... 15, Y in 16 ... 23.
+ * Depth 2 and 3, Y412 and Y416 (XV36, XV48): a qword of the words U, Y, V, A, MSB-aligned — U in bits 0 ... 15, Y in 16 ... 31, V in
+ * 32 ... 47.  Depth 1 names nothing: the 10-bit surface is Y410 at 131144.  A SAMPLE IS THE GROUP: src[0] == src[1] == src[2], the
+ * first pixel, on a boundary of the pixel's size (4 or 8 bytes); the pixel stride is 1 and the row stride the pitch in pixels, of
+ * either sign (HYD_FMT_QUAD_LAYOUT_MSG).  AYUV is a storage form of the 8-BIT class, the I444 picture of its three bytes; Y412 and
+ * Y416 of the 16-BIT class, the words as stored under the P01x conversion of that depth, so a Y416 picture is the I416 picture of
+ * its three words.
  */
 #ifndef HYD_SAMPLE_FMT_H_
 #define HYD_SAMPLE_FMT_H_
@@ -77,19 +87,22 @@
  * each in 16-bit words, LSB-aligned; 8192 — Y, U and V bytes packed in one plane, 4:2:2 (the subsampling bits are 0, depth 0 only);
  * 32768 — the same groups in 16-bit words, MSB-aligned (the subsampling bits are 0, depth 1 ... 3 only); 131072 — Y, U and V as
  * 10-bit fields of one dword a pixel, 4:4:4 (subsampling 2, filter 0, depth 1 only), and at its depth-0 corner the two RGB orders of
- * the same dword. */
+ * the same dword; 524288 — Y, U, V and an ignored fourth sample in one group a pixel, 4:4:4 (subsampling 2, filter 0): bytes in a
+ * dword at depth 0, MSB-aligned 16-bit words in a qword at depth 2 and 3 (depth 1 names nothing: that surface is Y410). */
 #define HYD_FMT_BASE_PAIRS 16
 #define HYD_FMT_BASE_PLANES 512
 #define HYD_FMT_BASE_PLANES16 2048
 #define HYD_FMT_BASE_PACKED 8192
 #define HYD_FMT_BASE_PACKED16 32768
 #define HYD_FMT_BASE_DWORD 131072
+#define HYD_FMT_BASE_QUAD 524288
 /* HydFmt.layout */
 #define HYD_LAYOUT_RGB 0    /* three samples a pixel, any strides */
 #define HYD_LAYOUT_PAIRS 1  /* a Y plane and a plane of (U, V) pairs */
 #define HYD_LAYOUT_PLANES 2 /* Y, U and V planes of their own */
 #define HYD_LAYOUT_PACKED 3 /* Y and chroma in one plane: groups of Y, U, Y, V bytes (or 16-bit words: HydFmt.bytes) in one of four orders */
 #define HYD_LAYOUT_DWORD 4  /* a pixel is one dword of three 10-bit fields: one pointer three times over, a sample is the dword */
+#define HYD_LAYOUT_QUAD 5   /* a pixel is one group of four samples, the fourth ignored (bytes in a dword, or words in a qword: HydFmt.bytes 4 or 8): one pointer three times over, a sample is the group */
 /* HydFmt.sub */
 #define HYD_FMT_SUB_420 0
 #define HYD_FMT_SUB_422 1
@@ -124,6 +137,19 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
         d.is_float = fmt >= HYD_FMT_FLOAT32;
         d.bytes = fmt == HYD_FMT_UINT8 ? 1 : fmt == HYD_FMT_FLOAT32 ? 4 : 2;
         d.bits = 8 * d.bytes;
+        return d;
+    }
+    if (fmt >= HYD_FMT_BASE_QUAD) { /* 524288 + matrix + 4 * 2 + 64 * depth: 4:4:4, no filter, depth 0, 2, 3 */
+        const int n = fmt - HYD_FMT_BASE_QUAD, depth = n >> 6;
+        if ((n & 60) != 4 * HYD_FMT_SUB_444 || depth == 1 || depth > 3)
+            return d;
+        d.device = 1;
+        d.bytes = depth ? 8 : 4;
+        d.layout = HYD_LAYOUT_QUAD;
+        d.matrix = n & 3;
+        d.sub = HYD_FMT_SUB_444;
+        d.depth = depth;
+        d.bits = depth == 0 ? 8 : depth == 2 ? 12 : 16;
         return d;
     }
     if (fmt >= HYD_FMT_BASE_DWORD) { /* 131072, 131073: the RGB orders; 131072 + matrix + 4 * 2 + 64 * 1: Y410 */
@@ -192,7 +218,8 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
  * the layout of src — pairs want unit pixel stride and V one sample behind U (and words on 2-byte boundaries), planes of
  * 16-bit words want their three addresses on 2-byte boundaries, packed 4:2:2 wants pixel stride 2 and U and V in the bytes beside
  * Y in one of the four orders (packed words: the same in words, on 2-byte boundaries), a dword a pixel wants pixel stride 1 and
- * one dword-aligned pointer three times over, every other format takes any layout; then
+ * one dword-aligned pointer three times over, a group of four a pixel the same on a boundary of the group's size (4 or 8 bytes),
+ * every other format takes any layout; then
  * the chroma pitch —
  * a plane each has no layout to hold (three free pointers), but its pixel_stride argument is the chroma planes' pitch in
  * samples, of either sign: one shorter than a chroma row of the picture the call names, `width` pixels across — the habitual
@@ -205,6 +232,7 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
 #define HYD_FMT_PACKED_LAYOUT_MSG "YUY2/UYVY wants pixel_stride 2 and U and V in the bytes beside Y"
 #define HYD_FMT_PACKED16_LAYOUT_MSG "Y210/Y216 wants pixel_stride 2 and U and V in the words beside Y"
 #define HYD_FMT_DWORD_LAYOUT_MSG "RGB10A2/Y410 wants pixel_stride 1 and three equal pointers on a 4-byte boundary"
+#define HYD_FMT_QUAD_LAYOUT_MSG "AYUV/Y416 wants pixel_stride 1 and three equal pointers on a boundary of the pixel's size"
 /* what hydamd_encode_image_multi says to a format with interpolated chroma */
 #define HYD_FMT_NV12_SHARDED_MSG "interpolated chroma is not sharded: a shard does not hold its neighbour's chroma rows"
 /* The byte order of a packed 4:2:2 picture, read off its pointers: 0 YUYV (U at +1, V at +3), 1 YVYU (+3, +1), 2 UYVY (-1, +1),
@@ -242,6 +270,9 @@ static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptr
     } else if (src && d.layout == HYD_LAYOUT_DWORD) {
         if (pixel_stride != 1 || src[1] != src[0] || src[2] != src[0] || ((size_t)src[0] & 3u))
             return HYD_FMT_DWORD_LAYOUT_MSG;
+    } else if (src && d.layout == HYD_LAYOUT_QUAD) {
+        if (pixel_stride != 1 || src[1] != src[0] || src[2] != src[0] || ((size_t)src[0] & (size_t)(d.bytes - 1)))
+            return HYD_FMT_QUAD_LAYOUT_MSG;
     }
     if (d.layout == HYD_LAYOUT_PLANES) {
         const size_t pitch = pixel_stride < 0 ? (size_t)0 - (size_t)pixel_stride : (size_t)pixel_stride;
@@ -256,7 +287,8 @@ static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptr
  * theirs.  Pairs: the one chroma plane has the Y plane's pitch and two samples for every two columns, so sample x0 of the row.
  * A plane each: the pitch is pixel_stride, sample x0 >> sx.  Packed 4:2:2: all three pointers move by y0 rows and 2 x0 samples
  * (bytes, or 16-bit words), the group of pixel x0.  x0 must be even, and y0 where sy is 1 (every origin the library computes is a multiple of 256).
- * A dword a pixel: all three pointers move by y0 rows and x0 dwords; any x0 and y0, since 4:4:4 has no parity to keep. */
+ * A dword a pixel, and a group of four samples a pixel: all three pointers move by y0 rows and x0 pixels (dwords, or qwords); any
+ * x0 and y0, since 4:4:4 has no parity to keep. */
 static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride, size_t x0,
                                   size_t y0, const void *origin[3]) {
     const HydFmt d = hyd_fmt_describe(fmt);
@@ -264,7 +296,7 @@ static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t r
     ptrdiff_t luma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0 * pixel_stride, chroma = luma;
     if (d.layout == HYD_LAYOUT_PACKED) {
         luma = chroma = (ptrdiff_t)y0 * row_stride + 2 * (ptrdiff_t)x0;
-    } else if (d.layout == HYD_LAYOUT_DWORD) {
+    } else if (d.layout == HYD_LAYOUT_DWORD || d.layout == HYD_LAYOUT_QUAD) {
         luma = chroma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;
     } else if (d.layout != HYD_LAYOUT_RGB) {
         luma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;

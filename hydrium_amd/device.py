@@ -34,7 +34,9 @@ BFLOAT16 = 4
 # names: I010, I210, I410 ...); base 8192: PACKED 4:2:2, 8 bits in one plane of Y, U, Y, V groups (YUY2 / UYVY / YVYU / VYUY: the byte order
 # is what the three pointers spell), subsampling and depth 0; base 32768: the same groups in 16-bit words of 10, 12 or 16 bits, MSB-aligned
 # (Y210 / Y212 / Y216), subsampling 0 and depth 1, 2, 3; base 131072: ONE DWORD A PIXEL, three 10-bit fields — Y410 at subsampling 2 (4:4:4)
-# and depth 1, and at the base's depth-0 corner RGB10A2 (131072) and BGR10A2 (131073), which are no YCbCr.  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
+# and depth 1, and at the base's depth-0 corner RGB10A2 (131072) and BGR10A2 (131073), which are no YCbCr; base 524288: FOUR SAMPLES A PIXEL, Y, U, V and
+# an ignored fourth, subsampling 2 (4:4:4) — AYUV (bytes in a dword) at depth 0, Y412 / Y416 (MSB-aligned words in a qword) at depth 2, 3; depth 1
+# names nothing (that surface is Y410).  matrix 0 ... 3: BT.709 limited range (HD video), BT.709 full, BT.601 limited (SD video), BT.601
 # full (what a JPEG decoder leaves: JFIF).  filter: nearest, or INTERPOLATED for centre-sited chroma (C: JPEG / JFIF, MPEG-1) or
 # left-sited (L: MPEG-2, H.264, HEVC, AV1 default) — csrc/hip/hydk_chroma.h; 4:4:4 has nearest chroma only.
 CHROMA_FILTERS = {"nearest": 0, "centre": 1, "center": 1, "left": 2}
@@ -48,7 +50,7 @@ def ycbcr_fmt(base: int, matrix: int = 0, sub: int = 0, filt: int = 0, depth: in
 
 def ycbcr_fields(fmt: int):
     """(base, matrix, subsampling, filter, depth) of a YCbCr sample format"""
-    base = 131072 if fmt >= 131072 else 32768 if fmt >= 32768 else 8192 if fmt >= 8192 else 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
+    base = 524288 if fmt >= 524288 else 131072 if fmt >= 131072 else 32768 if fmt >= 32768 else 8192 if fmt >= 8192 else 2048 if fmt >= 2048 else 512 if fmt >= 512 else 16
     n = int(fmt) - base
     return base, n & 3, (n >> 2) & 3, (n >> 4) & 3, n >> 6
 
@@ -56,7 +58,8 @@ def ycbcr_fields(fmt: int):
 _stems = [("NV12", 16, 0, 0)] + [(f"P0{b}", 16, 0, d) for b, d in P016_DEPTHS.items()] + \
     [(f"I{s}", 512, k, 0) for s, k in PLANAR_SUBSAMPLINGS.items()] + \
     [(f"I{s[2]}{b}", 2048, k, d) for b, d in P016_DEPTHS.items() for s, k in PLANAR_SUBSAMPLINGS.items()] + [("YUY2", 8192, 0, 0)] + \
-    [(f"Y2{b}", 32768, 0, d) for b, d in P016_DEPTHS.items()] + [("Y410", 131072, 2, 1)]
+    [(f"Y2{b}", 32768, 0, d) for b, d in P016_DEPTHS.items()] + [("Y410", 131072, 2, 1)] + \
+    [("AYUV", 524288, 2, 0), ("Y412", 524288, 2, 2), ("Y416", 524288, 2, 3)]
 for _stem, _base, _sub, _depth in _stems:  # NV12_BT709 = 16 ... I416_BT601_FULL = 2251, YUY2_BT709 = 8192 ..., Y210_BT709 = 32832 ..., as include/hydrium_amd.h has them
     for _infix, _filter in (("", 0), ("C", 1), ("L", 2)):
         for _matrix, _name in enumerate(("BT709", "BT709_FULL", "BT601", "BT601_FULL")):
@@ -80,6 +83,9 @@ RGB10A2, BGR10A2 = 131072, 131073
 RGB10_ORDERS = {"rgb": RGB10A2, "bgr": BGR10A2}
 Y410_FORMATS = tuple(ycbcr_fmt(131072, m, 2, 0, 1) for m in range(4))
 DWORD_FAMILY = (RGB10A2, BGR10A2) + Y410_FORMATS
+# four samples a pixel, the fourth ignored: AYUV_BT709 = 524296 ..., Y412_BT709 = 524424 ..., Y416_BT709 = 524488 ...
+AYUV_FORMATS, Y412_FORMATS, Y416_FORMATS = (tuple(ycbcr_fmt(524288, m, 2, 0, d) for m in range(4)) for d in (0, 2, 3))
+QUAD_FAMILY = AYUV_FORMATS + Y412_FORMATS + Y416_FORMATS
 
 
 def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
@@ -426,6 +432,85 @@ class Y410(Rgb10):
         self._surface(surface, width, Y410_FORMATS[ycbcr_fields(matrix)[1]])
 
 
+class Ayuv(Nv12):
+    """An AYUV picture in device memory — packed 4:4:4 YCbCr of 8 bits, one dword a pixel holding the bytes V, U, Y, A (DXGI AYUV,
+    VA-API AYUV / XYUV, DRM XYUV8888, ffmpeg vuya / vuyx): what a decoder leaves for 4:4:4 8-bit video — accepted wherever a Y410
+    object is.  The picture is the I444 picture of the three bytes; the fourth is ignored.
+
+    ``surface``: 2-D tensor of a 4-byte integer dtype, H rows with unit element stride, at least ``width`` pixels a row; or a
+    (H, at least width, 4) tensor of a 1-byte integer dtype with unit last stride and pixel stride 4, whose row stride is a whole
+    number of pixels.  Its first pixel sits on a 4-byte boundary; its row stride is the pitch.  ``width``: the picture's width in
+    pixels.  ``matrix``: one of NV12_FORMATS (the matrix and range) or one of AYUV_FORMATS.  A crop starts anywhere:
+    surface[y0:, x0:]."""
+
+    pixel_stride = 1  # a sample is the group
+    _group_bytes = 4
+    _kind = "AYUV"
+
+    def __init__(self, surface, width: int, matrix: int = NV12_BT709):
+        matrix = int(matrix)
+        if matrix not in AYUV_FORMATS and matrix not in NV12_FORMATS:
+            raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL (or an AYUV format)")
+        self._surface(surface, width, AYUV_FORMATS[ycbcr_fields(matrix)[1]])
+
+    def _surface(self, surface, width, fmt):
+        """the shape, stride, pitch and alignment rules of a surface of one group of four samples a pixel"""
+        group, kind = self._group_bytes, self._kind
+        name = str(surface.dtype).rpartition(".")[2]
+        if name.startswith(("float", "complex", "bfloat", "bool")) or surface.dim() not in (2, 3) or \
+                surface.element_size() != (group if surface.dim() == 2 else group // 4):
+            raise ValueError(f"an {kind} surface is (H, at least width) pixels of a {group}-byte integer dtype, or (H, at least width, 4) "
+                             f"samples of a {group // 4}-byte integer dtype")
+        if surface.dim() == 3 and (surface.shape[2] != 4 or surface.stride(2) != 1 or surface.stride(1) != 4):
+            raise ValueError(f"an {kind} surface of samples has four to a pixel, unit sample stride and pixel stride 4")
+        if surface.dim() == 2 and surface.stride(1) != 1:
+            raise ValueError(f"an {kind} surface has unit element stride")
+        h, row = surface.shape[:2]
+        width = int(width)
+        if h < 1 or width < 1 or row < width:
+            raise ValueError(f"a row of an {kind} picture is width pixels")
+        per = 1 if surface.dim() == 2 else 4  # elements a pixel
+        if int(surface.stride(0)) % per:
+            raise ValueError(f"the pitch of an {kind} surface is a whole number of pixels")
+        if surface.data_ptr() % group:
+            raise ValueError(f"an {kind} surface starts on a {group}-byte boundary")
+        self.surface, self.sample_fmt = surface, int(fmt)
+        self.height, self.width = int(h), width
+        pitch = int(surface.stride(0)) // per
+        self.pitch = pitch if h > 1 else max(pitch, width)  # in pixels
+
+    @classmethod
+    def from_surface(cls, *args, **kwargs):
+        raise TypeError(f"{cls.__name__} takes its surface")
+
+    def pointers(self):
+        """src[0 ... 2] of the C API: the first pixel, three times over."""
+        p = self.surface.data_ptr()
+        return [p, p, p]
+
+
+class Y416(Ayuv):
+    """A Y412 or Y416 picture in device memory — packed 4:4:4 YCbCr of 12 or 16 bits, one qword a pixel holding the 16-bit words
+    U, Y, V, A, MSB-aligned (XV36 / XV48, DRM XVYU12_16161616 / XVYU16161616) — accepted wherever an Ayuv object is.  The words
+    count as stored; a Y416 picture is the I416 picture of the three words, and the fourth is ignored.
+
+    ``surface``: 2-D tensor of an 8-byte integer dtype, or a (H, at least width, 4) tensor of a 2-byte integer dtype, under Ayuv's
+    rules with an 8-byte boundary.  ``width``, ``matrix`` (or one of Y412_FORMATS / Y416_FORMATS): as Ayuv's.  ``depth``: 12 or 16."""
+
+    _group_bytes = 8
+    _kind = "Y416"
+
+    def __init__(self, surface, width: int, matrix: int = NV12_BT709, depth: int = 16):
+        matrix = int(matrix)
+        if depth not in (12, 16):
+            raise ValueError("depth is 12 or 16 (10 bits: Y410)")
+        formats = Y412_FORMATS if depth == 12 else Y416_FORMATS
+        if matrix not in formats and matrix not in NV12_FORMATS:
+            raise ValueError("matrix is one of NV12_BT709, NV12_BT709_FULL, NV12_BT601, NV12_BT601_FULL (or a format of that depth)")
+        self._surface(surface, width, formats[ycbcr_fields(matrix)[1]])
+        self.depth = int(depth)
+
+
 class PlanarYuv16(PlanarYuv):
     """A planar YCbCr picture of 16-bit words in device memory — I010, I210, I410, I012 ... I416: PlanarYuv's three planes as
     tensors of a 2-byte integer dtype, ``depth`` 10, 12 or 16 significant bits LSB-aligned (bits above the depth are ignored) —
@@ -443,7 +528,7 @@ class PlanarYuv16(PlanarYuv):
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
     float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
-    An Nv12, P016, PlanarYuv, PlanarYuv16, PackedYuv, PackedYuv16, Rgb10 or Y410 object: its own format."""
+    An Nv12, P016, PlanarYuv, PlanarYuv16, PackedYuv, PackedYuv16, Rgb10, Y410, Ayuv or Y416 object: its own format."""
     if isinstance(t, Nv12):
         return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]

@@ -354,7 +354,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever NV12 is, and beside NV12, P010 and RGB pictures in one hydamd_encode_mixed_formats launch group.
  * hydamd_encode_image_multi takes the 12 nearest forms and refuses the 16 interpolated ones as it does NV12's (a 4:2:2 window
  * also crosses into an LF group another shard owns); the host-pointer entry points refuse all 28 with "Invalid Sample Format".
- * Out of scope: NV21 and NV16; packed AYUV; U and V planes of different pitches; top-left siting; host-pointer
+ * Out of scope: NV21 and NV16; U and V planes of different pitches; top-left siting; host-pointer
  * input; cross-shard interpolation.  (I010 and deeper planes: the next section; packed YUY2 / UYVY: the one after it.)
  */
 #define HYDAMD_I420_BT709 512
@@ -550,7 +550,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever NV12 is, and beside every other family — and pictures of different byte orders — in one
  * hydamd_encode_mixed_formats launch group.  hydamd_encode_image_multi takes the 4 nearest forms and refuses the 8 interpolated
  * ones as it does I422C / I422L; the host-pointer entry points refuse all 12 with "Invalid Sample Format".
- * Out of scope: AYUV (packed 4:4:4 of bytes; Y410 is the section after the next); 4:4:0 planes, rocJPEG's other native form
+ * Out of scope: 4:4:0 planes, rocJPEG's other native form
  * (subsampling 3 of the planar family names nothing); host-pointer input; cross-shard interpolation.
  */
 #define HYDAMD_YUY2_BT709 8192
@@ -602,7 +602,7 @@ HYDAMD_EXPORT int hydamd_begin_frame(HydAmdContext *ctx, unsigned num_presets);
  * Accepted wherever YUY2 is, and beside every other family — and pictures of different word orders — in one
  * hydamd_encode_mixed_formats launch group.  hydamd_encode_image_multi takes the 12 nearest forms and refuses the 24 interpolated
  * ones as it does YUY2C / YUY2L; the host-pointer entry points refuse all 36 with "Invalid Sample Format".
- * Out of scope: Y416 and AYUV (packed 4:4:4 of words and bytes; Y410 is the next section); v210; NV16 / NV24 / P210; LSB-aligned packed words; host-pointer input;
+ * Out of scope: v210; NV16 / NV24 / P210; LSB-aligned packed words; host-pointer input;
  * cross-shard interpolation.
  */
 #define HYDAMD_PACKED16_STEM(P, F, D) \
@@ -623,7 +623,7 @@ enum {
  *   HYDAMD_RGB10A2   131072          R in bits 0..9, G in 10..19, B in 20..29
  *   HYDAMD_BGR10A2   131073          B in bits 0..9, G in 10..19, R in 20..29
  *   HYDAMD_Y410_*    131144..131147  = 131072 + matrix + 4 * 2 (4:4:4) + 64 * 1 (10 bits); U in bits 0..9, Y in 10..19, V in 20..29
- * Six numbers; every other number from 131072 up names nothing.  Bits 30 and 31 are ignored.
+ * Six numbers; every other number from 131072 up to 524287 names nothing.  Bits 30 and 31 are ignored.
  *
  * How such a picture is named — A SAMPLE IS THE DWORD:
  *   src[0] == src[1] == src[2]   the first dword, on a 4-byte boundary
@@ -642,8 +642,8 @@ enum {
  *
  * Accepted wherever Y210 is, and beside every other family in one hydamd_encode_mixed_formats launch group.  There is no chroma
  * filter, so hydamd_encode_image_multi takes all six; the host-pointer entry points refuse all six with "Invalid Sample Format".
- * Out of scope: Y416 and AYUV (packed 4:4:4 of words and bytes); R11G11B10F; v210; PQ / HLG / BT.2020; an alpha in bits 30..31;
- * host-pointer input.
+ * Out of scope: R11G11B10F; v210; PQ / HLG / BT.2020; an alpha in bits 30..31; host-pointer input.  (The 8-, 12- and 16-bit
+ * siblings of Y410 — AYUV, Y412, Y416 — are the next section.)
  */
 enum {
     HYDAMD_RGB10A2 = 131072,
@@ -655,11 +655,61 @@ enum {
 };
 
 /*
+ * FOUR SAMPLES A PIXEL, DEVICE pixels: AYUV, Y412 and Y416 — packed 4:4:4 YCbCr, a pixel is one group of Y, U, V and a fourth
+ * sample that is ignored.  AYUV (DXGI AYUV, VA-API AYUV / XYUV, DRM XYUV8888, ffmpeg vuya / vuyx) is what a decoder leaves for
+ * 4:4:4 8-bit video, Y412 (XV36, DRM XVYU12_16161616) and Y416 (XV48, DRM XVYU16161616) for 12 and 16 bits; with Y410 of the section
+ * above they are the packed 4:4:4 surfaces DXGI, VA-API, DRM and AMF hand out.  Read by the transform kernel as they are, without a
+ * de-interleave pass into three planes.
+ *   HYDAMD_AYUV_*   524296..524299  = 524288 + matrix + 4 * 2 (4:4:4)           one DWORD: V in bits 0..7, U in 8..15, Y in 16..23
+ *                                                                                (bytes V, U, Y, A); bits 24..31 ignored
+ *   HYDAMD_Y412_*   524424..524427  = 524288 + matrix + 4 * 2 + 64 * 2 (12 bits) one QWORD: U in bits 0..15, Y in 16..31, V in 32..47
+ *                                                                                (words U, Y, V, A), MSB-aligned; bits 48..63 ignored
+ *   HYDAMD_Y416_*   524488..524491  = 524288 + matrix + 4 * 2 + 64 * 3 (16 bits) the same qword, 16 significant bits
+ * Twelve numbers; depth 1 (524360..524363) names nothing — the 10-bit surface is Y410 at 131144 — and so does every other number
+ * from 524288 up.
+ *
+ * How such a picture is named — A SAMPLE IS THE GROUP, exactly as Y410's sample is the dword:
+ *   src[0] == src[1] == src[2]   the first pixel, on a boundary of the pixel's size: 4 bytes for AYUV, 8 bytes for Y412 / Y416
+ *   pixel_stride                 1
+ *   row_stride                   the pitch of the surface in pixels (dwords or qwords respectively); may be negative
+ * Anything else is HYD_API_ERROR "AYUV/Y416 wants pixel_stride 1 and three equal pointers on a boundary of the pixel's size",
+ * nothing enqueued.  A row is W pixels and nothing outside the W pixels of rows 0 .. H - 1 is ever read.  The library finds an LF
+ * group, tile or shard at pixel (x0, y0) by adding y0 * row_stride + x0 pixels to all three pointers; a caller's own crop may start
+ * anywhere.
+ *
+ * AYUV is a storage form of the 8-bit class: the HYDAMD_I444_* picture of its three bytes, under the NV12 section's conversion.
+ * Y412 and Y416 are storage forms of the 16-bit class: the words count as stored — low bits are not masked, the P010 section's rule
+ * — under that section's conversion at 12 or 16 bits.  A Y416 picture is the HYDAMD_I416_* picture of its three words, and a Y412
+ * picture whose low four bits are zero the HYDAMD_I412_* picture of the words >> 4.  The fourth sample never matters.  The file is
+ * byte for byte what the reference writes for the HYD_UINT8 or HYD_UINT16 picture this produces.
+ *
+ * Accepted wherever Y410 is, and beside every other family in one hydamd_encode_mixed_formats launch group.  There is no chroma
+ * filter, so hydamd_encode_image_multi takes all twelve; the host-pointer entry points refuse all twelve with "Invalid Sample
+ * Format".
+ * Out of scope: other byte orders (ffmpeg ayuv, uyva, ayuv64le, 3-byte vyu444); an alpha channel; v210; NV16 / NV24 / P210;
+ * host-pointer input; PQ / HLG / BT.2020.
+ */
+enum {
+    HYDAMD_AYUV_BT709 = 524288 + 4 * 2,
+    HYDAMD_AYUV_BT709_FULL,
+    HYDAMD_AYUV_BT601,
+    HYDAMD_AYUV_BT601_FULL,
+    HYDAMD_Y412_BT709 = 524288 + 4 * 2 + 64 * 2,
+    HYDAMD_Y412_BT709_FULL,
+    HYDAMD_Y412_BT601,
+    HYDAMD_Y412_BT601_FULL,
+    HYDAMD_Y416_BT709 = 524288 + 4 * 2 + 64 * 3,
+    HYDAMD_Y416_BT709_FULL,
+    HYDAMD_Y416_BT601,
+    HYDAMD_Y416_BT601_FULL
+};
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_*, HYDAMD_YUY2_*, HYDAMD_Y21x_*, HYDAMD_RGB10A2, HYDAMD_BGR10A2 or HYDAMD_Y410_* formats (whose src and strides are
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_*, HYDAMD_YUY2_*, HYDAMD_Y21x_*, HYDAMD_RGB10A2, HYDAMD_BGR10A2, HYDAMD_Y410_*, HYDAMD_AYUV_*, HYDAMD_Y412_* or HYDAMD_Y416_* formats (whose src and strides are
  * described above).  With an interpolating format (HYDAMD_NV12C_*, HYDAMD_NV12L_*, their P01x and I42x forms) the LF group is a
  * picture of its own: its chroma clamps at its own edges.
  */
