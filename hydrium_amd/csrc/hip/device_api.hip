@@ -36,6 +36,7 @@
 #include "../../../include/hydrium_amd.h"
 #include "hydk_common.h"
 #include "../hyd_sample_fmt.h"
+#include "../host/streamclass.h"
 
 #pragma clang fp contract(off)
 
@@ -155,6 +156,9 @@ struct HydAmdContext {
     int nclusters = 9;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
+    int live_index = -1;            /* this context's place among its device's live ones (streamclass.c) */
+    int stream_class = HYD_STREAM_NORMAL; /* the queue pool of own_stream and lf_stream (hydamd_stream_class) */
+    int stream_priority = 0;        /* ... and the HIP priority that names it */
     char error[256] = "";
 
     /* device memory */
@@ -846,6 +850,7 @@ void hydamd_destroy(HydAmdContext *ctx) {
         (void)hipHostFree(ctx->h_status_pinned);
     if (ctx->own_stream)
         (void)hipStreamDestroy(ctx->own_stream);
+    hyd_stream_slot_release(ctx->device, ctx->live_index);
     delete ctx;
 }
 
@@ -973,14 +978,28 @@ static int create_impl(HydAmdContext *ctx, int debug_planes) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     {
         /* HYDAMD_STREAM_HIGH=n (A/B knob): the first n contexts a process creates get their stream at the device's highest
-         * priority — a staggered mix of stages instead of sixteen streams progressing alike (round 6; same bytes) */
+         * priority — a staggered mix of stages instead of sixteen streams progressing alike (round 6; same bytes).  Where
+         * it is set it decides alone.  Otherwise the context's place among its device's live ones does (streamclass.c):
+         * the runtime keeps a pool of GPU_MAX_HW_QUEUES hardware queues per stream priority, and at few queues the
+         * contexts beyond the first pool's worth go to the other pools instead of queueing behind those. */
         static std::atomic<int> created{0};
         static const int high = getenv("HYDAMD_STREAM_HIGH") ? atoi(getenv("HYDAMD_STREAM_HIGH")) : 0;
-        int lo = 0, hi = 0;
-        if (created.fetch_add(1) < high && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
-            HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->own_stream, hipStreamNonBlocking, hi));
+        static const int pool = hyd_queue_pool_size(getenv("GPU_MAX_HW_QUEUES"));
+        const int nth = created.fetch_add(1);
+        ctx->live_index = hyd_stream_slot_take(ctx->device);
+        int cls = high > 0 ? (nth < high ? HYD_STREAM_HIGH : HYD_STREAM_NORMAL) : hyd_stream_class(ctx->live_index, pool);
+        int lo = 0, hi = 0; /* numerically: least >= 0 (normal) >= greatest */
+        if (cls != HYD_STREAM_NORMAL && (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || hi == lo))
+            cls = HYD_STREAM_NORMAL;
+        const int prio = cls == HYD_STREAM_HIGH ? hi : cls == HYD_STREAM_LOW ? lo : 0;
+        if (prio == 0) /* a range that ends at normal on this side */
+            cls = HYD_STREAM_NORMAL;
+        if (cls != HYD_STREAM_NORMAL)
+            HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->own_stream, hipStreamNonBlocking, prio));
         else
             HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+        ctx->stream_class = cls;
+        ctx->stream_priority = prio;
     }
     ctx->stream = ctx->own_stream;
     if (const char *env = getenv("HYDAMD_TOKEN_CAP")) { /* records per group before the overflow path kicks in (tests) */
@@ -1155,6 +1174,8 @@ int hydamd_set_stream(HydAmdContext *ctx, void *hip_stream) {
 }
 
 void *hydamd_get_stream(HydAmdContext *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
+
+int hydamd_stream_class(const HydAmdContext *ctx) { return ctx ? ctx->stream_class : 0; }
 
 
 int hydamd_uses_register_luts(HydAmdContext *ctx) { return ctx && ctx->use_luts < 2; }
@@ -1530,8 +1551,12 @@ static int lf_drop() {
 static constexpr int lf_drop() { return 0; }
 #endif
 static int ensure_lf_stream(HydAmdContext *ctx) {
-    if (!ctx->lf_stream)
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->lf_stream, hipStreamNonBlocking));
+    if (!ctx->lf_stream) { /* in its context's queue pool: the two never invert */
+        if (ctx->stream_class != HYD_STREAM_NORMAL)
+            HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->lf_stream, hipStreamNonBlocking, ctx->stream_priority));
+        else
+            HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->lf_stream, hipStreamNonBlocking));
+    }
     return ST_OK;
 }
 

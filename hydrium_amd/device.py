@@ -795,6 +795,10 @@ class DeviceContext:
     def get_stream(self) -> int:
         return self.d.hydamd_get_stream(self.h) or 0
 
+    def stream_class(self) -> int:
+        """the queue pool of the context's own stream: 0 normal, 1 high, 2 low (hydamd_stream_class)"""
+        return int(self.d.hydamd_stream_class(C.c_void_p(self.h)))
+
     def uses_register_luts(self) -> bool:
         return bool(self.d.hydamd_uses_register_luts(self.h))
 

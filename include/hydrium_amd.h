@@ -73,6 +73,11 @@ HYDAMD_EXPORT const char *hydamd_error(HydAmdContext *ctx);
 /* Run on a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL restores the context's own. */
 HYDAMD_EXPORT int hydamd_set_stream(HydAmdContext *ctx, void *hip_stream);
 HYDAMD_EXPORT void *hydamd_get_stream(HydAmdContext *ctx);
+/* The hardware-queue pool of the context's own stream: 0 normal, 1 high, 2 low stream priority.  The HIP runtime keeps
+ * GPU_MAX_HW_QUEUES queues per priority; with 8 or fewer (its default is 4) a device's live contexts are dealt to the
+ * pools GPU_MAX_HW_QUEUES at a time (normal, high, low, normal, ...), so that more of them can have a kernel on the card
+ * at once; with more than 8 every context is normal.  A caller's own stream (hydamd_set_stream) is never touched. */
+HYDAMD_EXPORT int hydamd_stream_class(const HydAmdContext *ctx);
 
 /* 1 if K1 evaluates the format.c LUTs in registers (verified bit-exact at creation), 0 if it gathers from them. */
 HYDAMD_EXPORT int hydamd_uses_register_luts(HydAmdContext *ctx);
