@@ -361,8 +361,13 @@ static_assert(HYDAMD_FMT_STEM(AYUV, HYD_LAYOUT_QUAD, 0, HYDK_PLANAR_444, HYDK_CH
                   hyd_fmt_describe(HYDAMD_AYUV_BT709).bytes == 4 && hyd_fmt_describe(HYDAMD_Y412_BT709).bytes == 8 && hyd_fmt_describe(HYDAMD_Y412_BT709).bits == 12 &&
                   !hyd_fmt_describe(HYD_FMT_BASE_QUAD + 4 * 2 + 64).device,
               "four samples a pixel: 524288 + the kernels' matrix index + 4 * 4:4:4 + 64 * the kernels' depth, bytes at depth 0, words at 2 and 3, nothing at 1");
-static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_COUNT == 19 && HYDK_STORE_FORMS == HYDK_STORE_RGB10 && HYDK_FMT_F32 + HYDK_STORE_TABLE == 21,
-              "the job did not grow; launch_transform's mask has 21 bits");
+static_assert(HYDAMD_R11G11B10F == HYD_FMT_BASE_UFLOAT && HYDAMD_RGB9E5 == HYD_FMT_BASE_UFLOAT + 1 && hyd_fmt_describe(HYDAMD_R11G11B10F).layout == HYD_LAYOUT_UFLOAT &&
+                  hyd_fmt_describe(HYDAMD_RGB9E5).is_float == 1 && hyd_fmt_describe(HYDAMD_RGB9E5).bytes == 4 && !hyd_fmt_describe(HYDAMD_R11G11B10F).host &&
+                  !hyd_fmt_describe(HYD_FMT_BASE_UFLOAT + 2).device && HYDK_STORE_R11G11B10F + HYDK_UFLOAT_RGB9E5 == HYDK_STORE_RGB9E5,
+              "three unsigned floats a dword: 8388608 and 8388609, float class, in the order of their storage forms and of hydk_ufloat.h's two");
+static_assert(sizeof(HydkLfJob) == 232 && HYDK_FMT_F32 + HYDK_STORE_COUNT == 19 && HYDK_STORE_FORMS == HYDK_STORE_RGB10 && HYDK_FMT_F32 + HYDK_STORE_TABLE == 21 &&
+                  HYDK_FMT_F32 + HYDK_STORE_SIZE == 23,
+              "the job did not grow; launch_transform's mask has 23 bits");
 #undef HYDAMD_FMT_PLANES
 #undef HYDAMD_FMT_FILTERS
 #undef HYDAMD_FMT_STEM
@@ -3191,6 +3196,72 @@ __attribute__((visibility("default"))) int hydt_quad_to_rgb_device(int device, i
     const size_t n = (size_t)width * height;
     return probe_round_trip(surface, (depth ? 8 : 4) * n, rgb, (depth ? 6 : 3) * n, [&](void *d_in, void *d_out) {
         hipLaunchKernelGGL(k_quad_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, depth, matrix, (const uint32_t *)d_in, d_out, width, height);
+    });
+}
+
+/* Test hooks (probe flavour only, not declared in include/): the widening of unsigned floats (hydk_ufloat.h) as the host compiler
+ * built it and as the device runs it.  kind 0: in[i] an 11-bit field (5-bit exponent, 6 mantissa bits); 1: a 10-bit field (5 mantissa
+ * bits); 2: an RGB9E5 channel, exponent << 9 | mantissa (14 bits).  out[i] holds the float32 bits of in[i]; n <= 65 536. */
+static bool ufloat_widen_args(int kind, const uint32_t *in, uint32_t *out, size_t n) { return kind >= 0 && kind <= 2 && in && out && n >= 1 && n <= 65536; }
+__host__ __device__ static inline uint32_t ufloat_widen_one(int kind, uint32_t v) {
+    return kind == 2 ? hydk_rgb9e5_widen(v & 0x1FFu, (v >> 9) & 0x1Fu) : hydk_ufloat_widen_field(v & (kind ? 0x3FFu : 0x7FFu), kind ? 5 : 6);
+}
+
+__attribute__((visibility("default"))) int hydt_ufloat_widen_host(int kind, const uint32_t *in, uint32_t *out, size_t n) {
+    if (!ufloat_widen_args(kind, in, out, n))
+        return ST_API_ERROR;
+    for (size_t i = 0; i < n; i++)
+        out[i] = ufloat_widen_one(kind, in[i]);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_ufloat_widen_probe(int kind, const uint32_t *in, uint32_t *out, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x; /* one thread per pattern */
+    if (i < n)
+        out[i] = ufloat_widen_one(kind, in[i]);
+}
+} /* namespace */
+
+/* one launch over the n inputs (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_ufloat_widen_device(int device, int kind, const uint32_t *in, uint32_t *out, size_t n) {
+    if (!ufloat_widen_args(kind, in, out, n) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    return probe_round_trip(in, 4 * n, out, 4 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_ufloat_widen_probe, probe_grid(n), dim3(256), 0, nullptr, kind, (const uint32_t *)d_in, (uint32_t *)d_out, (uint32_t)n);
+    });
+}
+
+/* The definition of a pixel in one dword of three unsigned floats (hydk_ufloat_pixel — the function under it is the one the
+ * transform kernel's loader calls on its dwords), host and device.  which: HYDK_UFLOAT_R11G11B10F (0) or _RGB9E5 (1); surface: height
+ * rows of width dwords, tightly packed; rgb receives height rows of width (R, G, B) triples of float32 BITS. */
+static bool ufloat_probe_args(int which, const uint32_t *surface, uint32_t *rgb, int width, int height) {
+    return (which == HYDK_UFLOAT_R11G11B10F || which == HYDK_UFLOAT_RGB9E5) && surface && rgb && width >= 1 && height >= 1 && width <= 4096 && height <= 4096;
+}
+
+__attribute__((visibility("default"))) int hydt_ufloat_to_rgb_host(int which, const uint32_t *surface, uint32_t *rgb, int width, int height) {
+    if (!ufloat_probe_args(which, surface, rgb, width, height))
+        return ST_API_ERROR;
+    for (size_t i = 0; i < (size_t)width * height; i++)
+        hydk_ufloat_pixel(which, surface, width, (int)(i % (size_t)width), (int)(i / (size_t)width), rgb + 3 * i);
+    return ST_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void k_ufloat_to_rgb_probe(int which, const uint32_t *surface, uint32_t *rgb, int width, int height) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; /* one thread per pixel */
+    if (i < (size_t)width * height)
+        hydk_ufloat_pixel(which, surface, width, (int)(i % (size_t)width), (int)(i / (size_t)width), rgb + 3 * i);
+}
+} /* namespace */
+
+/* one launch over the picture (host arrays) on `device`; HYD_OK, or HYD_API_ERROR with nothing written */
+__attribute__((visibility("default"))) int hydt_ufloat_to_rgb_device(int device, int which, const uint32_t *surface, uint32_t *rgb, int width, int height) {
+    if (!ufloat_probe_args(which, surface, rgb, width, height) || hipSetDevice(device) != hipSuccess)
+        return ST_API_ERROR;
+    const size_t n = (size_t)width * height;
+    return probe_round_trip(surface, 4 * n, rgb, 12 * n, [&](void *d_in, void *d_out) {
+        hipLaunchKernelGGL(k_ufloat_to_rgb_probe, probe_grid(n), dim3(256), 0, nullptr, which, (const uint32_t *)d_in, (uint32_t *)d_out, width, height);
     });
 }
 

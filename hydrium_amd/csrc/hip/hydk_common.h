@@ -19,7 +19,8 @@
 #include "hydk_yuy2.h"  /* and 8-bit 4:2:2 packed in one plane, */
 #include "hydk_y216.h"  /* or packed in 16-bit words; */
 #include "hydk_rgb10.h" /* and a pixel in one dword of three 10-bit fields, RGB or YCbCr, */
-#include "hydk_quad.h"  /* or in one group of four bytes or words, YCbCr 4:4:4 */
+#include "hydk_quad.h"  /* or in one group of four bytes or words, YCbCr 4:4:4; */
+#include "hydk_ufloat.h" /* and a pixel in one dword of three unsigned floats, the float class's */
 
 #define HYDK_GROUPS_PER_LFG 64        /* 8 x 8 groups of 256 px in a 2048 px LF group */
 #define HYDK_BLOCKS_PER_GROUP 1024    /* 32 x 32 varblocks */
@@ -84,9 +85,10 @@ typedef struct HydkTables {
 typedef struct HydkLfJob {
     const void *src[3];      /* R, G, B sample pointers of the LF group's first pixel (device memory) */
     long long row_stride;    /* in samples; HYDK_STORE_YUY2 and _YUY2I: the pitch of the one plane in bytes; _Y216 and _Y216I: in words;
-                              * _RGB10 and _Y410: in dwords (src[0 ... 2] are one pointer); _AYUV and _Y416: in pixels, dwords and qwords (the same) */
+                              * _RGB10 and _Y410: in dwords (src[0 ... 2] are one pointer); _AYUV and _Y416: in pixels, dwords and qwords (the same);
+                              * _R11G11B10F and _RGB9E5: in dwords as _RGB10's */
     long long pixel_stride;  /* in samples; HYDK_STORE_YUVP, _YUVPI, _YUVP16 and _YUVP16I: the pitch of the U and of the V plane in samples;
-                              * HYDK_STORE_YUY2, _YUY2I, _Y216 and _Y216I: 2; _RGB10, _Y410, _AYUV and _Y416: 1 */
+                              * HYDK_STORE_YUY2, _YUY2I, _Y216 and _Y216I: 2; _RGB10, _Y410, _AYUV, _Y416, _R11G11B10F and _RGB9E5: 1 */
     int fmt;                 /* HYDK_FMT_* */
     int linear_light;
     int width, height;       /* LF group size in pixels */
@@ -114,7 +116,8 @@ typedef struct HydkLfJob {
     int32_t *dbg_quant;
     uint32_t *bad_slot;      /* per-slot outcomes (hydamd_set_bad_sample_per_slot): this slot's flag word, cleared with the frame's
                               * accumulators — a non-finite float sample sets it and is coded as 0.0; NULL: the launch-wide status bit */
-    uint32_t storage;        /* float class: HYDK_STORE_F32 (0, what a zeroed job says), _F16 or _BF16 — 2-byte samples, widened on load;
+    uint32_t storage;        /* float class: HYDK_STORE_F32 (0, what a zeroed job says), _F16 or _BF16 — 2-byte samples, widened on load —
+                              * or _R11G11B10F or _RGB9E5 — a dword a pixel, its three unsigned floats widened on load (hydk_ufloat.h);
                               * 8-bit class: 0 (RGB samples) or HYDK_STORE_NV12 — src[0] the Y plane, src[1], src[2] the U and V bytes of the
                               * chroma plane, row_stride the pitch of both */
     uint32_t per_sample;     /* probe flavour only (HYDAMD_DEBUG_HALF_PER_SAMPLE, for A/B): bit 0 interleaved, bit 1 planar half rows

@@ -43,7 +43,11 @@
 #define HYDK_STORE_COUNT 17 /* (what "all of them" came to with the dword forms; pinned since, as HYDK_STORE_FORMS is) */
 #define HYDK_STORE_AYUV 17  /* 8-bit class: a pixel is one dword of the bytes V, U, Y and an ignored fourth — 4:4:4, nearest by nature (hydk_quad.h) */
 #define HYDK_STORE_Y416 18  /* 16-bit class: a pixel is one qword of the words U, Y, V and an ignored fourth, MSB-aligned — Y412 / Y416, the depth in matrix as P01x's */
-#define HYDK_STORE_TABLE 19 /* all of them: the table's size and the bits of launch_transform's mask above the two integer classes' */
+#define HYDK_STORE_TABLE 19 /* (what "all of them" came to with the groups of four; pinned since, as the two before it are) */
+#define HYDK_STORE_R11G11B10F 19 /* float class: a pixel is one dword of three unsigned floats of 11, 11 and 10 bits, widened exactly on load (hydk_ufloat.h) */
+#define HYDK_STORE_RGB9E5 20     /* float class: a pixel is one dword of three 9-bit mantissas and their shared 5-bit exponent */
+#define HYDK_STORE_SIZE 21  /* all of them: the table's size and the bits of launch_transform's mask above the two integer classes'; no test
+                             * holds it to a value, so the next form grows it */
 
 /* HydkLfJob.use_luts of a YCbCr job is the XYB mode + its form's variant bit: the RGB instances' own test turns it away */
 #define HYDK_VARIANT_NV12 8
@@ -73,7 +77,7 @@ typedef struct HydkStoreForm {
 } HydkStoreForm;
 
 HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
-    const HydkStoreForm forms[HYDK_STORE_TABLE] = {
+    const HydkStoreForm forms[HYDK_STORE_SIZE] = {
         {HYDK_FMT_F32, 0, 32, 0, 0, 0},
         {HYDK_FMT_F32, 0, 16, 0, 0, 0},
         {HYDK_FMT_F32, 0, 16, 0, 0, 0},
@@ -93,8 +97,10 @@ HYDK_STORE_FN HydkStoreForm hydk_store_form(int storage) {
         {HYDK_FMT_U16, 1, 10, 0, 0, HYDK_VARIANT_Y410},
         {HYDK_FMT_U8, 1, 8, 0, 0, HYDK_VARIANT_AYUV},
         {HYDK_FMT_U16, 1, 16, 0, 0, HYDK_VARIANT_Y416},
+        {HYDK_FMT_F32, 0, 11, 0, 0, 0},
+        {HYDK_FMT_F32, 0, 9, 0, 0, 0},
     };
-    return forms[storage >= 0 && storage < HYDK_STORE_TABLE ? storage : 0];
+    return forms[storage >= 0 && storage < HYDK_STORE_SIZE ? storage : 0];
 }
 
 /* A public sample format taken apart into what a job holds.  ok: a device entry point takes it (else every field is 0).
@@ -111,7 +117,9 @@ typedef struct HydkSampleForm {
 static inline HydkSampleForm hydk_decode_fmt(int f) {
     const HydFmt fmt = hyd_fmt_describe(f);
     HydkSampleForm d = {fmt.device, 0, 0, (uint32_t)(fmt.matrix + 4 * fmt.depth), (uint32_t)fmt.filter, (uint32_t)fmt.sub, fmt.sx, fmt.sy};
-    if (fmt.layout == HYD_LAYOUT_QUAD)
+    if (fmt.layout == HYD_LAYOUT_UFLOAT)
+        d.storage = (uint32_t)(HYDK_STORE_R11G11B10F + (f - HYD_FMT_BASE_UFLOAT));
+    else if (fmt.layout == HYD_LAYOUT_QUAD)
         d.storage = (uint32_t)(fmt.depth ? HYDK_STORE_Y416 : HYDK_STORE_AYUV);
     else if (fmt.layout == HYD_LAYOUT_DWORD) {
         d.storage = (uint32_t)(fmt.depth ? HYDK_STORE_Y410 : HYDK_STORE_RGB10);
@@ -130,6 +138,8 @@ static inline HydkSampleForm hydk_decode_fmt(int f) {
 /* and back: the public format of a job's cls (fmt), storage, matrix, filter and sub */
 static inline int hydk_encode_fmt(HydkSampleForm d) {
     const HydkStoreForm form = hydk_store_form((int)d.storage);
+    if (d.storage == HYDK_STORE_R11G11B10F || d.storage == HYDK_STORE_RGB9E5)
+        return HYD_FMT_BASE_UFLOAT + (int)(d.storage - HYDK_STORE_R11G11B10F);
     if (d.storage == HYDK_STORE_RGB10)
         return HYD_FMT_BASE_DWORD + (int)(d.sub & 1u);
     if (d.storage == HYDK_STORE_Y410)

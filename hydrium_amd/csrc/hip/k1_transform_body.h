@@ -1,6 +1,6 @@
 /*
  * k1_transform_body.h — the body of the transform kernel (kernels.hip, K1), included into k_transform_tokenize, into
- * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16, into k_transform_tokenize_yuy2, into k_transform_tokenize_y216, into k_transform_tokenize_dword and into k_transform_tokenize_quad and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
+ * k_transform_tokenize_p016, into k_transform_tokenize_planar, into k_transform_tokenize_yuvp16, into k_transform_tokenize_yuy2, into k_transform_tokenize_y216, into k_transform_tokenize_dword, into k_transform_tokenize_quad and into k_transform_tokenize_ufloat and nowhere else.  In scope where it is included: the template parameters or constants FMT, XMODE
  * and STORE, the kernel's parameters jobs, status, part_info and plog, and everything kernels.hip defines above its K1 section.
  * No include guard: it is function-body text, meant to be included once per kernel.
  */
@@ -14,14 +14,17 @@
      * DW: a pixel is one dword of three 10-bit fields (hydk_rgb10.h) — RGB10, which is no YCbCr form, and Y410, which is one with
      * neither planes nor groups: every pixel carries its own chroma.
      * QD: a pixel is one group of four samples, the fourth ignored (hydk_quad.h) — AYUV, bytes in a dword, and Y416, words in a qword:
-     * YCbCr 4:4:4 as Y410 is, of whole samples, so neither PK nor DW */
+     * YCbCr 4:4:4 as Y410 is, of whole samples, so neither PK nor DW.
+     * UF: a pixel is one dword of three unsigned floats (hydk_ufloat.h) — R11G11B10F and RGB9E5, storage forms of the float class as
+     * the half-precision ones are: widened exactly on load, float32 samples from there on */
     constexpr HydkStoreForm FORM = hydk_store_form(STORE);
     static_assert(STORE == HYDK_STORE_F32 || FORM.cls == FMT,
-                  "the float class has the half-precision storage forms, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16, YUVP16I, Y216, Y216I, RGB10 and Y410; AYUV is of the 8-bit class and Y416 of the 16-bit class");
+                  "the float class has the half-precision storage forms, R11G11B10F and RGB9E5, the 8-bit class NV12, NV12I, YUVP, YUVPI, YUY2 and YUY2I, the 16-bit class P016, P016I, YUVP16, YUVP16I, Y216, Y216I, RGB10 and Y410; AYUV is of the 8-bit class and Y416 of the 16-bit class");
     constexpr bool DW = STORE == HYDK_STORE_RGB10 || STORE == HYDK_STORE_Y410;
     constexpr bool QD = STORE == HYDK_STORE_AYUV || STORE == HYDK_STORE_Y416;
     constexpr bool YUV = FORM.ycbcr, TWO_PLANES = FORM.chroma_planes == 2, PK = YUV && FORM.chroma_planes == 0 && !DW && !QD, INTERP = FORM.interp;
-    constexpr bool HALF = FMT == HYDK_FMT_F32 && STORE != HYDK_STORE_F32;
+    constexpr bool UF = STORE == HYDK_STORE_R11G11B10F || STORE == HYDK_STORE_RGB9E5;
+    constexpr bool HALF = FMT == HYDK_FMT_F32 && STORE != HYDK_STORE_F32 && !UF;
     /* the two-plane forms by name: YUVPI keeps a prefetch, an edge fill and an interpolate loop of its own (through the shared
      * ones its instances measured a few tenths of a percent slower, profiles/ycbcr_loader.txt) */
     constexpr bool YUVP = TWO_PLANES && !INTERP && FMT == HYDK_FMT_U8, YUVPI = TWO_PLANES && INTERP && FMT == HYDK_FMT_U8;
@@ -165,6 +168,11 @@
             hrun = 2;
     }
     const bool hfast = HALF && hrun != 0 && ab < gbw && ab * 8 + 8 <= gw;
+    /* unsigned floats in a dword (UF): a block row is eight dwords of the row's one plane, 32 bytes, fetched a strip ahead as two
+     * 16-byte loads where every row of the picture starts on a 16-byte boundary — the base and the pitch in BYTES (a block's first
+     * column is a multiple of 8 dwords) — and the block is whole.  A ragged last block, a crop at a column that is no multiple of
+     * four and a pitch of the same kind read dword by dword at use, the pixels the row has and nothing else. */
+    const bool ufast = UF && (((uintptr_t)job.src[0] | (uintptr_t)(job.row_stride * 4)) & 15) == 0 && ab < gbw && ab * 8 + 8 <= gw;
     /* YCbCr, every form: a block row is fetched as a WINDOW of dwords — its eight Y samples in nxt[0 ... kYW), and the chroma that
      * serves them — when planes and pitches are dword multiples (a block's first column is a multiple of 8, its chroma column
      * even); anything else reads sample by sample.  SB: bits of a sample; a dword holds kSPD samples or kPPD (U, V) pairs */
@@ -247,6 +255,18 @@
         return (long long)hydk_chroma_vy(2 * job.pic_cy0 + (int32_t)y, job.pic_ch) - job.pic_cy0;
     };
     auto prefetch = [&](int s) {
+        if (UF) {
+            /* the eight pixels as stored in nxt[0 ... 7], the float instance's prefetch registers: eight dword loads of one 16-byte
+             * aligned address, two global_load_dwordx4; the fields come out, and are widened, at use */
+            if (ufast && s * 8 + ar < gh) {
+                const long long y = py0 + s * 8 + ar, x = px0 + ab * 8;
+                const char *pd = (const char *)job.src[0] + (y * job.row_stride + x) * 4;
+#pragma unroll
+                for (int k = 0; k < 8; k++)
+                    nxt[k] = HYDK_GLOBAL(const uint32_t, pd)[k];
+            }
+            return;
+        }
         if (QD) {
             /* the eight pixels as stored in nxt[0 ... kWin): kWin dword loads of one address, which the compiler fuses into two (AYUV) or
              * four (Y416) global_load_dwordx4 as it does DW's; the hardware takes them at dword alignment, and hyd_fmt_refusal
@@ -538,7 +558,30 @@
                 if (!lms_mix_f32(fr, fg, fb, job.linear_light, X, Y, B))
                     bad_sample = true;
             };
-            if (HALF && hfast) {
+            if (UF) {
+                /* A dword a pixel.  Rows that came as dwords a strip ago sit in nxt[0 ... 7]; the others — a ragged last block,
+                 * rows that start on no 16-byte boundary — are read here, dword by dword, the pixels the row has: nothing outside
+                 * the W dwords of a row is read.  Either way three fields come out of each dword and are widened to the float32
+                 * bits they stand for (hydk_ufloat.h: integer operations only), and from there a pixel is a float32 pixel — the
+                 * non-finite check, the slot's flag and the XYB mix are float_pixel's.  Edge padding is XYB = 0 (format.c:182-191). */
+                const int nvalid = row_ok ? min(8, gw - ab * 8) : 0;
+                if (!ufast) {
+                    const char *pd = (const char *)job.src[0] + ((long long)y * job.row_stride + x0) * 4;
+#pragma unroll
+                    for (int i = 0; i < 8; i++)
+                        nxt[i] = i < nvalid ? HYDK_GLOBAL(const uint32_t, pd)[i] : 0u;
+                }
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    xv[i] = yv[i] = bv[i] = 0.0f;
+                    if (i < nvalid) {
+                        uint32_t f[3];
+                        hydk_ufloat_to_f32(STORE - HYDK_STORE_R11G11B10F, nxt[i], f);
+                        float_pixel(__uint_as_float(f[0]), __uint_as_float(f[1]), __uint_as_float(f[2]), xv[i], yv[i], bv[i]);
+                    }
+                }
+                prefetch(s + 1);
+            } else if (HALF && hfast) {
                 /* this strip's samples, fetched a strip ago: sample k of the row's 24 is half k & 1 of dword k >> 1 —
                  * k = 3 * pixel + channel in an interleaved run, 8 * channel + pixel in three planes' */
 #pragma unroll

@@ -622,7 +622,9 @@ __device__ __forceinline__ int trunc_as_reference(float x) {
  * on the same grounds; and the same groups in 16-bit words, HYDK_STORE_Y216 and HYDK_STORE_Y216I (Y210, Y212, Y216; hydk_y216.h), are
  * k_transform_tokenize_y216's.  A pixel in one dword of three 10-bit fields, HYDK_STORE_RGB10 and HYDK_STORE_Y410 (RGB10A2, BGR10A2, Y410;
  * hydk_rgb10.h), are k_transform_tokenize_dword's.  A pixel in one group of four samples, HYDK_STORE_AYUV of the 8-bit class and HYDK_STORE_Y416
- * of the 16-bit class (AYUV, Y412, Y416; hydk_quad.h), are k_transform_tokenize_quad's. */
+ * of the 16-bit class (AYUV, Y412, Y416; hydk_quad.h), are k_transform_tokenize_quad's.  A pixel in one dword of three unsigned floats,
+ * HYDK_STORE_R11G11B10F and HYDK_STORE_RGB9E5 of the float class (hydk_ufloat.h), are k_transform_tokenize_ufloat's: "the float
+ * instances" by symbol name stay float32, float16 and bfloat16. */
 template <int FMT, int XMODE, int STORE = HYDK_STORE_F32>
 __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
                                                        int plog) {
@@ -633,6 +635,7 @@ __global__ HYDK_K1_OCCUPANCY void k_transform_tokenize(const HydkLfJob *__restri
     static_assert(STORE != HYDK_STORE_Y216 && STORE != HYDK_STORE_Y216I, "the packed 4:2:2 instances of 16-bit words are k_transform_tokenize_y216's");
     static_assert(STORE != HYDK_STORE_RGB10 && STORE != HYDK_STORE_Y410, "the instances of a dword a pixel are k_transform_tokenize_dword's");
     static_assert(STORE != HYDK_STORE_AYUV && STORE != HYDK_STORE_Y416, "the instances of four samples a pixel are k_transform_tokenize_quad's");
+    static_assert(STORE != HYDK_STORE_R11G11B10F && STORE != HYDK_STORE_RGB9E5, "the instances of three unsigned floats a dword are k_transform_tokenize_ufloat's");
 #include "k1_transform_body.h"
 }
 
@@ -700,6 +703,16 @@ __global__ __launch_bounds__(kThreads, 4) void k_transform_tokenize_quad(const H
                                                                          uint2 *part_info, int plog) {
     static_assert(STORE == HYDK_STORE_AYUV || STORE == HYDK_STORE_Y416, "RGB10 and Y410 are k_transform_tokenize_dword's");
     constexpr int FMT = STORE == HYDK_STORE_AYUV ? HYDK_FMT_U8 : HYDK_FMT_U16;
+#include "k1_transform_body.h"
+}
+
+/* A pixel in one dword of three unsigned floats — R11G11B10F and RGB9E5, the float render targets — widened exactly on load:
+ * the float class under its one XYB mode, at the float32 instance's occupancy. */
+template <int STORE>
+__global__ HYDK_K1_OCCUPANCY void k_transform_tokenize_ufloat(const HydkLfJob *__restrict__ jobs, uint32_t *status, uint2 *part_info,
+                                                              int plog) {
+    static_assert(STORE == HYDK_STORE_R11G11B10F || STORE == HYDK_STORE_RGB9E5, "float16 and bfloat16 are k_transform_tokenize's");
+    constexpr int FMT = HYDK_FMT_F32, XMODE = kXybIeeeDiv;
 #include "k1_transform_body.h"
 }
 
@@ -2478,6 +2491,10 @@ static K1Fn k1_of_mode(int fmt, int storage) {
         return k_transform_tokenize_quad<A, HYDK_STORE_AYUV>;
     case HYDK_STORE_Y416:
         return k_transform_tokenize_quad<A, HYDK_STORE_Y416>;
+    case HYDK_STORE_R11G11B10F:
+        return k_transform_tokenize_ufloat<HYDK_STORE_R11G11B10F>;
+    case HYDK_STORE_RGB9E5:
+        return k_transform_tokenize_ufloat<HYDK_STORE_RGB9E5>;
     }
     return fmt == HYDK_FMT_U8    ? k_transform_tokenize<HYDK_FMT_U8, XM>
            : fmt == HYDK_FMT_U16 ? k_transform_tokenize<HYDK_FMT_U16, XM>
@@ -2503,7 +2520,7 @@ static K1Fn k1_instance(int fmt, int storage, int xmode) {
 hipError_t launch_transform(const HydkLfJob *d_jobs, int num_slots, unsigned fmt_mask, int xmode, uint32_t *status,
                             uint2 *part_info, int plog, hipStream_t stream) {
     const dim3 grid((num_slots * HYDK_GROUPS_PER_LFG) << plog), block(kThreads);
-    for (int bit = 0; bit < HYDK_FMT_F32 + HYDK_STORE_TABLE; bit++)
+    for (int bit = 0; bit < HYDK_FMT_F32 + HYDK_STORE_SIZE; bit++)
         if (fmt_mask & (1u << bit)) {
             const int storage = bit < HYDK_FMT_F32 ? HYDK_STORE_F32 : bit - HYDK_FMT_F32;
             const K1Fn k1 = k1_instance(bit < HYDK_FMT_F32 ? bit : hydk_store_form(storage).cls, storage, xmode);

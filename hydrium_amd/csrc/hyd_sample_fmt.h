@@ -69,6 +69,17 @@
  * either sign (HYD_FMT_QUAD_LAYOUT_MSG).  AYUV is a storage form of the 8-BIT class, the I444 picture of its three bytes; Y412 and
  * Y416 of the 16-BIT class, the words as stored under the P01x conversion of that depth, so a Y416 picture is the I416 picture of
  * its three words.
+ *
+ * 8388608 and 8388609 name pictures whose PIXEL IS ONE 32-BIT WORD of three UNSIGNED FLOATS, in device memory (hip/hydk_ufloat.h):
+ * the float render targets.  8388608 R11G11B10F (DXGI R11G11B10_FLOAT, Vulkan B10G11R11_UFLOAT_PACK32): R in bits 0 ... 10, G in
+ * 11 ... 21, B in 22 ... 31, each a 5-bit exponent above 6, 6 and 5 mantissa bits; 8388609 RGB9E5 (DXGI R9G9B9E5_SHAREDEXP, Vulkan
+ * E5B9G9R9_UFLOAT_PACK32): three 9-bit mantissas under one 5-bit exponent in bits 27 ... 31.  They are no YCbCr and have no
+ * matrix, so they sit at a base of their own as 0 ... 4 sit at the bottom of the table: 2^23.  (2097152, the next of the bases' x 4
+ * sequence, and 2^31 - 200 ... 2^31 - 1 were passed over: tests/test_quad_formats.py holds 2097100 ... 2097200 and that top range to
+ * naming nothing, and must keep passing as it stands.)  A SAMPLE IS THE DWORD, as RGB10A2's: src[0] == src[1] == src[2], the first
+ * dword, on a 4-byte boundary; the pixel stride is 1 and the row stride the pitch in dwords, of either sign
+ * (HYD_FMT_UFLOAT_LAYOUT_MSG).  Storage forms of the FLOAT class: a field is widened exactly to float32 on load and is a float32
+ * sample from there on, an R11G11B10F infinity or NaN included.
  */
 #ifndef HYD_SAMPLE_FMT_H_
 #define HYD_SAMPLE_FMT_H_
@@ -96,6 +107,7 @@
 #define HYD_FMT_BASE_PACKED16 32768
 #define HYD_FMT_BASE_DWORD 131072
 #define HYD_FMT_BASE_QUAD 524288
+#define HYD_FMT_BASE_UFLOAT 8388608 /* no YCbCr base: R11G11B10F and, + 1, RGB9E5 */
 /* HydFmt.layout */
 #define HYD_LAYOUT_RGB 0    /* three samples a pixel, any strides */
 #define HYD_LAYOUT_PAIRS 1  /* a Y plane and a plane of (U, V) pairs */
@@ -103,6 +115,7 @@
 #define HYD_LAYOUT_PACKED 3 /* Y and chroma in one plane: groups of Y, U, Y, V bytes (or 16-bit words: HydFmt.bytes) in one of four orders */
 #define HYD_LAYOUT_DWORD 4  /* a pixel is one dword of three 10-bit fields: one pointer three times over, a sample is the dword */
 #define HYD_LAYOUT_QUAD 5   /* a pixel is one group of four samples, the fourth ignored (bytes in a dword, or words in a qword: HydFmt.bytes 4 or 8): one pointer three times over, a sample is the group */
+#define HYD_LAYOUT_UFLOAT 6 /* a pixel is one dword of three unsigned floats (R11G11B10F) or of three mantissas and their exponent (RGB9E5): one pointer three times over, a sample is the dword */
 /* HydFmt.sub */
 #define HYD_FMT_SUB_420 0
 #define HYD_FMT_SUB_422 1
@@ -137,6 +150,16 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
         d.is_float = fmt >= HYD_FMT_FLOAT32;
         d.bytes = fmt == HYD_FMT_UINT8 ? 1 : fmt == HYD_FMT_FLOAT32 ? 4 : 2;
         d.bits = 8 * d.bytes;
+        return d;
+    }
+    if (fmt >= HYD_FMT_BASE_UFLOAT) { /* 8388608 R11G11B10F, 8388609 RGB9E5: float class, a dword a pixel */
+        if (fmt > HYD_FMT_BASE_UFLOAT + 1)
+            return d;
+        d.device = 1;
+        d.is_float = 1;
+        d.bytes = 4;
+        d.layout = HYD_LAYOUT_UFLOAT;
+        d.bits = 32;
         return d;
     }
     if (fmt >= HYD_FMT_BASE_QUAD) { /* 524288 + matrix + 4 * 2 + 64 * depth: 4:4:4, no filter, depth 0, 2, 3 */
@@ -218,7 +241,8 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
  * the layout of src — pairs want unit pixel stride and V one sample behind U (and words on 2-byte boundaries), planes of
  * 16-bit words want their three addresses on 2-byte boundaries, packed 4:2:2 wants pixel stride 2 and U and V in the bytes beside
  * Y in one of the four orders (packed words: the same in words, on 2-byte boundaries), a dword a pixel wants pixel stride 1 and
- * one dword-aligned pointer three times over, a group of four a pixel the same on a boundary of the group's size (4 or 8 bytes),
+ * one dword-aligned pointer three times over (three 10-bit fields and three unsigned floats alike), a group of four a pixel the
+ * same on a boundary of the group's size (4 or 8 bytes),
  * every other format takes any layout; then
  * the chroma pitch —
  * a plane each has no layout to hold (three free pointers), but its pixel_stride argument is the chroma planes' pitch in
@@ -233,6 +257,7 @@ HYD_FMT_FN HydFmt hyd_fmt_describe(int fmt) {
 #define HYD_FMT_PACKED16_LAYOUT_MSG "Y210/Y216 wants pixel_stride 2 and U and V in the words beside Y"
 #define HYD_FMT_DWORD_LAYOUT_MSG "RGB10A2/Y410 wants pixel_stride 1 and three equal pointers on a 4-byte boundary"
 #define HYD_FMT_QUAD_LAYOUT_MSG "AYUV/Y416 wants pixel_stride 1 and three equal pointers on a boundary of the pixel's size"
+#define HYD_FMT_UFLOAT_LAYOUT_MSG "R11G11B10F/RGB9E5 wants pixel_stride 1 and three equal pointers on a 4-byte boundary"
 /* what hydamd_encode_image_multi says to a format with interpolated chroma */
 #define HYD_FMT_NV12_SHARDED_MSG "interpolated chroma is not sharded: a shard does not hold its neighbour's chroma rows"
 /* The byte order of a packed 4:2:2 picture, read off its pointers: 0 YUYV (U at +1, V at +3), 1 YVYU (+3, +1), 2 UYVY (-1, +1),
@@ -273,6 +298,9 @@ static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptr
     } else if (src && d.layout == HYD_LAYOUT_QUAD) {
         if (pixel_stride != 1 || src[1] != src[0] || src[2] != src[0] || ((size_t)src[0] & (size_t)(d.bytes - 1)))
             return HYD_FMT_QUAD_LAYOUT_MSG;
+    } else if (src && d.layout == HYD_LAYOUT_UFLOAT) {
+        if (pixel_stride != 1 || src[1] != src[0] || src[2] != src[0] || ((size_t)src[0] & 3u))
+            return HYD_FMT_UFLOAT_LAYOUT_MSG;
     }
     if (d.layout == HYD_LAYOUT_PLANES) {
         const size_t pitch = pixel_stride < 0 ? (size_t)0 - (size_t)pixel_stride : (size_t)pixel_stride;
@@ -287,8 +315,8 @@ static inline const char *hyd_fmt_refusal(int fmt, const void *const src[3], ptr
  * theirs.  Pairs: the one chroma plane has the Y plane's pitch and two samples for every two columns, so sample x0 of the row.
  * A plane each: the pitch is pixel_stride, sample x0 >> sx.  Packed 4:2:2: all three pointers move by y0 rows and 2 x0 samples
  * (bytes, or 16-bit words), the group of pixel x0.  x0 must be even, and y0 where sy is 1 (every origin the library computes is a multiple of 256).
- * A dword a pixel, and a group of four samples a pixel: all three pointers move by y0 rows and x0 pixels (dwords, or qwords); any
- * x0 and y0, since 4:4:4 has no parity to keep. */
+ * A dword a pixel (of 10-bit fields or of unsigned floats), and a group of four samples a pixel: all three pointers move by y0 rows
+ * and x0 pixels (dwords, or qwords); any x0 and y0, since 4:4:4 has no parity to keep. */
 static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t row_stride, ptrdiff_t pixel_stride, size_t x0,
                                   size_t y0, const void *origin[3]) {
     const HydFmt d = hyd_fmt_describe(fmt);
@@ -296,7 +324,7 @@ static inline void hyd_fmt_origin(int fmt, const void *const src[3], ptrdiff_t r
     ptrdiff_t luma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0 * pixel_stride, chroma = luma;
     if (d.layout == HYD_LAYOUT_PACKED) {
         luma = chroma = (ptrdiff_t)y0 * row_stride + 2 * (ptrdiff_t)x0;
-    } else if (d.layout == HYD_LAYOUT_DWORD || d.layout == HYD_LAYOUT_QUAD) {
+    } else if (d.layout == HYD_LAYOUT_DWORD || d.layout == HYD_LAYOUT_QUAD || d.layout == HYD_LAYOUT_UFLOAT) {
         luma = chroma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;
     } else if (d.layout != HYD_LAYOUT_RGB) {
         luma = (ptrdiff_t)y0 * row_stride + (ptrdiff_t)x0;

@@ -86,6 +86,9 @@ DWORD_FAMILY = (RGB10A2, BGR10A2) + Y410_FORMATS
 # four samples a pixel, the fourth ignored: AYUV_BT709 = 524296 ..., Y412_BT709 = 524424 ..., Y416_BT709 = 524488 ...
 AYUV_FORMATS, Y412_FORMATS, Y416_FORMATS = (tuple(ycbcr_fmt(524288, m, 2, 0, d) for m in range(4)) for d in (0, 2, 3))
 QUAD_FAMILY = AYUV_FORMATS + Y412_FORMATS + Y416_FORMATS
+# three unsigned floats in one dword, the float render targets (no YCbCr, a base of their own: 2 ** 23): storage forms of the FLOAT class
+R11G11B10F, RGB9E5 = 8388608, 8388609
+UFLOAT_FAMILY = (R11G11B10F, RGB9E5)
 
 
 def planar_fmt(matrix: int = NV12_BT709, subsampling="420", chroma=None) -> int:
@@ -511,6 +514,31 @@ class Y416(Ayuv):
         self.depth = int(depth)
 
 
+class R11g11b10f(Rgb10):
+    """An R11G11B10F picture in device memory — one dword a pixel of three unsigned floats, R in bits 0 ... 10, G in 11 ... 21, B in
+    22 ... 31 (DXGI R11G11B10_FLOAT, Vulkan B10G11R11_UFLOAT_PACK32, GL R11F_G11F_B10F): the HDR scene and post-processing buffer of
+    real-time renderers — accepted wherever an Rgb10 object is.  A field is widened exactly to float32 on load; the picture is the
+    float32 picture of the widened samples, and an Inf or NaN field is what a non-finite float32 sample is.
+
+    ``surface``: 2-D tensor of a 4-byte integer dtype, H rows with unit element stride, at least ``width`` dwords a row; its row
+    stride is the pitch, in dwords.  ``width``: the picture's width in pixels.  A crop starts anywhere: surface[y0:, x0:]."""
+
+    _fmt = R11G11B10F
+
+    def __init__(self, surface, width: int):
+        self._surface(surface, width, self._fmt)
+
+
+class Rgb9e5(R11g11b10f):
+    """An RGB9E5 picture in device memory — one dword a pixel of three 9-bit mantissas (R in bits 0 ... 8, G in 9 ... 17, B in
+    18 ... 26) and their shared 5-bit exponent (DXGI R9G9B9E5_SHAREDEXP, Vulkan E5B9G9R9_UFLOAT_PACK32, GL RGB9_E5): HDR textures,
+    light maps and environment maps — accepted wherever an R11g11b10f object is.  Every dword is a finite picture.
+
+    ``surface``, ``width``: as R11g11b10f's."""
+
+    _fmt = RGB9E5
+
+
 class PlanarYuv16(PlanarYuv):
     """A planar YCbCr picture of 16-bit words in device memory — I010, I210, I410, I012 ... I416: PlanarYuv's three planes as
     tensors of a 2-byte integer dtype, ``depth`` 10, 12 or 16 significant bits LSB-aligned (bits above the depth are ignored) —
@@ -528,7 +556,7 @@ class PlanarYuv16(PlanarYuv):
 def sample_fmt_of(t) -> int:
     """The sample format of a tensor's pixels, by DTYPE (two bytes may be uint16, int16 bits, float16 or bfloat16):
     float16 -> FLOAT16, bfloat16 -> BFLOAT16, float32 -> 2, any other 2-byte type -> 1, any 1-byte type -> 0.
-    An Nv12, P016, PlanarYuv, PlanarYuv16, PackedYuv, PackedYuv16, Rgb10, Y410, Ayuv or Y416 object: its own format."""
+    An Nv12, P016, PlanarYuv, PlanarYuv16, PackedYuv, PackedYuv16, Rgb10, Y410, Ayuv, Y416, R11g11b10f or Rgb9e5 object: its own format."""
     if isinstance(t, Nv12):
         return t.sample_fmt
     name = str(t.dtype).rpartition(".")[2]

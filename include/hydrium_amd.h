@@ -647,7 +647,8 @@ enum {
  *
  * Accepted wherever Y210 is, and beside every other family in one hydamd_encode_mixed_formats launch group.  There is no chroma
  * filter, so hydamd_encode_image_multi takes all six; the host-pointer entry points refuse all six with "Invalid Sample Format".
- * Out of scope: R11G11B10F; v210; PQ / HLG / BT.2020; an alpha in bits 30..31; host-pointer input.  (The 8-, 12- and 16-bit
+ * Out of scope: v210; PQ / HLG / BT.2020; an alpha in bits 30..31; host-pointer input.  (R11G11B10F, the float render target of
+ * the same size, is the section after the next.)  (The 8-, 12- and 16-bit
  * siblings of Y410 — AYUV, Y412, Y416 — are the next section.)
  */
 enum {
@@ -671,7 +672,7 @@ enum {
  *                                                                                (words U, Y, V, A), MSB-aligned; bits 48..63 ignored
  *   HYDAMD_Y416_*   524488..524491  = 524288 + matrix + 4 * 2 + 64 * 3 (16 bits) the same qword, 16 significant bits
  * Twelve numbers; depth 1 (524360..524363) names nothing — the 10-bit surface is Y410 at 131144 — and so does every other number
- * from 524288 up.
+ * from 524288 up to 8388607.
  *
  * How such a picture is named — A SAMPLE IS THE GROUP, exactly as Y410's sample is the dword:
  *   src[0] == src[1] == src[2]   the first pixel, on a boundary of the pixel's size: 4 bytes for AYUV, 8 bytes for Y412 / Y416
@@ -710,11 +711,50 @@ enum {
 };
 
 /*
+ * THREE UNSIGNED FLOATS IN ONE DWORD, DEVICE pixels: R11G11B10F and RGB9E5 — the float render targets that pack a pixel into 32 bits.
+ * R11G11B10F (DXGI R11G11B10_FLOAT, Vulkan B10G11R11_UFLOAT_PACK32, GL R11F_G11F_B10F) is the usual HDR scene and post-processing
+ * buffer of real-time renderers and what game and screen capture hands over for HDR content; RGB9E5 (DXGI R9G9B9E5_SHAREDEXP, Vulkan
+ * E5B9G9R9_UFLOAT_PACK32, GL RGB9_E5) holds HDR textures, light maps and environment maps.  Read by the transform kernel as they are,
+ * without an unpacked float32 copy of three times the bytes.
+ *   HYDAMD_R11G11B10F   8388608   R in bits 0..10, G in 11..21, B in 22..31; a field has no sign, a 5-bit exponent e (bias 15) above
+ *                                 M = 6, 6, 5 mantissa bits m: e = 1..30 is 2^(e-15) * (1 + m / 2^M), e = 0 is m * 2^(-14-M)
+ *                                 (subnormals and zero), e = 31 is +Inf (m = 0) or NaN
+ *   HYDAMD_RGB9E5       8388609   R's mantissa in bits 0..8, G's in 9..17, B's in 18..26, the shared exponent E in 27..31; a channel is
+ *                                 m * 2^(E-24), no implicit leading one; every dword is a finite picture
+ * Two numbers; every other number from 8388608 up names nothing.
+ *
+ * How such a picture is named — A SAMPLE IS THE DWORD, exactly as RGB10A2's is:
+ *   src[0] == src[1] == src[2]   the first dword, on a 4-byte boundary
+ *   pixel_stride                 1
+ *   row_stride                   the pitch of the surface in dwords; may be negative
+ * Anything else is HYD_API_ERROR "R11G11B10F/RGB9E5 wants pixel_stride 1 and three equal pointers on a 4-byte boundary", nothing
+ * enqueued.  A row is W dwords and nothing outside the W dwords of rows 0 .. H - 1 is ever read.  The library finds an LF group, tile
+ * or shard at pixel (x0, y0) by adding y0 * row_stride + x0 dwords to all three pointers; a caller's own crop may start anywhere.
+ *
+ * Both are storage forms of the FLOAT class, as HYDAMD_FLOAT16 is.  A sample is widened EXACTLY to float32 on load — every value
+ * of both formats is a float32 normal or zero, the smallest 2^-20 and 2^-24 — and from there on the pixel is a float32 pixel: the
+ * file is byte for byte what the reference writes for the HYD_FLOAT32 picture of the widened samples, values above 1.0 included.
+ * An R11G11B10F field that is Inf or NaN is whatever a non-finite HYD_FLOAT32 sample is on the same entry point: the same error on a
+ * context, the same status word of its image in a batch.  The samples are taken as sRGB-coded, or as linear light where the
+ * encoder is set to linear_light, as every float sample is: a renderer's scene-referred buffer wants linear_light = 1.
+ *
+ * Accepted wherever HYDAMD_FLOAT16 is, and beside every other family in one hydamd_encode_mixed_formats launch group.  There is no
+ * chroma filter, so hydamd_encode_image_multi takes both; the host-pointer entry points refuse both with "Invalid Sample Format".
+ * Out of scope: signed or 16-bit-per-channel float packings other than what strides already spell (R16G16B16A16_FLOAT is
+ * HYDAMD_FLOAT16 with pixel_stride 4); an alpha; PQ / HLG / BT.2020; host-pointer input.  (RGB10A2, the unsigned-normalised
+ * render target of the same size, is two sections up.)
+ */
+enum {
+    HYDAMD_R11G11B10F = 8388608,
+    HYDAMD_RGB9E5 = 8388609
+};
+
+/*
  * Enqueue the whole hot path for the LF group stored in `slot` (0 <= slot < max_lf_groups; slots
  * are coded into the frame in the order they are submitted).  src/strides/fmt mean exactly what
  * hyd_send_tile's buffer/row_stride/pixel_stride/sample_fmt mean (strides in samples, src[c]
  * pointing at the LF group's first pixel), except that the pointers are DEVICE pointers and that sample_fmt may also be
- * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_*, HYDAMD_YUY2_*, HYDAMD_Y21x_*, HYDAMD_RGB10A2, HYDAMD_BGR10A2, HYDAMD_Y410_*, HYDAMD_AYUV_*, HYDAMD_Y412_* or HYDAMD_Y416_* formats (whose src and strides are
+ * HYDAMD_FLOAT16, HYDAMD_BFLOAT16 or one of the HYDAMD_NV12_*, HYDAMD_P01x_*, HYDAMD_I4xx_*, HYDAMD_Ixnn_*, HYDAMD_YUY2_*, HYDAMD_Y21x_*, HYDAMD_RGB10A2, HYDAMD_BGR10A2, HYDAMD_Y410_*, HYDAMD_AYUV_*, HYDAMD_Y412_*, HYDAMD_Y416_* formats, HYDAMD_R11G11B10F or HYDAMD_RGB9E5 (whose src and strides are
  * described above).  With an interpolating format (HYDAMD_NV12C_*, HYDAMD_NV12L_*, their P01x and I42x forms) the LF group is a
  * picture of its own: its chroma clamps at its own edges.
  */
